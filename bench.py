@@ -10,7 +10,9 @@ sharded (256 per rank, weak scaling), the fused weight blob is broadcast once fr
 RCCL, and there is no per-step collective (streams are independent).
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and
-`cpu_baseline` objects.  Inputs are resident in HBM before the timed region."""
+`cpu_baseline` objects.  Inputs are resident in HBM before the timed region.  `--steps K` is the
+number of timed steps (one block of K unless `--blocks` asks for more); `--dump-outputs DIR`
+writes what the last timed step returned, for comparing two builds output for output."""
 from __future__ import annotations
 
 import argparse
@@ -341,6 +343,31 @@ def parity_after_timed_region(workload: str, w: dict, kw: dict, sd: dict, eng, B
     return r_out, r_cache, what
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(arrays: dict, out_dir: str, limit: int = DUMP_LIMIT_BYTES, seed: int = 0) -> dict:
+    """--dump-outputs: every array as <out_dir>/<name>.npy in float32.  When they hold more than `limit` bytes in all, every array keeps the
+    same fraction of its elements, flattened: one seeded random index in each of k equal strata of its flat indices (ascending, distinct) -
+    the same elements for the same arguments."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    budget = limit - 4096 * len(arrays)                       # (room for the .npy headers)
+    total = sum(a.nbytes for a in arrays.values())
+    frac = 1.0 if total <= budget else budget / total
+    shapes = {}
+    for i, name in enumerate(sorted(arrays)):
+        a = arrays[name]
+        if frac < 1.0:
+            k = int(a.size * frac)
+            stride = a.size / max(k, 1)
+            idx = ((np.arange(k) + np.random.default_rng([seed, i]).random(k)) * stride).astype(np.int64)
+            a = a.reshape(-1)[np.minimum(idx, a.size - 1)]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        shapes[name] = list(arrays[name].shape)
+    return {"dir": out_dir, "arrays": shapes, "sampled_fraction": None if frac >= 1.0 else frac}
+
+
 # rocprofv3's FETCH_SIZE on gfx950 reports HALF of the bytes read, at every access width the kernels use and for cache-resident as
 # well as HBM-sourced data; WRITE_SIZE is exact, partial lines included (profiles/r5_hbm_counter_calib.txt: known byte counts in the
 # kernels' own access patterns, tools/micro/hbm_counter_calib.hip).  Traffic = 2 x FETCH_SIZE + WRITE_SIZE.
@@ -501,9 +528,9 @@ def main():
                          "(centered STFT, all frames, overlap-add) instead of one streaming hop per stream")
     ap.add_argument("--offline-engine", default="auto", choices=["auto", "frame_walk", "time_batched"],
                     help="fe_set_offline_engine: the time-batched (layer-by-layer) engine or the per-hop kernel walking the frames")
-    ap.add_argument("--blocks", type=int, default=25,
+    ap.add_argument("--blocks", type=int, default=1,
                     help="consecutive timed blocks of --steps steps each; value / ms_per_step are the MEDIAN block (min / max / blocks reported), "
-                         "fewer when a block takes long (--block-budget-s)")
+                         "fewer when a block takes long (--block-budget-s).  The default of one block makes --steps the number of timed steps")
     ap.add_argument("--block-budget-s", type=float, default=20.0)
     ap.add_argument("--cpu-dry-run", action="store_true",
                     help="no kernels, no GPU: the launch path alone - bench -> torch.distributed.run -> N ranks (gloo) -> weight-blob broadcast and its "
@@ -524,6 +551,10 @@ def main():
     ap.add_argument("--clock-ramp-ms", type=float, default=250.0,
                     help="untimed launches of the same step BEFORE the counted warm-up, until this much GPU time has passed "
                          "(brings the shader clock and the caches to steady state; reported as clock_ramp_steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed blocks, write what the last timed step returned (rank 0's streams) as DIR/<name>.npy in float32: "
+                         "streaming: wav_out [B, T*H] and the caches in the reference's order (cache_00, ...); offline: wav_out and spec_hat.  At most "
+                         f"{DUMP_LIMIT_BYTES >> 20} MB in all (larger outputs: the same seeded sample of elements of every array)")
     args = ap.parse_args()
 
     launched = "RANK" in os.environ and "WORLD_SIZE" in os.environ      # started by torch.distributed.run
@@ -784,6 +815,16 @@ def main():
         per_rank_ms = [dt / args.steps * 1e3]
     assert torch.isfinite(out).all()
 
+    # ---- what the last timed step returned, written before the parity launch below overwrites it
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        if offline:
+            arrs = {"wav_out": out, "spec_hat": spec_hat}
+        else:
+            arrs = {"wav_out": out}
+            arrs.update({f"cache_{i:02d}": c for i, c in enumerate(eng.split_state(state, B))})
+        dumped = dump_outputs({k: v.cpu().numpy() for k, v in arrs.items()}, args.dump_outputs)
+
     # ---- parity of exactly what was timed, outside the timed blocks: one more launch from the state the run left, against the oracle
     parity = None
     if rank == 0 and not offline and T == 1 and not args.no_parity:
@@ -831,6 +872,7 @@ def main():
                                         "widest_block_max_over_min": max(b_[0] / max(b_[4], 1e-12) for b_ in blocks)},
             "min_ms_per_step": min(b_[0] for b_ in blocks) / args.steps * 1e3, "max_ms_per_step": max(b_[0] for b_ in blocks) / args.steps * 1e3,
             "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "timed_steps": len(blocks) * args.steps, "dump_outputs": dumped,
             "dtype": "f32", "data": "synthetic",
             "config": {"workload": (f"{w['desc']} (N={w['N']}, H={w['H']}), offline Model.forward (centered STFT, all frames, overlap-add) over {B} utterances of "
                                     f"{args.offline_seconds:g} s per GPU and step = {T} frames each, engine {args.offline_engine}") if offline else

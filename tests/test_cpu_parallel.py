@@ -119,3 +119,25 @@ def test_bench_config3_command_line_dry_run_on_eight_gloo_ranks():
     assert d["launch_mode"] == "hip_graph" and "eager_ms_per_step" in d
     sp = d["rank_spread_ms_per_step"]
     assert 0.0 <= sp["min"] <= sp["max"] and sp["widest_block_max_over_min"] >= 1.0
+
+
+def test_bench_dump_outputs_writes_float32_within_the_limit(tmp_path):
+    """`bench.py --dump-outputs DIR`: one float32 .npy per returned array; over the size limit, the same seeded sample of every array's
+    elements on every call, and the files stay within the limit."""
+    import bench
+    rng = np.random.default_rng(0)
+    arrs = {"wav_out": rng.standard_normal((8, 256)), "cache_00": rng.standard_normal((3, 100)).astype(np.float32)}
+    full = bench.dump_outputs(arrs, str(tmp_path / "full"))
+    assert full["sampled_fraction"] is None and full["arrays"] == {"wav_out": [8, 256], "cache_00": [3, 100]}
+    for k, v in arrs.items():
+        got = np.load(tmp_path / "full" / f"{k}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, v.astype(np.float32))
+    limit = 4096 * len(arrs) + 4000
+    s1 = bench.dump_outputs(arrs, str(tmp_path / "s1"), limit=limit)
+    s2 = bench.dump_outputs(arrs, str(tmp_path / "s2"), limit=limit)
+    assert 0.0 < s1["sampled_fraction"] < 1.0 and s1 == dict(s2, dir=s1["dir"])
+    assert sum(os.path.getsize(p) for p in (tmp_path / "s1").iterdir()) <= limit
+    for k, v in arrs.items():
+        a, b = np.load(tmp_path / "s1" / f"{k}.npy"), np.load(tmp_path / "s2" / f"{k}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, b) and 0 < a.size < v.size
+        assert np.isin(a, v.astype(np.float32).reshape(-1)).all()

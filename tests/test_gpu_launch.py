@@ -10,6 +10,7 @@ import subprocess
 import sys
 import warnings
 
+import numpy as np
 import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -120,3 +121,23 @@ def test_host_contention_probe_is_labelled_as_such():
     assert line["contention_probe"] is True and line["n_gpus_really_used"] == 1 and line["roofline"] is None
     assert "NOT a scaling number" in line["metric"] and line["collective_backend"] == "gloo"
     assert len(line["per_rank_ms_per_step"]) == 2 and line["host_enqueue_us_per_step"] > 0.0
+
+
+def test_bench_dumps_the_last_timed_step_of_exactly_warmup_plus_steps_launches(tmp_path):
+    """`--dump-outputs DIR` writes what the last timed step returned.  `--steps` is the number of timed steps: W warm-up steps and K timed
+    steps from a zero state walk the same input hops whatever the split, so 3 + 7 and 5 + 5 must leave the same outputs, bit for bit, and
+    a second run with the same arguments must write the same files."""
+    def run(steps, warmup, d):
+        return _run([sys.executable, "bench.py", "--steps", str(steps), "--warmup", str(warmup), "--streams", "32", "--no-cpu-baseline",
+                     "--no-parity", "--dump-outputs", str(tmp_path / d)])
+    a, b, c = run(7, 3, "a"), run(7, 3, "b"), run(5, 5, "c")
+    assert a["steps"] == a["timed_steps"] == 7 and a["blocks"] == 1 and c["timed_steps"] == 5
+    names = sorted(a["dump_outputs"]["arrays"])
+    assert "wav_out" in names and "cache_00" in names and a["dump_outputs"]["sampled_fraction"] is None
+    assert a["dump_outputs"]["arrays"]["wav_out"] == [32, 256]
+    for n in names:
+        x = np.load(tmp_path / "a" / f"{n}.npy")
+        assert x.dtype == np.float32 and list(x.shape) == a["dump_outputs"]["arrays"][n] and np.isfinite(x).all()
+        assert np.array_equal(x, np.load(tmp_path / "b" / f"{n}.npy")), n
+        assert np.array_equal(x, np.load(tmp_path / "c" / f"{n}.npy")), n
+    assert np.abs(np.load(tmp_path / "a" / "wav_out.npy")).max() > 0.0
