@@ -656,9 +656,12 @@ __device__ __forceinline__ float row16_allreduce(float x, OP op) {
 
 // ln variant: one norm site.  buf holds the [ROWS x COLS] pre-norm values of the frame (leading dimension LD); the statistics are
 // over ALL of them (nn.GroupNorm(1, C) on [C, F] / the reference's LayerNorm over (F, C)): per-thread partial sums, DPP / row-swap
-// wave sums, four partials through LDS, one barrier.  FC = false: buf <- act(xhat * g[c] + b[c]).  FC = true (the blocks'
-// LayerNorm AS WRITTEN in models/fastenhancer/ln/model.py:31-34 - `diff.addcmul(inv_std * weight, bias)`, i.e. the centred value
-// plus inv_std * weight * bias): xres[r][c] += (v - mean) + inv_std * g[c] * b[c] (+ pe[r][c]).  The caller barriers afterwards.
+// wave sums, four partials through LDS.  Two passes, two barriers: the mean first, then the sum of (v - mean)^2 over the values
+// still in registers.  (A one-pass E[x^2] - mean^2 cancels as (|mean| / std)^2: at |mean| / std = 10 / 30 / 100 at the norm inputs
+// the waveform was 3.8e-5 / 1.8e-4 / 1.7e-3 off the fp64 oracle - tests/test_gpu_conditioning.py.)  The sums use separate slots,
+// red[0..3] and red[4..7], so the second pass's stores cannot race the first pass's loads.  FC = false: buf <- act(xhat * g[c] + b[c]).
+// FC = true (the blocks' LayerNorm AS WRITTEN in models/fastenhancer/ln/model.py:31-34 - `diff.addcmul(inv_std * weight, bias)`, i.e. the centred
+// value plus inv_std * weight * bias): xres[r][c] += (v - mean) + inv_std * g[c] * b[c] (+ pe[r][c]).  The caller barriers afterwards.
 template <int ROWS, int COLS, int LD, bool ACT, bool FC>
 __device__ __forceinline__ void ln_pass(float* buf, float* red, const float* g, const float* bt, float eps, float* xres = nullptr, int ldx = 0,
                                         const float* pe = nullptr) {
@@ -670,16 +673,22 @@ __device__ __forceinline__ void ln_pass(float* buf, float* red, const float* g, 
         const int e = tid + kThreads * i, ec = e < N ? e : N - 1, r = ec / COLS, c = ec - r * COLS;
         v[i] = buf[r * LD + c];
         gc[i] = g[c]; bc[i] = bt[c];          // (L2 loads: in flight under the reduction and its barrier)
-        const float m = e < N ? v[i] : 0.0f;
-        s += m; q = fmaf(m, m, q);
+        s += e < N ? v[i] : 0.0f;
     }
     auto add = [](float x, float y) { return x + y; };
     s = rows_allreduce(row16_allreduce(s, add), add);
-    q = rows_allreduce(row16_allreduce(q, add), add);
-    if ((tid & 63) == 0) { red[tid >> 6] = s; red[4 + (tid >> 6)] = q; }
+    if ((tid & 63) == 0) red[tid >> 6] = s;
     __syncthreads();
     const float mean = (red[0] + red[1] + red[2] + red[3]) * (1.0f / N);
-    const float var = fmaxf((red[4] + red[5] + red[6] + red[7]) * (1.0f / N) - mean * mean, 0.0f);
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+        const float d = tid + kThreads * i < N ? v[i] - mean : 0.0f;
+        q = fmaf(d, d, q);
+    }
+    q = rows_allreduce(row16_allreduce(q, add), add);
+    if ((tid & 63) == 0) red[4 + (tid >> 6)] = q;
+    __syncthreads();
+    const float var = (red[4] + red[5] + red[6] + red[7]) * (1.0f / N);
     const float inv = __builtin_amdgcn_rsqf(var + eps);
     // (threads past the end of the last round redo element N - 1 and store to a dummy slot: no partially executed region)
 #pragma unroll

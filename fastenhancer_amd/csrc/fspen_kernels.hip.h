@@ -711,11 +711,15 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(P
             __syncthreads();
             if (blk == 0) FS_CLK(9);
             // ---- intra_fc + LayerNorm([F, C]) + residual
-            float yv[2] = {fc_b, fc_b};
+            // (the bias is added after the dot product, as nn.Linear's reference does: an accumulator that starts at a large bias rounds
+            // each of the 32 products to ulp(bias) - ~6x the error of one rounding when the LayerNorm input carries a common offset,
+            // tests/test_gpu_conditioning.py)
+            float yv[2] = {0.0f, 0.0f};
 #pragma unroll
             for (int k = 0; k < 32; ++k)
 #pragma unroll
                 for (int q = 0; q < 2; ++q) yv[q] = fmaf(fc_w[k], hseq[((tid >> 4) + 16 * q) * 32 + k], yv[q]);
+            yv[0] += fc_b; yv[1] += fc_b;
             __builtin_amdgcn_sched_barrier(0);
             // inter GRUs: thread (group g = tid / 16 < 8, hidden unit c) keeps the unit's three gate rows of its group's GRU (96 weights) in
             // registers - fetched here, in flight across the LayerNorm - and walks the group's 4 sub-band rows (threads 128.. idle)

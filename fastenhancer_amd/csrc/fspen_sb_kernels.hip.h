@@ -358,7 +358,7 @@ __global__ void __launch_bounds__(kFsbThreads) __attribute__((amdgpu_waves_per_e
         {
             f32x4 y[4];
 #pragma unroll
-            for (int fl = 0; fl < 4; ++fl) y[fl] = fb;
+            for (int fl = 0; fl < 4; ++fl) y[fl] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
             for (int ks = 0; ks < 8; ++ks)
 #pragma unroll
@@ -366,6 +366,10 @@ __global__ void __launch_bounds__(kFsbThreads) __attribute__((amdgpu_waves_per_e
                     const float hb = HS[(((ks >> 2) * 32 + 4 * wave + fl) * 16 + 4 * (ks & 3) + lg) * 16 + li];
                     y[fl] = FE_MFMA(fw[ks], hb, y[fl]);
                 }
+            // (the bias after the products, as in fspen_kernels.hip.h's intra_fc: an accumulator that starts at a large bias rounds every
+            // partial sum to ulp(bias))
+#pragma unroll
+            for (int fl = 0; fl < 4; ++fl) y[fl] += fb;
             float s0 = 0.0f;
 #pragma unroll
             for (int fl = 0; fl < 4; ++fl) s0 += (y[fl][0] + y[fl][1]) + (y[fl][2] + y[fl][3]);

@@ -280,6 +280,17 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((
             for (int i = 0; i < cnt; ++i) { const float d = v[i] - mean; q_ = fmaf(d, d, q_); }
             rstd = 1.0f / sqrtf(block_sum(q_) * inv_n + 1.0e-5f);
         };
+        // the same for values laid out v[q] = value tid + q * kThreads of n: slots at or past n (padding) stay out of both sums.  (Counting
+        // them as zeros and subtracting their (0 - mean)^2 afterwards cancels when |mean| >> std.)  The shipped DSConv shapes fill every
+        // slot (NOUT a multiple of kThreads), where this is ln_stats bit for bit: no shipped shape, and so no test, runs a masked slot.
+        auto ln_stats_n = [&](const float* v, int cnt, int n, float inv_n, float& mean, float& rstd) {
+            float s_ = 0.0f;
+            for (int i = 0; i < cnt; ++i) s_ += tid + i * kThreads < n ? v[i] : 0.0f;
+            mean = block_sum(s_) * inv_n;
+            float q_ = 0.0f;
+            for (int i = 0; i < cnt; ++i) { const float d = tid + i * kThreads < n ? v[i] - mean : 0.0f; q_ = fmaf(d, d, q_); }
+            rstd = 1.0f / sqrtf(block_sum(q_) * inv_n + 1.0e-5f);
+        };
 
         // a conv layer's weights (a contiguous block of the packed buffer) -> LDS in one coalesced burst: the layers then read them
         // with LDS latency instead of an L2 round trip per tap (all threads call; ends with a barrier)
@@ -449,12 +460,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((
                 v[q] = acc;
             }
             float mean, rstd;
-            ln_stats(v, PER, 1.0f / (float)NOUT, mean, rstd);          // (threads past NOUT contribute zeros: corrected below)
-            constexpr int PADN = PER * kThreads - NOUT;                  // zero contributions: mean is exact, the variance needs - PADN * mean^2
-            if constexpr (PADN > 0) {
-                const float var = 1.0f / (rstd * rstd) - 1.0e-5f - (float)PADN / (float)NOUT * mean * mean;
-                rstd = 1.0f / sqrtf(var + 1.0e-5f);
-            }
+            ln_stats_n(v, PER, NOUT, 1.0f / (float)NOUT, mean, rstd);   // (the slots of threads past NOUT are left out)
             if (cache_io) cwait(site);
 #pragma unroll
             for (int q = 0; q < PER; ++q) {

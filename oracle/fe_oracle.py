@@ -284,6 +284,18 @@ def group_norm1(x: Array, g: Array, b: Array, eps: float = 1e-5) -> Array:
     return d / np.sqrt(v + x.dtype.type(eps)) * g[None, :, None] + b[None, :, None]
 
 
+def prenorm_tap(taps: Optional[dict], site: str, x: Array, axes) -> None:
+    """Optional tap of a norm site's input statistics (tests/conditioning.py): per sample |mean| / std, std and mean over `axes`,
+    computed in float64 from the values the norm is about to see.  Writes to `taps` only - the forward pass is untouched."""
+    if taps is None:
+        return
+    x64 = np.asarray(x, np.float64)
+    m, s = x64.mean(axis=axes), x64.std(axis=axes)
+    taps["prenorm." + site] = np.abs(m) / np.maximum(s, 1e-300)
+    taps["prenorm_std." + site] = s
+    taps["prenorm_mean." + site] = m
+
+
 def layer_norm_fc(x: Array, g: Array, b: Array, eps: float) -> Array:
     """LayerNorm of models/fastenhancer/ln/model.py:16-37 on x [..., F, C], statistics over (F, C) - AS WRITTEN there:
     `w = inv_std.mul(self.weight); x = diff.addcmul(w, self.bias)`, and torch.addcmul(input, t1, t2) = input + t1 * t2, so the
@@ -763,7 +775,10 @@ class FEOracle:
         B, F0, T, _ = spec.shape
         C2, F2 = c.rf_channels, c.rf_freq
         tap = (lambda k, v: taps.__setitem__(k, v.copy())) if taps is not None else (lambda k, v: None)
-        gn = lambda x, key: group_norm1(x, w[key + ".weight"], w[key + ".bias"])
+        def gn(x, key):
+            prenorm_tap(taps, key, x, (1, 2))
+            return group_norm1(x, w[key + ".weight"], w[key + ".bias"])
+
         bias = lambda key: w[key + ".bias"] if (key + ".bias") in w else None
         cv = lambda x, key: conv1d(x, w[key + ".weight"], bias(key), (w[key + ".weight"].shape[-1] - 1) // 2)
         x = spec.transpose(0, 2, 3, 1).reshape(B * T, 2, F0)
@@ -790,11 +805,13 @@ class FEOracle:
                 ys[t] = h
             h_out.append(h[None].copy())
             y = (ys @ w[p + "rnn_fc.weight"].T).reshape(T, B, F2, C2)
+            prenorm_tap(taps, p + "rnn_post_norm", y, (2, 3))
             x = layer_norm_fc(y, w[p + "rnn_post_norm.weight"], w[p + "rnn_post_norm.bias"], c.rf_eps) + x
             if (p + "pe") in w:
                 x = x + w[p + "pe"]
             tap(f"rf_block.{k}.rnn", x)
             a = mhsa(x.reshape(T * B, F2, C2), w[p + "attn.qkv.weight"], c.rf_heads) @ w[p + "attn_fc.weight"].T
+            prenorm_tap(taps, p + "attn_post_norm", a.reshape(T, B, F2, C2), (2, 3))
             x = layer_norm_fc(a.reshape(T, B, F2, C2), w[p + "attn_post_norm.weight"], w[p + "attn_post_norm.bias"], c.rf_eps) + x
             tap(f"rf_block.{k}", x)
         x = x.transpose(1, 0, 3, 2).reshape(B * T, C2, F2)

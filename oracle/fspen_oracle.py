@@ -10,7 +10,7 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from .fe_oracle import sigmoid, stft_windows
+from .fe_oracle import prenorm_tap, sigmoid, stft_windows
 
 Array = np.ndarray
 
@@ -260,6 +260,7 @@ class FSPENOracle:
             outs.append(o)
         y = np.concatenate(outs, axis=2) @ w[p + "intra_fc.weight"].T + w[p + "intra_fc.bias"]
         assert c.norm == "LayerNorm-FreqChannels"          # nn.LayerNorm([freq, channels]) (:150-151): biased variance, eps 1e-5
+        prenorm_tap(taps, p + "intra_ln", y, (1, 2))
         mean = y.mean(axis=(1, 2), keepdims=True)
         var = ((y - mean) ** 2).mean(axis=(1, 2), keepdims=True)
         y = (y - mean) / np.sqrt(var + self.dtype(1e-5)) * w[p + "intra_ln.weight"] + w[p + "intra_ln.bias"]

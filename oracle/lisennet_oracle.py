@@ -14,7 +14,7 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from .fe_oracle import sigmoid, stft_windows
+from .fe_oracle import prenorm_tap, sigmoid, stft_windows
 
 Array = np.ndarray
 
@@ -185,8 +185,9 @@ def conv2d(x: Array, w: Array, b: Optional[Array], stride_f: int = 1, pad_f: int
     return y if b is None else y + b[None, :, None, None]
 
 
-def custom_ln(x: Array, gamma: Array, beta: Array, eps=1e-5) -> Array:
+def custom_ln(x: Array, gamma: Array, beta: Array, eps=1e-5, taps: Optional[dict] = None, site: str = "") -> Array:
     """CustomLayerNorm with stat_dims (1, 3) (models/lisennet/model.py:27-37): statistics over (channel, freq) per (b, t)"""
+    prenorm_tap(taps, site, x, (1, 3))
     mu = x.mean(axis=(1, 3), keepdims=True)
     std = np.sqrt(x.var(axis=(1, 3), keepdims=True) + x.dtype.type(eps))
     return (x - mu) / std * gamma + beta
@@ -196,8 +197,9 @@ def prelu(x: Array, w: Array) -> Array:
     return np.where(x >= 0, x, x * w[None, :, None, None])
 
 
-def layer_norm_fd(x: Array, w: Array, b: Array, eps=1e-5) -> Array:
+def layer_norm_fd(x: Array, w: Array, b: Array, eps=1e-5, taps: Optional[dict] = None, site: str = "") -> Array:
     """nn.LayerNorm((n_freqs, emb_dim)) on [..., F, D]"""
+    prenorm_tap(taps, site, x, (-2, -1))
     mu = x.mean(axis=(-2, -1), keepdims=True)
     var = ((x - mu) ** 2).mean(axis=(-2, -1), keepdims=True)
     return (x - mu) / np.sqrt(var + x.dtype.type(eps)) * w + b
@@ -224,7 +226,7 @@ class LiSenNetOracle:
         return caches + [np.zeros(s, self.dtype) for s in c.cache_shapes(B)]
 
     # ---- DSConv.forward (:190-208)
-    def dsconv(self, p: str, x: Array, cache: Optional[Array]) -> Tuple[Array, Array]:
+    def dsconv(self, p: str, x: Array, cache: Optional[Array], taps: Optional[dict] = None) -> Tuple[Array, Array]:
         w = self.w
         x = np.concatenate([np.zeros_like(x[:, :, :1]) if cache is None else cache.astype(self.dtype), x], axis=2)
         cache_out = x[:, :, -1:].copy()
@@ -232,7 +234,7 @@ class LiSenNetOracle:
         lo = conv2d(x[..., :lowf], w[p + ".low_conv.weight"], w[p + ".low_conv.bias"], 1, 1)
         hi = conv2d(x[..., lowf:], w[p + ".high_conv.weight"], w[p + ".high_conv.bias"], 3, 1)
         y = np.concatenate([lo, hi], axis=3)
-        y = prelu(custom_ln(y, w[p + ".norm.gamma"], w[p + ".norm.beta"]), w[p + ".act.weight"])
+        y = prelu(custom_ln(y, w[p + ".norm.gamma"], w[p + ".norm.beta"], taps=taps, site=p + ".norm"), w[p + ".act.weight"])
         return y, cache_out
 
     # ---- USConv.forward (:218-226) with SPConvTranspose2d (:240-246)
@@ -251,7 +253,7 @@ class LiSenNetOracle:
         B, D, T, F = x.shape
         x = x.transpose(0, 2, 3, 1)                        # [B, T, F, D]
         res = x
-        y = layer_norm_fd(x, w[p + "intra_norm.weight"], w[p + "intra_norm.bias"]).reshape(B * T, F, D)
+        y = layer_norm_fd(x, w[p + "intra_norm.weight"], w[p + "intra_norm.bias"], taps=taps, site=p + "intra_norm").reshape(B * T, F, D)
         Hh = c.hidden // 2
         outs = []
         q = p + "intra_rnn_attn.rnn."
@@ -267,7 +269,7 @@ class LiSenNetOracle:
         if taps is not None:
             taps[tag + ".intra"] = x.copy()
         res = x
-        y = layer_norm_fd(x, w[p + "inter_norm.weight"], w[p + "inter_norm.bias"])
+        y = layer_norm_fd(x, w[p + "inter_norm.weight"], w[p + "inter_norm.bias"], taps=taps, site=p + "inter_norm")
         y = y.transpose(0, 2, 1, 3).reshape(B * F, T, D)
         q = p + "inter_rnn_attn.rnn."
         hh = np.zeros((B * F, c.hidden), self.dtype) if h is None else h.astype(self.dtype).reshape(B * F, c.hidden).copy()
@@ -282,10 +284,10 @@ class LiSenNetOracle:
         return x.transpose(0, 3, 1, 2), hh.reshape(1, B * F, c.hidden)
 
     # ---- ConvolutionalGLU.forward (:120-136)
-    def conv_glu(self, p: str, x: Array, cache: Optional[Array]) -> Tuple[Array, Array]:
+    def conv_glu(self, p: str, x: Array, cache: Optional[Array], taps: Optional[dict] = None) -> Tuple[Array, Array]:
         w = self.w
         res = x
-        y = custom_ln(x, w[p + "norm.gamma"], w[p + "norm.beta"])
+        y = custom_ln(x, w[p + "norm.gamma"], w[p + "norm.beta"], taps=taps, site=p + "norm")
         y = conv2d(y, w[p + "fc1.weight"], w[p + "fc1.bias"])
         hd = y.shape[1] // 2
         xx, v = y[:, :hd], y[:, hd:]
@@ -301,17 +303,17 @@ class LiSenNetOracle:
         cin = [None] * (c.n_caches - 1) if caches is None else list(caches)
         out: List[Array] = []
         x1 = prelu(custom_ln(conv2d(x, w["encoder.conv_1.0.weight"], w["encoder.conv_1.0.bias"]), w["encoder.conv_1.1.gamma"],
-                             w["encoder.conv_1.1.beta"]), w["encoder.conv_1.2.weight"])
-        x2, c0 = self.dsconv("encoder.conv_2", x1, cin[0])
-        x3, c1 = self.dsconv("encoder.conv_3", x2, cin[1])
-        x4, c2 = self.dsconv("encoder.conv_4", x3, cin[2])
+                             w["encoder.conv_1.1.beta"], taps=taps, site="encoder.conv_1.1"), w["encoder.conv_1.2.weight"])
+        x2, c0 = self.dsconv("encoder.conv_2", x1, cin[0], taps)
+        x3, c1 = self.dsconv("encoder.conv_3", x2, cin[1], taps)
+        x4, c2 = self.dsconv("encoder.conv_4", x3, cin[2], taps)
         out += [c0, c1, c2]
         if taps is not None:
             taps["encoder.conv_1"], taps["encoder.conv_2"], taps["encoder.conv_3"], taps["encoder.conv_4"] = x1.copy(), x2.copy(), x3.copy(), x4.copy()
         y = x4
         for b in range(c.n_blocks):
             y, h = self.dual_path(f"blocks.{b}.dp_rnn_attn.", y, cin[3 + 2 * b], taps, f"blocks.{b}")
-            y, cc = self.conv_glu(f"blocks.{b}.conv_glu.", y, cin[4 + 2 * b])
+            y, cc = self.conv_glu(f"blocks.{b}.conv_glu.", y, cin[4 + 2 * b], taps)
             out += [h, cc]
             if taps is not None:
                 taps[f"blocks.{b}"] = y.copy()
@@ -325,7 +327,8 @@ class LiSenNetOracle:
         y = np.concatenate([np.zeros_like(y[:, :, :1]) if cd is None else cd.astype(self.dtype), y], axis=2)
         out.append(y[:, :, -1:].copy())
         y = conv2d(y, w["decoder.mask_conv.0.weight"], w["decoder.mask_conv.0.bias"], 1, 1)
-        y = prelu(custom_ln(y, w["decoder.mask_conv.1.gamma"], w["decoder.mask_conv.1.beta"]), w["decoder.mask_conv.2.weight"])
+        y = prelu(custom_ln(y, w["decoder.mask_conv.1.gamma"], w["decoder.mask_conv.1.beta"], taps=taps, site="decoder.mask_conv.1"),
+                  w["decoder.mask_conv.2.weight"])
         y = conv2d(y, w["decoder.mask_conv.3.weight"], w["decoder.mask_conv.3.bias"])
         slope = w["decoder.lsigmoid.slope"].reshape(1, 1, 1, -1)                       # per frequency
         mask = sigmoid(slope * y).transpose(0, 3, 2, 1)                                 # [B, F, T, 2]

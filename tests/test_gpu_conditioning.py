@@ -1,0 +1,262 @@
+"""GPU tests on ill-conditioned weights and inputs (tests/conditioning.py) against the fp64 oracle.
+
+The rest of the suite runs benign data - fan-in scaled weights, 0.1 noise + 0.3 sine - where a kernel can lose digits without it
+showing.  Here every norm site sees |mean| / std of 10, 30 and 100, the GRUs saturate, the attention logits reach ~60, and the inputs
+include DC, clipped full-scale noise, impulses, sub-clamp levels and mixed batches.  fastenhancer.ln's blocks' attn_post_norm is not
+offset (conditioning.fe_ln_norm_offset); it runs the same ln_pass<..., FC = true> as the offset rnn_post_norm.
+
+Bound: max(TIGHT_REL[family], 5 * e32), e32 = the fp32 oracle's error against the fp64 oracle on the same case (the fp32 oracle centres
+before squaring: what careful fp32 arithmetic delivers there; LiSenNet: conditioning.LiSenNetSplitOracle), on the whole batch (_assert_close, with the north_star bound), and on every
+stream alone with that stream's own e32 - an error confined to one stream enters the batch's relative rms at ~1 / sqrt(B) of its size.
+
+What a cancelling norm looks like here (fastenhancer.ln's one-pass E[x^2] - mean^2, before the fix; per-hop waveform, relative rms):
+3.8e-5 at |mean| / std = 10, 1.8e-4 at 30, 1.7e-3 at 100 - it grows as the ratio squared.  Rounding of the fp32 values themselves grows
+linearly (e32: 1e-6, 4e-6, 2e-5 for FSPEN)."""
+import importlib
+
+import numpy as np
+import pytest
+import torch
+
+import conditioning as C
+from common import FSPEN_KWARGS, LISENNET_KWARGS, MODEL_KWARGS, MODEL_MODULE, rms
+from oracle.weightgen import make_input
+from test_gpu_parity import REL_TOL, TIGHT_REL, _assert_close, _dev
+
+pytestmark = pytest.mark.gpu
+
+
+def _hip(family, sd, cls="ONNXModel"):
+    if family in ("fspen", "lisennet"):
+        kw = (FSPEN_KWARGS if family == "fspen" else LISENNET_KWARGS)[0]
+        mod = importlib.import_module(f"fastenhancer_amd.models.{family}.model")
+    else:
+        kw = MODEL_KWARGS[family][0]
+        mod = importlib.import_module(f"fastenhancer_amd.models.{MODEL_MODULE[family]}.model")
+    m = getattr(mod, cls)(**kw).to(_dev()).eval()
+    m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
+    return m
+
+
+def _rel(a, b):
+    return rms(np.asarray(a, np.float64) - b) / max(rms(b), 1e-3)
+
+
+def _check(got, ref64, ref32, what, fam, floor=None):
+    """max(TIGHT_REL[fam], 5 e32) on the whole batch (_assert_close) and on every stream alone, with that stream's own e32; arrays are
+    stream-major [B, ...]"""
+    got, ref64 = np.asarray(got, np.float64), np.asarray(ref64, np.float64)
+    assert np.isfinite(got).all(), f"{what}: non-finite output"
+    floor = TIGHT_REL[fam] if floor is None else floor
+    _assert_close(got, ref64, what, tight=max(floor, 5.0 * _rel(ref32, ref64)))
+    for b in range(got.shape[0]):
+        e, e32 = _rel(got[b], ref64[b]), _rel(ref32[b], ref64[b])
+        assert e <= max(floor, 5.0 * e32), f"{what}: stream {b} relative rms err {e:.3e} > max({floor:.0e}, 5 x e32 = {5.0 * e32:.1e})"
+
+
+def _run_engine(eng, x, hop, T):
+    xd = torch.from_numpy(x).to(_dev())
+    st = eng.new_state(x.shape[0])
+    outs = [eng.step(xd[:, t * hop:(t + T) * hop].contiguous(), st, T=T).cpu().numpy() for t in range(0, x.shape[1] // hop, T)]
+    return np.concatenate(outs, 1), [c.cpu().numpy() for c in eng.split_state(st, x.shape[0])]
+
+
+def _check_stream(eng, x, hop, T, orc64, orc32, what, fam, floor=None, scale=1.0):
+    """waveform (times `scale`: sub-clamp inputs give outputs far below the 1e-3 floor of the relative error) and every cache"""
+    got, caches = _run_engine(eng, x, hop, T)
+    r64, c64 = C.run_oracle(orc64, x, hop)
+    r32, c32 = C.run_oracle(orc32, x, hop)
+    _check(got * scale, r64 * scale, r32 * scale, f"{what} wav", fam, floor)
+    B = x.shape[0]
+    for i, (a, b, c) in enumerate(zip(caches, c64, c32)):
+        _check(a.reshape(B, -1), np.asarray(b).reshape(B, -1), np.asarray(c).reshape(B, -1), f"{what} cache {i}", fam, floor)
+
+
+def _check_spectra(eng, x, hop, orc64, orc32, what, fam):
+    """the per-hop step's mask and enhanced spectrum (fe_debug_step stage taps) against the oracles' taps, hop by hop"""
+    xd = torch.from_numpy(x).to(_dev())
+    st = eng.new_state(x.shape[0])
+    c64, c32 = orc64.initialize_cache(x.shape[0]), orc32.initialize_cache(x.shape[0])
+    got, r64, r32 = {"mask": [], "spec_out": []}, {"mask": [], "spec_out": []}, {"mask": [], "spec_out": []}
+    for t in range(x.shape[1] // hop):
+        t64, t32 = {}, {}
+        _, *c64 = orc64.step(x[:, t * hop:(t + 1) * hop], *c64, taps=t64)
+        _, *c32 = orc32.step(x[:, t * hop:(t + 1) * hop], *c32, taps=t32)
+        _, dumps = eng.debug_step(xd[:, t * hop:(t + 1) * hop], st)
+        for k in got:
+            got[k].append(dumps[k].cpu().numpy())
+            r64[k].append(t64[k][:, :, 0, :])
+            r32[k].append(t32[k][:, :, 0, :])
+    for k in got:
+        _check(np.stack(got[k], 1), np.stack(r64[k], 1), np.stack(r32[k], 1), f"{what} {k}", fam)
+
+
+# Known residuals (strict xfail: they must fail until fixed).  The matrix-core GEMMs start their accumulators at the bias (fe_kernels.hip.h
+# mfma tiles; FSPEN's inter_fc / decoder layers): under a bias of 100 std every partial sum rounds to ulp(bias), one stream's error then
+# sits 1.1-1.2x above max(TIGHT_REL, 5 e32) - fe_ln_b cache 2 stream 0 3.0e-5 vs 2.8e-5, fspen cache 1 stream 2 6.3e-5 vs 5.2e-5, fspen
+# stream-batched with saturated GRUs cache 13 stream 1 1.7e-5 vs 1.4e-5.  FSPEN's intra_fc no longer does it (fspen_kernels.hip.h); the
+# shared FastEnhancer GEMMs are left as they are here, as moving their bias changes the bits of every shape.
+_BIAS_FIRST = "bias-first GEMM accumulation: one stream 1.1-1.2x above max(TIGHT_REL, 5 e32) (see the comment above)"
+
+
+def _known(*args):
+    return pytest.param(*args, marks=pytest.mark.xfail(strict=True, reason=_BIAS_FIRST))
+
+
+# ---------------------------------------------------------------- norm sites at |mean| / std = 10, 30, 100
+@pytest.mark.parametrize("ratio", [10, 30, _known(100)])
+def test_fe_ln_norm_offset(ratio):
+    """fastenhancer.ln: all 16 GroupNorm / LayerNorm sites of a frame go through ln_pass; 13 of them at |mean| / std >= ratio.
+    Per-hop launches (waveform, caches, mask and spectrum), a chunked launch (T = 4) and the offline Model, each against the fp64 oracle."""
+    name = "fe_ln_b"
+    sd0, sr, hop = C.base_state_dict(name)
+    x = make_input(4, 8 * hop, 4242, sr)
+    sd, _ = C.norm_offset(name, ratio, x)
+    o64, o32 = C.make_oracle(name, sd), C.make_oracle(name, sd, np.float32)
+    m = _hip(name, sd)
+    _check_stream(m.engine, x, hop, 1, o64, o32, f"fe_ln_b ratio {ratio} per-hop", "fastenhancer")
+    _check_stream(m.engine, x, hop, 4, o64, o32, f"fe_ln_b ratio {ratio} chunked", "fastenhancer")
+    _check_spectra(m.engine, x, hop, o64, o32, f"fe_ln_b ratio {ratio} per-hop", "fastenhancer")
+    mo = _hip(name, sd, "Model")
+    xo = x[:, :7 * hop + 37]
+    w64, s64 = o64.offline_forward(xo)
+    w32, s32 = o32.offline_forward(xo)
+    wav, spec = mo(torch.from_numpy(xo).to(_dev()))
+    _check(wav.cpu().numpy(), w64, w32, f"fe_ln_b ratio {ratio} offline wav", "fastenhancer")
+    _check(spec.cpu().numpy(), s64, s32, f"fe_ln_b ratio {ratio} offline spec", "fastenhancer")
+
+
+@pytest.mark.parametrize("ratio,sb", [(10, False), (10, True), (30, False), (30, True), _known(100, False), (100, True)])
+def test_fspen_norm_offset(ratio, sb):
+    """FSPEN's intra LayerNorms at |mean| / std >= ratio, per-stream kernel and the stream-batched middle (forced from one stream)"""
+    sd0, sr, hop = C.base_state_dict("fspen")
+    x = make_input(5, 5 * hop, 4243, sr)
+    sd, _ = C.norm_offset("fspen", ratio, x)
+    m = _hip("fspen", sd)
+    eng = m.engine
+    eng.set_option("fspen_stream_batch_min", 1 if sb else 0)
+    try:
+        _check_stream(eng, x, hop, 1, C.make_oracle("fspen", sd), C.make_oracle("fspen", sd, np.float32), f"fspen ratio {ratio} sb={sb}", "fspen")
+        kern = eng.last_step_kernel()
+    finally:
+        eng.set_option("fspen_stream_batch_min", 1536)
+    assert ("sb" in kern) == sb, kern
+
+
+@pytest.mark.parametrize("sb", [False, True])
+@pytest.mark.parametrize("ratio", C.NORM_RATIOS)
+def test_lisennet_norm_offset(ratio, sb):
+    """LiSenNet's norm sites at |mean| / std >= ratio (conv biases; the residual stream through encoder.conv_4's shift), per-stream and
+    stream-batched.  Reference: the fp64 network behind the fp32 oracle's phase features (conditioning.LiSenNetSplitOracle) - the
+    wrapped phase differences make a plain fp64 comparison ill-posed (fp32 vs fp64: 2e-2 on the unperturbed checkpoint)."""
+    sd0, sr, hop = C.base_state_dict("lisennet")
+    x = make_input(5, 4 * hop, 4244, sr)
+    sd, _ = C.norm_offset("lisennet", ratio, x)
+    m = _hip("lisennet", sd)
+    eng = m.engine
+    eng.set_option("lisennet_stream_batch_min", 1 if sb else 0)
+    try:
+        _check_stream(eng, x, hop, 1, C.reference_oracle("lisennet", sd), C.make_oracle("lisennet", sd, np.float32), f"lisennet ratio {ratio} sb={sb}",
+                      "lisennet")
+        kern = eng.last_step_kernel()
+    finally:
+        eng.set_option("lisennet_stream_batch_min", 513)
+    assert ("lisennet_sb_kernel" in kern) == sb, kern
+
+
+# ---------------------------------------------------------------- saturated GRUs and sharp attention
+def _offline(family, sd, x, what, engine=None):
+    mo = _hip(family, sd, "Model")
+    if engine:
+        mo.engine.set_offline_engine(engine)
+    wav, spec = mo(torch.from_numpy(x).to(_dev()))
+    if engine:
+        mo.engine.set_offline_engine("auto")
+    w64, s64 = C.make_oracle(family, sd).offline_forward(x)
+    w32, s32 = C.make_oracle(family, sd, np.float32).offline_forward(x)
+    fam = "fspen" if family == "fspen" else "fastenhancer"
+    _check(wav.cpu().numpy(), w64, w32, f"{what} offline wav", fam)
+    _check(spec.cpu().numpy(), s64, s32, f"{what} offline spec", fam)
+
+
+# (family, perturbation (conditioning.hard_state_dict), path): every kernel path that runs a GRU or an attention of these models
+HARD_PATHS = ([("fe_b", h, p) for h in ("gru", "attn") for p in ("wg8", "waves4", "chunked", "offline_tb", "companion")]
+              + [("fe_t", "attn", "per_hop"), ("fe_t", "attn", "chunked"),
+                 ("fe_dpt_b", "time_attn", "ring_wrap"),
+                 ("fe_dprnn_b", "gru", "per_hop"), ("fe_dprnn_b", "gru", "chunked"),
+                 ("fe_nc", "gru", "offline"),
+                 ("fspen", "gru", "per_stream"), _known("fspen", "gru", "stream_batched")])
+
+
+@pytest.mark.parametrize("family,hard,path", HARD_PATHS)
+def test_saturated_gru_and_sharp_attention(family, hard, path):
+    """Saturated GRUs (conditioning.GRU_FACTOR: > 10 % of the gate pre-activations beyond +-15, 3 % for dprnn) or attention logits of
+    ~60 (frequency attention of fe_b / fe_t, the dptransformer's time attention through its 31-slot K / V rings: 35 hops), against the
+    fp64 oracle: FastEnhancer_B's 512-thread per-hop kernel, the four-wave kernel, a chunked launch, the time-batched offline engine and
+    600 streams on the low-LDS companion; the other models per hop, chunked, offline (the noncausal BiGRU) and stream-batched (FSPEN)"""
+    sd, sr, hop = C.hard_state_dict(family, hard)
+    what = f"{family} {hard} {path}"
+    fam = "fspen" if family == "fspen" else "fastenhancer"
+    if path in ("offline_tb", "offline"):
+        # (6 frames, as on the streaming paths: over 20 saturated frames fe_b's fp32 oracle itself drifts 1.7e-4 from the fp64 one)
+        _offline(family, sd, make_input(2, 6 * hop + 17, 909, sr), what, "time_batched" if path == "offline_tb" else None)
+        return
+    o64, o32 = C.make_oracle(family, sd), C.make_oracle(family, sd, np.float32)
+    eng = _hip(family, sd).engine
+    if path == "companion":
+        B, hops = 600, 3
+        x = make_input(B, hops * hop, 910, sr)
+        got, caches = _run_engine(eng, x, hop, 1)
+        assert "LOW=" in eng.last_step_kernel(), eng.last_step_kernel()
+        sel = [0, 1, 255, 256, 511, 512, 599]
+        r64, c64 = C.run_oracle(o64, x[sel], hop)
+        r32, c32 = C.run_oracle(o32, x[sel], hop)
+        _check(got[sel], r64, r32, f"{what} wav", fam)
+        for i, (a_, b_, c_) in enumerate(zip(caches[2:], c64[2:], c32[2:])):       # the GRU states ([1, B * F2, C2], stream-major)
+            a_ = a_.reshape(B, -1)[sel]
+            _check(a_, np.asarray(b_).reshape(len(sel), -1), np.asarray(c_).reshape(len(sel), -1), f"{what} cache {2 + i}", fam)
+        return
+    B, hops = {"fe_dpt_b": (2, 35), "fspen": (5, 5)}.get(family, (4, 6))
+    x = make_input(B, hops * hop, 911, sr)
+    if family == "fe_b":
+        eng.set_step_kernel("waves4" if path in ("waves4", "chunked") else "wg8")
+    if family == "fspen":
+        eng.set_option("fspen_stream_batch_min", 1 if path == "stream_batched" else 0)
+    try:
+        _check_stream(eng, x, hop, 3 if path == "chunked" else 1, o64, o32, what, fam)
+        kern = eng.last_step_kernel()
+    finally:
+        if family == "fe_b":
+            eng.set_step_kernel("wg8")
+        if family == "fspen":
+            eng.set_option("fspen_stream_batch_min", 1536)
+    if family == "fspen":
+        assert ("sb" in kern) == (path == "stream_batched"), kern
+
+
+# ---------------------------------------------------------------- inputs (FastEnhancer_B, benign weights)
+def _inputs(sr, hop):
+    n = 6 * hop
+    return {"dc": (C.dc_input(3, n, 51, sr), None),
+            "clipped_noise": (C.clipped_noise_input(3, n, 52), None),
+            "sub_clamp": (C.sub_clamp_input(3, n, 53, sr, C.SUB_CLAMP_LEVEL), None),
+            # isolated impulses and the mixed batch's quiet stream put STFT bins on both sides of the 1e-5 compression clamp, where
+            # max(|X|, 1e-5)^(c - 1) jumps and the reference's own output moves with the FFT's summation order (test_edge_inputs):
+            # north_star bound only
+            "impulses": (C.impulse_input(3, n, 54), REL_TOL),
+            "mixed": (C.mixed_batch_input(6, n, 55, sr), REL_TOL)}
+
+
+@pytest.mark.parametrize("kind", ["dc", "clipped_noise", "sub_clamp", "impulses", "mixed"])
+@pytest.mark.parametrize("kern", ["wg8", "waves4"])
+def test_fe_b_edge_inputs_against_fp64(kind, kern):
+    name = "fe_b"
+    sd, sr, hop = C.base_state_dict(name)
+    x, floor = _inputs(sr, hop)[kind]
+    scale = 1.0 / C.SUB_CLAMP_LEVEL if kind == "sub_clamp" else 1.0
+    m = _hip(name, sd)
+    m.engine.set_step_kernel(kern)
+    try:
+        _check_stream(m.engine, x, hop, 1, C.make_oracle(name, sd), C.make_oracle(name, sd, np.float32), f"fe_b {kind} ({kern})", "fastenhancer", floor, scale)
+    finally:
+        m.engine.set_step_kernel("wg8")
