@@ -17,6 +17,8 @@ FE_ARCH_FSPEN = 2
 FE_ARCH_LISENNET = 3
 FE_OFFLINE_AUTO, FE_OFFLINE_FRAME_WALK, FE_OFFLINE_TIME_BATCHED = 0, 1, 2
 FE_STEP_KERNEL_WAVES4, FE_STEP_KERNEL_WG8, FE_STEP_KERNEL_WG8_PERSIST = 0, 1, 2
+FE_ACT_SILU, FE_ACT_RELU, FE_ACT_LEAKY_RELU, FE_ACT_ELU, FE_ACT_GELU, FE_ACT_GELU_TANH = 0, 1, 2, 3, 4, 5
+FE_MASK_NONE, FE_MASK_SIGMOID, FE_MASK_TANH = 0, 1, 2
 
 
 class fe_config(ctypes.Structure):
@@ -25,7 +27,7 @@ class fe_config(ctypes.Structure):
         ("channels", c_int), ("n_kernels", c_int), ("kernel_size", c_int * FE_MAX_KERNELS),
         ("stride", c_int), ("rf_channels", c_int), ("rf_freq", c_int), ("rf_blocks", c_int),
         ("rf_heads", c_int), ("input_compression", c_float), ("kernel_size_time", c_int), ("channels_frnn", c_int), ("lookbehind", c_int), ("ln", c_int), ("rf_eps", c_float),
-        ("bidirectional", c_int),
+        ("bidirectional", c_int), ("activation", c_int), ("activation_param", c_float), ("mask", c_int), ("resnet", c_int),
     ]
 
 

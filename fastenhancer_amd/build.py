@@ -40,8 +40,8 @@ def _hipcc() -> str:
     return "hipcc"
 
 
-# Shapes beyond the shipped yamls: `python -m fastenhancer_amd.build --add-shape C1,NL,C2,F2,KB,NFFT,HOP[,KT]` appends a line
-# to this (git-ignored, optional) file and rebuilds; fe_api.hip includes it after fe_shapes.def.  FE_LOCAL_DEF overrides the path.
+# Shapes beyond the shipped yamls: `python -m fastenhancer_amd.build --add-shape C1,NL,C2,F2,KB,NFFT,HOP[,KT][,act=..,mask=..]` appends
+# a line to this (git-ignored, optional) file and rebuilds; fe_api.hip includes it after fe_shapes.def.  FE_LOCAL_DEF overrides the path.
 LOCAL_DEF = os.environ.get("FE_LOCAL_DEF") or os.path.join(CSRC, "fe_shapes_local.def")
 # FE_SHAPES_DEF=<file>: a side build (FE_BUILD_TAG) with a SHORT shape list instead of csrc/fe_shapes.def - seconds instead of
 # minutes while a kernel is being worked on (tools/dev_shapes.def: B, T, L, NC); the library then knows those shapes only
@@ -65,11 +65,44 @@ def shapes(fname="fe_shapes.def", macro="X"):
     return out
 
 
+# --add-shape options: the model_kwargs activation / mask a shape is compiled for (Shape::EP = activation + 8 * mask; FE_ACT_* / FE_MASK_*)
+ACT_OPTIONS = ("silu", "relu", "leaky_relu", "elu", "gelu", "gelu_tanh")
+MASK_OPTIONS = ("none", "sigmoid", "tanh")
+
+
+def parse_shape_spec(spec: str):
+    """`C1,NL,...[,act=<name>][,mask=<name>][,resnet=0]` -> (the integers, EP).  Malformed input is a SystemExit with a readable message."""
+    ints, opts = [], {}
+    for tok in spec.replace(" ", "").split(","):
+        if "=" in tok:
+            k, _, val = tok.partition("=")
+            if k not in ("act", "mask", "resnet"):
+                raise SystemExit(f"--add-shape: unknown option {k!r} (options: act=<{'|'.join(ACT_OPTIONS)}>, mask=<{'|'.join(MASK_OPTIONS)}>)")
+            if k in opts:
+                raise SystemExit(f"--add-shape: option {k!r} given twice")
+            opts[k] = val.lower()
+        else:
+            if opts:
+                raise SystemExit("--add-shape: the act= / mask= options come after the shape's numbers")
+            try:
+                ints.append(int(tok))
+            except ValueError:
+                raise SystemExit(f"--add-shape: {tok!r} is not an integer (C1,NL,C2,F2,KB,NFFT,HOP[,KT[,...]][,act=..,mask=..])") from None
+    act, mask = opts.get("act", "silu"), opts.get("mask", "none")
+    if act not in ACT_OPTIONS:
+        raise SystemExit(f"--add-shape: act={act} is not supported (act=<{'|'.join(ACT_OPTIONS)}>)")
+    if mask not in MASK_OPTIONS:
+        raise SystemExit(f"--add-shape: mask={mask} is not supported (mask=<{'|'.join(MASK_OPTIONS)}>)")
+    if opts.get("resnet", "0") not in ("0", "false"):
+        raise SystemExit("--add-shape: resnet=1 is not built into this library (every shipped yaml uses resnet: false)")
+    return ints, ACT_OPTIONS.index(act) + 8 * MASK_OPTIONS.index(mask)
+
+
 def add_shape(spec: str) -> str:
-    """`C1,NL,C2,F2,KB,NFFT,HOP[,KT]` (channels, len(kernel_size)-1, rnnformer channels / freq / num_blocks, n_fft, hop_size,
-    kernel_size_time) -> a line in the local shape list.  The kernel template's constraints are checked here with a
-    readable message (hipcc would report them as failed static_asserts): stride 4 and kernel_size [8, 3, ...] are fixed."""
-    v = [int(x) for x in spec.replace(" ", "").split(",")]
+    """`C1,NL,C2,F2,KB,NFFT,HOP[,KT][,act=..,mask=..]` (channels, len(kernel_size)-1, rnnformer channels / freq / num_blocks, n_fft, hop_size,
+    kernel_size_time; the activation and mask of the model_kwargs) -> a line in the local shape list.  The kernel template's constraints are
+    checked here with a readable message (hipcc would report them as failed static_asserts): stride 4 and kernel_size [8, 3, ...] are fixed."""
+    v, ep = parse_shape_spec(spec)
     if len(v) not in (7, 8, 10, 11, 12, 13):
         raise SystemExit("--add-shape wants C1,NL,C2,F2,KB,NFFT,HOP[,KT[,0,FR[,TA[,LN[,BD]]]]]  (FR = 1: the dprnn variant, TA = 31: the dptransformer variant, "
                          "LN = 1: the ln variant, BD = 1: the noncausal variant)")
@@ -86,12 +119,20 @@ def add_shape(spec: str) -> str:
         errs.append("0 < hop_size <= n_fft")
     if not (1 <= NL <= 7 and 1 <= KB <= 8 and 1 <= KT <= 4 and NL * KT <= 16):
         errs.append("1 <= layers <= 7, 1 <= num_blocks <= 8, 1 <= kernel_size_time <= 4")
+    if ep:
+        LOW, FR, TA, BD = (v + [0] * 13)[8], (v + [0] * 13)[9], (v + [0] * 13)[10], (v + [0] * 13)[12]
+        if LOW or FR or TA or BD:
+            errs.append("act= / mask= are built for the default, time_kernel and ln models (LOW, FR, TA and BD must be 0)")
     if errs:
         raise SystemExit("unsupported shape: " + "; ".join(errs))
+    if ep:      # Shape's trailing template parameter: every positional one spelled out
+        v = v + [1, 0, 0, 0, 0, 0][len(v) - 7:] + [ep]
     args = ",".join(str(x) for x in v)
     if any(a == args or (len(v) == 7 and a == args + ",1") for _, a in shapes()):
         return ""
-    name = "U" + "_".join(str(x) for x in v)
+    name = "U" + "_".join(str(x) for x in v[:13 if ep else len(v)])
+    if ep:
+        name += f"_{ACT_OPTIONS[ep % 8]}_{MASK_OPTIONS[ep // 8]}"
     with open(LOCAL_DEF, "a") as f:
         f.write(f"X({name}, {', '.join(str(x) for x in v)})\n")
     return name

@@ -1,11 +1,43 @@
 """model_kwargs (yaml) -> FEConfig.  Mirrors the constructor signature of
-models/fastenhancer/default/model.py:384-403 and asserts the invariants that the
-HIP kernels specialise on (true for every shipped yaml, SURVEY.md top)."""
+models/fastenhancer/default/model.py:384-419 and asserts the invariants that the
+HIP kernels specialise on (true for every shipped yaml, SURVEY.md top).  The activation
+and the mask are options the kernels are compiled for per shape (Shape::EP)."""
 from __future__ import annotations
 
 import typing as tp
 from dataclasses import dataclass
 from typing import Any, Dict, Optional, Sequence, Tuple
+
+# activation -> (FE_ACT_* of include/fastenhancer_hip.h, the activation_kwargs it takes with their reference defaults); `inplace` is
+# accepted and ignored everywhere.  GELU's approximate = 'tanh' is FE_ACT_GELU_TANH.
+ACTIVATIONS = {"SiLU": (0, {}), "ReLU": (1, {}), "LeakyReLU": (2, {"negative_slope": 0.01}), "ELU": (3, {"alpha": 1.0}),
+               "GELU": (4, {"approximate": "none"})}
+MASKS = {None: 0, "sigmoid": 1, "tanh": 2}
+# FE_ACT_* -> the name `python -m fastenhancer_amd.build --add-shape ...,act=<name>` takes
+ACT_NAMES = ("silu", "relu", "leaky_relu", "elu", "gelu", "gelu_tanh")
+MASK_NAMES = ("none", "sigmoid", "tanh")
+_SUPPORTED_ACT = ("SiLU, ReLU, LeakyReLU(negative_slope), ELU(alpha), GELU(approximate='none' | 'tanh') "
+                  "(activation_kwargs: those constants and `inplace`, which is ignored)")
+
+
+def _activation(activation: str, activation_kwargs: Optional[Dict[str, Any]]) -> Tuple[int, float]:
+    """activation, activation_kwargs -> (FE_ACT_*, the activation's constant: LeakyReLU negative_slope / ELU alpha, else 0)"""
+    if activation not in ACTIVATIONS:
+        raise RuntimeError(f"model_kwargs.activation={activation} is not supported by the HIP path (supported: {_SUPPORTED_ACT}).")
+    code, params = ACTIVATIONS[activation]
+    ak = {k: v for k, v in dict(activation_kwargs or {}).items() if k != "inplace"}
+    extra = sorted(set(ak) - set(params))
+    if extra:
+        raise RuntimeError(f"model_kwargs.activation_kwargs {extra} of {activation} are not supported by the HIP path (supported: {_SUPPORTED_ACT}).")
+    if activation == "GELU":
+        approx = ak.get("approximate", "none")
+        if approx not in ("none", "tanh"):
+            raise RuntimeError(f"model_kwargs.activation_kwargs.approximate={approx!r}: GELU takes 'none' or 'tanh'")
+        return (5 if approx == "tanh" else 4), 0.0
+    if params:
+        (key, default), = params.items()
+        return code, float(ak.get(key, default))
+    return code, 0.0
 
 
 @dataclass(frozen=True)
@@ -52,6 +84,18 @@ class FEConfig:
     # `model: fastenhancer.noncausal` (models/fastenhancer/noncausal/model.py:186-187): the blocks' time GRU is bidirectional and
     # rnn_fc maps 2 C2 -> C2; the reference module has the offline `Model` only (no caches, no streaming step)
     noncausal: bool = False
+    # model_kwargs.activation / activation_kwargs / mask (model.py:397-404, 431): FE_ACT_*, the activation's constant (LeakyReLU
+    # negative_slope, ELU alpha), FE_MASK_*.  0 / 0 = SiLU and mask null, what every shipped yaml uses and the shipped shapes are built for
+    activation: int = 0
+    activation_param: float = 0.0
+    mask: int = 0
+
+    @property
+    def options(self) -> str:
+        """the --add-shape suffix of the kernel this config needs ('' = the shipped SiLU / no-mask build)"""
+        if self.activation == 0 and self.mask == 0:
+            return ""
+        return f"act={ACT_NAMES[self.activation]},mask={MASK_NAMES[self.mask]}"
 
     @property
     def time_kernel(self) -> bool:
@@ -111,10 +155,10 @@ class FEConfig:
         if rk.get("positional_embedding", "train") not in ("train", "fixed"):
             raise RuntimeError(f"rnnformer_kwargs.positional_embedding={rk.get('positional_embedding')} is not supported by "
                                "the HIP path (shipped: train; the kernel always adds rf_block.0.pe).")
-        if mask is not None:
-            raise RuntimeError(f"model_kwargs.mask={mask} is not supported by the HIP path (every shipped yaml uses null).")
-        if activation != "SiLU":
-            raise RuntimeError(f"model_kwargs.activation={activation} is not supported by the HIP path (shipped: SiLU).")
+        if mask not in MASKS:
+            raise RuntimeError(f"model_kwargs.mask={mask} is not supported. "           # models/fastenhancer/default/model.py:397-404
+                               "(supported: null, 'sigmoid', 'tanh')")
+        act, act_param = _activation(activation, activation_kwargs)
         if window != "hann":
             raise RuntimeError(f"model_kwargs.window={window} is not supported by the HIP path (shipped: hann).")
         if resnet:
@@ -132,7 +176,16 @@ class FEConfig:
             n_fft=int(n_fft), hop_size=int(hop_size), win_size=int(win_size),
             input_compression=float(input_compression), weight_norm=bool(weight_norm),
             normalize_final_conv=bool(normalize_final_conv), pre_post_init=pre_post_init,
+            activation=act, activation_param=act_param, mask=MASKS[mask],
         )
+
+
+def _default_options_only(cfg: FEConfig, variant: str) -> FEConfig:
+    """the variants without a golden test of the options keep the shipped activation and mask"""
+    if cfg.activation != 0 or cfg.mask != 0:
+        raise RuntimeError(f"model_kwargs activation / mask other than SiLU / null are not supported by the HIP path for the {variant} "
+                           "variant (built for the default, time_kernel and ln models).")
+    return cfg
 
 
 def time_kernel_config(channels: int = 64, kernel_size_freq: Sequence[int] = (8, 3, 3), kernel_size_time: int = 3, stride: int = 4,
@@ -160,7 +213,7 @@ def time_kernel_config(channels: int = 64, kernel_size_freq: Sequence[int] = (8,
 def noncausal_config(normalize_final_conv: bool = True, **model_kwargs) -> FEConfig:
     """yaml model_kwargs of `model: fastenhancer.noncausal` (configs/fastenhancer_dns/huge_noncausal.yaml:2-30: the default model's keys;
     defaults of models/fastenhancer/noncausal/model.py:349-368 - normalize_final_conv defaults to True there) -> FEConfig with noncausal set."""
-    base = FEConfig.from_model_kwargs(normalize_final_conv=normalize_final_conv, **model_kwargs)
+    base = _default_options_only(FEConfig.from_model_kwargs(normalize_final_conv=normalize_final_conv, **model_kwargs), "noncausal")
     import dataclasses
     return dataclasses.replace(base, noncausal=True)
 
@@ -187,6 +240,7 @@ def dprnn_config(channels: int = 64, kernel_size: Sequence[int] = (8, 3, 3), str
                                       win_size=win_size, window=window, stft_normalized=stft_normalized, mask=mask,
                                       input_compression=input_compression, weight_norm=weight_norm,
                                       normalize_final_conv=normalize_final_conv, pre_post_init=pre_post_init, resnet=False)
+    _default_options_only(base, "dprnn")
     import dataclasses
     return dataclasses.replace(base, channels_frnn=H, positional_embedding=None, final_scale_exp=(final_scale == "exp"))
 
@@ -224,6 +278,7 @@ def dpt_config(channels: int = 64, kernel_size: Sequence[int] = (8, 3, 3), strid
                                       win_size=win_size, window=window, stft_normalized=stft_normalized, mask=mask,
                                       input_compression=input_compression, weight_norm=weight_norm,
                                       normalize_final_conv=normalize_final_conv, pre_post_init=pre_post_init, resnet=False)
+    _default_options_only(base, "dptransformer")
     import dataclasses
     return dataclasses.replace(base, lookbehind=L, final_scale_exp=(final_scale == "exp"))
 

@@ -674,6 +674,7 @@ int pack_weights(fe_handle* h, const std::vector<float>& blob, std::vector<float
         scale(o.post1_b, 4 * C1, c);
         scale(o.post_t_w, szB(C1, 16), 1.0f / c);                                 // transposed conv: true-scale mask
     }
+    if (o.act_p > 0) p.buf[(size_t)o.act_p] = h->cfg.activation_param;            // LeakyReLU negative_slope / ELU alpha (Shape::EPP)
     p.raw(o.window, h->window.size(), h->window.data());
     p.raw(o.window_istft, h->window_istft.size(), h->window_istft.data());
     p.raw(o.twiddle, h->twiddle.size(), h->twiddle.data());
@@ -934,14 +935,28 @@ int fe_create(const fe_config* cfg, fe_handle** out) {
     const int ta = cfg->lookbehind > 0 ? cfg->lookbehind : 0;
     if (ta && ta != 31) return fail(FE_ERR_UNSUPPORTED_CONFIG, "lookbehind=%d (the dptransformer kernels are built for 31, every shipped yaml)", ta);
     if (ta && fr) return fail(FE_ERR_INVALID_ARG, "channels_frnn and lookbehind are exclusive");
+    // constructor options beyond the shipped yamls (models/fastenhancer/default/model.py:384-419): compiled per shape as Shape::EP
+    if (cfg->activation < FE_ACT_SILU || cfg->activation > FE_ACT_GELU_TANH) return fail(FE_ERR_INVALID_ARG, "activation=%d (FE_ACT_*)", cfg->activation);
+    if (cfg->mask < FE_MASK_NONE || cfg->mask > FE_MASK_TANH) return fail(FE_ERR_INVALID_ARG, "mask=%d (FE_MASK_*)", cfg->mask);
+    if (cfg->resnet) return fail(FE_ERR_UNSUPPORTED_CONFIG, "resnet=1 is not built into this library (every shipped yaml uses resnet: false)");
+    const int ep = cfg->activation + 8 * cfg->mask;
+    if (ep && (fr || ta || bd))
+        return fail(FE_ERR_UNSUPPORTED_CONFIG, "activation=%d / mask=%d: the options are built for the default, time_kernel and ln models only (this is the %s variant)",
+                    cfg->activation, cfg->mask, fr ? "dprnn" : (ta ? "dptransformer" : "noncausal"));
+    static const char* const act_names[] = {"silu", "relu", "leaky_relu", "elu", "gelu", "gelu_tanh"};
+    static const char* const mask_names[] = {"none", "sigmoid", "tanh"};
+    char ep_arg[64] = "";
+    if (ep) snprintf(ep_arg, sizeof ep_arg, ",act=%s,mask=%s", act_names[cfg->activation], mask_names[cfg->mask]);
     for (const fe::Impl* im : impls())
         if (im->C1 == cfg->channels && im->NL == cfg->n_kernels - 1 && im->C2 == cfg->rf_channels && im->F2 == cfg->rf_freq &&
-            im->KB == cfg->rf_blocks && im->NFFT == cfg->n_fft && im->HOP == cfg->hop_size && im->KT == kt && im->LOW == 0 && im->FR == fr && im->TA == ta && im->LN == ln && im->BD == bd)
+            im->KB == cfg->rf_blocks && im->NFFT == cfg->n_fft && im->HOP == cfg->hop_size && im->KT == kt && im->LOW == 0 && im->FR == fr && im->TA == ta && im->LN == ln && im->BD == bd &&
+            im->EP == ep)
             impl = im;
     const fe::Impl* impl_many = nullptr;
     for (const fe::Impl* im : impls())
         if (impl && im->LOW >= 1 && im->occ >= 2 && im->C1 == impl->C1 && im->NL == impl->NL && im->C2 == impl->C2 && im->F2 == impl->F2 &&
-            im->KB == impl->KB && im->NFFT == impl->NFFT && im->HOP == impl->HOP && im->KT == impl->KT && im->FR == impl->FR && im->TA == impl->TA && im->LN == impl->LN && !impl->BD)
+            im->KB == impl->KB && im->NFFT == impl->NFFT && im->HOP == impl->HOP && im->KT == impl->KT && im->FR == impl->FR && im->TA == impl->TA && im->LN == impl->LN && !impl->BD &&
+            im->EP == impl->EP)
             impl_many = im;
     // a companion reads its shape's packed buffer: every offset it uses must be the same function of the shape (fe::Pack does not depend on LOW; r4x: the
     // k4 copies sit behind the time-batched engine's and the 512-thread kernel's sections - checked here rather than trusted)
@@ -950,10 +965,12 @@ int fe_create(const fe_config* cfg, fe_handle** out) {
         return fail(FE_ERR_UNSUPPORTED_CONFIG, "build error: the low-LDS companion of this shape was compiled with a different packed-weight layout (fe::Pack must not depend on LOW)");
     if (!impl)
         return fail(FE_ERR_UNSUPPORTED_CONFIG,
-                    "no kernel compiled for channels=%d layers=%d rf_channels=%d rf_freq=%d rf_blocks=%d n_fft=%d hop=%d kernel_size_time=%d%s "
-                    "(build it: python -m fastenhancer_amd.build --add-shape %d,%d,%d,%d,%d,%d,%d,%d%s)",
+                    "no kernel compiled for channels=%d layers=%d rf_channels=%d rf_freq=%d rf_blocks=%d n_fft=%d hop=%d kernel_size_time=%d%s%s%s "
+                    "(build it: python -m fastenhancer_amd.build --add-shape %d,%d,%d,%d,%d,%d,%d,%d%s%s)",
                     cfg->channels, cfg->n_kernels - 1, cfg->rf_channels, cfg->rf_freq, cfg->rf_blocks, cfg->n_fft, cfg->hop_size, kt, fr ? " dprnn" : (ta ? " dptransformer" : (ln ? " ln" : (bd ? " noncausal" : ""))),
-                    cfg->channels, cfg->n_kernels - 1, cfg->rf_channels, cfg->rf_freq, cfg->rf_blocks, cfg->n_fft, cfg->hop_size, kt, fr ? ",0,1" : (ta ? ",0,0,31" : (ln ? ",0,0,0,1" : (bd ? ",0,0,0,0,1" : ""))));
+                    ep_arg[0] ? " " : "", ep_arg[0] ? ep_arg + 1 : "",
+                    cfg->channels, cfg->n_kernels - 1, cfg->rf_channels, cfg->rf_freq, cfg->rf_blocks, cfg->n_fft, cfg->hop_size, kt, fr ? ",0,1" : (ta ? ",0,0,31" : (ln ? ",0,0,0,1" : (bd ? ",0,0,0,0,1" : ""))),
+                    ep_arg);
     if (impl->lds_bytes > 160 * 1024)
         return fail(FE_ERR_UNSUPPORTED_CONFIG, "shape needs %zu bytes of LDS (> 160 KiB per CU)", impl->lds_bytes);
     fe_handle* h = new fe_handle();

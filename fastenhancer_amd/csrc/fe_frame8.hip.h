@@ -84,9 +84,9 @@ struct Wg8 {
 
 // One conv-layout GEMM job of a wave: row tile mt x the NT channel tiles J0 .. J0 + NT - 1, K = 4 KS.
 //   af(ks) -> A fragment element, bf(j, ks) -> B fragment element of ABSOLUTE tile j, bias(j) -> accumulator start.
-// Epilogue: optional SiLU (scaled trunk), store to out[(row0 + m)][col] for col < NCOLS.
+// Epilogue: optional activation (Shape::EPA, scaled trunk; ap: its constant), store to out[(row0 + m)][col] for col < NCOLS.
 template <class S, int NT, int J0, int KS, int NCOLS, int LDO, bool ACT, class AF, class BF, class BI, class SIDE>
-__device__ __forceinline__ void conv8(AF&& af, BF&& bf, BI&& bias, const SIDE& side, float* out, int row0, int mt, int lane) {
+__device__ __forceinline__ void conv8(AF&& af, BF&& bf, BI&& bias, const SIDE& side, float* out, int row0, int mt, int lane, float ap = 0.0f) {
     if constexpr (NT > 0) {
         const int li = lane & 15, lg = lane >> 4;
         f32x4 acc[1][NT];
@@ -102,7 +102,7 @@ __device__ __forceinline__ void conv8(AF&& af, BF&& bf, BI&& bias, const SIDE& s
                 for (int r = 0; r < 4; ++r) {
                     const int m = 16 * mt + 4 * lg + r;
                     float v = acc[0][j][r];
-                    if (ACT) v = silu_scaled_f(v);
+                    if (ACT) v = act_scaled_f<S::EPA>(v, ap);
                     out[(row0 + m) * LDO + col] = v;
                 }
             }
@@ -117,9 +117,10 @@ __device__ __forceinline__ void conv8(AF&& af, BF&& bf, BI&& bias, const SIDE& s
 }
 // the pair split: wh = 0 takes the tiles [0, NA), wh = 1 the tiles [NA, NA + NB)
 template <class S, int NA, int NB, int KS, int NCOLS, int LDO, bool ACT, class AF, class BF, class BI, class SIDE>
-__device__ __forceinline__ void conv8_pair(int wh, AF&& af, BF&& bf, BI&& bias, const SIDE& side, float* out, int row0, int mt, int lane) {
-    if (wh == 0) conv8<S, NA, 0, KS, NCOLS, LDO, ACT>(af, bf, bias, side, out, row0, mt, lane);
-    else conv8<S, NB, NA, KS, NCOLS, LDO, ACT>(af, bf, bias, side, out, row0, mt, lane);
+__device__ __forceinline__ void conv8_pair(int wh, AF&& af, BF&& bf, BI&& bias, const SIDE& side, float* out, int row0, int mt, int lane,
+                                           float ap = 0.0f) {
+    if (wh == 0) conv8<S, NA, 0, KS, NCOLS, LDO, ACT>(af, bf, bias, side, out, row0, mt, lane, ap);
+    else conv8<S, NB, NA, KS, NCOLS, LDO, ACT>(af, bf, bias, side, out, row0, mt, lane, ap);
 }
 
 // DBG: per-stage dumps (fe_debug_step) and the phase cycle probes (fe_profile_step).  PERSIST: more streams than CUs,
@@ -163,6 +164,8 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
     wb.lds = nullptr;
     wb.base = 0;
     wb.k4d = 0;
+    float ap = 0.0f;                                 // the activation's constant (Shape::EPP)
+    if constexpr (S::EPP) ap = wp[o.act_p];
 
     // ---- one-time: the zero halos (compressed spectrum, skip buffers), twiddles, weight unit 0.
     // !PERSIST (one stream per workgroup): everything the front of the frame waits for is requested HERE, in one memory round trip
@@ -357,7 +360,7 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
                     return sc[c * S::LDS_S + 4 * (16 * ws + li + tp) + s];
                 },
                 [&](int j, int ks) { return wb.at(o.enc_pre_w + (j * 4 + ks) * 64); },
-                [&](int j) { return wb.at16x4(o.enc_pre_b + j * 64); }, stage, Ebuf, 1, ws, lane);
+                [&](int j) { return wb.at16x4(o.enc_pre_b + j * 64); }, stage, Ebuf, 1, ws, lane, ap);
 #if FE_WG8_HPRE
             if constexpr (S::KB > 2) hpre_mma(HK2_{});        // (waves 4-7: the lighter half of this 12-MFMA phase)
 #endif
@@ -378,7 +381,7 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
                 conv8_pair<S, W8::NTA, W8::NTB, 3 * S::KS_C, C1, LDC, true>(
                     wh, [&](int ks) { return t0[(ks / S::KS_C) * LDC + 4 * (ks % S::KS_C)]; },
                     [&](int j, int ks) { return wb.at(o.enc_w[l] + (j * (3 * S::KS_C) + ks) * 64); },
-                    [&](int j) { return wb.at16x4(o.enc_b[l] + j * 64); }, stage, out, 1, ws, lane);
+                    [&](int j) { return wb.at16x4(o.enc_b[l] + j * 64); }, stage, out, 1, ws, lane, ap);
             }
             if (l == 0) FE_CLK(42);
             __syncthreads();
@@ -954,7 +957,7 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
                 conv8_pair<S, W8::NTA, W8::NTB, K0 + S::KS_C, C1, LDC, true>(
                     wh, [&](int ks) { return ks < K0 ? xa[4 * ks] : sk[4 * (ks - K0)]; },
                     [&](int j, int ks) { return wb.at(o.dec1_w[l] + (j * (K0 + S::KS_C) + ks) * 64); },
-                    [&](int j) { return wb.at16x4(o.dec1_b[l] + j * 64); }, stage, Wy, 1, ws, lane);
+                    [&](int j) { return wb.at16x4(o.dec1_b[l] + j * 64); }, stage, Wy, 1, ws, lane, ap);
             }
             __syncthreads();
             {
@@ -963,7 +966,7 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
                 conv8_pair<S, W8::NTA, W8::NTB, 3 * S::KS_C, C1, LDC, true>(
                     wh, [&](int ks) { return t0[(ks / S::KS_C) * LDC + 4 * (ks % S::KS_C)]; },
                     [&](int j, int ks) { return wb.at(o.dec3_w[l] + (j * (3 * S::KS_C) + ks) * 64); },
-                    [&](int j) { return wb.at16x4(o.dec3_b[l] + j * 64); }, stage, Wx, 1, ws, lane);
+                    [&](int j) { return wb.at16x4(o.dec3_b[l] + j * 64); }, stage, Wx, 1, ws, lane, ap);
             }
             __syncthreads();
             dbg_dump<S, NTH>(a, b, 5 + S::NL + 2 * S::KB + l, Wx + LDC, LDC);
@@ -991,7 +994,7 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
                 conv8_pair<S, W8::NTA, W8::NTB, 2 * S::KS_C, C1, LDC, true>(
                     wh, [&](int ks) { return ks < S::KS_C ? xa[4 * ks] : sk[4 * (ks - S::KS_C)]; },
                     [&](int j, int ks) { return wb.at(o.post1_w + (j * (2 * S::KS_C) + ks) * 64); },
-                    [&](int j) { return wb.at16x4(o.post1_b + j * 64); }, NoSide{}, Wy, 1, ws, lane);
+                    [&](int j) { return wb.at16x4(o.post1_b + j * 64); }, NoSide{}, Wy, 1, ws, lane, ap);
             }
             int* pflag = reinterpret_cast<int*>(smem + W8::MXF) + 4 + ws;
             const int seq = fc + 1;
@@ -1024,7 +1027,7 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
             conv8_pair<S, W8::NTA, W8::NTB, 2 * S::KS_C, C1, LDC, true>(
                 wh, [&](int ks) { return ks < S::KS_C ? xa[4 * ks] : sk[4 * (ks - S::KS_C)]; },
                 [&](int j, int ks) { return wb.at(o.post1_w + (j * (2 * S::KS_C) + ks) * 64); },
-                [&](int j) { return wb.at16x4(o.post1_b + j * 64); }, stage, Wy, 1, ws, lane);
+                [&](int j) { return wb.at16x4(o.post1_b + j * 64); }, stage, Wy, 1, ws, lane, ap);
         }
         __syncthreads();
         {
@@ -1050,6 +1053,7 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
                 float m0 = b0, m1 = b1;
                 if (i1 < F1) { m0 += PT[i1 * S::LDP + j1]; m1 += PT[i1 * S::LDP + 8 + j1]; }
                 if (i1 >= 1) { m0 += PT[(i1 - 1) * S::LDP + j1 + 4]; m1 += PT[(i1 - 1) * S::LDP + 8 + j1 + 4]; }
+                if constexpr (S::EPM != kMaskNone) { m0 = mask_f<S::EPM>(m0); m1 = mask_f<S::EPM>(m1); }
                 const float xr_ = sc[2 + f], xi_ = sc[S::LDS_S + 2 + f];
                 float yr = xr_ * m0 - xi_ * m1;
                 float yi = xr_ * m1 + xi_ * m0;

@@ -71,8 +71,17 @@ __host__ __device__ constexpr int round_up(int a, int b) { return ceil_div(a, b)
 // channels and sub-bands of the frame), the reference's LayerNorm over (F2, C2) after the blocks' fc layers; nothing folds.
 // BD = 1: the `fastenhancer.noncausal` variant (models/fastenhancer/noncausal/model.py:186-187): the blocks' time GRU is
 // bidirectional and rnn_fc maps 2 C2 -> C2; offline only, run by the time-batched engine (tb_kernels.hip.h) alone.
-template <int C1_, int NL_, int C2_, int F2_, int KB_, int NFFT_, int HOP_, int KT_ = 1, int LOW_ = 0, int FR_ = 0, int TA_ = 0, int LN_ = 0, int BD_ = 0>
+// EP = activation + 8 * mask: the constructor options of models/fastenhancer/default/model.py:384-419 beyond the shipped yamls'
+// (include/fastenhancer_hip.h FE_ACT_* / FE_MASK_*): the conv trunk's activation (0 = SiLU) and the function applied to the two
+// dec_post channels before the complex multiply (0 = identity).  EP = 0 is the shipped code, instruction for instruction.
+template <int C1_, int NL_, int C2_, int F2_, int KB_, int NFFT_, int HOP_, int KT_ = 1, int LOW_ = 0, int FR_ = 0, int TA_ = 0, int LN_ = 0, int BD_ = 0,
+          int EP_ = 0>
 struct Shape {
+    static constexpr int EP = EP_;
+    static constexpr int EPA = EP_ % 8;           // kAct*: activation of the conv trunk
+    static constexpr int EPM = EP_ / 8;           // kMask*: function of the mask
+    static constexpr bool EPP = EPA == 2 || EPA == 3;      // the activation has a run-time constant (Pack::act_p)
+    static_assert(EP_ >= 0 && EPA <= 5 && EPM <= 2, "EP = activation (0..5) + 8 * mask (0..2)");
     static constexpr bool LN = LN_ != 0;
     static constexpr bool BIDIR = BD_ != 0;
     static constexpr int ND = BD_ != 0 ? 2 : 1;      // GRU directions over time
@@ -203,6 +212,7 @@ struct PackedOffsets {
     // 256-float aligned and padded, so that a unit is staged by whole 1-KiB global_load_lds pieces.
     int n_units;
     int u_off[32], u_size[32];
+    int act_p;                          // Shape::EPP: the activation's constant (LeakyReLU negative_slope / ELU alpha), one float; else 0
 };
 
 template <class S>
@@ -306,6 +316,8 @@ struct Pack {
             const int ubeg = o.u_off[0], uend_ = o.u_off[o.n_units - 1] + o.u_size[o.n_units - 1];
             o.conv_k4_delta = alloc(uend_ - ubeg) - ubeg;
         }
+        o.act_p = 0;
+        if (S::EPP) o.act_p = alloc(4);     // (allocated last: every other offset is the same with and without it)
         o.total = round_up(cur, 64);
         return o;
     }
@@ -367,6 +379,59 @@ __device__ __forceinline__ float silu_scaled_f(float u) { return u * __builtin_a
 // x^p for x > 0 through the 1-ulp hardware log2 / exp2 (v_log_f32, v_exp_f32); pow_f(0, p > 0) = 0
 __device__ __forceinline__ float pow_f(float x, float p) { return x > 0.0f ? __builtin_amdgcn_exp2f(p * __builtin_amdgcn_logf(x)) : 0.0f; }
 __device__ __forceinline__ float tanh_f(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
+// The activations and masks of Shape::EP (FE_ACT_* / FE_MASK_* of include/fastenhancer_hip.h; the reference's
+// `getattr(nn, activation)(**activation_kwargs)` and `self.mask`, models/fastenhancer/default/model.py:397-404, 431).
+// act_f: plain value (the ln variant's trunk); act_scaled_f: in the trunk's scaled domain, kSiluScale * f(u / kSiluScale) -
+// kSiluScale is NEGATIVE, so ReLU there is min(u, 0).  p: LeakyReLU's negative_slope / ELU's alpha (Pack::act_p, read at run time).
+enum { kActSiLU = 0, kActReLU = 1, kActLeakyReLU = 2, kActELU = 3, kActGELU = 4, kActGELUTanh = 5 };
+enum { kMaskNone = 0, kMaskSigmoid = 1, kMaskTanh = 2 };
+// expm1, erf and tanh here are branch-free sequences of explicit FMAs and 1-ulp hardware ops, not the library's expm1f / erff / tanhf: how
+// the compiler if-converts and contracts those depends on the code around each instantiation, and the per-hop and the chunked kernels must
+// stay bit-identical.  expm1: 2^(x log2 e) - 1, and x + x^2 (1/2 + x/6 + x^2/24) where that cancels (|x| < 1/16: |error| < 1e-8);
+// erf: Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7); tanh: tanh_f (a few 1e-8 absolute).
+__device__ __forceinline__ float expm1_f(float x) {
+    float q = __builtin_fmaf(x, 1.0f / 24.0f, 1.0f / 6.0f);
+    q = __builtin_fmaf(q, x, 0.5f);
+    const float small = __builtin_fmaf(q * x, x, x);
+    const float big = __expf(x) - 1.0f;
+    return fabsf(x) < 0.0625f ? small : big;
+}
+__device__ __forceinline__ float erf_f(float x) {
+    const float ax = fabsf(x);
+    const float t = __builtin_amdgcn_rcpf(__builtin_fmaf(0.3275911f, ax, 1.0f));
+    float p = __builtin_fmaf(1.061405429f, t, -1.453152027f);
+    p = __builtin_fmaf(p, t, 1.421413741f);
+    p = __builtin_fmaf(p, t, -0.284496736f);
+    p = __builtin_fmaf(p, t, 0.254829592f);
+    const float e = __builtin_fmaf(-p * t, __expf(-ax * ax), 1.0f);
+    return copysignf(e, x);
+}
+__device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.0f + erf_f(x * 0.70710678118654752f)); }
+__device__ __forceinline__ float gelu_tanh_f(float x) {
+    return 0.5f * x * (1.0f + tanh_f(0.79788456080286536f * __builtin_fmaf(0.044715f * x, x * x, x)));
+}
+template <int A>
+__device__ __forceinline__ float act_f(float x, float p) {
+    if constexpr (A == kActSiLU) return silu_f(x);
+    else if constexpr (A == kActReLU) return fmaxf(x, 0.0f);
+    else if constexpr (A == kActLeakyReLU) return x > 0.0f ? x : p * x;
+    else if constexpr (A == kActELU) return x > 0.0f ? x : p * expm1_f(x);
+    else if constexpr (A == kActGELU) return gelu_f(x);
+    else return gelu_tanh_f(x);
+}
+template <int A>
+__device__ __forceinline__ float act_scaled_f(float u, float p) {
+    if constexpr (A == kActSiLU) return silu_scaled_f(u);
+    else if constexpr (A == kActReLU) return fminf(u, 0.0f);
+    else if constexpr (A == kActLeakyReLU) return u < 0.0f ? u : p * u;
+    else return kSiluScale * act_f<A>(u * (1.0f / kSiluScale), p);
+}
+template <int M>
+__device__ __forceinline__ float mask_f(float x) {
+    if constexpr (M == kMaskSigmoid) return sigmoid_f(x);
+    else if constexpr (M == kMaskTanh) return tanh_f(x);
+    else return x;
+}
 // GRU gate pre-activations carried SCALED on the latency chains (the time-batched scans, the FSPEN / LiSenNet recurrences): r, z by
 // -log2 e, the n parts by 2 log2 e - the scale sits in the weights / at the place the x side is produced -, so that sigmoid and tanh are
 // exp2 + rcp with no multiply on the step's chain (a lone wave issues one instruction every ~6 cycles whatever its kind)
@@ -662,9 +727,9 @@ __device__ __forceinline__ float row16_allreduce(float x, OP op) {
 // red[0..3] and red[4..7], so the second pass's stores cannot race the first pass's loads.  FC = false: buf <- act(xhat * g[c] + b[c]).
 // FC = true (the blocks' LayerNorm AS WRITTEN in models/fastenhancer/ln/model.py:31-34 - `diff.addcmul(inv_std * weight, bias)`, i.e. the centred
 // value plus inv_std * weight * bias): xres[r][c] += (v - mean) + inv_std * g[c] * b[c] (+ pe[r][c]).  The caller barriers afterwards.
-template <int ROWS, int COLS, int LD, bool ACT, bool FC>
+template <int ROWS, int COLS, int LD, bool ACT, bool FC, int EPA = kActSiLU>
 __device__ __forceinline__ void ln_pass(float* buf, float* red, const float* g, const float* bt, float eps, float* xres = nullptr, int ldx = 0,
-                                        const float* pe = nullptr) {
+                                        const float* pe = nullptr, float ap = 0.0f) {
     constexpr int N = ROWS * COLS, PER = ceil_div(N, kThreads);
     const int tid = threadIdx.x;
     float v[PER], gc[PER], bc[PER], s = 0.0f, q = 0.0f;
@@ -700,7 +765,7 @@ __device__ __forceinline__ void ln_pass(float* buf, float* red, const float* g, 
             (e < N ? xres + r * ldx + c : red + 8)[0] = x;
         } else {
             float y = fmaf((v[i] - mean) * inv, gc[i], bc[i]);
-            if (ACT) y = silu_f(y);
+            if (ACT) y = act_f<EPA>(y, ap);
             (e < N ? buf + r * LD + c : red + 8)[0] = y;
         }
     }
@@ -1078,13 +1143,13 @@ __device__ __forceinline__ void conv_multi(f32x4 (&acc)[S::MTPW][NT], const floa
         ConvB<S, NT, NSEG * KS_SEG, WS>{w, w_off}, side);
 }
 
-// Epilogue of a conv-layout GEMM: optional SiLU, store to out[(row0 + m)][col] for col < NCOLS.
+// Epilogue of a conv-layout GEMM: optional activation (Shape::EPA; ap: its constant), store to out[(row0 + m)][col] for col < NCOLS.
 // gskip != nullptr: also store the value into a global skip buffer in A-fragment order
 //   gskip[((mt * KS_C + col/4) * 64 + (col%4) * 16 + m%16)],   mt = m / 16
 // (what the decoder's 1x1 conv later reads back as coalesced 256-byte A fragments).
 template <class S, int NT, int NCOLS, int LDO, bool ACT>
 __device__ __forceinline__ void conv_store(const f32x4 (&acc)[S::MTPW][NT], float* out, int row0, int wave, int lane,
-                                           float* gskip = nullptr) {
+                                           float* gskip = nullptr, float ap = 0.0f) {
     const int li = lane & 15, lg = lane >> 4;
 #pragma unroll
     for (int i = 0; i < S::MTPW; ++i)
@@ -1096,7 +1161,7 @@ __device__ __forceinline__ void conv_store(const f32x4 (&acc)[S::MTPW][NT], floa
                 for (int r = 0; r < 4; ++r) {
                     const int m = 16 * (wave + 4 * i) + 4 * lg + r;
                     float v = acc[i][j][r];
-                    if (ACT) v = silu_scaled_f(v);
+                    if (ACT) v = act_scaled_f<S::EPA>(v, ap);
                     out[(row0 + m) * LDO + col] = v;
                     if (gskip != nullptr) gskip[((wave + 4 * i) * S::KS_C + (col >> 2)) * 64 + (col & 3) * 16 + 4 * lg + r] = v;
                 }
@@ -1112,7 +1177,7 @@ __device__ __forceinline__ void conv_store(const f32x4 (&acc)[S::MTPW][NT], floa
 // tiles x half the column tiles, weights 2x instead of 4x redundant.
 template <class S, int NS, int KS, int NCOLS, int LDO, bool ACT, class AF, class WS, class SIDE>
 __device__ __forceinline__ void conv_nsplit(AF&& af, const WS& w, int w_off, int bias_off, const SIDE& side, float* out, int row0,
-                                            int wave, int lane, float* gskip) {
+                                            int wave, int lane, float* gskip, float ap = 0.0f) {
     constexpr int MS = kWaves / NS, MT = S::MTC / MS, NTW = S::NTC / NS;
     const int li = lane & 15, lg = lane >> 4;
     const int wn = NS == kWaves ? wave : wave % NS, m0 = NS == kWaves ? 0 : (wave / NS) * MT;   // (literals keep the offsets immediates)
@@ -1150,7 +1215,7 @@ __device__ __forceinline__ void conv_nsplit(AF&& af, const WS& w, int w_off, int
                 for (int r = 0; r < 4; ++r) {
                     const int m = 16 * i + 4 * lg + r;
                     float v = acc[ii][j][r];
-                    if (ACT) v = silu_scaled_f(v);
+                    if (ACT) v = act_scaled_f<S::EPA>(v, ap);
                     out[(row0 + m) * LDO + col] = v;
                     if (gskip != nullptr) gskip[(i * S::KS_C + (col >> 2)) * 64 + (col & 3) * 16 + 4 * lg + r] = v;
                 }
@@ -1418,6 +1483,8 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
     wb.lds = nullptr;
     wb.base = 0;
     wb.k4d = o.k4_delta;
+    float ap = 0.0f;                                 // the activation's constant (Shape::EPP)
+    if constexpr (S::EPP) ap = wp[o.act_p];
 
     // ---- one-time: zero what must be zero - the 2-bin halo of the compressed spectrum and the halo rows of the
     // LDS-resident skip buffers (the work buffers' halos are re-zeroed per frame).  Everything else in LDS is either
@@ -1461,7 +1528,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
     };
     // ln variant: norm site `site` (Shape::LN_SITES order) over a [ROWS x COLS] LDS tile, GroupNorm form
     float* const lnred = smem + L::LNS;
-#define FE_LN_SITE(ROWS, COLS, LD, ACT, buf, site) ln_pass<ROWS, COLS, LD, ACT, false>(buf, lnred, wp + lz + o.ln_g[site], wp + lz + o.ln_b[site], 1.0e-5f)   /* (+ lz: not hoisted out of the frame loop) */
+#define FE_LN_SITE(ROWS, COLS, LD, ACT, buf, site) ln_pass<ROWS, COLS, LD, ACT, false, S::EPA>(buf, lnred, wp + lz + o.ln_g[site], wp + lz + o.ln_b[site], 1.0e-5f, nullptr, 0, nullptr, ap)   /* (+ lz: not hoisted out of the frame loop) */
     static_assert(!S::LN || (L::STAGED && L::SKIPS_LDS && S::KT == 1 && !S::FRNN && !S::TATT), "ln variant: built for the B-type plan (staged weights, LDS skips)");
     // weight units: unit U of frame t is consumed from LDS buffer ((U + t*NU) & 1) while the next streams in
     constexpr int NPW = L::STAGED ? ceil_div(ceil_div(Pack<S>::umax(), 256), kWaves) : 1;
@@ -1759,7 +1826,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                     ((q & 2) ? W1 : W0)[((q & 1) ? F1 + 1 : 0) * LDC + c] = 0.0f;
                 }
             }
-            conv_store<S, S::NTC, C1, LDC, !S::LN>(acc, encbuf(0), 1, wave, lane, SG ? skipg : nullptr);
+            conv_store<S, S::NTC, C1, LDC, !S::LN>(acc, encbuf(0), 1, wave, lane, SG ? skipg : nullptr, ap);
         }
         FE_KVW(0, W_F3);
         __syncthreads();
@@ -1849,7 +1916,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                     if (tid == 0) __hip_atomic_store(pflag + S::KB + lidx, (unsigned int)(t + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
             });
-            conv_store<S, S::NTC, C1, LDC, true>(acc, out, 1, wave, lane);
+            conv_store<S, S::NTC, C1, LDC, true>(acc, out, 1, wave, lane, nullptr, ap);
             }
         };
 
@@ -1868,7 +1935,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                 const float* a0 = in + li * LDC + lg;
                 conv_nsplit<S, NS, 3 * S::KS_C, C1, LDC, true>(
                     [&](int i, int ks) { return a0[(16 * i + ks / S::KS_C) * LDC + 4 * (ks % S::KS_C)]; }, wb, o.enc_w[l], o.enc_b[l], stage,
-                    out, 1, wave, lane, SG ? skipg + (l + 1) * SKIP_FLOATS : nullptr);
+                    out, 1, wave, lane, SG ? skipg + (l + 1) * SKIP_FLOATS : nullptr, ap);
                 if (l == 0) FE_CLK(41);
             } else {
             f32x4 acc[S::MTPW][S::NTC];
@@ -1879,7 +1946,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
             __builtin_amdgcn_sched_barrier(0);
             if (l == 0) FE_CLK(41);
             stage.commit();
-            conv_store<S, S::NTC, C1, LDC, !S::LN>(acc, out, 1, wave, lane, SG ? skipg + (l + 1) * SKIP_FLOATS : nullptr);
+            conv_store<S, S::NTC, C1, LDC, !S::LN>(acc, out, 1, wave, lane, SG ? skipg + (l + 1) * SKIP_FLOATS : nullptr, ap);
             }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -3007,7 +3074,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                             if (ks < K0) return xa0[(16 * i) * LD0 + 4 * ks];
                             if constexpr (SG) return skb.at_g((S::NL - l) * SKIP_FLOATS + (i * S::KS_C + (ks - K0)) * 64);
                             else return sk0[(16 * i) * LDC + 4 * (ks - K0)];
-                        }, wb, o.dec1_w[l], o.dec1_b[l], stage, Wy, 1, wave, lane, nullptr);
+                        }, wb, o.dec1_w[l], o.dec1_b[l], stage, Wy, 1, wave, lane, nullptr, ap);
                 } else {
                     f32x4 acc[S::MTPW][S::NTC];
                     acc_init_bias<S::MTPW, S::NTC>(acc, wb, o.dec1_b[l], 0, 1, S::NTC);
@@ -3023,7 +3090,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                         },
                         ConvB<S, S::NTC, K0 + S::KS_C, decltype(wb)>{wb, o.dec1_w[l]}, stage);
                     stage.commit();
-                    conv_store<S, S::NTC, C1, LDC, !S::LN>(acc, Wy, 1, wave, lane);
+                    conv_store<S, S::NTC, C1, LDC, !S::LN>(acc, Wy, 1, wave, lane, nullptr, ap);
                 }
             }
             __syncthreads();
@@ -3036,7 +3103,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                     const float* a0 = Wy + li * LDC + lg;
                     conv_nsplit<S, NS, 3 * S::KS_C, C1, LDC, true>(
                         [&](int i, int ks) { return a0[(16 * i + ks / S::KS_C) * LDC + 4 * (ks % S::KS_C)]; }, wb, o.dec3_w[l], o.dec3_b[l], stage,
-                        Wx, 1, wave, lane, nullptr);
+                        Wx, 1, wave, lane, nullptr, ap);
                 } else {
                 f32x4 acc[S::MTPW][S::NTC];
                 acc_init_bias<S::MTPW, S::NTC>(acc, wb, o.dec3_b[l], 0, 1, S::NTC);
@@ -3044,7 +3111,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                                               Wy + (16 * wave + li + 2) * LDC + lg};
                 conv_multi<S, S::NTC, 3, S::KS_C, LDC>(acc, taps, wb, o.dec3_w[l], stage);
                 stage.commit();
-                conv_store<S, S::NTC, C1, LDC, !S::LN>(acc, Wx, 1, wave, lane);   // Wx (and Y2 under it) was fully consumed before the barrier above
+                conv_store<S, S::NTC, C1, LDC, !S::LN>(acc, Wx, 1, wave, lane, nullptr, ap);   // Wx (and Y2 under it) was fully consumed before the barrier above
                 }
             }
             __syncthreads();
@@ -3065,7 +3132,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                         if (ks < S::KS_C) return xa0[(16 * i) * LDC + 4 * ks];
                         if constexpr (SG) return skb.at_g((i * S::KS_C + (ks - S::KS_C)) * 64);
                         else return sk0[(16 * i) * LDC + 4 * (ks - S::KS_C)];
-                    }, wb, o.post1_w, o.post1_b, stage, Wy, 1, wave, lane, nullptr);
+                    }, wb, o.post1_w, o.post1_b, stage, Wy, 1, wave, lane, nullptr, ap);
             } else {
             f32x4 acc[S::MTPW][S::NTC];
             acc_init_bias<S::MTPW, S::NTC>(acc, wb, o.post1_b, 0, 1, S::NTC);
@@ -3082,7 +3149,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                     ConvB<S, S::NTC, 2 * S::KS_C, decltype(wb)>{wb, o.post1_w}, stage);
             }
             stage.commit();
-            conv_store<S, S::NTC, C1, LDC, !S::LN>(acc, Wy, 1, wave, lane);
+            conv_store<S, S::NTC, C1, LDC, !S::LN>(acc, Wy, 1, wave, lane, nullptr, ap);
             }
         }
         __syncthreads();
@@ -3111,6 +3178,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                 float m0 = b0, m1 = b1;
                 if (i1 < F1) { m0 += PT[i1 * S::LDP + j1]; m1 += PT[i1 * S::LDP + 8 + j1]; }
                 if (i1 >= 1) { m0 += PT[(i1 - 1) * S::LDP + j1 + 4]; m1 += PT[(i1 - 1) * S::LDP + 8 + j1 + 4]; }
+                if constexpr (S::EPM != kMaskNone) { m0 = mask_f<S::EPM>(m0); m1 = mask_f<S::EPM>(m1); }
                 const float xr = sc[2 + f], xi = sc[S::LDS_S + 2 + f];
                 float yr = xr * m0 - xi * m1;
                 float yi = xr * m1 + xi * m0;

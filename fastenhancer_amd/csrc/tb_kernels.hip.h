@@ -134,11 +134,11 @@ struct ConvTiling {
 };
 
 // acc[i][j] = bias[column tile j of this wave]; A(i, ks) from `af`, B from the packed weights at w_off (KS k-steps per tile);
-// epilogue: optional SiLU (scaled trunk), store to the activation buffers out[f] (row 1 + m: row 0 is the halo) and - gskip -
+// epilogue: optional activation (Shape::EPA, scaled trunk; ap: its constant), store to the activation buffers out[f] (row 1 + m: row 0 is the halo) and - gskip -
 // to the frames' global skip slots in A-fragment order (one 16-byte store per lane and tile).
 template <class S, int FT, int KS, bool ACT, int NCOLS, int LDO, int OSTR, int ROW0, class AF>
 __device__ __forceinline__ void conv_gemm(AF&& af, const WSrc<false>& wb, int w_off, int b_off, float* out, float* gskip, size_t gskip_fstride,
-                                          int nvalid, int wave, int lane) {
+                                          int nvalid, int wave, int lane, float ap = 0.0f) {
     using CT = ConvTiling<S, FT>;
     constexpr int MT = CT::MT, NTW = CT::NTW, NTALL = (NCOLS + 15) / 16;
     const int li = lane & 15, lg = lane >> 4;
@@ -181,7 +181,7 @@ __device__ __forceinline__ void conv_gemm(AF&& af, const WSrc<false>& wb, int w_
                 f32x4 v = acc[i][j];
                 if (ACT) {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = silu_scaled_f(v[r]);
+                    for (int r = 0; r < 4; ++r) v[r] = act_scaled_f<S::EPA>(v[r], ap);
                 }
                 float* od = out + f * OSTR + (ROW0 + 16 * mt + 4 * lg) * LDO + col;
 #pragma unroll
@@ -344,6 +344,8 @@ __global__ void __launch_bounds__(kThreads) tb_enc_kernel(TbArgs a) {
     const int li = lane & 15, lg = lane >> 4;
     const WSrc<false> wb = make_wsrc<S>(a.wp, lane);
     const int wave = wave_k, wm = CT::NS == kWaves ? 0 : wave / CT::NS;
+    float ap = 0.0f;                  // the activation's constant (Shape::EPP)
+    if constexpr (S::EPP) ap = a.wp[o.act_p];
 
     float2* tw = reinterpret_cast<float2*>(smem + L::TW);
     for (int i = tid; i < N / 2; i += kThreads) tw[i] = reinterpret_cast<const float2*>(a.wp + o.twiddle)[i];
@@ -492,7 +494,7 @@ __global__ void __launch_bounds__(kThreads) tb_enc_kernel(TbArgs a) {
                     const int kk = 4 * ks + lg, c = kk & 1, s = (kk >> 1) & 3, tp = kk >> 3;
                     const int m = 16 * (CT::mtile0(i) + wm) + li;
                     return scb[CT::frame(i) * 2 * S::LDS_S + c * S::LDS_S + 4 * (m + tp) + s];
-                }, wb, o.enc_pre_w, o.enc_pre_b, A0, skip_tile, SKF, nvalid, wave, lane);
+                }, wb, o.enc_pre_w, o.enc_pre_b, A0, skip_tile, SKF, nvalid, wave, lane, ap);
         }
         __syncthreads();
         TB_MARK(2);                 // enc_pre
@@ -502,7 +504,7 @@ __global__ void __launch_bounds__(kThreads) tb_enc_kernel(TbArgs a) {
             const float* in = (l & 1) ? A1 : A0;
             float* out = (l & 1) ? A0 : A1;
             conv_gemm<S, FT, 3 * S::KS_C, true, C1, LDC, S::ACT, 1>(K3Src<S, FT>{in + (16 * wm + li) * LDC + lg}, wb, o.enc_w[l], o.enc_b[l], out,
-                                                                     skip_tile + (size_t)(l + 1) * F1 * C1, SKF, nvalid, wave, lane);
+                                                                     skip_tile + (size_t)(l + 1) * F1 * C1, SKF, nvalid, wave, lane, ap);
             __syncthreads();
             TB_MARK(3 + l);         // encoder layer l
         });
@@ -1417,6 +1419,8 @@ __global__ void __launch_bounds__(kThreads) tb_dec_kernel(TbArgs a) {
     const int li = lane & 15, lg = lane >> 4;
     const WSrc<false> wb = make_wsrc<S>(a.wp, lane);
     const int wave = wave_k, wm = CT::NS == kWaves ? 0 : wave / CT::NS;
+    float ap = 0.0f;                  // the activation's constant (Shape::EPP)
+    if constexpr (S::EPP) ap = a.wp[o.act_p];
     float2* tw = reinterpret_cast<float2*>(smem + L::TW);
     for (int i = tid; i < N / 2; i += kThreads) tw[i] = reinterpret_cast<const float2*>(a.wp + o.twiddle)[i];
     float* const Wy = smem + L::WY;
@@ -1501,12 +1505,12 @@ __global__ void __launch_bounds__(kThreads) tb_dec_kernel(TbArgs a) {
                         const int f = CT::frame(i), mt0 = CT::mtile0(i);
                         if (ks < K0) return (l == 0) ? x0[f * (F1 * LDX) + (16 * mt0) * LDX + 4 * ks] : x0[f * S::ACT + (16 * mt0) * LDC + 4 * ks];
                         return skb.at_g(f * (int)SKF + sk_off + ((mt0 + wm) * S::KS_C + (ks - K0)) * 64);
-                    }, wb, o.dec1_w[l], o.dec1_b[l], Wy, nullptr, 0, nvalid, wave, lane);
+                    }, wb, o.dec1_w[l], o.dec1_b[l], Wy, nullptr, 0, nvalid, wave, lane, ap);
             }
             __syncthreads();
             TB_MARK(3 + 2 * l);     // decoder layer l, 1x1
             conv_gemm<S, FT, 3 * S::KS_C, true, C1, LDC, S::ACT, 1>(K3Src<S, FT>{Wy + (16 * wm + li) * LDC + lg}, wb, o.dec3_w[l], o.dec3_b[l], Wx,
-                                                                     nullptr, 0, nvalid, wave, lane);
+                                                                     nullptr, 0, nvalid, wave, lane, ap);
             __syncthreads();
             TB_MARK(4 + 2 * l);     // decoder layer l, k = 3
         });
@@ -1518,7 +1522,7 @@ __global__ void __launch_bounds__(kThreads) tb_dec_kernel(TbArgs a) {
                     const int f = CT::frame(i), mt0 = CT::mtile0(i);
                     if (ks < S::KS_C) return x0[f * S::ACT + (16 * mt0) * LDC + 4 * ks];
                     return skb.at_g(f * (int)SKF + ((mt0 + wm) * S::KS_C + (ks - S::KS_C)) * 64);
-                }, wb, o.post1_w, o.post1_b, Wy, nullptr, 0, nvalid, wave, lane);
+                }, wb, o.post1_w, o.post1_b, Wy, nullptr, 0, nvalid, wave, lane, ap);
         }
         __syncthreads();
         TB_MARK(20);                // dec_post 1x1
@@ -1543,6 +1547,7 @@ __global__ void __launch_bounds__(kThreads) tb_dec_kernel(TbArgs a) {
                 float m0 = b0, m1 = b1;
                 if (i1 < F1) { m0 += PTf[i1 * S::LDP + j1]; m1 += PTf[i1 * S::LDP + 8 + j1]; }
                 if (i1 >= 1) { m0 += PTf[(i1 - 1) * S::LDP + j1 + 4]; m1 += PTf[(i1 - 1) * S::LDP + 8 + j1 + 4]; }
+                if constexpr (S::EPM != kMaskNone) { m0 = mask_f<S::EPM>(m0); m1 = mask_f<S::EPM>(m1); }
                 const float xr = xcr[q][0], xi = xcr[q][1];
                 float yr = xr * m0 - xi * m1, yi = xr * m1 + xi * m0;
                 if (a.mode == FE_MODE_OFFLINE && f < nvalid) {
@@ -1598,6 +1603,7 @@ __global__ void __launch_bounds__(kThreads) tb_dec_kernel(TbArgs a) {
                 float m0 = b0, m1 = b1;
                 if (i1 < F1) { m0 += PTf[i1 * S::LDP + j1]; m1 += PTf[i1 * S::LDP + 8 + j1]; }
                 if (i1 >= 1) { m0 += PTf[(i1 - 1) * S::LDP + j1 + 4]; m1 += PTf[(i1 - 1) * S::LDP + 8 + j1 + 4]; }
+                if constexpr (S::EPM != kMaskNone) { m0 = mask_f<S::EPM>(m0); m1 = mask_f<S::EPM>(m1); }
                 const float xr = xcg[fb], xi = xcg[F0 + fb];
                 float yr = xr * m0 - xi * m1, yi = xr * m1 + xi * m0;
                 if (sph != nullptr) { sph[((size_t)fb * TF + t) * 2] = yr; sph[((size_t)fb * TF + t) * 2 + 1] = yi; }

@@ -72,6 +72,7 @@ class Engine:
             c.ln = 1 if cfg.ln else 0
             c.rf_eps = cfg.rf_eps
             c.bidirectional = 1 if getattr(cfg, "noncausal", False) else 0
+            c.activation, c.activation_param, c.mask = cfg.activation, cfg.activation_param, cfg.mask
         self._h = c_void_p()
         if self.device is not None and self.device.type == "cuda":
             with torch.cuda.device(self.device):

@@ -44,10 +44,33 @@ extern "C" {
 #define FE_MAX_KERNELS 8
 
 /* Mirror of the yaml `model_kwargs` that select the architecture
- * (configs/fastenhancer/b.yaml:2-29; defaults models/fastenhancer/default/model.py:384-403).
- * Invariants of every shipped yaml are asserted by fe_create(): activation SiLU, mask null,
- * stride 4, kernel_size[0] 8 and 3 afterwards, window hann, stft_normalized False, weight
- * reparameterisations already removed (fused weights). */
+ * (configs/fastenhancer/b.yaml:2-29; defaults models/fastenhancer/default/model.py:384-419).
+ * Invariants of every shipped yaml are asserted by fe_create(): stride 4, kernel_size[0] 8 and 3
+ * afterwards, window hann, stft_normalized False, resnet False, weight reparameterisations already
+ * removed (fused weights).  activation and mask (every shipped yaml: SiLU, null) select a kernel built
+ * for them: the shipped shapes are built for SiLU / no mask; others are built on demand
+ * (python -m fastenhancer_amd.build --add-shape ...,act=<name>,mask=<name>), for the default,
+ * time_kernel and ln models.  A struct that is zero in the last four fields is the shipped setting.
+ *
+ *   activation (FE_ACT_*)    activation_param            the reference's Act(**activation_kwargs)
+ *   FE_ACT_SILU        0     -                           nn.SiLU
+ *   FE_ACT_RELU        1     -                           nn.ReLU
+ *   FE_ACT_LEAKY_RELU  2     negative_slope (0.01)       nn.LeakyReLU(negative_slope)
+ *   FE_ACT_ELU         3     alpha (1.0)                 nn.ELU(alpha)
+ *   FE_ACT_GELU        4     -                           nn.GELU(approximate='none')
+ *   FE_ACT_GELU_TANH   5     -                           nn.GELU(approximate='tanh')
+ *   mask (FE_MASK_*): FE_MASK_NONE 0 (mask: null), FE_MASK_SIGMOID 1, FE_MASK_TANH 2 - applied to the two
+ *   dec_post channels before the complex multiply (model.py:397-404, 671).  activation_param is taken as given
+ *   (the reference's defaults are in parentheses: a caller that zeroes the struct must set them itself). */
+#define FE_ACT_SILU 0
+#define FE_ACT_RELU 1
+#define FE_ACT_LEAKY_RELU 2
+#define FE_ACT_ELU 3
+#define FE_ACT_GELU 4
+#define FE_ACT_GELU_TANH 5
+#define FE_MASK_NONE 0
+#define FE_MASK_SIGMOID 1
+#define FE_MASK_TANH 2
 typedef struct fe_config {
     int arch;                        /* FE_ARCH_* */
     int n_fft, hop_size, win_size;   /* N, H, win (win <= N, N even) */
@@ -90,6 +113,10 @@ typedef struct fe_config {
                                       * 2 C2 -> C2.  Weight sections: + rf_block.k.rnn.{weight,bias}_{ih,hh}_l0_reverse, rnn_fc.weight [C2, 2 C2].
                                       * The reference module has the offline `Model` only (:348, :628-635): fe_offline is the one compute entry
                                       * point (no caches: fe_state_floats = the two STFT caches, fe_step / fe_spec_step return FE_ERR_UNSUPPORTED_CONFIG) */
+    int activation;                  /* FE_ACT_* (0 = SiLU, every shipped yaml) */
+    float activation_param;          /* FE_ACT_LEAKY_RELU: negative_slope, FE_ACT_ELU: alpha; ignored otherwise */
+    int mask;                        /* FE_MASK_* (0 = none, every shipped yaml) */
+    int resnet;                      /* must be 0: the resnet option (model.py:636-668) is not built into this library */
 } fe_config;
 
 typedef struct fe_handle fe_handle;

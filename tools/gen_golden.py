@@ -98,6 +98,15 @@ CONFIGS = {
     "fe_dprnn_s": ("configs/ablation/dprnn_s.yaml", 133, 1, 6, 0),
     "fe_dprnn_m": ("configs/ablation/dprnn_m.yaml", 134, 1, 6, 0),
     "fe_dpt_s": ("configs/ablation/dpt_s.yaml", 143, 1, 6, 0),
+    # constructor options beyond the shipped yamls (models/fastenhancer/default/model.py:384-419): the conv trunk's activation and the
+    # mask function, compiled per shape on demand (python -m fastenhancer_amd.build --add-shape ...,act=..,mask=..; tests/test_gpu_model_options.py)
+    "fe_b_relu_sig": ("configs/fastenhancer/b.yaml", 170, 2, 12, 200, {"activation": "ReLU", "mask": "sigmoid"}),
+    "fe_b_gelu_tanh": ("configs/fastenhancer/b.yaml", 171, 2, 12, 200, {"activation": "GELU", "activation_kwargs": {}, "mask": "tanh"}),
+    "fe_t_lrelu": ("configs/fastenhancer/t.yaml", 172, 2, 12, 200, {"activation": "LeakyReLU", "activation_kwargs": {"negative_slope": 0.2, "inplace": True}}),
+    "fe_t_elu": ("configs/fastenhancer/t.yaml", 175, 2, 12, 200, {"activation": "ELU", "activation_kwargs": {"alpha": 1.0}, "mask": "sigmoid"}),
+    "fe_tk_gelutanh": ("configs/ablation/time_kernel_b.yaml", 173, 2, 10, 120, {"activation": "GELU", "activation_kwargs": {"approximate": "tanh"},
+                                                                                "mask": "sigmoid"}),
+    "fe_ln_elu": ("configs/ablation/ln_b.yaml", 174, 2, 10, 120, {"activation": "ELU", "activation_kwargs": {"alpha": 0.5}, "mask": "tanh"}),
 }
 
 
