@@ -68,6 +68,9 @@ int fail(int code, const char* fmt, ...) {
     return code;
 }
 
+// what an entry point returns after a launch that reported `e`
+int launch_rc(hipError_t e) { return e == hipSuccess ? FE_OK : fail(FE_ERR_HIP, "kernel launch: %s", hipGetErrorString(e)); }
+
 #define FE_HIP_CHECK(expr)                                                                  \
     do {                                                                                    \
         hipError_t _e = (expr);                                                             \
@@ -155,7 +158,7 @@ struct fe_handle {
     // fe_set_step_kernel / fe_set_option: which kernel a step dispatches.  The environment variables named in kOptions set the values NEW handles start
     // with (A/B runs of tools/ab_*.sh; a value outside the option's range, garbage included, is ignored) - nothing else in the library reads them.
     int step_kernel = FE_STEP_KERNEL_WG8;
-    int opt[8] = {};                          // kOptions order
+    int opt[OPT_COUNT] = {};                  // kOptions order
     const char* last_kernels[16] = {};        // fe_last_step_kernel: what the last compute call enqueued (string literals of the launchers)
     int n_last_kernels = 0;
     const char* last_shape = nullptr;         // ... and the compiled shape record that launched it
@@ -175,8 +178,8 @@ struct fe_handle {
     float* spec_ring_dev = nullptr;           // fe_spec_step, dptransformer, time-pipelined: the K / V rings of TA + P slots per pair (grow-only)
     size_t spec_ring_floats = 0;
     unsigned int* bsync_dev = nullptr;        // BSRNN fused per-hop step: barrier counters of the sixteen-stream tiles [kSyncTiles][2] (zeroed once; monotonic)
-    float* bsplit_dev = nullptr;              // BSRNN per-hop step in three launches: band features | compressed spectrum | MLP pre-activations
-    int bsplit_streams = 0;                   // (grow-only, sized by fe_state_init / the first step of a larger batch)
+    float* sb_dev = nullptr;                  // stream-batched per-hop step of BSRNN / FSPEN / LiSenNet: its scratch (ensure_sb_scratch)
+    int sb_streams = 0;                       // (grow-only, sized by fe_state_init / the first step of a larger batch)
     size_t tb_work_floats = 0;
     unsigned int* tb_prog_dev = nullptr;      // fused stages: the scan workgroups' frame counters [KB][2 * max_wgs]
     std::vector<Section> sections;
@@ -190,20 +193,6 @@ struct fe_handle {
 };
 
 namespace {
-
-// what a compute entry point enqueues ends up in its handle (fe_last_step_kernel)
-struct KernelLogScope {
-    fe_handle* h;
-    explicit KernelLogScope(fe_handle* h_) : h(h_) {
-        fe::g_klog.n = 0;
-        h->last_shape = h->impl ? h->impl->name : h->bimpl ? h->bimpl->name : h->fimpl ? "fspen" : h->limpl ? "lisennet" : nullptr;
-    }
-    ~KernelLogScope() {
-        if (!h) return;
-        h->n_last_kernels = fe::g_klog.n;
-        std::memcpy(h->last_kernels, fe::g_klog.name, sizeof(h->last_kernels));
-    }
-};
 
 void add_section(fe_handle* h, const std::string& name, std::vector<int> shape) {
     size_t n = 1;
@@ -341,6 +330,20 @@ void build_tables(fe_handle* h) {
         h->twiddle[2 * k] = (float)std::cos(ang);
         h->twiddle[2 * k + 1] = (float)std::sin(ang);
     }
+}
+
+// what every fe_create path shares: the handle, its device and CU count, its window tables (the caller adds its kernels and sections)
+fe_handle* new_handle(const fe_config* cfg, const Dims& d) {
+    fe_handle* h = new fe_handle();
+    h->cfg = *cfg;
+    h->d = d;
+    if (hipGetDevice(&h->device) != hipSuccess) h->device = -1;   // no GPU: sections/tables still usable
+    else {
+        int cus = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess && cus > 0) h->max_wgs = cus;
+    }
+    build_tables(h);
+    return h;
 }
 
 // Writes fragments at the compile-time offsets of fe::Pack<S>::v (the kernel uses the same table).
@@ -731,77 +734,47 @@ int pack_weights(fe_handle* h, const std::vector<float>& blob, std::vector<float
 }
 
 
-// the baseline families' host sides (weight sections, handle creation, packers): one file each
+// The stream-batched per-hop step's scratch of BSRNN / FSPEN / LiSenNet (sb_dev): grow-only, (re)allocated to `bytes` for a batch of
+// B >= min_streams streams that is larger than the one it holds (min_streams <= 0: the family's stream-batched step is off).
+int ensure_sb_scratch(fe_handle* h, int B, int min_streams, size_t bytes) {
+    if (min_streams <= 0 || B < min_streams || B <= h->sb_streams) return FE_OK;
+    if (h->sb_dev) { FE_HIP_CHECK(hipFree(h->sb_dev)); h->sb_dev = nullptr; h->sb_streams = 0; }
+    FE_HIP_CHECK(hipMalloc(&h->sb_dev, bytes));
+    h->sb_streams = B;
+    return FE_OK;
+}
+
+// the baseline families' host sides (weight sections, handle creation, packers, launches, the traits the paths below take): one file each
 #include "fe_api_bsrnn.inc"
 #include "fe_api_fspen.inc"
 #include "fe_api_lisennet.inc"
 
-size_t bsrnn_lstm_floats(const fe_handle* h, int B) { return (size_t)2 * h->cfg.rf_blocks * B * 31 * 2 * h->cfg.channels; }
-
-fe::BArgs bsrnn_args(fe_handle* h, int B, int T) {
-    fe::BArgs a{};
-    a.xp_scratch = h->skip_dev;
-    a.wp = h->packed_dev;
-    a.off = h->boff;
-    a.B = B;
-    a.T = T;
-    a.compression = h->cfg.input_compression;
-    return a;
-}
-
-// The per-hop BSRNN step runs as three launches (bsrnn_kernels.hip.h, PART): per stream 31 C floats of band features, 514 of compressed
-// spectrum and 2056 of MLP pre-activations pass through this scratch.  Grow-only; fe_state_init sizes it for its batch, so that a
-// steady-state step allocates nothing (FE_BSRNN_SPLIT=0: the fused kernel, for A/B measurements).
-constexpr int kSyncTiles = 64;       // sixteen-stream tiles of a fused BSRNN step (one workgroup per CU: 1024 CUs)
-size_t bsplit_floats_per_stream(const fe_handle* h) {
-    return (size_t)31 * h->cfg.channels + 2 * 257 + 2 * 1028 + (h->bimpl->launch_sb ? (size_t)2 * 31 * 2 * h->cfg.channels : 0);      // (+ the stream-batched layers' y scratch)
-}
-int ensure_bsplit(fe_handle* h, int B) {
-    if (!h->bimpl || B <= h->bsplit_streams) return FE_OK;
-    if (!h->opt[OPT_BSRNN_THREE_LAUNCH]) return FE_OK;
-    if (h->bsplit_dev) { FE_HIP_CHECK(hipFree(h->bsplit_dev)); h->bsplit_dev = nullptr; h->bsplit_streams = 0; }
-    FE_HIP_CHECK(hipMalloc(&h->bsplit_dev, (size_t)B * bsplit_floats_per_stream(h) * sizeof(float)));
-    h->bsplit_streams = B;
-    if (!h->bsync_dev) {
-        FE_HIP_CHECK(hipMalloc(&h->bsync_dev, kSyncTiles * 2 * sizeof(unsigned int)));
-        FE_HIP_CHECK(hipMemset(h->bsync_dev, 0, kSyncTiles * 2 * sizeof(unsigned int)));
+// The baseline families (BSRNN, FSPEN, LiSenNet) share one implementation of every entry point, parameterised by the family's traits;
+// FastEnhancer has paths of its own.  Calls f(Family{}) for a baseline family's arch and returns true; false for FastEnhancer.
+template <class F>
+bool visit_baseline(int arch, F&& f) {
+    switch (arch) {
+    case FE_ARCH_BSRNN: f(BsrnnFamily{}); return true;
+    case FE_ARCH_FSPEN: f(FspenFamily{}); return true;
+    case FE_ARCH_LISENNET: f(LisennetFamily{}); return true;
+    default: return false;
     }
-    return FE_OK;
 }
 
-int launch_bsrnn(fe_handle* h, const fe::BArgs& a_in, void* stream) {
-    hipError_t e = hipSuccess;
-    fe::BArgs a = a_in;
-    a.ov_off = (h->step_kernel == FE_STEP_KERNEL_WAVES4 || !h->opt[OPT_BSRNN_ROLE_SPLIT]) ? 1 : 0;
-    // (fe_set_option("bsrnn_ov_profile", 1): fe_profile_step probes the role-split PART 1 of the three-launch step instead of the fused kernel's phases)
-    const bool ov_prof = h->opt[OPT_BSRNN_OV_PROFILE] != 0;
-    h->last_shape = h->bimpl->name;
-    if (a.mode == fe::FE_MODE_STREAM && a.T == 1 && a.dbg == nullptr && (a.clk == nullptr || (ov_prof && h->cfg.channels == 16 && a.B <= h->max_wgs))) {
-        const int rc = ensure_bsplit(h, a.B);
-        if (rc != FE_OK) return rc;
-        if (h->bsplit_dev && a.B <= h->bsplit_streams) {
-            a.mlp_x = h->bsplit_dev;
-            a.mlp_sp = a.mlp_x + (size_t)a.B * 31 * h->cfg.channels;
-            a.mlp_pre = a.mlp_sp + (size_t)a.B * 2 * 257;
-            a.sb_y = a.mlp_pre + (size_t)a.B * 2 * 1028;
-            a.gsync = (h->opt[OPT_BSRNN_FUSED] && a.clk == nullptr && (a.B + 15) / 16 <= kSyncTiles) ? h->bsync_dev : nullptr;
-            // large batches: the LSTM layers batched over the streams on the matrix cores (sixteen streams per workgroup) - from the batch
-            // size where sixteen-stream workgroups fill the chip better than one stream per workgroup (FE_BSRNN_SB: that threshold; 0 = never)
-            // (default 2048; measured crossover on 256 CUs: ~1900 streams, profiles/r4c_bsrnn_stream_batched.txt.  num_channels = 64 (r6): a sixteen-stream tile takes 5.8 ms
-            //  whatever the batch and the per-stream kernel 2.3 us per stream - crossover at ~2700 streams: the threshold counts 11 / 8 there)
-            const int sb_opt = h->opt[OPT_BSRNN_SB_MIN];
-            const int sb_min = h->cfg.channels == 64 ? (int)((long long)sb_opt * 11 / 8) : sb_opt;
-            if (h->bimpl->launch_sb && sb_min > 0 && a.B >= sb_min) h->bimpl->launch_sb(a, h->sboff, h->packed_floats, h->max_wgs, (hipStream_t)stream, &e);
-            else
-            h->bimpl->launch_split(a, h->max_wgs, (hipStream_t)stream, &e);
-            if (e != hipSuccess) return fail(FE_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-            return FE_OK;
-        }
+// what a compute entry point enqueues ends up in its handle (fe_last_step_kernel)
+struct KernelLogScope {
+    fe_handle* h;
+    explicit KernelLogScope(fe_handle* h_) : h(h_) {
+        fe::g_klog.n = 0;
+        h->last_shape = h->impl ? h->impl->name : nullptr;
+        visit_baseline(h->cfg.arch, [&](auto F) { h->last_shape = F.shape_name(h); });
     }
-    h->bimpl->launch(a, h->max_wgs, (hipStream_t)stream, &e);
-    if (e != hipSuccess) return fail(FE_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-    return FE_OK;
-}
+    ~KernelLogScope() {
+        if (!h) return;
+        h->n_last_kernels = fe::g_klog.n;
+        std::memcpy(h->last_kernels, fe::g_klog.name, sizeof(h->last_kernels));
+    }
+};
 
 int check_ready(const fe_handle* h) {
     if (!h) return fail(FE_ERR_INVALID_ARG, "null handle");
@@ -817,9 +790,7 @@ int ensure_scratch(fe_handle* h, int) {
     // (BSRNN: band-LSTM input projections of the C = 64 shape; FastEnhancer: the larger of the shape's own plan and its
     // low-LDS companion's, which runs two workgroups per CU)
     size_t floats = 0;
-    if (h->fimpl || h->limpl) floats = 0;
-    else if (h->bimpl) floats = (size_t)h->max_wgs * h->bimpl->xp_floats;
-    else {
+    if (!visit_baseline(h->cfg.arch, [&](auto F) { floats = F.xp_floats(h); })) {
         floats = (size_t)h->max_wgs * h->impl->occ * h->impl->skip_floats;
         if (h->impl_many) floats = std::max(floats, (size_t)h->max_wgs * h->impl_many->occ * h->impl_many->skip_floats);
     }
@@ -888,6 +859,68 @@ __global__ void __launch_bounds__(256) poison_lds_kernel(unsigned int* sink) {
     if (pl[(threadIdx.x * 97 + blockIdx.x) % (160 * 1024 / 4)] == 0x12345u && sink) sink[0] = 1u;      // (keeps the stores alive)
 }
 
+constexpr size_t round4(size_t n) { return (n + 3) & ~(size_t)3; }
+
+// the overlap-add of windowed frames [B][T][N] into wav_out (rows of out_stride samples; Tw_b: a ragged batch's lengths)
+static int ola(fe_handle* h, const float* frames, float* wav_out, size_t out_stride, int B, int T, hipStream_t st, const int* Tw_b = nullptr) {
+    const int n_out = h->d.HOP * (T - 1);
+    fe::note_kernel("istft_ola_kernel");
+    hipLaunchKernelGGL(fe::istft_ola_kernel, dim3((n_out + fe::kThreads - 1) / fe::kThreads, B), dim3(fe::kThreads), 0, st,
+                       frames, h->tables_dev, wav_out, out_stride, h->d.NFFT, h->d.HOP, T, Tw_b);
+    const hipError_t e = hipGetLastError();
+    return launch_rc(e);
+}
+
+// A baseline family's fe_offline work buffer: overlap-add tail | model state | time-pipeline frame counters (these three zeroed by
+// fe_offline) | windowed frames [B][T][N] | the family's ring (Family::ring_floats).  fe_offline_work_floats sizes it for the time-pipelined
+// launch whatever fe_set_time_pipeline says at the time of that call.
+template <class Fam>
+size_t baseline_zeroed_floats(Fam, const fe_handle* h, int B) {
+    return (size_t)B * (size_t)(h->d.NFFT - h->d.HOP) + round4(Fam::state_floats(h, B)) + round4((size_t)B * Fam::counters(h));
+}
+
+// frames in flight per utterance of a baseline family's time-pipelined offline launch (0: one workgroup walks the frames of an utterance)
+template <class Fam>
+int baseline_pipe_width(Fam, const fe_handle* h, int B, int T) {
+    if (!Fam::impl(h)->launch_pipe || h->pipe_frames == 0 || h->pipe_frames == 1 || T < 4) return 0;
+    int p = (h->max_wgs * Fam::impl(h)->occ) / B;
+    const int want = h->pipe_frames < 0 ? Fam::kPipeFrames : h->pipe_frames;
+    p = p < want ? p : want;
+    p = p < T ? p : T;
+    return p >= 2 ? p : 0;
+}
+
+template <class Fam>
+int baseline_offline(Fam, fe_handle* h, const float* noisy_dev, int B, int Tw, float* wav_hat_dev, float* spec_hat_dev, float* work_dev, hipStream_t st) {
+    const Dims& d = h->d;
+    const int T = 1 + Tw / d.HOP;
+    FE_HIP_CHECK(hipMemsetAsync(work_dev, 0, baseline_zeroed_floats(Fam{}, h, B) * sizeof(float), st));
+    typename Fam::Args a = Fam::args(h, B, T);
+    a.mode = fe::FE_MODE_OFFLINE;
+    a.Tw = Tw;
+    a.wav_in = noisy_dev; a.in_stride = (size_t)Tw;
+    a.wav_out = wav_hat_dev; a.out_stride = (size_t)d.HOP * (T - 1);
+    a.spec_out = spec_hat_dev;
+    a.cache_istft = work_dev; a.cache_stft = work_dev;
+    Fam::state(a) = work_dev + (size_t)B * (d.NFFT - d.HOP);
+    if (const int P = baseline_pipe_width(Fam{}, h, B, T)) {
+        // the frames of an utterance over P co-resident workgroups (the family's PIPE kernel); refused co-residency: the serial walk
+        const int rc = ensure_tables(h, st);
+        if (rc != FE_OK) return rc;
+        float* flags = Fam::state(a) + round4(Fam::state_floats(h, B));
+        a.pipe_flags = reinterpret_cast<unsigned int*>(flags);
+        a.frames = flags + round4((size_t)B * Fam::counters(h));
+        Fam::set_ring(a, a.frames + (size_t)B * T * d.NFFT);
+        a.pipe_p = P;
+        hipError_t e = hipSuccess;
+        Fam::impl(h)->launch_pipe(a, st, &e);
+        if (e == hipSuccess) return ola(h, a.frames, wav_hat_dev, (size_t)d.HOP * (T - 1), B, T, st);
+        (void)hipGetLastError();
+        a.pipe_flags = nullptr; a.frames = nullptr; Fam::set_ring(a, nullptr); a.pipe_p = 0;
+    }
+    return Fam::launch(h, a, st);
+}
+
 extern "C" {
 
 int fe_debug_poison_lds(void* stream) {
@@ -906,9 +939,8 @@ const char* fe_version(void) { return "fastenhancer_hip 0.1 (gfx950)"; }
 int fe_create(const fe_config* cfg, fe_handle** out) {
     if (!cfg || !out) return fail(FE_ERR_INVALID_ARG, "null argument");
     *out = nullptr;
-    if (cfg->arch == FE_ARCH_BSRNN) return create_bsrnn(cfg, out);
-    if (cfg->arch == FE_ARCH_FSPEN) return create_fspen(cfg, out);
-    if (cfg->arch == FE_ARCH_LISENNET) return create_lisennet(cfg, out);
+    int rc = FE_OK;
+    if (visit_baseline(cfg->arch, [&](auto F) { rc = F.create(cfg, out); })) return rc;
     if (cfg->arch != FE_ARCH_FASTENHANCER)
         return fail(FE_ERR_UNSUPPORTED_CONFIG, "arch %d is not built into this library", cfg->arch);
     if (cfg->n_fft % 2 != 0) return fail(FE_ERR_INVALID_ARG, "`n_fft` must be an even number, but given %d.", cfg->n_fft);
@@ -973,24 +1005,17 @@ int fe_create(const fe_config* cfg, fe_handle** out) {
                     ep_arg);
     if (impl->lds_bytes > 160 * 1024)
         return fail(FE_ERR_UNSUPPORTED_CONFIG, "shape needs %zu bytes of LDS (> 160 KiB per CU)", impl->lds_bytes);
-    fe_handle* h = new fe_handle();
-    h->cfg = *cfg;
+    Dims d{impl->C1, impl->NL, impl->C2, impl->F2, impl->KB, impl->NFFT, impl->HOP, impl->NFFT / 2, impl->NFFT / 8, impl->C2 / 4, {0}};
+    d.KT = impl->KT;
+    d.FR = impl->FR;
+    d.TA = impl->TA;
+    d.LN = impl->LN;
+    d.BD = impl->BD;
+    for (int i = 0; i < cfg->n_kernels; ++i) d.ks[i] = cfg->kernel_size[i];
+    fe_handle* h = new_handle(cfg, d);
     h->impl = impl;
     h->impl_many = impl_many;              // (fe_set_option("low_lds_companion", 0) keeps run_step off it)
-    h->d = Dims{impl->C1, impl->NL, impl->C2, impl->F2, impl->KB, impl->NFFT, impl->HOP, impl->NFFT / 2, impl->NFFT / 8, impl->C2 / 4, {0}};
-    h->d.KT = impl->KT;
-    h->d.FR = impl->FR;
-    h->d.TA = impl->TA;
-    h->d.LN = impl->LN;
-    h->d.BD = impl->BD;
-    for (int i = 0; i < cfg->n_kernels; ++i) h->d.ks[i] = cfg->kernel_size[i];
-    if (hipGetDevice(&h->device) != hipSuccess) h->device = -1;   // no GPU: sections/tables still usable
-    else {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess && cus > 0) h->max_wgs = cus;
-    }
     build_sections(h);
-    build_tables(h);
     *out = h;
     return FE_OK;
 }
@@ -1007,7 +1032,7 @@ void fe_destroy(fe_handle* h) {
     if (h->tb_prog_dev) (void)hipFree(h->tb_prog_dev);
     if (h->tb_work_dev) (void)hipFree(h->tb_work_dev);
     if (h->spec_ring_dev) (void)hipFree(h->spec_ring_dev);
-    if (h->bsplit_dev) (void)hipFree(h->bsplit_dev);
+    if (h->sb_dev) (void)hipFree(h->sb_dev);
     if (h->bsync_dev) (void)hipFree(h->bsync_dev);
     for (hipStream_t s : h->host_streams) if (s) (void)hipStreamDestroy(s);
     for (hipEvent_t e : h->host_events) if (e) (void)hipEventDestroy(e);
@@ -1044,7 +1069,8 @@ int fe_load_weights(fe_handle* h, const float* blob_dev, size_t nfloats, void* s
     FE_HIP_CHECK(hipMemcpyAsync(blob.data(), blob_dev, nfloats * sizeof(float), hipMemcpyDeviceToHost, st));
     FE_HIP_CHECK(hipStreamSynchronize(st));
     std::vector<float> packed;
-    int rc = h->limpl ? pack_weights_lisennet(h, blob, &packed) : h->fimpl ? pack_weights_fspen(h, blob, &packed) : (h->bimpl ? pack_weights_bsrnn(h, blob, &packed) : pack_weights(h, blob, &packed));
+    int rc = FE_OK;
+    if (!visit_baseline(h->cfg.arch, [&](auto F) { rc = F.pack_weights(h, blob, &packed); })) rc = pack_weights(h, blob, &packed);
     if (rc != FE_OK) return rc;
     if (h->packed_dev) { FE_HIP_CHECK(hipFree(h->packed_dev)); h->packed_dev = nullptr; }
     FE_HIP_CHECK(hipMalloc(&h->packed_dev, packed.size() * sizeof(float)));
@@ -1059,34 +1085,24 @@ int fe_load_weights(fe_handle* h, const float* blob_dev, size_t nfloats, void* s
 // time_kernel variant: floats of the causal convs' frame caches per stream (2 NL layers x [KT-1][F1][C1])
 static size_t tk_floats(const fe_handle* h) {
     const Dims& d = h->d;
-    return (h->bimpl || h->fimpl || h->limpl) ? 0 : (size_t)2 * d.NL * (d.KT - 1) * d.F1 * d.C1;
+    return (size_t)2 * d.NL * (d.KT - 1) * d.F1 * d.C1;
 }
 
 size_t fe_state_floats(const fe_handle* h, int B) {
     if (!h || B <= 0) return 0;
     const Dims& d = h->d;
-    if (h->limpl) return (size_t)B * (2 * (size_t)(d.NFFT - d.HOP) + h->limpl->cache_floats);
-    if (h->fimpl) return (size_t)B * 2 * (size_t)(d.NFFT - d.HOP) + fspen_gru_floats(B);
-    if (h->bimpl) return (size_t)B * 2 * (size_t)(d.NFFT - d.HOP) + bsrnn_lstm_floats(h, B);
+    size_t n = 0;
+    if (visit_baseline(h->cfg.arch, [&](auto F) { n = (size_t)B * 2 * (size_t)(d.NFFT - d.HOP) + F.state_floats(h, B); })) return n;
     return (size_t)B * (2 * (size_t)(d.NFFT - d.HOP) + d.hstate() + tk_floats(h));
 }
 
 int fe_state_init(fe_handle* h, float* state_dev, int B, void* stream) {
     if (!h || !state_dev || B <= 0) return fail(FE_ERR_INVALID_ARG, "bad argument");
     FE_HIP_CHECK(hipMemsetAsync(state_dev, 0, fe_state_floats(h, B) * sizeof(float), (hipStream_t)stream));
-    if (h->bimpl) {                // (the scratch of the three-launch per-hop step: sized here, so that the steps of this batch allocate nothing)
-        const int rc = ensure_bsplit(h, B);
-        if (rc != FE_OK) return rc;
-    }
-    if (h->fimpl) {
-        const int rc = ensure_fsplit(h, B);
-        if (rc != FE_OK) return rc;
-    }
-    if (h->limpl) {
-        const int rc = ensure_lsplit(h, B);
-        if (rc != FE_OK) return rc;
-    }
-    return FE_OK;
+    // (the scratch of the stream-batched per-hop step: sized here, so that the steps of this batch allocate nothing)
+    int rc = FE_OK;
+    visit_baseline(h->cfg.arch, [&](auto F) { rc = F.ensure_sb(h, B); });
+    return rc;
 }
 
 static int run_step(fe_handle* h, const float* wav_in, size_t in_stride, float* state, float* wav_out, size_t out_stride,
@@ -1098,39 +1114,18 @@ static int run_step(fe_handle* h, const float* wav_in, size_t in_stride, float* 
     const Dims& d = h->d;
     if (in_stride < (size_t)T * d.HOP && B > 1) return fail(FE_ERR_INVALID_ARG, "in_stride %zu < T*H", in_stride);
     if (out_stride < (size_t)T * d.HOP && B > 1) return fail(FE_ERR_INVALID_ARG, "out_stride %zu < T*H", out_stride);
-    if (h->limpl) {
-        fe::LArgs la = lisennet_args(h, B, T);
-        la.clk = clk;
-        la.dbg = dbg;
-        la.dbg_stride = h->limpl->dbg_floats;
-        const size_t ovl_b = (size_t)(d.NFFT - d.HOP);
-        la.mode = fe::FE_MODE_STREAM;
-        la.wav_in = wav_in; la.wav_out = wav_out; la.in_stride = in_stride; la.out_stride = out_stride;
-        la.cache_stft = state; la.cache_istft = state + (size_t)B * ovl_b; la.cache = state + 2 * (size_t)B * ovl_b;
-        return launch_lisennet(h, la, stream);
-    }
-    if (h->fimpl) {
-        fe::FArgs fa = fspen_args(h, B, T);
-        fa.clk = clk;
-        fa.dbg = dbg;
-        fa.dbg_stride = h->fimpl->dbg_floats;
-        const size_t ovl_b = (size_t)(d.NFFT - d.HOP);
-        fa.mode = fe::FE_MODE_STREAM;
-        fa.wav_in = wav_in; fa.wav_out = wav_out; fa.in_stride = in_stride; fa.out_stride = out_stride;
-        fa.cache_stft = state; fa.cache_istft = state + (size_t)B * ovl_b; fa.gru = state + 2 * (size_t)B * ovl_b;
-        return launch_fspen(h, fa, stream);
-    }
-    if (h->bimpl) {
-        fe::BArgs ba = bsrnn_args(h, B, T);
-        ba.clk = clk;
-        ba.dbg = dbg;
-        ba.dbg_stride = h->bimpl->dbg_floats;
-        const size_t ovl_b = (size_t)(d.NFFT - d.HOP);
-        ba.mode = fe::FE_MODE_STREAM;
-        ba.wav_in = wav_in; ba.wav_out = wav_out; ba.in_stride = in_stride; ba.out_stride = out_stride;
-        ba.cache_stft = state; ba.cache_istft = state + (size_t)B * ovl_b; ba.lstm = state + 2 * (size_t)B * ovl_b;
-        return launch_bsrnn(h, ba, stream);
-    }
+    if (visit_baseline(h->cfg.arch, [&](auto F) {
+            auto a = F.args(h, B, T);
+            a.clk = clk;
+            a.dbg = dbg;
+            a.dbg_stride = F.impl(h)->dbg_floats;
+            const size_t ovl = (size_t)(d.NFFT - d.HOP);
+            a.mode = fe::FE_MODE_STREAM;
+            a.wav_in = wav_in; a.wav_out = wav_out; a.in_stride = in_stride; a.out_stride = out_stride;
+            a.cache_stft = state; a.cache_istft = state + (size_t)B * ovl; F.state(a) = state + 2 * (size_t)B * ovl;
+            rc = F.launch(h, a, stream);
+        }))
+        return rc;
     if (d.BD) return fail(FE_ERR_UNSUPPORTED_CONFIG, "the noncausal model has no streaming step (models/fastenhancer/noncausal/model.py has the offline Model only): use fe_offline");
     rc = ensure_scratch(h, B);
     if (rc != FE_OK) return rc;
@@ -1158,8 +1153,7 @@ static int run_step(fe_handle* h, const float* wav_in, size_t in_stride, float* 
         im = h->impl_many;
     h->last_shape = im->name;
     im->launch(a, h->max_wgs, (hipStream_t)stream, &e);
-    if (e != hipSuccess) return fail(FE_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-    return FE_OK;
+    return launch_rc(e);
 }
 
 int fe_step(fe_handle* h, const float* wav_in_dev, size_t in_stride, float* state_dev, float* wav_out_dev, size_t out_stride,
@@ -1244,17 +1238,6 @@ static int pipe_width(const fe_handle* h, int B, int T, bool offline = false, bo
     return p < T ? p : T;
 }
 
-// BSRNN: frames in flight per utterance of a time-pipelined offline launch (0: one workgroup walks the frames).  A hand-off chain
-// (wait, fetch, gate GEMM, publish) is ~1/40 of a frame, so every co-resident workgroup the batch leaves free is worth having.
-static int bsrnn_pipe_width(const fe_handle* h, int B, int T) {
-    if (!h->bimpl || !h->bimpl->launch_pipe || h->pipe_frames == 0 || h->pipe_frames == 1 || T < 4) return 0;
-    int p = (h->max_wgs * h->bimpl->occ) / B;
-    const int want = h->pipe_frames < 0 ? 64 : h->pipe_frames;
-    p = p < want ? p : want;
-    p = p < T ? p : T;
-    return p >= 2 ? p : 0;
-}
-
 int fe_set_time_pipeline(fe_handle* h, int frames_in_flight) {
     if (!h) return fail(FE_ERR_INVALID_ARG, "bad argument");
     // The per-frame rings in work_dev (time_kernel inputs, dptransformer K / V, LiSenNet caches) are sized for at most kMaxPipeFrames
@@ -1283,24 +1266,13 @@ int fe_spec_step(fe_handle* h, const float* spec_in_dev, float* h_dev, float* sp
     if (rc != FE_OK) return rc;
     KernelLogScope klog_(h);
     if (!spec_in_dev || !h_dev || !spec_out_dev || B <= 0 || T <= 0) return fail(FE_ERR_INVALID_ARG, "bad argument");
-    if (h->limpl) {
-        fe::LArgs la = lisennet_args(h, B, T);
-        la.mode = fe::FE_MODE_SPEC;
-        la.spec_in = spec_in_dev; la.spec_out = spec_out_dev; la.cache = h_dev;
-        return launch_lisennet(h, la, stream);
-    }
-    if (h->fimpl) {
-        fe::FArgs fa = fspen_args(h, B, T);
-        fa.mode = fe::FE_MODE_SPEC;
-        fa.spec_in = spec_in_dev; fa.spec_out = spec_out_dev; fa.gru = h_dev;
-        return launch_fspen(h, fa, stream);
-    }
-    if (h->bimpl) {
-        fe::BArgs ba = bsrnn_args(h, B, T);
-        ba.mode = fe::FE_MODE_SPEC;
-        ba.spec_in = spec_in_dev; ba.spec_out = spec_out_dev; ba.lstm = h_dev;
-        return launch_bsrnn(h, ba, stream);
-    }
+    if (visit_baseline(h->cfg.arch, [&](auto F) {
+            auto a = F.args(h, B, T);
+            a.mode = fe::FE_MODE_SPEC;
+            a.spec_in = spec_in_dev; a.spec_out = spec_out_dev; F.state(a) = h_dev;
+            rc = F.launch(h, a, stream);
+        }))
+        return rc;
     if (h->d.BD) return fail(FE_ERR_UNSUPPORTED_CONFIG, "the noncausal model has no spec -> spec step with caches (models/fastenhancer/noncausal/model.py has the offline Model only): use fe_offline");
     if (use_tb_spec(h, B, T)) {
         // the chunk as one encoder pass, per block a scan that starts from the caller's GRU state and leaves the new one + a tile pass,
@@ -1374,8 +1346,7 @@ int fe_spec_step(fe_handle* h, const float* spec_in_dev, float* h_dev, float* sp
         }
     } else
     h->impl->launch(a, h->max_wgs, (hipStream_t)stream, &e);
-    if (e != hipSuccess) return fail(FE_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-    return FE_OK;
+    return launch_rc(e);
 }
 
 // floats of the time-batched engine's work buffer: xc | skip | x | gx | hs | frames | carried GRU state, each a multiple of 4 floats
@@ -1512,8 +1483,7 @@ static int tb_run(fe_handle* h, fe::tb::TbArgs a0, float* work_dev, int B, int T
             FE_HIP_CHECK(hipStreamWaitEvent(st, h->tb_events[1 + s], 0));
         }
     }
-    if (e != hipSuccess) return fail(FE_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-    return FE_OK;
+    return launch_rc(e);
 }
 
 // FE_OFFLINE_AUTO: the time-batched engine, except for the big shapes (M, L and their 48 kHz forms: block weights streamed from L2,
@@ -1600,47 +1570,31 @@ static int offline_tb(fe_handle* h, const float* noisy_dev, size_t in_stride, co
     if (rc != FE_OK) return rc;
     size_t off[7];
     tb_work_floats(h, B, T, off);
-    a.frames = work_dev + off[5];
-    const int n_out = d.HOP * (T - 1);
-    fe::note_kernel("istft_ola_kernel");
-        hipLaunchKernelGGL(fe::istft_ola_kernel, dim3((n_out + fe::kThreads - 1) / fe::kThreads, B), dim3(fe::kThreads), 0, st,
-                       a.frames, h->tables_dev, wav_hat_dev, out_stride, d.NFFT, d.HOP, T, Tw_b_dev);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(FE_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-    return FE_OK;
+    return ola(h, work_dev + off[5], wav_hat_dev, out_stride, B, T, st, Tw_b_dev);
 }
 
 size_t fe_offline_work_floats(const fe_handle* h, int B, int Tw) {
     if (!h || B <= 0 || Tw <= 0) return 0;
     const Dims& d = h->d;
+    const int T = 1 + Tw / d.HOP;
+    size_t n = 0;
+    if (visit_baseline(h->cfg.arch, [&](auto F) {
+            n = baseline_zeroed_floats(F, h, B) + (size_t)B * T * d.NFFT + (size_t)B * F.ring_floats(h);
+        }))
+        return n;
     if (h->impl && h->impl->tb) {
         // Sized for the engine the CURRENT fe_set_offline_engine setting selects (FastEnhancer_L x 16 x 4 s: the time-batched buffers are
         // 3 GB against the frame walk's 25 MB), and MONOTONE in B under that setting: a buffer sized for B serves every batch of at most B
         // utterances of at most Tw samples.  Under AUTO the big shapes walk from 8 utterances on but take the time-batched engine below
         // that, so their size covers the time-batched need of min(B, 7) as well.  After fe_set_offline_engine: query again (header).
-        const int T = 1 + Tw / d.HOP;
         const size_t walk = d.BD ? 0 : (size_t)B * ((size_t)(d.NFFT - d.HOP) + d.hstate() + tk_floats(h)) + (((size_t)B * d.KB + 3) & ~(size_t)3) + (size_t)B * T * d.NFFT;
         if (d.BD || use_tb_offline(h, B)) return std::max(walk, tb_work_floats(h, B, T, nullptr));
         if (h->offline_engine == FE_OFFLINE_AUTO) return std::max(walk, tb_work_floats(h, std::min(B, kAutoWalkFrom - 1), T, nullptr));
         return walk;
     }
-    if (h->limpl) {     // tail + caches, and the time pipeline's counters, windowed frames and cache ring (widest pipeline: 64 + 2 slots)
-        const int T = 1 + Tw / d.HOP;
-        const size_t cf = (size_t)B * h->limpl->cache_floats;
-        return (size_t)B * (size_t)(d.NFFT - d.HOP) + ((cf + 3) & ~(size_t)3) + (((size_t)B * h->limpl->nsite + 3) & ~(size_t)3) + (size_t)B * T * d.NFFT + (size_t)B * 66 * h->limpl->cache_floats;
-    }
-    if (h->fimpl) {     // tail + inter-GRU states, and the time pipeline's frame counters + windowed frames
-        const int T = 1 + Tw / d.HOP;
-        return (size_t)B * (size_t)(d.NFFT - d.HOP) + ((fspen_gru_floats(B) + 3) & ~(size_t)3) + (((size_t)B * h->fimpl->num_blocks + 3) & ~(size_t)3) + (size_t)B * T * d.NFFT;
-    }
-    if (h->bimpl) {     // overlap-add tail + LSTM states, and - whatever fe_set_time_pipeline says at call time - the frame counters and the windowed frames
-        const int T = 1 + Tw / d.HOP;
-        return (size_t)B * (size_t)(d.NFFT - d.HOP) + ((bsrnn_lstm_floats(h, B) + 3) & ~(size_t)3) + (((size_t)B * h->cfg.rf_blocks + 3) & ~(size_t)3) + (size_t)B * T * d.NFFT;
-    }
     // GRU state (zero initial state, model.py:626-627) + overlap-add tail, both zeroed by fe_offline; time-pipelined
     // launches: + the frame counters [B][KB] and the windowed output frames [B][T][N]
-    size_t n = (size_t)B * ((size_t)(d.NFFT - d.HOP) + d.hstate() + tk_floats(h));
-    const int T = 1 + Tw / d.HOP;
+    n = (size_t)B * ((size_t)(d.NFFT - d.HOP) + d.hstate() + tk_floats(h));
     // (whatever fe_set_time_pipeline says at the time of THIS call: a buffer sized with the pipeline off must still do when it is on)
     if (h->impl && T >= 4) {
         n += (((size_t)B * (d.KB + (d.KT > 1 ? 2 * d.NL : 0)) + 3) & ~(size_t)3) + (size_t)B * T * d.NFFT;
@@ -1660,128 +1614,13 @@ int fe_offline(fe_handle* h, const float* noisy_dev, int B, int Tw, float* wav_h
     if (Tw <= d.NFFT / 2)   // torch.stft reflect padding needs pad < length
         return fail(FE_ERR_INVALID_ARG, "Tw=%d: reflect padding of n_fft/2=%d needs a longer input", Tw, d.NFFT / 2);
     hipStream_t st = (hipStream_t)stream;
+    if (visit_baseline(h->cfg.arch, [&](auto F) { rc = baseline_offline(F, h, noisy_dev, B, Tw, wav_hat_dev, spec_hat_dev, work_dev, st); })) return rc;
     const int T = 1 + Tw / d.HOP;
     if (use_tb_offline(h, B)) return offline_tb(h, noisy_dev, (size_t)Tw, nullptr, Tw, B, wav_hat_dev, (size_t)d.HOP * (T - 1), spec_hat_dev, work_dev, st);
     {   // zero the state, the tail and the frame counters (not the frames: every element is written)
         size_t nz = (size_t)B * ((size_t)(d.NFFT - d.HOP) + d.hstate() + tk_floats(h));
-        if (h->bimpl) nz = (size_t)B * (size_t)(d.NFFT - d.HOP) + ((bsrnn_lstm_floats(h, B) + 3) & ~(size_t)3) + (((size_t)B * h->cfg.rf_blocks + 3) & ~(size_t)3);
-        else if (h->fimpl) nz = (size_t)B * (size_t)(d.NFFT - d.HOP) + ((fspen_gru_floats(B) + 3) & ~(size_t)3) + (((size_t)B * h->fimpl->num_blocks + 3) & ~(size_t)3);
-        else if (h->limpl) nz = (size_t)B * (size_t)(d.NFFT - d.HOP) + (((size_t)B * h->limpl->cache_floats + 3) & ~(size_t)3) + (((size_t)B * h->limpl->nsite + 3) & ~(size_t)3);
-        else if (pipe_width(h, B, T, true)) nz += ((size_t)B * (d.KB + (d.KT > 1 ? 2 * d.NL : 0)) + 3) & ~(size_t)3;
+        if (pipe_width(h, B, T, true)) nz += ((size_t)B * (d.KB + (d.KT > 1 ? 2 * d.NL : 0)) + 3) & ~(size_t)3;
         FE_HIP_CHECK(hipMemsetAsync(work_dev, 0, nz * sizeof(float), st));
-    }
-    if (h->limpl) {
-        fe::LArgs la = lisennet_args(h, B, T);
-        la.mode = fe::FE_MODE_OFFLINE;
-        la.Tw = Tw;
-        la.wav_in = noisy_dev; la.in_stride = (size_t)Tw;
-        la.wav_out = wav_hat_dev; la.out_stride = (size_t)d.HOP * (T - 1);
-        la.spec_out = spec_hat_dev;
-        la.cache_istft = work_dev; la.cache_stft = work_dev;
-        la.cache = work_dev + (size_t)B * (d.NFFT - d.HOP);
-        if (h->limpl->launch_pipe && h->pipe_frames != 0 && h->pipe_frames != 1 && T >= 4) {
-            // the frames of an utterance over co-resident workgroups (lisennet_kernels.hip.h, PIPE); refused co-residency: the serial walk
-            int P = (h->max_wgs * h->limpl->occ) / B;
-            const int want = h->pipe_frames < 0 ? 32 : h->pipe_frames;
-            P = P < want ? P : want;
-            P = P < T ? P : T;
-            if (P >= 2) {
-                rc = ensure_tables(h, st);
-                if (rc != FE_OK) return rc;
-                const size_t cf = (size_t)B * h->limpl->cache_floats;
-                float* flags = la.cache + ((cf + 3) & ~(size_t)3);
-                la.pipe_flags = reinterpret_cast<unsigned int*>(flags);
-                la.frames = flags + (((size_t)B * h->limpl->nsite + 3) & ~(size_t)3);
-                la.ring = la.frames + (size_t)B * T * d.NFFT;
-                la.pipe_p = P;
-                hipError_t e = hipSuccess;
-                h->limpl->launch_pipe(la, st, &e);
-                if (e == hipSuccess) {
-                    const int n_out = d.HOP * (T - 1);
-                    fe::note_kernel("istft_ola_kernel");
-        hipLaunchKernelGGL(fe::istft_ola_kernel, dim3((n_out + fe::kThreads - 1) / fe::kThreads, B), dim3(fe::kThreads), 0, st,
-                                       la.frames, h->tables_dev, wav_hat_dev, (size_t)n_out, d.NFFT, d.HOP, T);
-                    e = hipGetLastError();
-                    if (e != hipSuccess) return fail(FE_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-                    return FE_OK;
-                }
-                (void)hipGetLastError();
-                la.pipe_flags = nullptr; la.frames = nullptr; la.ring = nullptr; la.pipe_p = 0;
-            }
-        }
-        return launch_lisennet(h, la, stream);
-    }
-    if (h->fimpl) {
-        fe::FArgs fa = fspen_args(h, B, T);
-        fa.mode = fe::FE_MODE_OFFLINE;
-        fa.Tw = Tw;
-        fa.wav_in = noisy_dev; fa.in_stride = (size_t)Tw;
-        fa.wav_out = wav_hat_dev; fa.out_stride = (size_t)d.HOP * (T - 1);
-        fa.spec_out = spec_hat_dev;
-        fa.cache_istft = work_dev; fa.cache_stft = work_dev;
-        fa.gru = work_dev + (size_t)B * (d.NFFT - d.HOP);
-        if (h->fimpl->launch_pipe && h->pipe_frames != 0 && h->pipe_frames != 1 && T >= 4) {
-            // the frames of an utterance over co-resident workgroups (fspen_kernels.hip.h, PIPE); refused co-residency: the serial walk
-            int P = (h->max_wgs * h->fimpl->occ) / B;
-            const int want = h->pipe_frames < 0 ? 32 : h->pipe_frames;
-            P = P < want ? P : want;
-            P = P < T ? P : T;
-            if (P >= 2) {
-                rc = ensure_tables(h, st);
-                if (rc != FE_OK) return rc;
-                float* flags = fa.gru + ((fspen_gru_floats(B) + 3) & ~(size_t)3);
-                fa.pipe_flags = reinterpret_cast<unsigned int*>(flags);
-                fa.frames = flags + (((size_t)B * h->fimpl->num_blocks + 3) & ~(size_t)3);
-                fa.pipe_p = P;
-                hipError_t e = hipSuccess;
-                h->fimpl->launch_pipe(fa, st, &e);
-                if (e == hipSuccess) {
-                    const int n_out = d.HOP * (T - 1);
-                    fe::note_kernel("istft_ola_kernel");
-        hipLaunchKernelGGL(fe::istft_ola_kernel, dim3((n_out + fe::kThreads - 1) / fe::kThreads, B), dim3(fe::kThreads), 0, st,
-                                       fa.frames, h->tables_dev, wav_hat_dev, (size_t)n_out, d.NFFT, d.HOP, T);
-                    e = hipGetLastError();
-                    if (e != hipSuccess) return fail(FE_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-                    return FE_OK;
-                }
-                (void)hipGetLastError();
-                fa.pipe_flags = nullptr; fa.frames = nullptr; fa.pipe_p = 0;
-            }
-        }
-        return launch_fspen(h, fa, stream);
-    }
-    if (h->bimpl) {
-        fe::BArgs ba = bsrnn_args(h, B, T);
-        ba.mode = fe::FE_MODE_OFFLINE;
-        ba.Tw = Tw;
-        ba.wav_in = noisy_dev; ba.in_stride = (size_t)Tw;
-        ba.wav_out = wav_hat_dev; ba.out_stride = (size_t)d.HOP * (T - 1);
-        ba.spec_out = spec_hat_dev;
-        ba.cache_istft = work_dev; ba.cache_stft = work_dev;
-        ba.lstm = work_dev + (size_t)B * (d.NFFT - d.HOP);
-        if (const int P = bsrnn_pipe_width(h, B, T)) {
-            // the frames of an utterance over P co-resident workgroups (bsrnn_kernels.hip.h, PIPE); refused co-residency: the serial walk
-            rc = ensure_tables(h, st);
-            if (rc != FE_OK) return rc;
-            float* flags = ba.lstm + ((bsrnn_lstm_floats(h, B) + 3) & ~(size_t)3);
-            ba.pipe_flags = reinterpret_cast<unsigned int*>(flags);
-            ba.frames = flags + (((size_t)B * h->cfg.rf_blocks + 3) & ~(size_t)3);
-            ba.pipe_p = P;
-            hipError_t e = hipSuccess;
-            h->bimpl->launch_pipe(ba, st, &e);
-            if (e == hipSuccess) {
-                const int n_out = d.HOP * (T - 1);
-                fe::note_kernel("istft_ola_kernel");
-        hipLaunchKernelGGL(fe::istft_ola_kernel, dim3((n_out + fe::kThreads - 1) / fe::kThreads, B), dim3(fe::kThreads), 0, st,
-                                   ba.frames, h->tables_dev, wav_hat_dev, (size_t)n_out, d.NFFT, d.HOP, T);
-                e = hipGetLastError();
-                if (e != hipSuccess) return fail(FE_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-                return FE_OK;
-            }
-            (void)hipGetLastError();
-            ba.pipe_flags = nullptr; ba.frames = nullptr; ba.pipe_p = 0;
-        }
-        return launch_bsrnn(h, ba, stream);
     }
     rc = ensure_scratch(h, B);
     if (rc != FE_OK) return rc;
@@ -1819,20 +1658,12 @@ int fe_offline(fe_handle* h, const float* noisy_dev, int B, int Tw, float* wav_h
             a.tk = tk_serial;
             a.h = h_serial;
             h->impl->launch(a, h->max_wgs, st, &e);
-            if (e != hipSuccess) return fail(FE_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-            return FE_OK;
+            return launch_rc(e);
         }
-        const int n_out = d.HOP * (T - 1);
-        fe::note_kernel("istft_ola_kernel");
-        hipLaunchKernelGGL(fe::istft_ola_kernel, dim3((n_out + fe::kThreads - 1) / fe::kThreads, B), dim3(fe::kThreads), 0, st,
-                           a.frames, h->tables_dev, wav_hat_dev, (size_t)n_out, d.NFFT, d.HOP, T);
-        e = hipGetLastError();
-        if (e != hipSuccess) return fail(FE_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-        return FE_OK;
+        return ola(h, a.frames, wav_hat_dev, (size_t)d.HOP * (T - 1), B, T, st);
     }
     h->impl->launch(a, h->max_wgs, st, &e);
-    if (e != hipSuccess) return fail(FE_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-    return FE_OK;
+    return launch_rc(e);
 }
 
 // ---------------------------------------------------------------------------- stand-alone STFT / iSTFT
@@ -1870,7 +1701,7 @@ static fe::StftArgs stft_args(const fe_handle* h, int B) {
 }
 
 // spec_hat rows of an offline call: N/2 (FastEnhancer: the model drops the Nyquist bin) or N/2 + 1 (BSRNN / FSPEN / LiSenNet)
-static int offline_spec_rows(const fe_handle* h) { return h->d.NFFT / 2 + ((h->bimpl || h->fimpl || h->limpl) ? 1 : 0); }
+static int offline_spec_rows(const fe_handle* h) { return h->d.NFFT / 2 + (h->cfg.arch == FE_ARCH_FASTENHANCER ? 0 : 1); }
 
 // A ragged batch has ONE batched form: the time-batched engine (the frame walk and its time pipeline take one length per launch).  It is
 // taken whenever the model has that engine and the caller has not asked for the frame walk - also for the big shapes at 8+ utterances,
@@ -1985,58 +1816,14 @@ int fe_istft_offline(fe_handle* h, const float* spec_in_dev, int B, int T, int F
     a.spec = const_cast<float*>(spec_in_dev); a.frames = frames_dev;
     a.compression = compress ? h->cfg.input_compression : 1.0f;
     FE_STFT_LAUNCH(istft_frames_kernel, a, dim3(T, B), st);
-    const int n_out = H * (T - 1);
-    fe::note_kernel("istft_ola_kernel");
-        hipLaunchKernelGGL(fe::istft_ola_kernel, dim3((n_out + fe::kThreads - 1) / fe::kThreads, B), dim3(fe::kThreads), 0, st,
-                       frames_dev, h->tables_dev, wav_out_dev, (size_t)n_out, N, H, T);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(FE_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-    return FE_OK;
+    return ola(h, frames_dev, wav_out_dev, (size_t)H * (T - 1), B, T, st);
 }
 
 double fe_flops_per_frame(const fe_handle* h) {
     if (!h) return 0.0;
     const Dims& d = h->d;
-    if (h->limpl) {   // models/lisennet/macs.py:8-66 with T = 1
-        const double C = 16, Nb = 2, F1 = 257;
-        double m = 3 * (C / 4) * F1;
-        const double co[3] = {C / 2, C / 4 * 3, C}, fi[3] = {257, 128, 64};
-        for (int i = 0; i < 3; ++i) {
-            const double f = fi[i], fq = std::floor(f / 4), fhi = std::floor((f - fq + 2 - 5) / 3) + 1;
-            m += (2 * 3 * fq + 2 * 5 * fhi) * co[i] * co[i];
-        }
-        auto gru = [](double i, double hd) { return (i + hd) * hd * 3 + hd * 3; };
-        const double hh = 24, ff = 32;
-        for (int b = 0; b < (int)Nb; ++b) {
-            m += (gru(C, hh / 2) * 2 + hh * C + gru(C, hh) + hh * C) * ff;
-            m += (C * C * 4 + C * 2 * 3 + C * 2 + C * 2 * C) * ff;
-        }
-        double c_in = C, f = 32, c_out = 0;
-        for (double c_o : {C / 4 * 3, C / 2, C / 4}) { c_out = c_o; m += (3 * (f / 2) + 3 * 3 * (f / 2)) * c_in * 2 * c_out; c_in = c_out; f *= 2; }
-        f += 1;
-        m += (c_out * 2 * 2 * 2 + 2 * 2 + 2 * 2) * f;
-        return 2.0 * m + 2.0 * 2.5 * d.NFFT * std::log2((double)d.NFFT);
-    }
-    if (h->fimpl) {   // models/fspen/macs.py:36-141 with T = 1 (switches as committed: conv output lengths, no BN / LN / bias terms)
-        const double C1[3] = {4, 16, 32}, K[3] = {6, 8, 6}, C2 = 16;
-        double F = 257, m = 0;
-        for (int i = 0; i < 3; ++i) { F = std::floor(F / 2); m += (i == 0 ? 2 : C1[i - 1]) * C1[i] * F * K[i]; }
-        m += 32 * 32 * F + 32 * (4 * 8 + 7 * 6 + 11 * 6 + 20 * 6 + 40 * 6) + 32 * 64 * 32 + 32 * C2 * 32;
-        const double gru = (C2 + C2) * C2 * 3 + C2 * 3;
-        m += 3 * (gru * 2 + 2 * C2 * C2 + C2 + gru + C2 * C2 + C2) * 32;
-        m += C2 * 32 * 32 + 32 * 32 * 64 + 32 * (8 * 2 + 6 * 3 + 8 * 5 + 8 * 10 + 8 * 20);
-        for (int i = 2; i >= 0; --i) { m += C1[i] * (i == 0 ? 2 : C1[i - 1]) * F * K[i]; F = i == 0 ? F * 2 + 1 : F * 2; }
-        m += 257 * 8;
-        return 2.0 * m + 2.0 * 2.5 * d.NFFT * std::log2((double)d.NFFT);
-    }
-    if (h->bimpl) {   // models/bsrnn/macs.py:18-51
-        const double C = h->cfg.channels, Hh = 2 * C, Lr = h->cfg.rf_blocks;
-        double m = 0;
-        for (int b = 0; b < 31; ++b) m += 2 * kSub[b] * C;
-        m += (C * Hh * 4 + Hh * Hh * 4 + Hh * C + (C * Hh * 4 + Hh * Hh * 4) * 2 + 2 * Hh * C) * 31 * Lr;
-        for (int b = 0; b < 31; ++b) m += (C * C * 4 + 4 * C * 4 * kSub[b]) * 2;
-        return 2.0 * m + 2.0 * 2.5 * d.NFFT * std::log2((double)d.NFFT);
-    }
+    double macs = 0;
+    if (visit_baseline(h->cfg.arch, [&](auto F) { macs = F.macs(h); })) return 2.0 * macs + 2.0 * 2.5 * d.NFFT * std::log2((double)d.NFFT);
     const double C1 = d.C1, C2 = d.C2, F1 = d.F1, F2 = d.F2, K = d.KB;
     const double KT = d.KT;
     double m = 2 * C1 * 8 * F1;
@@ -2056,71 +1843,46 @@ double fe_flops_per_frame(const fe_handle* h) {
     return 2.0 * m + 2.0 * 2.5 * d.NFFT * std::log2((double)d.NFFT);
 }
 
-int fe_debug_stages(const fe_handle* h) { return !h ? 0 : h->limpl ? h->limpl->dbg_stages : h->fimpl ? h->fimpl->dbg_stages : (h->bimpl ? h->bimpl->dbg_stages : (h->impl ? h->impl->dbg_stages : 0)); }
-size_t fe_debug_floats(const fe_handle* h) { return !h ? 0 : h->limpl ? h->limpl->dbg_floats : h->fimpl ? h->fimpl->dbg_floats : (h->bimpl ? h->bimpl->dbg_floats : (h->impl ? h->impl->dbg_floats : 0)); }
+int fe_debug_stages(const fe_handle* h) {
+    if (!h) return 0;
+    int n = h->impl ? h->impl->dbg_stages : 0;
+    visit_baseline(h->cfg.arch, [&](auto F) { n = F.impl(h)->dbg_stages; });
+    return n;
+}
+
+size_t fe_debug_floats(const fe_handle* h) {
+    if (!h) return 0;
+    size_t n = h->impl ? h->impl->dbg_floats : 0;
+    visit_baseline(h->cfg.arch, [&](auto F) { n = F.impl(h)->dbg_floats; });
+    return n;
+}
 
 int fe_debug_stage(const fe_handle* h, int idx, const char** name, int* rows, int* cols, size_t* offset_floats) {
     if (!h || idx < 0 || idx >= fe_debug_stages(h)) return fail(FE_ERR_INVALID_ARG, "stage index %d", idx);
-    static thread_local std::string nm;
-    if (h->limpl) {
-        static const char* const names[16] = {"spec_in", "compressed", "features", "encoder.conv_1", "encoder.conv_2", "encoder.conv_3", "encoder.conv_4",
-                                              "blocks.0.intra", "blocks.0.inter", "blocks.0", "blocks.1.intra", "blocks.1.inter", "blocks.1",
-                                              "decoder.up3", "mask", "spec_out"};
-        int r, c; size_t off;
-        h->limpl->dbg_stage(idx, &r, &c, &off);
-        if (name) *name = names[idx];
-        if (rows) *rows = r;
-        if (cols) *cols = c;
-        if (offset_floats) *offset_floats = off;
-        return FE_OK;
-    }
-    if (h->fimpl) {
-        static const char* const names[16] = {"spec_in", "compressed", "subband_encoder", "fullband_encoder.2", "feature_merge", "dpe.0.intra",
-                                              "dpe.0.inter", "dpe.1.intra", "dpe.1.inter", "dpe.2.intra", "dpe.2.inter", "feature_split",
-                                              "fullband_decoder.0", "fullband_decoder.1", "mask", "spec_out"};
-        int r, c; size_t off;
-        h->fimpl->dbg_stage(idx, &r, &c, &off);
-        if (name) *name = names[idx];
-        if (rows) *rows = r;
-        if (cols) *cols = c;
-        if (offset_floats) *offset_floats = off;
-        return FE_OK;
-    }
-    if (h->bimpl) {   // spec_in, compressed, band_split, (layer.l.time, layer.l.freq)..., mask_mlp, spec_out
-        const int L = h->cfg.rf_blocks;
-        char bufn[64];
-        if (idx == 0) nm = "spec_in";
-        else if (idx == 1) nm = "compressed";
-        else if (idx == 2) nm = "band_split";
-        else if (idx < 3 + 2 * L) { snprintf(bufn, sizeof bufn, (idx - 3) % 2 == 0 ? "layer.%d.time" : "layer.%d.freq", (idx - 3) / 2); nm = bufn; }
-        else if (idx == 3 + 2 * L) nm = "mask_mlp";
+    int r, c;
+    size_t off;
+    const char* stage = nullptr;
+    if (!visit_baseline(h->cfg.arch, [&](auto F) { stage = F.stage_name(h, idx); F.impl(h)->dbg_stage(idx, &r, &c, &off); })) {
+        static thread_local std::string nm;
+        const Dims& d = h->d;
+        char buf[64];
+        int s = idx;
+        if (s == 0) nm = "spec_in";
+        else if (s == 1) nm = "compressed";
+        else if (s == 2) nm = "enc_pre";
+        else if (s < 3 + d.NL) { snprintf(buf, sizeof buf, "encoder.%d", s - 3); nm = buf; }
+        else if (s == 3 + d.NL) nm = "rf_pre";
+        else if (s < 4 + d.NL + 2 * d.KB) {
+            int k = (s - 4 - d.NL) / 2, w = (s - 4 - d.NL) % 2;
+            snprintf(buf, sizeof buf, w == 0 ? "rf_block.%d.rnn" : "rf_block.%d", k); nm = buf;
+        } else if (s == 4 + d.NL + 2 * d.KB) nm = "rf_post";
+        else if (s < 5 + 2 * d.NL + 2 * d.KB) { snprintf(buf, sizeof buf, "decoder.%d", s - 5 - d.NL - 2 * d.KB); nm = buf; }
+        else if (s == 5 + 2 * d.NL + 2 * d.KB) nm = "mask";
         else nm = "spec_out";
-        int r, c; size_t off;
-        h->bimpl->dbg_stage(idx, &r, &c, &off);
-        if (name) *name = nm.c_str();
-        if (rows) *rows = r;
-        if (cols) *cols = c;
-        if (offset_floats) *offset_floats = off;
-        return FE_OK;
+        stage = nm.c_str();
+        h->impl->dbg_stage(idx, &r, &c, &off);
     }
-    const Dims& d = h->d;
-    char buf[64];
-    int s = idx;
-    if (s == 0) nm = "spec_in";
-    else if (s == 1) nm = "compressed";
-    else if (s == 2) nm = "enc_pre";
-    else if (s < 3 + d.NL) { snprintf(buf, sizeof buf, "encoder.%d", s - 3); nm = buf; }
-    else if (s == 3 + d.NL) nm = "rf_pre";
-    else if (s < 4 + d.NL + 2 * d.KB) {
-        int k = (s - 4 - d.NL) / 2, w = (s - 4 - d.NL) % 2;
-        snprintf(buf, sizeof buf, w == 0 ? "rf_block.%d.rnn" : "rf_block.%d", k); nm = buf;
-    } else if (s == 4 + d.NL + 2 * d.KB) nm = "rf_post";
-    else if (s < 5 + 2 * d.NL + 2 * d.KB) { snprintf(buf, sizeof buf, "decoder.%d", s - 5 - d.NL - 2 * d.KB); nm = buf; }
-    else if (s == 5 + 2 * d.NL + 2 * d.KB) nm = "mask";
-    else nm = "spec_out";
-    int r, c; size_t off;
-    h->impl->dbg_stage(idx, &r, &c, &off);
-    if (name) *name = nm.c_str();
+    if (name) *name = stage;
     if (rows) *rows = r;
     if (cols) *cols = c;
     if (offset_floats) *offset_floats = off;

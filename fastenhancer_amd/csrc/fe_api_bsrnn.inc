@@ -1,6 +1,29 @@
-// fe_api_bsrnn.inc - host side of the BSRNN family: weight sections, handle creation, packer (included by fe_api.hip inside its anonymous namespace)
+// fe_api_bsrnn.inc - host side of the BSRNN family: weight sections, handle creation, packer, launch (included by fe_api.hip inside its anonymous namespace)
 // ============================================================================ BSRNN (models/bsrnn/model.py)
 const int kSub[31] = {2, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 16, 16, 16, 16, 16, 16, 16, 17};
+
+// The family as fe_api.hip's shared baseline-family paths see it (visit_baseline: the stream and spec steps, offline, the buffer sizes, debug stages)
+struct BsrnnFamily {
+    using Args = fe::BArgs;
+    static const fe::BImpl* impl(const fe_handle* h) { return h->bimpl; }
+    static const char* shape_name(const fe_handle* h) { return h->bimpl->name; }
+    static float*& state(Args& a) { return a.lstm; }
+    static size_t state_floats(const fe_handle* h, int B) { return (size_t)2 * h->cfg.rf_blocks * B * 31 * 2 * h->cfg.channels; }
+    static size_t counters(const fe_handle* h) { return h->cfg.rf_blocks; }      // time-pipeline frame counters per stream
+    // default frames in flight per utterance of a time-pipelined offline launch: a hand-off chain (wait, fetch, gate GEMM, publish) is ~1/40
+    // of a frame, so every co-resident workgroup the batch leaves free is worth having
+    static constexpr int kPipeFrames = 64;
+    static size_t ring_floats(const fe_handle*) { return 0; }
+    static void set_ring(Args&, float*) {}
+    static size_t xp_floats(const fe_handle* h) { return (size_t)h->max_wgs * h->bimpl->xp_floats; }     // (band-LSTM input projections of C = 64)
+    static Args args(fe_handle* h, int B, int T);
+    static int create(const fe_config* cfg, fe_handle** out);
+    static int pack_weights(fe_handle* h, const std::vector<float>& blob, std::vector<float>* out);
+    static int ensure_sb(fe_handle* h, int B);
+    static int launch(fe_handle* h, const Args& a, void* stream);
+    static const char* stage_name(const fe_handle* h, int idx);
+    static double macs(const fe_handle* h);
+};
 
 void build_sections_bsrnn(fe_handle* h) {
     const int C = h->cfg.channels, L = h->cfg.rf_blocks, HH = 2 * C;
@@ -34,7 +57,7 @@ void build_sections_bsrnn(fe_handle* h) {
         }
 }
 
-int create_bsrnn(const fe_config* cfg, fe_handle** out) {
+int BsrnnFamily::create(const fe_config* cfg, fe_handle** out) {
     if (cfg->n_fft != 512) return fail(FE_ERR_INVALID_ARG, "Only n_fft=512 is supported, but given %d", cfg->n_fft);
     if (cfg->win_size > cfg->n_fft) return fail(FE_ERR_INVALID_ARG, "n_fft(%d) must be bigger than win_size(%d)", cfg->n_fft, cfg->win_size);
     if (cfg->hop_size <= 0 || cfg->hop_size > cfg->n_fft) return fail(FE_ERR_INVALID_ARG, "hop_size %d out of range", cfg->hop_size);
@@ -44,22 +67,14 @@ int create_bsrnn(const fe_config* cfg, fe_handle** out) {
     if (!bi)
         return fail(FE_ERR_UNSUPPORTED_CONFIG, "no BSRNN kernel compiled for num_channels=%d num_layers=%d hop=%d", cfg->channels,
                     cfg->rf_blocks, cfg->hop_size);
-    fe_handle* h = new fe_handle();
-    h->cfg = *cfg;
+    fe_handle* h = new_handle(cfg, Dims{cfg->channels, 0, 0, 0, cfg->rf_blocks, cfg->n_fft, cfg->hop_size, cfg->n_fft / 2, 0, 0, {0}});
     h->bimpl = bi;
-    h->d = Dims{cfg->channels, 0, 0, 0, cfg->rf_blocks, cfg->n_fft, cfg->hop_size, cfg->n_fft / 2, 0, 0, {0}};
-    if (hipGetDevice(&h->device) != hipSuccess) h->device = -1;
-    else {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess && cus > 0) h->max_wgs = cus;
-    }
     build_sections_bsrnn(h);
-    build_tables(h);
     *out = h;
     return FE_OK;
 }
 
-int pack_weights_bsrnn(fe_handle* h, const std::vector<float>& blob, std::vector<float>* out) {
+int BsrnnFamily::pack_weights(fe_handle* h, const std::vector<float>& blob, std::vector<float>* out) {
     const int C = h->cfg.channels, L = h->cfg.rf_blocks, HH = 2 * C, G4 = 4 * HH, R = 4 * 257;
     const bool whh_regs = h->bimpl->whh_regs;
     fe::BOffsets& o = h->boff;
@@ -326,4 +341,85 @@ int pack_weights_bsrnn(fe_handle* h, const std::vector<float>& blob, std::vector
     buf.resize(o.total, 0.0f);
     *out = std::move(buf);
     return FE_OK;
+}
+
+fe::BArgs BsrnnFamily::args(fe_handle* h, int B, int T) {
+    fe::BArgs a{};
+    a.xp_scratch = h->skip_dev;
+    a.wp = h->packed_dev;
+    a.off = h->boff;
+    a.B = B;
+    a.T = T;
+    a.compression = h->cfg.input_compression;
+    return a;
+}
+
+// The per-hop BSRNN step runs as three launches (bsrnn_kernels.hip.h, PART): per stream 31 C floats of band features, 514 of compressed
+// spectrum and 2056 of MLP pre-activations pass through the stream-batched scratch.  Grow-only; fe_state_init sizes it for its batch, so that a
+// steady-state step allocates nothing (FE_BSRNN_SPLIT=0: the fused kernel, for A/B measurements).
+constexpr int kSyncTiles = 64;       // sixteen-stream tiles of a fused BSRNN step (one workgroup per CU: 1024 CUs)
+size_t bsplit_floats_per_stream(const fe_handle* h) {
+    return (size_t)31 * h->cfg.channels + 2 * 257 + 2 * 1028 + (h->bimpl->launch_sb ? (size_t)2 * 31 * 2 * h->cfg.channels : 0);      // (+ the stream-batched layers' y scratch)
+}
+int BsrnnFamily::ensure_sb(fe_handle* h, int B) {
+    // (bsrnn_three_launch_step is 0 or 1: the three-launch step, when it is on, takes the scratch from one stream on)
+    const int rc = ensure_sb_scratch(h, B, h->opt[OPT_BSRNN_THREE_LAUNCH], (size_t)B * bsplit_floats_per_stream(h) * sizeof(float));
+    if (rc != FE_OK || !h->sb_dev || h->bsync_dev) return rc;
+    FE_HIP_CHECK(hipMalloc(&h->bsync_dev, kSyncTiles * 2 * sizeof(unsigned int)));
+    FE_HIP_CHECK(hipMemset(h->bsync_dev, 0, kSyncTiles * 2 * sizeof(unsigned int)));
+    return FE_OK;
+}
+
+int BsrnnFamily::launch(fe_handle* h, const fe::BArgs& a_in, void* stream) {
+    hipError_t e = hipSuccess;
+    fe::BArgs a = a_in;
+    a.ov_off = (h->step_kernel == FE_STEP_KERNEL_WAVES4 || !h->opt[OPT_BSRNN_ROLE_SPLIT]) ? 1 : 0;
+    // (fe_set_option("bsrnn_ov_profile", 1): fe_profile_step probes the role-split PART 1 of the three-launch step instead of the fused kernel's phases)
+    const bool ov_prof = h->opt[OPT_BSRNN_OV_PROFILE] != 0;
+    if (a.mode == fe::FE_MODE_STREAM && a.T == 1 && a.dbg == nullptr && (a.clk == nullptr || (ov_prof && h->cfg.channels == 16 && a.B <= h->max_wgs))) {
+        const int rc = ensure_sb(h, a.B);
+        if (rc != FE_OK) return rc;
+        if (h->sb_dev && a.B <= h->sb_streams) {
+            a.mlp_x = h->sb_dev;
+            a.mlp_sp = a.mlp_x + (size_t)a.B * 31 * h->cfg.channels;
+            a.mlp_pre = a.mlp_sp + (size_t)a.B * 2 * 257;
+            a.sb_y = a.mlp_pre + (size_t)a.B * 2 * 1028;
+            a.gsync = (h->opt[OPT_BSRNN_FUSED] && a.clk == nullptr && (a.B + 15) / 16 <= kSyncTiles) ? h->bsync_dev : nullptr;
+            // large batches: the LSTM layers batched over the streams on the matrix cores (sixteen streams per workgroup) - from the batch
+            // size where sixteen-stream workgroups fill the chip better than one stream per workgroup (FE_BSRNN_SB: that threshold; 0 = never)
+            // (default 2048; measured crossover on 256 CUs: ~1900 streams, profiles/r4c_bsrnn_stream_batched.txt.  num_channels = 64 (r6): a sixteen-stream tile takes 5.8 ms
+            //  whatever the batch and the per-stream kernel 2.3 us per stream - crossover at ~2700 streams: the threshold counts 11 / 8 there)
+            const int sb_opt = h->opt[OPT_BSRNN_SB_MIN];
+            const int sb_min = h->cfg.channels == 64 ? (int)((long long)sb_opt * 11 / 8) : sb_opt;
+            if (h->bimpl->launch_sb && sb_min > 0 && a.B >= sb_min) h->bimpl->launch_sb(a, h->sboff, h->packed_floats, h->max_wgs, (hipStream_t)stream, &e);
+            else
+            h->bimpl->launch_split(a, h->max_wgs, (hipStream_t)stream, &e);
+            return launch_rc(e);
+        }
+    }
+    h->bimpl->launch(a, h->max_wgs, (hipStream_t)stream, &e);
+    return launch_rc(e);
+}
+
+// spec_in, compressed, band_split, (layer.l.time, layer.l.freq)..., mask_mlp, spec_out
+const char* BsrnnFamily::stage_name(const fe_handle* h, int idx) {
+    static thread_local std::string nm;
+    const int L = h->cfg.rf_blocks;
+    char bufn[64];
+    if (idx == 0) nm = "spec_in";
+    else if (idx == 1) nm = "compressed";
+    else if (idx == 2) nm = "band_split";
+    else if (idx < 3 + 2 * L) { snprintf(bufn, sizeof bufn, (idx - 3) % 2 == 0 ? "layer.%d.time" : "layer.%d.freq", (idx - 3) / 2); nm = bufn; }
+    else if (idx == 3 + 2 * L) nm = "mask_mlp";
+    else nm = "spec_out";
+    return nm.c_str();
+}
+
+double BsrnnFamily::macs(const fe_handle* h) {   // models/bsrnn/macs.py:18-51
+    const double C = h->cfg.channels, Hh = 2 * C, Lr = h->cfg.rf_blocks;
+    double m = 0;
+    for (int b = 0; b < 31; ++b) m += 2 * kSub[b] * C;
+    m += (C * Hh * 4 + Hh * Hh * 4 + Hh * C + (C * Hh * 4 + Hh * Hh * 4) * 2 + 2 * Hh * C) * 31 * Lr;
+    for (int b = 0; b < 31; ++b) m += (C * C * 4 + 4 * C * 4 * kSub[b]) * 2;
+    return m;
 }

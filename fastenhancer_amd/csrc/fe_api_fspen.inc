@@ -1,8 +1,29 @@
-// fe_api_fspen.inc - host side of FSPEN: weight sections, handle creation, packer (included by fe_api.hip inside its anonymous namespace)
+// fe_api_fspen.inc - host side of FSPEN: weight sections, handle creation, packer, launch (included by fe_api.hip inside its anonymous namespace)
 // ============================================================================ FSPEN (models/fspen/model.py)
 // fused state_dict of ONNXModel after remove_weight_reparameterizations (:299-340), reference layouts
 const int kSeK[5] = {4, 7, 11, 20, 40};                   // SubbandEncoder kernels (:41-44)
 const int kSdN[5] = {2, 3, 5, 10, 20};                    // SubbandDecoder outputs per row (:70)
+
+// The family as fe_api.hip's shared baseline-family paths see it (visit_baseline: the stream and spec steps, offline, the buffer sizes, debug stages)
+struct FspenFamily {
+    using Args = fe::FArgs;
+    static const fe::FImpl* impl(const fe_handle* h) { return h->fimpl; }
+    static const char* shape_name(const fe_handle*) { return "fspen"; }
+    static float*& state(Args& a) { return a.gru; }
+    static size_t state_floats(const fe_handle*, int B) { return (size_t)B * fe::FShape<256>::CACHE_FLOATS; }
+    static size_t counters(const fe_handle* h) { return h->fimpl->num_blocks; }      // time-pipeline frame counters per stream
+    static constexpr int kPipeFrames = 32;
+    static size_t ring_floats(const fe_handle*) { return 0; }
+    static void set_ring(Args&, float*) {}
+    static size_t xp_floats(const fe_handle*) { return 0; }
+    static Args args(fe_handle* h, int B, int T);
+    static int create(const fe_config* cfg, fe_handle** out);
+    static int pack_weights(fe_handle* h, const std::vector<float>& blob, std::vector<float>* out);
+    static int ensure_sb(fe_handle* h, int B);
+    static int launch(fe_handle* h, const Args& a, void* stream);
+    static const char* stage_name(const fe_handle*, int idx);
+    static double macs(const fe_handle* h);
+};
 
 void build_sections_fspen(fe_handle* h) {
     char nm[160];
@@ -55,7 +76,7 @@ void build_sections_fspen(fe_handle* h) {
     }
 }
 
-int create_fspen(const fe_config* cfg, fe_handle** out) {
+int FspenFamily::create(const fe_config* cfg, fe_handle** out) {
     if (cfg->n_fft != 512) return fail(FE_ERR_INVALID_ARG, "Only n_fft == 512 is allowed, but given %d", cfg->n_fft);
     if (cfg->win_size > cfg->n_fft) return fail(FE_ERR_INVALID_ARG, "n_fft(%d) must be bigger than win_size(%d)", cfg->n_fft, cfg->win_size);
     // the one architecture of configs/others/fspen.yaml: channels [4, 16, 32], kernel_size [6, 8, 6], stride 2, DPE 3 x (16 ch, 32 bands, 8 groups)
@@ -66,23 +87,15 @@ int create_fspen(const fe_config* cfg, fe_handle** out) {
         return fail(FE_ERR_UNSUPPORTED_CONFIG, "no FSPEN kernel compiled for channels[-1]=%d kernels=%d dpe=(%d blocks, %d ch, %d bands, %d groups) hop=%d "
                     "(configs/others/fspen.yaml is the compiled architecture)", cfg->channels, cfg->n_kernels, cfg->rf_blocks, cfg->rf_channels,
                     cfg->rf_freq, cfg->rf_heads, cfg->hop_size);
-    fe_handle* h = new fe_handle();
-    h->cfg = *cfg;
+    fe_handle* h = new_handle(cfg, Dims{32, 0, 16, 32, 3, cfg->n_fft, cfg->hop_size, cfg->n_fft / 2, 0, 0, {0}});
     h->fimpl = fi;
-    h->d = Dims{32, 0, 16, 32, 3, cfg->n_fft, cfg->hop_size, cfg->n_fft / 2, 0, 0, {0}};
-    if (hipGetDevice(&h->device) != hipSuccess) h->device = -1;
-    else {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess && cus > 0) h->max_wgs = cus;
-    }
     build_sections_fspen(h);
-    build_tables(h);
     *out = h;
     return FE_OK;
 }
 
 // k-major repack of the fused weights at the compile-time offsets of fe::FPk (fspen_kernels.hip.h)
-int pack_weights_fspen(fe_handle* h, const std::vector<float>& blob, std::vector<float>* out) {
+int FspenFamily::pack_weights(fe_handle* h, const std::vector<float>& blob, std::vector<float>* out) {
     using P = fe::FPk;
     std::vector<float> buf(P::TOTAL, 0.0f);
     auto S = [&](const std::string& n) { return sec(h, blob, n); };
@@ -327,9 +340,7 @@ int pack_weights_fspen(fe_handle* h, const std::vector<float>& blob, std::vector
     return FE_OK;
 }
 
-size_t fspen_gru_floats(int B) { return (size_t)B * fe::FShape<256>::CACHE_FLOATS; }
-
-fe::FArgs fspen_args(fe_handle* h, int B, int T) {
+fe::FArgs FspenFamily::args(fe_handle* h, int B, int T) {
     fe::FArgs a{};
     a.wp = h->packed_dev;
     a.B = B;
@@ -341,30 +352,43 @@ fe::FArgs fspen_args(fe_handle* h, int B, int T) {
 // FSPEN per-hop step of large batches: the middle of the network batched over the streams (fspen_sb_kernels.hip.h) from FE_FSPEN_SB streams
 // (0 = never; measured crossover on 256 CUs at ~1500 streams - a sixteen-stream workgroup per CU needs 4096 to fill the chip)
 // (fe_set_option("fspen_stream_batch_min", n); default 1536)
-int ensure_fsplit(fe_handle* h, int B) {
-    const int sb_min = h->opt[OPT_FSPEN_SB_MIN];
-    if (!h->fimpl || sb_min <= 0 || B < sb_min || B <= h->bsplit_streams) return FE_OK;
-    if (h->bsplit_dev) { FE_HIP_CHECK(hipFree(h->bsplit_dev)); h->bsplit_dev = nullptr; h->bsplit_streams = 0; }
-    FE_HIP_CHECK(hipMalloc(&h->bsplit_dev, ((size_t)B + 16) * h->fimpl->split_floats_per_stream * sizeof(float)));      // (+ 16: the last stream tile's lane-private scratch is whole)
-    h->bsplit_streams = B;
-    return FE_OK;
+int FspenFamily::ensure_sb(fe_handle* h, int B) {
+    // (+ 16: the last stream tile's lane-private scratch is whole)
+    return ensure_sb_scratch(h, B, h->opt[OPT_FSPEN_SB_MIN], ((size_t)B + 16) * h->fimpl->split_floats_per_stream * sizeof(float));
 }
 
-int launch_fspen(fe_handle* h, const fe::FArgs& a_in, void* stream) {
+int FspenFamily::launch(fe_handle* h, const fe::FArgs& a_in, void* stream) {
     hipError_t e = hipSuccess;
     fe::FArgs a = a_in;
     const int sb_min = h->opt[OPT_FSPEN_SB_MIN];
-    h->last_shape = "fspen";
     if (a.mode == fe::FE_MODE_STREAM && a.T == 1 && a.dbg == nullptr && sb_min > 0 && a.B >= sb_min) {      // (fe_profile_step: the DPE kernel's counters only)
-        const int rc = ensure_fsplit(h, a.B);
+        const int rc = ensure_sb(h, a.B);
         if (rc != FE_OK) return rc;
-        a.tok = h->bsplit_dev;
+        a.tok = h->sb_dev;
         a.carry = a.tok + (size_t)a.B * 2048;
         h->fimpl->launch_sb(a, h->max_wgs, (hipStream_t)stream, &e);
-        if (e != hipSuccess) return fail(FE_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-        return FE_OK;
+        return launch_rc(e);
     }
     h->fimpl->launch(a, h->max_wgs, (hipStream_t)stream, &e);
-    if (e != hipSuccess) return fail(FE_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-    return FE_OK;
+    return launch_rc(e);
+}
+
+const char* FspenFamily::stage_name(const fe_handle*, int idx) {
+    static const char* const names[16] = {"spec_in", "compressed", "subband_encoder", "fullband_encoder.2", "feature_merge", "dpe.0.intra",
+                                          "dpe.0.inter", "dpe.1.intra", "dpe.1.inter", "dpe.2.intra", "dpe.2.inter", "feature_split",
+                                          "fullband_decoder.0", "fullband_decoder.1", "mask", "spec_out"};
+    return names[idx];
+}
+
+double FspenFamily::macs(const fe_handle*) {   // models/fspen/macs.py:36-141 with T = 1 (switches as committed: conv output lengths, no BN / LN / bias terms)
+    const double C1[3] = {4, 16, 32}, K[3] = {6, 8, 6}, C2 = 16;
+    double F = 257, m = 0;
+    for (int i = 0; i < 3; ++i) { F = std::floor(F / 2); m += (i == 0 ? 2 : C1[i - 1]) * C1[i] * F * K[i]; }
+    m += 32 * 32 * F + 32 * (4 * 8 + 7 * 6 + 11 * 6 + 20 * 6 + 40 * 6) + 32 * 64 * 32 + 32 * C2 * 32;
+    const double gru = (C2 + C2) * C2 * 3 + C2 * 3;
+    m += 3 * (gru * 2 + 2 * C2 * C2 + C2 + gru + C2 * C2 + C2) * 32;
+    m += C2 * 32 * 32 + 32 * 32 * 64 + 32 * (8 * 2 + 6 * 3 + 8 * 5 + 8 * 10 + 8 * 20);
+    for (int i = 2; i >= 0; --i) { m += C1[i] * (i == 0 ? 2 : C1[i - 1]) * F * K[i]; F = i == 0 ? F * 2 + 1 : F * 2; }
+    m += 257 * 8;
+    return m;
 }

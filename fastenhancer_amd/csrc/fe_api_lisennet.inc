@@ -1,5 +1,28 @@
 // fe_api_lisennet.inc - host side of LiSenNet: weight sections, handle creation, packer, launch (included by fe_api.hip inside its anonymous namespace)
 // ============================================================================ LiSenNet (models/lisennet/model.py)
+
+// The family as fe_api.hip's shared baseline-family paths see it (visit_baseline: the stream and spec steps, offline, the buffer sizes, debug stages)
+struct LisennetFamily {
+    using Args = fe::LArgs;
+    static const fe::LImpl* impl(const fe_handle* h) { return h->limpl; }
+    static const char* shape_name(const fe_handle*) { return "lisennet"; }
+    static float*& state(Args& a) { return a.cache; }
+    static size_t state_floats(const fe_handle* h, int B) { return (size_t)B * h->limpl->cache_floats; }
+    static size_t counters(const fe_handle* h) { return h->limpl->nsite; }      // time-pipeline frame counters per stream
+    static constexpr int kPipeFrames = 32;
+    // the time pipeline's ring of the caches of the frames in flight (LArgs::ring), sized for the widest pipeline: 64 + 2 slots per stream
+    static size_t ring_floats(const fe_handle* h) { return 66 * h->limpl->cache_floats; }
+    static void set_ring(Args& a, float* ring) { a.ring = ring; }
+    static size_t xp_floats(const fe_handle*) { return 0; }
+    static Args args(fe_handle* h, int B, int T);
+    static int create(const fe_config* cfg, fe_handle** out);
+    static int pack_weights(fe_handle* h, const std::vector<float>& blob, std::vector<float>* out);
+    static int ensure_sb(fe_handle* h, int B);
+    static int launch(fe_handle* h, const Args& a, void* stream);
+    static const char* stage_name(const fe_handle*, int idx);
+    static double macs(const fe_handle* h);
+};
+
 // the checkpoint as it is (remove_weight_reparameterizations is a no-op, :476-477), reference layouts, module order
 void build_sections_lisennet(fe_handle* h) {
     const int C = 16, c1 = 4, c2 = 8, c3 = 12, F = 257, Hd = 24, nf = 32;
@@ -68,23 +91,15 @@ void build_sections_lisennet(fe_handle* h) {
     add_section(h, "decoder.lsigmoid.slope", {F, 1, 1});
 }
 
-int create_lisennet(const fe_config* cfg, fe_handle** out) {
+int LisennetFamily::create(const fe_config* cfg, fe_handle** out) {
     if (cfg->win_size > cfg->n_fft) return fail(FE_ERR_INVALID_ARG, "n_fft(%d) must be bigger than win_size(%d)", cfg->n_fft, cfg->win_size);
     const fe::LImpl* li = (cfg->channels == 16 && cfg->rf_blocks == 2 && cfg->n_fft == 512 && cfg->hop_size == 256) ? fe_limpl_h256() : nullptr;
     if (!li)
         return fail(FE_ERR_UNSUPPORTED_CONFIG, "no LiSenNet kernel compiled for num_channels=%d n_blocks=%d n_fft=%d hop=%d "
                     "(configs/others/lisennet.yaml is the compiled architecture)", cfg->channels, cfg->rf_blocks, cfg->n_fft, cfg->hop_size);
-    fe_handle* h = new fe_handle();
-    h->cfg = *cfg;
+    fe_handle* h = new_handle(cfg, Dims{16, 0, 16, 32, 2, cfg->n_fft, cfg->hop_size, cfg->n_fft / 2, 0, 0, {0}});
     h->limpl = li;
-    h->d = Dims{16, 0, 16, 32, 2, cfg->n_fft, cfg->hop_size, cfg->n_fft / 2, 0, 0, {0}};
-    if (hipGetDevice(&h->device) != hipSuccess) h->device = -1;
-    else {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess && cus > 0) h->max_wgs = cus;
-    }
     build_sections_lisennet(h);
-    build_tables(h);
     *out = h;
     return FE_OK;
 }
@@ -281,7 +296,7 @@ void pack_weights_lisennet_sb(fe_handle* h, const std::vector<float>& blob, std:
 }
 
 // k-major repack at the compile-time offsets of fe::LPk (lisennet_kernels.hip.h)
-int pack_weights_lisennet(fe_handle* h, const std::vector<float>& blob, std::vector<float>* out) {
+int LisennetFamily::pack_weights(fe_handle* h, const std::vector<float>& blob, std::vector<float>* out) {
     using P = fe::LPk;
     std::vector<float> buf(P::TOTAL + fe::LSbPk::TOTAL, 0.0f);
     auto S = [&](const std::string& n) { return sec(h, blob, n); };
@@ -393,7 +408,7 @@ int pack_weights_lisennet(fe_handle* h, const std::vector<float>& blob, std::vec
     return FE_OK;
 }
 
-fe::LArgs lisennet_args(fe_handle* h, int B, int T) {
+fe::LArgs LisennetFamily::args(fe_handle* h, int B, int T) {
     fe::LArgs a{};
     a.wp = h->packed_dev;
     a.B = B;
@@ -404,28 +419,49 @@ fe::LArgs lisennet_args(fe_handle* h, int B, int T) {
 
 // LiSenNet per-hop step of large batches: conv_3 .. up3 batched over the streams (lisennet_sb_kernels.hip.h) from "lisennet_stream_batch_min" streams
 // (0 = never).  The carry (fe::LCarry: the tiles' activation tensors + the compressed spectra) is grow-only scratch of the handle.
-int ensure_lsplit(fe_handle* h, int B) {
-    const int sb_min = h->opt[OPT_LISENNET_SB_MIN];
-    if (!h->limpl || sb_min <= 0 || B < sb_min || B <= h->bsplit_streams) return FE_OK;
-    if (h->bsplit_dev) { FE_HIP_CHECK(hipFree(h->bsplit_dev)); h->bsplit_dev = nullptr; h->bsplit_streams = 0; }
-    FE_HIP_CHECK(hipMalloc(&h->bsplit_dev, fe::LCarry::floats(B) * sizeof(float)));
-    h->bsplit_streams = B;
-    return FE_OK;
+int LisennetFamily::ensure_sb(fe_handle* h, int B) {
+    return ensure_sb_scratch(h, B, h->opt[OPT_LISENNET_SB_MIN], fe::LCarry::floats(B) * sizeof(float));
 }
 
-int launch_lisennet(fe_handle* h, const fe::LArgs& a_in, void* stream) {
+int LisennetFamily::launch(fe_handle* h, const fe::LArgs& a_in, void* stream) {
     hipError_t e = hipSuccess;
     fe::LArgs a = a_in;
     const int sb_min = h->opt[OPT_LISENNET_SB_MIN];
     if (a.mode == fe::FE_MODE_STREAM && a.T == 1 && sb_min > 0 && a.B >= sb_min && h->limpl->launch_sb) {
-        const int rc = ensure_lsplit(h, a.B);
+        const int rc = ensure_sb(h, a.B);
         if (rc != FE_OK) return rc;
-        a.carry = h->bsplit_dev;
+        a.carry = h->sb_dev;
         h->limpl->launch_sb(a, h->max_wgs, (hipStream_t)stream, &e);
-        if (e != hipSuccess) return fail(FE_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-        return FE_OK;
+        return launch_rc(e);
     }
     h->limpl->launch(a, h->max_wgs, (hipStream_t)stream, &e);
-    if (e != hipSuccess) return fail(FE_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-    return FE_OK;
+    return launch_rc(e);
+}
+
+const char* LisennetFamily::stage_name(const fe_handle*, int idx) {
+    static const char* const names[16] = {"spec_in", "compressed", "features", "encoder.conv_1", "encoder.conv_2", "encoder.conv_3", "encoder.conv_4",
+                                          "blocks.0.intra", "blocks.0.inter", "blocks.0", "blocks.1.intra", "blocks.1.inter", "blocks.1",
+                                          "decoder.up3", "mask", "spec_out"};
+    return names[idx];
+}
+
+double LisennetFamily::macs(const fe_handle*) {   // models/lisennet/macs.py:8-66 with T = 1
+    const double C = 16, Nb = 2, F1 = 257;
+    double m = 3 * (C / 4) * F1;
+    const double co[3] = {C / 2, C / 4 * 3, C}, fi[3] = {257, 128, 64};
+    for (int i = 0; i < 3; ++i) {
+        const double f = fi[i], fq = std::floor(f / 4), fhi = std::floor((f - fq + 2 - 5) / 3) + 1;
+        m += (2 * 3 * fq + 2 * 5 * fhi) * co[i] * co[i];
+    }
+    auto gru = [](double i, double hd) { return (i + hd) * hd * 3 + hd * 3; };
+    const double hh = 24, ff = 32;
+    for (int b = 0; b < (int)Nb; ++b) {
+        m += (gru(C, hh / 2) * 2 + hh * C + gru(C, hh) + hh * C) * ff;
+        m += (C * C * 4 + C * 2 * 3 + C * 2 + C * 2 * C) * ff;
+    }
+    double c_in = C, f = 32, c_out = 0;
+    for (double c_o : {C / 4 * 3, C / 2, C / 4}) { c_out = c_o; m += (3 * (f / 2) + 3 * 3 * (f / 2)) * c_in * 2 * c_out; c_in = c_out; f *= 2; }
+    f += 1;
+    m += (c_out * 2 * 2 * 2 + 2 * 2 + 2 * 2) * f;
+    return m;
 }
