@@ -42,6 +42,8 @@ SYMBOLS = {
     "fe_state_floats": (c_size_t, [c_void_p, c_int]),
     "fe_state_init": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "fe_step": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),
+    "fe_step_slots": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),
+    "fe_state_reset_slots": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "fe_step_host": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p]),
     "fe_spec_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "fe_set_time_pipeline": (c_int, [c_void_p, c_int]),

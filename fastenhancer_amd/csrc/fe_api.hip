@@ -1105,6 +1105,20 @@ int fe_state_init(fe_handle* h, float* state_dev, int B, void* stream) {
     return rc;
 }
 
+static const char* const kNoncausalNoStep =
+    "the noncausal model has no streaming step (models/fastenhancer/noncausal/model.py has the offline Model only): use fe_offline";
+
+// FastEnhancer's streaming step of B streams: the shape's own record, or - per-hop launches above the streams the shape's own plan holds at once
+// (#CUs; 2 x #CUs for T) - the low-LDS companion (two workgroups per CU, three for the T shapes; same packed weights - Pack<S> does not depend
+// on LOW), where one is compiled and measured faster.  probe: a debug / profile step (always the shape's own record)
+static const fe::Impl* step_impl(const fe_handle* h, int B, int T, bool probe) {
+    if (h->impl_many && h->opt[OPT_LOW_LDS_COMPANION] && T == 1 && B > h->max_wgs * h->impl->occ && (h->impl_many->many_persist || B <= h->max_wgs * h->impl_many->occ) &&
+        (h->impl_many->many_one_round || B > h->max_wgs * h->impl_many->occ) && !probe &&
+        !(h->step_kernel == FE_STEP_KERNEL_WG8_PERSIST && h->impl->wg8))
+        return h->impl_many;
+    return h->impl;
+}
+
 static int run_step(fe_handle* h, const float* wav_in, size_t in_stride, float* state, float* wav_out, size_t out_stride,
                     int B, int T, float* dbg, unsigned long long* clk, void* stream) {
     int rc = check_ready(h);
@@ -1126,7 +1140,7 @@ static int run_step(fe_handle* h, const float* wav_in, size_t in_stride, float* 
             rc = F.launch(h, a, stream);
         }))
         return rc;
-    if (d.BD) return fail(FE_ERR_UNSUPPORTED_CONFIG, "the noncausal model has no streaming step (models/fastenhancer/noncausal/model.py has the offline Model only): use fe_offline");
+    if (d.BD) return fail(FE_ERR_UNSUPPORTED_CONFIG, "%s", kNoncausalNoStep);
     rc = ensure_scratch(h, B);
     if (rc != FE_OK) return rc;
     fe::FrameArgs a = base_args(h, B, T);
@@ -1144,13 +1158,7 @@ static int run_step(fe_handle* h, const float* wav_in, size_t in_stride, float* 
     a.dbg_stride = h->impl->dbg_floats;
     hipError_t e = hipSuccess;
     a.mode = fe::FE_MODE_STREAM;
-    // per-hop launches above the streams the shape's own plan holds at once (#CUs; 2 x #CUs for T): the low-LDS companion (two workgroups per CU, three
-    // for the T shapes; same packed weights - Pack<S> does not depend on LOW), where one is compiled and measured faster
-    const fe::Impl* im = h->impl;
-    if (h->impl_many && h->opt[OPT_LOW_LDS_COMPANION] && T == 1 && B > h->max_wgs * h->impl->occ && (h->impl_many->many_persist || B <= h->max_wgs * h->impl_many->occ) &&
-        (h->impl_many->many_one_round || B > h->max_wgs * h->impl_many->occ) && !dbg && !clk &&
-        !(h->step_kernel == FE_STEP_KERNEL_WG8_PERSIST && h->impl->wg8))
-        im = h->impl_many;
+    const fe::Impl* im = step_impl(h, B, T, dbg || clk);
     h->last_shape = im->name;
     im->launch(a, h->max_wgs, (hipStream_t)stream, &e);
     return launch_rc(e);
@@ -1159,6 +1167,105 @@ static int run_step(fe_handle* h, const float* wav_in, size_t in_stride, float* 
 int fe_step(fe_handle* h, const float* wav_in_dev, size_t in_stride, float* state_dev, float* wav_out_dev, size_t out_stride,
             int B, int T, void* stream) {
     return run_step(h, wav_in_dev, in_stride, state_dev, wav_out_dev, out_stride, B, T, nullptr, nullptr, stream);
+}
+
+// the slotted entry points: FastEnhancer's causal models only (checked after the handle and before the arguments' contents)
+static int check_slots_family(const fe_handle* h, const char* fn) {
+    if (h->cfg.arch != FE_ARCH_FASTENHANCER)
+        return fail(FE_ERR_UNSUPPORTED_CONFIG, "%s: slot-indexed state is built for the FastEnhancer family (the default, time_kernel, ln, dprnn and "
+                    "dptransformer models); BSRNN, FSPEN and LiSenNet step whole state buffers with fe_step", fn);
+    if (h->d.BD) return fail(FE_ERR_UNSUPPORTED_CONFIG, "%s", kNoncausalNoStep);
+    return FE_OK;
+}
+
+int fe_step_slots(fe_handle* h, const float* wav_in_dev, size_t in_stride, float* state_dev, int capacity, const int* slots_dev,
+                  float* wav_out_dev, size_t out_stride, int n, int T, void* stream) {
+    if (!h) return fail(FE_ERR_INVALID_ARG, "null handle");
+    int rc = check_slots_family(h, "fe_step_slots");
+    if (rc != FE_OK) return rc;
+    rc = check_ready(h);
+    if (rc != FE_OK) return rc;
+    KernelLogScope klog_(h);
+    if (!wav_in_dev || !state_dev || !slots_dev || !wav_out_dev || n <= 0 || T <= 0 || capacity < n)
+        return fail(FE_ERR_INVALID_ARG, "bad argument (need non-null pointers, 1 <= n <= capacity, T >= 1)");
+    const Dims& d = h->d;
+    if (in_stride < (size_t)T * d.HOP && n > 1) return fail(FE_ERR_INVALID_ARG, "in_stride %zu < T*H", in_stride);
+    if (out_stride < (size_t)T * d.HOP && n > 1) return fail(FE_ERR_INVALID_ARG, "out_stride %zu < T*H", out_stride);
+    rc = ensure_scratch(h, n);
+    if (rc != FE_OK) return rc;
+    // the launch fe_step(B = n) makes, with every state address taken from (slots_dev[b], capacity)
+    fe::SlotFrameArgs a{};
+    static_cast<fe::FrameArgs&>(a) = base_args(h, n, T);
+    const size_t ovl = (size_t)(d.NFFT - d.HOP);
+    a.wav_in = wav_in_dev;
+    a.wav_out = wav_out_dev;
+    a.in_stride = in_stride;
+    a.out_stride = out_stride;
+    a.cache_stft = state_dev;
+    a.cache_istft = state_dev + (size_t)capacity * ovl;
+    a.h = state_dev + 2 * (size_t)capacity * ovl;
+    a.tk = a.h + (size_t)capacity * d.hstate();
+    a.capacity = capacity;
+    a.slots = slots_dev;
+    a.mode = fe::FE_MODE_STREAM;
+    const fe::Impl* im = step_impl(h, n, T, false);
+    if (!im->launch_slots) return fail(FE_ERR_UNSUPPORTED_CONFIG, "fe_step_slots: no slotted kernel is compiled for shape %s", im->name ? im->name : "?");
+    h->last_shape = im->name;
+    hipError_t e = hipSuccess;
+    im->launch_slots(a, h->max_wgs, (hipStream_t)stream, &e);
+    return launch_rc(e);
+}
+
+// fe_state_reset_slots: what fe_state_init writes (zeros) for the named slots.  The state is a list of regions [rows][capacity][len]
+// (stream-major over the capacity); one workgroup per named slot zeroes its len floats in every row of every region.
+struct ResetRegion {
+    size_t off;          // floats from the start of the state
+    int rows, len;
+};
+struct ResetArgs {
+    float* state;
+    const int* slots;
+    int capacity, n_regions;
+    ResetRegion r[5];
+};
+
+__global__ void __launch_bounds__(256) state_reset_slots_kernel(ResetArgs a) {
+    const int s = a.slots[blockIdx.x];
+    if (s < 0 || s >= a.capacity) return;         // (out of range: nothing is written)
+    for (int j = 0; j < a.n_regions; ++j) {
+        const ResetRegion g = a.r[j];
+        for (int row = 0; row < g.rows; ++row) {
+            float* p = a.state + g.off + ((size_t)row * a.capacity + s) * g.len;
+            for (int i = (int)threadIdx.x; i < g.len; i += (int)blockDim.x) p[i] = 0.0f;
+        }
+    }
+}
+
+int fe_state_reset_slots(fe_handle* h, float* state_dev, int capacity, const int* slots_dev, int n, void* stream) {
+    if (!h) return fail(FE_ERR_INVALID_ARG, "null handle");
+    int rc = check_slots_family(h, "fe_state_reset_slots");
+    if (rc != FE_OK) return rc;
+    if (!state_dev || !slots_dev || n <= 0 || capacity < n) return fail(FE_ERR_INVALID_ARG, "bad argument (need non-null pointers, 1 <= n <= capacity)");
+    const Dims& d = h->d;
+    const size_t cap = (size_t)capacity, ovl = (size_t)(d.NFFT - d.HOP), hbase = 2 * cap * ovl;
+    ResetArgs a{};
+    a.state = state_dev;
+    a.slots = slots_dev;
+    a.capacity = capacity;
+    int nr = 0;
+    a.r[nr++] = {0, 1, (int)ovl};                                         // cache_stft [cap][N-H]
+    a.r[nr++] = {cap * ovl, 1, (int)ovl};                                 // cache_istft [cap][N-H]
+    if (d.TA) {
+        const int ring = d.F2 * d.C2 * d.TA;                              // K and V rings per block: [2 KB][cap][F2 * C2 * L], then the heads [cap]
+        a.r[nr++] = {hbase, 2 * d.KB, ring};
+        a.r[nr++] = {hbase + cap * (size_t)(2 * d.KB) * ring, 1, 1};
+    } else {
+        a.r[nr++] = {hbase, d.KB, d.F2 * d.C2};                           // GRU states [KB][cap][F2 * C2]
+    }
+    if (d.KT > 1) a.r[nr++] = {hbase + cap * d.hstate(), 2 * d.NL, (int)(tk_floats(h) / (2 * d.NL))};   // conv caches [2 NL][cap][KT-1][F1][C1]
+    a.n_regions = nr;
+    hipLaunchKernelGGL(state_reset_slots_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, a);
+    return launch_rc(hipGetLastError());
 }
 
 int fe_step_host(fe_handle* h, const float* wav_in_host, size_t in_stride, float* state_dev, float* wav_out_host, size_t out_stride,

@@ -124,11 +124,12 @@ __device__ __forceinline__ void conv8_pair(int wh, AF&& af, BF&& bf, BI&& bias, 
 }
 
 // DBG: per-stage dumps (fe_debug_step) and the phase cycle probes (fe_profile_step).  PERSIST: more streams than CUs,
-// each workgroup walks the streams blockIdx.x, blockIdx.x + gridDim.x, ...
-template <class S, bool DBG, bool PERSIST>
-__global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(2, 2))) fe_frame8_kernel(FrameArgs a_in) {
+// each workgroup walks the streams blockIdx.x, blockIdx.x + gridDim.x, ...  SLOT (fe_step_slots): stream b's state is slot a.slots[b] of a
+// state sized for a.capacity streams, as in fe_frame_kernel
+template <class S, bool DBG, bool PERSIST, bool SLOT = false>
+__global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(2, 2))) fe_frame8_kernel(typename KernelArgs<SLOT>::type a_in) {
     static_assert(Wg8<S>::OK, "fe_frame8_kernel: shape outside the 512-thread kernel's plan");
-    FrameArgs a = a_in;
+    typename KernelArgs<SLOT>::type a = a_in;
 #ifdef FE_PROBE_HOT
     if constexpr (!DBG) a.dbg = nullptr;
 #else
@@ -197,7 +198,13 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
         const StageSide<NPW, PERSIST ? 0 : o.u_size[1] / 256, kWaves8> st1{&job1};
         if constexpr (!PERSIST) {
             const int b0 = (int)blockIdx.x;
-            fv = (tid < OVL) ? a.cache_stft[(size_t)b0 * OVL + tid] : a.wav_in[(size_t)b0 * a.in_stride + tid - OVL];
+            if constexpr (SLOT) {
+                const int s0 = a.slots[b0];
+                const bool live = (unsigned)s0 < (unsigned)a.capacity;
+                fv = (tid < OVL) ? (live ? a.cache_stft[(size_t)s0 * OVL + tid] : 0.0f) : a.wav_in[(size_t)b0 * a.in_stride + tid - OVL];
+            } else {
+                fv = (tid < OVL) ? a.cache_stft[(size_t)b0 * OVL + tid] : a.wav_in[(size_t)b0 * a.in_stride + tid - OVL];
+            }
             fw = wp[o.window + tid];
             if (wave < 4) Dft<S>::load(dc, wb, o, wave);
             st1(0, 1);
@@ -221,6 +228,19 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
     int fc = 0;
 #pragma unroll 1
     do {
+        int sb = b;                                      // the stream's state slot
+        int nst = a.B;                                   // streams the state is sized for
+        if constexpr (SLOT) {
+            static_assert(!DBG, "slotted step: production instantiations only");
+            sb = a.slots[b];
+            nst = a.capacity;
+            if ((unsigned)sb >= (unsigned)nst) {         // (wave-uniform) no state: the stream's output row is zero
+                if (tid0 < H) a.wav_out[(size_t)b * a.out_stride + tid0] = 0.0f;
+                __builtin_amdgcn_s_waitcnt(0);           // (the weight stages issued for this stream have landed before the next one or the end)
+                b += (int)gridDim.x;
+                continue;
+            }
+        }
         // PERSIST: a loop-variant zero keeps the wave-uniform / per-lane offsets of a frame from being hoisted out of the stream loop
         // (hoisted, they stay live through the whole frame and spill - see fe_frame_kernel)
         int lz = 0, lzv = 0;
@@ -230,8 +250,8 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
         const int lane = tid & 63;
         const int ws = wave & 3, wh = wave >> 2;          // SIMD slot, half
         const int li = lane & 15, lg = lane >> 4;
-        float* cst = a.cache_stft + (size_t)b * OVL;
-        float* cis = a.cache_istft + (size_t)b * OVL;
+        float* cst = a.cache_stft + (size_t)sb * OVL;
+        float* cis = a.cache_istft + (size_t)sb * OVL;
         const int fpar = (S::NU & 1) ? (fc & 1) : 0;
 #define FE8_BEGIN_UNIT(U)                                                                          \
         constexpr int fe_un_ = ((U) + 1 == S::NU) ? 0 : (U) + 1;                                   \
@@ -256,7 +276,7 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
             constexpr int k = decltype(k_)::value;
             if (wave >= 4) {
                 const int row = 16 * hrt + (lane & 15);
-                const float* hrow = a.h + ((size_t)k * a.B + b) * (S::F2 * S::C2) + (row < S::F2 ? row : S::F2 - 1) * S::C2 + (lane >> 4);
+                const float* hrow = a.h + ((size_t)k * nst + sb) * (S::F2 * S::C2) + (row < S::F2 ? row : S::F2 - 1) * S::C2 + (lane >> 4);
 #pragma unroll
                 for (int ks = 0; ks < HK2; ++ks) hpa[k][ks] = hrow[4 * ks];
 #pragma unroll
@@ -482,7 +502,7 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
             const StG stg{&jb1};
 #endif
             float hpre[HPT];
-            const float* hg0 = a.h + (size_t)b * (F2 * C2);
+            const float* hg0 = a.h + (size_t)sb * (F2 * C2);
 #pragma unroll
             for (int q = 0; q < HPT; ++q) { const int i = tid + q * NTH; hpre[q] = hg0[i < F2 * C2 ? i : F2 * C2 - 1]; }
             f32x4 acc[1][1];
@@ -510,7 +530,7 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
         // =========================== RNNFormer blocks (a9-a11) ===========================
 #pragma unroll
         for (int k = 0; k < S::KB; ++k) {
-            float* hg = a.h + ((size_t)k * a.B + b) * (F2 * C2);
+            float* hg = a.h + ((size_t)k * nst + sb) * (F2 * C2);
             const int ub = k * u8_stride;
             if (k == 0) FE_CLK(20);
             {
@@ -870,7 +890,7 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
                 // the next block's hidden state is fetched now and parked after the GEMM
                 float hpre[HPT];
                 if (k + 1 < S::KB) {
-                    const float* hgn = hg + (size_t)a.B * (F2 * C2);
+                    const float* hgn = hg + (size_t)nst * (F2 * C2);
 #pragma unroll
                     for (int q = 0; q < HPT; ++q) { const int i = tid + q * NTH; hpre[q] = hgn[i < F2 * C2 ? i : F2 * C2 - 1]; }
                 }
@@ -1095,7 +1115,7 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
                 const f32x4* hst = reinterpret_cast<const f32x4*>(smem + W8::HST);
 #pragma unroll
                 for (int k = 0; k < S::KB; ++k) {
-                    f32x4* dst = reinterpret_cast<f32x4*>(a.h + ((size_t)k * a.B + b) * (F2 * C2));
+                    f32x4* dst = reinterpret_cast<f32x4*>(a.h + ((size_t)k * nst + sb) * (F2 * C2));
                     for (int e = tid; e < N4; e += NTH) dst[e] = hst[k * N4 + e];
                 }
             }

@@ -32,6 +32,8 @@ struct Impl {
     const char* name = nullptr;      // the line of fe_shapes.def this record was compiled from (fe_shape.hip.in): part of fe_last_step_kernel's answer
     bool many_one_round = true;      // companion: used from the first stream above the shape's own plan (false: only beyond occ x #CUs streams, as persistent workgroups)
     int EP = 0;                      // Shape::EP: activation + 8 * mask (FE_ACT_* / FE_MASK_*); 0 = SiLU, no mask function
+    // fe_step_slots: launch_impl's choice for a.B streams, made with the SLOT instantiations (a.slots / a.capacity); nullptr without a frame kernel
+    void (*launch_slots)(const SlotFrameArgs&, int max_wgs, hipStream_t, hipError_t*) = nullptr;
 };
 
 // the instantiation a launcher picked, as fe_last_step_kernel reports it
@@ -43,49 +45,59 @@ constexpr const char* frame_kernel_name(bool dbg, bool per_hop, bool persist) {
     return S::LOW == 2 ? "fe_frame_kernel<LOW=2, generic>" : S::LOW == 1 ? "fe_frame_kernel<LOW=1, generic>" : "fe_frame_kernel<generic>";
 }
 
-template <class S, bool DBG, int MODE, bool T1, bool PERSIST>
-void launch_one(const FrameArgs& a, int grid_x, hipStream_t st, hipError_t* err) {
+// ... and its slotted form (fe_step_slots): the same name with "slots" in the brackets
+template <class S>
+constexpr const char* frame_kernel_slot_name(bool per_hop, bool persist) {
+    if (per_hop && !persist) return S::LOW == 2 ? "fe_frame_kernel<LOW=2, per-hop, slots>" : S::LOW == 1 ? "fe_frame_kernel<LOW=1, per-hop, slots>" : "fe_frame_kernel<per-hop, slots>";
+    if (per_hop) return S::LOW == 2 ? "fe_frame_kernel<LOW=2, per-hop, persistent, slots>" : S::LOW == 1 ? "fe_frame_kernel<LOW=1, per-hop, persistent, slots>" : "fe_frame_kernel<per-hop, persistent, slots>";
+    return S::LOW == 2 ? "fe_frame_kernel<LOW=2, generic, slots>" : S::LOW == 1 ? "fe_frame_kernel<LOW=1, generic, slots>" : "fe_frame_kernel<generic, slots>";
+}
+
+template <class S, bool DBG, int MODE, bool T1, bool PERSIST, bool SLOT = false>
+void launch_one(const typename KernelArgs<SLOT>::type& a, int grid_x, hipStream_t st, hipError_t* err) {
     // the opt-in for > 64 KiB of dynamic LDS is a per-device function attribute: one flag per device, set once
     // (an engine may live on any GPU of the process; relaxed atomics - setting it twice is harmless)
     static std::atomic<bool> attr_set[kMaxDevices];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) dev = 0;
     if (!attr_set[dev].load(std::memory_order_relaxed)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fe_frame_kernel<S, DBG, MODE, T1, PERSIST>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fe_frame_kernel<S, DBG, MODE, T1, PERSIST, false, SLOT>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)Lds<S>::BYTES);
         if (e != hipSuccess) { *err = e; return; }
         attr_set[dev].store(true, std::memory_order_relaxed);
     }
     dim3 grid(grid_x), block(kThreads);
-    note_kernel(frame_kernel_name<S>(DBG, T1, PERSIST));
-    hipLaunchKernelGGL((fe_frame_kernel<S, DBG, MODE, T1, PERSIST>), grid, block, Lds<S>::BYTES, st, a);
+    note_kernel(SLOT ? frame_kernel_slot_name<S>(T1, PERSIST) : frame_kernel_name<S>(DBG, T1, PERSIST));
+    hipLaunchKernelGGL((fe_frame_kernel<S, DBG, MODE, T1, PERSIST, false, SLOT>), grid, block, Lds<S>::BYTES, st, a);
     *err = hipGetLastError();
 }
 
 // a.step_kernel (fe_set_step_kernel; the handle's default comes from the environment variable FE_WG8, else 1):
 //   0 = the four-wave kernel everywhere; 1 = the 512-thread kernel (fe_frame8.hip.h: two waves per SIMD, channel-grouped GRU gates)
 //   for the per-hop step of the shapes it is built for, up to one stream per CU; 2 = also above that (persistent workgroups)
-template <class S, bool DBG, bool PERSIST>
-void launch_one8(const FrameArgs& a, int grid_x, hipStream_t st, hipError_t* err) {
+template <class S, bool DBG, bool PERSIST, bool SLOT = false>
+void launch_one8(const typename KernelArgs<SLOT>::type& a, int grid_x, hipStream_t st, hipError_t* err) {
     static std::atomic<bool> attr_set[kMaxDevices];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) dev = 0;
     if (!attr_set[dev].load(std::memory_order_relaxed)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fe_frame8_kernel<S, DBG, PERSIST>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fe_frame8_kernel<S, DBG, PERSIST, SLOT>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)Wg8<S>::BYTES);
         if (e != hipSuccess) { *err = e; return; }
         attr_set[dev].store(true, std::memory_order_relaxed);
     }
     dim3 grid(grid_x), block(kThreads8);
-    note_kernel(DBG ? "fe_frame8_kernel<debug>" : PERSIST ? "fe_frame8_kernel<persistent>" : "fe_frame8_kernel");
-    hipLaunchKernelGGL((fe_frame8_kernel<S, DBG, PERSIST>), grid, block, Wg8<S>::BYTES, st, a);
+    if constexpr (SLOT) note_kernel(PERSIST ? "fe_frame8_kernel<persistent, slots>" : "fe_frame8_kernel<slots>");
+    else note_kernel(DBG ? "fe_frame8_kernel<debug>" : PERSIST ? "fe_frame8_kernel<persistent>" : "fe_frame8_kernel");
+    hipLaunchKernelGGL((fe_frame8_kernel<S, DBG, PERSIST, SLOT>), grid, block, Wg8<S>::BYTES, st, a);
     *err = hipGetLastError();
 }
 
 // max_wgs: workgroups that are resident at once (one per CU: 129+ KiB of LDS and waves_per_eu(1,1)); a batch with more
 // streams runs on a grid of max_wgs PERSISTENT workgroups, each walking its streams b, b + grid, ...
-template <class S>
-void launch_impl(const FrameArgs& a, int max_wgs, hipStream_t st, hipError_t* err) {
+// SLOT (fe_step_slots): the same choice, made with the slotted instantiations (streaming mode; no debug dumps or cycle probes)
+template <class S, bool SLOT = false>
+void launch_impl(const typename KernelArgs<SLOT>::type& a, int max_wgs, hipStream_t st, hipError_t* err) {
     const int slots = max_wgs * Lds<S>::OCC;         // resident workgroups
     const int grid = a.B < slots ? a.B : slots;
     if constexpr (Wg8<S>::OK) {
@@ -96,13 +108,26 @@ void launch_impl(const FrameArgs& a, int max_wgs, hipStream_t st, hipError_t* er
 #else
             const bool dbg8 = a.dbg != nullptr || a.clk != nullptr;
 #endif
+            if constexpr (SLOT) {
+                if (grid8 == a.B) { launch_one8<S, false, false, true>(a, grid8, st, err); return; }
+                if (a.step_kernel > 1) { launch_one8<S, false, true, true>(a, grid8, st, err); return; }
+            } else {
             if (grid8 == a.B) {
                 if (dbg8) launch_one8<S, true, false>(a, grid8, st, err);
                 else launch_one8<S, false, false>(a, grid8, st, err);
                 return;
             }
             if (a.step_kernel > 1 && !dbg8) { launch_one8<S, false, true>(a, grid8, st, err); return; }
+            }
         }
+    }
+    if constexpr (SLOT) {
+        if (a.T == 1) {
+            if (grid == a.B) launch_one<S, false, FE_MODE_STREAM, true, false, true>(a, grid, st, err);
+            else launch_one<S, false, FE_MODE_STREAM, true, true, true>(a, grid, st, err);
+        }
+        else launch_one<S, false, -1, false, true, true>(a, grid, st, err);
+        return;
     }
 #ifdef FE_PROBE_HOT
     if (a.dbg != nullptr) launch_one<S, true, -1, false, true>(a, grid, st, err);
@@ -165,6 +190,7 @@ Impl make_impl() {
             DebugLayout<S>::total(), DebugLayout<S>::n_stages, &Pack<S>::v, &launch_impl<S>, &launch_pipe_impl<S>, &dbg_stage_impl<S>};
     im.many_one_round = Lds<S>::MANY_ONE_ROUND;
     im.EP = S::EP;
+    im.launch_slots = &launch_impl<S, true>;
     return im;
     }
 }

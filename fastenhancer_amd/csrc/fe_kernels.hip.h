@@ -358,6 +358,16 @@ struct FrameArgs {
     int step_kernel;          // host side only (fe_impl.h::launch_impl): FE_STEP_KERNEL_* of the handle (fe_set_step_kernel)
 };
 
+// The slot-indexed step (fe_step_slots; the SLOT instantiations): FrameArgs with two fields at the end.  Call stream b is state slot slots[b] of a
+// state sized for `capacity` streams - every state address takes (slot, capacity) where the plain step takes (b, B); wav_in / wav_out rows stay
+// in call order.  (A type of its own, so that the other instantiations keep their kernel-argument block - and their code - as they were.)
+struct SlotFrameArgs : FrameArgs {
+    int capacity;
+    const int* slots;         // [B] device int32; a slot outside [0, capacity) gets zero output rows and touches no state
+};
+template <bool SLOT> struct KernelArgs { using type = FrameArgs; };
+template <> struct KernelArgs<true> { using type = SlotFrameArgs; };
+
 // ------------------------------------------------------------------------------------------
 #ifndef FE_PROBE_TID
 #define FE_PROBE_TID 0      // the thread whose clock the phase probes record (measurement builds: -DFE_PROBE_TID=256 = wave 4 of the 512-thread kernel)
@@ -1447,9 +1457,11 @@ __device__ __forceinline__ void attention_head(const float* G, float* Hl, int ho
 // workgroup to another goes through st_state / ld_state - a plain load or store added to a ring or state would be a silent stale read
 // (no release / acquire fence covers it).  The serial chain is
 // T x (state round trip + one GRU phase) instead of T x (whole frame): ~12 frames in flight for FastEnhancer_B.
-template <class S, bool DBG, int MODE, bool T1, bool PERSIST, bool PIPE = false>
-__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(Lds<S>::OCC, Lds<S>::OCC))) fe_frame_kernel(FrameArgs a_in) {
-    FrameArgs a = a_in;
+// SLOT (fe_step_slots): stream b's state is slot a.slots[b] of a state sized for a.capacity streams (sb, nst below); a slot out of range
+// gets zero output rows and neither reads nor writes state.  SLOT = false: sb = b, nst = a.B - the code of the plain step.
+template <class S, bool DBG, int MODE, bool T1, bool PERSIST, bool PIPE = false, bool SLOT = false>
+__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(Lds<S>::OCC, Lds<S>::OCC))) fe_frame_kernel(typename KernelArgs<SLOT>::type a_in) {
+    typename KernelArgs<SLOT>::type a = a_in;
 #ifdef FE_PROBE_HOT          // measurement builds: the production instantiations keep the cycle probes (tools/gpu_phases.py ... 1)
     if constexpr (!DBG) a.dbg = nullptr;
 #else
@@ -1561,8 +1573,22 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
     };
 #pragma unroll 1
     do {
-    float* cst = a.cache_stft + (size_t)b * OVL;
-    float* cis = a.cache_istft + (size_t)b * OVL;
+    int sb = b;                                      // the stream's state slot
+    int nst = a.B;                                   // streams the state is sized for
+    if constexpr (SLOT) {
+        static_assert(!PIPE && !DBG, "slotted step: per-hop / generic streaming instantiations only");
+        sb = a.slots[b];
+        nst = a.capacity;
+        if ((unsigned)sb >= (unsigned)nst) {         // (wave-uniform) no state: the stream's output rows are zero
+            float* out = a.wav_out + (size_t)b * a.out_stride;
+            for (int n = tid; n < a.T * S::HOP; n += kThreads) out[n] = 0.0f;
+            __builtin_amdgcn_s_waitcnt(0);           // (the weight stage issued for this stream has landed before the next one or the end)
+            b += (int)gridDim.x;
+            continue;
+        }
+    }
+    float* cst = a.cache_stft + (size_t)sb * OVL;
+    float* cis = a.cache_istft + (size_t)sb * OVL;
     constexpr int NFLAG = S::KB + (S::KT > 1 ? 2 * S::NL : 0);       // counters per stream
     unsigned int* pflag = PIPE ? a.pipe_flags + (size_t)b * NFLAG : nullptr;
     // wait until the block-k state of frame t-1 is published (all threads call; thread 0 polls)
@@ -1586,7 +1612,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
     };
 
     int ring_head0 = 0;                              // dptransformer: slot of the oldest cached frame when this launch starts
-    if constexpr (S::TATT && !PIPE) ring_head0 = (int)a.h[(size_t)a.B * S::KB * S::HSTATE + b];
+    if constexpr (S::TATT && !PIPE) ring_head0 = (int)a.h[(size_t)nst * S::KB * S::HSTATE + sb];
     // dptransformer, per-hop launch with one stream per workgroup (r4): the K / V window of a block - 31 cached frames x [F2][C2] x 2,
     // 214 KB per stream and block for B, the whole HBM traffic of this HBM-bound step - is fetched into REGISTERS (4 HD floats per lane
     // and round of sixteen (sub-band, head) pairs: 216 of the 342 the lone wave per SIMD has left) in pieces issued at the END of the
@@ -1656,8 +1682,8 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
             if constexpr (WPF && it < W_NIT) {
                 if (kblk < S::KB) {
                     const size_t cstride = (size_t)F2 * C2 * S::LB;
-                    const float* kc = a.h + ((size_t)(2 * kblk) * a.B + b) * cstride + (size_t)(16 * it) * (S::LB * HD);
-                    const float* vc = kc + (size_t)a.B * cstride;
+                    const float* kc = a.h + ((size_t)(2 * kblk) * nst + sb) * cstride + (size_t)(16 * it) * (S::LB * HD);
+                    const float* vc = kc + (size_t)nst * cstride;
                     // (plain loads: the rings of 256 streams - 164 MB for B - live in the 256 MiB Infinity Cache from launch to launch; non-temporal
                     //  loads measured 52.5 -> 76.6 us, profiles/r4u_*)
 #pragma unroll
@@ -1846,13 +1872,13 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
             constexpr int CPT = (KT - 1) * Q4 / kThreads, NPT = Q4 / kThreads;
             static_assert(Q4 % kThreads == 0, "cache slots are moved by whole float4 rounds");
             float* CAb = smem + L::CA;
-            float4* tkg = reinterpret_cast<float4*>(a.tk + ((size_t)lidx * a.B + b) * S::TKQ);
+            float4* tkg = reinterpret_cast<float4*>(a.tk + ((size_t)lidx * nst + sb) * S::TKQ);
             // PIPE (time-pipelined offline launch): the conv's input of every frame goes through a RING of pipe_p + KT - 1 slots per
             // (conv, stream) in a.tk instead of the two-slot cache - frame t publishes its input in slot t mod RS and counts it in
             // pflag[KB + conv]; frames t + 1 .. t + KT - 1 wait for that count and fetch the slot (agent-scope accesses on both sides).
             // Slot t mod RS is overwritten by frame t + RS, run by the workgroup of frame t + KT - 1 after that frame: every reader is done.
             const int RS = PIPE ? a.pipe_p + KT - 1 : 1;
-            float* ringb = a.tk + (((size_t)lidx * a.B + b) * RS) * (size_t)(F1 * C1);
+            float* ringb = a.tk + (((size_t)lidx * nst + sb) * RS) * (size_t)(F1 * C1);
             f32x4 acc[S::MTPW][S::NTC];
             float4 creg[CPT];
             static_for<KT>([&](auto s_) {
@@ -2147,7 +2173,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
             // hidden state of block 0: fetched now, parked in LDS after the GEMM
             float hpre[HPT];
             if constexpr (!PIPE && !S::TATT) {     // (PIPE: the state is fetched as late as possible, inside the GRU phase)
-                const float* hg0 = a.h + (size_t)b * (F2 * C2);
+                const float* hg0 = a.h + (size_t)sb * (F2 * C2);
 #pragma unroll
                 for (int q = 0; q < HPT; ++q) { const int i = tid + q * kThreads; hpre[q] = hg0[i < F2 * C2 ? i : F2 * C2 - 1]; }   // (clamped, not predicated: no branch per load)
             }
@@ -2216,7 +2242,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
         // FastEnhancer_B kernel drops from 256 to 174 VGPRs); big shapes: rolled, for register pressure and code size
 #pragma unroll (S::C1 <= 48 ? S::KB : 1)
         for (int k = 0; k < S::KB; ++k) {
-            float* hg = a.h + ((size_t)k * a.B + b) * (F2 * C2);
+            float* hg = a.h + ((size_t)k * nst + sb) * (F2 * C2);
             const int kb = k * o.blk_stride;
             if (k == 0) FE_CLK(20);
             if constexpr (S::TATT) {
@@ -2264,8 +2290,8 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                     constexpr int LBK = S::LB, PAIRS = F2 * S::NH;
                     const int RS = LBK + a.pipe_p;
                     const size_t cstride = (size_t)F2 * C2 * RS;
-                    float* kc = a.h + ((size_t)(2 * k) * a.B + b) * cstride;
-                    float* vc = a.h + ((size_t)(2 * k + 1) * a.B + b) * cstride;
+                    float* kc = a.h + ((size_t)(2 * k) * nst + sb) * cstride;
+                    float* vc = a.h + ((size_t)(2 * k + 1) * nst + sb) * cstride;
                     const int wbase = a.tatt_base;
                     {
                         const int slot = (t + wbase) % RS;
@@ -2347,8 +2373,8 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                     // later phases.
                     constexpr int LBK = S::LB;
                     const size_t cstride = (size_t)F2 * C2 * LBK;
-                    float* kc = a.h + ((size_t)(2 * k) * a.B + b) * cstride;
-                    float* vc = a.h + ((size_t)(2 * k + 1) * a.B + b) * cstride;
+                    float* kc = a.h + ((size_t)(2 * k) * nst + sb) * cstride;
+                    float* vc = a.h + ((size_t)(2 * k + 1) * nst + sb) * cstride;
                     const int grp = tid >> 4, l16 = tid & 15;
                     const int mask_lo = (a.mode == FE_MODE_OFFLINE) ? (LBK - t > 0 ? LBK - t : 0) : 0;
                     const float sc = __builtin_amdgcn_rsqf((float)HD);
@@ -2398,12 +2424,12 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                         }
                         if constexpr (it < W_NB) kvw_issue(k + 1, it_);
                     });
-                    if (k == S::KB - 1 && tid == 0) a.h[(size_t)a.B * S::KB * S::HSTATE + b] = (float)((head + 1) % LBK);
+                    if (k == S::KB - 1 && tid == 0) a.h[(size_t)nst * S::KB * S::HSTATE + sb] = (float)((head + 1) % LBK);
                     } else {
                     constexpr int LBK = S::LB, PAIRS = F2 * S::NH;
                     const size_t cstride = (size_t)F2 * C2 * LBK;                    // one cache tensor of one stream: [F2][NH][L][HD]
-                    float* kc = a.h + ((size_t)(2 * k) * a.B + b) * cstride;
-                    float* vc = a.h + ((size_t)(2 * k + 1) * a.B + b) * cstride;
+                    float* kc = a.h + ((size_t)(2 * k) * nst + sb) * cstride;
+                    float* vc = a.h + ((size_t)(2 * k + 1) * nst + sb) * cstride;
                     const int grp = tid >> 4, l16 = tid & 15;
                     const int mask_lo = (a.mode == FE_MODE_OFFLINE) ? (LBK - t > 0 ? LBK - t : 0) : 0;
                     const float sc = __builtin_amdgcn_rsqf((float)HD);               // (hd)^-0.5
@@ -2464,7 +2490,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                             }
                         }
                     }
-                    if (k == S::KB - 1 && tid == 0) a.h[(size_t)a.B * S::KB * S::HSTATE + b] = (float)((head + 1) % LBK);
+                    if (k == S::KB - 1 && tid == 0) a.h[(size_t)nst * S::KB * S::HSTATE + sb] = (float)((head + 1) % LBK);
                     }
                 }
             } else
@@ -2937,7 +2963,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                 // next block: GRU hidden weights into registers inside the GEMM; hidden state fetched now / parked after it
                 Wgh.bind(wb, (o.blk_whh[0] + kb + o.blk_stride), (o.blk_bhh[0] + kb + o.blk_stride), GNT, wave, k + 1 < S::KB && !S::TATT);
                 if (!PIPE && !S::TATT && k + 1 < S::KB) {
-                    const float* hgn = hg + (size_t)a.B * (F2 * C2);
+                    const float* hgn = hg + (size_t)nst * (F2 * C2);
 #pragma unroll
                     for (int q = 0; q < HPT; ++q) { const int i = tid + q * kThreads; hpre[q] = hgn[i < F2 * C2 ? i : F2 * C2 - 1]; }
                 }

@@ -5,6 +5,7 @@ runs in libfastenhancer_hip.so."""
 from __future__ import annotations
 
 import ctypes
+import operator
 from ctypes import byref, c_char_p, c_int, c_size_t, c_void_p
 from typing import Dict, List, Mapping, Optional, Tuple
 
@@ -240,6 +241,62 @@ class Engine:
             _lib.check(self.lib.fe_step(self._h, _ptr(wav_in), wav_in.stride(0) if B > 1 else T * H, _ptr(state), _ptr(wav_out),
                                         wav_out.stride(0) if B > 1 else T * H, B, T, _stream(self.device)), "fe_step")
         return wav_out
+
+    def _slot_tensor(self, slots, capacity: int) -> Tensor:
+        """slots -> a device int32 tensor for fe_step_slots / fe_state_reset_slots.  A CUDA int32 tensor is passed through unchecked (the form
+        for graph capture: its contents may change from replay to replay); a list or CPU tensor is checked here first - integers in
+        [0, capacity), no duplicates - and copied to the device."""
+        if isinstance(slots, Tensor) and slots.is_cuda:
+            if slots.dtype != torch.int32 or slots.dim() != 1 or not slots.is_contiguous():
+                raise ValueError("a device slot tensor must be a contiguous 1-D int32 tensor")
+            return slots
+        if isinstance(slots, Tensor) and (slots.dim() != 1 or slots.is_floating_point() or slots.is_complex() or slots.dtype == torch.bool):
+            raise ValueError("slots must be a 1-D integer tensor")
+        vals = []
+        for s in (slots.tolist() if isinstance(slots, Tensor) else slots):
+            if isinstance(s, bool):
+                raise ValueError(f"slot {s!r} is not an integer")
+            try:
+                vals.append(operator.index(s))
+            except TypeError:
+                raise ValueError(f"slot {s!r} is not an integer") from None
+        for s in vals:
+            if not 0 <= s < capacity:
+                raise ValueError(f"slot {s} is outside [0, {capacity})")
+        if len(set(vals)) != len(vals):
+            raise ValueError("duplicate slots")
+        if not 1 <= len(vals) <= capacity:
+            raise ValueError(f"{len(vals)} slots for a capacity of {capacity}")
+        self._require_gpu()
+        return torch.tensor(vals, dtype=torch.int32).to(self.device, non_blocking=False)
+
+    def step_slots(self, wav_in: Tensor, state: Tensor, capacity: int, slots, wav_out: Optional[Tensor] = None, T: int = 1) -> Tensor:
+        """fe_step_slots: wav_in [n, T*H] (row i = state slot slots[i]) -> wav_out [n, T*H]; only the named slots of `state`
+        (sized for `capacity` streams) are updated.  slots: a list / CPU tensor (checked) or a CUDA int32 tensor (not checked)."""
+        sl = self._slot_tensor(slots, capacity)
+        self._require_gpu()
+        n = wav_in.shape[0]
+        H = self.cfg.hop_size
+        assert sl.numel() == n, (sl.numel(), n)
+        assert wav_in.is_cuda and wav_in.dtype == torch.float32 and wav_in.stride(1) == 1 and wav_in.shape[1] == T * H
+        assert state.numel() == self.state_floats(capacity) and state.is_contiguous()
+        if wav_out is None:
+            wav_out = torch.empty(n, T * H, dtype=torch.float32, device=wav_in.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.fe_step_slots(self._h, _ptr(wav_in), wav_in.stride(0) if n > 1 else T * H, _ptr(state), int(capacity), _ptr(sl),
+                                              _ptr(wav_out), wav_out.stride(0) if n > 1 else T * H, n, T, _stream(self.device)), "fe_step_slots")
+        self._slots_keep = sl          # (a copied list: alive until the next call - the launch is asynchronous)
+        return wav_out
+
+    def reset_slots(self, state: Tensor, capacity: int, slots) -> None:
+        """fe_state_reset_slots: the named slots of `state` (sized for `capacity` streams) as fe_state_init leaves them (zero)."""
+        sl = self._slot_tensor(slots, capacity)
+        self._require_gpu()
+        assert state.numel() == self.state_floats(capacity) and state.is_contiguous()
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.fe_state_reset_slots(self._h, _ptr(state), int(capacity), _ptr(sl), sl.numel(), _stream(self.device)),
+                       "fe_state_reset_slots")
+        self._slots_keep = sl
 
     def step_host(self, wav_in: Tensor, state: Tensor, wav_out: Optional[Tensor] = None, T: int = 1) -> Tensor:
         """fe_step_host: wav_in [B, n*T*H] in HOST memory (pinned for full speed) -> wav_out [B, n*T*H] in host memory, n calls of T hops

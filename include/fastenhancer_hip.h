@@ -160,6 +160,24 @@ int fe_state_init(fe_handle* h, float* state_dev, int B, void* stream);
 int fe_step(fe_handle* h, const float* wav_in_dev, size_t in_stride, float* state_dev,
             float* wav_out_dev, size_t out_stride, int B, int T, void* stream);
 
+/* The same step for n of the streams of a state buffer sized for `capacity` streams (fe_state_floats(h, capacity), every tensor of
+ * the layout above sized for `capacity`): stream i of the call (i < n) is state slot slots_dev[i]; wav_in / wav_out rows are in call
+ * order, as for fe_step (row i = wav_in [i*in_stride + t*H + k]).  The state of slots not named is left untouched, so streams can join
+ * and leave a batch without copying state.
+ *   slots_dev: a DEVICE int32 array of n entries, read by the kernel when it runs (a captured graph may serve other streams on each
+ *     replay after its contents are rewritten).  Its contents are not checked on the host.  Duplicate slots are undefined.  A slot
+ *     outside [0, capacity) touches no state: its stream's wav_out rows are zero.
+ *   The host checks 1 <= n <= capacity, T >= 1, non-null pointers and the strides as fe_step does.  The kernel is the one fe_step(B = n)
+ *     picks (fe_last_step_kernel names its slotted form, "... slots>"); the results of each stream are those of fe_step on a state
+ *     holding only the named slots, bit for bit.
+ *   FastEnhancer family only (the default, time_kernel, ln, dprnn and dptransformer models): BSRNN, FSPEN and LiSenNet return
+ *     FE_ERR_UNSUPPORTED_CONFIG, and so does the noncausal model, as for fe_step. */
+int fe_step_slots(fe_handle* h, const float* wav_in_dev, size_t in_stride, float* state_dev, int capacity, const int* slots_dev,
+                  float* wav_out_dev, size_t out_stride, int n, int T, void* stream);
+/* What fe_state_init writes (zeros), for the named slots only: a stream joining.  slots_dev, capacity, duplicates and the families as for
+ * fe_step_slots; out-of-range slots are skipped. */
+int fe_state_reset_slots(fe_handle* h, float* state_dev, int capacity, const int* slots_dev, int n, void* stream);
+
 /* The same step for callers whose audio lives in HOST memory (the reference's scripts/test_onnx.py feeds numpy arrays hop by hop):
  * n_calls consecutive fe_step calls of T hops each, hop block c = hops c*T .. c*T+T-1 of
  *   wav_in_host [b*in_stride + t*H + n], wav_out_host [b*out_stride + t*H + n]   (page-locked for asynchronous copies; pageable works, slower)
