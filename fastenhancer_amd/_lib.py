@@ -44,6 +44,8 @@ SYMBOLS = {
     "fe_step": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),
     "fe_step_slots": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),
     "fe_state_reset_slots": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "fe_step_pinned": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),
+    "fe_step_slots_pinned": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),
     "fe_step_host": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p]),
     "fe_spec_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "fe_set_time_pipeline": (c_int, [c_void_p, c_int]),

@@ -174,6 +174,8 @@ struct fe_handle {
     unsigned long long* tb_probe_dev = nullptr;   // FE_TB_PROBE builds: phase clocks [4][kProbeSlots]
     hipStream_t host_streams[2] = {nullptr, nullptr};     // fe_step_host: copy-in / copy-out streams (lazy)
     hipEvent_t host_events[7] = {};                       // ... and its events
+    int* ident_slots_dev = nullptr;           // fe_step_pinned: the identity slot list 0 .. ident_slots - 1 (grow-only)
+    int ident_slots = 0;
     float* tb_work_dev = nullptr;             // fe_spec_step on the time-batched engine: grow-only work buffer
     float* spec_ring_dev = nullptr;           // fe_spec_step, dptransformer, time-pipelined: the K / V rings of TA + P slots per pair (grow-only)
     size_t spec_ring_floats = 0;
@@ -1036,6 +1038,7 @@ void fe_destroy(fe_handle* h) {
     if (h->bsync_dev) (void)hipFree(h->bsync_dev);
     for (hipStream_t s : h->host_streams) if (s) (void)hipStreamDestroy(s);
     for (hipEvent_t e : h->host_events) if (e) (void)hipEventDestroy(e);
+    if (h->ident_slots_dev) (void)hipFree(h->ident_slots_dev);
     delete h;
 }
 
@@ -1178,6 +1181,9 @@ static int check_slots_family(const fe_handle* h, const char* fn) {
     return FE_OK;
 }
 
+static int launch_slotted(fe_handle* h, const float* wav_in_dev, size_t in_stride, float* state_dev, int capacity, const int* slots_dev,
+                          float* wav_out_dev, size_t out_stride, int n, int T, void* stream, bool pinned);
+
 int fe_step_slots(fe_handle* h, const float* wav_in_dev, size_t in_stride, float* state_dev, int capacity, const int* slots_dev,
                   float* wav_out_dev, size_t out_stride, int n, int T, void* stream) {
     if (!h) return fail(FE_ERR_INVALID_ARG, "null handle");
@@ -1191,9 +1197,16 @@ int fe_step_slots(fe_handle* h, const float* wav_in_dev, size_t in_stride, float
     const Dims& d = h->d;
     if (in_stride < (size_t)T * d.HOP && n > 1) return fail(FE_ERR_INVALID_ARG, "in_stride %zu < T*H", in_stride);
     if (out_stride < (size_t)T * d.HOP && n > 1) return fail(FE_ERR_INVALID_ARG, "out_stride %zu < T*H", out_stride);
-    rc = ensure_scratch(h, n);
+    return launch_slotted(h, wav_in_dev, in_stride, state_dev, capacity, slots_dev, wav_out_dev, out_stride, n, T, stream, false);
+}
+
+// the launch fe_step(B = n) makes, with every state address taken from (slots_dev[b], capacity); pinned: the HIO instantiations, whose
+// wav_in / wav_out are device views of page-locked host memory (fe_step_slots_pinned)
+static int launch_slotted(fe_handle* h, const float* wav_in_dev, size_t in_stride, float* state_dev, int capacity, const int* slots_dev,
+                          float* wav_out_dev, size_t out_stride, int n, int T, void* stream, bool pinned) {
+    const Dims& d = h->d;
+    int rc = ensure_scratch(h, n);
     if (rc != FE_OK) return rc;
-    // the launch fe_step(B = n) makes, with every state address taken from (slots_dev[b], capacity)
     fe::SlotFrameArgs a{};
     static_cast<fe::FrameArgs&>(a) = base_args(h, n, T);
     const size_t ovl = (size_t)(d.NFFT - d.HOP);
@@ -1209,11 +1222,90 @@ int fe_step_slots(fe_handle* h, const float* wav_in_dev, size_t in_stride, float
     a.slots = slots_dev;
     a.mode = fe::FE_MODE_STREAM;
     const fe::Impl* im = step_impl(h, n, T, false);
-    if (!im->launch_slots) return fail(FE_ERR_UNSUPPORTED_CONFIG, "fe_step_slots: no slotted kernel is compiled for shape %s", im->name ? im->name : "?");
+    auto launch = pinned ? im->launch_slots_pinned : im->launch_slots;
+    if (!launch) return fail(FE_ERR_UNSUPPORTED_CONFIG, "%s: no slotted kernel is compiled for shape %s", pinned ? "fe_step_slots_pinned" : "fe_step_slots",
+                             im->name ? im->name : "?");
     h->last_shape = im->name;
     hipError_t e = hipSuccess;
-    im->launch_slots(a, h->max_wgs, (hipStream_t)stream, &e);
+    launch(a, h->max_wgs, (hipStream_t)stream, &e);
     return launch_rc(e);
+}
+
+// fe_step_pinned / fe_step_slots_pinned: `count` floats from p must be page-locked host memory with a device mapping on the current device
+// (hipHostMalloc / hipHostRegister: torch's pin_memory()).  Anything else - pageable or device memory - would make the kernel take a page
+// fault, so it is refused here, before any launch.  Both ends of the range are looked up; *dev = the device view of p.
+static int pinned_view(const float* p, size_t count, const char* fn, const char* what, const float** dev) {
+    const float* ends[2] = {p, p + (count - 1)};
+    const char* dv[2] = {nullptr, nullptr};
+    for (int i = 0; i < 2; ++i) {
+        hipPointerAttribute_t at{};
+        bool ok = hipPointerGetAttributes(&at, ends[i]) == hipSuccess && at.type == hipMemoryTypeHost;
+        void* dp = nullptr;
+        if (ok) ok = hipHostGetDevicePointer(&dp, const_cast<float*>(ends[i]), 0) == hipSuccess && dp != nullptr;
+        (void)hipGetLastError();        // (a refused lookup must not surface as the error of a later launch)
+        if (!ok)
+            return fail(FE_ERR_INVALID_ARG, "%s: %s is not page-locked host memory mapped for this device (%s float of the range): pin the buffer "
+                        "(torch: pin_memory(); C: hipHostMalloc / hipHostRegister)", fn, what, i ? "last" : "first");
+        dv[i] = static_cast<const char*>(dp);
+    }
+    if (dv[1] - dv[0] != reinterpret_cast<const char*>(ends[1]) - reinterpret_cast<const char*>(ends[0]))
+        return fail(FE_ERR_INVALID_ARG, "%s: %s spans more than one pinned allocation: pin the buffer as one piece (pin_memory())", fn, what);
+    *dev = reinterpret_cast<const float*>(dv[0]);
+    return FE_OK;
+}
+
+// the identity slot list 0 .. B-1 of fe_step_pinned (grow-only; written before the first step that needs it, not inside a capture)
+static int ensure_ident_slots(fe_handle* h, int B) {
+    if (h->ident_slots >= B) return FE_OK;
+    int cap = 256;
+    while (cap < B) cap *= 2;
+    std::vector<int> ids(cap);
+    for (int i = 0; i < cap; ++i) ids[i] = i;
+    if (h->ident_slots_dev) { FE_HIP_CHECK(hipFree(h->ident_slots_dev)); h->ident_slots_dev = nullptr; h->ident_slots = 0; }    // (hipFree waits for the launches that read it)
+    FE_HIP_CHECK(hipMalloc(&h->ident_slots_dev, cap * sizeof(int)));
+    FE_HIP_CHECK(hipMemcpy(h->ident_slots_dev, ids.data(), cap * sizeof(int), hipMemcpyHostToDevice));
+    h->ident_slots = cap;
+    return FE_OK;
+}
+
+// identity: fe_step_pinned (capacity = n, stream i = slot i of the handle's identity list)
+static int step_pinned(fe_handle* h, const char* fn, const float* wav_in_host, size_t in_stride, float* state_dev, int capacity, const int* slots_dev,
+                       bool identity, float* wav_out_host, size_t out_stride, int n, int T, void* stream) {
+    if (!h) return fail(FE_ERR_INVALID_ARG, "null handle");
+    int rc = check_slots_family(h, fn);
+    if (rc != FE_OK) return rc;
+    if (!wav_in_host || !state_dev || !wav_out_host || (!identity && !slots_dev) || n <= 0 || T <= 0 || capacity < n)
+        return fail(FE_ERR_INVALID_ARG, "%s: bad argument (need non-null pointers, 1 <= n <= capacity, T >= 1)", fn);
+    const Dims& d = h->d;
+    const size_t row = (size_t)T * d.HOP;
+    if (in_stride < row && n > 1) return fail(FE_ERR_INVALID_ARG, "%s: in_stride %zu < T*H", fn, in_stride);
+    if (out_stride < row && n > 1) return fail(FE_ERR_INVALID_ARG, "%s: out_stride %zu < T*H", fn, out_stride);
+    rc = check_ready(h);
+    if (rc != FE_OK) return rc;
+    KernelLogScope klog_(h);
+    const float* in_dev = nullptr;
+    const float* out_dev = nullptr;
+    rc = pinned_view(wav_in_host, (size_t)(n - 1) * in_stride + row, fn, "wav_in", &in_dev);
+    if (rc != FE_OK) return rc;
+    rc = pinned_view(wav_out_host, (size_t)(n - 1) * out_stride + row, fn, "wav_out", &out_dev);
+    if (rc != FE_OK) return rc;
+    if (identity) {
+        rc = ensure_ident_slots(h, n);
+        if (rc != FE_OK) return rc;
+        slots_dev = h->ident_slots_dev;
+    }
+    return launch_slotted(h, in_dev, n > 1 ? in_stride : row, state_dev, capacity, slots_dev, const_cast<float*>(out_dev), n > 1 ? out_stride : row,
+                          n, T, stream, true);
+}
+
+int fe_step_pinned(fe_handle* h, const float* wav_in_host, size_t in_stride, float* state_dev, float* wav_out_host, size_t out_stride,
+                   int B, int T, void* stream) {
+    return step_pinned(h, "fe_step_pinned", wav_in_host, in_stride, state_dev, B, nullptr, true, wav_out_host, out_stride, B, T, stream);
+}
+
+int fe_step_slots_pinned(fe_handle* h, const float* wav_in_host, size_t in_stride, float* state_dev, int capacity, const int* slots_dev,
+                         float* wav_out_host, size_t out_stride, int n, int T, void* stream) {
+    return step_pinned(h, "fe_step_slots_pinned", wav_in_host, in_stride, state_dev, capacity, slots_dev, false, wav_out_host, out_stride, n, T, stream);
 }
 
 // fe_state_reset_slots: what fe_state_init writes (zeros) for the named slots.  The state is a list of regions [rows][capacity][len]

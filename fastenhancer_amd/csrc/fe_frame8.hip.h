@@ -125,10 +125,13 @@ __device__ __forceinline__ void conv8_pair(int wh, AF&& af, BF&& bf, BI&& bias, 
 
 // DBG: per-stage dumps (fe_debug_step) and the phase cycle probes (fe_profile_step).  PERSIST: more streams than CUs,
 // each workgroup walks the streams blockIdx.x, blockIdx.x + gridDim.x, ...  SLOT (fe_step_slots): stream b's state is slot a.slots[b] of a
-// state sized for a.capacity streams, as in fe_frame_kernel
-template <class S, bool DBG, bool PERSIST, bool SLOT = false>
+// state sized for a.capacity streams, as in fe_frame_kernel.  HIO (fe_step_slots_pinned; SLOT only): the audio is page-locked host
+// memory - the hop sample of each thread is requested ahead into hv (the first stream's before any other load of the kernel, the next
+// stream's once the current one's has been taken), and the output row goes out in non-temporal 16-byte stores
+template <class S, bool DBG, bool PERSIST, bool SLOT = false, bool HIO = false>
 __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(2, 2))) fe_frame8_kernel(typename KernelArgs<SLOT>::type a_in) {
     static_assert(Wg8<S>::OK, "fe_frame8_kernel: shape outside the 512-thread kernel's plan");
+    static_assert(!HIO || (SLOT && !DBG), "host audio: slotted production instantiations only");
     typename KernelArgs<SLOT>::type a = a_in;
 #ifdef FE_PROBE_HOT
     if constexpr (!DBG) a.dbg = nullptr;
@@ -153,6 +156,11 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
     const int lane = tid & 63;
     const int wave0 = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wave = wave0;
+    float hv = 0.0f;                                 // (HIO) this thread's hop sample of the next stream the workgroup runs
+    auto hop_issue = [&](int bb) {
+        if constexpr (HIO) { if (bb < a.B && tid0 >= OVL) hv = a.wav_in[(size_t)bb * a.in_stride + tid0 - OVL]; }
+    };
+    hop_issue((int)blockIdx.x);
 #ifdef FE_WG8_PRIO
     if (wave0 >= 4) __builtin_amdgcn_s_setprio(FE_WG8_PRIO);      // experiment: the second wave of a SIMD runs ahead of the first
 #endif
@@ -201,7 +209,8 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
             if constexpr (SLOT) {
                 const int s0 = a.slots[b0];
                 const bool live = (unsigned)s0 < (unsigned)a.capacity;
-                fv = (tid < OVL) ? (live ? a.cache_stft[(size_t)s0 * OVL + tid] : 0.0f) : a.wav_in[(size_t)b0 * a.in_stride + tid - OVL];
+                if constexpr (HIO) fv = (tid < OVL) ? (live ? a.cache_stft[(size_t)s0 * OVL + tid] : 0.0f) : hv;
+                else fv = (tid < OVL) ? (live ? a.cache_stft[(size_t)s0 * OVL + tid] : 0.0f) : a.wav_in[(size_t)b0 * a.in_stride + tid - OVL];
             } else {
                 fv = (tid < OVL) ? a.cache_stft[(size_t)b0 * OVL + tid] : a.wav_in[(size_t)b0 * a.in_stride + tid - OVL];
             }
@@ -235,9 +244,12 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
             sb = a.slots[b];
             nst = a.capacity;
             if ((unsigned)sb >= (unsigned)nst) {         // (wave-uniform) no state: the stream's output row is zero
+                if constexpr (HIO) { if (tid0 < H) __builtin_nontemporal_store(0.0f, a.wav_out + (size_t)b * a.out_stride + tid0); }
+                else
                 if (tid0 < H) a.wav_out[(size_t)b * a.out_stride + tid0] = 0.0f;
                 __builtin_amdgcn_s_waitcnt(0);           // (the weight stages issued for this stream have landed before the next one or the end)
                 b += (int)gridDim.x;
+                hop_issue(b);
                 continue;
             }
         }
@@ -329,6 +341,10 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
             if constexpr (PERSIST) {
                 if (wave < 4) Dft<S>::load(dc, wb, o, wave);             // in flight while the frame is fetched
                 const float* xin = a.wav_in + (size_t)b * a.in_stride;
+                if constexpr (HIO) {
+                    fv = (tid < OVL) ? cst[tid] : hv;                      // (requested ahead) and the next stream's, under this frame
+                    hop_issue(b + (int)gridDim.x);
+                } else
                 fv = (tid < OVL) ? cst[tid] : xin[tid - OVL];            // one sample per thread
                 fw = wp[o.window + tid];
                 q0[tid] = fv * fw;
@@ -1107,8 +1123,22 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
             const int pi = Dft<S>::pidx(tid & (Dft<S>::N1 - 1), tid / Dft<S>::N1);
             const float xo = (q0[pi] + q1[pi]) * ow + oc;
             // one sample per thread: the first H go out, the rest is the new overlap tail (the old tail was read before the barrier)
+            if constexpr (HIO) {
+                // whole 16-byte pieces to host memory: lane 4j gathers the samples of lanes 4j + 1 .. 4j + 3 (every lane of the wave shuffles)
+                const float x1 = __shfl_down(xo, 1), x2 = __shfl_down(xo, 2), x3 = __shfl_down(xo, 3);
+                float* orow = a.wav_out + (size_t)b * a.out_stride;
+                if (tid < H) {
+                    if (H % 4 == 0 && (reinterpret_cast<size_t>(orow) & 15) == 0) {
+                        if ((tid & 3) == 0) __builtin_nontemporal_store(f32x4{xo, x1, x2, x3}, reinterpret_cast<f32x4*>(orow + tid));
+                    } else {
+                        __builtin_nontemporal_store(xo, orow + tid);
+                    }
+                }
+                else cis[tid - H] = xo;
+            } else {
             if (tid < H) a.wav_out[(size_t)b * a.out_stride + tid] = xo;
             else cis[tid - H] = xo;
+            }
             if constexpr (W8::HSTASH) {       // the frame's new GRU states: [KB][B][F2 * C2], 16 bytes per thread and store
                 constexpr int N4 = F2 * C2 / 4;
                 static_assert((F2 * C2) % 4 == 0 && W8::HST % 4 == 0, "16-byte state rows");

@@ -34,6 +34,8 @@ struct Impl {
     int EP = 0;                      // Shape::EP: activation + 8 * mask (FE_ACT_* / FE_MASK_*); 0 = SiLU, no mask function
     // fe_step_slots: launch_impl's choice for a.B streams, made with the SLOT instantiations (a.slots / a.capacity); nullptr without a frame kernel
     void (*launch_slots)(const SlotFrameArgs&, int max_wgs, hipStream_t, hipError_t*) = nullptr;
+    // fe_step_slots_pinned: the same choice with the HIO instantiations (wav_in / wav_out: device views of page-locked host memory)
+    void (*launch_slots_pinned)(const SlotFrameArgs&, int max_wgs, hipStream_t, hipError_t*) = nullptr;
 };
 
 // the instantiation a launcher picked, as fe_last_step_kernel reports it
@@ -53,7 +55,15 @@ constexpr const char* frame_kernel_slot_name(bool per_hop, bool persist) {
     return S::LOW == 2 ? "fe_frame_kernel<LOW=2, generic, slots>" : S::LOW == 1 ? "fe_frame_kernel<LOW=1, generic, slots>" : "fe_frame_kernel<generic, slots>";
 }
 
-template <class S, bool DBG, int MODE, bool T1, bool PERSIST, bool SLOT = false>
+// ... and its pinned form (fe_step_slots_pinned, the HIO instantiations): "slots, pinned"
+template <class S>
+constexpr const char* frame_kernel_pinned_name(bool per_hop, bool persist) {
+    if (per_hop && !persist) return S::LOW == 2 ? "fe_frame_kernel<LOW=2, per-hop, slots, pinned>" : S::LOW == 1 ? "fe_frame_kernel<LOW=1, per-hop, slots, pinned>" : "fe_frame_kernel<per-hop, slots, pinned>";
+    if (per_hop) return S::LOW == 2 ? "fe_frame_kernel<LOW=2, per-hop, persistent, slots, pinned>" : S::LOW == 1 ? "fe_frame_kernel<LOW=1, per-hop, persistent, slots, pinned>" : "fe_frame_kernel<per-hop, persistent, slots, pinned>";
+    return S::LOW == 2 ? "fe_frame_kernel<LOW=2, generic, slots, pinned>" : S::LOW == 1 ? "fe_frame_kernel<LOW=1, generic, slots, pinned>" : "fe_frame_kernel<generic, slots, pinned>";
+}
+
+template <class S, bool DBG, int MODE, bool T1, bool PERSIST, bool SLOT = false, bool HIO = false>
 void launch_one(const typename KernelArgs<SLOT>::type& a, int grid_x, hipStream_t st, hipError_t* err) {
     // the opt-in for > 64 KiB of dynamic LDS is a per-device function attribute: one flag per device, set once
     // (an engine may live on any GPU of the process; relaxed atomics - setting it twice is harmless)
@@ -61,43 +71,46 @@ void launch_one(const typename KernelArgs<SLOT>::type& a, int grid_x, hipStream_
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) dev = 0;
     if (!attr_set[dev].load(std::memory_order_relaxed)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fe_frame_kernel<S, DBG, MODE, T1, PERSIST, false, SLOT>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fe_frame_kernel<S, DBG, MODE, T1, PERSIST, false, SLOT, HIO>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)Lds<S>::BYTES);
         if (e != hipSuccess) { *err = e; return; }
         attr_set[dev].store(true, std::memory_order_relaxed);
     }
     dim3 grid(grid_x), block(kThreads);
-    note_kernel(SLOT ? frame_kernel_slot_name<S>(T1, PERSIST) : frame_kernel_name<S>(DBG, T1, PERSIST));
-    hipLaunchKernelGGL((fe_frame_kernel<S, DBG, MODE, T1, PERSIST, false, SLOT>), grid, block, Lds<S>::BYTES, st, a);
+    note_kernel(HIO ? frame_kernel_pinned_name<S>(T1, PERSIST) : SLOT ? frame_kernel_slot_name<S>(T1, PERSIST) : frame_kernel_name<S>(DBG, T1, PERSIST));
+    hipLaunchKernelGGL((fe_frame_kernel<S, DBG, MODE, T1, PERSIST, false, SLOT, HIO>), grid, block, Lds<S>::BYTES, st, a);
     *err = hipGetLastError();
 }
 
 // a.step_kernel (fe_set_step_kernel; the handle's default comes from the environment variable FE_WG8, else 1):
 //   0 = the four-wave kernel everywhere; 1 = the 512-thread kernel (fe_frame8.hip.h: two waves per SIMD, channel-grouped GRU gates)
 //   for the per-hop step of the shapes it is built for, up to one stream per CU; 2 = also above that (persistent workgroups)
-template <class S, bool DBG, bool PERSIST, bool SLOT = false>
+template <class S, bool DBG, bool PERSIST, bool SLOT = false, bool HIO = false>
 void launch_one8(const typename KernelArgs<SLOT>::type& a, int grid_x, hipStream_t st, hipError_t* err) {
     static std::atomic<bool> attr_set[kMaxDevices];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) dev = 0;
     if (!attr_set[dev].load(std::memory_order_relaxed)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fe_frame8_kernel<S, DBG, PERSIST, SLOT>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fe_frame8_kernel<S, DBG, PERSIST, SLOT, HIO>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)Wg8<S>::BYTES);
         if (e != hipSuccess) { *err = e; return; }
         attr_set[dev].store(true, std::memory_order_relaxed);
     }
     dim3 grid(grid_x), block(kThreads8);
-    if constexpr (SLOT) note_kernel(PERSIST ? "fe_frame8_kernel<persistent, slots>" : "fe_frame8_kernel<slots>");
+    if constexpr (HIO) note_kernel(PERSIST ? "fe_frame8_kernel<persistent, slots, pinned>" : "fe_frame8_kernel<slots, pinned>");
+    else if constexpr (SLOT) note_kernel(PERSIST ? "fe_frame8_kernel<persistent, slots>" : "fe_frame8_kernel<slots>");
     else note_kernel(DBG ? "fe_frame8_kernel<debug>" : PERSIST ? "fe_frame8_kernel<persistent>" : "fe_frame8_kernel");
-    hipLaunchKernelGGL((fe_frame8_kernel<S, DBG, PERSIST, SLOT>), grid, block, Wg8<S>::BYTES, st, a);
+    hipLaunchKernelGGL((fe_frame8_kernel<S, DBG, PERSIST, SLOT, HIO>), grid, block, Wg8<S>::BYTES, st, a);
     *err = hipGetLastError();
 }
 
 // max_wgs: workgroups that are resident at once (one per CU: 129+ KiB of LDS and waves_per_eu(1,1)); a batch with more
 // streams runs on a grid of max_wgs PERSISTENT workgroups, each walking its streams b, b + grid, ...
 // SLOT (fe_step_slots): the same choice, made with the slotted instantiations (streaming mode; no debug dumps or cycle probes)
-template <class S, bool SLOT = false>
+// HIO (fe_step_slots_pinned; SLOT only): ... with the instantiations that read and write the audio in page-locked host memory
+template <class S, bool SLOT = false, bool HIO = false>
 void launch_impl(const typename KernelArgs<SLOT>::type& a, int max_wgs, hipStream_t st, hipError_t* err) {
+    static_assert(SLOT || !HIO, "host audio: slotted instantiations only");
     const int slots = max_wgs * Lds<S>::OCC;         // resident workgroups
     const int grid = a.B < slots ? a.B : slots;
     if constexpr (Wg8<S>::OK) {
@@ -109,8 +122,8 @@ void launch_impl(const typename KernelArgs<SLOT>::type& a, int max_wgs, hipStrea
             const bool dbg8 = a.dbg != nullptr || a.clk != nullptr;
 #endif
             if constexpr (SLOT) {
-                if (grid8 == a.B) { launch_one8<S, false, false, true>(a, grid8, st, err); return; }
-                if (a.step_kernel > 1) { launch_one8<S, false, true, true>(a, grid8, st, err); return; }
+                if (grid8 == a.B) { launch_one8<S, false, false, true, HIO>(a, grid8, st, err); return; }
+                if (a.step_kernel > 1) { launch_one8<S, false, true, true, HIO>(a, grid8, st, err); return; }
             } else {
             if (grid8 == a.B) {
                 if (dbg8) launch_one8<S, true, false>(a, grid8, st, err);
@@ -123,10 +136,10 @@ void launch_impl(const typename KernelArgs<SLOT>::type& a, int max_wgs, hipStrea
     }
     if constexpr (SLOT) {
         if (a.T == 1) {
-            if (grid == a.B) launch_one<S, false, FE_MODE_STREAM, true, false, true>(a, grid, st, err);
-            else launch_one<S, false, FE_MODE_STREAM, true, true, true>(a, grid, st, err);
+            if (grid == a.B) launch_one<S, false, FE_MODE_STREAM, true, false, true, HIO>(a, grid, st, err);
+            else launch_one<S, false, FE_MODE_STREAM, true, true, true, HIO>(a, grid, st, err);
         }
-        else launch_one<S, false, -1, false, true, true>(a, grid, st, err);
+        else launch_one<S, false, -1, false, true, true, HIO>(a, grid, st, err);
         return;
     }
 #ifdef FE_PROBE_HOT
@@ -191,6 +204,7 @@ Impl make_impl() {
     im.many_one_round = Lds<S>::MANY_ONE_ROUND;
     im.EP = S::EP;
     im.launch_slots = &launch_impl<S, true>;
+    im.launch_slots_pinned = &launch_impl<S, true, true>;
     return im;
     }
 }

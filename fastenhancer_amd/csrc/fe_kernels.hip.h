@@ -368,6 +368,26 @@ struct SlotFrameArgs : FrameArgs {
 template <bool SLOT> struct KernelArgs { using type = FrameArgs; };
 template <> struct KernelArgs<true> { using type = SlotFrameArgs; };
 
+// The pinned step (fe_step_slots_pinned; the HIO instantiations, SLOT only): wav_in / wav_out are device views of page-locked HOST
+// memory, so every audio access crosses PCIe.  Output rows go out as non-temporal 16-byte stores - one posted write each - where the row
+// is 16-byte aligned, else float by float.  (Vector stores only; the host reads the rows once the stream has completed, so no fence.)
+__device__ __forceinline__ void hio_store_row(float* out, const float* src, int n, int tid, int nth) {
+    int done = 0;
+    if ((reinterpret_cast<size_t>(out) & 15) == 0) {
+        const int n4 = n >> 2;
+        f32x4* o4 = reinterpret_cast<f32x4*>(out);
+        for (int i = tid; i < n4; i += nth) {
+            const f32x4 v = {src[4 * i], src[4 * i + 1], src[4 * i + 2], src[4 * i + 3]};
+            __builtin_nontemporal_store(v, o4 + i);
+        }
+        done = 4 * n4;
+    }
+    for (int i = done + tid; i < n; i += nth) __builtin_nontemporal_store(src[i], out + i);
+}
+__device__ __forceinline__ void hio_zero_row(float* out, int n, int tid, int nth) {
+    for (int i = tid; i < n; i += nth) __builtin_nontemporal_store(0.0f, out + i);
+}
+
 // ------------------------------------------------------------------------------------------
 #ifndef FE_PROBE_TID
 #define FE_PROBE_TID 0      // the thread whose clock the phase probes record (measurement builds: -DFE_PROBE_TID=256 = wave 4 of the 512-thread kernel)
@@ -1459,8 +1479,12 @@ __device__ __forceinline__ void attention_head(const float* G, float* Hl, int ho
 // T x (state round trip + one GRU phase) instead of T x (whole frame): ~12 frames in flight for FastEnhancer_B.
 // SLOT (fe_step_slots): stream b's state is slot a.slots[b] of a state sized for a.capacity streams (sb, nst below); a slot out of range
 // gets zero output rows and neither reads nor writes state.  SLOT = false: sb = b, nst = a.B - the code of the plain step.
-template <class S, bool DBG, int MODE, bool T1, bool PERSIST, bool PIPE = false, bool SLOT = false>
+// HIO (fe_step_slots_pinned; SLOT only): the audio is page-locked host memory.  The hop of the next frame a workgroup runs is requested
+// ahead and held in registers (hv, hop_issue below): its first one before any other load of the kernel, so that the PCIe round trip runs
+// under the prologue; frame t + 1's (or the next stream's first) as soon as frame t's has been taken.  Rows go out through hio_store_row.
+template <class S, bool DBG, int MODE, bool T1, bool PERSIST, bool PIPE = false, bool SLOT = false, bool HIO = false>
 __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(Lds<S>::OCC, Lds<S>::OCC))) fe_frame_kernel(typename KernelArgs<SLOT>::type a_in) {
+    static_assert(!HIO || (SLOT && !PIPE && !DBG), "host audio: slotted streaming instantiations only");
     typename KernelArgs<SLOT>::type a = a_in;
 #ifdef FE_PROBE_HOT          // measurement builds: the production instantiations keep the cycle probes (tools/gpu_phases.py ... 1)
     if constexpr (!DBG) a.dbg = nullptr;
@@ -1485,6 +1509,20 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
     const int wave0 = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wave = wave0;
     const int li = lane & 15, lg = lane >> 4;
+    constexpr int HNPT = HIO ? N / kThreads : 1;     // (HIO) frame samples per thread, as in the STFT below; hv[q] = sample tid + q kThreads
+    float hv[HNPT];
+    auto hop_issue = [&](int bb, int tt) {
+        if constexpr (HIO) {
+            const bool ok = bb < a.B && tt < a.T;
+            const float* xin = a.wav_in + (size_t)(ok ? bb : 0) * a.in_stride + (size_t)(ok ? tt : 0) * H;
+#pragma unroll
+            for (int q = 0; q < HNPT; ++q) {
+                const int n = tid0 + q * kThreads;
+                hv[q] = (ok && n >= OVL) ? xin[n - OVL] : 0.0f;
+            }
+        }
+    };
+    hop_issue((int)blockIdx.x, 0);
     const float* __restrict__ wp = a.wp;
     WSrc<Lds<S>::STAGED> wb;
     constexpr PackedOffsets o = Pack<S>::v;
@@ -1581,9 +1619,12 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
         nst = a.capacity;
         if ((unsigned)sb >= (unsigned)nst) {         // (wave-uniform) no state: the stream's output rows are zero
             float* out = a.wav_out + (size_t)b * a.out_stride;
+            if constexpr (HIO) hio_zero_row(out, a.T * S::HOP, tid, kThreads);
+            else
             for (int n = tid; n < a.T * S::HOP; n += kThreads) out[n] = 0.0f;
             __builtin_amdgcn_s_waitcnt(0);           // (the weight stage issued for this stream has landed before the next one or the end)
             b += (int)gridDim.x;
+            hop_issue(b, 0);
             continue;
         }
     }
@@ -1745,8 +1786,13 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
 #pragma unroll
                 for (int q = 0; q < NPT; ++q) {
                     const int n = tid + q * kThreads;
-                    fv[q] = (n < OVL) ? cst[n] : xin[n - OVL];
+                    if constexpr (HIO) fv[q] = (n < OVL) ? cst[n] : hv[q];          // (the hop was requested ahead: hop_issue)
+                    else fv[q] = (n < OVL) ? cst[n] : xin[n - OVL];
                     fw[q] = win[n];
+                }
+                if constexpr (HIO) {                     // the next hop this workgroup runs: frame t + 1, else the next stream's first
+                    if (t + 1 < a.T) hop_issue(b, t + 1);
+                    else hop_issue(b + (int)gridDim.x, 0);
                 }
 #pragma unroll
                 for (int q = 0; q < NPT; ++q) {
@@ -3286,6 +3332,8 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                 for (int n = tid; n < N; n += kThreads) fr[n] = xo[n];
             } else if (mode == FE_MODE_STREAM) {
                 float* out = a.wav_out + (size_t)b * a.out_stride + (size_t)t * H;
+                if constexpr (HIO) hio_store_row(out, xo, H, tid, kThreads);
+                else
                 for (int n = tid; n < H; n += kThreads) out[n] = xo[n];
             } else {
                 // torch.istft(center=True) (functional/audio_modules.py:117-119): y = OLA / sum_t w^2, trimmed by N/2.

@@ -298,6 +298,59 @@ class Engine:
                        "fe_state_reset_slots")
         self._slots_keep = sl
 
+    def _pinned_audio(self, name: str, x: Optional[Tensor], rows: int, T: int) -> Tensor:
+        """x -> a page-locked CPU float32 tensor [rows, T*H] (row stride free), or a fresh one when x is None.  Anything else is a
+        ValueError before any native call: the kernel reads and writes this memory over PCIe, and unpinned memory would fault it."""
+        H = self.cfg.hop_size
+        if x is None:
+            return torch.empty(rows, T * H, dtype=torch.float32).pin_memory()
+        if not isinstance(x, Tensor) or x.device.type != "cpu":
+            raise ValueError(f"{name} must be a CPU tensor in page-locked memory (pin_memory()), not {getattr(x, 'device', type(x).__name__)}")
+        if not x.is_pinned():
+            raise ValueError(f"{name} is not in page-locked memory: pin the buffer (pin_memory())")
+        if x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1 or tuple(x.shape) != (rows, T * H):
+            raise ValueError(f"{name} must be float32 [{rows}, {T * H}] with unit stride along the samples, got {x.dtype} {tuple(x.shape)}")
+        return x
+
+    def step_pinned(self, wav_in: Tensor, state: Tensor, wav_out: Optional[Tensor] = None, T: int = 1) -> Tensor:
+        """fe_step_pinned: wav_in [B, T*H] in page-locked HOST memory -> wav_out [B, T*H] in page-locked host memory (allocated when None),
+        one launch that reads and writes the audio over PCIe; state (device) updated in place.  Asynchronous on the current stream:
+        synchronise it before reading wav_out or rewriting wav_in."""
+        if not isinstance(wav_in, Tensor) or wav_in.dim() != 2:
+            raise ValueError("wav_in must be a 2-D tensor [B, T*H]")
+        B = wav_in.shape[0]
+        wav_in = self._pinned_audio("wav_in", wav_in, B, T)
+        wav_out = self._pinned_audio("wav_out", wav_out, B, T)
+        self._require_gpu()
+        assert state.is_cuda and state.numel() == self.state_floats(B) and state.is_contiguous()
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.fe_step_pinned(self._h, ctypes.c_void_p(wav_in.data_ptr()), wav_in.stride(0) if B > 1 else T * self.cfg.hop_size,
+                                               _ptr(state), ctypes.c_void_p(wav_out.data_ptr()), wav_out.stride(0) if B > 1 else T * self.cfg.hop_size,
+                                               B, T, _stream(self.device)), "fe_step_pinned")
+        self._pinned_keep = (wav_in, wav_out)          # (alive until the next call - the launch is asynchronous)
+        return wav_out
+
+    def step_slots_pinned(self, wav_in: Tensor, state: Tensor, capacity: int, slots, wav_out: Optional[Tensor] = None, T: int = 1) -> Tensor:
+        """fe_step_slots_pinned: step_slots with wav_in / wav_out [n, T*H] in page-locked HOST memory (wav_out allocated when None).
+        slots as for step_slots.  Asynchronous on the current stream: synchronise it before reading wav_out or rewriting wav_in."""
+        if not isinstance(wav_in, Tensor) or wav_in.dim() != 2:
+            raise ValueError("wav_in must be a 2-D tensor [n, T*H]")
+        n = wav_in.shape[0]
+        wav_in = self._pinned_audio("wav_in", wav_in, n, T)
+        wav_out = self._pinned_audio("wav_out", wav_out, n, T)
+        sl = self._slot_tensor(slots, capacity)
+        self._require_gpu()
+        assert sl.numel() == n, (sl.numel(), n)
+        assert state.is_cuda and state.numel() == self.state_floats(capacity) and state.is_contiguous()
+        H = self.cfg.hop_size
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.fe_step_slots_pinned(self._h, ctypes.c_void_p(wav_in.data_ptr()), wav_in.stride(0) if n > 1 else T * H, _ptr(state),
+                                                     int(capacity), _ptr(sl), ctypes.c_void_p(wav_out.data_ptr()), wav_out.stride(0) if n > 1 else T * H,
+                                                     n, T, _stream(self.device)), "fe_step_slots_pinned")
+        self._slots_keep = sl
+        self._pinned_keep = (wav_in, wav_out)
+        return wav_out
+
     def step_host(self, wav_in: Tensor, state: Tensor, wav_out: Optional[Tensor] = None, T: int = 1) -> Tensor:
         """fe_step_host: wav_in [B, n*T*H] in HOST memory (pinned for full speed) -> wav_out [B, n*T*H] in host memory, n calls of T hops
         each with the copies of the neighbouring calls under each kernel; state (device) updated in place.  Asynchronous on the current

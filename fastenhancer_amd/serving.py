@@ -1,8 +1,9 @@
 """StreamPool: streams that join and leave one state buffer (fe_step_slots / fe_state_reset_slots).
 
 The pool owns a state buffer sized for `capacity` streams.  open() hands out a free slot and resets its state; close() frees it;
-step() advances only the streams named, each reading and writing its own slot - no gather or scatter of state.  No threads,
-no queues: the caller decides which streams have a hop ready on each tick."""
+step() advances only the streams named, each reading and writing its own slot - no gather or scatter of state; step_host() does the
+same for audio in page-locked host memory (fe_step_slots_pinned).  No threads, no queues: the caller decides which streams have a hop
+ready on each tick."""
 from __future__ import annotations
 
 from typing import List, Optional, Sequence
@@ -47,3 +48,11 @@ class StreamPool:
             if s not in self._open:
                 raise ValueError(f"slot {s} is not open")
         return self.engine.step_slots(wav_in, self.state, self.capacity, list(slots), wav_out=wav_out, T=T)
+
+    def step_host(self, slots: Sequence[int], wav_in: Tensor, wav_out: Optional[Tensor] = None, T: int = 1) -> Tensor:
+        """step() for audio in page-locked HOST memory (fe_step_slots_pinned): wav_in [n, T*H] pinned -> wav_out [n, T*H] pinned
+        (allocated when None), in one launch.  Asynchronous on the current stream: synchronise it before reading wav_out."""
+        for s in slots:
+            if s not in self._open:
+                raise ValueError(f"slot {s} is not open")
+        return self.engine.step_slots_pinned(wav_in, self.state, self.capacity, list(slots), wav_out=wav_out, T=T)

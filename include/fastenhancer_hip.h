@@ -178,6 +178,20 @@ int fe_step_slots(fe_handle* h, const float* wav_in_dev, size_t in_stride, float
  * fe_step_slots; out-of-range slots are skipped. */
 int fe_state_reset_slots(fe_handle* h, float* state_dev, int capacity, const int* slots_dev, int n, void* stream);
 
+/* fe_step / fe_step_slots for audio in PAGE-LOCKED HOST memory: one launch whose kernel reads each hop over PCIe and writes the enhanced
+ * hop back there - no staging buffers, copies or events, and one node when captured into a graph.  Row layout, strides, families, slot
+ * rules and the kernel choice are those of fe_step_slots (fe_step_pinned: capacity = B, stream i = slot i); the results are theirs on
+ * device copies of the same rows, bit for bit.  fe_last_step_kernel names the kernel with "pinned" in the brackets.
+ *   Pinning rule: every float of both audio ranges must be host memory that is page-locked and mapped for the current device
+ *     (hipHostMalloc / hipHostRegister; torch's pin_memory()).  The first and last float of each range are looked up before anything is
+ *     launched; pageable or device memory is FE_ERR_INVALID_ARG.  state_dev and slots_dev are device memory, as for fe_step_slots.
+ *   Completion rule: the call is asynchronous on `stream`.  wav_in_host must not be rewritten, nor wav_out_host read, until `stream`
+ *     has completed the step (hipStreamSynchronize or an event); the output is visible to the host from then on. */
+int fe_step_pinned(fe_handle* h, const float* wav_in_host, size_t in_stride, float* state_dev, float* wav_out_host, size_t out_stride,
+                   int B, int T, void* stream);
+int fe_step_slots_pinned(fe_handle* h, const float* wav_in_host, size_t in_stride, float* state_dev, int capacity, const int* slots_dev,
+                         float* wav_out_host, size_t out_stride, int n, int T, void* stream);
+
 /* The same step for callers whose audio lives in HOST memory (the reference's scripts/test_onnx.py feeds numpy arrays hop by hop):
  * n_calls consecutive fe_step calls of T hops each, hop block c = hops c*T .. c*T+T-1 of
  *   wav_in_host [b*in_stride + t*H + n], wav_out_host [b*out_stride + t*H + n]   (page-locked for asynchronous copies; pageable works, slower)
