@@ -16,7 +16,6 @@
 //    vector-ALU dot products over 16-byte weight loads, software-pipelined one row ahead: these phases are bound by the
 //    L2 -> CU path (780 KB of MLP weights per frame for xt), not by arithmetic.
 #pragma once
-#include <atomic>
 
 #include "fe_kernels.hip.h"
 
@@ -1363,19 +1362,9 @@ struct BImpl {
 
 template <class S, bool HOT, bool PROF, bool DBG, bool OCC2 = false>
 void blaunch_one(const BArgs& a, int grid, hipStream_t st, hipError_t* err) {
-    static std::atomic<bool> attr_set[64];           // per device (see fe_impl.h::launch_one)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_set[dev].load(std::memory_order_relaxed)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&bsrnn_frame_kernel<S, HOT, PROF, DBG, OCC2>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)BLds<S>::BYTES);
-        if (e != hipSuccess) { *err = e; return; }
-        attr_set[dev].store(true, std::memory_order_relaxed);
-    }
-    note_kernel(DBG ? "bsrnn_frame_kernel<debug>" : PROF ? "bsrnn_frame_kernel<profile>" : HOT ? (OCC2 ? "bsrnn_frame_kernel<per-hop, two workgroups per CU>" : "bsrnn_frame_kernel<per-hop>")
-                    : (OCC2 ? "bsrnn_frame_kernel<generic, two workgroups per CU>" : "bsrnn_frame_kernel<generic>"));
-    hipLaunchKernelGGL((bsrnn_frame_kernel<S, HOT, PROF, DBG, OCC2>), dim3(grid), dim3(kThreads), BLds<S>::BYTES, st, a);
-    *err = hipGetLastError();
+    const char* name = DBG ? "bsrnn_frame_kernel<debug>" : PROF ? "bsrnn_frame_kernel<profile>" : HOT ? (OCC2 ? "bsrnn_frame_kernel<per-hop, two workgroups per CU>" : "bsrnn_frame_kernel<per-hop>")
+                           : (OCC2 ? "bsrnn_frame_kernel<generic, two workgroups per CU>" : "bsrnn_frame_kernel<generic>");
+    *err = launch<&bsrnn_frame_kernel<S, HOT, PROF, DBG, OCC2>>(name, dim3(grid), dim3(kThreads), BLds<S>::BYTES, st, a);
 }
 
 template <class S>
@@ -1399,20 +1388,10 @@ void blaunch_impl(const BArgs& a, int max_wgs, hipStream_t st, hipError_t* err) 
 
 template <class S, bool OCC2, int PART>
 void blaunch_part(const BArgs& a, int grid, hipStream_t st, hipError_t* err) {
-    auto* fn = &bsrnn_frame_kernel<S, true, false, false, OCC2, false, PART>;
     using LP = BLds<S, (PART == 2 || PART == 3) ? PART : 0>;
-    static std::atomic<bool> attr_set[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_set[dev].load(std::memory_order_relaxed)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LP::BYTES);
-        if (e != hipSuccess) { *err = e; return; }
-        attr_set[dev].store(true, std::memory_order_relaxed);
-    }
-    note_kernel(PART == 1 ? (OCC2 ? "bsrnn_frame_kernel<PART 1, two workgroups per CU>" : "bsrnn_frame_kernel<PART 1>")
-                : PART == 2 ? "bsrnn_frame_kernel<PART 2>" : "bsrnn_frame_kernel<PART 3>");      // (r6: their own LDS plans, up to four workgroups per CU)
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(kThreads), LP::BYTES, st, a);
-    *err = hipGetLastError();
+    const char* name = PART == 1 ? (OCC2 ? "bsrnn_frame_kernel<PART 1, two workgroups per CU>" : "bsrnn_frame_kernel<PART 1>")
+                       : PART == 2 ? "bsrnn_frame_kernel<PART 2>" : "bsrnn_frame_kernel<PART 3>";      // (r6: their own LDS plans, up to four workgroups per CU)
+    *err = launch<&bsrnn_frame_kernel<S, true, false, false, OCC2, false, PART>>(name, dim3(grid), dim3(kThreads), LP::BYTES, st, a);
 }
 
 // grid of a per-stream front / tail launch (PART 3 / 2): their own LDS plans fit four times per CU
@@ -1450,22 +1429,12 @@ void blaunch_split_impl(const BArgs& a, int max_wgs, hipStream_t st, hipError_t*
     else blaunch_part<S, false, 1>(a, a.B < max_wgs ? a.B : max_wgs, st, err);
     if (*err != hipSuccess) return;
     {
-        auto* fn = &bsrnn_mlp_kernel<S>;
-        static std::atomic<bool> attr_set[64];
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-        if (!attr_set[dev].load(std::memory_order_relaxed)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BMlpLds<S>::BYTES);
-            if (e != hipSuccess) { *err = e; return; }
-            attr_set[dev].store(true, std::memory_order_relaxed);
-        }
         BArgs am = a;
         const bool msplit = S::C == 16 && a.B <= max_wgs;      // (fewer 64-stream groups than CUs: one sixteen-stream tile per workgroup, column tiles over its waves)
         am.mlp_tpw = msplit ? 0 : 1;
         const int groups = msplit ? (a.B + 15) / 16 : (a.B + 16 * kWaves - 1) / (16 * kWaves);
-        note_kernel(msplit ? "bsrnn_mlp_kernel<one 16-stream tile per workgroup>" : "bsrnn_mlp_kernel");
-        hipLaunchKernelGGL(fn, dim3(2 * kBands * groups), dim3(kThreads), BMlpLds<S>::BYTES, st, am);
-        *err = hipGetLastError();
+        *err = launch<&bsrnn_mlp_kernel<S>>(msplit ? "bsrnn_mlp_kernel<one 16-stream tile per workgroup>" : "bsrnn_mlp_kernel", dim3(2 * kBands * groups),
+                                            dim3(kThreads), BMlpLds<S>::BYTES, st, am);
         if (*err != hipSuccess) return;
     }
     if (FITS2 && a.B > max_wgs) blaunch_part<S, FITS2, 2>(a, bpart_grid<S, 2>(a.B, max_wgs), st, err);
@@ -1474,17 +1443,7 @@ void blaunch_split_impl(const BArgs& a, int max_wgs, hipStream_t st, hipError_t*
 
 template <class S, bool MULTI>
 void blaunch_mlp_one(const BArgs& am, int groups, hipStream_t st, hipError_t* err) {
-    auto* fn = &bsrnn_mlp_kernel<S, MULTI>;
-    static std::atomic<bool> attr_set[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_set[dev].load(std::memory_order_relaxed)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BMlpLds<S>::BYTES);
-        if (e != hipSuccess) { *err = e; return; }
-        attr_set[dev].store(true, std::memory_order_relaxed);
-    }
-    hipLaunchKernelGGL(fn, dim3(2 * kBands * groups), dim3(kThreads), BMlpLds<S>::BYTES, st, am);
-    *err = hipGetLastError();
+    *err = launch<&bsrnn_mlp_kernel<S, MULTI>>(nullptr, dim3(2 * kBands * groups), dim3(kThreads), BMlpLds<S>::BYTES, st, am);      // (blaunch_mlp has noted it)
 }
 
 template <class S>
@@ -1519,19 +1478,8 @@ void blaunch_sb_impl(const BArgs& a, const SbOffsets& so, int total_floats, int 
 
 template <class S>
 void blaunch_pipe_impl(const BArgs& a, hipStream_t st, hipError_t* err) {
-    auto* fn = &bsrnn_frame_kernel<S, false, false, false, false, true>;
-    static std::atomic<bool> attr_set[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_set[dev].load(std::memory_order_relaxed)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BLds<S>::BYTES);
-        if (e != hipSuccess) { *err = e; return; }
-        attr_set[dev].store(true, std::memory_order_relaxed);
-    }
-    BArgs args = a;
-    void* kargs[] = {&args};
-    note_kernel("bsrnn_frame_kernel<time-pipelined>");
-    *err = hipLaunchCooperativeKernel(reinterpret_cast<const void*>(fn), dim3(a.B * a.pipe_p), dim3(kThreads), kargs, (unsigned int)BLds<S>::BYTES, st);
+    *err = launch_coop<&bsrnn_frame_kernel<S, false, false, false, false, true>>("bsrnn_frame_kernel<time-pipelined>", dim3(a.B * a.pipe_p), dim3(kThreads),
+                                                                                 BLds<S>::BYTES, st, a);
 }
 
 template <class S>

@@ -698,34 +698,10 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
 template <class S, bool PROF = false, bool FUSED = false>
 void blaunch_ov(const BArgs& a, int grid, hipStream_t st, hipError_t* err) {
     if constexpr (S::C == 16) {
-        auto* fn = &bsrnn_ov_kernel<S, PROF, FUSED>;
-        static std::atomic<bool> attr_set[64];
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-        if (!attr_set[dev].load(std::memory_order_relaxed)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BOvLds<S>::BYTES);
-            if (e != hipSuccess) { *err = e; return; }
-            attr_set[dev].store(true, std::memory_order_relaxed);
-        }
-        if constexpr (FUSED) {
-            // the workgroups of a sixteen-stream tile wait for each other: a cooperative launch (co-residency guaranteed, or refused)
-            static const bool plain = [] { const char* e = getenv("FE_EXP_FUSED_PLAIN"); return e && e[0] == '1'; }();      // (timing experiment)
-            if (plain) {
-                hipLaunchKernelGGL(fn, dim3(grid), dim3(kThreads), BOvLds<S>::BYTES, st, a);
-                *err = hipGetLastError();
-                note_kernel("bsrnn_ov_kernel<fused step, plain launch>");
-                return;
-            }
-            BArgs args = a;
-            void* kargs[] = {&args};
-            *err = hipLaunchCooperativeKernel(reinterpret_cast<const void*>(fn), dim3(grid), dim3(kThreads), kargs, (unsigned int)BOvLds<S>::BYTES, st);
-            if (*err == hipSuccess) note_kernel("bsrnn_ov_kernel<fused step>");
-            else (void)hipGetLastError();
-            return;
-        }
-        note_kernel(PROF ? "bsrnn_ov_kernel<profile>" : "bsrnn_ov_kernel");
-        hipLaunchKernelGGL(fn, dim3(grid), dim3(kThreads), BOvLds<S>::BYTES, st, a);
-        *err = hipGetLastError();
+        // FUSED: the workgroups of a sixteen-stream tile wait for each other - a cooperative launch (co-residency guaranteed, or refused: the
+        // caller then falls back to the three launches, so a refusal notes nothing and leaves no error behind)
+        if constexpr (FUSED) *err = launch_coop<&bsrnn_ov_kernel<S, PROF, FUSED>, true>("bsrnn_ov_kernel<fused step>", dim3(grid), dim3(kThreads), BOvLds<S>::BYTES, st, a);
+        else *err = launch<&bsrnn_ov_kernel<S, PROF, FUSED>>(PROF ? "bsrnn_ov_kernel<profile>" : "bsrnn_ov_kernel", dim3(grid), dim3(kThreads), BOvLds<S>::BYTES, st, a);
     } else {
         *err = hipErrorInvalidValue;
     }

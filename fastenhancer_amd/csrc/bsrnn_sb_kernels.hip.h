@@ -663,29 +663,11 @@ __global__ void __launch_bounds__(kSbThreads) __attribute__((amdgpu_waves_per_eu
 
 template <class S>
 void sb_launch_layers(const SbArgs& a, hipStream_t st, hipError_t* err) {
-    static std::atomic<bool> attr_set[64];      // (more than 64 KB of dynamic LDS; per device: a process may drive several)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+    const dim3 grid((a.B + kSbStreams - 1) / kSbStreams), block(kSbThreads);
     if constexpr (SbLds<S>::FITS) {
-        auto* fn = &bsrnn_sb_layers_kernel<S>;
-        if (!attr_set[dev].load(std::memory_order_relaxed)) {
-            *err = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SbLds<S>::BYTES);
-            if (*err != hipSuccess) return;
-            attr_set[dev].store(true, std::memory_order_relaxed);
-        }
-        note_kernel("bsrnn_sb_layers_kernel");
-        hipLaunchKernelGGL(fn, dim3((a.B + kSbStreams - 1) / kSbStreams), dim3(kSbThreads), SbLds<S>::BYTES, st, a);
-        *err = hipGetLastError();
+        *err = launch<&bsrnn_sb_layers_kernel<S>>("bsrnn_sb_layers_kernel", grid, block, SbLds<S>::BYTES, st, a);
     } else if constexpr (Sb64Lds<S>::FITS) {
-        auto* fn = &bsrnn_sb64_layers_kernel<S>;
-        if (!attr_set[dev].load(std::memory_order_relaxed)) {
-            *err = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)Sb64Lds<S>::BYTES);
-            if (*err != hipSuccess) return;
-            attr_set[dev].store(true, std::memory_order_relaxed);
-        }
-        note_kernel("bsrnn_sb64_layers_kernel");
-        hipLaunchKernelGGL(fn, dim3((a.B + kSbStreams - 1) / kSbStreams), dim3(kSbThreads), Sb64Lds<S>::BYTES, st, a);
-        *err = hipGetLastError();
+        *err = launch<&bsrnn_sb64_layers_kernel<S>>("bsrnn_sb64_layers_kernel", grid, block, Sb64Lds<S>::BYTES, st, a);
     } else {
         *err = hipErrorNotSupported;
     }

@@ -1091,12 +1091,20 @@ static size_t tk_floats(const fe_handle* h) {
     return (size_t)2 * d.NL * (d.KT - 1) * d.F1 * d.C1;
 }
 
+// The streaming state of `rows` streams, in floats from its start: cache_stft [rows][N-H] at 0, cache_istft [rows][N-H], then the model's
+// own state - FastEnhancer: h (GRU states or K / V rings, rows * hstate()), tk (the time_kernel conv caches), total floats; the other
+// families lay out their own state from h on.  rows = B for fe_step, the capacity for the slotted entry points.
+struct StateLayout { size_t cache_istft, h, tk, total; };
+static StateLayout state_layout(const fe_handle* h, size_t rows) {
+    const size_t ovl = (size_t)(h->d.NFFT - h->d.HOP), hs = 2 * rows * ovl, tk = hs + rows * h->d.hstate();
+    return {rows * ovl, hs, tk, tk + rows * tk_floats(h)};
+}
+
 size_t fe_state_floats(const fe_handle* h, int B) {
     if (!h || B <= 0) return 0;
-    const Dims& d = h->d;
     size_t n = 0;
-    if (visit_baseline(h->cfg.arch, [&](auto F) { n = (size_t)B * 2 * (size_t)(d.NFFT - d.HOP) + F.state_floats(h, B); })) return n;
-    return (size_t)B * (2 * (size_t)(d.NFFT - d.HOP) + d.hstate() + tk_floats(h));
+    if (visit_baseline(h->cfg.arch, [&](auto F) { n = state_layout(h, B).h + F.state_floats(h, B); })) return n;
+    return state_layout(h, B).total;
 }
 
 int fe_state_init(fe_handle* h, float* state_dev, int B, void* stream) {
@@ -1122,56 +1130,6 @@ static const fe::Impl* step_impl(const fe_handle* h, int B, int T, bool probe) {
     return h->impl;
 }
 
-static int run_step(fe_handle* h, const float* wav_in, size_t in_stride, float* state, float* wav_out, size_t out_stride,
-                    int B, int T, float* dbg, unsigned long long* clk, void* stream) {
-    int rc = check_ready(h);
-    if (rc != FE_OK) return rc;
-    KernelLogScope klog_(h);
-    if (!wav_in || !state || !wav_out || B <= 0 || T <= 0) return fail(FE_ERR_INVALID_ARG, "bad argument");
-    const Dims& d = h->d;
-    if (in_stride < (size_t)T * d.HOP && B > 1) return fail(FE_ERR_INVALID_ARG, "in_stride %zu < T*H", in_stride);
-    if (out_stride < (size_t)T * d.HOP && B > 1) return fail(FE_ERR_INVALID_ARG, "out_stride %zu < T*H", out_stride);
-    if (visit_baseline(h->cfg.arch, [&](auto F) {
-            auto a = F.args(h, B, T);
-            a.clk = clk;
-            a.dbg = dbg;
-            a.dbg_stride = F.impl(h)->dbg_floats;
-            const size_t ovl = (size_t)(d.NFFT - d.HOP);
-            a.mode = fe::FE_MODE_STREAM;
-            a.wav_in = wav_in; a.wav_out = wav_out; a.in_stride = in_stride; a.out_stride = out_stride;
-            a.cache_stft = state; a.cache_istft = state + (size_t)B * ovl; F.state(a) = state + 2 * (size_t)B * ovl;
-            rc = F.launch(h, a, stream);
-        }))
-        return rc;
-    if (d.BD) return fail(FE_ERR_UNSUPPORTED_CONFIG, "%s", kNoncausalNoStep);
-    rc = ensure_scratch(h, B);
-    if (rc != FE_OK) return rc;
-    fe::FrameArgs a = base_args(h, B, T);
-    const size_t ovl = (size_t)(d.NFFT - d.HOP);
-    a.wav_in = wav_in;
-    a.wav_out = wav_out;
-    a.in_stride = in_stride;
-    a.out_stride = out_stride;
-    a.cache_stft = state;
-    a.cache_istft = state + (size_t)B * ovl;
-    a.h = state + 2 * (size_t)B * ovl;
-    a.tk = a.h + (size_t)B * d.hstate();
-    a.dbg = dbg;
-    a.clk = clk;
-    a.dbg_stride = h->impl->dbg_floats;
-    hipError_t e = hipSuccess;
-    a.mode = fe::FE_MODE_STREAM;
-    const fe::Impl* im = step_impl(h, B, T, dbg || clk);
-    h->last_shape = im->name;
-    im->launch(a, h->max_wgs, (hipStream_t)stream, &e);
-    return launch_rc(e);
-}
-
-int fe_step(fe_handle* h, const float* wav_in_dev, size_t in_stride, float* state_dev, float* wav_out_dev, size_t out_stride,
-            int B, int T, void* stream) {
-    return run_step(h, wav_in_dev, in_stride, state_dev, wav_out_dev, out_stride, B, T, nullptr, nullptr, stream);
-}
-
 // the slotted entry points: FastEnhancer's causal models only (checked after the handle and before the arguments' contents)
 static int check_slots_family(const fe_handle* h, const char* fn) {
     if (h->cfg.arch != FE_ARCH_FASTENHANCER)
@@ -1181,8 +1139,79 @@ static int check_slots_family(const fe_handle* h, const char* fn) {
     return FE_OK;
 }
 
-static int launch_slotted(fe_handle* h, const float* wav_in_dev, size_t in_stride, float* state_dev, int capacity, const int* slots_dev,
-                          float* wav_out_dev, size_t out_stride, int n, int T, void* stream, bool pinned);
+// "audio in, audio out, state, count, T, strides" of every streaming step.  ptrs: all pointers of the call are non-null; capacity = n for the
+// steps without a slot list.  fn (the pinned steps name themselves; else nullptr) and bad (the wording of the first refusal) are the entry point's own.
+static int check_step_args(const fe_handle* h, const char* fn, const char* bad, bool ptrs, int n, int capacity, int T, size_t in_stride, size_t out_stride) {
+    const char* sep = fn ? ": " : "";
+    if (!fn) fn = "";
+    if (!ptrs || n <= 0 || T <= 0 || capacity < n) return fail(FE_ERR_INVALID_ARG, "%s%s%s", fn, sep, bad);
+    const size_t row = (size_t)T * h->d.HOP;
+    if (in_stride < row && n > 1) return fail(FE_ERR_INVALID_ARG, "%s%sin_stride %zu < T*H", fn, sep, in_stride);
+    if (out_stride < row && n > 1) return fail(FE_ERR_INVALID_ARG, "%s%sout_stride %zu < T*H", fn, sep, out_stride);
+    return FE_OK;
+}
+static const char* const kBadSlotArgs = "bad argument (need non-null pointers, 1 <= n <= capacity, T >= 1)";
+
+// FastEnhancer's streaming step of n streams, however it was asked for.  slots == nullptr: fe_step and the debug / profile steps - the plain
+// instantiations and their FrameArgs, state of rows = n streams.  slots: the launch fe_step(B = n) makes with every state address taken
+// from (slots[b], rows = capacity); pinned: the HIO instantiations, whose wav_in / wav_out are device views of page-locked host memory.
+static int launch_fe_step(fe_handle* h, const float* wav_in, size_t in_stride, float* state, int rows, const int* slots, bool pinned,
+                          float* wav_out, size_t out_stride, int n, int T, float* dbg, unsigned long long* clk, void* stream) {
+    int rc = ensure_scratch(h, n);
+    if (rc != FE_OK) return rc;
+    fe::SlotFrameArgs a{};
+    static_cast<fe::FrameArgs&>(a) = base_args(h, n, T);
+    const StateLayout L = state_layout(h, rows);
+    a.mode = fe::FE_MODE_STREAM;
+    a.wav_in = wav_in; a.wav_out = wav_out; a.in_stride = in_stride; a.out_stride = out_stride;
+    a.cache_stft = state; a.cache_istft = state + L.cache_istft; a.h = state + L.h; a.tk = state + L.tk;
+    const fe::Impl* im = step_impl(h, n, T, dbg || clk);
+    hipError_t e = hipSuccess;
+    if (!slots) {
+        a.dbg = dbg;
+        a.clk = clk;
+        a.dbg_stride = h->impl->dbg_floats;
+        h->last_shape = im->name;
+        im->launch(a, h->max_wgs, (hipStream_t)stream, &e);       // (the FrameArgs part alone: the plain kernels' argument block)
+        return launch_rc(e);
+    }
+    a.capacity = rows;
+    a.slots = slots;
+    auto launch = pinned ? im->launch_slots_pinned : im->launch_slots;
+    if (!launch) return fail(FE_ERR_UNSUPPORTED_CONFIG, "%s: no slotted kernel is compiled for shape %s", pinned ? "fe_step_slots_pinned" : "fe_step_slots",
+                             im->name ? im->name : "?");
+    h->last_shape = im->name;
+    launch(a, h->max_wgs, (hipStream_t)stream, &e);
+    return launch_rc(e);
+}
+
+static int run_step(fe_handle* h, const float* wav_in, size_t in_stride, float* state, float* wav_out, size_t out_stride,
+                    int B, int T, float* dbg, unsigned long long* clk, void* stream) {
+    int rc = check_ready(h);
+    if (rc != FE_OK) return rc;
+    KernelLogScope klog_(h);
+    rc = check_step_args(h, nullptr, "bad argument", wav_in && state && wav_out, B, B, T, in_stride, out_stride);
+    if (rc != FE_OK) return rc;
+    if (visit_baseline(h->cfg.arch, [&](auto F) {
+            auto a = F.args(h, B, T);
+            a.clk = clk;
+            a.dbg = dbg;
+            a.dbg_stride = F.impl(h)->dbg_floats;
+            const StateLayout L = state_layout(h, B);
+            a.mode = fe::FE_MODE_STREAM;
+            a.wav_in = wav_in; a.wav_out = wav_out; a.in_stride = in_stride; a.out_stride = out_stride;
+            a.cache_stft = state; a.cache_istft = state + L.cache_istft; F.state(a) = state + L.h;
+            rc = F.launch(h, a, stream);
+        }))
+        return rc;
+    if (h->d.BD) return fail(FE_ERR_UNSUPPORTED_CONFIG, "%s", kNoncausalNoStep);
+    return launch_fe_step(h, wav_in, in_stride, state, B, nullptr, false, wav_out, out_stride, B, T, dbg, clk, stream);
+}
+
+int fe_step(fe_handle* h, const float* wav_in_dev, size_t in_stride, float* state_dev, float* wav_out_dev, size_t out_stride,
+            int B, int T, void* stream) {
+    return run_step(h, wav_in_dev, in_stride, state_dev, wav_out_dev, out_stride, B, T, nullptr, nullptr, stream);
+}
 
 int fe_step_slots(fe_handle* h, const float* wav_in_dev, size_t in_stride, float* state_dev, int capacity, const int* slots_dev,
                   float* wav_out_dev, size_t out_stride, int n, int T, void* stream) {
@@ -1192,43 +1221,9 @@ int fe_step_slots(fe_handle* h, const float* wav_in_dev, size_t in_stride, float
     rc = check_ready(h);
     if (rc != FE_OK) return rc;
     KernelLogScope klog_(h);
-    if (!wav_in_dev || !state_dev || !slots_dev || !wav_out_dev || n <= 0 || T <= 0 || capacity < n)
-        return fail(FE_ERR_INVALID_ARG, "bad argument (need non-null pointers, 1 <= n <= capacity, T >= 1)");
-    const Dims& d = h->d;
-    if (in_stride < (size_t)T * d.HOP && n > 1) return fail(FE_ERR_INVALID_ARG, "in_stride %zu < T*H", in_stride);
-    if (out_stride < (size_t)T * d.HOP && n > 1) return fail(FE_ERR_INVALID_ARG, "out_stride %zu < T*H", out_stride);
-    return launch_slotted(h, wav_in_dev, in_stride, state_dev, capacity, slots_dev, wav_out_dev, out_stride, n, T, stream, false);
-}
-
-// the launch fe_step(B = n) makes, with every state address taken from (slots_dev[b], capacity); pinned: the HIO instantiations, whose
-// wav_in / wav_out are device views of page-locked host memory (fe_step_slots_pinned)
-static int launch_slotted(fe_handle* h, const float* wav_in_dev, size_t in_stride, float* state_dev, int capacity, const int* slots_dev,
-                          float* wav_out_dev, size_t out_stride, int n, int T, void* stream, bool pinned) {
-    const Dims& d = h->d;
-    int rc = ensure_scratch(h, n);
+    rc = check_step_args(h, nullptr, kBadSlotArgs, wav_in_dev && state_dev && slots_dev && wav_out_dev, n, capacity, T, in_stride, out_stride);
     if (rc != FE_OK) return rc;
-    fe::SlotFrameArgs a{};
-    static_cast<fe::FrameArgs&>(a) = base_args(h, n, T);
-    const size_t ovl = (size_t)(d.NFFT - d.HOP);
-    a.wav_in = wav_in_dev;
-    a.wav_out = wav_out_dev;
-    a.in_stride = in_stride;
-    a.out_stride = out_stride;
-    a.cache_stft = state_dev;
-    a.cache_istft = state_dev + (size_t)capacity * ovl;
-    a.h = state_dev + 2 * (size_t)capacity * ovl;
-    a.tk = a.h + (size_t)capacity * d.hstate();
-    a.capacity = capacity;
-    a.slots = slots_dev;
-    a.mode = fe::FE_MODE_STREAM;
-    const fe::Impl* im = step_impl(h, n, T, false);
-    auto launch = pinned ? im->launch_slots_pinned : im->launch_slots;
-    if (!launch) return fail(FE_ERR_UNSUPPORTED_CONFIG, "%s: no slotted kernel is compiled for shape %s", pinned ? "fe_step_slots_pinned" : "fe_step_slots",
-                             im->name ? im->name : "?");
-    h->last_shape = im->name;
-    hipError_t e = hipSuccess;
-    launch(a, h->max_wgs, (hipStream_t)stream, &e);
-    return launch_rc(e);
+    return launch_fe_step(h, wav_in_dev, in_stride, state_dev, capacity, slots_dev, false, wav_out_dev, out_stride, n, T, nullptr, nullptr, stream);
 }
 
 // fe_step_pinned / fe_step_slots_pinned: `count` floats from p must be page-locked host memory with a device mapping on the current device
@@ -1274,12 +1269,9 @@ static int step_pinned(fe_handle* h, const char* fn, const float* wav_in_host, s
     if (!h) return fail(FE_ERR_INVALID_ARG, "null handle");
     int rc = check_slots_family(h, fn);
     if (rc != FE_OK) return rc;
-    if (!wav_in_host || !state_dev || !wav_out_host || (!identity && !slots_dev) || n <= 0 || T <= 0 || capacity < n)
-        return fail(FE_ERR_INVALID_ARG, "%s: bad argument (need non-null pointers, 1 <= n <= capacity, T >= 1)", fn);
-    const Dims& d = h->d;
-    const size_t row = (size_t)T * d.HOP;
-    if (in_stride < row && n > 1) return fail(FE_ERR_INVALID_ARG, "%s: in_stride %zu < T*H", fn, in_stride);
-    if (out_stride < row && n > 1) return fail(FE_ERR_INVALID_ARG, "%s: out_stride %zu < T*H", fn, out_stride);
+    rc = check_step_args(h, fn, kBadSlotArgs, wav_in_host && state_dev && wav_out_host && (identity || slots_dev), n, capacity, T, in_stride, out_stride);
+    if (rc != FE_OK) return rc;
+    const size_t row = (size_t)T * h->d.HOP;
     rc = check_ready(h);
     if (rc != FE_OK) return rc;
     KernelLogScope klog_(h);
@@ -1294,8 +1286,8 @@ static int step_pinned(fe_handle* h, const char* fn, const float* wav_in_host, s
         if (rc != FE_OK) return rc;
         slots_dev = h->ident_slots_dev;
     }
-    return launch_slotted(h, in_dev, n > 1 ? in_stride : row, state_dev, capacity, slots_dev, const_cast<float*>(out_dev), n > 1 ? out_stride : row,
-                          n, T, stream, true);
+    return launch_fe_step(h, in_dev, n > 1 ? in_stride : row, state_dev, capacity, slots_dev, true, const_cast<float*>(out_dev), n > 1 ? out_stride : row,
+                          n, T, nullptr, nullptr, stream);
 }
 
 int fe_step_pinned(fe_handle* h, const float* wav_in_host, size_t in_stride, float* state_dev, float* wav_out_host, size_t out_stride,
@@ -1339,22 +1331,24 @@ int fe_state_reset_slots(fe_handle* h, float* state_dev, int capacity, const int
     if (rc != FE_OK) return rc;
     if (!state_dev || !slots_dev || n <= 0 || capacity < n) return fail(FE_ERR_INVALID_ARG, "bad argument (need non-null pointers, 1 <= n <= capacity)");
     const Dims& d = h->d;
-    const size_t cap = (size_t)capacity, ovl = (size_t)(d.NFFT - d.HOP), hbase = 2 * cap * ovl;
+    const StateLayout L = state_layout(h, capacity);
+    const size_t cap = (size_t)capacity;
+    const int ovl = d.NFFT - d.HOP;
     ResetArgs a{};
     a.state = state_dev;
     a.slots = slots_dev;
     a.capacity = capacity;
     int nr = 0;
-    a.r[nr++] = {0, 1, (int)ovl};                                         // cache_stft [cap][N-H]
-    a.r[nr++] = {cap * ovl, 1, (int)ovl};                                 // cache_istft [cap][N-H]
+    a.r[nr++] = {0, 1, ovl};                                              // cache_stft [cap][N-H]
+    a.r[nr++] = {L.cache_istft, 1, ovl};                                  // cache_istft [cap][N-H]
     if (d.TA) {
         const int ring = d.F2 * d.C2 * d.TA;                              // K and V rings per block: [2 KB][cap][F2 * C2 * L], then the heads [cap]
-        a.r[nr++] = {hbase, 2 * d.KB, ring};
-        a.r[nr++] = {hbase + cap * (size_t)(2 * d.KB) * ring, 1, 1};
+        a.r[nr++] = {L.h, 2 * d.KB, ring};
+        a.r[nr++] = {L.h + cap * (size_t)(2 * d.KB) * ring, 1, 1};
     } else {
-        a.r[nr++] = {hbase, d.KB, d.F2 * d.C2};                           // GRU states [KB][cap][F2 * C2]
+        a.r[nr++] = {L.h, d.KB, d.F2 * d.C2};                           // GRU states [KB][cap][F2 * C2]
     }
-    if (d.KT > 1) a.r[nr++] = {hbase + cap * d.hstate(), 2 * d.NL, (int)(tk_floats(h) / (2 * d.NL))};   // conv caches [2 NL][cap][KT-1][F1][C1]
+    if (d.KT > 1) a.r[nr++] = {L.tk, 2 * d.NL, (int)(tk_floats(h) / (2 * d.NL))};   // conv caches [2 NL][cap][KT-1][F1][C1]
     a.n_regions = nr;
     hipLaunchKernelGGL(state_reset_slots_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, a);
     return launch_rc(hipGetLastError());

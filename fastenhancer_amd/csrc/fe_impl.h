@@ -3,10 +3,6 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-
-#include <cstdlib>
-
 #include "fe_kernels.hip.h"
 #include "fe_frame8.hip.h"
 #include "tb_kernels.hip.h"
@@ -38,48 +34,24 @@ struct Impl {
     void (*launch_slots_pinned)(const SlotFrameArgs&, int max_wgs, hipStream_t, hipError_t*) = nullptr;
 };
 
-// the instantiation a launcher picked, as fe_last_step_kernel reports it
-template <class S>
+// the instantiation a launcher picked, as fe_last_step_kernel reports it: "fe_frame_kernel<[LOW=n, ]<what>[, slots[, pinned]]>"
+// (fe_step_slots / fe_step_slots_pinned run the SLOT / HIO instantiations; there is no slotted debug kernel)
+#define FE_NAME_LOW(tail) (S::LOW == 2 ? "fe_frame_kernel<LOW=2, " tail ">" : S::LOW == 1 ? "fe_frame_kernel<LOW=1, " tail ">" : "fe_frame_kernel<" tail ">")
+#define FE_NAME(tail) (HIO ? FE_NAME_LOW(tail ", slots, pinned") : SLOT ? FE_NAME_LOW(tail ", slots") : FE_NAME_LOW(tail))
+template <class S, bool SLOT = false, bool HIO = false>
 constexpr const char* frame_kernel_name(bool dbg, bool per_hop, bool persist) {
-    if (dbg) return S::LOW == 2 ? "fe_frame_kernel<LOW=2, debug>" : S::LOW == 1 ? "fe_frame_kernel<LOW=1, debug>" : "fe_frame_kernel<debug>";
-    if (per_hop && !persist) return S::LOW == 2 ? "fe_frame_kernel<LOW=2, per-hop>" : S::LOW == 1 ? "fe_frame_kernel<LOW=1, per-hop>" : "fe_frame_kernel<per-hop>";
-    if (per_hop) return S::LOW == 2 ? "fe_frame_kernel<LOW=2, per-hop, persistent>" : S::LOW == 1 ? "fe_frame_kernel<LOW=1, per-hop, persistent>" : "fe_frame_kernel<per-hop, persistent>";
-    return S::LOW == 2 ? "fe_frame_kernel<LOW=2, generic>" : S::LOW == 1 ? "fe_frame_kernel<LOW=1, generic>" : "fe_frame_kernel<generic>";
+    if (dbg) return FE_NAME_LOW("debug");
+    if (per_hop && !persist) return FE_NAME("per-hop");
+    if (per_hop) return FE_NAME("per-hop, persistent");
+    return FE_NAME("generic");
 }
-
-// ... and its slotted form (fe_step_slots): the same name with "slots" in the brackets
-template <class S>
-constexpr const char* frame_kernel_slot_name(bool per_hop, bool persist) {
-    if (per_hop && !persist) return S::LOW == 2 ? "fe_frame_kernel<LOW=2, per-hop, slots>" : S::LOW == 1 ? "fe_frame_kernel<LOW=1, per-hop, slots>" : "fe_frame_kernel<per-hop, slots>";
-    if (per_hop) return S::LOW == 2 ? "fe_frame_kernel<LOW=2, per-hop, persistent, slots>" : S::LOW == 1 ? "fe_frame_kernel<LOW=1, per-hop, persistent, slots>" : "fe_frame_kernel<per-hop, persistent, slots>";
-    return S::LOW == 2 ? "fe_frame_kernel<LOW=2, generic, slots>" : S::LOW == 1 ? "fe_frame_kernel<LOW=1, generic, slots>" : "fe_frame_kernel<generic, slots>";
-}
-
-// ... and its pinned form (fe_step_slots_pinned, the HIO instantiations): "slots, pinned"
-template <class S>
-constexpr const char* frame_kernel_pinned_name(bool per_hop, bool persist) {
-    if (per_hop && !persist) return S::LOW == 2 ? "fe_frame_kernel<LOW=2, per-hop, slots, pinned>" : S::LOW == 1 ? "fe_frame_kernel<LOW=1, per-hop, slots, pinned>" : "fe_frame_kernel<per-hop, slots, pinned>";
-    if (per_hop) return S::LOW == 2 ? "fe_frame_kernel<LOW=2, per-hop, persistent, slots, pinned>" : S::LOW == 1 ? "fe_frame_kernel<LOW=1, per-hop, persistent, slots, pinned>" : "fe_frame_kernel<per-hop, persistent, slots, pinned>";
-    return S::LOW == 2 ? "fe_frame_kernel<LOW=2, generic, slots, pinned>" : S::LOW == 1 ? "fe_frame_kernel<LOW=1, generic, slots, pinned>" : "fe_frame_kernel<generic, slots, pinned>";
-}
+#undef FE_NAME
+#undef FE_NAME_LOW
 
 template <class S, bool DBG, int MODE, bool T1, bool PERSIST, bool SLOT = false, bool HIO = false>
 void launch_one(const typename KernelArgs<SLOT>::type& a, int grid_x, hipStream_t st, hipError_t* err) {
-    // the opt-in for > 64 KiB of dynamic LDS is a per-device function attribute: one flag per device, set once
-    // (an engine may live on any GPU of the process; relaxed atomics - setting it twice is harmless)
-    static std::atomic<bool> attr_set[kMaxDevices];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) dev = 0;
-    if (!attr_set[dev].load(std::memory_order_relaxed)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fe_frame_kernel<S, DBG, MODE, T1, PERSIST, false, SLOT, HIO>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)Lds<S>::BYTES);
-        if (e != hipSuccess) { *err = e; return; }
-        attr_set[dev].store(true, std::memory_order_relaxed);
-    }
-    dim3 grid(grid_x), block(kThreads);
-    note_kernel(HIO ? frame_kernel_pinned_name<S>(T1, PERSIST) : SLOT ? frame_kernel_slot_name<S>(T1, PERSIST) : frame_kernel_name<S>(DBG, T1, PERSIST));
-    hipLaunchKernelGGL((fe_frame_kernel<S, DBG, MODE, T1, PERSIST, false, SLOT, HIO>), grid, block, Lds<S>::BYTES, st, a);
-    *err = hipGetLastError();
+    *err = launch<&fe_frame_kernel<S, DBG, MODE, T1, PERSIST, false, SLOT, HIO>>(frame_kernel_name<S, SLOT, HIO>(DBG, T1, PERSIST), dim3(grid_x), dim3(kThreads),
+                                                                                 Lds<S>::BYTES, st, a);
 }
 
 // a.step_kernel (fe_set_step_kernel; the handle's default comes from the environment variable FE_WG8, else 1):
@@ -87,21 +59,10 @@ void launch_one(const typename KernelArgs<SLOT>::type& a, int grid_x, hipStream_
 //   for the per-hop step of the shapes it is built for, up to one stream per CU; 2 = also above that (persistent workgroups)
 template <class S, bool DBG, bool PERSIST, bool SLOT = false, bool HIO = false>
 void launch_one8(const typename KernelArgs<SLOT>::type& a, int grid_x, hipStream_t st, hipError_t* err) {
-    static std::atomic<bool> attr_set[kMaxDevices];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) dev = 0;
-    if (!attr_set[dev].load(std::memory_order_relaxed)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fe_frame8_kernel<S, DBG, PERSIST, SLOT, HIO>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)Wg8<S>::BYTES);
-        if (e != hipSuccess) { *err = e; return; }
-        attr_set[dev].store(true, std::memory_order_relaxed);
-    }
-    dim3 grid(grid_x), block(kThreads8);
-    if constexpr (HIO) note_kernel(PERSIST ? "fe_frame8_kernel<persistent, slots, pinned>" : "fe_frame8_kernel<slots, pinned>");
-    else if constexpr (SLOT) note_kernel(PERSIST ? "fe_frame8_kernel<persistent, slots>" : "fe_frame8_kernel<slots>");
-    else note_kernel(DBG ? "fe_frame8_kernel<debug>" : PERSIST ? "fe_frame8_kernel<persistent>" : "fe_frame8_kernel");
-    hipLaunchKernelGGL((fe_frame8_kernel<S, DBG, PERSIST, SLOT, HIO>), grid, block, Wg8<S>::BYTES, st, a);
-    *err = hipGetLastError();
+    const char* name = HIO    ? (PERSIST ? "fe_frame8_kernel<persistent, slots, pinned>" : "fe_frame8_kernel<slots, pinned>")
+                       : SLOT ? (PERSIST ? "fe_frame8_kernel<persistent, slots>" : "fe_frame8_kernel<slots>")
+                              : (DBG ? "fe_frame8_kernel<debug>" : PERSIST ? "fe_frame8_kernel<persistent>" : "fe_frame8_kernel");
+    *err = launch<&fe_frame8_kernel<S, DBG, PERSIST, SLOT, HIO>>(name, dim3(grid_x), dim3(kThreads8), Wg8<S>::BYTES, st, a);
 }
 
 // max_wgs: workgroups that are resident at once (one per CU: 129+ KiB of LDS and waves_per_eu(1,1)); a batch with more
@@ -111,71 +72,41 @@ void launch_one8(const typename KernelArgs<SLOT>::type& a, int grid_x, hipStream
 template <class S, bool SLOT = false, bool HIO = false>
 void launch_impl(const typename KernelArgs<SLOT>::type& a, int max_wgs, hipStream_t st, hipError_t* err) {
     static_assert(SLOT || !HIO, "host audio: slotted instantiations only");
-    const int slots = max_wgs * Lds<S>::OCC;         // resident workgroups
-    const int grid = a.B < slots ? a.B : slots;
+    // the choice: debug instantiation (fe_debug_step / fe_profile_step; never slotted), per-hop or generic kernel, 512-thread or four-wave, grid
+#ifdef FE_PROBE_HOT
+    const bool dbg = !SLOT && a.dbg != nullptr;
+#else
+    const bool dbg = !SLOT && (a.dbg != nullptr || a.clk != nullptr);
+#endif
+    const bool per_hop = a.mode == FE_MODE_STREAM && a.T == 1;       // (the slotted steps are always streaming steps)
+    const int resident = max_wgs * Lds<S>::OCC;
+    int grid = a.B < resident ? a.B : resident;
     if constexpr (Wg8<S>::OK) {
-        if (a.step_kernel > 0 && a.mode == FE_MODE_STREAM && a.T == 1) {
-            const int grid8 = a.B < max_wgs ? a.B : max_wgs;       // (one 512-thread workgroup per CU)
-#ifdef FE_PROBE_HOT
-            const bool dbg8 = a.dbg != nullptr;
-#else
-            const bool dbg8 = a.dbg != nullptr || a.clk != nullptr;
-#endif
-            if constexpr (SLOT) {
-                if (grid8 == a.B) { launch_one8<S, false, false, true, HIO>(a, grid8, st, err); return; }
-                if (a.step_kernel > 1) { launch_one8<S, false, true, true, HIO>(a, grid8, st, err); return; }
-            } else {
-            if (grid8 == a.B) {
-                if (dbg8) launch_one8<S, true, false>(a, grid8, st, err);
-                else launch_one8<S, false, false>(a, grid8, st, err);
-                return;
-            }
-            if (a.step_kernel > 1 && !dbg8) { launch_one8<S, false, true>(a, grid8, st, err); return; }
-            }
+        // one 512-thread workgroup per CU; more streams than that: persistent workgroups at step_kernel 2 (no debug form), else the four-wave kernel
+        if (a.step_kernel > 0 && per_hop && (a.B <= max_wgs || (a.step_kernel > 1 && !dbg))) {
+            if constexpr (!SLOT)
+                if (dbg) return launch_one8<S, true, false>(a, a.B, st, err);
+            if (a.B <= max_wgs) return launch_one8<S, false, false, SLOT, HIO>(a, a.B, st, err);
+            return launch_one8<S, false, true, SLOT, HIO>(a, max_wgs, st, err);
         }
     }
-    if constexpr (SLOT) {
-        if (a.T == 1) {
-            if (grid == a.B) launch_one<S, false, FE_MODE_STREAM, true, false, true, HIO>(a, grid, st, err);
-            else launch_one<S, false, FE_MODE_STREAM, true, true, true, HIO>(a, grid, st, err);
-        }
-        else launch_one<S, false, -1, false, true, true, HIO>(a, grid, st, err);
-        return;
-    }
-#ifdef FE_PROBE_HOT
-    if (a.dbg != nullptr) launch_one<S, true, -1, false, true>(a, grid, st, err);
-#else
-    if (a.dbg != nullptr || a.clk != nullptr) launch_one<S, true, -1, false, true>(a, grid, st, err);     // fe_debug_step / fe_profile_step
-#endif
-    else if (a.mode == FE_MODE_STREAM && a.T == 1) {                                   // the per-hop hot path
+    if constexpr (!SLOT)
+        if (dbg) return launch_one<S, true, -1, false, true>(a, grid, st, err);
+    if (per_hop) {                                                                       // the per-hop hot path
 #ifdef FE_EXP_NONPERSIST      // experiment: one workgroup per stream at any batch (the hardware queues what is not resident); LOW = 1 keeps nothing per workgroup in global memory
-        if (S::LOW == 1) { launch_one<S, false, FE_MODE_STREAM, true, false>(a, a.B, st, err); return; }
+        if (!SLOT && S::LOW == 1) grid = a.B;
 #endif
-        if (grid == a.B) launch_one<S, false, FE_MODE_STREAM, true, false>(a, grid, st, err);
-        else launch_one<S, false, FE_MODE_STREAM, true, true>(a, grid, st, err);
+        if (grid == a.B) return launch_one<S, false, FE_MODE_STREAM, true, false, SLOT, HIO>(a, grid, st, err);
+        return launch_one<S, false, FE_MODE_STREAM, true, true, SLOT, HIO>(a, grid, st, err);
     }
-    else launch_one<S, false, -1, false, true>(a, grid, st, err);                        // chunked streaming, fe_spec_step, fe_offline
+    launch_one<S, false, -1, false, true, SLOT, HIO>(a, grid, st, err);                    // chunked streaming, fe_spec_step, fe_offline
 }
 
 // Time-pipelined launch: B * pipe_p workgroups that wait on each other inside the kernel - a cooperative launch, so
 // that the runtime guarantees (or refuses) their co-residency instead of a spin-wait deadlock.
 template <class S>
 void launch_pipe_impl(const FrameArgs& a, hipStream_t st, hipError_t* err) {
-    {
-    auto* fn = &fe_frame_kernel<S, false, -1, false, true, true>;
-    static std::atomic<bool> attr_set[kMaxDevices];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) dev = 0;
-    if (!attr_set[dev].load(std::memory_order_relaxed)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)Lds<S>::BYTES);
-        if (e != hipSuccess) { *err = e; return; }
-        attr_set[dev].store(true, std::memory_order_relaxed);
-    }
-    FrameArgs args = a;
-    void* kargs[] = {&args};
-    note_kernel("fe_frame_kernel<time-pipelined>");
-    *err = hipLaunchCooperativeKernel(reinterpret_cast<const void*>(fn), dim3(a.B * a.pipe_p), dim3(kThreads), kargs, (unsigned int)Lds<S>::BYTES, st);
-    }
+    *err = launch_coop<&fe_frame_kernel<S, false, -1, false, true, true>>("fe_frame_kernel<time-pipelined>", dim3(a.B * a.pipe_p), dim3(kThreads), Lds<S>::BYTES, st, a);
 }
 
 template <class S>

@@ -24,6 +24,8 @@
 #include <type_traits>
 #include <utility>
 
+#include "fe_launch.h"      // note_kernel, launch / launch_coop: how every kernel below is enqueued
+
 #ifndef FE_OCC_SMALL
 #define FE_OCC_SMALL 3
 #endif
@@ -43,9 +45,6 @@ constexpr int kWaves = 4;
 #define FE_WG8_HPRE 0
 #endif
 
-// fe_last_step_kernel (C ABI, r6): every host-side launcher names the kernel it enqueues (a string literal: family + instantiation);
-// the compute entry points of fe_api.hip collect the names of one call in the handle.  Defined in fe_api.hip (thread-local log).
-void note_kernel(const char* name);
 
 // compile-time loop: f(std::integral_constant<int, 0>{}), ..., f(std::integral_constant<int, N-1>{})
 template <class F, int... I>

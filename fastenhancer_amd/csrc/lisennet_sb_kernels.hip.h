@@ -26,7 +26,6 @@
 // in the layout above), this kernel, lisennet_frame_kernel<PART 2> (mask conv, LayerNorm, sigmoid, mask, iSTFT per stream).
 // (included by lisennet_kernels.hip.h, after LShape / LPk)
 #pragma once
-#include <atomic>
 
 namespace fe {
 
@@ -1145,18 +1144,7 @@ __global__ void __launch_bounds__(kLsbThreads) __attribute__((amdgpu_waves_per_e
 
 template <class S>
 hipError_t lisennet_sb_launch(const LSbArgs& a, hipStream_t st) {
-    static std::atomic<bool> attr_set[64];          // (per device: a process may drive several)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_set[dev].load(std::memory_order_relaxed)) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lisennet_sb_kernel<S>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LSbLds::BYTES);
-        if (e != hipSuccess) return e;
-        attr_set[dev].store(true, std::memory_order_relaxed);
-    }
-    const int grid = (a.B + kLsbStreams - 1) / kLsbStreams;
-    note_kernel("lisennet_sb_kernel");
-    hipLaunchKernelGGL(lisennet_sb_kernel<S>, dim3(grid), dim3(kLsbThreads), LSbLds::BYTES, st, a);
-    return hipGetLastError();
+    return launch<&lisennet_sb_kernel<S>>("lisennet_sb_kernel", dim3((a.B + kLsbStreams - 1) / kLsbStreams), dim3(kLsbThreads), LSbLds::BYTES, st, a);
 }
 
 }  // namespace fe

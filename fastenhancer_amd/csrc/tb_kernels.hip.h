@@ -22,13 +22,11 @@
 // All contractions run on the fp32 matrix cores (v_mfma_f32_16x16x4_f32) through the same software-pipelined panels as
 // the per-hop kernel; weights are read from the same packed buffer (fe::Pack<S>, fragment order, L2-resident).
 #pragma once
-#include <atomic>
 #include <cstdlib>
 
 #include "fe_kernels.hip.h"
 
 namespace fe {
-constexpr int kMaxDevices = 64;
 namespace tb {
 
 constexpr int kPD = 8;          // software-pipeline depth of the MFMA panels: weight fragments stream from L2
@@ -1658,18 +1656,6 @@ struct TbImpl {
     void (*launch)(int stage, const TbArgs&, int max_wgs, hipStream_t, hipError_t*);
 };
 
-template <class K>
-inline void set_lds(K* kern, size_t bytes, hipError_t* err) {
-    static std::atomic<bool> done[kMaxDevices];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) dev = 0;
-    if (!done[dev].load(std::memory_order_relaxed)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) { *err = e; return; }
-        done[dev].store(true, std::memory_order_relaxed);
-    }
-}
-
 // persistent grids: as many workgroups as fit on the chip at once (LDS-limited), each walking tiles blockIdx.x, + gridDim.x, ...
 template <class S>
 void tb_launch(int stage, const TbArgs& a, int max_wgs, hipStream_t st, hipError_t* err) {
@@ -1685,12 +1671,8 @@ void tb_launch(int stage, const TbArgs& a, int max_wgs, hipStream_t st, hipError
         return ntiles < slots ? ntiles : slots;
     };
     if (stage == TB_ENC) {
-        auto* k = &tb_enc_kernel<S, C::FT_E>;
         constexpr size_t lds = EncLds<S, C::FT_E>::BYTES;
-        set_lds(k, lds, err);
-        if (*err != hipSuccess) return;
-        note_kernel("tb_enc_kernel");
-        hipLaunchKernelGGL(k, dim3(grid_for(C::FT_E, lds)), dim3(kThreads), lds, st, a);
+        *err = launch<&tb_enc_kernel<S, C::FT_E>>("tb_enc_kernel", dim3(grid_for(C::FT_E, lds)), dim3(kThreads), lds, st, a);
     } else if (stage == TB_SCAN) {
         // 16 rows per workgroup when that fills the chip (the MFMA throughput of the 16x16x4 tiles is what counts then), else 4
         static const int force = [] { const char* v = std::getenv("FE_TB_SCAN_ROWS"); return v ? std::atoi(v) : 0; }();
@@ -1703,6 +1685,7 @@ void tb_launch(int stage, const TbArgs& a, int max_wgs, hipStream_t st, hipError
             hipLaunchKernelGGL((tb_scan_kernel<S>), dim3((a.B * S::F2 + 15) / 16, S::ND), dim3(kThreads), 0, st, a);
         else
             hipLaunchKernelGGL((tb_scan4_kernel<S>), dim3(a.B * S::F2 / 4, S::ND), dim3(kThreads), 0, st, a);
+        *err = hipGetLastError();
     } else if (stage == TB_STAGE) {
         // the fused stage: only where the 16-row scan is the one in use, its workgroups leave room for tile workgroups on every CU, and the
         // block runs on the register-resident path; anything else is refused (the caller launches scan and tiles one after the other)
@@ -1711,37 +1694,21 @@ void tb_launch(int stage, const TbArgs& a, int max_wgs, hipStream_t st, hipError
             const int TPU = (a.T + C::FT_B - 1) / C::FT_B, ntiles = a.B * TPU;
             const int room = 2 * max_wgs - nscan - 16;           // (a margin: the co-residency the runtime grants is sized by its own occupancy estimate)
             if (!(4 * wg4 > 5 * max_wgs) || nscan > max_wgs || room < max_wgs / 2 || a.prog == nullptr) { *err = hipErrorNotSupported; return; }
-            auto* k = &tb_stage_kernel<S, C::FT_B>;
-            constexpr size_t lds = BlkLds<S, C::FT_B>::BYTES;
-            set_lds(k, lds, err);
-            if (*err != hipSuccess) return;
             TbArgs args = a;
             args.nscan = nscan;
-            void* kargs[] = {&args};
             int grid = nscan + (ntiles < room ? ntiles : room);
             static const int dbg = [] { const char* v = std::getenv("FE_TB_FUSE_DEBUG"); return v ? std::atoi(v) : 0; }();
             if (dbg == 1) grid = nscan;          // (timing experiment: the scan role alone, with its agent-scope stores and publishes; results are garbage)
-            *err = hipLaunchCooperativeKernel(reinterpret_cast<const void*>(k), dim3(grid), dim3(kThreads), kargs, (unsigned int)lds, st);
-            if (*err != hipSuccess) (void)hipGetLastError();
-            else note_kernel("tb_stage_kernel");
-            return;
+            // (a refusal leaves no error behind and notes nothing: the caller launches scan and tiles separately)
+            *err = launch_coop<&tb_stage_kernel<S, C::FT_B>, true>("tb_stage_kernel", dim3(grid), dim3(kThreads), BlkLds<S, C::FT_B>::BYTES, st, args);
         }
     } else if (stage == TB_BLK) {
-        auto* k = &tb_blk_kernel<S, C::FT_B>;
         constexpr size_t lds = BlkLds<S, C::FT_B>::BYTES;
-        set_lds(k, lds, err);
-        if (*err != hipSuccess) return;
-        note_kernel("tb_blk_kernel");
-        hipLaunchKernelGGL(k, dim3(grid_for(C::FT_B, lds)), dim3(kThreads), lds, st, a);
+        *err = launch<&tb_blk_kernel<S, C::FT_B>>("tb_blk_kernel", dim3(grid_for(C::FT_B, lds)), dim3(kThreads), lds, st, a);
     } else {
-        auto* k = &tb_dec_kernel<S, C::FT_D>;
         constexpr size_t lds = DecLds<S, C::FT_D>::BYTES;
-        set_lds(k, lds, err);
-        if (*err != hipSuccess) return;
-        note_kernel("tb_dec_kernel");
-        hipLaunchKernelGGL(k, dim3(grid_for(C::FT_D, lds)), dim3(kThreads), lds, st, a);
+        *err = launch<&tb_dec_kernel<S, C::FT_D>>("tb_dec_kernel", dim3(grid_for(C::FT_D, lds)), dim3(kThreads), lds, st, a);
     }
-    *err = hipGetLastError();
 }
 
 template <class S>

@@ -228,19 +228,43 @@ class Engine:
         return torch.cat([t.to(torch.float32) for t in pieces]).contiguous()
 
     # ------------------------------------------------------------------ compute
+    def _step(self, wav_in: Tensor, state: Tensor, wav_out: Optional[Tensor], T: int, capacity: Optional[int] = None, slots=None,
+              pinned: bool = False) -> Tensor:
+        """The streaming step behind step / step_slots / step_pinned / step_slots_pinned.  slots (with capacity): the slot-indexed entry
+        points, `state` sized for `capacity` streams; pinned: wav_in / wav_out are page-locked host memory instead of device memory."""
+        slotted = slots is not None
+        H = self.cfg.hop_size
+        if pinned:
+            if not isinstance(wav_in, Tensor) or wav_in.dim() != 2:
+                raise ValueError(f"wav_in must be a 2-D tensor [{'n' if slotted else 'B'}, T*H]")
+            wav_in = self._pinned_audio("wav_in", wav_in, wav_in.shape[0], T)
+            wav_out = self._pinned_audio("wav_out", wav_out, wav_in.shape[0], T)
+        sl = self._slot_tensor(slots, capacity) if slotted else None
+        self._require_gpu()
+        n = wav_in.shape[0]
+        if slotted:
+            assert sl.numel() == n, (sl.numel(), n)
+        if not pinned:
+            assert wav_in.is_cuda and wav_in.dtype == torch.float32 and wav_in.stride(1) == 1 and wav_in.shape[1] == T * H
+        assert (state.is_cuda or not pinned) and state.numel() == self.state_floats(capacity if slotted else n) and state.is_contiguous()
+        if wav_out is None:
+            wav_out = torch.empty(n, T * H, dtype=torch.float32, device=wav_in.device)
+        name = "fe_step" + ("_slots" if slotted else "") + ("_pinned" if pinned else "")
+        args = [self._h, _ptr(wav_in), wav_in.stride(0) if n > 1 else T * H, _ptr(state)]
+        args += [int(capacity), _ptr(sl)] if slotted else []
+        args += [_ptr(wav_out), wav_out.stride(0) if n > 1 else T * H, n, T, _stream(self.device)]
+        with torch.cuda.device(self.device):
+            _lib.check(getattr(self.lib, name)(*args), name)
+        # (alive until the next call - the launch is asynchronous: a copied slot list, the pinned audio)
+        if slotted:
+            self._slots_keep = sl
+        if pinned:
+            self._pinned_keep = (wav_in, wav_out)
+        return wav_out
+
     def step(self, wav_in: Tensor, state: Tensor, wav_out: Optional[Tensor] = None, T: int = 1) -> Tensor:
         """wav_in [B, T*H] (row stride free) -> wav_out [B, T*H]; state updated in place."""
-        self._require_gpu()
-        B = wav_in.shape[0]
-        H = self.cfg.hop_size
-        assert wav_in.is_cuda and wav_in.dtype == torch.float32 and wav_in.stride(1) == 1 and wav_in.shape[1] == T * H
-        assert state.numel() == self.state_floats(B) and state.is_contiguous()
-        if wav_out is None:
-            wav_out = torch.empty(B, T * H, dtype=torch.float32, device=wav_in.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.fe_step(self._h, _ptr(wav_in), wav_in.stride(0) if B > 1 else T * H, _ptr(state), _ptr(wav_out),
-                                        wav_out.stride(0) if B > 1 else T * H, B, T, _stream(self.device)), "fe_step")
-        return wav_out
+        return self._step(wav_in, state, wav_out, T)
 
     def _slot_tensor(self, slots, capacity: int) -> Tensor:
         """slots -> a device int32 tensor for fe_step_slots / fe_state_reset_slots.  A CUDA int32 tensor is passed through unchecked (the form
@@ -273,20 +297,7 @@ class Engine:
     def step_slots(self, wav_in: Tensor, state: Tensor, capacity: int, slots, wav_out: Optional[Tensor] = None, T: int = 1) -> Tensor:
         """fe_step_slots: wav_in [n, T*H] (row i = state slot slots[i]) -> wav_out [n, T*H]; only the named slots of `state`
         (sized for `capacity` streams) are updated.  slots: a list / CPU tensor (checked) or a CUDA int32 tensor (not checked)."""
-        sl = self._slot_tensor(slots, capacity)
-        self._require_gpu()
-        n = wav_in.shape[0]
-        H = self.cfg.hop_size
-        assert sl.numel() == n, (sl.numel(), n)
-        assert wav_in.is_cuda and wav_in.dtype == torch.float32 and wav_in.stride(1) == 1 and wav_in.shape[1] == T * H
-        assert state.numel() == self.state_floats(capacity) and state.is_contiguous()
-        if wav_out is None:
-            wav_out = torch.empty(n, T * H, dtype=torch.float32, device=wav_in.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.fe_step_slots(self._h, _ptr(wav_in), wav_in.stride(0) if n > 1 else T * H, _ptr(state), int(capacity), _ptr(sl),
-                                              _ptr(wav_out), wav_out.stride(0) if n > 1 else T * H, n, T, _stream(self.device)), "fe_step_slots")
-        self._slots_keep = sl          # (a copied list: alive until the next call - the launch is asynchronous)
-        return wav_out
+        return self._step(wav_in, state, wav_out, T, capacity, slots)
 
     def reset_slots(self, state: Tensor, capacity: int, slots) -> None:
         """fe_state_reset_slots: the named slots of `state` (sized for `capacity` streams) as fe_state_init leaves them (zero)."""
@@ -316,40 +327,12 @@ class Engine:
         """fe_step_pinned: wav_in [B, T*H] in page-locked HOST memory -> wav_out [B, T*H] in page-locked host memory (allocated when None),
         one launch that reads and writes the audio over PCIe; state (device) updated in place.  Asynchronous on the current stream:
         synchronise it before reading wav_out or rewriting wav_in."""
-        if not isinstance(wav_in, Tensor) or wav_in.dim() != 2:
-            raise ValueError("wav_in must be a 2-D tensor [B, T*H]")
-        B = wav_in.shape[0]
-        wav_in = self._pinned_audio("wav_in", wav_in, B, T)
-        wav_out = self._pinned_audio("wav_out", wav_out, B, T)
-        self._require_gpu()
-        assert state.is_cuda and state.numel() == self.state_floats(B) and state.is_contiguous()
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.fe_step_pinned(self._h, ctypes.c_void_p(wav_in.data_ptr()), wav_in.stride(0) if B > 1 else T * self.cfg.hop_size,
-                                               _ptr(state), ctypes.c_void_p(wav_out.data_ptr()), wav_out.stride(0) if B > 1 else T * self.cfg.hop_size,
-                                               B, T, _stream(self.device)), "fe_step_pinned")
-        self._pinned_keep = (wav_in, wav_out)          # (alive until the next call - the launch is asynchronous)
-        return wav_out
+        return self._step(wav_in, state, wav_out, T, pinned=True)
 
     def step_slots_pinned(self, wav_in: Tensor, state: Tensor, capacity: int, slots, wav_out: Optional[Tensor] = None, T: int = 1) -> Tensor:
         """fe_step_slots_pinned: step_slots with wav_in / wav_out [n, T*H] in page-locked HOST memory (wav_out allocated when None).
         slots as for step_slots.  Asynchronous on the current stream: synchronise it before reading wav_out or rewriting wav_in."""
-        if not isinstance(wav_in, Tensor) or wav_in.dim() != 2:
-            raise ValueError("wav_in must be a 2-D tensor [n, T*H]")
-        n = wav_in.shape[0]
-        wav_in = self._pinned_audio("wav_in", wav_in, n, T)
-        wav_out = self._pinned_audio("wav_out", wav_out, n, T)
-        sl = self._slot_tensor(slots, capacity)
-        self._require_gpu()
-        assert sl.numel() == n, (sl.numel(), n)
-        assert state.is_cuda and state.numel() == self.state_floats(capacity) and state.is_contiguous()
-        H = self.cfg.hop_size
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.fe_step_slots_pinned(self._h, ctypes.c_void_p(wav_in.data_ptr()), wav_in.stride(0) if n > 1 else T * H, _ptr(state),
-                                                     int(capacity), _ptr(sl), ctypes.c_void_p(wav_out.data_ptr()), wav_out.stride(0) if n > 1 else T * H,
-                                                     n, T, _stream(self.device)), "fe_step_slots_pinned")
-        self._slots_keep = sl
-        self._pinned_keep = (wav_in, wav_out)
-        return wav_out
+        return self._step(wav_in, state, wav_out, T, capacity, slots, pinned=True)
 
     def step_host(self, wav_in: Tensor, state: Tensor, wav_out: Optional[Tensor] = None, T: int = 1) -> Tensor:
         """fe_step_host: wav_in [B, n*T*H] in HOST memory (pinned for full speed) -> wav_out [B, n*T*H] in host memory, n calls of T hops
