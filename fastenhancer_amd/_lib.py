@@ -3,7 +3,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, byref, c_char_p, c_double, c_float, c_int, c_size_t, c_void_p
+from ctypes import POINTER, byref, c_char_p, c_double, c_float, c_int, c_longlong, c_size_t, c_void_p
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # FASTENHANCER_HIP_LIB: a side build of the same library (ab/lib_<tag>.so from FE_BUILD_TAG=<tag> python -m fastenhancer_amd.build)
@@ -19,6 +19,7 @@ FE_OFFLINE_AUTO, FE_OFFLINE_FRAME_WALK, FE_OFFLINE_TIME_BATCHED = 0, 1, 2
 FE_STEP_KERNEL_WAVES4, FE_STEP_KERNEL_WG8, FE_STEP_KERNEL_WG8_PERSIST = 0, 1, 2
 FE_ACT_SILU, FE_ACT_RELU, FE_ACT_LEAKY_RELU, FE_ACT_ELU, FE_ACT_GELU, FE_ACT_GELU_TANH = 0, 1, 2, 3, 4, 5
 FE_MASK_NONE, FE_MASK_SIGMOID, FE_MASK_TANH = 0, 1, 2
+FE_AUDIO_F32, FE_AUDIO_S16 = 0, 1
 
 
 class fe_config(ctypes.Structure):
@@ -29,6 +30,11 @@ class fe_config(ctypes.Structure):
         ("rf_heads", c_int), ("input_compression", c_float), ("kernel_size_time", c_int), ("channels_frnn", c_int), ("lookbehind", c_int), ("ln", c_int), ("rf_eps", c_float),
         ("bidirectional", c_int), ("activation", c_int), ("activation_param", c_float), ("mask", c_int), ("resnet", c_int),
     ]
+
+
+class fe_stream_desc(ctypes.Structure):
+    """one stream of fe_step_streams: state slot, hops to advance, element offsets of its first input / output sample (24 bytes)"""
+    _fields_ = [("slot", c_int), ("hops", c_int), ("in_offset", c_longlong), ("out_offset", c_longlong)]
 
 
 # every symbol include/fastenhancer_hip.h declares: name -> (restype, argtypes)
@@ -46,6 +52,8 @@ SYMBOLS = {
     "fe_state_reset_slots": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "fe_step_pinned": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),
     "fe_step_slots_pinned": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),
+    "fe_step_streams": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
+    "fe_step_streams_pinned": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
     "fe_step_host": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p]),
     "fe_spec_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "fe_set_time_pipeline": (c_int, [c_void_p, c_int]),

@@ -1229,23 +1229,25 @@ int fe_step_slots(fe_handle* h, const float* wav_in_dev, size_t in_stride, float
 // fe_step_pinned / fe_step_slots_pinned: `count` floats from p must be page-locked host memory with a device mapping on the current device
 // (hipHostMalloc / hipHostRegister: torch's pin_memory()).  Anything else - pageable or device memory - would make the kernel take a page
 // fault, so it is refused here, before any launch.  Both ends of the range are looked up; *dev = the device view of p.
-static int pinned_view(const float* p, size_t count, const char* fn, const char* what, const float** dev) {
-    const float* ends[2] = {p, p + (count - 1)};
+// (E: float, or short for the int16 audio of fe_step_streams_pinned.)
+extern "C++" template <class E>
+static int pinned_view(const E* p, size_t count, const char* fn, const char* what, const E** dev) {
+    const E* ends[2] = {p, p + (count - 1)};
     const char* dv[2] = {nullptr, nullptr};
     for (int i = 0; i < 2; ++i) {
         hipPointerAttribute_t at{};
         bool ok = hipPointerGetAttributes(&at, ends[i]) == hipSuccess && at.type == hipMemoryTypeHost;
         void* dp = nullptr;
-        if (ok) ok = hipHostGetDevicePointer(&dp, const_cast<float*>(ends[i]), 0) == hipSuccess && dp != nullptr;
+        if (ok) ok = hipHostGetDevicePointer(&dp, const_cast<E*>(ends[i]), 0) == hipSuccess && dp != nullptr;
         (void)hipGetLastError();        // (a refused lookup must not surface as the error of a later launch)
         if (!ok)
-            return fail(FE_ERR_INVALID_ARG, "%s: %s is not page-locked host memory mapped for this device (%s float of the range): pin the buffer "
+            return fail(FE_ERR_INVALID_ARG, "%s: %s is not page-locked host memory mapped for this device (%s element of the range): pin the buffer "
                         "(torch: pin_memory(); C: hipHostMalloc / hipHostRegister)", fn, what, i ? "last" : "first");
         dv[i] = static_cast<const char*>(dp);
     }
     if (dv[1] - dv[0] != reinterpret_cast<const char*>(ends[1]) - reinterpret_cast<const char*>(ends[0]))
         return fail(FE_ERR_INVALID_ARG, "%s: %s spans more than one pinned allocation: pin the buffer as one piece (pin_memory())", fn, what);
-    *dev = reinterpret_cast<const float*>(dv[0]);
+    *dev = reinterpret_cast<const E*>(dv[0]);
     return FE_OK;
 }
 
@@ -1298,6 +1300,74 @@ int fe_step_pinned(fe_handle* h, const float* wav_in_host, size_t in_stride, flo
 int fe_step_slots_pinned(fe_handle* h, const float* wav_in_host, size_t in_stride, float* state_dev, int capacity, const int* slots_dev,
                          float* wav_out_host, size_t out_stride, int n, int T, void* stream) {
     return step_pinned(h, "fe_step_slots_pinned", wav_in_host, in_stride, state_dev, capacity, slots_dev, false, wav_out_host, out_stride, n, T, stream);
+}
+
+// fe_step_streams / fe_step_streams_pinned: the launch fe_step_slots(n, T_max) makes, with the STRM instantiations - per-stream hop counts and audio
+// offsets from desc_dev, float32 or int16 audio.  One set of kernels serves device and page-locked host audio: pinned only decides whether the two
+// ranges are looked up (pinned_view) and how the kernel is named.  The descriptors' contents are the kernel's to check (fe_kernels.hip.h::stream_view).
+static_assert(sizeof(fe_stream_desc) == 24 && sizeof(fe::StreamDesc) == 24 && offsetof(fe_stream_desc, slot) == offsetof(fe::StreamDesc, slot) &&
+              offsetof(fe_stream_desc, hops) == offsetof(fe::StreamDesc, hops) && offsetof(fe_stream_desc, in_offset) == offsetof(fe::StreamDesc, in_offset) &&
+              offsetof(fe_stream_desc, out_offset) == offsetof(fe::StreamDesc, out_offset), "fe_stream_desc is the kernels' StreamDesc");
+static int step_streams(fe_handle* h, const char* fn, bool pinned, const void* wav_in, size_t in_count, float* state_dev, int capacity,
+                        const fe_stream_desc* desc_dev, void* wav_out, size_t out_count, int n, int T_max, int format, void* stream) {
+    if (!h) return fail(FE_ERR_INVALID_ARG, "null handle");
+    int rc = check_slots_family(h, fn);
+    if (rc != FE_OK) return rc;
+    if (!wav_in || !state_dev || !desc_dev || !wav_out || n <= 0 || T_max <= 0 || capacity < n || in_count == 0 || out_count == 0)
+        return fail(FE_ERR_INVALID_ARG, "%s: bad argument (need non-null pointers to at least one element, 1 <= n <= capacity, T_max >= 1)", fn);
+    if (format != FE_AUDIO_F32 && format != FE_AUDIO_S16)
+        return fail(FE_ERR_INVALID_ARG, "%s: format %d is neither FE_AUDIO_F32 (0) nor FE_AUDIO_S16 (1)", fn, format);
+    rc = check_ready(h);
+    if (rc != FE_OK) return rc;
+    KernelLogScope klog_(h);
+    if (pinned) {
+        // the whole of both buffers, [wav, wav + count) in elements of the format: what the kernel's own bounds check confines every access to
+        if (format == FE_AUDIO_S16) {
+            const short* in_dev = nullptr;
+            const short* out_dev = nullptr;
+            rc = pinned_view(static_cast<const short*>(wav_in), in_count, fn, "wav_in", &in_dev);
+            if (rc == FE_OK) rc = pinned_view(static_cast<const short*>(wav_out), out_count, fn, "wav_out", &out_dev);
+            wav_in = in_dev;
+            wav_out = const_cast<short*>(out_dev);
+        } else {
+            const float* in_dev = nullptr;
+            const float* out_dev = nullptr;
+            rc = pinned_view(static_cast<const float*>(wav_in), in_count, fn, "wav_in", &in_dev);
+            if (rc == FE_OK) rc = pinned_view(static_cast<const float*>(wav_out), out_count, fn, "wav_out", &out_dev);
+            wav_in = in_dev;
+            wav_out = const_cast<float*>(out_dev);
+        }
+        if (rc != FE_OK) return rc;
+    }
+    rc = ensure_scratch(h, n);
+    if (rc != FE_OK) return rc;
+    fe::StreamFrameArgs a{};
+    static_cast<fe::FrameArgs&>(a) = base_args(h, n, T_max);
+    const StateLayout L = state_layout(h, capacity);
+    a.mode = fe::FE_MODE_STREAM;
+    a.wav_in = static_cast<const float*>(wav_in); a.wav_out = static_cast<float*>(wav_out);       // (typed by a.format in the kernel)
+    a.cache_stft = state_dev; a.cache_istft = state_dev + L.cache_istft; a.h = state_dev + L.h; a.tk = state_dev + L.tk;
+    a.capacity = capacity;
+    a.desc = reinterpret_cast<const fe::StreamDesc*>(desc_dev);
+    a.in_count = in_count; a.out_count = out_count;
+    a.format = format;
+    a.pinned = pinned ? 1 : 0;
+    const fe::Impl* im = step_impl(h, n, T_max, false);
+    if (!im->launch_streams) return fail(FE_ERR_UNSUPPORTED_CONFIG, "%s: no packet-audio kernel is compiled for shape %s", fn, im->name ? im->name : "?");
+    h->last_shape = im->name;
+    hipError_t e = hipSuccess;
+    im->launch_streams(a, h->max_wgs, (hipStream_t)stream, &e);
+    return launch_rc(e);
+}
+
+int fe_step_streams(fe_handle* h, const void* wav_in_dev, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,
+                    void* wav_out_dev, size_t out_count, int n, int T_max, int format, void* stream) {
+    return step_streams(h, "fe_step_streams", false, wav_in_dev, in_count, state_dev, capacity, desc_dev, wav_out_dev, out_count, n, T_max, format, stream);
+}
+
+int fe_step_streams_pinned(fe_handle* h, const void* wav_in_host, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,
+                           void* wav_out_host, size_t out_count, int n, int T_max, int format, void* stream) {
+    return step_streams(h, "fe_step_streams_pinned", true, wav_in_host, in_count, state_dev, capacity, desc_dev, wav_out_host, out_count, n, T_max, format, stream);
 }
 
 // fe_state_reset_slots: what fe_state_init writes (zeros) for the named slots.  The state is a list of regions [rows][capacity][len]

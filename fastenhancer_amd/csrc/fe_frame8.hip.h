@@ -127,12 +127,16 @@ __device__ __forceinline__ void conv8_pair(int wh, AF&& af, BF&& bf, BI&& bias, 
 // each workgroup walks the streams blockIdx.x, blockIdx.x + gridDim.x, ...  SLOT (fe_step_slots): stream b's state is slot a.slots[b] of a
 // state sized for a.capacity streams, as in fe_frame_kernel.  HIO (fe_step_slots_pinned; SLOT only): the audio is page-locked host
 // memory - the hop sample of each thread is requested ahead into hv (the first stream's before any other load of the kernel, the next
-// stream's once the current one's has been taken), and the output row goes out in non-temporal 16-byte stores
-template <class S, bool DBG, bool PERSIST, bool SLOT = false, bool HIO = false>
-__global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(2, 2))) fe_frame8_kernel(typename KernelArgs<SLOT>::type a_in) {
+// stream's once the current one's has been taken), and the output row goes out in non-temporal 16-byte stores.  STRM (fe_step_streams /
+// fe_step_streams_pinned; HIO only): slot, hop count (0 or 1 here) and audio offsets come from the stream's descriptor (stream_view), the audio is
+// float32 or int16 PCM (a.format, wave-uniform); a stream without a hop is skipped and no hop of it is requested, as in fe_frame_kernel
+template <class S, bool DBG, bool PERSIST, bool SLOT = false, bool HIO = false, bool STRM = false>
+__global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(2, 2))) fe_frame8_kernel(typename KernelArgs<SLOT, STRM>::type a_in) {
     static_assert(Wg8<S>::OK, "fe_frame8_kernel: shape outside the 512-thread kernel's plan");
     static_assert(!HIO || (SLOT && !DBG), "host audio: slotted production instantiations only");
-    typename KernelArgs<SLOT>::type a = a_in;
+    static_assert(!STRM || HIO, "packet audio: the host-audio instantiations only");
+    typename KernelArgs<SLOT, STRM>::type a = a_in;
+    if constexpr (STRM) a.T = 1;                     // (one hop per launch: what stream_view clamps the hop counts to)
 #ifdef FE_PROBE_HOT
     if constexpr (!DBG) a.dbg = nullptr;
 #else
@@ -158,6 +162,10 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
     const int wave = wave0;
     float hv = 0.0f;                                 // (HIO) this thread's hop sample of the next stream the workgroup runs
     auto hop_issue = [&](int bb) {
+        if constexpr (STRM) {
+            const StreamView v = stream_view<H>(a, bb);
+            if (v.hops && tid0 >= OVL) hv = stream_sample(a.wav_in, a.format, v.in_off + (tid0 - OVL));
+        } else
         if constexpr (HIO) { if (bb < a.B && tid0 >= OVL) hv = a.wav_in[(size_t)bb * a.in_stride + tid0 - OVL]; }
     };
     hop_issue((int)blockIdx.x);
@@ -207,8 +215,16 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
         if constexpr (!PERSIST) {
             const int b0 = (int)blockIdx.x;
             if constexpr (SLOT) {
-                const int s0 = a.slots[b0];
-                const bool live = (unsigned)s0 < (unsigned)a.capacity;
+                int s0;
+                bool live;
+                if constexpr (STRM) {
+                    const StreamView v0 = stream_view<H>(a, b0);
+                    s0 = v0.slot;
+                    live = v0.hops != 0 && (unsigned)s0 < (unsigned)a.capacity;
+                } else {
+                    s0 = a.slots[b0];
+                    live = (unsigned)s0 < (unsigned)a.capacity;
+                }
                 if constexpr (HIO) fv = (tid < OVL) ? (live ? a.cache_stft[(size_t)s0 * OVL + tid] : 0.0f) : hv;
                 else fv = (tid < OVL) ? (live ? a.cache_stft[(size_t)s0 * OVL + tid] : 0.0f) : a.wav_in[(size_t)b0 * a.in_stride + tid - OVL];
             } else {
@@ -235,14 +251,28 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
 
     int b = (int)blockIdx.x;
     int fc = 0;
+    StreamView sv{-1, 0, 0, 0};                          // (STRM) the stream this workgroup is running
 #pragma unroll 1
     do {
         int sb = b;                                      // the stream's state slot
         int nst = a.B;                                   // streams the state is sized for
         if constexpr (SLOT) {
             static_assert(!DBG, "slotted step: production instantiations only");
+            if constexpr (STRM) {
+                sv = stream_view<H>(a, b);
+                sb = sv.slot;
+            } else
             sb = a.slots[b];
             nst = a.capacity;
+            if constexpr (STRM) {
+                if (sv.hops == 0 || (unsigned)sb >= (unsigned)nst) {      // (wave-uniform) no hop: nothing; no state: the stream's output row is zero
+                    if (sv.hops) stream_zero_row(a.wav_out, a.format, sv.out_off, H, tid0, NTH);
+                    __builtin_amdgcn_s_waitcnt(0);       // (the weight stages issued for this stream have landed before the next one or the end)
+                    b += (int)gridDim.x;
+                    hop_issue(b);
+                    continue;
+                }
+            } else
             if ((unsigned)sb >= (unsigned)nst) {         // (wave-uniform) no state: the stream's output row is zero
                 if constexpr (HIO) { if (tid0 < H) __builtin_nontemporal_store(0.0f, a.wav_out + (size_t)b * a.out_stride + tid0); }
                 else
@@ -1123,6 +1153,33 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
             const int pi = Dft<S>::pidx(tid & (Dft<S>::N1 - 1), tid / Dft<S>::N1);
             const float xo = (q0[pi] + q1[pi]) * ow + oc;
             // one sample per thread: the first H go out, the rest is the new overlap tail (the old tail was read before the barrier)
+            if constexpr (STRM) {
+                if (a.format) {
+                    // int16 PCM: even lanes pack two samples, lane 8j gathers the four words of lanes 8j, 8j + 2, 8j + 4, 8j + 6 (every lane shuffles)
+                    const int qv = pcm16_out(xo);
+                    const int pw = pcm16_pair(qv, __shfl_down(qv, 1));
+                    const int p1 = __shfl_down(pw, 2), p2 = __shfl_down(pw, 4), p3 = __shfl_down(pw, 6);
+                    short* orow = reinterpret_cast<short*>(a.wav_out) + sv.out_off;
+                    if (tid < H) {
+                        if (H % 8 == 0 && (reinterpret_cast<size_t>(orow) & 15) == 0) {
+                            if ((tid & 7) == 0) __builtin_nontemporal_store(i32x4{pw, p1, p2, p3}, reinterpret_cast<i32x4*>(orow + tid));
+                        } else {
+                            __builtin_nontemporal_store((short)qv, orow + tid);
+                        }
+                    }
+                } else {
+                    const float x1 = __shfl_down(xo, 1), x2 = __shfl_down(xo, 2), x3 = __shfl_down(xo, 3);
+                    float* orow = a.wav_out + sv.out_off;
+                    if (tid < H) {
+                        if (H % 4 == 0 && (reinterpret_cast<size_t>(orow) & 15) == 0) {
+                            if ((tid & 3) == 0) __builtin_nontemporal_store(f32x4{xo, x1, x2, x3}, reinterpret_cast<f32x4*>(orow + tid));
+                        } else {
+                            __builtin_nontemporal_store(xo, orow + tid);
+                        }
+                    }
+                }
+                if (tid >= H) cis[tid - H] = xo;
+            } else
             if constexpr (HIO) {
                 // whole 16-byte pieces to host memory: lane 4j gathers the samples of lanes 4j + 1 .. 4j + 3 (every lane of the wave shuffles)
                 const float x1 = __shfl_down(xo, 1), x2 = __shfl_down(xo, 2), x3 = __shfl_down(xo, 3);

@@ -32,6 +32,9 @@ struct Impl {
     void (*launch_slots)(const SlotFrameArgs&, int max_wgs, hipStream_t, hipError_t*) = nullptr;
     // fe_step_slots_pinned: the same choice with the HIO instantiations (wav_in / wav_out: device views of page-locked host memory)
     void (*launch_slots_pinned)(const SlotFrameArgs&, int max_wgs, hipStream_t, hipError_t*) = nullptr;
+    // fe_step_streams / fe_step_streams_pinned: the same choice for a.B streams and a.T = T_max with the STRM instantiations (a.desc: per-stream
+    // hop counts and audio offsets; float32 or int16 audio in device or page-locked host memory - one set of kernels serves all four)
+    void (*launch_streams)(const StreamFrameArgs&, int max_wgs, hipStream_t, hipError_t*) = nullptr;
 };
 
 // the instantiation a launcher picked, as fe_last_step_kernel reports it: "fe_frame_kernel<[LOW=n, ]<what>[, slots[, pinned]]>"
@@ -45,33 +48,53 @@ constexpr const char* frame_kernel_name(bool dbg, bool per_hop, bool persist) {
     if (per_hop) return FE_NAME("per-hop, persistent");
     return FE_NAME("generic");
 }
+// ... and of the STRM instantiations: "<what>, streams[, pinned][, s16]" (where the audio lives and its format are run-time facts of the call)
+#define FE_NAME_STRM(tail) (pinned ? (s16 ? FE_NAME_LOW(tail ", streams, pinned, s16") : FE_NAME_LOW(tail ", streams, pinned")) \
+                                   : (s16 ? FE_NAME_LOW(tail ", streams, s16") : FE_NAME_LOW(tail ", streams")))
+template <class S>
+constexpr const char* stream_kernel_name(bool per_hop, bool persist, bool pinned, bool s16) {
+    if (per_hop && !persist) return FE_NAME_STRM("per-hop");
+    if (per_hop) return FE_NAME_STRM("per-hop, persistent");
+    return FE_NAME_STRM("generic");
+}
+#undef FE_NAME_STRM
 #undef FE_NAME
 #undef FE_NAME_LOW
 
-template <class S, bool DBG, int MODE, bool T1, bool PERSIST, bool SLOT = false, bool HIO = false>
-void launch_one(const typename KernelArgs<SLOT>::type& a, int grid_x, hipStream_t st, hipError_t* err) {
-    *err = launch<&fe_frame_kernel<S, DBG, MODE, T1, PERSIST, false, SLOT, HIO>>(frame_kernel_name<S, SLOT, HIO>(DBG, T1, PERSIST), dim3(grid_x), dim3(kThreads),
-                                                                                 Lds<S>::BYTES, st, a);
+template <class S, bool DBG, int MODE, bool T1, bool PERSIST, bool SLOT = false, bool HIO = false, bool STRM = false>
+void launch_one(const typename KernelArgs<SLOT, STRM>::type& a, int grid_x, hipStream_t st, hipError_t* err) {
+    const char* name = frame_kernel_name<S, SLOT, HIO>(DBG, T1, PERSIST);
+    if constexpr (STRM) name = stream_kernel_name<S>(T1, PERSIST, a.pinned != 0, a.format != 0);
+    *err = launch<&fe_frame_kernel<S, DBG, MODE, T1, PERSIST, false, SLOT, HIO, STRM>>(name, dim3(grid_x), dim3(kThreads), Lds<S>::BYTES, st, a);
 }
 
 // a.step_kernel (fe_set_step_kernel; the handle's default comes from the environment variable FE_WG8, else 1):
 //   0 = the four-wave kernel everywhere; 1 = the 512-thread kernel (fe_frame8.hip.h: two waves per SIMD, channel-grouped GRU gates)
 //   for the per-hop step of the shapes it is built for, up to one stream per CU; 2 = also above that (persistent workgroups)
-template <class S, bool DBG, bool PERSIST, bool SLOT = false, bool HIO = false>
-void launch_one8(const typename KernelArgs<SLOT>::type& a, int grid_x, hipStream_t st, hipError_t* err) {
+template <class S, bool DBG, bool PERSIST, bool SLOT = false, bool HIO = false, bool STRM = false>
+void launch_one8(const typename KernelArgs<SLOT, STRM>::type& a, int grid_x, hipStream_t st, hipError_t* err) {
     const char* name = HIO    ? (PERSIST ? "fe_frame8_kernel<persistent, slots, pinned>" : "fe_frame8_kernel<slots, pinned>")
                        : SLOT ? (PERSIST ? "fe_frame8_kernel<persistent, slots>" : "fe_frame8_kernel<slots>")
                               : (DBG ? "fe_frame8_kernel<debug>" : PERSIST ? "fe_frame8_kernel<persistent>" : "fe_frame8_kernel");
-    *err = launch<&fe_frame8_kernel<S, DBG, PERSIST, SLOT, HIO>>(name, dim3(grid_x), dim3(kThreads8), Wg8<S>::BYTES, st, a);
+    if constexpr (STRM) {
+        const bool pinned = a.pinned != 0, s16 = a.format != 0;
+        name = PERSIST ? (pinned ? (s16 ? "fe_frame8_kernel<persistent, streams, pinned, s16>" : "fe_frame8_kernel<persistent, streams, pinned>")
+                                 : (s16 ? "fe_frame8_kernel<persistent, streams, s16>" : "fe_frame8_kernel<persistent, streams>"))
+                       : (pinned ? (s16 ? "fe_frame8_kernel<streams, pinned, s16>" : "fe_frame8_kernel<streams, pinned>")
+                                 : (s16 ? "fe_frame8_kernel<streams, s16>" : "fe_frame8_kernel<streams>"));
+    }
+    *err = launch<&fe_frame8_kernel<S, DBG, PERSIST, SLOT, HIO, STRM>>(name, dim3(grid_x), dim3(kThreads8), Wg8<S>::BYTES, st, a);
 }
 
 // max_wgs: workgroups that are resident at once (one per CU: 129+ KiB of LDS and waves_per_eu(1,1)); a batch with more
 // streams runs on a grid of max_wgs PERSISTENT workgroups, each walking its streams b, b + grid, ...
 // SLOT (fe_step_slots): the same choice, made with the slotted instantiations (streaming mode; no debug dumps or cycle probes)
 // HIO (fe_step_slots_pinned; SLOT only): ... with the instantiations that read and write the audio in page-locked host memory
-template <class S, bool SLOT = false, bool HIO = false>
-void launch_impl(const typename KernelArgs<SLOT>::type& a, int max_wgs, hipStream_t st, hipError_t* err) {
+// STRM (fe_step_streams / fe_step_streams_pinned; HIO only): ... with the packet-audio instantiations (a.T = T_max picks per-hop or generic)
+template <class S, bool SLOT = false, bool HIO = false, bool STRM = false>
+void launch_impl(const typename KernelArgs<SLOT, STRM>::type& a, int max_wgs, hipStream_t st, hipError_t* err) {
     static_assert(SLOT || !HIO, "host audio: slotted instantiations only");
+    static_assert(HIO || !STRM, "packet audio: the host-audio instantiations only");
     // the choice: debug instantiation (fe_debug_step / fe_profile_step; never slotted), per-hop or generic kernel, 512-thread or four-wave, grid
 #ifdef FE_PROBE_HOT
     const bool dbg = !SLOT && a.dbg != nullptr;
@@ -86,8 +109,8 @@ void launch_impl(const typename KernelArgs<SLOT>::type& a, int max_wgs, hipStrea
         if (a.step_kernel > 0 && per_hop && (a.B <= max_wgs || (a.step_kernel > 1 && !dbg))) {
             if constexpr (!SLOT)
                 if (dbg) return launch_one8<S, true, false>(a, a.B, st, err);
-            if (a.B <= max_wgs) return launch_one8<S, false, false, SLOT, HIO>(a, a.B, st, err);
-            return launch_one8<S, false, true, SLOT, HIO>(a, max_wgs, st, err);
+            if (a.B <= max_wgs) return launch_one8<S, false, false, SLOT, HIO, STRM>(a, a.B, st, err);
+            return launch_one8<S, false, true, SLOT, HIO, STRM>(a, max_wgs, st, err);
         }
     }
     if constexpr (!SLOT)
@@ -96,10 +119,10 @@ void launch_impl(const typename KernelArgs<SLOT>::type& a, int max_wgs, hipStrea
 #ifdef FE_EXP_NONPERSIST      // experiment: one workgroup per stream at any batch (the hardware queues what is not resident); LOW = 1 keeps nothing per workgroup in global memory
         if (!SLOT && S::LOW == 1) grid = a.B;
 #endif
-        if (grid == a.B) return launch_one<S, false, FE_MODE_STREAM, true, false, SLOT, HIO>(a, grid, st, err);
-        return launch_one<S, false, FE_MODE_STREAM, true, true, SLOT, HIO>(a, grid, st, err);
+        if (grid == a.B) return launch_one<S, false, FE_MODE_STREAM, true, false, SLOT, HIO, STRM>(a, grid, st, err);
+        return launch_one<S, false, FE_MODE_STREAM, true, true, SLOT, HIO, STRM>(a, grid, st, err);
     }
-    launch_one<S, false, -1, false, true, SLOT, HIO>(a, grid, st, err);                    // chunked streaming, fe_spec_step, fe_offline
+    launch_one<S, false, -1, false, true, SLOT, HIO, STRM>(a, grid, st, err);                    // chunked streaming, fe_spec_step, fe_offline
 }
 
 // Time-pipelined launch: B * pipe_p workgroups that wait on each other inside the kernel - a cooperative launch, so
@@ -136,6 +159,7 @@ Impl make_impl() {
     im.EP = S::EP;
     im.launch_slots = &launch_impl<S, true>;
     im.launch_slots_pinned = &launch_impl<S, true, true>;
+    im.launch_streams = &launch_impl<S, true, true, true>;
     return im;
     }
 }

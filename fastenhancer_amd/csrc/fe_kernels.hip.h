@@ -364,8 +364,23 @@ struct SlotFrameArgs : FrameArgs {
     int capacity;
     const int* slots;         // [B] device int32; a slot outside [0, capacity) gets zero output rows and touches no state
 };
-template <bool SLOT> struct KernelArgs { using type = FrameArgs; };
-template <> struct KernelArgs<true> { using type = SlotFrameArgs; };
+// The packet-audio step (fe_step_streams / fe_step_streams_pinned; the STRM instantiations, SLOT and HIO only): SlotFrameArgs with four fields at
+// the end.  Call stream b has a descriptor of its own - state slot, hops to advance in this call (0 .. T), element offsets of its first input and
+// output sample from wav_in / wav_out - and the audio is float32 or int16 PCM (format).  a.slots, the strides and a.T as a per-stream hop count are
+// unused: T is the cap on hops.  (Again a type of its own: the SLOT / HIO instantiations keep their argument blocks.)
+struct StreamDesc {           // = fe_stream_desc of the C ABI (24 bytes)
+    int slot, hops;
+    long long in_offset, out_offset;
+};
+struct StreamFrameArgs : SlotFrameArgs {
+    const StreamDesc* desc;   // [B] device memory, read when the kernel runs
+    size_t in_count, out_count;   // elements of wav_in / wav_out: no access outside [0, count)
+    int format;               // 0 = float32, 1 = int16 PCM (FE_AUDIO_*)
+    int pinned;               // host side only (fe_impl.h: the kernel's name): the audio is page-locked host memory
+};
+template <bool SLOT, bool STRM = false> struct KernelArgs { using type = FrameArgs; };
+template <> struct KernelArgs<true, false> { using type = SlotFrameArgs; };
+template <> struct KernelArgs<true, true> { using type = StreamFrameArgs; };
 
 // The pinned step (fe_step_slots_pinned; the HIO instantiations, SLOT only): wav_in / wav_out are device views of page-locked HOST
 // memory, so every audio access crosses PCIe.  Output rows go out as non-temporal 16-byte stores - one posted write each - where the row
@@ -385,6 +400,69 @@ __device__ __forceinline__ void hio_store_row(float* out, const float* src, int 
 }
 __device__ __forceinline__ void hio_zero_row(float* out, int n, int tid, int nth) {
     for (int i = tid; i < n; i += nth) __builtin_nontemporal_store(0.0f, out + i);
+}
+
+// ---- the packet-audio step (STRM).  What the kernel makes of call stream b's descriptor, wave-uniform (every word through readfirstlane):
+// hops clamped to [0, T]; and 0 - the stream is skipped, nothing of it is read or written - unless both of its audio ranges
+// [offset, offset + hops * H) lie inside [0, count).  This check is what keeps a bad descriptor from becoming an access outside the buffers.
+struct StreamView {
+    int slot, hops;
+    long long in_off, out_off;
+};
+template <int H>
+__device__ __forceinline__ StreamView stream_view(const StreamFrameArgs& a, int b) {
+    StreamView v{-1, 0, 0, 0};
+    if (b < a.B) {
+        const int* p = reinterpret_cast<const int*>(a.desc + b);
+        int w[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) w[i] = __builtin_amdgcn_readfirstlane(p[i]);
+        v.slot = w[0];
+        const int hops = w[1] < 0 ? 0 : (w[1] > a.T ? a.T : w[1]);
+        v.in_off = (long long)(((unsigned long long)(unsigned)w[3] << 32) | (unsigned)w[2]);
+        v.out_off = (long long)(((unsigned long long)(unsigned)w[5] << 32) | (unsigned)w[4]);
+        const unsigned long long len = (unsigned long long)hops * H;
+        const bool in_ok = v.in_off >= 0 && (unsigned long long)v.in_off <= a.in_count && a.in_count - (unsigned long long)v.in_off >= len;
+        const bool out_ok = v.out_off >= 0 && (unsigned long long)v.out_off <= a.out_count && a.out_count - (unsigned long long)v.out_off >= len;
+        v.hops = (in_ok && out_ok) ? hops : 0;
+    }
+    return v;
+}
+// int16 PCM, full scale 32768.  In: s / 32768 (exact).  Out: clamp(rint(y * 32768), -32768, 32767), ties to even, NaN -> 0.
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float pcm16_in(const void* base, long long idx) { return (float)static_cast<const short*>(base)[idx] * (1.0f / 32768.0f); }
+__device__ __forceinline__ int pcm16_out(float y) {
+    const float r = fminf(fmaxf(__builtin_rintf(y * 32768.0f), -32768.0f), 32767.0f);
+    return y == y ? (int)r : 0;
+}
+__device__ __forceinline__ int pcm16_pair(int lo, int hi) { return (lo & 0xffff) | (hi << 16); }
+// sample `idx` of the input in either format (a wave-uniform branch)
+__device__ __forceinline__ float stream_sample(const void* base, int format, long long idx) {
+    return format ? pcm16_in(base, idx) : static_cast<const float*>(base)[idx];
+}
+// n samples from src (LDS) to elements idx .. of the output: hio_store_row for floats; int16 as non-temporal 16-byte stores of eight samples
+// where the row is 16-byte aligned, else sample by sample.  (Vector stores only.)
+__device__ __forceinline__ void stream_store_row(void* base, int format, long long idx, const float* src, int n, int tid, int nth) {
+    if (!format) return hio_store_row(static_cast<float*>(base) + idx, src, n, tid, nth);
+    short* out = static_cast<short*>(base) + idx;
+    int done = 0;
+    if ((reinterpret_cast<size_t>(out) & 15) == 0) {
+        const int n8 = n >> 3;
+        i32x4* o4 = reinterpret_cast<i32x4*>(out);
+        for (int i = tid; i < n8; i += nth) {
+            const float* s = src + 8 * i;
+            const i32x4 v = {pcm16_pair(pcm16_out(s[0]), pcm16_out(s[1])), pcm16_pair(pcm16_out(s[2]), pcm16_out(s[3])),
+                             pcm16_pair(pcm16_out(s[4]), pcm16_out(s[5])), pcm16_pair(pcm16_out(s[6]), pcm16_out(s[7]))};
+            __builtin_nontemporal_store(v, o4 + i);
+        }
+        done = 8 * n8;
+    }
+    for (int i = done + tid; i < n; i += nth) __builtin_nontemporal_store((short)pcm16_out(src[i]), out + i);
+}
+__device__ __forceinline__ void stream_zero_row(void* base, int format, long long idx, int n, int tid, int nth) {
+    if (!format) return hio_zero_row(static_cast<float*>(base) + idx, n, tid, nth);
+    short* out = static_cast<short*>(base) + idx;
+    for (int i = tid; i < n; i += nth) __builtin_nontemporal_store((short)0, out + i);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1481,10 +1559,15 @@ __device__ __forceinline__ void attention_head(const float* G, float* Hl, int ho
 // HIO (fe_step_slots_pinned; SLOT only): the audio is page-locked host memory.  The hop of the next frame a workgroup runs is requested
 // ahead and held in registers (hv, hop_issue below): its first one before any other load of the kernel, so that the PCIe round trip runs
 // under the prologue; frame t + 1's (or the next stream's first) as soon as frame t's has been taken.  Rows go out through hio_store_row.
-template <class S, bool DBG, int MODE, bool T1, bool PERSIST, bool PIPE = false, bool SLOT = false, bool HIO = false>
-__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(Lds<S>::OCC, Lds<S>::OCC))) fe_frame_kernel(typename KernelArgs<SLOT>::type a_in) {
+// STRM (fe_step_streams / fe_step_streams_pinned; HIO only - a device pointer and a mapped host pointer are both addresses, so one flavour serves
+// both): stream b advances sv.hops <= a.T hops (stream_view: its descriptor, clamped and bounds-checked), reads and writes its audio at its own
+// element offsets, as float32 or int16 PCM (a.format, a wave-uniform branch at the two I/O sites); a stream with no hop is skipped, and the hop
+// requested ahead is never one beyond a stream's own count.
+template <class S, bool DBG, int MODE, bool T1, bool PERSIST, bool PIPE = false, bool SLOT = false, bool HIO = false, bool STRM = false>
+__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(Lds<S>::OCC, Lds<S>::OCC))) fe_frame_kernel(typename KernelArgs<SLOT, STRM>::type a_in) {
     static_assert(!HIO || (SLOT && !PIPE && !DBG), "host audio: slotted streaming instantiations only");
-    typename KernelArgs<SLOT>::type a = a_in;
+    static_assert(!STRM || HIO, "packet audio: the host-audio instantiations only");
+    typename KernelArgs<SLOT, STRM>::type a = a_in;
 #ifdef FE_PROBE_HOT          // measurement builds: the production instantiations keep the cycle probes (tools/gpu_phases.py ... 1)
     if constexpr (!DBG) a.dbg = nullptr;
 #else
@@ -1510,7 +1593,22 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
     const int li = lane & 15, lg = lane >> 4;
     constexpr int HNPT = HIO ? N / kThreads : 1;     // (HIO) frame samples per thread, as in the STFT below; hv[q] = sample tid + q kThreads
     float hv[HNPT];
+    StreamView sv{-1, 0, 0, 0};                      // (STRM) the stream this workgroup is running
+    // (STRM) hop tt of the stream with view v into hv - nothing is requested where the stream has no such hop
+    auto hop_load = [&](const StreamView& v, int tt) {
+        if constexpr (STRM) {
+            const bool ok = tt < v.hops;
+            const long long x0 = ok ? v.in_off + (long long)tt * H - OVL : 0;
+#pragma unroll
+            for (int q = 0; q < HNPT; ++q) {
+                const int n = tid0 + q * kThreads;
+                hv[q] = (ok && n >= OVL) ? stream_sample(a.wav_in, a.format, x0 + n) : 0.0f;
+            }
+        }
+    };
     auto hop_issue = [&](int bb, int tt) {
+        if constexpr (STRM) hop_load(stream_view<H>(a, bb), tt);
+        else
         if constexpr (HIO) {
             const bool ok = bb < a.B && tt < a.T;
             const float* xin = a.wav_in + (size_t)(ok ? bb : 0) * a.in_stride + (size_t)(ok ? tt : 0) * H;
@@ -1614,8 +1712,21 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
     int nst = a.B;                                   // streams the state is sized for
     if constexpr (SLOT) {
         static_assert(!PIPE && !DBG, "slotted step: per-hop / generic streaming instantiations only");
+        if constexpr (STRM) {
+            sv = stream_view<H>(a, b);
+            sb = sv.slot;
+        } else
         sb = a.slots[b];
         nst = a.capacity;
+        if constexpr (STRM) {
+            if (sv.hops == 0 || (unsigned)sb >= (unsigned)nst) {      // (wave-uniform) no hop: nothing; no state: its sv.hops output rows are zero
+                if (sv.hops) stream_zero_row(a.wav_out, a.format, sv.out_off, sv.hops * S::HOP, tid, kThreads);
+                __builtin_amdgcn_s_waitcnt(0);       // (the weight stage issued for this stream has landed before the next one or the end)
+                b += (int)gridDim.x;
+                hop_issue(b, 0);
+                continue;
+            }
+        } else
         if ((unsigned)sb >= (unsigned)nst) {         // (wave-uniform) no state: the stream's output rows are zero
             float* out = a.wav_out + (size_t)b * a.out_stride;
             if constexpr (HIO) hio_zero_row(out, a.T * S::HOP, tid, kThreads);
@@ -1677,8 +1788,10 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
     constexpr int W_F0 = 0, W_F1 = FE_KVW_FRONT == 0 ? 1 : -1, W_F2 = FE_KVW_FRONT == 0 ? 2 : 1, W_F3 = FE_KVW_FRONT == 0 ? 3 : 2;
     constexpr int W_FE = W_F3 + 1;
     float kvw[W_NIT][WPF ? 4 * HD : 1];
+    int t_end = a.T;
+    if constexpr (STRM) t_end = T1 ? 1 : sv.hops;     // (sv.hops >= 1 here)
 #pragma unroll 1
-    for (int t = t_first; t < a.T; t += t_step, ++fc) {
+    for (int t = t_first; t < t_end; t += t_step, ++fc) {
         // A loop-variant zero keeps the (many) wave-uniform offsets of a frame from being hoisted out of the frame
         // loop: hoisted, they sit in SGPRs for the whole kernel and spill to VGPR lanes by the hundred.
         // (Measured on the kernels with a frame loop: FastEnhancer_B 46.0 -> 44.1 us per frame, T 21.2 -> 20.5 us,
@@ -1789,6 +1902,10 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                     else fv[q] = (n < OVL) ? cst[n] : xin[n - OVL];
                     fw[q] = win[n];
                 }
+                if constexpr (STRM) {                    // ... of this stream's own count; the next stream's first only if it has one
+                    if (t + 1 < t_end) hop_load(sv, t + 1);
+                    else hop_issue(b + (int)gridDim.x, 0);
+                } else
                 if constexpr (HIO) {                     // the next hop this workgroup runs: frame t + 1, else the next stream's first
                     if (t + 1 < a.T) hop_issue(b, t + 1);
                     else hop_issue(b + (int)gridDim.x, 0);
@@ -3331,6 +3448,8 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                 for (int n = tid; n < N; n += kThreads) fr[n] = xo[n];
             } else if (mode == FE_MODE_STREAM) {
                 float* out = a.wav_out + (size_t)b * a.out_stride + (size_t)t * H;
+                if constexpr (STRM) stream_store_row(a.wav_out, a.format, sv.out_off + (long long)t * H, xo, H, tid, kThreads);
+                else
                 if constexpr (HIO) hio_store_row(out, xo, H, tid, kThreads);
                 else
                 for (int n = tid; n < H; n += kThreads) out[n] = xo[n];

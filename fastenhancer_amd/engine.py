@@ -334,6 +334,93 @@ class Engine:
         slots as for step_slots.  Asynchronous on the current stream: synchronise it before reading wav_out or rewriting wav_in."""
         return self._step(wav_in, state, wav_out, T, capacity, slots, pinned=True)
 
+    # ---- packet audio: per-stream hop counts and offsets, float32 or int16 PCM (fe_step_streams / fe_step_streams_pinned)
+    @staticmethod
+    def pack_stream_desc(desc) -> Tensor:
+        """[(slot, hops, in_offset, out_offset), ...] -> a CPU int32 tensor [n, 6], the memory image of n fe_stream_desc."""
+        rows = [tuple(operator.index(v) for v in d) for d in desc]
+        if any(len(r) != 4 for r in rows):
+            raise ValueError("a stream descriptor is (slot, hops, in_offset, out_offset)")
+        arr = (_lib.fe_stream_desc * max(len(rows), 1))(*[_lib.fe_stream_desc(*r) for r in rows])
+        words = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.int32).view(-1, 6)
+        return words[:len(rows)].clone()
+
+    def _stream_desc_tensor(self, desc, capacity: int, T_max: int, in_count: int, out_count: int) -> Tensor:
+        """desc -> a device int32 tensor [n, 6].  A CUDA int32 tensor [n, 6] is passed through unchecked (the form for graph capture: the
+        kernel checks every descriptor itself); a list of (slot, hops, in_offset, out_offset) is checked here first - slots in [0, capacity)
+        without duplicates, 0 <= hops <= T_max, both ranges inside their buffers - and copied to the device."""
+        H = self.cfg.hop_size
+        if isinstance(desc, Tensor):
+            if desc.dtype != torch.int32 or desc.dim() != 2 or desc.shape[1] != 6 or not desc.is_contiguous():
+                raise ValueError("a descriptor tensor must be a contiguous int32 tensor [n, 6] (Engine.pack_stream_desc)")
+            if desc.is_cuda:
+                return desc
+            self._require_gpu()
+            return desc.to(self.device)
+        rows = [tuple(operator.index(v) for v in d) for d in desc]
+        if not 1 <= len(rows) <= capacity:
+            raise ValueError(f"{len(rows)} streams for a capacity of {capacity}")
+        for slot, hops, i0, o0 in rows:
+            if not 0 <= slot < capacity:
+                raise ValueError(f"slot {slot} is outside [0, {capacity})")
+            if not 0 <= hops <= T_max:
+                raise ValueError(f"hops {hops} is outside [0, {T_max}]")
+            if i0 < 0 or i0 + hops * H > in_count:
+                raise ValueError(f"slot {slot}: input range [{i0}, {i0 + hops * H}) is outside [0, {in_count})")
+            if o0 < 0 or o0 + hops * H > out_count:
+                raise ValueError(f"slot {slot}: output range [{o0}, {o0 + hops * H}) is outside [0, {out_count})")
+        if len({r[0] for r in rows}) != len(rows):
+            raise ValueError("duplicate slots")
+        self._require_gpu()
+        return self.pack_stream_desc(rows).to(self.device)
+
+    def _step_streams(self, wav_in: Tensor, state: Tensor, capacity: int, desc, wav_out: Tensor, T_max: int, pinned: bool) -> Tensor:
+        name = "fe_step_streams" + ("_pinned" if pinned else "")
+        for what, x in (("wav_in", wav_in), ("wav_out", wav_out)):
+            if not isinstance(x, Tensor) or x.dtype not in (torch.float32, torch.int16) or not x.is_contiguous() or x.numel() == 0:
+                raise ValueError(f"{what} must be a contiguous, non-empty float32 or int16 tensor")
+        if wav_in.dtype != wav_out.dtype:
+            raise ValueError(f"wav_in is {wav_in.dtype} and wav_out {wav_out.dtype}: one format per call")
+        for what, x in (("wav_in", wav_in), ("wav_out", wav_out)):
+            if pinned and (x.device.type != "cpu" or not x.is_pinned()):
+                raise ValueError(f"{what} must be a CPU tensor in page-locked memory (pin_memory())")
+            if not pinned and not x.is_cuda:
+                raise ValueError(f"{what} must be a device tensor ({name}_pinned takes page-locked host memory)")
+        if T_max < 1:
+            raise ValueError("T_max must be at least 1")
+        d = self._stream_desc_tensor(desc, capacity, T_max, wav_in.numel(), wav_out.numel())
+        self._require_gpu()
+        assert state.is_cuda and state.numel() == self.state_floats(capacity) and state.is_contiguous()
+        fmt = _lib.FE_AUDIO_S16 if wav_in.dtype == torch.int16 else _lib.FE_AUDIO_F32
+        with torch.cuda.device(self.device):
+            _lib.check(getattr(self.lib, name)(self._h, _ptr(wav_in), wav_in.numel(), _ptr(state), int(capacity), _ptr(d), _ptr(wav_out), wav_out.numel(),
+                                               d.shape[0], int(T_max), fmt, _stream(self.device)), name)
+        self._desc_keep = d          # (alive until the next call - the launch is asynchronous)
+        if pinned:
+            self._pinned_keep = (wav_in, wav_out)
+        return wav_out
+
+    def step_streams(self, wav_in: Tensor, state: Tensor, capacity: int, desc, wav_out: Tensor, T_max: int = 1) -> Tensor:
+        """fe_step_streams: every stream of `desc` advances its own number of hops (0 .. T_max), reading wav_in [in_offset + t*H ...] and
+        writing wav_out [out_offset + t*H ...] - flat device buffers, both float32 or both int16 PCM (full scale 32768).  desc: a list of
+        (slot, hops, in_offset, out_offset) (checked) or a CUDA int32 tensor [n, 6] (pack_stream_desc; checked by the kernel only)."""
+        return self._step_streams(wav_in, state, capacity, desc, wav_out, T_max, pinned=False)
+
+    def step_streams_pinned(self, wav_in: Tensor, state: Tensor, capacity: int, desc, wav_out: Tensor, T_max: int = 1) -> Tensor:
+        """fe_step_streams_pinned: step_streams with wav_in / wav_out in page-locked HOST memory, read and written by the kernel over PCIe.
+        Asynchronous on the current stream: synchronise it before reading wav_out or rewriting wav_in."""
+        return self._step_streams(wav_in, state, capacity, desc, wav_out, T_max, pinned=True)
+
+    def new_pinned(self, *shape: int, dtype=torch.float32) -> Tensor:
+        """a zeroed page-locked host tensor (the audio of the pinned steps)"""
+        self._require_gpu()
+        return torch.zeros(*shape, dtype=dtype).pin_memory()
+
+    def synchronize(self) -> None:
+        """wait for the current stream of the engine's device (the completion rule of the pinned steps)"""
+        self._require_gpu()
+        torch.cuda.current_stream(self.device).synchronize()
+
     def step_host(self, wav_in: Tensor, state: Tensor, wav_out: Optional[Tensor] = None, T: int = 1) -> Tensor:
         """fe_step_host: wav_in [B, n*T*H] in HOST memory (pinned for full speed) -> wav_out [B, n*T*H] in host memory, n calls of T hops
         each with the copies of the neighbouring calls under each kernel; state (device) updated in place.  Asynchronous on the current

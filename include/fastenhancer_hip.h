@@ -192,6 +192,40 @@ int fe_step_pinned(fe_handle* h, const float* wav_in_host, size_t in_stride, flo
 int fe_step_slots_pinned(fe_handle* h, const float* wav_in_host, size_t in_stride, float* state_dev, int capacity, const int* slots_dev,
                          float* wav_out_host, size_t out_stride, int n, int T, void* stream);
 
+/* The streaming step for PACKET audio: every stream of the call advances its own number of hops, reads and writes its audio at its own
+ * place in two buffers (a service's rings), as float32 or as int16 PCM - one launch for a tick on which some streams have no complete
+ * hop, most have one and some have several.  State buffer, capacity, families and the kernel choice are those of fe_step_slots(n, T = T_max).
+ *   desc_dev: a DEVICE array of n descriptors, read by the kernel when it runs (a captured graph serves other streams, hop counts and
+ *     offsets on each replay after its contents are rewritten); not checked on the host.
+ *   Addressing: stream i reads hop t (t < hops) at wav_in [in_offset + t*H .. + H) and writes wav_out [out_offset + t*H .. + H), in ELEMENTS
+ *     of `format`: FE_AUDIO_F32 floats, FE_AUDIO_S16 int16.  Any element alignment is legal; rows that are 16-byte aligned go out as
+ *     16-byte stores.
+ *   hops: clamped by the kernel to [0, T_max].  With 0 hops the stream neither reads nor writes audio or state.
+ *   Bounds: in_count / out_count are the element counts of the two buffers.  A stream whose clamped range [offset, offset + hops*H) does
+ *     not lie inside [0, count) on EITHER side is skipped like a stream with 0 hops: no audio, no state, nothing outside the buffers.  The
+ *     kernel makes this check for every stream on every call.
+ *   Slots: as for fe_step_slots - a slot outside [0, capacity) touches no state and its hops output rows are zero; duplicates are undefined.
+ *   int16: input x = s / 32768 (exact); output q = clamp(rint(y * 32768), -32768, 32767), ties to even, NaN -> 0.  The state is float
+ *     either way: the results are those of the float32 call on s / 32768, quantised on the way out.
+ *   The host checks 1 <= n <= capacity, T_max >= 1, non-null pointers and the format; families as for fe_step_slots.  Each stream's rows and
+ *     state are those of fe_step_slots(T = its hops) under the same kernel, bit for bit (FE_STEP_KERNEL_WAVES4 where hop counts differ: the
+ *     chunked-equals-per-hop contract of fe_set_step_kernel).  fe_last_step_kernel names the kernel with "streams" (and "pinned", "s16")
+ *     in the brackets.
+ * fe_step_streams_pinned: wav_in / wav_out are page-locked HOST memory, read and written by the kernel over PCIe - the pinning and completion
+ *   rules of fe_step_slots_pinned, checked for [wav, wav + count) of each buffer; the in-kernel bounds check is the same. */
+typedef struct fe_stream_desc {      /* 24 bytes */
+    int slot;                        /* state slot */
+    int hops;                        /* hops this stream advances in this call */
+    long long in_offset;             /* element offset of its first input sample from wav_in */
+    long long out_offset;            /* element offset of its first output sample from wav_out */
+} fe_stream_desc;
+#define FE_AUDIO_F32 0
+#define FE_AUDIO_S16 1               /* int16 PCM, full scale 32768 */
+int fe_step_streams(fe_handle* h, const void* wav_in_dev, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,
+                    void* wav_out_dev, size_t out_count, int n, int T_max, int format, void* stream);
+int fe_step_streams_pinned(fe_handle* h, const void* wav_in_host, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,
+                           void* wav_out_host, size_t out_count, int n, int T_max, int format, void* stream);
+
 /* The same step for callers whose audio lives in HOST memory (the reference's scripts/test_onnx.py feeds numpy arrays hop by hop):
  * n_calls consecutive fe_step calls of T hops each, hop block c = hops c*T .. c*T+T-1 of
  *   wav_in_host [b*in_stride + t*H + n], wav_out_host [b*out_stride + t*H + n]   (page-locked for asynchronous copies; pageable works, slower)
