@@ -86,9 +86,6 @@ __device__ __forceinline__ int ov_band(int i) {
 __device__ __forceinline__ void ov_group_barrier(unsigned int* cnt, unsigned int arrive) {
     __builtin_amdgcn_s_waitcnt(0x0f70);          // vmcnt(0): this thread's stores have left the CU
     __syncthreads();
-#ifdef FE_EXP_FUS_NOBAR      // (timing experiment: no waiting for the other workgroups)
-    return;
-#endif
     if (threadIdx.x == 0) {
         const unsigned int old = __hip_atomic_fetch_add(cnt, arrive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const unsigned int target = (old / 16u + 1u) * 16u;
@@ -635,9 +632,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
                     kind = j & 1; band = 29 - (j >> 1); it0 = 0;
                     nitw = (4 * bsrnn_band_sub(band) + 15) >> 4;
                 }
-#ifndef FE_EXP_FUS_NOMLP      // (timing experiment: the fused step without its mask decoder)
                 bsrnn_mlp_wave<S, true>(a, h1, kind, band, tile, 1, it0, 1, nitw, lane);
-#endif
             }
         }
         ov_group_barrier(gcnt + 1, arrive);

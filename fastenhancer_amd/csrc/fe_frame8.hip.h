@@ -25,25 +25,6 @@
 
 namespace fe {
 
-// FE_WG8_HPRE=1 (r5; MEASURED NEGATIVE, off by default - profiles/r5_headline_hpre.txt): the GRU's hidden halves
-// W_hh h_{t-1} of ALL blocks - h_{t-1} is known when the frame starts - accumulated by waves 4-7 in the front of the frame (next to the DFT of
-// waves 0-3 and in enc_pre), the GRU jobs moved to the waves that hold the sums (wave 4, 5: channel group 0 + the mixed tile of a row tile;
-// wave 6, 7: channel group 1).  The products removed altogether (wrong results) are worth 31.64 -> 30.09 us; moved, the frame is 33.5 us: the
-// front grows by 7.4 k cycles (operand fetches of three blocks: +4.9 k before the first phase, DFT phase +1.3 k, enc_pre +1.2 k) and a
-// block's GRU phase shrinks by 0.67 k instead of 1.15 k - its GEMM, now on ONE wave per SIMD, runs at 57 cycles per MFMA (LDS operand
-// latency that the second wave of a SIMD used to cover).
-// (FE_WG8_HPRE defaults to 0 in fe_kernels.hip.h: the packed section u8_gh4 exists in such builds only)
-#ifndef FE_WG8_MIXSPLIT
-#define FE_WG8_MIXSPLIT 1
-#endif
-// r6: dec_post's 1x1 conv and the transposed conv behind it in ONE phase (one stream per workgroup).  The transposed conv of row tile ws reads the 1x1's
-// outputs of that row tile only - the tiles of waves (ws, 0) and (ws, 1), the two waves of SIMD ws - so the pair hands over through an LDS counter instead of
-// a workgroup barrier, and wave (ws, 0) runs the 12 MFMAs with the weight fragments it fetched into registers at the top of the phase (the phase of its own
-// cost ~1.4 k cycles for 0.4 k of matrix-pipe time).  Same chain, same summation order: bit-identical.  MEASURED NEGATIVE (30.86 -> 30.96 us, same box, parity
-// green): the 12 dependent MFMAs now trail the HEAVY wave of each SIMD alone (a lone wave's dependent 16x16x4 chain runs at ~64 cycles per MFMA) - off by default.
-#ifndef FE_WG8_FUSEPOST
-#define FE_WG8_FUSEPOST 0
-#endif
 constexpr int kThreads8 = 512;
 constexpr int kWaves8 = 8;
 
@@ -69,11 +50,11 @@ struct Wg8 {
     // The new GRU states of the KB blocks wait in LDS for the end of the frame and leave as whole lines (HST, when it fits): stored from the GRU
     // epilogues - 64-byte pieces of [F2][C2] rows - their acknowledgements were charged to the next vmcnt wait of the weight staging
     // (vmcnt counts loads and stores in order): 0.6 us of the 31.6 us frame (same-box timing experiment, profiles/r4a_wg8_steps.txt)
-    // r6 (FE_WG8_MIXSPLIT): the mixed gate tile's x half and h half are computed by different waves (4 / 5: x, 6 / 7: h - 63 MFMAs per SIMD instead
+    // r6: the mixed gate tile's x half and h half are computed by different waves (4 / 5: x, 6 / 7: h - 63 MFMAs per SIMD instead
     // of 72 / 72 / 54 / 54); both write their raw sums here, [half][row tile][16 rows][LDM], and the h-half wave finishes the tile's gate math
-    // one element per lane.  + 4 words: the x-half waves' "written" counters per row tile (monotonic: frame * KB + block + 1)
+    // one element per lane.  + 8 words: the x-half waves' "written" counter of each row tile (monotonic: frame * KB + block + 1), the rest padding
     static constexpr int LDM = 13;
-    static constexpr int MXB = L::NOSTAGE_TOTAL + 4 * SLOT, MX_FLOATS = round_up(4 * 16 * LDM + 8, 4), MXF = MXB + 4 * 16 * LDM;      // (+ 4 words: FE_WG8_FUSEPOST's counters per SIMD pair)
+    static constexpr int MXB = L::NOSTAGE_TOTAL + 4 * SLOT, MX_FLOATS = round_up(4 * 16 * LDM + 8, 4), MXF = MXB + 4 * 16 * LDM;
     static constexpr int HST = MXB + MX_FLOATS;
     static constexpr bool HSTASH = (size_t)(HST + S::KB * S::F2 * S::C2) * 4 <= 160 * 1024;
     static constexpr size_t BYTES = (size_t)(HST + (HSTASH ? S::KB * S::F2 * S::C2 : 0)) * 4;
@@ -169,9 +150,6 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
         if constexpr (HIO) { if (bb < a.B && tid0 >= OVL) hv = a.wav_in[(size_t)bb * a.in_stride + tid0 - OVL]; }
     };
     hop_issue((int)blockIdx.x);
-#ifdef FE_WG8_PRIO
-    if (wave0 >= 4) __builtin_amdgcn_s_setprio(FE_WG8_PRIO);      // experiment: the second wave of a SIMD runs ahead of the first
-#endif
     const float* __restrict__ wp = a.wp;
     WSrc<true> wb;
     constexpr PackedOffsets o = Pack<S>::v;
@@ -240,7 +218,7 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
             smem[L::E + e * S::ACT + (q >= LDC ? (F1 + 1) * LDC + (q - LDC) : q)] = 0.0f;
         }
         if (tid < N / 2) tw[tid] = twv;
-        if (tid < 8) smem[W8::MXF + tid] = 0.0f;          // (the hand-over counters of the mixed tile / the dec_post pairs: ints, 0)
+        if (tid < 8) smem[W8::MXF + tid] = 0.0f;          // (the mixed tile's hand-over counters and the padding behind them: ints, 0)
         st0.commit();
         if constexpr (!PERSIST) {
             st1.commit();
@@ -305,62 +283,6 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
             wb.base = o.u_off[(U)];                                                                \
         }                                                                                          \
         const StageSide<NPW, ((!PERSIST && ((U) + 1 == S::NU || (U) == 0)) || (U) == S::U_RFPRE + 1) ? 0 : o.u_size[fe_un_] / 256, kWaves8> stage{&job}
-#if FE_WG8_HPRE
-        // ---- W_hh h_{t-1} of every block, on waves 4-7: job = (channel group hcg, row tile hrt) [+ the mixed tile on waves 4, 5]
-        constexpr int HK2 = S::KS_2, HNQ = HK2 / 4, HKR = HK2 % 4, HTS = HNQ * 256 + HKR * 64;
-        static_assert(HKR <= 1, "one plain k-step after the 16-byte groups");
-        const int hcg = (wave - 4) >> 1, hrt = wave & 1;
-        f32x4 hp[S::KB][4];                     // [block]: r, z, n (with b_hn) of the group; [3]: the mixed tile (waves 4, 5)
-        float hpa[S::KB][HK2];                  // per block: A fragments (rows of h), B fragments of the job's tiles, start values - all requested
-        f32x4 hpb[S::KB][4][HNQ > 0 ? HNQ : 1];    // at the top of the frame (dead once the block's products are issued)
-        float hpr[S::KB][4], hpbn[S::KB], hpbm[S::KB];
-        auto hpre_load = [&](auto k_) {
-            constexpr int k = decltype(k_)::value;
-            if (wave >= 4) {
-                const int row = 16 * hrt + (lane & 15);
-                const float* hrow = a.h + ((size_t)k * nst + sb) * (S::F2 * S::C2) + (row < S::F2 ? row : S::F2 - 1) * S::C2 + (lane >> 4);
-#pragma unroll
-                for (int ks = 0; ks < HK2; ++ks) hpa[k][ks] = hrow[4 * ks];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int t = j < 3 ? 3 * hcg + j : 3 * S::G8_NG;              // (j = 3: the mixed tile; fetched by waves 6, 7 too - unused there)
-#pragma unroll
-                    for (int q = 0; q < HNQ; ++q) hpb[k][j][q] = wb.at_gv4(o.u8_gh4[k] + t * HTS + q * 256, wb.lane4 * 4);
-                    if constexpr (HKR == 1) hpr[k][j] = wb.at_g(o.u8_gh4[k] + t * HTS + HNQ * 256);
-                }
-                hpbn[k] = wb.at16_g(o.u8_gh[k] + S::G8_NT * HK2 * 64 + (3 * hcg + 2) * 16);      // b_hn of the group's n tile
-                hpbm[k] = wb.at16_g(o.u8_gh[k] + S::G8_NT * HK2 * 64 + (3 * S::G8_NG) * 16);      // the mixed tile's h-side start values
-            }
-        };
-        auto hpre_mma = [&](auto k_) {
-            constexpr int k = decltype(k_)::value;
-            if (wave >= 4) {
-                hp[k][0] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-                hp[k][1] = hp[k][0];
-                hp[k][2] = f32x4{hpbn[k], hpbn[k], hpbn[k], hpbn[k]};
-                hp[k][3] = f32x4{hpbm[k], hpbm[k], hpbm[k], hpbm[k]};
-                auto bfr = [&](int j, int ks) { return ks < 4 * HNQ ? hpb[k][j][ks >> 2][ks & 3] : hpr[k][j]; };
-                if (wave < 6) {
-#pragma unroll
-                    for (int ks = 0; ks < HK2; ++ks)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) hp[k][j] = FE_MFMA(hpa[k][ks], bfr(j, ks), hp[k][j]);
-                } else {
-#pragma unroll
-                    for (int ks = 0; ks < HK2; ++ks)
-#pragma unroll
-                        for (int j = 0; j < 3; ++j) hp[k][j] = FE_MFMA(hpa[k][ks], bfr(j, ks), hp[k][j]);
-                }
-            }
-        };
-        using HK0 = std::integral_constant<int, 0>;
-        using HK1 = std::integral_constant<int, (S::KB > 1 ? 1 : 0)>;
-        using HK2_ = std::integral_constant<int, (S::KB > 2 ? 2 : 0)>;
-        static_assert(S::KB <= 3, "FE_WG8_HPRE schedules three blocks");
-        hpre_load(HK0{});
-        if constexpr (S::KB > 1) hpre_load(HK1{});
-        if constexpr (S::KB > 2) hpre_load(HK2_{});
-#endif
         FE_CLK(0);
         // =========================== STFT (a1-a3) ===========================
         // LDS quarters of the FFT arena: q0 windowed frame / iSTFT partial sums, q1 iSTFT partial sums, q3 spectrum {Re[N/2], Im[N/2]}
@@ -385,12 +307,6 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
             FE_CLK(1);
             float* nyq = a.dbg ? a.dbg + (size_t)b * a.dbg_stride + DebugLayout<S>::offset(0) + 2 * F0 : nullptr;
             if (wave < 4) Dft<S>::template forward<false>(q0, q3, tw, dc, wave, lane, nyq);
-#if FE_WG8_HPRE
-            else {
-                hpre_mma(HK0{});
-                if constexpr (S::KB > 1) hpre_mma(HK1{});
-            }
-#endif
             __syncthreads();
             FE_CLK(2);
             const float* Xr = q3;
@@ -427,9 +343,6 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
                 },
                 [&](int j, int ks) { return wb.at(o.enc_pre_w + (j * 4 + ks) * 64); },
                 [&](int j) { return wb.at16x4(o.enc_pre_b + j * 64); }, stage, Ebuf, 1, ws, lane, ap);
-#if FE_WG8_HPRE
-            if constexpr (S::KB > 2) hpre_mma(HK2_{});        // (waves 4-7: the lighter half of this 12-MFMA phase)
-#endif
         }
         __syncthreads();
         dbg_dump<S, NTH>(a, b, 2, Ebuf + LDC, LDC);
@@ -468,29 +381,13 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
         constexpr int HPT = W8::HPT;
         constexpr int K2 = S::KS_2;
         f32x4 xr;                                      // residual stream x: row tile wh, channel tile ws
-        // GRU: (channel group, row tile) jobs - waves 0-3 a 16-channel group x a row tile (three gate tiles: 54 MFMAs), waves 4 and 5
-        // (SIMDs 0 and 1) the mixed tile of the left-over channels x a row tile (18 MFMAs), waves 6 and 7 none: 72 / 72 / 54 / 54
-        // MFMAs per SIMD, and the three gates of a (row, channel) meet in one lane
+        // GRU: (channel group, row tile) jobs - waves 0-3 a 16-channel group x a row tile (three gate tiles: 54 MFMAs), waves 4 / 5
+        // (SIMDs 0 and 1) the x half and waves 6 / 7 (SIMDs 2 and 3) the h half of a row tile's mixed tile of the left-over channels (9 MFMAs
+        // each): 63 MFMAs per SIMD, and the three gates of a (row, channel) meet in one lane
         const int g_rt = wave & 1;                                         // row tile of this wave's GRU job
         const int g_t0 = wave < 4 ? 3 * (wave >> 1) : 3 * S::G8_NG;        // its first gate tile
         // block weights in LDS (W8 slots): B fragment (tile, k-step) of a unit at u[(tile * K2 + ks) * 64 + lane], start value of a tile's
         // column at u[NT * K2 * 64 + tile * 16 + li]
-#ifdef FE_EXP_BREG      // timing experiment (wrong results): the blocks' B operands as register values, no block-weight staging - the upper bound of register-resident block weights
-        float breg0 = 0.001f * (float)lane, breg1 = 0.002f, breg2 = -0.001f, breg3 = 0.0005f;
-        asm volatile("" : "+v"(breg0), "+v"(breg1), "+v"(breg2), "+v"(breg3));
-#define FE8_B(expr, ks) (((ks) & 3) == 0 ? breg0 : ((ks) & 3) == 1 ? breg1 : ((ks) & 3) == 2 ? breg2 : breg3)
-#define FE8_STAGE_ON 0
-#else
-#define FE8_B(expr, ks) (expr)
-#define FE8_STAGE_ON 1
-#endif
-#ifdef FE_EXP_AREG      // ... and their A operands too (no LDS operand reads in the blocks' GEMMs at all)
-        float areg0 = 0.003f * (float)(lane & 15), areg1 = 0.001f, areg2 = -0.002f;
-        asm volatile("" : "+v"(areg0), "+v"(areg1), "+v"(areg2));
-#define FE8_A(expr, ks) ((ks) % 3 == 0 ? areg0 : (ks) % 3 == 1 ? areg1 : areg2)
-#else
-#define FE8_A(expr, ks) (expr)
-#endif
         const float* const sGx = smem + W8::WB0 + 1 * W8::SLOT;
         const float* const sGh = smem + W8::WB0 + 3 * W8::SLOT;
         const float* const sF = smem + W8::WB0 + 0 * W8::SLOT;
@@ -501,9 +398,9 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
         jb2 = jb1;
         auto stage_to = [&](DmaJobT<NPWB>& j, int src_floats, int dst_floats) { j.l = smem + dst_floats; j.soff = (src_floats + wave * 256) * 4; };
         constexpr int u8_stride = S::KB > 1 ? o.u8_gx[1] - o.u8_gx[0] : 0;
-        using StG = StageSide<NPWB, FE8_STAGE_ON * (S::U8_G / 256), kWaves8>;
-        using StF = StageSide<NPWB, FE8_STAGE_ON * (S::U8_F / 256), kWaves8>;
-        using StQ = StageSide<NPWB, FE8_STAGE_ON * (S::U8_Q / 256), kWaves8>;
+        using StG = StageSide<NPWB, S::U8_G / 256, kWaves8>;
+        using StF = StageSide<NPWB, S::U8_F / 256, kWaves8>;
+        using StQ = StageSide<NPWB, S::U8_Q / 256, kWaves8>;
         float pe_r[4];
         // unpredicated epilogue stores into the [F2P][C2 + 2] token buffers (pad rows are real rows, lanes past C2 aim at the pad column)
         auto tok_dst = [&](float* base) {
@@ -541,12 +438,8 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
         {
             // X[f2][c2] = Y1[f2][:] . Wc[c2][:] + b
             FE8_BEGIN_UNIT(S::U_RFPRE + 1);
-#if FE_WG8_HPRE
-            const NoSide stg{};                                         // (the hidden weights never pass through LDS)
-#else
             stage_to(jb1, o.u8_gh[0], W8::WB0 + 3 * W8::SLOT);          // ... and the hidden weights -> slot 3
             const StG stg{&jb1};
-#endif
             float hpre[HPT];
             const float* hg0 = a.h + (size_t)sb * (F2 * C2);
 #pragma unroll
@@ -559,9 +452,7 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
                 acc, [&](int, int ks) { return ya[4 * ks]; },
                 [&](int, int ks) { return wb.at(o.rfpre_w + (nt * S::KS_C + ks) * 64); }, stg);
             (void)stage;
-#if !FE_WG8_HPRE
             stg.commit();
-#endif
             xr = acc[0][0];
             float* xd = tok_dst(Xb);
 #pragma unroll
@@ -603,91 +494,6 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
                 const float* bh = sGh + S::G8_NT * K2 * 64 + g_t0 * 16 + li;
                 __builtin_amdgcn_sched_barrier(0);
                 if (k == 0) FE_CLK(45);
-#if FE_WG8_HPRE
-                if (wave >= 4) {
-                    // x halves on top of the hidden halves accumulated in the front: the group's tiles r, z, n (+ the mixed tile on waves 4, 5:
-                    // it shares the row tile's A fragments)
-                    const int ch = 16 * hcg + li;
-                    constexpr int R = S::G8_R;
-                    const int chm = 16 * S::G8_NG + (li < R ? li : 0);
-                    float hprev[4], hprevm[4];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        hprev[r] = Hs[(16 * hrt + 4 * lg + r) * LDX + ch];
-                        hprevm[r] = Hs[(16 * hrt + 4 * lg + r) * LDX + chm];
-                    }
-                    const float* xa8 = Xb + (16 * hrt + li) * LDX + lg;
-                    const float* wx8 = sGx + (3 * hcg) * (K2 * 64) + lane;
-                    const float* wxm = sGx + (3 * S::G8_NG) * (K2 * 64) + lane;
-                    const float* bx8 = sGx + S::G8_NT * K2 * 64 + (3 * hcg) * 16 + li;
-                    const float b0 = bx8[0], b1 = bx8[16], b2 = bx8[32], bm = sGx[S::G8_NT * K2 * 64 + (3 * S::G8_NG) * 16 + li];
-                    f32x4 ar, az, anx = f32x4{b2, b2, b2, b2}, anh, ax = f32x4{bm, bm, bm, bm}, ah;
-                    static_for<S::KB>([&](auto kk_) {         // (hp is indexed at compile time: the block loop is unrolled)
-                        constexpr int kk = decltype(kk_)::value;
-                        if (k == kk) { ar = hp[kk][0] + f32x4{b0, b0, b0, b0}; az = hp[kk][1] + f32x4{b1, b1, b1, b1}; anh = hp[kk][2]; ah = hp[kk][3]; }
-                    });
-                    if (wave < 6) {
-                        mma_panel_sel<1, 4, K2, PDK>(
-                            [&](int, int j, int) -> f32x4& { return j == 0 ? ar : (j == 1 ? az : (j == 2 ? anx : ax)); },
-                            [&](int, int ks) { return xa8[4 * ks]; },
-                            [&](int j, int ks) { return j < 3 ? wx8[(j * K2 + ks) * 64] : wxm[ks * 64]; }, sideg);
-                    } else {
-                        mma_panel_sel<1, 3, K2, PDK>(
-                            [&](int, int j, int) -> f32x4& { return j == 0 ? ar : (j == 1 ? az : anx); },
-                            [&](int, int ks) { return xa8[4 * ks]; },
-                            [&](int j, int ks) { return wx8[(j * K2 + ks) * 64]; }, sideg);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (k == 0) FE_CLK(46);
-                    float hn[4];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float rr = sigmoid_pre(ar[r]);        // (the packer scales the gate rows: -log2 e / 2 log2 e)
-                        const float zz = sigmoid_pre(az[r]);
-                        const float nn = tanh_pre(__builtin_fmaf(rr, anh[r], anx[r]));
-                        hn[r] = __builtin_fmaf(zz, hprev[r] - nn, nn);          // (1 - z) n + z h
-                    }
-                    if (16 * hrt + 4 * lg < F2) {       // (F2 % 4 == 0: the four rows of a lane are valid together)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const int row = 16 * hrt + 4 * lg + r;
-                            Hl[row * LDX + ch] = hn[r];
-                            if constexpr (W8::HSTASH) smem[W8::HST + k * (F2 * C2) + row * C2 + ch] = hn[r];
-                            else hg[row * C2 + ch] = hn[r];
-                        }
-                    }
-                    if (wave < 6) {
-                        // the mixed tile: lanes li < R hold r, R .. 2 R - 1 z, 2 R .. 3 R - 1 n of channel 16 NG + li % R; the z and n values
-                        // move down to the r lanes (DPP row shifts), which finish the R channels
-                        auto shl = [](float v, auto n_) {      // lane i <- lane i + n of its 16-lane row
-                            constexpr int n = decltype(n_)::value;
-                            return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x100 + n, 0xf, 0xf, true));
-                        };
-                        float hm[4];
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const float sx = ax[r], sh = ah[r], sm = sx + sh;
-                            const float rr = sigmoid_pre(sm);
-                            const float zz = sigmoid_pre(shl(sm, std::integral_constant<int, R>{}));
-                            const float nn = tanh_pre(__builtin_fmaf(rr, shl(sh, std::integral_constant<int, 2 * R>{}), shl(sx, std::integral_constant<int, 2 * R>{})));
-                            hm[r] = __builtin_fmaf(zz, hprevm[r] - nn, nn);
-                        }
-                        if (li < R && 16 * hrt + 4 * lg < F2) {
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) {
-                                const int row = 16 * hrt + 4 * lg + r;
-                                Hl[row * LDX + chm] = hm[r];
-                                if constexpr (W8::HSTASH) smem[W8::HST + k * (F2 * C2) + row * C2 + chm] = hm[r];
-                                else hg[row * C2 + chm] = hm[r];
-                            }
-                        }
-                    }
-                } else {
-                    constexpr int NSG = (K2 + 3) / 4;      // waves 0-3: their share of the staging only
-#pragma unroll
-                    for (int g = 0; g < NSG; ++g) sideg(g, NSG);
-                }
-#else
                 if (wave < 4) {
                     // a 16-channel group: tiles r, z (x and h halves in one accumulator), n (separate halves)
                     const int ch = 16 * (wave >> 1) + li;
@@ -697,15 +503,10 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
                     const float b0 = bx[0], b1 = bx[16], b2 = bx[32], b3 = bh[32];
                     f32x4 ar = f32x4{b0, b0, b0, b0}, az = f32x4{b1, b1, b1, b1};
                     f32x4 anx = f32x4{b2, b2, b2, b2}, anh = f32x4{b3, b3, b3, b3};
-#ifdef FE_EXP_NOHH      // timing experiment (wrong results): the GRU phases without their W_hh h products
-                    constexpr int KSG = K2;
-#else
-                    constexpr int KSG = 2 * K2;
-#endif
-                    mma_panel_sel<1, 3, KSG, PDK>(
+                    mma_panel_sel<1, 3, 2 * K2, PDK>(
                         [&](int, int j, int ks) -> f32x4& { return j == 0 ? ar : (j == 1 ? az : (ks < K2 ? anx : anh)); },
-                        [&](int, int ks) { return FE8_A(ks < K2 ? xa[4 * ks] : ha[4 * (ks - K2)], ks); },
-                        [&](int j, int ks) { return FE8_B(ks < K2 ? wx[(j * K2 + ks) * 64] : wh_[(j * K2 + (ks - K2)) * 64], ks + j); }, sideg);
+                        [&](int, int ks) { return ks < K2 ? xa[4 * ks] : ha[4 * (ks - K2)]; },
+                        [&](int j, int ks) { return ks < K2 ? wx[(j * K2 + ks) * 64] : wh_[(j * K2 + (ks - K2)) * 64]; }, sideg);
                     __builtin_amdgcn_sched_barrier(0);
                     if (k == 0) FE_CLK(46);
                     float hn[4];
@@ -725,14 +526,12 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
                             else hg[row * C2 + ch] = hn[r];
                         }
                     }
-                }
-#if FE_WG8_MIXSPLIT
-                else {
+                } else {
                     // r6: the mixed tile (the left-over R channels' r | z | n columns) of row tile g_rt, x half on waves 4 / 5, h half on waves
                     // 6 / 7: 9 MFMAs each next to the 54 of their SIMD's channel-group job - 63 MFMAs per SIMD.  Each half goes to LDS as a
                     // [16 rows][3 R columns] matrix; the h-half wave waits for its partner's counter (a wave's LDS operations execute in order)
-                    // and finishes the R channels one (row, channel) per lane.  Same chains, same summation order, same gate arithmetic as the
-                    // one-wave form (bit-identical results).
+                    // and finishes the R channels one (row, channel) per lane.  Same chains, same summation order and gate arithmetic as ONE wave
+                    // running the tile's x and h halves as a single 2 K2-step panel.
                     constexpr int R = S::G8_R, LDM = W8::LDM;
                     const bool hhalf = wave >= 6;
                     float* mx = smem + W8::MXB + ((hhalf ? 2 : 0) + g_rt) * (16 * LDM);
@@ -744,14 +543,14 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
                         const float b0 = bx[0];
                         s0 = f32x4{b0, b0, b0, b0};
                         mma_panel_sel<1, 1, K2, PDK>([&](int, int, int ks) -> f32x4& { return (ks & 1) ? s1 : s0; },
-                                                     [&](int, int ks) { return FE8_A(xa[4 * ks], ks); }, [&](int, int ks) { return FE8_B(wx[ks * 64], ks); }, sideg);
+                                                     [&](int, int ks) { return xa[4 * ks]; }, [&](int, int ks) { return wx[ks * 64]; }, sideg);
                     } else {
                         const float b1 = bh[0];
                         s0 = f32x4{b1, b1, b1, b1};
-                        // (the one-wave form ran x and h as ONE 2 K2-step panel with chains by the parity of the global k-step: K2 is odd here,
-                        // so the biased chain took the h half's odd local steps)
+                        // (the chains go by the parity of the k-step of the whole 2 K2-step x | h panel: K2 is odd here, so the biased chain takes
+                        // the h half's odd local steps)
                         mma_panel_sel<1, 1, K2, PDK>([&](int, int, int ks) -> f32x4& { return ((ks + K2) & 1) ? s1 : s0; },
-                                                     [&](int, int ks) { return FE8_A(ha[4 * ks], ks); }, [&](int, int ks) { return FE8_B(wh_[ks * 64], ks); }, sideg);
+                                                     [&](int, int ks) { return ha[4 * ks]; }, [&](int, int ks) { return wh_[ks * 64]; }, sideg);
                     }
                     // (the priority stays raised through the hand-over and the gate math: at priority 0 every instruction of this dependent chain
                     // waited for a gap between the MFMAs of the SIMD's 54-MFMA job - 1.5 k cycles for ~35 instructions, and this wave arrived last)
@@ -792,77 +591,6 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
                     }
                     __builtin_amdgcn_s_setprio(0);
                 }
-#else
-                else if (wave < 6) {
-                    // the mixed tile: lanes li < R hold r, R .. 2 R - 1 z, 2 R .. 3 R - 1 n of channel 16 NG + li % R; the z and n values
-                    // move down to the r lanes (DPP row shifts), which finish the R channels.  (18 dependent MFMAs next to the 54
-                    // independent ones of this SIMD's big job: two chains per half, and a raised priority - arbitrated oldest-first,
-                    // this wave got a matrix-pipe slot only when the other one stalled and the whole workgroup waited for it)
-                    constexpr int R = S::G8_R;
-                    const int ch = 16 * S::G8_NG + (li < R ? li : 0);
-                    float hprev[4];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) hprev[r] = Hs[(16 * g_rt + 4 * lg + r) * LDX + ch];
-                    const float b0 = bx[0], b1 = bh[0];
-                    f32x4 ax = f32x4{b0, b0, b0, b0}, ah = f32x4{b1, b1, b1, b1};
-                    f32x4 ax1 = f32x4{0.0f, 0.0f, 0.0f, 0.0f}, ah1 = ax1;
-#ifdef FE_WG8_MIX4      // four accumulator chains per half instead of two: the dependent chain of the small job ends earlier
-                    f32x4 ax2 = ax1, ax3 = ax1, ah2 = ax1, ah3 = ax1;
-#endif
-                    __builtin_amdgcn_s_setprio(3);
-#ifdef FE_EXP_NOHH
-                    constexpr int KSG = K2;
-#else
-                    constexpr int KSG = 2 * K2;
-#endif
-                    mma_panel_sel<1, 1, KSG, PDK>(
-#ifdef FE_WG8_MIX4
-                        [&](int, int, int ks) -> f32x4& { return ks < K2 ? ((ks & 3) == 0 ? ax : (ks & 3) == 1 ? ax1 : (ks & 3) == 2 ? ax2 : ax3)
-                                                                         : ((ks & 3) == 0 ? ah : (ks & 3) == 1 ? ah1 : (ks & 3) == 2 ? ah2 : ah3); },
-#else
-                        [&](int, int, int ks) -> f32x4& { return ks < K2 ? ((ks & 1) ? ax1 : ax) : ((ks & 1) ? ah1 : ah); },
-#endif
-                        [&](int, int ks) { return FE8_A(ks < K2 ? xa[4 * ks] : ha[4 * (ks - K2)], ks); },
-                        [&](int, int ks) { return FE8_B(ks < K2 ? wx[ks * 64] : wh_[(ks - K2) * 64], ks); }, sideg);
-                    __builtin_amdgcn_s_setprio(0);
-#ifdef FE_WG8_MIX4
-                    ax = (ax + ax1) + (ax2 + ax3);
-                    ah = (ah + ah1) + (ah2 + ah3);
-#else
-                    ax += ax1;
-                    ah += ah1;
-#endif
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (k == 0) FE_CLK(46);
-                    auto shl = [](float v, auto n_) {      // lane i <- lane i + n of its 16-lane row
-                        constexpr int n = decltype(n_)::value;
-                        return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x100 + n, 0xf, 0xf, true));
-                    };
-                    float hn[4];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float sx = ax[r], sh = ah[r], sm = sx + sh;
-                        const float rr = sigmoid_pre(sm);
-                        const float zz = sigmoid_pre(shl(sm, std::integral_constant<int, R>{}));
-                        const float nn = tanh_pre(__builtin_fmaf(rr, shl(sh, std::integral_constant<int, 2 * R>{}), shl(sx, std::integral_constant<int, 2 * R>{})));
-                        hn[r] = __builtin_fmaf(zz, hprev[r] - nn, nn);          // (1 - z) n + z h
-                    }
-                    if (li < R && 16 * g_rt + 4 * lg < F2) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const int row = 16 * g_rt + 4 * lg + r;
-                            Hl[row * LDX + ch] = hn[r];
-                            if constexpr (W8::HSTASH) smem[W8::HST + k * (F2 * C2) + row * C2 + ch] = hn[r];
-                            else hg[row * C2 + ch] = hn[r];
-                        }
-                    }
-                } else {
-                    constexpr int NSG = (2 * K2 + 3) / 4;      // no GRU job: this wave's share of the staging only
-#pragma unroll
-                    for (int g = 0; g < NSG; ++g) sideg(g, NSG);
-                }
-#endif
-#endif
                 st1.commit();
                 st2.commit();
             }
@@ -881,10 +609,10 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
                 const float* hla = Hl + (16 * wh + li) * LDX + lg;
                 const float* wf = sF + ntf * (K2 * 64) + lane;
                 if (k + 1 < S::KB) {
-                    mma_panel<1, 1, K2, PDK>(acc, [&](int, int ks) { return FE8_A(hla[4 * ks], ks); }, [&](int, int ks) { return FE8_B(wf[ks * 64], ks); }, stn);
+                    mma_panel<1, 1, K2, PDK>(acc, [&](int, int ks) { return hla[4 * ks]; }, [&](int, int ks) { return wf[ks * 64]; }, stn);
                     stn.commit();
                 } else
-                    mma_panel<1, 1, K2, PDK>(acc, [&](int, int ks) { return FE8_A(hla[4 * ks], ks); }, [&](int, int ks) { return FE8_B(wf[ks * 64], ks); }, NoSide{});
+                    mma_panel<1, 1, K2, PDK>(acc, [&](int, int ks) { return hla[4 * ks]; }, [&](int, int ks) { return wf[ks * 64]; }, NoSide{});
                 float* xd = tok_dst(Xb);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
@@ -906,11 +634,11 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
                 __builtin_amdgcn_sched_barrier(0);
                 if (k == 0) FE_CLK(50);
                 const float* xa = Xb + (16 * wh + li) * LDX + lg;
-                mma_panel<1, NTPW3, K2, PDK>(acc, [&](int, int ks) { return FE8_A(xa[4 * ks], ks); },
+                mma_panel<1, NTPW3, K2, PDK>(acc, [&](int, int ks) { return xa[4 * ks]; },
                                              [&](int j, int ks) {
                                                  int nt = ws + 4 * j;
                                                  nt = nt < S::NT3 ? nt : S::NT3 - 1;
-                                                 return FE8_B(sQ[(nt * K2 + ks) * 64 + lane], ks + j);
+                                                 return sQ[(nt * K2 + ks) * 64 + lane];
                                              }, st1);
                 st1.commit();
                 __builtin_amdgcn_sched_barrier(0);
@@ -946,18 +674,14 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
                 const float* hla = Hl + (16 * wh + li) * LDX + lg;
                 const float* wf = sF + ntf * (K2 * 64) + lane;
                 if (k + 1 < S::KB) {
-#if FE_WG8_HPRE
-                    mma_panel<1, 1, K2, PDK>(acc, [&](int, int ks) { return FE8_A(hla[4 * ks], ks); }, [&](int, int ks) { return FE8_B(wf[ks * 64], ks); }, NoSide{});
-#else
                     stage_to(jb1, o.u8_gh[0] + ub + u8_stride, W8::WB0 + 3 * W8::SLOT);
                     const StG stn{&jb1};
-                    mma_panel<1, 1, K2, PDK>(acc, [&](int, int ks) { return FE8_A(hla[4 * ks], ks); }, [&](int, int ks) { return FE8_B(wf[ks * 64], ks); }, stn);
+                    mma_panel<1, 1, K2, PDK>(acc, [&](int, int ks) { return hla[4 * ks]; }, [&](int, int ks) { return wf[ks * 64]; }, stn);
                     stn.commit();
-#endif
                 } else {
                     stage_to(jb1, o.u_off[S::U_RFPOST], W8::WB1);
                     const StageSide<NPWB, o.u_size[S::U_RFPOST] / 256, kWaves8> stn{&jb1};
-                    mma_panel<1, 1, K2, PDK>(acc, [&](int, int ks) { return FE8_A(hla[4 * ks], ks); }, [&](int, int ks) { return FE8_B(wf[ks * 64], ks); }, stn);
+                    mma_panel<1, 1, K2, PDK>(acc, [&](int, int ks) { return hla[4 * ks]; }, [&](int, int ks) { return wf[ks * 64]; }, stn);
                     stn.commit();
                 }
                 if (k + 1 < S::KB) {
@@ -1042,50 +766,7 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
         // =========================== dec_post (a15) ===========================
         float* PT = smem + L::PT;
         typename Dft<S>::InvConst idc;
-        constexpr bool FUSEP = FE_WG8_FUSEPOST && !PERSIST;
-        float mb0 = 0.0f, mb1 = 0.0f;                  // the mask's two biases (FUSEP: the transposed conv's unit is not staged)
-        if constexpr (FUSEP) {
-            FE8_BEGIN_UNIT(S::U_POST);
-            (void)stage;
-            float wt[S::KS_C];
-            if (wh == 0) {
-#pragma unroll
-                for (int ks = 0; ks < S::KS_C; ++ks) wt[ks] = wb.at_g(o.post_t_w + ks * 64);
-            }
-            mb0 = wp[o.post_t_b];
-            mb1 = wp[o.post_t_b + 1];
-            {
-                const float* xa = Wx + (16 * ws + li + 1) * LDC + lg;
-                const float* sk = Ebuf + (16 * ws + li + 1) * LDC + lg;
-                conv8_pair<S, W8::NTA, W8::NTB, 2 * S::KS_C, C1, LDC, true>(
-                    wh, [&](int ks) { return ks < S::KS_C ? xa[4 * ks] : sk[4 * (ks - S::KS_C)]; },
-                    [&](int j, int ks) { return wb.at(o.post1_w + (j * (2 * S::KS_C) + ks) * 64); },
-                    [&](int j) { return wb.at16x4(o.post1_b + j * 64); }, NoSide{}, Wy, 1, ws, lane, ap);
-            }
-            int* pflag = reinterpret_cast<int*>(smem + W8::MXF) + 4 + ws;
-            const int seq = fc + 1;
-            if (wh == 1) {
-                __atomic_signal_fence(__ATOMIC_SEQ_CST);
-                __builtin_amdgcn_s_waitcnt(0xc07f);          // lgkmcnt(0): this wave's tile is in LDS
-                if (lane == 0) __hip_atomic_store(pflag, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                __atomic_signal_fence(__ATOMIC_SEQ_CST);
-            } else {
-                __atomic_signal_fence(__ATOMIC_SEQ_CST);
-                while (__builtin_amdgcn_readfirstlane(__hip_atomic_load(pflag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) < seq) {}
-                __atomic_signal_fence(__ATOMIC_SEQ_CST);
-                // transposed conv as a GEMM: P[i][co * 8 + j] = sum_ci x[i][ci] w[ci][co][j]   (rows of tile ws; a wave's own LDS writes are visible to it in order)
-                const float* xa = Wy + (16 * ws + li + 1) * LDC + lg;
-                float av[S::KS_C];
-#pragma unroll
-                for (int ks = 0; ks < S::KS_C; ++ks) av[ks] = xa[4 * ks];
-                f32x4 pacc = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-                for (int ks = 0; ks < S::KS_C; ++ks) pacc = FE_MFMA(av[ks], wt[ks], pacc);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) PT[(16 * ws + 4 * lg + r) * S::LDP + li] = pacc[r];
-                Dft<S>::load(idc, wb, o, wave);               // iSTFT constants, in flight during the mask phase
-            }
-        } else {
+        float mb0 = 0.0f, mb1 = 0.0f;                  // the mask's two biases
         {
             FE8_BEGIN_UNIT(S::U_POST);
             const float* xa = Wx + (16 * ws + li + 1) * LDC + lg;
@@ -1106,7 +787,6 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
             if (wave < 4) Dft<S>::load(idc, wb, o, wave);         // iSTFT constants, in flight during the mask phase
             mb0 = wb.scalar(o.post_t_b);
             mb1 = wb.scalar(o.post_t_b + 1);
-        }
         }
         __syncthreads();
 
@@ -1213,9 +893,6 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
         ++fc;
     } while (PERSIST && b < a.B);
 #undef FE8_BEGIN_UNIT
-#undef FE8_B
-#undef FE8_A
-#undef FE8_STAGE_ON
     FE_CLK(63);
 }
 

@@ -116,9 +116,6 @@ void launch_impl(const typename KernelArgs<SLOT, STRM>::type& a, int max_wgs, hi
     if constexpr (!SLOT)
         if (dbg) return launch_one<S, true, -1, false, true>(a, grid, st, err);
     if (per_hop) {                                                                       // the per-hop hot path
-#ifdef FE_EXP_NONPERSIST      // experiment: one workgroup per stream at any batch (the hardware queues what is not resident); LOW = 1 keeps nothing per workgroup in global memory
-        if (!SLOT && S::LOW == 1) grid = a.B;
-#endif
         if (grid == a.B) return launch_one<S, false, FE_MODE_STREAM, true, false, SLOT, HIO, STRM>(a, grid, st, err);
         return launch_one<S, false, FE_MODE_STREAM, true, true, SLOT, HIO, STRM>(a, grid, st, err);
     }

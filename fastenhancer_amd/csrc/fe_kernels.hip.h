@@ -39,12 +39,6 @@ constexpr int FE_MODE_STREAM = 0, FE_MODE_SPEC = 1, FE_MODE_OFFLINE = 2;
 constexpr int kThreads = 256;
 constexpr int kWaves = 4;
 
-// FE_WG8_HPRE=1: a measured-negative variant of the 512-thread per-hop kernel (fe_frame8.hip.h, profiles/r5_headline_hpre.txt); its extra packed
-// section (PackedOffsets::u8_gh4) exists in such builds only
-#ifndef FE_WG8_HPRE
-#define FE_WG8_HPRE 0
-#endif
-
 
 // compile-time loop: f(std::integral_constant<int, 0>{}), ..., f(std::integral_constant<int, N-1>{})
 template <class F, int... I>
@@ -148,7 +142,6 @@ struct Shape {
     // 512-thread per-hop kernel: its block weights are staged through LDS like the conv weights, as units of whole 1-KiB pieces:
     // B fragments [tile][k-step][64] followed by the tiles' start values [tile][16] (a token GEMM's bias)
     static constexpr int U8_G = round_up(G8_NT * (C2 / 4) * 64 + G8_NT * 16, 256);                     // GRU input / hidden weights: the channel-grouped gate tiles
-    static constexpr int U8_GH4 = round_up(G8_NT * (((C2 / 4) / 4) * 256 + ((C2 / 4) % 4) * 64), 256);      // the hidden weights regrouped for 16-byte fetches (PackedOffsets::u8_gh4)
     static constexpr int U8_F = round_up(ceil_div(C2, 16) * (C2 / 4) * 64 + ceil_div(C2, 16) * 16, 256);   // rnn_fc / attn_fc
     static constexpr int U8_Q = round_up(ceil_div(3 * C2, 16) * (C2 / 4) * 64, 256);                   // qkv (no bias)
     static constexpr int U8_SLOT = U8_G > U8_Q ? U8_G : U8_Q;                                        // one of the four staging slots
@@ -161,15 +154,6 @@ struct Shape {
 // Offsets (floats) of the packed weights inside the handle's device buffer.  The layout is a pure
 // function of the shape, evaluated at compile time and shared by the host packer (fe_api.hip) and the
 // kernel, where every offset folds into an instruction immediate / one SGPR add.
-#ifndef FE_FBAL
-#define FE_FBAL 1           // r5: rnn_fc / attn_fc of the shapes with more than four column tiles over balanced (column tile, row tile) jobs (fe_frame_kernel; 0: whole column tiles, for A/B runs)
-#endif
-#ifndef FE_QBAL
-#define FE_QBAL 1           // r5: qkv's last two column tiles (NT3 % 4 == 2: L) split by row halves over the wave pairs (0: whole column tiles, for A/B runs)
-#endif
-#ifndef FE_K4_STREAM
-#define FE_K4_STREAM 1      // r4x: shapes that stream their block weights from L2 inside the GEMMs (M, L, their 48 kHz / variant shapes) fetch four k-steps per 16-byte load too
-#endif
 struct PackedOffsets {
     int enc_pre_w, enc_pre_b;
     int enc_w[16], enc_b[8];            // enc_w / dec3_w: [layer * KT + tap], taps in consumption order (tap 0 = the current frame)
@@ -184,7 +168,7 @@ struct PackedOffsets {
     int blk_qkv_b[8], blk_fhh[8], blk_fbhn[8];
     // dptransformer variant: the time attention's qkv weights per block, the model's positional bias [NH][32] (slot L = current frame)
     int blk_tqkv[8], tpe;
-    int blk_end, k4_delta;      // end of the block-weight region; distance to its k4-regrouped copy (Shape::REGW, else 0)
+    int blk_end, k4_delta;      // end of the block-weight region; distance to its k4-regrouped copy
     int conv_k4_delta;          // time-batched engine (Shape::TB): distance from the conv units to their k4-regrouped copy (r4w), else 0
     // ln variant: rf_post's 1x1 conv as a staged unit (B fragments + bias), gain / bias of every norm site ([channel])
     int rfpost1_w, rfpost1_b, ln_g[48], ln_b[48];
@@ -204,8 +188,6 @@ struct PackedOffsets {
     // (start values: b_ih, plus b_hh on pure r / z tiles whose x and h halves share an accumulator / b_hh on the n tiles and the mixed
     // tile, else 0); f1, q, f2: rnn_fc, qkv, attn_fc in their plain column order.
     int u8_gx[8], u8_gh[8], u8_f1[8], u8_q[8], u8_f2[8];
-    int u8_gh4[8];                      // r5: the hidden-weight tiles once more, [tile][k-step / 4][lane][4] + the k-steps % 4 plain: fetched by the waves that
-                                        // accumulate W_hh h of all blocks in the front of the frame (fe_frame8.hip.h, FE_WG8_HPRE)
     int total;
     // LDS-staged weight "units" in consumption order (one per conv-type GEMM phase): [weights | bias],
     // 256-float aligned and padded, so that a unit is staged by whole 1-KiB global_load_lds pieces.
@@ -275,11 +257,8 @@ struct Pack {
             for (int q = 0; q < S::LN_SITES; ++q) { o.ln_g[q] = alloc(szBias(C1 > C2 ? C1 : C2)); o.ln_b[q] = alloc(szBias(C1 > C2 ? C1 : C2)); }
         o.blk_stride = S::KB > 1 ? o.blk_wih[1] - o.blk_wih[0] : 0;
         o.gru_flat = S::GFLAT ? 1 : 0;
-        o.k4_delta = 0;
-        if (S::REGW || FE_K4_STREAM) {      // k4-regrouped copy of [blk_wih[0], blk_end): the register-resident fetches (TokW) and, r4x, the STREAMED block weights of the big shapes
-            const int n = o.blk_end - o.blk_wih[0];
-            o.k4_delta = alloc(n) - o.blk_wih[0];
-        }
+        // k4-regrouped copy of [blk_wih[0], blk_end): the register-resident fetches (TokW) and, r4x, the STREAMED block weights of the big shapes
+        o.k4_delta = alloc(o.blk_end - o.blk_wih[0]) - o.blk_wih[0];
         o.window = alloc(S::NFFT); o.window_istft = alloc(S::NFFT); o.twiddle = alloc(S::NFFT);
         {
             constexpr int N1 = S::NFFT / 32, KC = N1 / 2, MT = N1 / 16;
@@ -302,10 +281,6 @@ struct Pack {
                 o.u8_q[k] = cur; cur += S::U8_Q;
                 o.u8_f2[k] = cur; cur += S::U8_F;
             }
-#if FE_WG8_HPRE
-        if (S::G8P)
-            for (int k = 0; k < S::KB; ++k) { cur = round_up(cur, 256); o.u8_gh4[k] = cur; cur += S::U8_GH4; }
-#endif
         o.conv_k4_delta = 0;
         if (S::KT == 1 && !S::LN) {     // (allocated after everything else: every other offset is the same with and without it; NOT a function of LOW: a companion shares its shape's buffer)
             // r4w: the time-batched engine's conv GEMMs stream their weight fragments from L2 - one wave-level load per (tile, k-step) kept the
@@ -1216,7 +1191,7 @@ struct ConvB {
     const WS& w;
     int w_off;
     mutable f32x4 cur[NT];
-    static constexpr bool K4 = FE_K4_STREAM && !std::is_same_v<std::remove_cv_t<WS>, WSrc<true>> && KS_TOT >= 4;
+    static constexpr bool K4 = !std::is_same_v<std::remove_cv_t<WS>, WSrc<true>> && KS_TOT >= 4;
     __device__ __forceinline__ float operator()(int j, int ks) const {
         constexpr int CK4 = Pack<S>::v.conv_k4_delta;
         if constexpr (K4 && CK4 != 0) {
@@ -1296,7 +1271,7 @@ __device__ __forceinline__ void conv_nsplit(AF&& af, const WS& w, int w_off, int
         for (int i = 0; i < MT; ++i) acc[i][j] = bj;
     }
     constexpr int CK4 = Pack<S>::v.conv_k4_delta;
-    if constexpr (FE_K4_STREAM && CK4 != 0 && KS >= 4 && !std::is_same_v<std::remove_cv_t<WS>, WSrc<true>>) {
+    if constexpr (CK4 != 0 && KS >= 4 && !std::is_same_v<std::remove_cv_t<WS>, WSrc<true>>) {
         // r4x: the streamed conv weights four k-steps per 16-byte load, from the k4-regrouped copy of the conv units (the one the time-batched
         // engine reads; its KS % 4 left-over k-steps are plain)
         f32x4 cur[NTW];
@@ -1413,11 +1388,11 @@ struct TokW {
     mutable f32x4 cur[REG ? 1 : NTPW][REG ? 1 : NG];
     __device__ __forceinline__ float get(int j, int g, int ks) const {
         if constexpr (REG) return w[j][g][ks];
-        else if constexpr (FE_K4_STREAM) {
+        else {
             if (ks >= 4 * (KS / 4)) return src->at_gv(w_off + src->k4d + (tile(j, g) * KS + ks) * 64, src->lane4 + oob(j));
             if ((ks & 3) == 0) cur[j][g] = src->at_gv4(w_off + src->k4d + tile(j, g) * (KS * 64) + (ks >> 2) * 256, src->lane4 * 4 + oob(j));
             return cur[j][g][ks & 3];
-        } else return src->at_gv(w_off + (tile(j, g) * KS + ks) * 64, src->lane4 + oob(j));
+        }
     }
     __device__ __forceinline__ float bias(int j, int g) const {
         if constexpr (REG) return bv[j][g];
@@ -1771,21 +1746,15 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
     // piece by piece so that a phase's own weight fetches (older in the in-order vmcnt queue) never wait for more than one piece.
     // The time attention itself then runs from registers; what stays exposed is the part of the stream that does not fit under the
     // compute in between (kvw_issue / FE_KVW below, phase B of the blocks).
-#ifndef FE_KVW_PREFETCH
-#define FE_KVW_PREFETCH 1
-#endif
     constexpr int W_PAIRS = F2 * S::NH;
-    constexpr bool WPF = FE_KVW_PREFETCH && S::TATT && !PIPE && !DBG && T1 && !PERSIST && W_PAIRS % 16 == 0 && (W_PAIRS / 16) * 4 * HD <= 224;
+    constexpr bool WPF = S::TATT && !PIPE && !DBG && T1 && !PERSIST && W_PAIRS % 16 == 0 && (W_PAIRS / 16) * 4 * HD <= 224;
     constexpr int W_NIT = WPF ? W_PAIRS / 16 : 1;
 #ifndef FE_KVW_NB
 #define FE_KVW_NB 2
 #endif
-#ifndef FE_KVW_FRONT
-#define FE_KVW_FRONT 0
-#endif
     constexpr int W_NB = FE_KVW_NB;                  // pieces of the next block's window issued inside phase B itself
     // front schedule of block 0's window: piece issued after {frame load, DFT, compress, enc_pre}, the encoder layers take the next NL
-    constexpr int W_F0 = 0, W_F1 = FE_KVW_FRONT == 0 ? 1 : -1, W_F2 = FE_KVW_FRONT == 0 ? 2 : 1, W_F3 = FE_KVW_FRONT == 0 ? 3 : 2;
+    constexpr int W_F0 = 0, W_F1 = 1, W_F2 = 2, W_F3 = 3;
     constexpr int W_FE = W_F3 + 1;
     float kvw[W_NIT][WPF ? 4 * HD : 1];
     int t_end = a.T;
@@ -1801,20 +1770,16 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
         // generic, time-pipelined) - r1's "L loses 7 %" was measured when one instantiation served everything.  FastEnhancer_L:
         // SGPR spills 2322 / 2371 / 2380 -> 37 / 93 / 119, VGPR spills 114 / 205 / 75 -> 0 (with the per-lane zero below);
         // 512 / 1024 streams 60.2 / 60.8 % -> 65.3 / 65.4 % of the fp32 peak, 16 x 4 s offline (frame walk) 16.1 -> 15.5 ms.
-#ifndef FE_LZ_BIG
-#define FE_LZ_BIG 1      // (0: r3's behaviour, for A/B builds)
-#endif
-#ifndef FE_LZ_T1
-#define FE_LZ_T1 1      // r4w: the big shapes' per-hop instantiation too - it has no loop, but its offsets were all derived at kernel entry and
-#endif                  // parked in spilled SGPRs (FastEnhancer_L: 1022 SGPR spills -> 0; 256 streams 377 -> 364 us, 0.645 -> 0.669).  0: r4d's behaviour
-        if constexpr (S::C1 <= 96 || (FE_LZ_BIG && (PERSIST || PIPE || !T1 || FE_LZ_T1))) asm volatile("" : "+s"(lz));
+        // r4w: the big shapes' per-hop instantiation too - it has no loop, but its offsets were all derived at kernel entry and
+        // parked in spilled SGPRs (FastEnhancer_L: 1022 SGPR spills -> 0; 256 streams 377 -> 364 us, 0.645 -> 0.669)
+        asm volatile("" : "+s"(lz));
         const int wave = wave0 + lz;
         // LOW = 2 companions (256 VGPRs, operands streamed from L2): the same for the per-lane offsets - hoisted out of the
         // stream loop they stay live through the whole frame and the persistent instantiation spills (S: 167 -> 92 VGPRs,
         // 48 kHz B: 73 -> 14; +12 % / +15 % at 1024 streams).  Kernels that fit anyway pay for the re-derived offsets
         // (B companion -3 %, T -7 %): not applied there.
         int lzv = 0;
-        if constexpr ((PERSIST && S::LOW == 2) || (FE_LZ_BIG && S::C1 > 96 && (PERSIST || PIPE || !T1))) asm volatile("" : "+v"(lzv));
+        if constexpr ((PERSIST && S::LOW == 2) || (S::C1 > 96 && (PERSIST || PIPE || !T1))) asm volatile("" : "+v"(lzv));
         const int tid = tid0 + lzv;
         const int lane = lane0 + lzv;
         const int li = lane & 15, lg = lane >> 4;
@@ -1958,7 +1923,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                 Xi = &X[0].y;
             }
             FE_CLK(2);
-            if constexpr (W_F1 >= 0) FE_KVW(0, W_F1);
+            FE_KVW(0, W_F1);
             // spectrum bins 0..F0 (F0 = Nyquist, dropped by the model)
             if (a.dbg) {
                 float* dst = a.dbg + (size_t)b * a.dbg_stride + DebugLayout<S>::offset(0);
@@ -1975,7 +1940,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
         } else {
             const float* sp = a.spec_in + (size_t)b * (F0 + 1) * a.T * 2;
             FE_KVW(0, W_F0);
-            if constexpr (W_F1 >= 0) FE_KVW(0, W_F1);
+            FE_KVW(0, W_F1);
             for (int f = tid; f < F0; f += kThreads) {
                 float re = sp[((size_t)f * a.T + t) * 2], im = sp[((size_t)f * a.T + t) * 2 + 1];
                 float mag = fmaxf(sqrtf(re * re + im * im), 1.0e-5f);
@@ -2184,7 +2149,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
         // column tile) items q = wave + 4 x, x < NXI (slot 1, index x): L 6 + 6 + 6 + 6 tile-rows instead of 8 + 8 + 4 + 4, M 4 + 4 + 4 + 3 instead of
         // 6 + 3 + 3 + 3.  (The GRU phase of these shapes has been running on such jobs since r2: GBAL.)
         // (three items per wave in three different row tiles - 48 kHz L, six row tiles - measured -0.3 %: no A fragment is shared any more; left as it was)
-        constexpr bool FBAL = FE_FBAL && !REGW && S::NT2 > 4 && S::NT2 <= 8 && !S::LN &&
+        constexpr bool FBAL = !REGW && S::NT2 > 4 && S::NT2 <= 8 && !S::LN &&
                               ((kWaves % S::MT2) == 0 || ceil_div((S::NT2 - 4) * S::MT2, kWaves) <= 2);
         constexpr int NE = FBAL ? S::NT2 - 4 : 1, NXQ = NE * S::MT2, NXI = FBAL ? ceil_div(NXQ, kWaves) : 1;
         static_assert(!FBAL || (NXI <= S::MT2 && NTPW2 == 2), "FBAL: the extra items live in slot 1 of the residual registers");
@@ -2809,11 +2774,10 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                             [&](int g, int ks) {
                                 const int k = ks < K2 ? ks : ks - K2;
                                 const int base = (ks < K2 ? wih : whh) + (g * S::NT2 + ct) * (K2 * 64);
-                                if constexpr (FE_K4_STREAM) {       // four k-steps per 16-byte load (the k4 copy; its K2 % 4 left-over k-steps are plain)
-                                    if (k >= 4 * (K2 / 4)) return wb.at_g(base + wb.k4d + k * 64);
-                                    if ((k & 3) == 0) gcur[g] = wb.at_gv4(base + wb.k4d + (k >> 2) * 256, wb.lane4 * 4);
-                                    return gcur[g][k & 3];
-                                } else return wb.at_g(base + k * 64);
+                                // four k-steps per 16-byte load (the k4 copy; its K2 % 4 left-over k-steps are plain)
+                                if (k >= 4 * (K2 / 4)) return wb.at_g(base + wb.k4d + k * 64);
+                                if ((k & 3) == 0) gcur[g] = wb.at_gv4(base + wb.k4d + (k >> 2) * 256, wb.lane4 * 4);
+                                return gcur[g][k & 3];
                             }, NoSide{});
                         const int c = 16 * ct + li;
                         if (c < C2) {
@@ -2953,7 +2917,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                 Wgi.bind(wb, (o.blk_wih[0] + kb + o.blk_stride), (o.blk_bih[0] + kb + o.blk_stride), GNT, wave, k + 1 < S::KB && !S::TATT);
                 // r5, QBAL: eighteen column tiles (L) are 5 : 5 : 4 : 4 over the waves; the last two tiles' row tiles go half and half to the wave pairs
                 // (0, 2) / (1, 3) instead: 4.5 tiles each.  (Gi is LDS only: no register-resident ownership to move.)
-                constexpr bool QBAL = FE_QBAL && !REGW && !L::PERHEAD && (S::NT3 % 4) == 2 && (S::MT2 % 2) == 0 && NTPW3 >= 2;
+                constexpr bool QBAL = !REGW && !L::PERHEAD && (S::NT3 % 4) == 2 && (S::MT2 % 2) == 0 && NTPW3 >= 2;
                 if constexpr (QBAL) {
                     constexpr int NQ = NTPW - 1, MH = S::MT2 / 2, KS = S::KS_2;
                     f32x4 acc[S::MT2][NQ];

@@ -110,24 +110,9 @@ struct LSbLds {
     static constexpr size_t BYTES = (size_t)TOTAL * 4;
 };
 
-// r6d experiment (FE_LSB_NT=1): the per-stream cache tensors - read once and written once per step - as non-temporal accesses, so that they do not displace the carry in L2
-#ifndef FE_LSB_NT
-#define FE_LSB_NT 0
-#endif
-__device__ __forceinline__ f32x4 lsb_ld_state4(const float* p) {
-#if FE_LSB_NT
-    return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
-#else
-    return *reinterpret_cast<const f32x4*>(p);
-#endif
-}
-__device__ __forceinline__ void lsb_st_state4(float* p, f32x4 v) {
-#if FE_LSB_NT
-    __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p));
-#else
-    *reinterpret_cast<f32x4*>(p) = v;
-#endif
-}
+// 16-byte accesses to the per-stream cache tensors
+__device__ __forceinline__ f32x4 lsb_ld_state4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+__device__ __forceinline__ void lsb_st_state4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 
 struct LSbArgs {
     const float* wp;          // the packed buffer of lisennet_frame_kernel; the stream-batched region starts at LPk::TOTAL

@@ -221,7 +221,7 @@ __device__ __forceinline__ void tok_panel(f32x4 (&acc)[MTT][NTPW], const float* 
         [&](int j, int ks) {
             int nt = wave + 4 * j;
             nt = nt < NT ? nt : NT - 1;
-            if constexpr (K4D != 0 && FE_K4_STREAM && KS >= 4) {
+            if constexpr (K4D != 0 && KS >= 4) {
                 const int base = w_off + K4D + nt * (KS * 64);
                 if (ks >= 4 * (KS / 4)) return wb.at_g(base + ks * 64);
                 if ((ks & 3) == 0) cur[j] = wb.at_gv4(base + (ks >> 2) * 256, wb.lane4 * 4);
@@ -1263,7 +1263,7 @@ __device__ __forceinline__ void blk_body(const TbArgs& a, float* smem, const int
                     [&](int j, int ks) {
                         int nt = wave + 4 * (j0 + j);
                         nt = nt < S::NT3 ? nt : S::NT3 - 1;
-                        if constexpr (FE_K4_STREAM && S::KS_2 >= 4 && o.k4_delta != 0) {       // (r4x: four k-steps per 16-byte load from the k4 copy)
+                        if constexpr (S::KS_2 >= 4 && o.k4_delta != 0) {       // (r4x: four k-steps per 16-byte load from the k4 copy)
                             const int base = o.blk_qkv[0] + kb + o.k4_delta + nt * (S::KS_2 * 64);
                             if (ks >= 4 * (S::KS_2 / 4)) return wb.at_g(base + ks * 64);
                             if ((ks & 3) == 0) qcur[j] = wb.at_gv4(base + (ks >> 2) * 256, wb.lane4 * 4);
