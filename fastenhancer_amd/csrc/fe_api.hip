@@ -790,8 +790,8 @@ int ensure_scratch(fe_handle* h, int) {
     return FE_OK;
 }
 
-fe::FrameArgs base_args(fe_handle* h, int B, int T) {
-    fe::FrameArgs a{};
+// the handle's part of a frame-kernel argument block (a: the fields the caller has set already)
+fe::StreamFrameArgs base_args(fe_handle* h, int B, int T, fe::StreamFrameArgs a = {}) {
     a.wp = h->packed_dev;
     a.B = B;
     a.T = T;
@@ -1139,36 +1139,38 @@ static int check_step_args(const fe_handle* h, const char* fn, const char* bad, 
 }
 static const char* const kBadSlotArgs = "bad argument (need non-null pointers, 1 <= n <= capacity, T >= 1)";
 
-// FastEnhancer's streaming step of n streams, however it was asked for.  slots == nullptr: fe_step and the debug / profile steps - the plain
-// instantiations and their FrameArgs, state of rows = n streams.  slots: the launch fe_step(B = n) makes with every state address taken
-// from (slots[b], rows = capacity); pinned: the HIO instantiations, whose wav_in / wav_out are device views of page-locked host memory.
-static int launch_fe_step(fe_handle* h, const float* wav_in, size_t in_stride, float* state, int rows, const int* slots, bool pinned,
-                          float* wav_out, size_t out_stride, int n, int T, float* dbg, unsigned long long* clk, void* stream) {
-    int rc = ensure_scratch(h, n);
-    if (rc != FE_OK) return rc;
-    fe::SlotFrameArgs a{};
-    static_cast<fe::FrameArgs&>(a) = base_args(h, n, T);
-    const StateLayout L = state_layout(h, rows);
+// What a streaming step of any family puts into its argument block for the call: streaming mode, audio pointers and strides, and the two STFT caches
+// at the head of a state of L's rows.  Returns where the model's own state starts (L.h).
+extern "C++" template <class Args>
+static float* stream_io(Args& a, const float* wav_in, size_t in_stride, float* wav_out, size_t out_stride, float* state, const StateLayout& L) {
     a.mode = fe::FE_MODE_STREAM;
     a.wav_in = wav_in; a.wav_out = wav_out; a.in_stride = in_stride; a.out_stride = out_stride;
-    a.cache_stft = state; a.cache_istft = state + L.cache_istft; a.h = state + L.h; a.tk = state + L.tk;
-    const fe::Impl* im = step_impl(h, n, T, dbg || clk);
-    hipError_t e = hipSuccess;
-    if (!slots) {
-        a.dbg = dbg;
-        a.clk = clk;
-        a.dbg_stride = h->impl->dbg_floats;
-        h->last_shape = im->name;
-        im->launch(a, h->max_wgs, (hipStream_t)stream, &e);       // (the FrameArgs part alone: the plain kernels' argument block)
-        return launch_rc(e);
+    a.cache_stft = state; a.cache_istft = state + L.cache_istft;
+    return state + L.h;
+}
+
+// FastEnhancer's streaming step of n streams, however it was asked for: the entry point sets the flavour's own fields in `own`, this fills in the
+// rest and launches.  own.capacity = the rows of the state (n for the plain flavour).  STEP_PLAIN (fe_step, the debug / profile steps): dbg, clk,
+// dbg_stride.  STEP_SLOTS / STEP_SLOTS_PINNED: slots - the launch fe_step(B = n) makes with every state address taken from (slots[b], capacity);
+// pinned: wav_in / wav_out are device views of page-locked host memory.  STEP_STREAMS: desc, in_count, out_count, format, pinned (no strides).
+static int launch_fe_step(fe_handle* h, const char* fn, fe::StepFlavour flavour, const fe::StreamFrameArgs& own, const float* wav_in, size_t in_stride,
+                          float* state, float* wav_out, size_t out_stride, int n, int T, void* stream) {
+    int rc = ensure_scratch(h, n);
+    if (rc != FE_OK) return rc;
+    fe::StreamFrameArgs a = base_args(h, n, T, own);
+    const StateLayout L = state_layout(h, own.capacity);
+    a.h = stream_io(a, wav_in, in_stride, wav_out, out_stride, state, L);
+    a.tk = state + L.tk;
+    const fe::Impl* im = step_impl(h, n, T, a.dbg || a.clk);
+    if (!im->launch_step) {      // (a noncausal record; every entry point refuses those models earlier.  The slotted wording names the entry point's family, not fn, as it always has)
+        const char* shape = im->name ? im->name : "?";
+        if (flavour == fe::STEP_PLAIN) return fail(FE_ERR_UNSUPPORTED_CONFIG, "%s", kNoncausalNoStep);
+        if (flavour == fe::STEP_STREAMS) return fail(FE_ERR_UNSUPPORTED_CONFIG, "%s: no packet-audio kernel is compiled for shape %s", fn, shape);
+        return fail(FE_ERR_UNSUPPORTED_CONFIG, "%s: no slotted kernel is compiled for shape %s", flavour == fe::STEP_SLOTS_PINNED ? "fe_step_slots_pinned" : "fe_step_slots", shape);
     }
-    a.capacity = rows;
-    a.slots = slots;
-    auto launch = pinned ? im->launch_slots_pinned : im->launch_slots;
-    if (!launch) return fail(FE_ERR_UNSUPPORTED_CONFIG, "%s: no slotted kernel is compiled for shape %s", pinned ? "fe_step_slots_pinned" : "fe_step_slots",
-                             im->name ? im->name : "?");
     h->last_shape = im->name;
-    launch(a, h->max_wgs, (hipStream_t)stream, &e);
+    hipError_t e = hipSuccess;
+    im->launch_step(a, flavour, h->max_wgs, (hipStream_t)stream, &e);
     return launch_rc(e);
 }
 
@@ -1184,15 +1186,15 @@ static int run_step(fe_handle* h, const float* wav_in, size_t in_stride, float* 
             a.clk = clk;
             a.dbg = dbg;
             a.dbg_stride = F.impl(h)->dbg_floats;
-            const StateLayout L = state_layout(h, B);
-            a.mode = fe::FE_MODE_STREAM;
-            a.wav_in = wav_in; a.wav_out = wav_out; a.in_stride = in_stride; a.out_stride = out_stride;
-            a.cache_stft = state; a.cache_istft = state + L.cache_istft; F.state(a) = state + L.h;
+            F.state(a) = stream_io(a, wav_in, in_stride, wav_out, out_stride, state, state_layout(h, B));
             rc = F.launch(h, a, stream);
         }))
         return rc;
     if (h->d.BD) return fail(FE_ERR_UNSUPPORTED_CONFIG, "%s", kNoncausalNoStep);
-    return launch_fe_step(h, wav_in, in_stride, state, B, nullptr, false, wav_out, out_stride, B, T, dbg, clk, stream);
+    fe::StreamFrameArgs own{};
+    own.dbg = dbg; own.clk = clk; own.dbg_stride = h->impl->dbg_floats;
+    own.capacity = B;
+    return launch_fe_step(h, "fe_step", fe::STEP_PLAIN, own, wav_in, in_stride, state, wav_out, out_stride, B, T, stream);
 }
 
 int fe_step(fe_handle* h, const float* wav_in_dev, size_t in_stride, float* state_dev, float* wav_out_dev, size_t out_stride,
@@ -1200,26 +1202,40 @@ int fe_step(fe_handle* h, const float* wav_in_dev, size_t in_stride, float* stat
     return run_step(h, wav_in_dev, in_stride, state_dev, wav_out_dev, out_stride, B, T, nullptr, nullptr, stream);
 }
 
-int fe_step_slots(fe_handle* h, const float* wav_in_dev, size_t in_stride, float* state_dev, int capacity, const int* slots_dev,
-                  float* wav_out_dev, size_t out_stride, int n, int T, void* stream) {
+// What every slotted entry point does before it enqueues anything: handle, family, the call's own arguments (check_args), the handle's readiness; go()
+// then runs inside the kernel log's scope.  args_first: the pinned and packet steps check their arguments before readiness and outside that scope,
+// fe_step_slots after it and inside (a refused call empties fe_last_step_kernel's answer) - which of two faults a call reports depends on this order:
+// deliberate API history, pinned by tests/test_c_abi_errors.py.
+extern "C++" template <class Check, class Go>
+static int slotted_step(fe_handle* h, const char* fn, bool args_first, Check&& check_args, Go&& go) {
     if (!h) return fail(FE_ERR_INVALID_ARG, "null handle");
-    int rc = check_slots_family(h, "fe_step_slots");
-    if (rc != FE_OK) return rc;
-    rc = check_ready(h);
+    int rc = check_slots_family(h, fn);
+    if (rc == FE_OK && args_first) rc = check_args();
+    if (rc == FE_OK) rc = check_ready(h);
     if (rc != FE_OK) return rc;
     KernelLogScope klog_(h);
-    rc = check_step_args(h, nullptr, kBadSlotArgs, wav_in_dev && state_dev && slots_dev && wav_out_dev, n, capacity, T, in_stride, out_stride);
-    if (rc != FE_OK) return rc;
-    return launch_fe_step(h, wav_in_dev, in_stride, state_dev, capacity, slots_dev, false, wav_out_dev, out_stride, n, T, nullptr, nullptr, stream);
+    if (!args_first) rc = check_args();
+    return rc != FE_OK ? rc : go();
+}
+
+int fe_step_slots(fe_handle* h, const float* wav_in_dev, size_t in_stride, float* state_dev, int capacity, const int* slots_dev,
+                  float* wav_out_dev, size_t out_stride, int n, int T, void* stream) {
+    return slotted_step(h, "fe_step_slots", false,
+        [&] { return check_step_args(h, nullptr, kBadSlotArgs, wav_in_dev && state_dev && slots_dev && wav_out_dev, n, capacity, T, in_stride, out_stride); },
+        [&] {
+            fe::StreamFrameArgs own{};
+            own.capacity = capacity; own.slots = slots_dev;
+            return launch_fe_step(h, "fe_step_slots", fe::STEP_SLOTS, own, wav_in_dev, in_stride, state_dev, wav_out_dev, out_stride, n, T, stream);
+        });
 }
 
 // fe_step_pinned / fe_step_slots_pinned: `count` floats from p must be page-locked host memory with a device mapping on the current device
 // (hipHostMalloc / hipHostRegister: torch's pin_memory()).  Anything else - pageable or device memory - would make the kernel take a page
 // fault, so it is refused here, before any launch.  Both ends of the range are looked up; *dev = the device view of p.
-// (E: float, or short for the int16 audio of fe_step_streams_pinned.)
+// (E: float, or short for the int16 audio of fe_step_streams_pinned, whose buffers are typed by the call's format - hence void pointers.)
 extern "C++" template <class E>
-static int pinned_view(const E* p, size_t count, const char* fn, const char* what, const E** dev) {
-    const E* ends[2] = {p, p + (count - 1)};
+static int pinned_view(const void* p, size_t count, const char* fn, const char* what, const void** dev) {
+    const E* ends[2] = {static_cast<const E*>(p), static_cast<const E*>(p) + (count - 1)};
     const char* dv[2] = {nullptr, nullptr};
     for (int i = 0; i < 2; ++i) {
         hipPointerAttribute_t at{};
@@ -1234,7 +1250,7 @@ static int pinned_view(const E* p, size_t count, const char* fn, const char* wha
     }
     if (dv[1] - dv[0] != reinterpret_cast<const char*>(ends[1]) - reinterpret_cast<const char*>(ends[0]))
         return fail(FE_ERR_INVALID_ARG, "%s: %s spans more than one pinned allocation: pin the buffer as one piece (pin_memory())", fn, what);
-    *dev = reinterpret_cast<const E*>(dv[0]);
+    *dev = dv[0];
     return FE_OK;
 }
 
@@ -1255,28 +1271,21 @@ static int ensure_ident_slots(fe_handle* h, int B) {
 // identity: fe_step_pinned (capacity = n, stream i = slot i of the handle's identity list)
 static int step_pinned(fe_handle* h, const char* fn, const float* wav_in_host, size_t in_stride, float* state_dev, int capacity, const int* slots_dev,
                        bool identity, float* wav_out_host, size_t out_stride, int n, int T, void* stream) {
-    if (!h) return fail(FE_ERR_INVALID_ARG, "null handle");
-    int rc = check_slots_family(h, fn);
-    if (rc != FE_OK) return rc;
-    rc = check_step_args(h, fn, kBadSlotArgs, wav_in_host && state_dev && wav_out_host && (identity || slots_dev), n, capacity, T, in_stride, out_stride);
-    if (rc != FE_OK) return rc;
-    const size_t row = (size_t)T * h->d.HOP;
-    rc = check_ready(h);
-    if (rc != FE_OK) return rc;
-    KernelLogScope klog_(h);
-    const float* in_dev = nullptr;
-    const float* out_dev = nullptr;
-    rc = pinned_view(wav_in_host, (size_t)(n - 1) * in_stride + row, fn, "wav_in", &in_dev);
-    if (rc != FE_OK) return rc;
-    rc = pinned_view(wav_out_host, (size_t)(n - 1) * out_stride + row, fn, "wav_out", &out_dev);
-    if (rc != FE_OK) return rc;
-    if (identity) {
-        rc = ensure_ident_slots(h, n);
-        if (rc != FE_OK) return rc;
-        slots_dev = h->ident_slots_dev;
-    }
-    return launch_fe_step(h, in_dev, n > 1 ? in_stride : row, state_dev, capacity, slots_dev, true, const_cast<float*>(out_dev), n > 1 ? out_stride : row,
-                          n, T, nullptr, nullptr, stream);
+    return slotted_step(h, fn, true,
+        [&] { return check_step_args(h, fn, kBadSlotArgs, wav_in_host && state_dev && wav_out_host && (identity || slots_dev), n, capacity, T, in_stride, out_stride); },
+        [&] {
+            const size_t row = (size_t)T * h->d.HOP;
+            const void* in = nullptr;
+            const void* out = nullptr;
+            int rc = pinned_view<float>(wav_in_host, (size_t)(n - 1) * in_stride + row, fn, "wav_in", &in);
+            if (rc == FE_OK) rc = pinned_view<float>(wav_out_host, (size_t)(n - 1) * out_stride + row, fn, "wav_out", &out);
+            if (rc == FE_OK && identity) rc = ensure_ident_slots(h, n);
+            if (rc != FE_OK) return rc;
+            fe::StreamFrameArgs own{};
+            own.capacity = capacity; own.slots = identity ? h->ident_slots_dev : slots_dev;
+            return launch_fe_step(h, fn, fe::STEP_SLOTS_PINNED, own, static_cast<const float*>(in), n > 1 ? in_stride : row, state_dev,
+                                  const_cast<float*>(static_cast<const float*>(out)), n > 1 ? out_stride : row, n, T, stream);
+        });
 }
 
 int fe_step_pinned(fe_handle* h, const float* wav_in_host, size_t in_stride, float* state_dev, float* wav_out_host, size_t out_stride,
@@ -1297,54 +1306,33 @@ static_assert(sizeof(fe_stream_desc) == 24 && sizeof(fe::StreamDesc) == 24 && of
               offsetof(fe_stream_desc, out_offset) == offsetof(fe::StreamDesc, out_offset), "fe_stream_desc is the kernels' StreamDesc");
 static int step_streams(fe_handle* h, const char* fn, bool pinned, const void* wav_in, size_t in_count, float* state_dev, int capacity,
                         const fe_stream_desc* desc_dev, void* wav_out, size_t out_count, int n, int T_max, int format, void* stream) {
-    if (!h) return fail(FE_ERR_INVALID_ARG, "null handle");
-    int rc = check_slots_family(h, fn);
-    if (rc != FE_OK) return rc;
-    if (!wav_in || !state_dev || !desc_dev || !wav_out || n <= 0 || T_max <= 0 || capacity < n || in_count == 0 || out_count == 0)
-        return fail(FE_ERR_INVALID_ARG, "%s: bad argument (need non-null pointers to at least one element, 1 <= n <= capacity, T_max >= 1)", fn);
-    if (format != FE_AUDIO_F32 && format != FE_AUDIO_S16)
-        return fail(FE_ERR_INVALID_ARG, "%s: format %d is neither FE_AUDIO_F32 (0) nor FE_AUDIO_S16 (1)", fn, format);
-    rc = check_ready(h);
-    if (rc != FE_OK) return rc;
-    KernelLogScope klog_(h);
-    if (pinned) {
-        // the whole of both buffers, [wav, wav + count) in elements of the format: what the kernel's own bounds check confines every access to
-        if (format == FE_AUDIO_S16) {
-            const short* in_dev = nullptr;
-            const short* out_dev = nullptr;
-            rc = pinned_view(static_cast<const short*>(wav_in), in_count, fn, "wav_in", &in_dev);
-            if (rc == FE_OK) rc = pinned_view(static_cast<const short*>(wav_out), out_count, fn, "wav_out", &out_dev);
-            wav_in = in_dev;
-            wav_out = const_cast<short*>(out_dev);
-        } else {
-            const float* in_dev = nullptr;
-            const float* out_dev = nullptr;
-            rc = pinned_view(static_cast<const float*>(wav_in), in_count, fn, "wav_in", &in_dev);
-            if (rc == FE_OK) rc = pinned_view(static_cast<const float*>(wav_out), out_count, fn, "wav_out", &out_dev);
-            wav_in = in_dev;
-            wav_out = const_cast<float*>(out_dev);
-        }
-        if (rc != FE_OK) return rc;
-    }
-    rc = ensure_scratch(h, n);
-    if (rc != FE_OK) return rc;
-    fe::StreamFrameArgs a{};
-    static_cast<fe::FrameArgs&>(a) = base_args(h, n, T_max);
-    const StateLayout L = state_layout(h, capacity);
-    a.mode = fe::FE_MODE_STREAM;
-    a.wav_in = static_cast<const float*>(wav_in); a.wav_out = static_cast<float*>(wav_out);       // (typed by a.format in the kernel)
-    a.cache_stft = state_dev; a.cache_istft = state_dev + L.cache_istft; a.h = state_dev + L.h; a.tk = state_dev + L.tk;
-    a.capacity = capacity;
-    a.desc = reinterpret_cast<const fe::StreamDesc*>(desc_dev);
-    a.in_count = in_count; a.out_count = out_count;
-    a.format = format;
-    a.pinned = pinned ? 1 : 0;
-    const fe::Impl* im = step_impl(h, n, T_max, false);
-    if (!im->launch_streams) return fail(FE_ERR_UNSUPPORTED_CONFIG, "%s: no packet-audio kernel is compiled for shape %s", fn, im->name ? im->name : "?");
-    h->last_shape = im->name;
-    hipError_t e = hipSuccess;
-    im->launch_streams(a, h->max_wgs, (hipStream_t)stream, &e);
-    return launch_rc(e);
+    return slotted_step(h, fn, true,
+        [&]() -> int {
+            if (!wav_in || !state_dev || !desc_dev || !wav_out || n <= 0 || T_max <= 0 || capacity < n || in_count == 0 || out_count == 0)
+                return fail(FE_ERR_INVALID_ARG, "%s: bad argument (need non-null pointers to at least one element, 1 <= n <= capacity, T_max >= 1)", fn);
+            if (format != FE_AUDIO_F32 && format != FE_AUDIO_S16)
+                return fail(FE_ERR_INVALID_ARG, "%s: format %d is neither FE_AUDIO_F32 (0) nor FE_AUDIO_S16 (1)", fn, format);
+            return FE_OK;
+        },
+        [&]() -> int {
+            // the whole of both buffers, [wav, wav + count) in elements of the format: what the kernel's own bounds check confines every access to
+            const void* in = wav_in;
+            const void* out = wav_out;
+            if (pinned) {
+                const auto view = format == FE_AUDIO_S16 ? &pinned_view<short> : &pinned_view<float>;
+                int rc = view(wav_in, in_count, fn, "wav_in", &in);
+                if (rc == FE_OK) rc = view(wav_out, out_count, fn, "wav_out", &out);
+                if (rc != FE_OK) return rc;
+            }
+            fe::StreamFrameArgs own{};
+            own.capacity = capacity;
+            own.desc = reinterpret_cast<const fe::StreamDesc*>(desc_dev);
+            own.in_count = in_count; own.out_count = out_count;
+            own.format = format;
+            own.pinned = pinned ? 1 : 0;
+            return launch_fe_step(h, fn, fe::STEP_STREAMS, own, static_cast<const float*>(in), 0, state_dev, const_cast<float*>(static_cast<const float*>(out)), 0,
+                                  n, T_max, stream);       // (the audio is typed by a.format in the kernel)
+        });
 }
 
 int fe_step_streams(fe_handle* h, const void* wav_in_dev, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,
@@ -1543,7 +1531,7 @@ int fe_spec_step(fe_handle* h, const float* spec_in_dev, float* h_dev, float* sp
     }
     rc = ensure_scratch(h, B);
     if (rc != FE_OK) return rc;
-    fe::FrameArgs a = base_args(h, B, T);
+    fe::StreamFrameArgs a = base_args(h, B, T);
     a.spec_in = spec_in_dev;
     a.spec_out = spec_out_dev;
     a.h = h_dev;
@@ -1589,13 +1577,13 @@ int fe_spec_step(fe_handle* h, const float* spec_in_dev, float* h_dev, float* sp
             a.tk = h_dev + (size_t)B * d.hstate();
             a.tatt_base = 0;
             a.tk_base = 0;
-            h->impl->launch(a, h->max_wgs, st, &e);
+            h->impl->launch_step(a, fe::STEP_PLAIN, h->max_wgs, st, &e);
         } else if (rings) {
             hipLaunchKernelGGL(ring_out_kernel, dim3(cgrid), dim3(256), 0, st, h->spec_ring_dev, caches, heads, nfl, B, SZ, L, RS, T);
             e = hipGetLastError();
         }
     } else
-    h->impl->launch(a, h->max_wgs, (hipStream_t)stream, &e);
+    h->impl->launch_step(a, fe::STEP_PLAIN, h->max_wgs, (hipStream_t)stream, &e);
     return launch_rc(e);
 }
 
@@ -1874,7 +1862,7 @@ int fe_offline(fe_handle* h, const float* noisy_dev, int B, int Tw, float* wav_h
     }
     rc = ensure_scratch(h, B);
     if (rc != FE_OK) return rc;
-    fe::FrameArgs a = base_args(h, B, T);
+    fe::StreamFrameArgs a = base_args(h, B, T);
     a.mode = fe::FE_MODE_OFFLINE;
     a.Tw = Tw;
     a.wav_in = noisy_dev;
@@ -1907,12 +1895,12 @@ int fe_offline(fe_handle* h, const float* noisy_dev, int B, int Tw, float* wav_h
             a.frames = nullptr;
             a.tk = tk_serial;
             a.h = h_serial;
-            h->impl->launch(a, h->max_wgs, st, &e);
+            h->impl->launch_step(a, fe::STEP_PLAIN, h->max_wgs, st, &e);
             return launch_rc(e);
         }
         return ola(h, a.frames, wav_hat_dev, (size_t)d.HOP * (T - 1), B, T, st);
     }
-    h->impl->launch(a, h->max_wgs, st, &e);
+    h->impl->launch_step(a, fe::STEP_PLAIN, h->max_wgs, st, &e);
     return launch_rc(e);
 }
 
