@@ -733,6 +733,14 @@ int ensure_sb_scratch(fe_handle* h, int B, int min_streams, size_t bytes) {
     return FE_OK;
 }
 
+// One tensor of a streaming state sized for `capacity` streams: [rows][capacity][len] floats, stream-major, `off` floats from the start of
+// the state (state_regions lists them; the families' own parts are their traits' regions()).
+struct StateRegion {
+    size_t off;
+    int rows, len;
+};
+constexpr int kMaxStateRegions = 12;      // (LiSenNet: the two STFT caches + nine model caches)
+
 // the baseline families' host sides (weight sections, handle creation, packers, launches, the traits the paths below take): one file each
 #include "fe_api_bsrnn.inc"
 #include "fe_api_fspen.inc"
@@ -1345,12 +1353,31 @@ int fe_step_streams_pinned(fe_handle* h, const void* wav_in_host, size_t in_coun
     return step_streams(h, "fe_step_streams_pinned", true, wav_in_host, in_count, state_dev, capacity, desc_dev, wav_out_host, out_count, n, T_max, format, stream);
 }
 
-// fe_state_reset_slots: what fe_state_init writes (zeros) for the named slots.  The state is a list of regions [rows][capacity][len]
-// (stream-major over the capacity); one workgroup per named slot zeroes its len floats in every row of every region.
-struct ResetRegion {
-    size_t off;          // floats from the start of the state
-    int rows, len;
-};
+// The streaming state of `capacity` streams as a list of regions [rows][capacity][len], in the order of the layout (include/fastenhancer_hip.h):
+// every family's state is such a list, so a stream's share of it - `len` floats in every row of every region - is what fe_state_reset_slots
+// zeroes and what the state records of fe_state_export_slots / fe_state_import_slots hold.  Returns the number of regions.
+static int state_regions(const fe_handle* h, size_t capacity, StateRegion* r) {
+    const Dims& d = h->d;
+    const StateLayout L = state_layout(h, capacity);
+    const int ovl = d.NFFT - d.HOP;
+    int nr = 0;
+    r[nr++] = {0, 1, ovl};                                              // cache_stft [cap][N-H]
+    r[nr++] = {L.cache_istft, 1, ovl};                                  // cache_istft [cap][N-H]
+    if (visit_baseline(h->cfg.arch, [&](auto F) { nr += F.regions(h, capacity, L.h, r + nr); })) return nr;
+    if (d.TA) {
+        const int ring = d.F2 * d.C2 * d.TA;                              // K and V rings per block: [2 KB][cap][F2 * C2 * L], then the heads [cap]
+        r[nr++] = {L.h, 2 * d.KB, ring};
+        r[nr++] = {L.h + capacity * (size_t)(2 * d.KB) * ring, 1, 1};
+    } else {
+        r[nr++] = {L.h, d.KB, d.F2 * d.C2};                             // GRU states [KB][cap][F2 * C2]
+    }
+    if (d.KT > 1) r[nr++] = {L.tk, 2 * d.NL, (int)(tk_floats(h) / (2 * d.NL))};   // conv caches [2 NL][cap][KT-1][F1][C1]
+    return nr;
+}
+
+// fe_state_reset_slots: what fe_state_init writes (zeros) for the named slots: one workgroup per named slot zeroes its len floats in every
+// row of every region.
+using ResetRegion = StateRegion;
 struct ResetArgs {
     float* state;
     const int* slots;
@@ -1375,28 +1402,152 @@ int fe_state_reset_slots(fe_handle* h, float* state_dev, int capacity, const int
     int rc = check_slots_family(h, "fe_state_reset_slots");
     if (rc != FE_OK) return rc;
     if (!state_dev || !slots_dev || n <= 0 || capacity < n) return fail(FE_ERR_INVALID_ARG, "bad argument (need non-null pointers, 1 <= n <= capacity)");
-    const Dims& d = h->d;
-    const StateLayout L = state_layout(h, capacity);
-    const size_t cap = (size_t)capacity;
-    const int ovl = d.NFFT - d.HOP;
     ResetArgs a{};
     a.state = state_dev;
     a.slots = slots_dev;
     a.capacity = capacity;
-    int nr = 0;
-    a.r[nr++] = {0, 1, ovl};                                              // cache_stft [cap][N-H]
-    a.r[nr++] = {L.cache_istft, 1, ovl};                                  // cache_istft [cap][N-H]
-    if (d.TA) {
-        const int ring = d.F2 * d.C2 * d.TA;                              // K and V rings per block: [2 KB][cap][F2 * C2 * L], then the heads [cap]
-        a.r[nr++] = {L.h, 2 * d.KB, ring};
-        a.r[nr++] = {L.h + cap * (size_t)(2 * d.KB) * ring, 1, 1};
-    } else {
-        a.r[nr++] = {L.h, d.KB, d.F2 * d.C2};                           // GRU states [KB][cap][F2 * C2]
-    }
-    if (d.KT > 1) a.r[nr++] = {L.tk, 2 * d.NL, (int)(tk_floats(h) / (2 * d.NL))};   // conv caches [2 NL][cap][KT-1][F1][C1]
-    a.n_regions = nr;
+    StateRegion r[kMaxStateRegions];
+    a.n_regions = state_regions(h, (size_t)capacity, r);          // (the FastEnhancer family: at most five)
+    std::copy(r, r + a.n_regions, a.r);
     hipLaunchKernelGGL(state_reset_slots_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, a);
     return launch_rc(hipGetLastError());
+}
+
+// fe_state_export_slots / fe_state_import_slots: a stream's state record is the state of a capacity-1 batch, so the record side of a region
+// is the same list at capacity 1 - the regions back to back, [rows][len] each - and moving a stream is a copy of its `len` floats of every row
+// between the two lists.  One launch: grid (stream of the call, chunk of the record), so the workgroups follow the bytes, not the streams.
+// A thread moves one 16-byte granule of the RECORD side at a time (consecutive lanes: consecutive granules, so both sides are read and written
+// in runs of whole cache lines wherever a row is long enough); the granule grid is laid on the record's address, not its index, so that side is
+// always aligned.  A granule that lies in one row and whose state address is 16-byte aligned too goes as one 16-byte load and store; any other
+// one - row ends, the one-float `head`, regions whose two sides differ in alignment, the ragged ends of a record - float by float.
+struct RecordRegion {
+    size_t off;          // floats from the start of the state (at the call's capacity)
+    int rec;             // floats from the start of a record (the same region at capacity 1)
+    int rows, len;
+};
+struct RecordArgs {
+    float* state;
+    float* records;
+    const int* slots;
+    int capacity, n_regions;
+    int rec_floats;      // floats per record
+    int granules;        // granules per workgroup
+    int to_state;        // 0: export (state -> records), 1: import
+    RecordRegion r[kMaxStateRegions];
+};
+constexpr int kRecordGranules = 1024;      // 16 KB of a record per workgroup, four granules per thread
+
+// where float e of a stream's record lives in the state (slot s): nullptr if e is outside the record
+__device__ inline float* record_state_addr(const RecordArgs& a, int s, int e, int* left_in_row) {
+    for (int j = 0; j < a.n_regions; ++j) {
+        const RecordRegion g = a.r[j];
+        const int k = e - g.rec;
+        if (k < 0 || k >= g.rows * g.len) continue;
+        const int row = k / g.len, i = k - row * g.len;
+        *left_in_row = g.len - i;
+        return a.state + g.off + ((size_t)row * a.capacity + s) * g.len + i;
+    }
+    return nullptr;
+}
+
+__global__ void __launch_bounds__(256) state_records_kernel(RecordArgs a) {
+    const int s = a.slots[blockIdx.x];
+    const bool live = s >= 0 && s < a.capacity;
+    if (a.to_state && !live) return;                       // import of a slot out of range: nothing is written anywhere
+    float* const rec = a.records + (size_t)blockIdx.x * a.rec_floats;
+    const int shift = (int)((reinterpret_cast<size_t>(rec) >> 2) & 3);      // floats from the 16-byte boundary below rec
+    const int g0 = (int)blockIdx.y * a.granules;
+    for (int g = g0 + (int)threadIdx.x; g < g0 + a.granules; g += (int)blockDim.x) {
+        const int e0 = 4 * g - shift;
+        const int lo = e0 < 0 ? 0 : e0, hi = e0 + 4 < a.rec_floats ? e0 + 4 : a.rec_floats;
+        if (lo >= hi) continue;
+        const bool whole = hi - lo == 4;
+        if (!live) {                                       // export of a slot out of range: the record of a fresh fe_state_init
+            if (whole) *reinterpret_cast<float4*>(rec + lo) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            else for (int e = lo; e < hi; ++e) rec[e] = 0.0f;
+            continue;
+        }
+        int left = 0;
+        float* st = record_state_addr(a, s, lo, &left);
+        if (whole && st && left >= 4 && (reinterpret_cast<size_t>(st) & 15) == 0) {
+            if (a.to_state) *reinterpret_cast<float4*>(st) = *reinterpret_cast<const float4*>(rec + lo);
+            else *reinterpret_cast<float4*>(rec + lo) = *reinterpret_cast<const float4*>(st);
+            continue;
+        }
+        for (int e = lo; e < hi; ++e) {
+            if (left <= 0) st = record_state_addr(a, s, e, &left);
+            if (!st) break;
+            if (a.to_state) *st = rec[e]; else rec[e] = *st;
+            ++st; --left;
+        }
+    }
+}
+
+// `count` floats from p as the kernel may address them: device memory of the current device as it is, or the device view of page-locked host
+// memory mapped for it (pinned_view).  Both ends of the range are looked up; pageable memory, or memory of another device, is refused.
+static int records_view(const float* p, size_t count, const char* fn, const float** dev) {
+    int cur = -1;
+    FE_HIP_CHECK(hipGetDevice(&cur));
+    const float* ends[2] = {p, p + (count - 1)};
+    bool device = true;
+    for (int i = 0; i < 2 && device; ++i) {
+        hipPointerAttribute_t at{};
+        device = hipPointerGetAttributes(&at, ends[i]) == hipSuccess && at.type == hipMemoryTypeDevice && at.device == cur;
+        (void)hipGetLastError();
+    }
+    if (device) { *dev = p; return FE_OK; }
+    const void* v = nullptr;
+    const int rc = pinned_view<float>(p, count, fn, "records", &v);
+    if (rc != FE_OK)
+        return fail(FE_ERR_INVALID_ARG, "%s: records is neither memory of the current device nor page-locked host memory mapped for it, from its first to its "
+                    "last float: pin a host buffer as one piece (torch: pin_memory(); C: hipHostMalloc / hipHostRegister)", fn);
+    *dev = static_cast<const float*>(v);
+    return FE_OK;
+}
+
+static int state_records(fe_handle* h, const char* fn, bool to_state, float* state_dev, int capacity, const int* slots_dev, float* records, int n, void* stream) {
+    if (!h) return fail(FE_ERR_INVALID_ARG, "null handle");
+    if (h->cfg.arch == FE_ARCH_FASTENHANCER && h->d.BD) return fail(FE_ERR_UNSUPPORTED_CONFIG, "%s", kNoncausalNoStep);
+    if (!state_dev || !slots_dev || !records || n <= 0 || capacity < n)
+        return fail(FE_ERR_INVALID_ARG, "%s: bad argument (need non-null pointers, 1 <= n <= capacity)", fn);
+    RecordArgs a{};
+    StateRegion at_cap[kMaxStateRegions], at_one[kMaxStateRegions];
+    a.n_regions = state_regions(h, (size_t)capacity, at_cap);
+    state_regions(h, 1, at_one);
+    const size_t rec = fe_state_floats(h, 1);
+    size_t covered = 0;
+    for (int j = 0; j < a.n_regions; ++j) {
+        if (at_one[j].off != covered) break;               // (the regions of one stream lie back to back: that is what makes them a record)
+        a.r[j] = {at_cap[j].off, (int)at_one[j].off, at_cap[j].rows, at_cap[j].len};
+        covered += (size_t)at_one[j].rows * at_one[j].len;
+    }
+    if (covered != rec || rec >= (size_t)1 << 30) return fail(FE_ERR_UNSUPPORTED_CONFIG, "%s: the state's regions do not add up to fe_state_floats(h, 1)", fn);
+    const float* view = nullptr;
+    const int rc = records_view(records, (size_t)n * rec, fn, &view);
+    if (rc != FE_OK) return rc;
+    a.state = state_dev;
+    a.records = const_cast<float*>(view);
+    a.slots = slots_dev;
+    a.capacity = capacity;
+    a.rec_floats = (int)rec;
+    a.to_state = to_state ? 1 : 0;
+    // (+ 1: a record that does not start on a 16-byte boundary touches one granule more)
+    const size_t granules = (rec + 3) / 4 + 1;
+    // few streams: smaller chunks, so that a handful of large records still spreads over the device (at least one round of 256 threads each)
+    a.granules = kRecordGranules;
+    while (a.granules > 256 && (size_t)n * ((granules + a.granules - 1) / a.granules) < (size_t)2 * h->max_wgs) a.granules /= 2;
+    while ((granules + a.granules - 1) / a.granules > 65535) a.granules *= 2;          // (the grid's second dimension)
+    const size_t chunks = (granules + a.granules - 1) / a.granules;
+    return launch_rc(fe::launch<state_records_kernel>(to_state ? "state_records_kernel<import>" : "state_records_kernel<export>",
+                                                      dim3((unsigned)n, (unsigned)chunks), dim3(256), 0, (hipStream_t)stream, a));
+}
+
+int fe_state_export_slots(fe_handle* h, const float* state_dev, int capacity, const int* slots_dev, float* records, int n, void* stream) {
+    return state_records(h, "fe_state_export_slots", false, const_cast<float*>(state_dev), capacity, slots_dev, records, n, stream);
+}
+
+int fe_state_import_slots(fe_handle* h, float* state_dev, int capacity, const int* slots_dev, const float* records, int n, void* stream) {
+    return state_records(h, "fe_state_import_slots", true, state_dev, capacity, slots_dev, const_cast<float*>(records), n, stream);
 }
 
 int fe_step_host(fe_handle* h, const float* wav_in_host, size_t in_stride, float* state_dev, float* wav_out_host, size_t out_stride,

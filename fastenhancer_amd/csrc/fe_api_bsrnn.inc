@@ -9,6 +9,11 @@ struct BsrnnFamily {
     static const char* shape_name(const fe_handle* h) { return h->bimpl->name; }
     static float*& state(Args& a) { return a.lstm; }
     static size_t state_floats(const fe_handle* h, int B) { return (size_t)2 * h->cfg.rf_blocks * B * 31 * 2 * h->cfg.channels; }
+    // the model's state of `cap` streams as regions from float `off` on (state_regions): h0, c0, h1, c1, ... [2 L][cap][31 * 2C]
+    static int regions(const fe_handle* h, size_t, size_t off, StateRegion* r) {
+        r[0] = {off, 2 * h->cfg.rf_blocks, 31 * 2 * h->cfg.channels};
+        return 1;
+    }
     static size_t counters(const fe_handle* h) { return h->cfg.rf_blocks; }      // time-pipeline frame counters per stream
     // default frames in flight per utterance of a time-pipelined offline launch: a hand-off chain (wait, fetch, gate GEMM, publish) is ~1/40
     // of a frame, so every co-resident workgroup the batch leaves free is worth having

@@ -11,6 +11,12 @@ struct FspenFamily {
     static const char* shape_name(const fe_handle*) { return "fspen"; }
     static float*& state(Args& a) { return a.gru; }
     static size_t state_floats(const fe_handle*, int B) { return (size_t)B * fe::FShape<256>::CACHE_FLOATS; }
+    // the model's state of `cap` streams as regions from float `off` on (state_regions): the inter-GRU states [NB * G][cap][F / G][C]
+    static int regions(const fe_handle*, size_t, size_t off, StateRegion* r) {
+        using S = fe::FShape<256>;
+        r[0] = {off, S::NCACHE, S::FG * S::C};
+        return 1;
+    }
     static size_t counters(const fe_handle* h) { return h->fimpl->num_blocks; }      // time-pipeline frame counters per stream
     static constexpr int kPipeFrames = 32;
     static size_t ring_floats(const fe_handle*) { return 0; }

@@ -8,6 +8,17 @@ struct LisennetFamily {
     static const char* shape_name(const fe_handle*) { return "lisennet"; }
     static float*& state(Args& a) { return a.cache; }
     static size_t state_floats(const fe_handle* h, int B) { return (size_t)B * h->limpl->cache_floats; }
+    // the model's state of `cap` streams as regions from float `off` on (state_regions): the nine caches in the order of the reference's
+    // list, each [cap][its floats per stream]
+    static int regions(const fe_handle*, size_t cap, size_t off, StateRegion* r) {
+        using S = fe::LShape<256>;
+        int n = 0;
+        auto add = [&](int len) { r[n++] = {off, 1, len}; off += cap * (size_t)len; };
+        add(S::K_PHA); add(S::K_E2); add(S::K_E3); add(S::K_E4);
+        for (int b = 0; b < S::NB; ++b) { add(S::K_H); add(S::K_GLU); }
+        add(S::K_DEC);
+        return n;
+    }
     static size_t counters(const fe_handle* h) { return h->limpl->nsite; }      // time-pipeline frame counters per stream
     static constexpr int kPipeFrames = 32;
     // the time pipeline's ring of the caches of the frames in flight (LArgs::ring), sized for the widest pipeline: 64 + 2 slots per stream

@@ -309,6 +309,58 @@ class Engine:
                        "fe_state_reset_slots")
         self._slots_keep = sl
 
+    # ---- state records: a stream's state as a capacity-1 state buffer (fe_state_export_slots / fe_state_import_slots)
+    @property
+    def record_floats(self) -> int:
+        """floats of one stream's state record: state_floats(1)"""
+        return self.state_floats(1)
+
+    def _records(self, records: Tensor, n: int) -> Tensor:
+        """records -> float32 [n, record_floats], rows back to back, on this engine's device or in page-locked host memory (any 4-byte
+        alignment: a view into a larger buffer is fine).  Anything else is a ValueError before any native call."""
+        rf = self.record_floats
+        if not isinstance(records, Tensor) or records.dtype != torch.float32 or tuple(records.shape) != (n, rf):
+            raise ValueError(f"records must be a float32 tensor [{n}, {rf}], got {getattr(records, 'dtype', type(records).__name__)} "
+                             f"{tuple(getattr(records, 'shape', ()))}")
+        if records.stride(1) != 1 or (n > 1 and records.stride(0) != rf):
+            raise ValueError("records must lie back to back (row stride = record_floats, unit stride inside a record)")
+        if records.is_cuda:
+            if records.device != self.device:
+                raise ValueError(f"records are on {records.device}, the engine on {self.device}: carry them through page-locked host memory")
+        elif not records.is_pinned():
+            raise ValueError("host records must be in page-locked memory: pin the buffer (pin_memory())")
+        return records
+
+    def _move_records(self, name: str, state: Tensor, capacity: int, slots, records: Optional[Tensor]) -> Tensor:
+        if records is not None:       # (before the slots: a list of them is copied to the device by its check)
+            records = self._records(records, slots.numel() if isinstance(slots, Tensor) else len(slots))
+        sl = self._slot_tensor(slots, capacity)
+        n = sl.numel()
+        self._require_gpu()
+        assert state.is_cuda and state.numel() == self.state_floats(capacity) and state.is_contiguous()
+        if records is None:
+            records = torch.empty(n, self.record_floats, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(getattr(self.lib, name)(self._h, _ptr(state), int(capacity), _ptr(sl), _ptr(records), n, _stream(self.device)), name)
+        self._slots_keep = sl            # (alive until the next call - the launch is asynchronous)
+        if not records.is_cuda:
+            self._pinned_keep = (records,)
+        return records
+
+    def export_slots(self, state: Tensor, capacity: int, slots, out: Optional[Tensor] = None) -> Tensor:
+        """fe_state_export_slots: the state records [n, record_floats] of the named slots of `state` (sized for `capacity` streams), which is
+        not written.  out: a CUDA tensor of this device or a page-locked CPU tensor (a new CUDA tensor when None).  slots as for step_slots;
+        a slot out of range (device slot tensors only) yields a fresh stream's record.  Asynchronous on the current stream: synchronise it
+        before reading host records."""
+        return self._move_records("fe_state_export_slots", state, capacity, slots, out)
+
+    def import_slots(self, state: Tensor, capacity: int, slots, records: Tensor) -> None:
+        """fe_state_import_slots: slot slots[i] of `state` becomes records[i] (device or page-locked host memory); no other float of the
+        state is written.  Asynchronous on the current stream: host records must stay as they are until it has completed."""
+        if records is None:
+            raise ValueError("records must be a float32 tensor")
+        self._move_records("fe_state_import_slots", state, capacity, slots, records)
+
     def _pinned_audio(self, name: str, x: Optional[Tensor], rows: int, T: int) -> Tensor:
         """x -> a page-locked CPU float32 tensor [rows, T*H] (row stride free), or a fresh one when x is None.  Anything else is a
         ValueError before any native call: the kernel reads and writes this memory over PCIe, and unpinned memory would fault it."""

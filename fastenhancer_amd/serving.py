@@ -7,7 +7,11 @@ ready on each tick.
 
 PacketPool: a StreamPool for PACKET audio - int16 PCM that arrives in pieces of any length (10 or 20 ms packets against a hop of 256
 samples, with network jitter).  push() copies a packet into the stream's page-locked ring, tick() is ONE fe_step_streams_pinned launch in
-which every stream advances by the whole hops it has, pull() returns the enhanced PCM.  The kernel reads and writes the rings themselves."""
+which every stream advances by the whole hops it has, pull() returns the enhanced PCM.  The kernel reads and writes the rings themselves.
+
+Moving a stream: export() gathers the state records of open slots (fe_state_export_slots: a record is the stream's state as a capacity-1
+state buffer), adopt() opens slots for records made elsewhere, move() takes a live stream to another pool - of another engine of the same
+config, on another GPU if need be - and resize() grows or shrinks a pool in place.  PacketPool carries the stream's rings along."""
 from __future__ import annotations
 
 from typing import List, Optional, Sequence, Tuple
@@ -62,6 +66,95 @@ class StreamPool:
                 raise ValueError(f"slot {s} is not open")
         return self.engine.step_slots_pinned(wav_in, self.state, self.capacity, list(slots), wav_out=wav_out, T=T)
 
+    # ---- moving live streams (fe_state_export_slots / fe_state_import_slots)
+    def export(self, slots: Sequence[int], pinned: bool = False) -> Tensor:
+        """The state records [n, record_floats] of the named open slots, on the engine's device or (pinned) in page-locked host memory - then
+        synchronise the engine before reading them.  The slots stay open: close() drops them."""
+        slots = list(slots)
+        for s in slots:
+            if s not in self._open:
+                raise ValueError(f"slot {s} is not open")
+        out = self.engine.new_pinned(len(slots), self.engine.record_floats) if pinned else None
+        return self.engine.export_slots(self.state, self.capacity, slots, out=out)
+
+    def adopt(self, records: Tensor) -> List[int]:
+        """Opens one free slot per record [n, record_floats] and imports the record into it (no reset first); the slots in record order.
+        Raises when there are not enough free slots, and opens none then."""
+        n = int(records.shape[0])
+        if n > len(self._free):
+            raise RuntimeError(f"{n} records for {len(self._free)} free slots of {self.capacity}")
+        if n == 0:
+            return []
+        slots = self._free[-n:][::-1]                     # (what n pops would hand out; taken off the list once the import is enqueued)
+        self.engine.import_slots(self.state, self.capacity, slots, records)
+        del self._free[-n:]
+        self._open.update(slots)
+        return slots
+
+    def _check_move(self, slot: int, dst_pool: "StreamPool") -> None:
+        """what move() refuses before anything is copied"""
+        if slot not in self._open:
+            raise ValueError(f"slot {slot} is not open")
+        a, b = getattr(self.engine, "cfg", None), getattr(dst_pool.engine, "cfg", None)
+        if type(a) is not type(b) or a != b:
+            raise ValueError("the pools' engines have different configs: a state record is valid for one config only")
+        if not dst_pool._free:
+            raise RuntimeError(f"all {dst_pool.capacity} slots of the destination are open")
+
+    def move(self, slot: int, dst_pool: "StreamPool") -> int:
+        """Takes the live stream in `slot` to dst_pool (export, adopt there, close here) and returns its slot there.  The pools may belong
+        to different engines of the same config, on different devices: the record then travels through page-locked host memory (export to
+        it, synchronise, import from it on the other device), which needs no peer access."""
+        self._check_move(slot, dst_pool)
+        same = getattr(self.engine, "device", None) == getattr(dst_pool.engine, "device", None)
+        rec = self.export([slot], pinned=not same)
+        if not same:
+            self.engine.synchronize()
+        new = dst_pool.adopt(rec)[0]
+        if not same:
+            dst_pool.engine.synchronize()                 # (the host record is released when this returns)
+        self.close(slot)
+        return new
+
+    def resize(self, capacity: int) -> None:
+        """Grows or shrinks the pool to `capacity` slots: a new state buffer (engine.new_state), every open stream exported and imported at
+        the SAME slot number, the free list rebuilt.  Shrinking below 1 + the highest open slot raises and changes nothing.  The old state
+        tensor is not reused: a caller that holds pool.state must read it again."""
+        capacity = int(capacity)
+        if capacity < 1:
+            raise ValueError("capacity must be at least 1")
+        if self._open and capacity < 1 + max(self._open):
+            raise ValueError(f"slot {max(self._open)} is open: the pool cannot shrink below {1 + max(self._open)} slots")
+        if capacity == self.capacity:
+            return
+        state = self.engine.new_state(capacity)
+        if self._open:
+            slots = sorted(self._open)
+            self.engine.import_slots(state, capacity, slots, self.engine.export_slots(self.state, self.capacity, slots))
+        self.state = state
+        self.capacity = capacity
+        self._free = [s for s in range(capacity - 1, -1, -1) if s not in self._open]
+
+
+def carry_ring(src_in: Tensor, src_out: Tensor, pushed: int, stepped: int, pulled: int, dst_in: Tensor, dst_out: Tensor) -> Tuple[int, int, int]:
+    """What a packet stream has in flight, from one slot's rings (1-D, src_in / src_out) to another's (dst_in / dst_out, of any other
+    length): input samples stepped <= k < pushed (pushed, not yet stepped) and output samples pulled <= k < stepped (stepped, not yet
+    pulled).  The stream's sample k sits at position k mod ring on both sides, so the sample numbering - the three counters, which are
+    returned - carries over as it is and the next push / tick / pull find everything in place.  OverflowError, before anything is copied,
+    if pushed - pulled exceeds the destination ring."""
+    rs, rd = src_in.numel(), dst_in.numel()
+    if src_out.numel() != rs or dst_out.numel() != rd:
+        raise ValueError("the input and output ring of a slot have one length")
+    if not 0 <= pulled <= stepped <= pushed or pushed - pulled > rs:
+        raise ValueError(f"counters pulled {pulled} <= stepped {stepped} <= pushed {pushed} do not describe a ring of {rs} samples")
+    if pushed - pulled > rd:
+        raise OverflowError(f"{pushed - pulled} samples in flight do not fit the destination ring of {rd} samples")
+    k = torch.arange(stepped, pushed, dtype=torch.int64)
+    dst_in[k % rd] = src_in[k % rs]
+    k = torch.arange(pulled, stepped, dtype=torch.int64)
+    dst_out[k % rd] = src_out[k % rs]
+    return pushed, stepped, pulled
+
 
 class PacketPool(StreamPool):
     """Streams fed by int16 PCM packets of any length.  Every slot has an input and an output ring of ring_hops * H samples in page-locked
@@ -86,6 +179,47 @@ class PacketPool(StreamPool):
         slot = super().open()
         self._pushed[slot] = self._stepped[slot] = self._pulled[slot] = 0
         return slot
+
+    def adopt(self, records: Tensor) -> List[int]:
+        """StreamPool.adopt; the adopted streams start with empty rings (move() carries a stream's rings along)."""
+        slots = super().adopt(records)
+        for slot in slots:
+            self._pushed[slot] = self._stepped[slot] = self._pulled[slot] = 0
+        return slots
+
+    def move(self, slot: int, dst_pool: "PacketPool") -> int:
+        """StreamPool.move with the packet side: what the stream has in flight - samples pushed but not yet stepped, samples stepped but
+        not yet pulled - and its three counters go to dst_pool's rings (carry_ring), which may have another ring_hops.  OverflowError,
+        before anything is copied, if that does not fit the destination ring.  The stream's next push / tick / pull on dst_pool behave as
+        if it had always lived there."""
+        if not isinstance(dst_pool, PacketPool):
+            raise TypeError("a packet stream moves to a PacketPool")
+        self._check_move(slot, dst_pool)
+        counters = (self._pushed[slot], self._stepped[slot], self._pulled[slot])
+        if counters[0] - counters[2] > dst_pool.ring:
+            raise OverflowError(f"slot {slot}: {counters[0] - counters[2]} samples in flight do not fit the destination ring of {dst_pool.ring} samples")
+        src_in, src_out = self.ring_in[slot].clone(), self.ring_out[slot].clone()      # (close() may hand the slot out again)
+        new = super().move(slot, dst_pool)
+        p = carry_ring(src_in, src_out, *counters, dst_pool.ring_in[new], dst_pool.ring_out[new])
+        dst_pool._pushed[new], dst_pool._stepped[new], dst_pool._pulled[new] = p
+        return new
+
+    def resize(self, capacity: int) -> None:
+        """StreamPool.resize with the packet side: new rings of the same ring_hops, the open slots' rows and counters at the same slot
+        numbers.  pool.ring_in / pool.ring_out are new tensors, like pool.state."""
+        old = self.capacity
+        super().resize(capacity)
+        if self.capacity == old:
+            return
+        keep = min(old, self.capacity)
+        rings = []
+        for ring in (self.ring_in, self.ring_out):
+            new = self.engine.new_pinned(self.capacity, self.ring, dtype=torch.int16)
+            new[:keep] = ring[:keep]
+            rings.append(new)
+        self.ring_in, self.ring_out = rings
+        grow = [0] * (self.capacity - keep)
+        self._pushed, self._stepped, self._pulled = (c[:keep] + grow for c in (self._pushed, self._stepped, self._pulled))
 
     def _check_open(self, slot: int) -> None:
         if slot not in self._open:

@@ -178,6 +178,31 @@ int fe_step_slots(fe_handle* h, const float* wav_in_dev, size_t in_stride, float
  * fe_step_slots; out-of-range slots are skipped. */
 int fe_state_reset_slots(fe_handle* h, float* state_dev, int capacity, const int* slots_dev, int n, void* stream);
 
+/* Moving live streams between state buffers.  The STATE RECORD of a stream is fe_state_floats(h, 1) floats: exactly the state buffer of a
+ * capacity-1 batch holding that stream, in the layout above - the reference's cache list for one stream.  It is no new format: a record can be
+ * handed to fe_step(B = 1) as it stands; n records lie back to back, records[i * fe_state_floats(h, 1) + ...]; every state is a list of tensors
+ * [rows][capacity][len], so fe_state_floats(h, B) = B * fe_state_floats(h, 1) for every family.  dptransformer rings are copied verbatim
+ * together with the stream's `head` (no rotation; a +inf "slot not in use" mark survives).  A record is valid for handles of the same
+ * fe_config and library version, on any device; it is not portable across shapes.
+ *   export: records[i] = the state of slot slots_dev[i] of state_dev (sized for `capacity`); state_dev is not written.  A slot outside
+ *     [0, capacity) yields the record fe_state_init leaves (zeros).
+ *   import: slot slots_dev[i] of state_dev = records[i], with no reset first; no other float of state_dev is written.  A slot outside
+ *     [0, capacity) is skipped: nothing is written anywhere.  Duplicate slots are undefined.
+ *   Families: every family with a streaming state - the FastEnhancer default, time_kernel, ln, dprnn and dptransformer models, BSRNN, FSPEN
+ *     and LiSenNet; for the last three, slot s is stream s of a state that plain fe_step(B = capacity) steps (the slotted STEPS stay
+ *     FastEnhancer's).  The noncausal model returns FE_ERR_UNSUPPORTED_CONFIG, as for fe_step.  Scratch the handle owns (BSRNN's inter-launch
+ *     buffers, the rings of fe_spec_step) is not state and is not touched.  Weights need not be loaded.
+ *   slots_dev: a DEVICE int32 array of n entries, read by the kernel when it runs (a captured graph may move other streams on each replay);
+ *     its contents are not checked on the host.
+ *   records: device memory of the current device, or page-locked HOST memory mapped for it (the pinning rule of fe_step_slots_pinned), which
+ *     the kernel reads or writes directly over PCIe.  The first and last float of the range are looked up before anything is launched:
+ *     pageable memory is FE_ERR_INVALID_ARG.  Any 4-byte alignment is legal (16-byte loads and stores are used where both sides allow).
+ *     records overlapping state_dev is undefined.
+ *   The host checks non-null pointers and 1 <= n <= capacity before any device work.  One launch, asynchronous on `stream`; for host records
+ *     the completion rule of fe_step_slots_pinned applies.  fe_last_step_kernel is not affected. */
+int fe_state_export_slots(fe_handle* h, const float* state_dev, int capacity, const int* slots_dev, float* records, int n, void* stream);
+int fe_state_import_slots(fe_handle* h, float* state_dev, int capacity, const int* slots_dev, const float* records, int n, void* stream);
+
 /* fe_step / fe_step_slots for audio in PAGE-LOCKED HOST memory: one launch whose kernel reads each hop over PCIe and writes the enhanced
  * hop back there - no staging buffers, copies or events, and one node when captured into a graph.  Row layout, strides, families, slot
  * rules and the kernel choice are those of fe_step_slots (fe_step_pinned: capacity = B, stream i = slot i); the results are theirs on
