@@ -24,7 +24,7 @@ BSRNN_DEPS = ["fe_kernels.hip.h", "fe_launch.h", "bsrnn_kernels.hip.h", "bsrnn_s
 FSPEN_DEPS = ["fe_kernels.hip.h", "fe_launch.h", "fspen_kernels.hip.h", "fspen_sb_kernels.hip.h"]
 LISENNET_DEPS = ["fe_kernels.hip.h", "fe_launch.h", "fspen_kernels.hip.h", "fspen_sb_kernels.hip.h", "lisennet_kernels.hip.h", "lisennet_sb_kernels.hip.h"]
 API_DEPS = ["fe_kernels.hip.h", "fe_launch.h", "fe_frame8.hip.h", "fe_impl.h", "tb_kernels.hip.h", "fe_shapes.def", "bsrnn_kernels.hip.h", "bsrnn_sb_kernels.hip.h", "bsrnn_ov_kernels.hip.h", "fe_bsrnn_shapes.def", "stft_kernels.hip.h", "fspen_kernels.hip.h", "fspen_sb_kernels.hip.h", "lisennet_kernels.hip.h", "lisennet_sb_kernels.hip.h",
-            "fe_api_bsrnn.inc", "fe_api_fspen.inc", "fe_api_lisennet.inc",
+            "fe_api_bsrnn.inc", "fe_api_fspen.inc", "fe_api_lisennet.inc", "fe_fragments.h",
             os.path.join("..", "..", "include", "fastenhancer_hip.h")]
 # -amdgpu-mfma-vgpr-form: MFMA accumulators in VGPRs instead of AGPRs - every epilogue read of an AGPR accumulator is a
 # v_accvgpr_read, a VALU instruction that the fp32 matrix path cannot overlap (~600 of them per wave and frame on

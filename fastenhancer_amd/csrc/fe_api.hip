@@ -8,11 +8,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <string>
 #include <vector>
 
 #include "../../include/fastenhancer_hip.h"
+#include "fe_fragments.h"
 #include "fe_impl.h"
 #include "bsrnn_kernels.hip.h"
 #include "fspen_kernels.hip.h"
@@ -348,38 +348,8 @@ fe_handle* new_handle(const fe_config* cfg, const Dims& d) {
     return h;
 }
 
-// Writes fragments at the compile-time offsets of fe::Pack<S>::v (the kernel uses the same table).
-struct Packer {
-    std::vector<float> buf;
-    // B operand in fragment order: dst[(nt*KS + ks)*64 + lane] = B(k = 4ks + lane/16, n = 16nt + lane%16)
-    void pack_b(int off, int K, int Ncols, const std::function<float(int, int)>& Bkn) {
-        const int KS = K / 4, NT = (Ncols + 15) / 16;
-        for (int nt = 0; nt < NT; ++nt)
-            for (int ks = 0; ks < KS; ++ks)
-                for (int lane = 0; lane < 64; ++lane) {
-                    int k = 4 * ks + lane / 16, n = 16 * nt + lane % 16;
-                    buf[off + ((size_t)nt * KS + ks) * 64 + lane] = n < Ncols ? Bkn(k, n) : 0.0f;
-                }
-    }
-    // A operand: dst[(mt*KS + ks)*64 + lane] = A(m = 16mt + lane%16, k = 4ks + lane/16)
-    void pack_a(int off, int Mrows, int K, const std::function<float(int, int)>& Amk) {
-        const int KS = K / 4, MT = (Mrows + 15) / 16;
-        for (int mt = 0; mt < MT; ++mt)
-            for (int ks = 0; ks < KS; ++ks)
-                for (int lane = 0; lane < 64; ++lane) {
-                    int m = 16 * mt + lane % 16, k = 4 * ks + lane / 16;
-                    buf[off + ((size_t)mt * KS + ks) * 64 + lane] = m < Mrows ? Amk(m, k) : 0.0f;
-                }
-    }
-    void raw(int off, size_t n, const float* src) { memcpy(&buf[off], src, n * sizeof(float)); }
-    void rep4(int off, size_t n, const float* src) {   // [n][4]: each value four times (16-byte accumulator initialisers)
-        for (size_t i = 0; i < n; ++i)
-            for (int r = 0; r < 4; ++r) buf[(size_t)off + 4 * i + r] = src[i];
-    }
-};
-
-// constant operands of the matrix-core DFT (fe::Dft in fe_kernels.hip.h), N = N1 * 32, at the four given offsets of p.buf
-void pack_dft_constants(Packer& p, int N, int dft1, int dft2, int dft3, int dft4) {
+// constant operands of the matrix-core DFT (fe::Dft in fe_kernels.hip.h), N = N1 * 32, at the four given offsets of p
+void pack_dft_constants(fe::frag::Buffer& p, int N, int dft1, int dft2, int dft3, int dft4) {
     {
         const int N1 = N / 32, KC = N1 / 2, MT = N1 / 16;
         auto c32 = [](int a, int b) { return std::cos(2.0 * M_PI * (double)((a * b) % 32) / 32.0); };
@@ -415,20 +385,31 @@ void pack_dft_constants(Packer& p, int N, int dft1, int dft2, int dft3, int dft4
     }
 }
 
-const float* sec(const fe_handle* h, const std::vector<float>& blob, const std::string& name) {
-    for (const Section& s : h->sections)
-        if (s.name == name) return blob.data() + s.offset;
-    return nullptr;
+// the fused blob by section name: S("enc_pre.0.weight")
+struct Blob {
+    const fe_handle* h;
+    const float* v;
+    const float* operator()(const std::string& name) const {
+        for (const Section& s : h->sections)
+            if (s.name == name) return v + s.offset;
+        return nullptr;
+    }
+};
+
+// [window | window_istft | twiddle] of the handle, where a family's offset table wants them
+void pack_stft_tables(fe::frag::Buffer& p, const fe_handle* h, int window, int window_istft, int twiddle) {
+    p.raw(window, h->window.size(), h->window.data());
+    p.raw(window_istft, h->window_istft.size(), h->window_istft.data());
+    p.raw(twiddle, h->twiddle.size(), h->twiddle.data());
 }
 
-int pack_weights(fe_handle* h, const std::vector<float>& blob, std::vector<float>* out) {
+// FastEnhancer: fragments (fe_fragments.h) at the compile-time offsets of fe::Pack<S>::v (the kernel uses the same table)
+int pack_weights(fe_handle* h, const Blob& S, std::vector<float>* out) {
     const Dims& d = h->d;
     const int C1 = d.C1, C2 = d.C2, F1 = d.F1, F2 = d.F2;
     const fe::PackedOffsets& o = *h->impl->off;
-    Packer p;
-    p.buf.assign((size_t)o.total, 0.0f);
+    fe::frag::Buffer p((size_t)o.total);
     char nm[128];
-    auto S = [&](const std::string& n) { return sec(h, blob, n); };
     // (Co, Ci, 3), or (Co, Ci, KT, 3) for the time_kernel variant: one B operand per time tap, k = freq_tap*Ci + ci.
     // Units are in consumption order: unit 0 multiplies the CURRENT frame = time index KT-1 of the causal kernel, unit j the
     // frame j steps back = time index KT-1-j
@@ -460,7 +441,7 @@ int pack_weights(fe_handle* h, const std::vector<float>& blob, std::vector<float
     if (d.TA) {     // [NH][L + 1] -> [NH][32]
         const float* tp = S("time_pe");
         for (int hh = 0; hh < 4; ++hh)
-            for (int j = 0; j <= d.TA; ++j) p.buf[o.tpe + hh * 32 + j] = tp[hh * (d.TA + 1) + j];
+            for (int j = 0; j <= d.TA; ++j) p[o.tpe + hh * 32 + j] = tp[hh * (d.TA + 1) + j];
     }
     for (int k = 0; k < d.KB; ++k) {
         auto key = [&](const char* s) { snprintf(nm, sizeof nm, "rf_block.%d.%s", k, s); return std::string(nm); };
@@ -487,7 +468,7 @@ int pack_weights(fe_handle* h, const std::vector<float>& blob, std::vector<float
         }
         if (o.u8_gx[k] != 0) {
             // 512-thread per-hop kernel (fe_frame8.hip.h, Shape::G8P): the block weights as LDS-staged units (PackedOffsets::u8_*):
-            // B fragments [tile][k-step][64] followed by the tiles' start values [tile][16].
+            // plain B fragments followed by the tiles' start values [tile][16].
             const float* wih = S(key("rnn.weight_ih_l0"));
             const float* whh = S(key("rnn.weight_hh_l0"));
             const float* bih = S(key("rnn.bias_ih_l0"));
@@ -495,17 +476,11 @@ int pack_weights(fe_handle* h, const std::vector<float>& blob, std::vector<float
             const int NG = C2 / 16, R = C2 % 16, NT = 3 * NG + 1, KS = C2 / 4;
             // tile t, column c -> row of the (rows, C2) weight matrix (-1: padding); bias(t, c)
             // (rscale(row): the gate rows carry -log2 e (r, z) / 2 log2 e (n) so that sigma / tanh are one exp2 + rcp of the accumulator)
-            auto pack_u8 = [&](int off, int ntiles, const float* w, const std::function<int(int, int)>& wrow, const std::function<float(int, int)>& bias,
-                               const std::function<float(int)>& rscale = [](int) { return 1.0f; }) {
-                for (int t = 0; t < ntiles; ++t) {
-                    for (int ks = 0; ks < KS; ++ks)
-                        for (int lane = 0; lane < 64; ++lane) {
-                            const int row = wrow(t, lane % 16);
-                            p.buf[(size_t)off + ((size_t)t * KS + ks) * 64 + lane] = row >= 0 ? w[(size_t)row * C2 + 4 * ks + lane / 16] * rscale(row) : 0.0f;
-                        }
-                    for (int c = 0; c < 16; ++c) p.buf[(size_t)off + (size_t)ntiles * KS * 64 + t * 16 + c] = wrow(t, c) >= 0 ? bias(t, c) * rscale(wrow(t, c)) : 0.0f;
-                }
+            auto pack_u8 = [&](int off, int ntiles, const float* w, auto&& wrow, auto&& bias, auto&& rscale) {
+                p.tiles(off, ntiles, KS, [&](int t, int c, int kk) { const int row = wrow(t, c); return row >= 0 ? w[(size_t)row * C2 + kk] * rscale(row) : 0.0f; });
+                p.rows((size_t)off + (size_t)ntiles * KS * 64, ntiles, [&](int t, int c) { const int row = wrow(t, c); return row >= 0 ? bias(t, c) * rscale(row) : 0.0f; });
             };
+            auto one = [](int) { return 1.0f; };
             auto gscale = [&](int row) { return row < 2 * C2 ? fe::kGateRZ : fe::kGateN; };
             // channel-grouped gate tiles: tile 3 G + gate: column c <-> channel 16 G + c of that gate; the last tile: columns [0, R) r,
             // [R, 2 R) z, [2 R, 3 R) n of the R = C2 % 16 left-over channels
@@ -519,18 +494,9 @@ int pack_weights(fe_handle* h, const std::vector<float>& blob, std::vector<float
             auto plain = [&](int ncols) { return [ncols](int t, int c) { return 16 * t + c < ncols ? 16 * t + c : -1; }; };
             const float* f1b = S(key("rnn_fc.bias"));
             const float* f2b = S(key("attn_fc.bias"));
-            pack_u8(o.u8_f1[k], fe::ceil_div(C2, 16), S(key("rnn_fc.weight")), plain(C2), [&](int t, int c) { return f1b[16 * t + c]; });
-            {   // qkv: fragments only (the unit has no start values)
-                const float* wq = S(key("attn.qkv.weight"));
-                const int ntq = fe::ceil_div(3 * C2, 16);
-                for (int t = 0; t < ntq; ++t)
-                    for (int ks = 0; ks < KS; ++ks)
-                        for (int lane = 0; lane < 64; ++lane) {
-                            const int row = 16 * t + lane % 16;
-                            p.buf[(size_t)o.u8_q[k] + ((size_t)t * KS + ks) * 64 + lane] = row < 3 * C2 ? wq[(size_t)row * C2 + 4 * ks + lane / 16] : 0.0f;
-                        }
-            }
-            pack_u8(o.u8_f2[k], fe::ceil_div(C2, 16), S(key("attn_fc.weight")), plain(C2), [&](int t, int c) { return f2b[16 * t + c]; });
+            pack_u8(o.u8_f1[k], fe::ceil_div(C2, 16), S(key("rnn_fc.weight")), plain(C2), [&](int t, int c) { return f1b[16 * t + c]; }, one);
+            pack_1x1(o.u8_q[k], S(key("attn.qkv.weight")), C2, 3 * C2);      // qkv: fragments only (the unit has no start values)
+            pack_u8(o.u8_f2[k], fe::ceil_div(C2, 16), S(key("attn_fc.weight")), plain(C2), [&](int t, int c) { return f2b[16 * t + c]; }, one);
         }
         if (h->impl->tb && !d.TA) {
             // time-batched engine (tb_kernels.hip.h): per direction the input weights as ONE flat (3 C2)-column matrix (rows r | z | n as
@@ -543,7 +509,7 @@ int pack_weights(fe_handle* h, const std::vector<float>& blob, std::vector<float
                 const float* bih = S(key((std::string("rnn.bias_ih_l0") + sfx).c_str()));
                 const float* bhh = S(key((std::string("rnn.bias_hh_l0") + sfx).c_str()));
                 pack_1x1(o.tb_wih[k][dir], wih, C2, 3 * C2);
-                for (int c = 0; c < 3 * C2; ++c) p.buf[(size_t)o.tb_bx[k][dir] + c] = bih[c] + (c < 2 * C2 ? bhh[c] : 0.0f);
+                for (int c = 0; c < 3 * C2; ++c) p[(size_t)o.tb_bx[k][dir] + c] = bih[c] + (c < 2 * C2 ? bhh[c] : 0.0f);
                 for (int g = 0; g < 3; ++g) pack_1x1(o.tb_whh[k][dir] + g * gsz, whh + (size_t)g * C2 * C2, C2, C2);
                 p.raw(o.tb_bhn[k][dir], C2, bhh + 2 * C2);
             }
@@ -565,11 +531,11 @@ int pack_weights(fe_handle* h, const std::vector<float>& blob, std::vector<float
                 const float* bhh = S(key((std::string("frnn.bias_hh_l0") + sfx).c_str()));
                 std::copy(w, w + (size_t)3 * H * C2, wih.begin() + (size_t)dir * 3 * H * C2);
                 for (int r = 0; r < 3 * H; ++r) bi[(size_t)dir * 3 * H + r] = bih[r] + (r < 2 * H ? bhh[r] : 0.0f);
-                float* dst = p.buf.data() + o.blk_fhh[k] + (size_t)dir * H * 3 * H;
+                const size_t dst = o.blk_fhh[k] + (size_t)dir * H * 3 * H;
                 for (int j = 0; j < H; ++j)
                     for (int g = 0; g < 3; ++g)
-                        for (int u = 0; u < H; ++u) dst[((size_t)j * 3 + g) * H + u] = whh[((size_t)g * H + u) * H + j];
-                for (int u = 0; u < H; ++u) p.buf[o.blk_fbhn[k] + (size_t)dir * H + u] = bhh[2 * H + u];
+                        for (int u = 0; u < H; ++u) p[dst + ((size_t)j * 3 + g) * H + u] = whh[((size_t)g * H + u) * H + j];
+                for (int u = 0; u < H; ++u) p[o.blk_fbhn[k] + (size_t)dir * H + u] = bhh[2 * H + u];
             }
             pack_1x1(o.blk_qkv[k], wih.data(), C2, 3 * C2);
             p.raw(o.blk_qkv_b[k], 3 * C2, bi.data());
@@ -658,7 +624,7 @@ int pack_weights(fe_handle* h, const std::vector<float>& blob, std::vector<float
     {   // scaled conv trunk (fe_kernels.hip.h, kSiluScale): biases of the SiLU layers, entry weights, exit weights
         const float c = d.LN ? 1.0f : fe::kSiluScale;      // (ln variant: no scaling - a norm layer follows every conv)
         auto szB = [](int K, int N) { return (size_t)fe::ceil_div(N, 16) * (K / 4) * 64; };
-        auto scale = [&](int off, size_t n, float f) { for (size_t i = 0; i < n; ++i) p.buf[(size_t)off + i] *= f; };
+        auto scale = [&](int off, size_t n, float f) { for (size_t i = 0; i < n; ++i) p[(size_t)off + i] *= f; };
         scale(o.enc_pre_w, szB(16, C1), c); scale(o.enc_pre_b, 4 * C1, c);       // (biases: 4x replicated tables)
         for (int i = 0; i < d.NL; ++i) { scale(o.enc_b[i], 4 * C1, c); scale(o.dec1_b[i], 4 * C1, c); scale(o.dec3_b[i], 4 * C1, c); }
         scale(o.rfpre_w, szB(C1, C2), 1.0f / c);                                  // encoder -> RNNFormer: back to true scale
@@ -666,48 +632,28 @@ int pack_weights(fe_handle* h, const std::vector<float>& blob, std::vector<float
         scale(o.post1_b, 4 * C1, c);
         scale(o.post_t_w, szB(C1, 16), 1.0f / c);                                 // transposed conv: true-scale mask
     }
-    if (o.act_p > 0) p.buf[(size_t)o.act_p] = h->cfg.activation_param;            // LeakyReLU negative_slope / ELU alpha (Shape::EPP)
-    p.raw(o.window, h->window.size(), h->window.data());
-    p.raw(o.window_istft, h->window_istft.size(), h->window_istft.data());
-    p.raw(o.twiddle, h->twiddle.size(), h->twiddle.data());
+    if (o.act_p > 0) p[(size_t)o.act_p] = h->cfg.activation_param;            // LeakyReLU negative_slope / ELU alpha (Shape::EPP)
+    pack_stft_tables(p, h, o.window, o.window_istft, o.twiddle);
     pack_dft_constants(p, h->cfg.n_fft, o.dft1, o.dft2, o.dft3, o.dft4);
+    // a copy of [beg, end) delta floats on, in which tiles are then regrouped to k4 order (fe_fragments.h) for 16-byte fetches
+    auto copy_region = [&](int beg, int end, int delta) { for (int i = beg; i < end; ++i) p[(size_t)i + delta] = p[i]; };
     if (o.k4_delta != 0) {
-        // Register-resident block weights (fe::Shape::REGW): a second copy of the block-weight region whose B-operand tiles are
-        // regrouped four k-steps per lane ([ks / 4][lane][4], the ks % 4 remainder plain) for 16-byte fetches - fe::TokW
-        const int KS = C2 / 4, NF4 = KS / 4, tile_floats = KS * 64;
-        std::copy(p.buf.begin() + o.blk_wih[0], p.buf.begin() + o.blk_end, p.buf.begin() + o.blk_wih[0] + o.k4_delta);
-        std::vector<float> t((size_t)tile_floats);
-        auto regroup = [&](int off, int floats) {
-            for (int tl = 0; tl < floats / tile_floats; ++tl) {
-                float* dst = &p.buf[(size_t)off + o.k4_delta + (size_t)tl * tile_floats];
-                std::copy(dst, dst + tile_floats, t.begin());
-                for (int ks = 0; ks < 4 * NF4; ++ks)
-                    for (int ln = 0; ln < 64; ++ln) dst[(ks / 4) * 256 + ln * 4 + (ks % 4)] = t[(size_t)ks * 64 + ln];
-            }
-        };
-        const int szCC = fe::ceil_div(C2, 16) * tile_floats, szC3 = fe::ceil_div(3 * C2, 16) * tile_floats;
+        // Register-resident block weights (fe::Shape::REGW): a second copy of the block-weight region with its B-operand tiles in k4 order
+        // (the KS % 4 remainder plain) - fe::TokW
+        copy_region(o.blk_wih[0], o.blk_end, o.k4_delta);
+        const int KS = C2 / 4, NTC = fe::ceil_div(C2, 16), NT3 = fe::ceil_div(3 * C2, 16);
+        auto regroup = [&](int off, int tiles) { p.regroup_k4((size_t)off + o.k4_delta, off, tiles, KS, 0, KS); };
         for (int k = 0; k < d.KB; ++k) {
-            regroup(o.blk_wih[k], 3 * szCC); regroup(o.blk_whh[k], 3 * szCC);
-            regroup(o.blk_fc1_w[k], szCC); regroup(o.blk_qkv[k], szC3); regroup(o.blk_fc2_w[k], szCC);
-            if (d.TA) regroup(o.blk_tqkv[k], szC3);
+            regroup(o.blk_wih[k], 3 * NTC); regroup(o.blk_whh[k], 3 * NTC);
+            regroup(o.blk_fc1_w[k], NTC); regroup(o.blk_qkv[k], NT3); regroup(o.blk_fc2_w[k], NTC);
+            if (d.TA) regroup(o.blk_tqkv[k], NT3);
         }
     }
     if (o.conv_k4_delta != 0) {
-        // Time-batched engine (r4w): a copy of the conv units whose weight tiles are regrouped four k-steps per lane for 16-byte fetches
-        // (tb_kernels.hip.h::conv_gemm; the biases and the filterbanks in the copy stay as they are).  Must run AFTER every conv weight is packed.
-        const int ubeg = o.u_off[0], uend = o.u_off[o.n_units - 1] + o.u_size[o.n_units - 1];
-        std::copy(p.buf.begin() + ubeg, p.buf.begin() + uend, p.buf.begin() + ubeg + o.conv_k4_delta);
-        std::vector<float> t;
-        auto regroup_c = [&](int off, int tiles, int KS) {
-            const int tile_floats = KS * 64, NF4 = KS / 4;
-            t.resize((size_t)tile_floats);
-            for (int tl = 0; tl < tiles; ++tl) {
-                float* dst = &p.buf[(size_t)off + o.conv_k4_delta + (size_t)tl * tile_floats];
-                std::copy(dst, dst + tile_floats, t.begin());
-                for (int ks = 0; ks < 4 * NF4; ++ks)
-                    for (int ln = 0; ln < 64; ++ln) dst[(ks / 4) * 256 + ln * 4 + (ks % 4)] = t[(size_t)ks * 64 + ln];
-            }
-        };
+        // Time-batched engine (r4w): a copy of the conv units whose weight tiles are in k4 order (tb_kernels.hip.h::conv_gemm; the biases
+        // and the filterbanks in the copy stay as they are).  Must run AFTER every conv weight is packed.
+        copy_region(o.u_off[0], o.u_off[o.n_units - 1] + o.u_size[o.n_units - 1], o.conv_k4_delta);
+        auto regroup_c = [&](int off, int tiles, int KS) { p.regroup_k4((size_t)off + o.conv_k4_delta, off, tiles, KS, 0, KS); };
         const int NTC = fe::ceil_div(C1, 16), KSC = C1 / 4, KS2 = C2 / 4;
         regroup_c(o.enc_pre_w, NTC, 4);
         for (int l = 0; l < d.NL; ++l) {
@@ -718,7 +664,7 @@ int pack_weights(fe_handle* h, const std::vector<float>& blob, std::vector<float
         regroup_c(o.post1_w, NTC, 2 * KSC);
         regroup_c(o.post_t_w, 1, KSC);
     }
-    *out = std::move(p.buf);
+    *out = std::move(p.v);
     return FE_OK;
 }
 
@@ -1059,6 +1005,26 @@ int fe_weight_section(const fe_handle* h, int idx, const char** name, size_t* of
     return FE_OK;
 }
 
+// the one packing path: fused blob (host) -> the buffer the kernels read (host); no HIP call
+static int pack_blob(fe_handle* h, const float* blob, std::vector<float>* packed) {
+    int rc = FE_OK;
+    const Blob S{h, blob};
+    if (!visit_baseline(h->cfg.arch, [&](auto F) { rc = F.pack_weights(h, S, packed); })) rc = pack_weights(h, S, packed);
+    return rc;
+}
+
+int fe_debug_pack_weights(fe_handle* h, const float* blob_host, size_t nfloats, float* out_host, size_t capacity, size_t* packed_floats) {
+    if (!h || !blob_host) return fail(FE_ERR_INVALID_ARG, "null argument");
+    if (nfloats != h->blob_floats) return fail(FE_ERR_INVALID_ARG, "blob has %zu floats, expected %zu", nfloats, h->blob_floats);
+    std::vector<float> packed;
+    const int rc = pack_blob(h, blob_host, &packed);
+    if (rc != FE_OK) return rc;
+    if (out_host && capacity < packed.size()) return fail(FE_ERR_INVALID_ARG, "output holds %zu floats, the packed buffer has %zu", capacity, packed.size());
+    if (packed_floats) *packed_floats = packed.size();
+    if (out_host) std::memcpy(out_host, packed.data(), packed.size() * sizeof(float));
+    return FE_OK;
+}
+
 int fe_load_weights(fe_handle* h, const float* blob_dev, size_t nfloats, void* stream) {
     if (!h || !blob_dev) return fail(FE_ERR_INVALID_ARG, "null argument");
     if (nfloats != h->blob_floats) return fail(FE_ERR_INVALID_ARG, "blob has %zu floats, expected %zu", nfloats, h->blob_floats);
@@ -1067,8 +1033,7 @@ int fe_load_weights(fe_handle* h, const float* blob_dev, size_t nfloats, void* s
     FE_HIP_CHECK(hipMemcpyAsync(blob.data(), blob_dev, nfloats * sizeof(float), hipMemcpyDeviceToHost, st));
     FE_HIP_CHECK(hipStreamSynchronize(st));
     std::vector<float> packed;
-    int rc = FE_OK;
-    if (!visit_baseline(h->cfg.arch, [&](auto F) { rc = F.pack_weights(h, blob, &packed); })) rc = pack_weights(h, blob, &packed);
+    int rc = pack_blob(h, blob.data(), &packed);
     if (rc != FE_OK) return rc;
     if (h->packed_dev) { FE_HIP_CHECK(hipFree(h->packed_dev)); h->packed_dev = nullptr; }
     FE_HIP_CHECK(hipMalloc(&h->packed_dev, packed.size() * sizeof(float)));

@@ -23,7 +23,7 @@ struct BsrnnFamily {
     static size_t xp_floats(const fe_handle* h) { return (size_t)h->max_wgs * h->bimpl->xp_floats; }     // (band-LSTM input projections of C = 64)
     static Args args(fe_handle* h, int B, int T);
     static int create(const fe_config* cfg, fe_handle** out);
-    static int pack_weights(fe_handle* h, const std::vector<float>& blob, std::vector<float>* out);
+    static int pack_weights(fe_handle* h, const Blob& S, std::vector<float>* out);
     static int ensure_sb(fe_handle* h, int B);
     static int launch(fe_handle* h, const Args& a, void* stream);
     static const char* stage_name(const fe_handle* h, int idx);
@@ -79,22 +79,15 @@ int BsrnnFamily::create(const fe_config* cfg, fe_handle** out) {
     return FE_OK;
 }
 
-int BsrnnFamily::pack_weights(fe_handle* h, const std::vector<float>& blob, std::vector<float>* out) {
+// Grows in allocation order: the offsets it hands out are BOffsets / SbOffsets.  Fragment orders: fe_fragments.h
+int BsrnnFamily::pack_weights(fe_handle* h, const Blob& S, std::vector<float>* out) {
     const int C = h->cfg.channels, L = h->cfg.rf_blocks, HH = 2 * C, G4 = 4 * HH, R = 4 * 257;
     const bool whh_regs = h->bimpl->whh_regs;
     fe::BOffsets& o = h->boff;
-    std::vector<float> buf;
-    auto alloc = [&](size_t n) { size_t off = (buf.size() + 63) & ~(size_t)63; buf.resize(off + n, 0.0f); return (int)off; };
-    auto S = [&](const std::string& n) { return sec(h, blob, n); };
-    auto pack_b = [&](int K, int Ncols, const std::function<float(int, int)>& Bkn) {
-        const int KS = K / 4, NT = (Ncols + 15) / 16;
-        int off = alloc((size_t)NT * KS * 64);
-        for (int nt = 0; nt < NT; ++nt)
-            for (int ks = 0; ks < KS; ++ks)
-                for (int lane = 0; lane < 64; ++lane) {
-                    int k = 4 * ks + lane / 16, n = 16 * nt + lane % 16;
-                    buf[off + ((size_t)nt * KS + ks) * 64 + lane] = n < Ncols ? Bkn(k, n) : 0.0f;
-                }
+    fe::frag::Buffer buf;
+    auto pack_b = [&](int K, int Ncols, auto&& Bkn) {
+        const int off = buf.alloc((size_t)((Ncols + 15) / 16) * (K / 4) * 64);
+        buf.pack_b(off, K, Ncols, Bkn);
         return off;
     };
     // LSTM gate rows (order i, f, g, o) are packed pre-scaled: with pre' = s_g * pre the kernel evaluates every gate as
@@ -103,8 +96,8 @@ int BsrnnFamily::pack_weights(fe_handle* h, const std::vector<float>& blob, std:
     auto gscale = [&](int row) { return (float)((row / HH) == 2 ? -2.0 * kL2E : -kL2E); };
     char nm[160];
     {   // band split: [k/4][band*C + c] float4 - thread (band, c) reads its zero-padded row as 16-byte loads coalesced over the threads
-        o.bs_w = alloc((size_t)31 * C * fe::kBsKP);
-        o.bs_b = alloc(31 * C);
+        o.bs_w = buf.alloc((size_t)31 * C * fe::kBsKP);
+        o.bs_b = buf.alloc(31 * C);
         for (int b = 0; b < 31; ++b) {
             snprintf(nm, sizeof nm, "band_split.fc.%d.weight", b);
             const float* w = S(nm);                                   // (C, 2sub)
@@ -112,7 +105,7 @@ int BsrnnFamily::pack_weights(fe_handle* h, const std::vector<float>& blob, std:
             for (int c = 0; c < C; ++c)
                 for (int k = 0; k < k2; ++k) buf[o.bs_w + (((size_t)(k / 4) * 31 * C) + b * C + c) * 4 + (k & 3)] = w[c * k2 + k];
             snprintf(nm, sizeof nm, "band_split.fc.%d.bias", b);
-            memcpy(&buf[o.bs_b + b * C], S(nm), C * sizeof(float));
+            buf.raw(o.bs_b + b * C, C, S(nm));
         }
     }
     for (int l = 0; l < L; ++l) {
@@ -123,14 +116,14 @@ int BsrnnFamily::pack_weights(fe_handle* h, const std::vector<float>& blob, std:
             o.t_w[l] = pack_b(C + HH, G4, [&](int k, int n) { return gscale(n) * (k < C ? wih[n * C + k] : whh[n * HH + (k - C)]); });
             const float* bi = S(key("rnn_time.%d.bias_ih"));
             const float* bh = S(key("rnn_time.%d.bias_hh"));
-            o.t_b[l] = alloc(G4);
+            o.t_b[l] = buf.alloc(G4);
             for (int i = 0; i < G4; ++i) buf[o.t_b[l] + i] = gscale(i) * (bi[i] + bh[i]);
         }
         {
             const float* w = S(key("fc_time.%d.weight"));         // (C, HH)
             o.tfc_w[l] = pack_b(HH, C, [&](int k, int n) { return w[n * HH + k]; });
-            o.tfc_b[l] = alloc(C);
-            memcpy(&buf[o.tfc_b[l]], S(key("fc_time.%d.bias")), C * sizeof(float));
+            o.tfc_b[l] = buf.alloc(C);
+            buf.raw(o.tfc_b[l], C, S(key("fc_time.%d.bias")));
         }
         for (int d = 0; d < 2; ++d) {
             const char* sfx = d ? "_reverse" : "";
@@ -139,14 +132,14 @@ int BsrnnFamily::pack_weights(fe_handle* h, const std::vector<float>& blob, std:
             o.f_wih[l][d] = pack_b(C, G4, [&](int k, int n) { return gscale(n) * wih[n * C + k]; });
             const float* bi = S(keyd("bias_ih"));
             const float* bh = S(keyd("bias_hh"));
-            o.f_b[l][d] = alloc(G4);
+            o.f_b[l][d] = buf.alloc(G4);
             for (int i = 0; i < G4; ++i) buf[o.f_b[l][d] + i] = gscale(i) * (bi[i] + bh[i]);
             {   // recurrence weights in thread order.  Thread t (0..NTD-1; NTD = 128, or 256 for C = 64) of a direction = 4 u + q, hidden unit u (+ NTD/4 rr).
                 // KSPLIT shapes: q = K-quarter; the thread holds, for all four gates g, W_hh[g*HH + u + 32 rr][q*HH/4 + kk] at
                 //   [rr][g*HH/4 + kk][t].  Otherwise q = gate: it holds row W_hh[q*HH + u + 32 rr][k] at [rr][k][t].
                 // (streamed shapes: the k index in float4 groups)
                 const float* whh = S(keyd("weight_hh"));      // (4HH, HH), gate-major rows
-                o.f_whh[l][d] = alloc((size_t)G4 * HH);
+                o.f_whh[l][d] = buf.alloc((size_t)G4 * HH);
                 const int NTD = h->bimpl->rec_threads, UPP = NTD / 4;      // threads of a direction (256 for C = 64: SEQD), units per pass
                 const int RPT = HH / UPP, Q = HH / 4;
                 const bool ksplit = h->bimpl->ksplit;
@@ -165,8 +158,8 @@ int BsrnnFamily::pack_weights(fe_handle* h, const std::vector<float>& blob, std:
         {
             const float* w = S(key("fc_freq.%d.weight"));         // (C, 2HH)
             o.ffc_w[l] = pack_b(2 * HH, C, [&](int k, int n) { return w[n * 2 * HH + k]; });
-            o.ffc_b[l] = alloc(C);
-            memcpy(&buf[o.ffc_b[l]], S(key("fc_freq.%d.bias")), C * sizeof(float));
+            o.ffc_b[l] = buf.alloc(C);
+            buf.raw(o.ffc_b[l], C, S(key("fc_freq.%d.bias")));
         }
     }
     if (h->bimpl->launch_sb) {
@@ -176,46 +169,29 @@ int BsrnnFamily::pack_weights(fe_handle* h, const std::vector<float>& blob, std:
         fe::SbOffsets& so = h->sboff;
         const int KSC = C / 4, KSH = HH / 4, KS1 = KSC + KSH, NTO = C / 16;
         auto pack_lstm = [&](const float* wih, const float* whh, const float* bi, const float* bh, int* w_off, int* b_off) {
-            *w_off = alloc((size_t)KSH * KS1 * 64);
-            *b_off = alloc((size_t)KSH * 16);
-            for (int t = 0; t < KSH; ++t) {
-                for (int ks = 0; ks < KS1; ++ks)
-                    for (int lane = 0; lane < 64; ++lane) {
-                        const int rho = lane % 16, lgk = lane / 16, row = (rho % 4) * HH + KSH * (rho / 4) + t;
-                        const float v = ks < KSC ? wih[(size_t)row * C + KSC * lgk + ks] : whh[(size_t)row * HH + KSH * lgk + (ks - KSC)];
-                        buf[*w_off + ((size_t)t * KS1 + ks) * 64 + lane] = gscale(row) * v;
-                    }
-                for (int lg = 0; lg < 4; ++lg)
-                    for (int r = 0; r < 4; ++r) {
-                        const int row = r * HH + KSH * lg + t;
-                        buf[*b_off + t * 16 + lg * 4 + r] = gscale(row) * (bi[row] + bh[row]);
-                    }
-            }
+            *w_off = buf.alloc((size_t)KSH * KS1 * 64);
+            *b_off = buf.alloc((size_t)KSH * 16);
+            auto row = [&](int t, int rho) { return (rho % 4) * HH + KSH * (rho / 4) + t; };
+            buf.tiles(*w_off, KSH, KS1, [&](int t, int rho, int k) {
+                const int ks = k / 4, lgk = k % 4, rw = row(t, rho);
+                return gscale(rw) * (ks < KSC ? wih[(size_t)rw * C + KSC * lgk + ks] : whh[(size_t)rw * HH + KSH * lgk + (ks - KSC)]);
+            });
+            buf.rows(*b_off, KSH, [&](int t, int rho) { return gscale(row(t, rho)) * (bi[row(t, rho)] + bh[row(t, rho)]); });
         };
+        auto chan = [&](int to, int rho) { return KSC * (rho / 4) + 4 * to + rho % 4; };
         auto pack_fc = [&](const float* w, int ld, int col0, int* w_off) {       // rows = channels, columns col0 .. col0 + HH - 1 of a (C, ld) matrix
-            *w_off = alloc((size_t)NTO * KSH * 64);
-            for (int to = 0; to < NTO; ++to)
-                for (int ks = 0; ks < KSH; ++ks)
-                    for (int lane = 0; lane < 64; ++lane) {
-                        const int rho = lane % 16, lgk = lane / 16, ch = KSC * (rho / 4) + 4 * to + rho % 4;
-                        buf[*w_off + ((size_t)to * KSH + ks) * 64 + lane] = w[(size_t)ch * ld + col0 + KSH * lgk + ks];
-                    }
+            *w_off = buf.alloc((size_t)NTO * KSH * 64);
+            buf.tiles(*w_off, NTO, KSH, [&](int to, int rho, int k) { return w[(size_t)chan(to, rho) * ld + col0 + KSH * (k % 4) + k / 4]; });
         };
-        // k-steps [k0, k0 + nk) of a packed matrix's tiles ([tile][kst][64]) once more as [tile][nk / 4][lane][4]
+        // k-steps [k0, k0 + nk) of a packed matrix's tiles once more, in k4 order
         auto k4_copy = [&](int src, int ntiles, int kst, int k0, int nk) {
-            const int dst = alloc((size_t)ntiles * nk * 64);
-            for (int t = 0; t < ntiles; ++t)
-                for (int q = 0; q < nk / 4; ++q)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int j = 0; j < 4; ++j)
-                            buf[dst + (((size_t)t * (nk / 4) + q) * 64 + lane) * 4 + j] = buf[src + ((size_t)t * kst + k0 + 4 * q + j) * 64 + lane];
+            const int dst = buf.alloc((size_t)ntiles * nk * 64);
+            buf.regroup_k4(dst, src, ntiles, kst, k0, nk);
             return dst;
         };
         auto pack_fc_bias = [&](const float* b, int* b_off) {
-            *b_off = alloc((size_t)NTO * 16);
-            for (int to = 0; to < NTO; ++to)
-                for (int lg = 0; lg < 4; ++lg)
-                    for (int r = 0; r < 4; ++r) buf[*b_off + to * 16 + lg * 4 + r] = b[KSC * lg + 4 * to + r];
+            *b_off = buf.alloc((size_t)NTO * 16);
+            buf.rows(*b_off, NTO, [&](int to, int rho) { return b[chan(to, rho)]; });
         };
         for (int l = 0; l < L; ++l) {
             auto key = [&](const char* fmt) { snprintf(nm, sizeof nm, fmt, l); return std::string(nm); };
@@ -228,7 +204,7 @@ int BsrnnFamily::pack_weights(fe_handle* h, const std::vector<float>& blob, std:
                 const char* sfx = d ? "_reverse" : "";
                 auto keyd = [&](const char* stem) { snprintf(nm, sizeof nm, "rnn_freq.%d.%s_l0%s", l, stem, sfx); return std::string(nm); };
                 pack_lstm(S(keyd("weight_ih")), S(keyd("weight_hh")), S(keyd("bias_ih")), S(keyd("bias_hh")), &so.f_w[l][d], &so.f_b[l][d]);
-                if (C == 64) {      // bsrnn_sb64_layers_kernel: x k-steps (streamed every step) and h k-steps as [tile][k-step / 4][lane][4]
+                if (C == 64) {      // bsrnn_sb64_layers_kernel: x k-steps (streamed every step) and h k-steps in k4 order
                     so.f_wx4[l][d] = k4_copy(so.f_w[l][d], KSH, KS1, 0, KSC);
                     so.f_wh4[l][d] = k4_copy(so.f_w[l][d], KSH, KS1, KSC, KSH);
                 } else so.f_wx4[l][d] = so.f_wh4[l][d] = 0;
@@ -240,10 +216,10 @@ int BsrnnFamily::pack_weights(fe_handle* h, const std::vector<float>& blob, std:
     }
     const char* kinds[2] = {"mlp_mask", "mlp_residual"};
     for (int kind = 0; kind < 2; ++kind) {
-        o.m_w1[kind] = alloc((size_t)31 * 4 * C * C);      // [band][k/4][o] float4
-        o.m_b1[kind] = alloc((size_t)31 * 4 * C);
-        o.m_w2[kind] = alloc((size_t)R * 4 * C);           // [k/4][global row] float4
-        o.m_b2[kind] = alloc(R);
+        o.m_w1[kind] = buf.alloc((size_t)31 * 4 * C * C);      // [band][k/4][o] float4
+        o.m_b1[kind] = buf.alloc((size_t)31 * 4 * C);
+        o.m_w2[kind] = buf.alloc((size_t)R * 4 * C);           // [k/4][global row] float4
+        o.m_b2[kind] = buf.alloc(R);
         int row0 = 0;
         for (int b = 0; b < 31; ++b) {
             snprintf(nm, sizeof nm, "mask_decoder.%s.%d.0.weight", kinds[kind], b);
@@ -254,7 +230,7 @@ int BsrnnFamily::pack_weights(fe_handle* h, const std::vector<float>& blob, std:
                         buf[o.m_w1[kind] + (((size_t)b * (C / 4) + k / 4) * (4 * C) + oo) * 4 + (k & 3)] = w1[oo * C + k];
             }
             snprintf(nm, sizeof nm, "mask_decoder.%s.%d.0.bias", kinds[kind], b);
-            memcpy(&buf[o.m_b1[kind] + b * 4 * C], S(nm), 4 * C * sizeof(float));
+            buf.raw(o.m_b1[kind] + b * 4 * C, 4 * C, S(nm));
             snprintf(nm, sizeof nm, "mask_decoder.%s.%d.2.weight", kinds[kind], b);
             const int rows = 4 * kSub[b];
             {
@@ -264,14 +240,14 @@ int BsrnnFamily::pack_weights(fe_handle* h, const std::vector<float>& blob, std:
                         buf[o.m_w2[kind] + ((size_t)(k / 4) * R + row0 + r) * 4 + (k & 3)] = w2[r * 4 * C + k];
             }
             snprintf(nm, sizeof nm, "mask_decoder.%s.%d.2.bias", kinds[kind], b);
-            memcpy(&buf[o.m_b2[kind] + row0], S(nm), rows * sizeof(float));
+            buf.raw(o.m_b2[kind] + row0, rows, S(nm));
             row0 += rows;
         }
     }
     {   // index tables (ints stored in the float buffer): band of a layer-2 row; a bin's first value row and 2*sub of its band
-        o.row_band = alloc(R);
-        o.bin_row = alloc(257);
-        o.bin_2sub = alloc(257);
+        o.row_band = buf.alloc(R);
+        o.bin_row = buf.alloc(257);
+        o.bin_2sub = buf.alloc(257);
         int row0 = 0, f0 = 0;
         for (int b = 0; b < 31; ++b) {
             for (int r = 0; r < 4 * kSub[b]; ++r) { const int v = b; memcpy(&buf[o.row_band + row0 + r], &v, 4); }
@@ -284,45 +260,33 @@ int BsrnnFamily::pack_weights(fe_handle* h, const std::vector<float>& blob, std:
             f0 += kSub[b];
         }
     }
-    o.window = alloc(h->window.size()); memcpy(&buf[o.window], h->window.data(), h->window.size() * sizeof(float));
-    o.window_istft = alloc(h->window_istft.size()); memcpy(&buf[o.window_istft], h->window_istft.data(), h->window_istft.size() * sizeof(float));
-    o.twiddle = alloc(h->twiddle.size()); memcpy(&buf[o.twiddle], h->twiddle.data(), h->twiddle.size() * sizeof(float));
+    o.window = buf.alloc(h->window.size()); o.window_istft = buf.alloc(h->window_istft.size()); o.twiddle = buf.alloc(h->twiddle.size());
+    pack_stft_tables(buf, h, o.window, o.window_istft, o.twiddle);
     if (C == 16) {
         // r5: the role-split PART 1's copies, regrouped from the sections packed above for 16-byte fetches (see BOffsets)
         const int KSC = C / 4, KSH = HH / 4, KS1 = KSC + KSH, NCT = HH / 16;
         for (int l = 0; l < L; ++l) {
-            o.ov_t[l] = alloc((size_t)NCT * 4 * (KS1 / 4) * 256);
-            for (int ct = 0; ct < NCT; ++ct)
-                for (int g = 0; g < 4; ++g)
-                    for (int q = 0; q < KS1 / 4; ++q)
-                        for (int lane = 0; lane < 64; ++lane)
-                            for (int j = 0; j < 4; ++j)
-                                buf[o.ov_t[l] + (((size_t)(ct * 4 + g) * (KS1 / 4) + q) * 64 + lane) * 4 + j] = buf[o.t_w[l] + ((size_t)(g * NCT + ct) * KS1 + 4 * q + j) * 64 + lane];
-            auto regroup = [&](int src, int ks_total) {          // one column tile's [ks][lane] -> [ks / 4][lane][4]
-                const int off = alloc((size_t)ks_total * 64);
-                for (int q = 0; q < ks_total / 4; ++q)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int j = 0; j < 4; ++j) buf[off + ((size_t)q * 64 + lane) * 4 + j] = buf[src + (size_t)(4 * q + j) * 64 + lane];
-                return off;
-            };
-            o.ov_tx[l] = alloc((size_t)NCT * 4 * 16 * C);
+            o.ov_t[l] = buf.alloc((size_t)NCT * 4 * KS1 * 64);       // tile ct * 4 + g <- the time LSTM's column tile g * NCT + ct
+            buf.regroup_k4(o.ov_t[l], o.t_w[l], NCT * 4, KS1, 0, KS1, [&](int t) { return (t % 4) * NCT + t / 4; });
+            o.ov_tx[l] = buf.alloc((size_t)NCT * 4 * 16 * C);
             for (int ct = 0; ct < NCT; ++ct)
                 for (int g = 0; g < 4; ++g)
                     for (int r = 0; r < 16; ++r)
                         for (int ch = 0; ch < C; ++ch)
                             buf[o.ov_tx[l] + (((size_t)(ct * 4 + g) * 16 + r) * C) + ch] = buf[o.t_w[l] + ((size_t)(g * NCT + ct) * KS1 + ch / 4) * 64 + (ch % 4) * 16 + r];
-            o.ov_f1t[l] = alloc((size_t)C * HH);
+            o.ov_f1t[l] = buf.alloc((size_t)C * HH);
             for (int ch = 0; ch < C; ++ch)
                 for (int un = 0; un < HH; ++un) buf[o.ov_f1t[l] + (size_t)ch * HH + un] = buf[o.tfc_w[l] + (size_t)(un / 4) * 64 + (un % 4) * 16 + ch];
-            o.ov_f2[l] = regroup(o.ffc_w[l], 2 * KSH);
+            o.ov_f2[l] = buf.alloc((size_t)2 * KSH * 64);
+            buf.regroup_k4(o.ov_f2[l], o.ffc_w[l], 1, 2 * KSH, 0, 2 * KSH);
             for (int d = 0; d < 2; ++d) {
                 // row-major for the transposed chains: W[n][ch] = fragment (tile n / 16, k-step ch / 4) lane (ch % 4) * 16 + n % 16
-                o.ov_ipt[l][d] = alloc((size_t)G4 * C);
+                o.ov_ipt[l][d] = buf.alloc((size_t)G4 * C);
                 for (int n = 0; n < G4; ++n)
                     for (int ch = 0; ch < C; ++ch)
                         buf[o.ov_ipt[l][d] + (size_t)n * C + ch] = buf[o.f_wih[l][d] + ((size_t)(n / 16) * KSC + ch / 4) * 64 + (ch % 4) * 16 + n % 16];
                 // W_hh: lane = half * 32 + unit holds gate rows (half, 2 + half) of its unit; source [k][4 u + gate] (register shapes, NTD = 128)
-                o.ov_hh[l][d] = alloc((size_t)2 * (HH / 4) * 256);
+                o.ov_hh[l][d] = buf.alloc((size_t)2 * (HH / 4) * 256);
                 for (int rs = 0; rs < 2; ++rs)
                     for (int q = 0; q < HH / 4; ++q)
                         for (int lane = 0; lane < 64; ++lane)
@@ -335,16 +299,13 @@ int BsrnnFamily::pack_weights(fe_handle* h, const std::vector<float>& blob, std:
     }
     {   // the matrix-core DFT's constant operands (r5: the role-split PART 1 runs the STFT on them), N = 512: N1 = 16, KC = 8, MT = 1
         const int N1 = h->cfg.n_fft / 32, KC = N1 / 2, MT = N1 / 16;
-        o.dft1 = alloc(2 * 2 * 8 * 64); o.dft2 = alloc((size_t)2 * KC * 64); o.dft3 = alloc((size_t)2 * MT * KC * 64); o.dft4 = alloc(2 * 2 * 8 * 64);
-        Packer p;
-        p.buf.swap(buf);
-        pack_dft_constants(p, h->cfg.n_fft, o.dft1, o.dft2, o.dft3, o.dft4);
-        p.buf.swap(buf);
+        o.dft1 = buf.alloc(2 * 2 * 8 * 64); o.dft2 = buf.alloc((size_t)2 * KC * 64); o.dft3 = buf.alloc((size_t)2 * MT * KC * 64); o.dft4 = buf.alloc(2 * 2 * 8 * 64);
+        pack_dft_constants(buf, h->cfg.n_fft, o.dft1, o.dft2, o.dft3, o.dft4);
     }
     o.total = (int)((buf.size() + 63) & ~(size_t)63);
     h->packed_floats = o.total;
-    buf.resize(o.total, 0.0f);
-    *out = std::move(buf);
+    buf.v.resize(o.total, 0.0f);
+    *out = std::move(buf.v);
     return FE_OK;
 }
 

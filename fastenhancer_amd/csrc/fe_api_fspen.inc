@@ -24,7 +24,7 @@ struct FspenFamily {
     static size_t xp_floats(const fe_handle*) { return 0; }
     static Args args(fe_handle* h, int B, int T);
     static int create(const fe_config* cfg, fe_handle** out);
-    static int pack_weights(fe_handle* h, const std::vector<float>& blob, std::vector<float>* out);
+    static int pack_weights(fe_handle* h, const Blob& S, std::vector<float>* out);
     static int ensure_sb(fe_handle* h, int B);
     static int launch(fe_handle* h, const Args& a, void* stream);
     static const char* stage_name(const fe_handle*, int idx);
@@ -101,12 +101,11 @@ int FspenFamily::create(const fe_config* cfg, fe_handle** out) {
 }
 
 // k-major repack of the fused weights at the compile-time offsets of fe::FPk (fspen_kernels.hip.h)
-int FspenFamily::pack_weights(fe_handle* h, const std::vector<float>& blob, std::vector<float>* out) {
+int FspenFamily::pack_weights(fe_handle* h, const Blob& S, std::vector<float>* out) {
     using P = fe::FPk;
-    std::vector<float> buf(P::TOTAL, 0.0f);
-    auto S = [&](const std::string& n) { return sec(h, blob, n); };
+    fe::frag::Buffer buf(P::TOTAL);
     char nm[160];
-    for (int i = 0; i < 512; ++i) { buf[P::WINDOW + i] = h->window[i]; buf[P::WINDOW_I + i] = h->window_istft[i]; buf[P::TW + i] = h->twiddle[i]; }
+    pack_stft_tables(buf, h, P::WINDOW, P::WINDOW_I, P::TW);
     for (int i = 0, row = 0; i < 5; row += kSeK[i], ++i) {
         snprintf(nm, sizeof nm, "subband_encoder.conv%d.0.weight", i + 1);
         const float* w = S(nm);                                       // (32, 1, K)
@@ -176,10 +175,15 @@ int FspenFamily::pack_weights(fe_handle* h, const std::vector<float>& blob, std:
             for (int c = 0; c < 16; ++c) { for (int k = 0; k < 16; ++k) buf[Gb + P::G_FC_W + k * 16 + c] = fw[c * 16 + k]; buf[Gb + P::G_FC_B + c] = fb[c]; }
         }
     }
-    {   // stream-batched DPE (fspen_sb_kernels.hip.h): A-operand fragments - lane (li = row, lg) of k-step ks holds W[row][4 (ks % 4) + lg];
+    {   // stream-batched DPE (fspen_sb_kernels.hip.h): A-operand fragments (fe_fragments.h, plain order) and the tiles' per-row biases;
         // the r / z rows and biases carry -log2 e, the n rows 2 log2 e (sigma / tanh as one exp2 + rcp of the pre-scaled value)
         using Q = fe::FSbPk;
         const float kRZ = -1.4426950408889634f, kN = 2.8853900817779268f;
+        auto feat = [](int row) { return 4 * (row & 3) + (row >> 2); };        // output row 4 lg + r  <->  feature 4 r + lg
+        // GRU bias of (unit u, gate g of r, z, n_x, n_h)
+        auto gbias = [&](const float* bi, const float* bh, int u, int g) {
+            return g == 0 ? (bi[u] + bh[u]) * kRZ : g == 1 ? (bi[16 + u] + bh[16 + u]) * kRZ : g == 2 ? bi[32 + u] * kN : bh[32 + u] * kN;
+        };
         for (int b = 0; b < 3; ++b) {
             const int D = P::SB + b * Q::D_SIZE;
             snprintf(nm, sizeof nm, "dpe_blocks.%d.", b);
@@ -192,37 +196,24 @@ int FspenFamily::pack_weights(fe_handle* h, const std::vector<float>& blob, std:
                 const float* bh = S(p + "intra_rnn.bias_hh_l0" + sfx);
                 for (int q = 0; q < 4; ++q) {
                     const int wave = d * 4 + q;
-                    for (int ks = 0; ks < 8; ++ks)
-                        for (int lane = 0; lane < 64; ++lane) {
-                            const int li = lane & 15, lg = lane >> 4, j = li >> 2, g = li & 3, u = 4 * q + j, k = 4 * (ks & 3) + lg;
-                            float v = 0.0f;      // row (unit u, gate g of r, z, n_x, n_h): the x half of n_x, the h half of n_h
-                            if (ks < 4) { if (g == 0) v = wi[u * 16 + k] * kRZ; else if (g == 1) v = wi[(16 + u) * 16 + k] * kRZ; else if (g == 2) v = wi[(32 + u) * 16 + k] * kN; }
-                            else { if (g == 0) v = wh[u * 16 + k] * kRZ; else if (g == 1) v = wh[(16 + u) * 16 + k] * kRZ; else if (g == 3) v = wh[(32 + u) * 16 + k] * kN; }
-                            buf[D + Q::I_W + (wave * 8 + ks) * 64 + lane] = v;
-                        }
-                    for (int lg = 0; lg < 4; ++lg) {
-                        const int u = 4 * q + lg;
-                        float* dst = &buf[D + Q::I_B + (wave * 4 + lg) * 4];
-                        dst[0] = (bi[u] + bh[u]) * kRZ; dst[1] = (bi[16 + u] + bh[16 + u]) * kRZ; dst[2] = bi[32 + u] * kN; dst[3] = bh[32 + u] * kN;
-                    }
+                    // row 4 j + g = (unit u = 4 q + j, gate g of r, z, n_x, n_h): k < 16 the x half (n_h: zero), k >= 16 the h half (n_x: zero)
+                    buf.tiles(D + Q::I_W + wave * 8 * 64, 1, 8, [&](int, int row, int k) {
+                        const int u = 4 * q + (row >> 2), g = row & 3;
+                        if (g == (k < 16 ? 3 : 2)) return 0.0f;
+                        return (k < 16 ? wi : wh)[((g < 2 ? g : 2) * 16 + u) * 16 + k % 16] * (g < 2 ? kRZ : kN);
+                    });
+                    buf.rows(D + Q::I_B + wave * 16, 1, [&](int, int row) { return gbias(bi, bh, 4 * q + (row >> 2), row & 3); });
                 }
             }
-            auto feat = [](int li) { return 4 * (li & 3) + (li >> 2); };        // output row li = 4 lg + r  <->  feature 4 r + lg
             {
                 const float* w = S(p + "intra_fc.weight");                      // (16, 32)
                 const float* bb = S(p + "intra_fc.bias");
                 const float* lw = S(p + "intra_ln.weight");
                 const float* lb = S(p + "intra_ln.bias");
-                for (int ks = 0; ks < 8; ++ks)
-                    for (int lane = 0; lane < 64; ++lane) buf[D + Q::FC_W + ks * 64 + lane] = w[feat(lane & 15) * 32 + 16 * (ks >> 2) + 4 * (ks & 3) + (lane >> 4)];
-                for (int lg = 0; lg < 4; ++lg)
-                    for (int r = 0; r < 4; ++r) {
-                        buf[D + Q::FC_B + lg * 4 + r] = bb[4 * r + lg];
-                        for (int f = 0; f < 32; ++f) {
-                            buf[D + Q::LN_W + f * 16 + lg * 4 + r] = lw[f * 16 + 4 * r + lg];
-                            buf[D + Q::LN_B + f * 16 + lg * 4 + r] = lb[f * 16 + 4 * r + lg];
-                        }
-                    }
+                buf.tiles(D + Q::FC_W, 1, 8, [&](int, int row, int k) { return w[feat(row) * 32 + k]; });
+                buf.rows(D + Q::FC_B, 1, [&](int, int row) { return bb[feat(row)]; });
+                buf.rows(D + Q::LN_W, 32, [&](int f, int row) { return lw[f * 16 + feat(row)]; });
+                buf.rows(D + Q::LN_B, 32, [&](int f, int row) { return lb[f * 16 + feat(row)]; });
             }
             for (int g = 0; g < 8; ++g) {
                 const int Gb = D + Q::GRP + g * Q::G_SIZE;
@@ -233,29 +224,17 @@ int FspenFamily::pack_weights(fe_handle* h, const std::vector<float>& blob, std:
                 const float* bh = S(q + ".bias_hh_l0");
                 const float* fw = S(p + "inter_rnn.inter_fc." + std::to_string(g) + ".weight");
                 const float* fb = S(p + "inter_rnn.inter_fc." + std::to_string(g) + ".bias");
-                for (int i = 0; i < 24; ++i) {
-                    const int gate = i < 8 ? 0 : (i < 16 ? 1 : 2), ksl = i < 16 ? (i & 7) : i - 16;      // ksl < 4: x half, else h half
-                    const float* src = ksl < 4 ? wi : wh;
-                    for (int lane = 0; lane < 64; ++lane)
-                        buf[Gb + Q::G_W + i * 64 + lane] = src[(gate * 16 + feat(lane & 15)) * 16 + 4 * (ksl & 3) + (lane >> 4)] * (gate < 2 ? kRZ : kN);
-                }
-                for (int lg = 0; lg < 4; ++lg)
-                    for (int r = 0; r < 4; ++r) {
-                        const int u = 4 * r + lg;
-                        buf[Gb + Q::G_B + 0 + lg * 4 + r] = (bi[u] + bh[u]) * kRZ;
-                        buf[Gb + Q::G_B + 16 + lg * 4 + r] = (bi[16 + u] + bh[16 + u]) * kRZ;
-                        buf[Gb + Q::G_B + 32 + lg * 4 + r] = bi[32 + u] * kN;
-                        buf[Gb + Q::G_B + 48 + lg * 4 + r] = bh[32 + u] * kN;
-                        buf[Gb + Q::G_FCB + lg * 4 + r] = fb[u];
-                    }
-                for (int ks = 0; ks < 4; ++ks)
-                    for (int lane = 0; lane < 64; ++lane) buf[Gb + Q::G_FCW + ks * 64 + lane] = fw[feat(lane & 15) * 16 + 4 * ks + (lane >> 4)];
+                // 24 k-steps: r (x | h), z (x | h), n_x, n_h
+                buf.tiles(Gb + Q::G_W, 1, 24, [&](int, int row, int k) {
+                    const int i = k / 4, gate = i < 8 ? 0 : (i < 16 ? 1 : 2), ksl = i < 16 ? (i & 7) : i - 16;      // ksl < 4: x half, else h half
+                    return (ksl < 4 ? wi : wh)[(gate * 16 + feat(row)) * 16 + 4 * (ksl & 3) + k % 4] * (gate < 2 ? kRZ : kN);
+                });
+                buf.rows(Gb + Q::G_B, 4, [&](int gt, int row) { return gbias(bi, bh, feat(row), gt); });
+                buf.rows(Gb + Q::G_FCB, 1, [&](int, int row) { return fb[feat(row)]; });
+                buf.tiles(Gb + Q::G_FCW, 1, 4, [&](int, int row, int k) { return fw[feat(row) * 16 + k]; });
             }
         }
-    }
-    {   // stream-batched fullband_encoder_post, feature merge / split, fullband_decoder.0's 1x1 (fspen_sb_kernels.hip.h)
-        using Q = fe::FSbPk;
-        auto feat = [](int li) { return 4 * (li & 3) + (li >> 2); };
+        // stream-batched fullband_encoder_post, feature merge / split, fullband_decoder.0's 1x1 (fspen_sb_kernels.hip.h)
         const float* wpo = S("fullband_encoder_post.weight");  // (32, 32, 1)
         const float* wf2 = S("fullband_encoder.2.0.weight");   // Conv1d (32, 16, 6)
         const float* bf2 = S("fullband_encoder.2.0.bias");
@@ -269,44 +248,30 @@ int FspenFamily::pack_weights(fe_handle* h, const std::vector<float>& blob, std:
         const float* wd1 = S("fullband_decoder.1.0.weight");  // (16, 32, 1)
         const float* wd1t = S("fullband_decoder.1.1.weight"); // ConvTranspose1d (16 in, 4 out, 8)
         const float* bd1t = S("fullband_decoder.1.1.bias");
-        for (int row = 0; row < 16; ++row) buf[P::SB + Q::FD1T_B + row] = row < 8 ? bd1t[row & 3] : 0.0f;
         const float* wdt = S("fullband_decoder.0.1.weight");  // ConvTranspose1d (32 in, 16 out, 6)
-        const float* bdt = S("fullband_decoder.0.1.bias");
-        for (int o = 0; o < 16; ++o) buf[P::SB + Q::FD0T_B + o] = bdt[o];
-        for (int lane = 0; lane < 64; ++lane) {
-            const int li = lane & 15, lg = lane >> 4;
-            for (int ot = 0; ot < 2; ++ot)
-                for (int ks = 0; ks < 24; ++ks) buf[P::SB + Q::FE2_W + (ot * 24 + ks) * 64 + lane] = wf2[((16 * ot + feat(li)) * 16 + 4 * (ks & 3) + lg) * 6 + (ks >> 2)];
-            for (int ot = 0; ot < 2; ++ot)
-                for (int ks = 0; ks < 8; ++ks) buf[P::SB + Q::POST_W + (ot * 8 + ks) * 64 + lane] = wpo[(16 * ot + feat(li)) * 32 + 4 * ks + lg];
-            for (int jt = 0; jt < 2; ++jt)
-                for (int ks = 0; ks < 16; ++ks) {
-                    const int i = ks < 8 ? 4 * ks + lg : 32 + 16 * ((ks - 8) >> 2) + 4 * lg + ((ks - 8) & 3);
-                    buf[P::SB + Q::MG1_W + (jt * 16 + ks) * 64 + lane] = w1[(16 * jt + feat(li)) * 64 + i];
-                }
-            for (int ks = 0; ks < 8; ++ks) buf[P::SB + Q::MG2_W + ks * 64 + lane] = w2[feat(li) * 32 + 4 * ks + lg];
-            for (int ct = 0; ct < 2; ++ct)
-                for (int ks = 0; ks < 4; ++ks) buf[P::SB + Q::SP1_W + (ct * 4 + ks) * 64 + lane] = s1[(16 * ct + feat(li)) * 16 + 4 * ks + lg];
-            for (int jt = 0; jt < 4; ++jt)
-                for (int ks = 0; ks < 8; ++ks) buf[P::SB + Q::SP2_W + (jt * 8 + ks) * 64 + lane] = s2[(16 * jt + (jt < 2 ? feat(li) : li)) * 32 + 4 * ks + lg];
-            for (int ot = 0; ot < 2; ++ot)      // (rows 4 lg + r <-> output 4 r + lg: its output is the next product's B operand, stored to LDS)
-                for (int ks = 0; ks < 16; ++ks) buf[P::SB + Q::FD0_W + (ot * 16 + ks) * 64 + lane] = wd0[(16 * ot + feat(li)) * 64 + (ks < 8 ? 4 * ks + lg : 32 + 4 * (ks - 8) + lg)];
-            for (int par = 0; par < 2; ++par)
-                for (int t = 0; t < 3; ++t)
-                    for (int ks = 0; ks < 8; ++ks) buf[P::SB + Q::FD0T_W + ((par * 3 + t) * 8 + ks) * 64 + lane] = wdt[((4 * ks + lg) * 16 + li) * 6 + par + 2 * t];
-            for (int ks = 0; ks < 8; ++ks) buf[P::SB + Q::FD1_W + ks * 64 + lane] = wd1[feat(li) * 32 + (ks < 4 ? 4 * lg + ks : 16 + 4 * (ks - 4) + lg)];
-            for (int j = 0; j < 5; ++j)
-                for (int cq = 0; cq < 4; ++cq) {
-                    const int par = li >> 2, o = li & 3, k = (par ? 8 : 7) - 2 * j;      // output positions 2 m + par <- input position m - 2 + j
-                    buf[P::SB + Q::FD1T_W + (j * 4 + cq) * 64 + lane] = (li < 8 && k >= 0 && k < 8) ? wd1t[((4 * cq + lg) * 4 + o) * 8 + k] : 0.0f;
-                }
-        }
-        for (int lg = 0; lg < 4; ++lg)
-            for (int r = 0; r < 4; ++r) {
-                buf[P::SB + Q::MG2_B + lg * 4 + r] = b2[4 * r + lg];
-                for (int ot = 0; ot < 2; ++ot) buf[P::SB + Q::FE2_B + ot * 16 + lg * 4 + r] = bf2[16 * ot + 4 * r + lg];
-                for (int ct = 0; ct < 2; ++ct) buf[P::SB + Q::SP1_B + ct * 16 + lg * 4 + r] = sb1[16 * ct + 4 * r + lg];
-            }
+        const int SB = P::SB;
+        buf.rows(SB + Q::FD1T_B, 1, [&](int, int row) { return row < 8 ? bd1t[row & 3] : 0.0f; });
+        buf.raw(SB + Q::FD0T_B, 16, S("fullband_decoder.0.1.bias"));
+        buf.tiles(SB + Q::FE2_W, 2, 24, [&](int ot, int row, int k) { return wf2[((16 * ot + feat(row)) * 16 + k % 16) * 6 + k / 16]; });      // k = tap * 16 + channel
+        buf.tiles(SB + Q::POST_W, 2, 8, [&](int ot, int row, int k) { return wpo[(16 * ot + feat(row)) * 32 + k]; });
+        buf.tiles(SB + Q::MG1_W, 2, 16, [&](int jt, int row, int k) {
+            const int ks = k / 4, lg = k % 4, i = ks < 8 ? k : 32 + 16 * ((ks - 8) >> 2) + 4 * lg + ((ks - 8) & 3);
+            return w1[(16 * jt + feat(row)) * 64 + i];
+        });
+        buf.tiles(SB + Q::MG2_W, 1, 8, [&](int, int row, int k) { return w2[feat(row) * 32 + k]; });
+        buf.tiles(SB + Q::SP1_W, 2, 4, [&](int ct, int row, int k) { return s1[(16 * ct + feat(row)) * 16 + k]; });
+        buf.tiles(SB + Q::SP2_W, 4, 8, [&](int jt, int row, int k) { return s2[(16 * jt + (jt < 2 ? feat(row) : row)) * 32 + k]; });
+        // (rows 4 lg + r <-> output 4 r + lg: its output is the next product's B operand, stored to LDS)
+        buf.tiles(SB + Q::FD0_W, 2, 16, [&](int ot, int row, int k) { return wd0[(16 * ot + feat(row)) * 64 + k]; });
+        buf.tiles(SB + Q::FD0T_W, 6, 8, [&](int t, int row, int k) { return wdt[(k * 16 + row) * 6 + t / 3 + 2 * (t % 3)]; });      // tile = parity * 3 + tap pair
+        buf.tiles(SB + Q::FD1_W, 1, 8, [&](int, int row, int k) { const int ks = k / 4, lg = k % 4; return wd1[feat(row) * 32 + (ks < 4 ? 4 * lg + ks : 16 + 4 * (ks - 4) + lg)]; });
+        buf.tiles(SB + Q::FD1T_W, 5, 4, [&](int j, int row, int k) {
+            const int par = row >> 2, o = row & 3, tap = (par ? 8 : 7) - 2 * j;      // output positions 2 m + par <- input position m - 2 + j
+            return (row < 8 && tap >= 0 && tap < 8) ? wd1t[(k * 4 + o) * 8 + tap] : 0.0f;
+        });
+        buf.rows(SB + Q::MG2_B, 1, [&](int, int row) { return b2[feat(row)]; });
+        buf.rows(SB + Q::FE2_B, 2, [&](int ot, int row) { return bf2[16 * ot + feat(row)]; });
+        buf.rows(SB + Q::SP1_B, 2, [&](int ct, int row) { return sb1[16 * ct + feat(row)]; });
     }
     conv("feature_split.0", 32, 16, 1, P::SP1_W, P::SP1_B);
     {   // feature_split.1 Linear (64 out j, 32 in f) -> [f][j]
@@ -342,7 +307,7 @@ int FspenFamily::pack_weights(fe_handle* h, const std::vector<float>& blob, std:
     convt("fullband_decoder.1.1", 16, 4, 8, P::FD1_T, P::FD1_B);
     conv("fullband_decoder.2.0", 4, 8, 1, P::FD2_W, -1);
     convt("fullband_decoder.2.1", 4, 2, 6, P::FD2_T, P::FD2_B);
-    *out = std::move(buf);
+    *out = std::move(buf.v);
     return FE_OK;
 }
 

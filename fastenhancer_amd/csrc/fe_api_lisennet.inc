@@ -27,7 +27,7 @@ struct LisennetFamily {
     static size_t xp_floats(const fe_handle*) { return 0; }
     static Args args(fe_handle* h, int B, int T);
     static int create(const fe_config* cfg, fe_handle** out);
-    static int pack_weights(fe_handle* h, const std::vector<float>& blob, std::vector<float>* out);
+    static int pack_weights(fe_handle* h, const Blob& S, std::vector<float>* out);
     static int ensure_sb(fe_handle* h, int B);
     static int launch(fe_handle* h, const Args& a, void* stream);
     static const char* stage_name(const fe_handle*, int idx);
@@ -116,22 +116,15 @@ int LisennetFamily::create(const fe_config* cfg, fe_handle** out) {
 }
 
 // r6: the stream-batched middle's operands (lisennet_sb_kernels.hip.h, fe::LSbPk behind fe::LPk::TOTAL).  A fragments of the TRANSPOSED products in
-// "k4" order: dst[((tile * NQ + quad) * 64 + lane) * 4 + j] = A[row = lane % 16][k-step 4 quad + j, lane group lane / 16] - what that k index means
-// (source / tap / channel group of a convolution, channel 4 lg + j, hidden unit ...) is each layer's own choice below and the kernel's B operand follows it.
-void pack_weights_lisennet_sb(fe_handle* h, const std::vector<float>& blob, std::vector<float>& buf) {
+// k4 order (fe_fragments.h), written by fn(tile, row, quad m, j, lane group lgk) for k-step 4 m + j: what that k index means (source / tap /
+// channel group of a convolution, channel 4 lg + j, hidden unit ...) is each layer's own choice below and the kernel's B operand follows it.
+void pack_weights_lisennet_sb(const Blob& S, fe::frag::Buffer& buf) {
     using Q = fe::LSbPk;
     const int SB = fe::LPk::TOTAL;
-    auto S = [&](const std::string& n) { return sec(h, blob, n); };
-    auto packA = [&](int dst, int NT, int NQ, const std::function<float(int, int, int, int, int)>& fn) {
-        for (int t = 0; t < NT; ++t)
-            for (int m = 0; m < NQ; ++m)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 4; ++j) buf[SB + dst + ((size_t)(t * NQ + m) * 64 + lane) * 4 + j] = fn(t, lane % 16, m, j, lane / 16);
+    auto packA = [&](int dst, int NT, int NQ, auto&& fn) {
+        buf.tiles<fe::frag::kK4>(SB + dst, NT, 4 * NQ, [&](int t, int row, int k) { return fn(t, row, k / 16, (k / 4) % 4, k % 4); });
     };
-    auto packR = [&](int dst, int NT, const std::function<float(int, int)>& fn) {          // per-row values [tile][16]: a lane reads its rows 4 lg .. 4 lg + 3
-        for (int t = 0; t < NT; ++t)
-            for (int row = 0; row < 16; ++row) buf[SB + dst + t * 16 + row] = fn(t, row);
-    };
+    auto packR = [&](int dst, int NT, auto&& fn) { buf.rows(SB + dst, NT, fn); };          // per-row values [tile][16]
     const double kL2E = 1.4426950408889634;
     const float sR = (float)-kL2E, sN = (float)(2.0 * kL2E);       // sigma(v) = rcp(1 + exp2(sR v)), tanh(v) = 1 - 2 rcp(1 + exp2(sN v))
     // convolutions: k-step j of quad m, lane group lgk <-> pair 4 m + lgk = ((source s, tap df), channel group g), channel 4 g + j
@@ -175,7 +168,7 @@ void pack_weights_lisennet_sb(fe_handle* h, const std::vector<float>& blob, std:
     dsconv("encoder.conv_4.high_conv", 12, 16, 5, 8, Q::C4_HI, Q::C4_BH);
     ds_norm("encoder.conv_4", 16, 32, Q::C4_G, Q::C4_BE, Q::C4_P);
     // USConv (O, 2 CX, 1, 3) over cat(x, skip): source 0 = x, 1 = skip; oc(tile, row) = the conv channel a row computes (-1: idle row)
-    auto usconv = [&](const std::string& key, int CX, int NT, int NQ, int dst_w, int dst_b, const std::function<int(int, int)>& oc) {
+    auto usconv = [&](const std::string& key, int CX, int NT, int NQ, int dst_w, int dst_b, auto&& oc) {
         const float* w = S(key + ".weight");
         const float* b = S(key + ".bias");
         const int G = CX / 4, NPAIR = 2 * 3 * G, cin = 2 * CX;
@@ -307,12 +300,11 @@ void pack_weights_lisennet_sb(fe_handle* h, const std::vector<float>& blob, std:
 }
 
 // k-major repack at the compile-time offsets of fe::LPk (lisennet_kernels.hip.h)
-int LisennetFamily::pack_weights(fe_handle* h, const std::vector<float>& blob, std::vector<float>* out) {
+int LisennetFamily::pack_weights(fe_handle* h, const Blob& S, std::vector<float>* out) {
     using P = fe::LPk;
-    std::vector<float> buf(P::TOTAL + fe::LSbPk::TOTAL, 0.0f);
-    auto S = [&](const std::string& n) { return sec(h, blob, n); };
-    auto copy = [&](const std::string& n, int dst, int cnt) { const float* w = S(n); for (int i = 0; i < cnt; ++i) buf[dst + i] = w[i]; };
-    for (int i = 0; i < 512; ++i) { buf[P::WINDOW + i] = h->window[i]; buf[P::WINDOW_I + i] = h->window_istft[i]; buf[P::TW + i] = h->twiddle[i]; }
+    fe::frag::Buffer buf(P::TOTAL + fe::LSbPk::TOTAL);
+    auto copy = [&](const std::string& n, int dst, int cnt) { buf.raw(dst, cnt, S(n)); };
+    pack_stft_tables(buf, h, P::WINDOW, P::WINDOW_I, P::TW);
     {
         const float* w = S("encoder.conv_1.0.weight");            // (4, 3, 1, 1) -> [c][o]
         for (int o = 0; o < 4; ++o) for (int c = 0; c < 3; ++c) buf[P::C1_W + c * 4 + o] = w[o * 3 + c];
@@ -414,8 +406,8 @@ int LisennetFamily::pack_weights(fe_handle* h, const std::vector<float>& blob, s
         copy("decoder.mask_conv.3.bias", P::M3_B, 2);
         copy("decoder.lsigmoid.slope", P::SLOPE, 257);
     }
-    pack_weights_lisennet_sb(h, blob, buf);
-    *out = std::move(buf);
+    pack_weights_lisennet_sb(S, buf);
+    *out = std::move(buf.v);
     return FE_OK;
 }
 

@@ -131,6 +131,15 @@ class Engine:
             _lib.check(self.lib.fe_load_weights(self._h, _ptr(blob_dev), blob_dev.numel(), _stream(self.device)), "fe_load_weights")
         self.loaded = True
 
+    def pack_blob(self, blob_cpu: Tensor) -> Tensor:
+        """the buffer the kernels read, packed on the CPU from a make_blob() blob: what load_blob uploads (fe_debug_pack_weights; needs no GPU)."""
+        assert not blob_cpu.is_cuda and blob_cpu.dtype == torch.float32 and blob_cpu.is_contiguous()
+        n = c_size_t()
+        _lib.check(self.lib.fe_debug_pack_weights(self._h, _ptr(blob_cpu), blob_cpu.numel(), None, 0, byref(n)), "fe_debug_pack_weights")
+        out = torch.empty(n.value, dtype=torch.float32)
+        _lib.check(self.lib.fe_debug_pack_weights(self._h, _ptr(blob_cpu), blob_cpu.numel(), _ptr(out), out.numel(), byref(n)), "fe_debug_pack_weights")
+        return out
+
     def load_state_dict(self, state_dict: Mapping[str, Tensor], strict: bool = True):
         blob = self.make_blob(state_dict, strict=strict)
         self.load_blob(blob.to(self.device))

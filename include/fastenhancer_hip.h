@@ -423,6 +423,12 @@ int fe_profile_step(fe_handle* h, const float* wav_in_dev, size_t in_stride, flo
  * (The reference has no counterpart: PyTorch pads explicitly, models/bsrnn/model.py:136-153.) */
 int fe_debug_poison_lds(void* stream);
 
+/* Test support: the packing fe_load_weights does between its two copies, host to host - no HIP call, works without a GPU (as fe_create
+ * does).  blob_host: the fused blob (nfloats == fe_weight_floats(h)); out_host: the buffer the kernels read, *packed_floats its size.
+ * out_host == NULL reports the size only.  A null handle or blob, a wrong nfloats or a capacity below the packed size is
+ * FE_ERR_INVALID_ARG with nothing written. */
+int fe_debug_pack_weights(fe_handle* h, const float* blob_host, size_t nfloats, float* out_host, size_t capacity, size_t* packed_floats);
+
 const char* fe_last_error(void);
 const char* fe_version(void);
 /* r6: the digest of the sources this library was built from (fastenhancer_amd/build.py::source_key: csrc/* and this header).  The Python binding refuses an
