@@ -5,7 +5,7 @@ and the mask are options the kernels are compiled for per shape (Shape::EP)."""
 from __future__ import annotations
 
 import typing as tp
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Any, Dict, Optional, Sequence, Tuple
 
 # activation -> (FE_ACT_* of include/fastenhancer_hip.h, the activation_kwargs it takes with their reference defaults); `inplace` is
@@ -40,8 +40,21 @@ def _activation(activation: str, activation_kwargs: Optional[Dict[str, Any]]) ->
     return code, 0.0
 
 
+class _STFTGeometry:
+    """what every family's config derives from its n_fft / hop_size fields"""
+
+    @property
+    def F0(self) -> int:
+        return self.n_fft // 2
+
+    @property
+    def cache_len(self) -> int:
+        """samples of each of the two STFT caches"""
+        return self.n_fft - self.hop_size
+
+
 @dataclass(frozen=True)
-class FEConfig:
+class FEConfig(_STFTGeometry):
     channels: int = 64
     kernel_size: Tuple[int, ...] = (8, 3, 3)
     stride: int = 4
@@ -102,10 +115,6 @@ class FEConfig:
         return self.kernel_size_time > 1
 
     @property
-    def F0(self) -> int:
-        return self.n_fft // 2
-
-    @property
     def F1(self) -> int:
         return self.n_fft // 2 // self.stride
 
@@ -113,9 +122,16 @@ class FEConfig:
     def n_layers(self) -> int:
         return len(self.kernel_size) - 1
 
-    @property
-    def cache_len(self) -> int:
-        return self.n_fft - self.hop_size
+    def cache_shapes(self, B: int):
+        """ONNXModel.initialize_cache sized for B streams (b-major): the blocks' GRU states (model.py:614-618); time_kernel variant:
+        between the encoder's and the decoder's causal-conv frame caches (time_kernel/model.py:746-754); dptransformer variant: h_k, h_v
+        per block instead (dptransformer/model.py:194-198, 740-744); the noncausal model has no caches"""
+        if self.noncausal:
+            return []
+        if self.dpt:
+            return [(B * self.rf_freq, self.rf_heads, self.lookbehind, self.rf_channels // self.rf_heads)] * (2 * self.rf_blocks)
+        conv = [(B, self.channels, self.kernel_size_time - 1, self.F1)] * (self.n_layers if self.time_kernel else 0)
+        return conv + [(1, B * self.rf_freq, self.rf_channels)] * self.rf_blocks + conv
 
     @staticmethod
     def from_model_kwargs(
@@ -206,16 +222,14 @@ def time_kernel_config(channels: int = 64, kernel_size_freq: Sequence[int] = (8,
                                       win_size=win_size, window=window, stft_normalized=stft_normalized, mask=mask,
                                       input_compression=input_compression, weight_norm=weight_norm,
                                       normalize_final_conv=normalize_final_conv, pre_post_init=pre_post_init, resnet=False)
-    import dataclasses
-    return dataclasses.replace(base, kernel_size_time=int(kernel_size_time), final_scale_exp=(final_scale == "exp"))
+    return replace(base, kernel_size_time=int(kernel_size_time), final_scale_exp=(final_scale == "exp"))
 
 
 def noncausal_config(normalize_final_conv: bool = True, **model_kwargs) -> FEConfig:
     """yaml model_kwargs of `model: fastenhancer.noncausal` (configs/fastenhancer_dns/huge_noncausal.yaml:2-30: the default model's keys;
     defaults of models/fastenhancer/noncausal/model.py:349-368 - normalize_final_conv defaults to True there) -> FEConfig with noncausal set."""
     base = _default_options_only(FEConfig.from_model_kwargs(normalize_final_conv=normalize_final_conv, **model_kwargs), "noncausal")
-    import dataclasses
-    return dataclasses.replace(base, noncausal=True)
+    return replace(base, noncausal=True)
 
 
 def dprnn_config(channels: int = 64, kernel_size: Sequence[int] = (8, 3, 3), stride: int = 4, dprnn_kwargs: Optional[Dict[str, Any]] = None,
@@ -241,8 +255,7 @@ def dprnn_config(channels: int = 64, kernel_size: Sequence[int] = (8, 3, 3), str
                                       input_compression=input_compression, weight_norm=weight_norm,
                                       normalize_final_conv=normalize_final_conv, pre_post_init=pre_post_init, resnet=False)
     _default_options_only(base, "dprnn")
-    import dataclasses
-    return dataclasses.replace(base, channels_frnn=H, positional_embedding=None, final_scale_exp=(final_scale == "exp"))
+    return replace(base, channels_frnn=H, positional_embedding=None, final_scale_exp=(final_scale == "exp"))
 
 
 def ln_config(final_scale: Any = "exp", final_scale_init: str = "1/sqrt(fan_in)", **model_kwargs) -> FEConfig:
@@ -251,8 +264,7 @@ def ln_config(final_scale: Any = "exp", final_scale_init: str = "1/sqrt(fan_in)"
     if final_scale not in (True, False, "exp"):
         raise AssertionError(f"final_scale={final_scale}")
     base = FEConfig.from_model_kwargs(**model_kwargs)
-    import dataclasses
-    return dataclasses.replace(base, ln=True, final_scale_exp=(final_scale == "exp"))
+    return replace(base, ln=True, final_scale_exp=(final_scale == "exp"))
 
 
 def dpt_config(channels: int = 64, kernel_size: Sequence[int] = (8, 3, 3), stride: int = 4, dpt_kwargs: Optional[Dict[str, Any]] = None,
@@ -279,15 +291,14 @@ def dpt_config(channels: int = 64, kernel_size: Sequence[int] = (8, 3, 3), strid
                                       input_compression=input_compression, weight_norm=weight_norm,
                                       normalize_final_conv=normalize_final_conv, pre_post_init=pre_post_init, resnet=False)
     _default_options_only(base, "dptransformer")
-    import dataclasses
-    return dataclasses.replace(base, lookbehind=L, final_scale_exp=(final_scale == "exp"))
+    return replace(base, lookbehind=L, final_scale_exp=(final_scale == "exp"))
 
 
 BSRNN_SUBBANDS = (2,) + (3,) * 10 + (8,) * 12 + (16,) * 7 + (17,)     # models/bsrnn/model.py:107-111
 
 
 @dataclass(frozen=True)
-class BSRNNConfig:
+class BSRNNConfig(_STFTGeometry):
     """yaml model_kwargs of `model: bsrnn` (configs/others/bsrnn_xt.yaml:2-11; models/bsrnn/model.py:261-272)."""
     num_channels: int = 16
     num_layers: int = 6
@@ -299,20 +310,16 @@ class BSRNNConfig:
     input_compression: float = 0.3
 
     @property
-    def F0(self) -> int:
-        return self.n_fft // 2
-
-    @property
-    def cache_len(self) -> int:
-        return self.n_fft - self.hop_size
-
-    @property
     def n_bands(self) -> int:
         return len(BSRNN_SUBBANDS)
 
     @property
     def hidden(self) -> int:
         return 2 * self.num_channels
+
+    def cache_shapes(self, B: int):
+        """ONNXModel.initialize_cache (models/bsrnn/model.py:409-416, onnx form), sized for B streams: the LSTMs' (h, c) per layer"""
+        return [(B * self.n_bands, self.hidden)] * (2 * self.num_layers)
 
     @staticmethod
     def from_model_kwargs(num_channels: int = 16, num_layers: int = 6, bias: bool = True, affine: bool = True,
@@ -329,7 +336,7 @@ class BSRNNConfig:
 
 
 @dataclass(frozen=True)
-class FSPENConfig:
+class FSPENConfig(_STFTGeometry):
     """yaml model_kwargs of `model: fspen` (configs/others/fspen.yaml:2-16; models/fspen/model.py:201-212, DPEConfig :191-197).
     One architecture is compiled (the yaml's); fe_create rejects any other."""
     channels: tuple = (4, 16, 32)
@@ -346,16 +353,12 @@ class FSPENConfig:
     input_compression: float = 0.3
 
     @property
-    def F0(self) -> int:
-        return self.n_fft // 2
-
-    @property
-    def cache_len(self) -> int:
-        return self.n_fft - self.hop_size
-
-    @property
     def n_caches(self) -> int:
         return self.num_blocks * self.groups
+
+    def cache_shapes(self, B: int):
+        """ONNXModel.initialize_cache (models/fspen/model.py:293-297 -> :111-116), sized for B streams: the inter-GRU states"""
+        return [(1, B * (self.freq // self.groups), self.dpe_channels)] * self.n_caches
 
     @staticmethod
     def from_model_kwargs(channels=(4, 16, 32), kernel_size=(6, 8, 6), stride=(2, 2, 2), dpe_kwargs=None, n_fft: int = 512,
@@ -377,7 +380,7 @@ class FSPENConfig:
 
 
 @dataclass(frozen=True)
-class LiSenNetConfig:
+class LiSenNetConfig(_STFTGeometry):
     """yaml model_kwargs of `model: lisennet` (configs/others/lisennet.yaml:2-8; models/lisennet/model.py:313-323).
     One architecture is compiled (the yaml's: 16 channels, 2 blocks, n_fft 512, hop 256); fe_create rejects any other."""
     num_channels: int = 16
@@ -386,14 +389,6 @@ class LiSenNetConfig:
     hop_size: int = 256
     win_size: int = 512
     input_compression: float = 0.3
-
-    @property
-    def F0(self) -> int:
-        return self.n_fft // 2
-
-    @property
-    def cache_len(self) -> int:
-        return self.n_fft - self.hop_size
 
     @property
     def hidden(self) -> int:
@@ -422,3 +417,10 @@ class LiSenNetConfig:
         if n_fft < win_size:
             raise AssertionError(f"n_fft({n_fft}) must be bigger than win_size({win_size})")
         return LiSenNetConfig(int(num_channels), int(n_blocks), int(n_fft), int(hop_size), int(win_size), float(input_compression))
+
+
+# the reference's `model:` key (hps.model, the module path under models/) -> what builds the config from the yaml model_kwargs
+MODEL_CONFIGS = {"fastenhancer.default": FEConfig.from_model_kwargs, "fastenhancer.time_kernel": time_kernel_config,
+                 "fastenhancer.dprnn": dprnn_config, "fastenhancer.dptransformer": dpt_config, "fastenhancer.ln": ln_config,
+                 "fastenhancer.noncausal": noncausal_config, "bsrnn": BSRNNConfig.from_model_kwargs,
+                 "fspen": FSPENConfig.from_model_kwargs, "lisennet": LiSenNetConfig.from_model_kwargs}

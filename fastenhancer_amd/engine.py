@@ -13,9 +13,8 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from .config import BSRNNConfig, FEConfig, FSPENConfig, LiSenNetConfig
-from .weights import (bsrnn_expected_fused_shapes, bsrnn_fold_state_dict, check_fused, check_shapes, fold_state_dict,
-                      fspen_expected_fused_shapes, fspen_fold_state_dict, lisennet_expected_shapes, lisennet_state_dict)
+from .config import FEConfig
+from .family import family_of, views
 
 
 def _ptr(t: Optional[Tensor]) -> c_void_p:
@@ -36,44 +35,12 @@ class Engine:
         if self.device is not None and self.device.type == "cuda" and self.device.index is None and torch.cuda.is_available():
             # torch.device('cuda') != torch.device('cuda:0'): keep one spelling, the indexed one tensors report
             self.device = torch.device("cuda", torch.cuda.current_device())
+        self.family = family_of(cfg)
         c = _lib.fe_config()
-        self.is_bsrnn = isinstance(cfg, BSRNNConfig)
-        self.is_fspen = isinstance(cfg, FSPENConfig)
-        self.is_lisennet = isinstance(cfg, LiSenNetConfig)
+        c.arch = self.family.arch
         c.n_fft, c.hop_size, c.win_size = cfg.n_fft, cfg.hop_size, cfg.win_size
         c.input_compression = cfg.input_compression
-        if self.is_lisennet:
-            c.arch = _lib.FE_ARCH_LISENNET
-            c.channels, c.rf_blocks = cfg.num_channels, cfg.n_blocks
-        elif self.is_fspen:
-            c.arch = _lib.FE_ARCH_FSPEN
-            c.channels = cfg.channels[-1]
-            c.n_kernels = len(cfg.kernel_size)
-            for i, k in enumerate(cfg.kernel_size):
-                c.kernel_size[i] = k
-            if len(set(cfg.stride)) != 1 or list(cfg.channels) != [4, 16, 32]:
-                raise _lib.FEError(f"no FSPEN kernel compiled for channels={list(cfg.channels)} stride={list(cfg.stride)} "
-                                   "(configs/others/fspen.yaml is the compiled architecture)")
-            c.stride = cfg.stride[0]
-            c.rf_channels, c.rf_freq, c.rf_blocks, c.rf_heads = cfg.dpe_channels, cfg.freq, cfg.num_blocks, cfg.groups
-        elif self.is_bsrnn:
-            c.arch = _lib.FE_ARCH_BSRNN
-            c.channels, c.rf_blocks = cfg.num_channels, cfg.num_layers
-        else:
-            c.arch = _lib.FE_ARCH_FASTENHANCER
-            c.channels = cfg.channels
-            c.n_kernels = len(cfg.kernel_size)
-            for i, k in enumerate(cfg.kernel_size):
-                c.kernel_size[i] = k
-            c.stride = cfg.stride
-            c.rf_channels, c.rf_freq, c.rf_blocks, c.rf_heads = cfg.rf_channels, cfg.rf_freq, cfg.rf_blocks, cfg.rf_heads
-            c.kernel_size_time = cfg.kernel_size_time
-            c.channels_frnn = cfg.channels_frnn
-            c.lookbehind = cfg.lookbehind
-            c.ln = 1 if cfg.ln else 0
-            c.rf_eps = cfg.rf_eps
-            c.bidirectional = 1 if getattr(cfg, "noncausal", False) else 0
-            c.activation, c.activation_param, c.mask = cfg.activation, cfg.activation_param, cfg.mask
+        self.family.fill_config(c, cfg)       # (may raise: no kernel compiled for this architecture)
         self._h = c_void_p()
         if self.device is not None and self.device.type == "cuda":
             with torch.cuda.device(self.device):
@@ -105,18 +72,8 @@ class Engine:
 
     def make_blob(self, state_dict: Mapping[str, Tensor], strict: bool = True) -> Tensor:
         """reference checkpoint (training or fused form) -> flat fp32 blob on the CPU."""
-        if self.is_lisennet:
-            fused = lisennet_state_dict(state_dict, self.cfg)
-            check_shapes(fused, lisennet_expected_shapes(self.cfg), strict=strict)
-        elif self.is_fspen:
-            fused = fspen_fold_state_dict(state_dict, self.cfg)
-            check_shapes(fused, fspen_expected_fused_shapes(self.cfg), strict=strict)
-        elif self.is_bsrnn:
-            fused = bsrnn_fold_state_dict(state_dict, self.cfg)
-            check_shapes(fused, bsrnn_expected_fused_shapes(self.cfg), strict=strict)
-        else:
-            fused = fold_state_dict(state_dict, self.cfg)
-            check_fused(fused, self.cfg, strict=strict)
+        fused = self.family.fold(state_dict, self.cfg)
+        self.family.check(fused, self.cfg, strict=strict)
         blob = torch.zeros(self.weight_floats, dtype=torch.float32)
         for name, off, cnt in self.sections:
             t = fused[name].contiguous().reshape(-1)
@@ -157,80 +114,14 @@ class Engine:
         return torch.zeros(self.state_floats(B), dtype=torch.float32, device=self.device)
 
     def split_state(self, state: Tensor, B: int, head0: bool = False) -> List[Tensor]:
-        """Views of the opaque state as the reference cache list
-        [cache_stft [B,N-H], cache_istft [B,N-H], K x h [1,B*F2,C2]] (scripts/export_onnx.py:43-46)."""
-        c = self.cfg
-        L = c.cache_len
-        out = [state[:B * L].view(B, L), state[B * L:2 * B * L].view(B, L)]
-        o = 2 * B * L
-        if self.is_lisennet:       # the reference's cache list, each tensor sized for B streams (models/lisennet/model.py:380-396)
-            for shp in c.cache_shapes(B):
-                n = 1
-                for d_ in shp:
-                    n *= d_
-                out.append(state[o:o + n].view(*shp))
-                o += n
-            return out
-        if self.is_fspen:          # num_blocks * groups inter-GRU states [1, B * freq/groups, C]  (models/fspen/model.py:293-297, :111-116)
-            n = B * (c.freq // c.groups) * c.dpe_channels
-            for _ in range(c.n_caches):
-                out.append(state[o:o + n].view(1, B * (c.freq // c.groups), c.dpe_channels))
-                o += n
-            return out
-        if self.is_bsrnn:          # 2 * num_layers LSTM caches (h, c) of shape [B*31, 2C]  (models/bsrnn/model.py:409-416)
-            n = B * c.n_bands * c.hidden
-            for _ in range(2 * c.num_layers):
-                out.append(state[o:o + n].view(B * c.n_bands, c.hidden))
-                o += n
-            return out
-        if c.dpt:     # K and V caches per block, [B*F2, NH, L, hd] (models/fastenhancer/dptransformer/model.py:194-198)
-            # In the state every cache is a ring over its L slots with one head per stream (include/fastenhancer_hip.h,
-            # fe_config.lookbehind): the reference's tensors (oldest frame first) are the rings rotated left by head - copies,
-            # (gathered on the device without looking at the heads: no device-to-host sync on the per-hop path), or views
-            # when the caller knows every head is 0 (head0: a fresh state)
-            n = B * c.rf_freq * c.rf_channels * c.lookbehind
-            L, hd = c.lookbehind, c.rf_channels // c.rf_heads
-            heads = state[o + 2 * c.rf_blocks * n:o + 2 * c.rf_blocks * n + B]
-            rot = not head0
-            if rot:
-                idx = (heads.long()[:, None] + torch.arange(L, device=state.device)[None, :]) % L            # [B, L]
-                idx = idx[:, None, None, :, None].expand(B, c.rf_freq, c.rf_heads, L, hd)
-            for _ in range(2 * c.rf_blocks):
-                t = state[o:o + n].view(B, c.rf_freq, c.rf_heads, L, hd)
-                if rot:
-                    t = torch.gather(t, 3, idx)
-                out.append(t.reshape(B * c.rf_freq, c.rf_heads, L, hd))
-                o += n
-            return out
-        n = B * c.rf_freq * c.rf_channels
-        hs = []
-        for _ in range(c.rf_blocks):
-            hs.append(state[o:o + n].view(1, B * c.rf_freq, c.rf_channels))
-            o += n
-        if not c.time_kernel:
-            return out + hs
-        # time_kernel variant: the causal convs' frame caches, kept as [B, kt-1, F1, C1]; the reference tensors
-        # (B, C1, kt-1, F1) are permuted views of them, and its cache list is encoder caches, GRU states, decoder caches
-        # (models/fastenhancer/time_kernel/model.py:746-754)
-        tk = []
-        n = B * (c.kernel_size_time - 1) * c.F1 * c.channels
-        for _ in range(2 * c.n_layers):
-            tk.append(state[o:o + n].view(B, c.kernel_size_time - 1, c.F1, c.channels).permute(0, 3, 1, 2))
-            o += n
-        return out + tk[:c.n_layers] + hs + tk[c.n_layers:]
+        """Views of the opaque state as the reference cache list [cache_stft [B,N-H], cache_istft [B,N-H], *the model's caches]
+        (scripts/export_onnx.py:43-46).  The dptransformer variant's caches are copies unless head0 (family.py)."""
+        n = B * self.cfg.cache_len
+        return views(state[:2 * n], [(B, self.cfg.cache_len)] * 2) + self.family.split(self.cfg, state[2 * n:], B, head0)
 
     def model_state_order(self, caches: List[Tensor]) -> List[Tensor]:
         """the model's cache list (reference order) -> flat pieces in the order of the C ABI state (h ..., then the conv caches)"""
-        c = self.cfg
-        if not (self.is_bsrnn or self.is_fspen or self.is_lisennet) and c.dpt:      # reference-order caches = rings with head 0
-            B = caches[0].shape[0] // c.rf_freq
-            return [t.reshape(-1) for t in caches] + [torch.zeros(B, dtype=torch.float32, device=caches[0].device)]
-        if self.is_bsrnn or self.is_fspen or self.is_lisennet or not c.time_kernel:
-            return [t.reshape(-1) for t in caches]
-        nl, K = c.n_layers, c.rf_blocks
-        assert len(caches) == 2 * nl + K, f"expected {2 * nl + K} caches, got {len(caches)}"
-        conv = lambda t: t.permute(0, 2, 3, 1).reshape(-1)          # (B, C1, kt-1, F1) -> [B, kt-1, F1, C1]
-        return [t.reshape(-1) for t in caches[nl:nl + K]] + [conv(t) for t in caches[:nl]] + [conv(t) for t in caches[nl + K:]]
+        return self.family.order(self.cfg, caches)
 
     def pack_state(self, caches: List[Tensor], B: int) -> Tensor:
         pieces = [t.reshape(-1) for t in caches[:2]] + self.model_state_order(list(caches[2:]))
@@ -560,7 +451,7 @@ class Engine:
         cfg = self.cfg
         T = 1 + Tw // cfg.hop_size
         wav = torch.empty(B, cfg.hop_size * (T - 1), dtype=torch.float32, device=noisy.device)
-        spec = torch.empty(B, cfg.F0 + (1 if (self.is_bsrnn or self.is_fspen or self.is_lisennet) else 0), T, 2, dtype=torch.float32, device=noisy.device)
+        spec = torch.empty(B, self.family.spec_bins(cfg), T, 2, dtype=torch.float32, device=noisy.device)
         work = torch.empty(int(self.lib.fe_offline_work_floats(self._h, B, Tw)), dtype=torch.float32, device=noisy.device)
         self._last_work = work          # (tools/gpu_tb_check.py looks at the time-batched engine's intermediate buffers)
         with torch.cuda.device(self.device):
@@ -578,7 +469,7 @@ class Engine:
         lens = [int(t.numel()) for t in xs]
         Tw = max(lens)
         Tmax = 1 + Tw // cfg.hop_size
-        F = cfg.F0 + (1 if (self.is_bsrnn or self.is_fspen or self.is_lisennet) else 0)
+        F = self.family.spec_bins(cfg)
         batch = torch.zeros(B, Tw, dtype=torch.float32, device=dev)
         for b, t in enumerate(xs):
             batch[b, :lens[b]] = t

@@ -113,23 +113,6 @@ def build_fspen_oracle(dtype=np.float32):
     return cfg, sd, fused, fo.FSPENOracle(cfg, fused, dtype)
 
 
-def product_config(name):
-    """the HIP path's FEConfig for a MODEL_KWARGS entry (the time_kernel variant's yaml has its own keys)"""
-    from fastenhancer_amd.config import FEConfig as PCfg, dprnn_config, dpt_config, time_kernel_config
-    kw = MODEL_KWARGS[name][0]
-    if MODEL_MODULE[name] == "fastenhancer.dprnn":
-        return dprnn_config(**kw)
-    if MODEL_MODULE[name] == "fastenhancer.dptransformer":
-        return dpt_config(**kw)
-    if MODEL_MODULE[name] == "fastenhancer.ln":
-        from fastenhancer_amd.config import ln_config
-        return ln_config(**kw)
-    if MODEL_MODULE[name] == "fastenhancer.noncausal":
-        from fastenhancer_amd.config import noncausal_config
-        return noncausal_config(**kw)
-    return time_kernel_config(**kw) if MODEL_MODULE[name] == "fastenhancer.time_kernel" else PCfg.from_model_kwargs(**kw)
-
-
 # configs/others/lisennet.yaml:2-8
 LISENNET_KWARGS = _other("configs/others/lisennet.yaml", 401)
 
@@ -140,3 +123,53 @@ def build_lisennet_oracle(dtype=np.float32):
     cfg = lo.LiSenNetConfig.from_model_kwargs(kw)
     sd = lo.make_state_dict(cfg, seed)
     return cfg, sd, sd, lo.LiSenNetOracle(cfg, sd, dtype)
+
+
+# ---------------------------------------------------------------- any configuration name -> product config / engine / mirror
+CONFIG_NAMES = tuple(MODEL_KWARGS) + tuple(BSRNN_KWARGS) + ("fspen", "lisennet")
+
+def model_module(name):
+    """the reference's `model:` key of a configuration name"""
+    return MODEL_MODULE[name] if name in MODEL_MODULE else "bsrnn" if name in BSRNN_KWARGS else name
+
+
+def model_kwargs(name):
+    """(model_kwargs, sampling rate, golden seed) of a configuration name"""
+    return {**MODEL_KWARGS, **BSRNN_KWARGS, "fspen": FSPEN_KWARGS, "lisennet": LISENNET_KWARGS}[name]
+
+
+def build_named_oracle(name, dtype=np.float32):
+    """(oracle config, seeded training-form state dict, fused state dict, oracle) of a configuration name"""
+    if name in MODEL_KWARGS:
+        return build_oracle(name, dtype)
+    if name in BSRNN_KWARGS:
+        return build_bsrnn_oracle(name, dtype)
+    return {"fspen": build_fspen_oracle, "lisennet": build_lisennet_oracle}[name](dtype)
+
+
+def product_config(name):
+    """the HIP path's config of a configuration name"""
+    from fastenhancer_amd.config import MODEL_CONFIGS
+    return MODEL_CONFIGS[model_module(name)](**model_kwargs(name)[0])
+
+
+def hip_engine(name, device=None):
+    """the (unloaded) Engine of a configuration name"""
+    from fastenhancer_amd.engine import Engine
+    return Engine(product_config(name), device)
+
+
+def hip_model(name, cls="ONNXModel", device=None, load=True, sd=None):
+    """the mirror class `cls` of a configuration name, built from the yaml model_kwargs as the reference's scripts build it, on
+    `device`; load: with the seeded training-form state dict of build_*_oracle (or `sd`, when the caller has built one) loaded"""
+    import importlib
+    import torch
+    mod = importlib.import_module(f"fastenhancer_amd.models.{model_module(name)}.model")
+    m = getattr(mod, cls)(**model_kwargs(name)[0])
+    if device is not None:
+        m = m.to(device)
+    m = m.eval()
+    if load:
+        sd = build_named_oracle(name)[1] if sd is None else sd
+        m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
+    return m

@@ -23,18 +23,8 @@ WORK_HOPS = (1, 4, 37, 250)          # Tw = hops * hop + 7: from below the time 
 
 
 def make_engine(name):
-    from common import BSRNN_KWARGS, FSPEN_KWARGS, LISENNET_KWARGS, product_config
-    from fastenhancer_amd.config import BSRNNConfig, FSPENConfig, LiSenNetConfig
-    from fastenhancer_amd.engine import Engine
-    if name in BSRNN_KWARGS:
-        cfg = BSRNNConfig.from_model_kwargs(**BSRNN_KWARGS[name][0])
-    elif name == "fspen":
-        cfg = FSPENConfig.from_model_kwargs(**FSPEN_KWARGS[0])
-    elif name == "lisennet":
-        cfg = LiSenNetConfig.from_model_kwargs(**LISENNET_KWARGS[0])
-    else:
-        cfg = product_config(name)
-    return Engine(cfg, None)
+    from common import hip_engine
+    return hip_engine(name)
 
 
 def host_queries(name):

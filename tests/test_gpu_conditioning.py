@@ -12,14 +12,12 @@ stream alone with that stream's own e32 - an error confined to one stream enters
 What a cancelling norm looks like here (fastenhancer.ln's one-pass E[x^2] - mean^2, before the fix; per-hop waveform, relative rms):
 3.8e-5 at |mean| / std = 10, 1.8e-4 at 30, 1.7e-3 at 100 - it grows as the ratio squared.  Rounding of the fp32 values themselves grows
 linearly (e32: 1e-6, 4e-6, 2e-5 for FSPEN)."""
-import importlib
-
 import numpy as np
 import pytest
 import torch
 
 import conditioning as C
-from common import FSPEN_KWARGS, LISENNET_KWARGS, MODEL_KWARGS, MODEL_MODULE, rms
+from common import hip_model, rms
 from oracle.weightgen import make_input
 from test_gpu_parity import REL_TOL, TIGHT_REL, _assert_close, _dev
 
@@ -27,15 +25,7 @@ pytestmark = pytest.mark.gpu
 
 
 def _hip(family, sd, cls="ONNXModel"):
-    if family in ("fspen", "lisennet"):
-        kw = (FSPEN_KWARGS if family == "fspen" else LISENNET_KWARGS)[0]
-        mod = importlib.import_module(f"fastenhancer_amd.models.{family}.model")
-    else:
-        kw = MODEL_KWARGS[family][0]
-        mod = importlib.import_module(f"fastenhancer_amd.models.{MODEL_MODULE[family]}.model")
-    m = getattr(mod, cls)(**kw).to(_dev()).eval()
-    m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
-    return m
+    return hip_model(family, cls, _dev(), sd=sd)
 
 
 def _rel(a, b):

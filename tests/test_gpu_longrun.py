@@ -8,13 +8,11 @@ the device, sampled streams against the golden-pinned oracle in windows of 50 ho
 later window failing), and the whole run TWICE - each time on a fresh handle, from a fresh state, with NaN in every CU's LDS first
 (fe_debug_poison_lds) - bit for bit the same.
 Reference semantics: scripts/export_onnx.py:48-58 (the step), models/bsrnn/model.py:367-390, models/fastenhancer/default/model.py:620-710."""
-import importlib
-
 import numpy as np
 import pytest
 import torch
 
-from common import BSRNN_KWARGS, MODEL_KWARGS, MODEL_MODULE, build_bsrnn_oracle, build_oracle, rms
+from common import build_named_oracle, hip_model, model_kwargs, rms
 from oracle.weightgen import make_input
 
 pytestmark = pytest.mark.gpu
@@ -26,18 +24,9 @@ BOUND = {"fastenhancer": 2e-5, "bsrnn": 1e-5}
 
 
 def _fresh_model(name):
-    dev = torch.device("cuda:0")
-    if name.startswith("bsrnn"):
-        kw, sr, seed = BSRNN_KWARGS[name]
-        cfg, sd, fused, orc = build_bsrnn_oracle(name)
-        mod = importlib.import_module("fastenhancer_amd.models.bsrnn.model")
-    else:
-        kw, sr, seed = MODEL_KWARGS[name]
-        cfg, sd, fused, orc = build_oracle(name)
-        mod = importlib.import_module(f"fastenhancer_amd.models.{MODEL_MODULE[name]}.model")
-    m = mod.ONNXModel(**kw).to(dev).eval()
-    m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
-    return m, orc, cfg, fused, sr, seed
+    _, sr, seed = model_kwargs(name)
+    cfg, sd, fused, orc = build_named_oracle(name)
+    return hip_model(name, device=torch.device("cuda:0"), sd=sd), orc, cfg, fused, sr, seed
 
 
 def _oracle_run(name, orc, cfg, fused, x):
@@ -98,16 +87,6 @@ def test_long_run_at_full_batch_is_finite_exact_and_reproducible_from_poisoned_l
     assert np.array_equal(runs[0][0], runs[1][0]) and np.array_equal(runs[0][1], runs[1][1]), f"{name} B={B} {kernel}: two runs from fresh, poisoned state differ"
 
 
-def _fresh_lisennet():
-    from common import LISENNET_KWARGS, build_lisennet_oracle
-    kw, sr, seed = LISENNET_KWARGS
-    cfg, sd, _, orc = build_lisennet_oracle()
-    mod = importlib.import_module("fastenhancer_amd.models.lisennet.model")
-    m = mod.ONNXModel(**kw).to(torch.device("cuda:0")).eval()
-    m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
-    return m, orc, cfg, None, sr, seed
-
-
 @pytest.mark.parametrize("name,B,hops,want", [("lisennet", 601, 240, "lisennet_sb_kernel"), ("bsrnn_t", 2093, 64, "bsrnn_sb_layers_kernel"), ("bsrnn_s", 2829, 16, "bsrnn_sb64_layers_kernel")])
 def test_stream_batched_steps_long_run_from_poisoned_lds(name, B, hops, want):
     """r6: the stream-batched steps built this round (LiSenNet from conv_1 to the mask head - all of its caches but the phase travel through LDS staging and a carry in
@@ -119,7 +98,7 @@ def test_stream_batched_steps_long_run_from_poisoned_lds(name, B, hops, want):
     ref = sel = ref_caches = None
     window = max(4, hops // 4)
     for rep in range(2):
-        m, orc, cfg, fused, sr, seed = _fresh_lisennet() if name == "lisennet" else _fresh_model(name)
+        m, orc, cfg, fused, sr, seed = _fresh_model(name)
         eng, H = m.engine, cfg.hop_size
         x = make_input(B, hops * H, seed + 777, sr)
         if ref is None:

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-from common import MODEL_KWARGS, MODEL_MODULE, build_oracle, load_golden, rms
+from common import MODEL_KWARGS, MODEL_MODULE, build_named_oracle, build_oracle, hip_model, load_golden, model_kwargs, rms
 from oracle.weightgen import make_input
 
 pytestmark = pytest.mark.gpu
@@ -81,12 +81,60 @@ def _assert_close(got, ref, what, tight=None):
 
 
 def _model(name, cls="ONNXModel"):
-    kw, sr, seed = MODEL_KWARGS[name]
-    cfg, sd, fused, orc = build_oracle(name)
-    mod = importlib.import_module(f"fastenhancer_amd.models.{MODEL_MODULE[name]}.model")
-    m = getattr(mod, cls)(**kw).to(_dev()).eval()
-    m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
-    return m, orc, cfg, sr, seed
+    """any configuration name -> (its mirror with the oracle's seeded weights, the oracle, the oracle's config, sampling rate, seed)"""
+    _, sr, seed = model_kwargs(name)
+    cfg, sd, fused, orc = build_named_oracle(name)
+    return hip_model(name, cls, _dev(), sd=sd), orc, cfg, sr, seed
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int32)
+
+
+@pytest.mark.parametrize("name", ["fe_t", "fe_dpt_t", "fe_tk_b", "bsrnn_xxt", "fspen", "lisennet"])
+def test_mirror_forward_threads_the_caches_like_the_engine(name):
+    """ONNXModel.forward of the smallest configuration of every family (and of the two FastEnhancer variants whose state order is not
+    the reference's), two hops of T = 1 for B = 2: first without caches, then with clones of the caches it returned.  Expected: what
+    Engine.spec_step gives when driven directly with the same state, packed by pack_state (the golden-pinned path).  fe_dpt_t: two hops
+    are fewer than its lookbehind, so the second call still carries the +inf marks of the cache-less start."""
+    m = _model(name)[0]
+    eng, c, B = m.engine, m.cfg, 2
+    stft = [torch.zeros(B, c.cache_len, device=_dev())] * 2
+    fresh = m.initialize_cache(torch.zeros(B, 1, device=_dev()))
+    gen = torch.Generator().manual_seed(4242)
+    specs = [torch.randn(B, c.n_fft // 2 + 1, 1, 2, generator=gen).to(_dev()) for _ in range(2)]
+
+    def engine_step(spec, h):
+        """(spec_hat, caches) of fe_spec_step on the model state h, which it updates in place"""
+        spec_hat = eng.spec_step(spec, h)
+        return spec_hat, eng.split_state(torch.cat([torch.cat(stft).reshape(-1), h]), B)[2:]
+
+    def check(got, want, given=(), kept=()):
+        spec_hat, *caches = got
+        assert [t.shape for t in caches] == [t.shape for t in fresh] and all(t.dtype == torch.float32 and t.device == eng.device for t in caches)
+        assert len({t.untyped_storage().data_ptr() for t in caches}) == 1, "the caches returned are views of one buffer"
+        for a, b in zip(given, kept):
+            assert torch.equal(_bits(a), _bits(b)), "a cache passed in was written"
+        assert spec_hat.shape == want[0].shape and spec_hat.dtype == torch.float32 and torch.equal(_bits(spec_hat), _bits(want[0]))
+        assert len(caches) == len(want[1])
+        for i, (a, b) in enumerate(zip(caches, want[1])):
+            assert torch.equal(_bits(a), _bits(b)), (name, "cache", i)
+
+    # hop 0, no caches: the zero state - dptransformer: with +inf in the first element of every slot of the K rings (fe_config.lookbehind)
+    h = eng.pack_state(stft + fresh, B)[2 * B * c.cache_len:].clone()
+    if getattr(c, "dpt", False):
+        n = B * c.rf_freq * c.rf_channels * c.lookbehind              # floats of one ring: K of block k at 2 k n, its V after it
+        for k in range(c.rf_blocks):
+            h[2 * k * n:(2 * k + 1) * n].view(-1, c.rf_channels // c.rf_heads)[:, 0] = float("inf")
+    got = m(specs[0])
+    check(got, engine_step(specs[0], h))
+    # hop 1, with clones of the caches returned
+    given = [t.clone() for t in got[1:]]
+    kept = [t.clone() for t in given]
+    h = eng.pack_state(stft + kept, B)[2 * B * c.cache_len:].clone()
+    if getattr(c, "dpt", False):
+        assert any(torch.isinf(t).any() for t in given), "the start marks are still in the caches"
+    check(m(specs[1], *given), engine_step(specs[1], h), given, kept)
 
 
 @pytest.mark.parametrize("name", GPU_SHAPES)
@@ -332,7 +380,7 @@ def test_streaming_model_has_the_reference_value_semantics(name):
     returned by call n stay what they were through five more calls and are still valid input: resuming from them reproduces, bit for bit,
     what the uninterrupted run produced."""
     from fastenhancer_amd.streaming import StreamingModel
-    m, orc, cfg, sr, seed = _bsrnn(name) if name.startswith("bsrnn") else _model(name)
+    m, orc, cfg, sr, seed = _model(name)
     M = StreamingModel(m)
     B, hops, H, keep = 3, 9, cfg.hop_size, 2
     x = torch.from_numpy(make_input(B, hops * H, 31, sr)).to(_dev())
@@ -610,7 +658,7 @@ def test_low_lds_companion_above_cus(name, B):
 
 def test_full_size_bsrnn_xt_256_streams():
     """BASELINE config 5: BSRNN-xt, 256 streams."""
-    m, orc, cfg, sr, seed = _bsrnn("bsrnn_xt")
+    m, orc, cfg, sr, seed = _model("bsrnn_xt")
     _full_size_check(m, orc, cfg, sr, 256, 4, [0, 1, 17, 128, 254, 255], "bsrnn_xt B=256")
 
 
@@ -620,7 +668,7 @@ def test_bsrnn_role_split_part1_agrees_with_the_phase_by_phase_kernel(name, B):
     the scans alone on two waves, the layers' matrix-core chains on the other two, LDS counters between them);
     fe_set_step_kernel(FE_STEP_KERNEL_WAVES4) selects the phase-by-phase kernel.  Both against the oracle on sampled streams, and against
     each other on every stream and every cache - twelve hops, so that the time-LSTM state both kernels write back is fed forward."""
-    m, orc, cfg, sr, seed = _bsrnn(name)
+    m, orc, cfg, sr, seed = _model(name)
     eng = m.engine
     hops, H = 12, cfg.hop_size
     x = make_input(B, hops * H, seed + 77, sr)
@@ -742,7 +790,7 @@ def test_edge_inputs():
 def test_bsrnn_edge_inputs(kern):
     """Silence (BSRNN's mask has a residual branch: the output is small, not zero) and a burst forty times full scale that drives the LSTM gates into
     saturation (exp2 overflows to inf, rcp(inf) = 0: no NaN) - both PART 1 kernels of the per-hop step against the oracle, finite everywhere."""
-    m, orc, cfg, sr, seed = _bsrnn("bsrnn_xt")
+    m, orc, cfg, sr, seed = _model("bsrnn_xt")
     eng = m.engine
     eng.set_step_kernel(kern)
     B, hops, H = 3, 6, cfg.hop_size
@@ -935,7 +983,7 @@ def test_step_with_host_buffers_matches_device_stepping(name, T):
     buffers: the same kernel on the same data - bit for bit, pinned or pageable host memory, strided rows; and enhance_stream on a
     CPU tensor against enhance_stream on the device."""
     from fastenhancer_amd.streaming import enhance_stream
-    m, orc, cfg, sr, seed = (_bsrnn(name) if name.startswith("bsrnn") else _model(name))
+    m, orc, cfg, sr, seed = _model(name)
     eng = m.engine
     B, H, n = 5, cfg.hop_size, 7
     x = torch.from_numpy(make_input(B, n * T * H + 40, 515, sr))
@@ -1157,10 +1205,7 @@ def test_ragged_offline_batch_is_bit_identical_to_one_call_per_utterance(name, n
     and are walked one after the other inside the call.  A sample of the files is also checked against the oracle.
     r5: the big shapes under AUTO with 8+ files (AUTO walks an equal-length batch of that size; a ragged one takes the batched pass) and the
     explicit frame walk (one by one inside the call, scratch sized for it)."""
-    if name.startswith("bsrnn"):
-        m, orc, cfg, sr, seed = _bsrnn(name, "Model")
-    else:
-        m, orc, cfg, sr, seed = _model(name, "Model")
+    m, orc, cfg, sr, seed = _model(name, "Model")
     eng = m.engine
     if engine:
         eng.set_offline_engine(engine)
@@ -1215,20 +1260,10 @@ def test_offline_cli_pushes_a_directory_through_in_ragged_batches(tmp_path, monk
 
 
 # ------------------------------------------------------------------------------------------------ BSRNN (a22-a25)
-def _bsrnn(name, cls="ONNXModel"):
-    from common import BSRNN_KWARGS, build_bsrnn_oracle
-    kw, sr, seed = BSRNN_KWARGS[name]
-    cfg, sd, fused, orc = build_bsrnn_oracle(name)
-    mod = importlib.import_module("fastenhancer_amd.models.bsrnn.model")
-    m = getattr(mod, cls)(**kw).to(_dev()).eval()
-    m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
-    return m, orc, cfg, sr, seed
-
-
 @pytest.mark.parametrize("name", ["bsrnn_xxt", "bsrnn_xt", "bsrnn_t", "bsrnn_s"])
 def test_bsrnn_every_stage_matches_oracle(name):
     """Per-stage activations (fe_debug_step): band split, each layer's time- / band-LSTM half, the mask MLPs."""
-    m, orc, cfg, sr, seed = _bsrnn(name)
+    m, orc, cfg, sr, seed = _model(name)
     eng = m.engine
     B, hops, H = 3, 3, cfg.hop_size
     x = make_input(B, hops * H, 515, sr)
@@ -1254,7 +1289,7 @@ def test_bsrnn_every_stage_matches_oracle(name):
 def test_bsrnn_streaming_matches_reference_golden(name):
     from fastenhancer_amd.streaming import StreamingModel
     g = load_golden(name)
-    m, orc, cfg, sr, seed = _bsrnn(name)
+    m, orc, cfg, sr, seed = _model(name)
     M = StreamingModel(m)
     B, hops, H = int(g["B"]), int(g["hops"]), cfg.hop_size
     x = torch.from_numpy(make_input(B, hops * H, seed + 1000, sr)).to(_dev())
@@ -1273,7 +1308,7 @@ def test_bsrnn_streaming_matches_reference_golden(name):
 @pytest.mark.parametrize("name", ["bsrnn_xxt", "bsrnn_xt", "bsrnn_t", "bsrnn_s"])
 def test_bsrnn_offline_matches_reference_golden(name):
     g = load_golden(name)
-    m, orc, cfg, sr, seed = _bsrnn(name, "Model")
+    m, orc, cfg, sr, seed = _model(name, "Model")
     x = torch.from_numpy(make_input(int(g["B"]), int(g["hops"]) * cfg.hop_size + 37, seed + 2000, sr)).to(_dev())
     wav_hat, spec_hat = m(x)
     _assert_close(wav_hat.cpu().numpy(), g["offline_wav"], "offline wav")
@@ -1284,7 +1319,7 @@ def test_bsrnn_offline_matches_reference_golden(name):
 def test_bsrnn_time_pipelined_offline_agrees_with_the_serial_walk(name, B):
     """fe_offline of BSRNN with the frames of an utterance spread over co-resident workgroups (the time-LSTM state handed from frame
     to frame through per-layer counters) against one workgroup walking the frames, and against the oracle."""
-    m, orc, cfg, sr, seed = _bsrnn(name, "Model")
+    m, orc, cfg, sr, seed = _model(name, "Model")
     eng = m.engine
     x = make_input(B, 41 * cfg.hop_size + 19, seed + 31, sr)
     xd = torch.from_numpy(x).to(_dev())
@@ -1305,7 +1340,7 @@ def test_bsrnn_time_pipelined_offline_agrees_with_the_serial_walk(name, B):
 
 @pytest.mark.parametrize("name", ["bsrnn_xt", "bsrnn_t", "bsrnn_s"])
 def test_bsrnn_batch_and_chunk_vs_oracle(name):
-    m, orc, cfg, sr, seed = _bsrnn(name)
+    m, orc, cfg, sr, seed = _model(name)
     eng = m.engine
     B, T, H = 5, 5, cfg.hop_size
     x = make_input(B, T * H, 77, sr)
@@ -1404,7 +1439,7 @@ print('added-shape parity ok', err, r)
 
 def test_bsrnn_more_streams_than_cus():
     """persistent BSRNN workgroups: 300 streams on 256 CUs (workgroups 0..43 walk two streams each)"""
-    m, orc, cfg, sr, seed = _bsrnn("bsrnn_xxt")
+    m, orc, cfg, sr, seed = _model("bsrnn_xxt")
     _full_size_check(m, orc, cfg, sr, 300, 3, [0, 1, 43, 44, 255, 256, 257, 299], "bsrnn_xxt B=300")
 
 
@@ -1417,7 +1452,7 @@ def test_bsrnn_stream_batched_layers_above_2048_streams(name, B):
     streamed; from 2816 streams - the threshold counts 11 / 8 there), 2829 = a last tile of 13.  Oracle parity (outputs and every time-LSTM cache) on a sample that covers first / last tiles and columns, and
     bitwise position independence on all streams (_full_size_check runs the batch again in reversed order: every stream then sits
     in another tile and another column)."""
-    m, orc, cfg, sr, seed = _bsrnn(name)
+    m, orc, cfg, sr, seed = _model(name)
     _full_size_check(m, orc, cfg, sr, B, 3 if name != "bsrnn_s" else 2, [0, 1, 15, 16, 17, 1000, 2047, B - 14, B - 13, B - 2, B - 1], f"{name} B={B}")
     assert "bsrnn_sb" in m.engine.last_step_kernel(), m.engine.last_step_kernel()
 
@@ -1426,7 +1461,7 @@ def test_bsrnn_split_step_with_ragged_stream_tiles():
     """the per-hop step in three launches (frame kernel head, mask-decoder MLPs batched over the streams, tail): 1030 streams = two
     persistent workgroups per CU in the head / tail and a last MLP stream tile of 6 rows (16-stream tiles, 64-stream workgroups);
     7 streams = one partial tile.  Oracle parity on a sample and position independence (_full_size_check)."""
-    m, orc, cfg, sr, seed = _bsrnn("bsrnn_xt")
+    m, orc, cfg, sr, seed = _model("bsrnn_xt")
     _full_size_check(m, orc, cfg, sr, 1030, 2, [0, 15, 16, 63, 64, 511, 512, 1023, 1024, 1029], "bsrnn_xt B=1030")
     _full_size_check(m, orc, cfg, sr, 7, 3, [0, 3, 6], "bsrnn_xt B=7")
 
@@ -1435,8 +1470,8 @@ def test_steps_can_be_captured_into_a_hip_graph():
     """no allocation, free or synchronisation inside fe_step: a burst of per-hop launches captured into a HIP graph
     (torch.cuda.CUDAGraph on the capture stream) replays to the same bits as the eager launches, for the LDS-skip (B),
     global-skip (M: per-workgroup scratch allocated at load time) and BSRNN kernels"""
-    for name, loader in (("fe_b", _model), ("fe_m", _model), ("bsrnn_xt", _bsrnn)):
-        m, orc, cfg, sr, seed = loader(name)
+    for name in ("fe_b", "fe_m", "bsrnn_xt"):
+        m, orc, cfg, sr, seed = _model(name)
         eng = m.engine
         B, hops, H = 7, 5, cfg.hop_size
         x = torch.from_numpy(make_input(B, hops * H, 21, sr)).to(_dev())
@@ -1461,19 +1496,9 @@ def test_steps_can_be_captured_into_a_hip_graph():
 
 
 # ------------------------------------------------------------------------------------------------ FSPEN
-def _fspen(cls="ONNXModel"):
-    from common import FSPEN_KWARGS, build_fspen_oracle
-    kw, sr, seed = FSPEN_KWARGS
-    cfg, sd, fused, orc = build_fspen_oracle()
-    mod = importlib.import_module("fastenhancer_amd.models.fspen.model")
-    m = getattr(mod, cls)(**kw).to(_dev()).eval()
-    m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
-    return m, orc, cfg, sr, seed
-
-
 def test_fspen_every_stage_matches_oracle():
     """fe_debug_step taps of the FSPEN kernel against the oracle's (models/fspen/model.py:342-407), three hops with state."""
-    m, orc, cfg, sr, seed = _fspen()
+    m, orc, cfg, sr, seed = _model("fspen")
     eng = m.engine
     B, hops, H = 3, 3, cfg.hop_size
     x = make_input(B, hops * H, 616, sr)
@@ -1506,7 +1531,7 @@ def test_fspen_streaming_matches_reference_golden():
     """scripts/export_onnx.py:48-58 composition with `model: fspen`: 10 hops x 2 streams, all 24 inter-GRU caches."""
     from fastenhancer_amd.streaming import StreamingModel
     g = load_golden("fspen")
-    m, orc, cfg, sr, seed = _fspen()
+    m, orc, cfg, sr, seed = _model("fspen")
     M = StreamingModel(m)
     B, hops, H = int(g["B"]), int(g["hops"]), cfg.hop_size
     x = torch.from_numpy(make_input(B, hops * H, seed + 1000, sr)).to(_dev())
@@ -1521,7 +1546,7 @@ def test_fspen_streaming_matches_reference_golden():
     for i in range(cfg.n_caches):
         _assert_close(caches[2 + i].cpu().numpy(), g[f"stream_c{i}"], f"inter GRU cache {i}")
     # the model mirror's own spec -> spec call (ONNXModel.forward) on the last hop's input
-    m2, *_ = _fspen()
+    m2, *_ = _model("fspen")
     c0 = orc.initialize_cache(B)
     spec_in, _ = orc.stft_step(make_input(B, hops * H, seed + 1000, sr)[:, :H], c0[0])
     ref, ref_c = orc.spec_forward(spec_in, c0[2:])
@@ -1533,7 +1558,7 @@ def test_fspen_streaming_matches_reference_golden():
 
 def test_fspen_offline_matches_reference_golden():
     g = load_golden("fspen")
-    m, orc, cfg, sr, seed = _fspen("Model")
+    m, orc, cfg, sr, seed = _model("fspen", "Model")
     x = torch.from_numpy(make_input(int(g["B"]), int(g["hops"]) * cfg.hop_size + 37, seed + 2000, sr)).to(_dev())
     wav_hat, spec_hat = m(x)
     _assert_close(wav_hat.cpu().numpy(), g["offline_wav"], "offline wav")
@@ -1544,7 +1569,7 @@ def test_fspen_offline_matches_reference_golden():
 def test_fspen_time_pipelined_offline_agrees_with_the_serial_walk(B):
     """FSPEN's offline Model.forward with the frames of an utterance over co-resident workgroups (the inter-GRU states of each DPE
     block handed from frame to frame) against one workgroup walking the frames, and against the oracle."""
-    m, orc, cfg, sr, seed = _fspen("Model")
+    m, orc, cfg, sr, seed = _model("fspen", "Model")
     eng = m.engine
     x = make_input(B, 57 * cfg.hop_size + 21, seed + 77, sr)
     xd = torch.from_numpy(x).to(_dev())
@@ -1566,7 +1591,7 @@ def test_fspen_time_pipelined_offline_agrees_with_the_serial_walk(B):
 def test_fspen_full_size(B):
     """256 streams (one workgroup per CU), 600 (three per CU) and 1000 (persistent): oracle parity on a sample, bitwise
     position independence on all streams; chunked launch == per-hop launches"""
-    m, orc, cfg, sr, seed = _fspen()
+    m, orc, cfg, sr, seed = _model("fspen")
     _full_size_check(m, orc, cfg, sr, B, 3, [0, 1, 17, 255, B // 2, B - 2, B - 1], f"fspen B={B}")
     eng = m.engine
     H = cfg.hop_size
@@ -1583,27 +1608,17 @@ def test_fspen_stream_batched_middle_above_1536_streams(B):
     feature split, fullband_decoder.0 - batched over the streams on the matrix cores (fspen_sb_kernels.hip.h: front per stream, sixteen
     streams per workgroup, tail per stream).  2057 streams = a last tile of 9.  Oracle parity (outputs and all 24 inter-GRU caches) on a sample that covers first / last tiles and columns, bitwise
     position independence on all streams (_full_size_check runs the batch again in reversed order)."""
-    m, orc, cfg, sr, seed = _fspen()
+    m, orc, cfg, sr, seed = _model("fspen")
     _full_size_check(m, orc, cfg, sr, B, 3, [0, 1, 15, 16, 17, 511, 1000, B - 10, B - 9, B - 2, B - 1], f"fspen B={B}")
 
 
 # ------------------------------------------------------------------------------------------------ LiSenNet (SURVEY.md §8(f) rank 4)
-def _lisennet(cls="ONNXModel"):
-    from common import LISENNET_KWARGS, build_lisennet_oracle
-    kw, sr, seed = LISENNET_KWARGS
-    cfg, sd, _, orc = build_lisennet_oracle()
-    mod = importlib.import_module("fastenhancer_amd.models.lisennet.model")
-    m = getattr(mod, cls)(**kw).to(_dev()).eval()
-    m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
-    return m, orc, cfg, sr, seed
-
-
 @pytest.mark.parametrize("sb,B", [(False, 3), (True, 3), (True, 21)])
 def test_lisennet_every_stage_matches_oracle(sb, B):
     """fe_debug_step taps of the LiSenNet kernel against the oracle's (models/lisennet/model.py:398-474), three hops with state.  sb (r6): the same taps
     and caches through the three-launch step whose middle - conv_1 .. the mask head - runs batched over sixteen streams per workgroup on the matrix cores
     (lisennet_sb_kernels.hip.h; fe_set_option("lisennet_stream_batch_min", 1)): 3 streams = one partly filled tile, 21 = a last tile of 5."""
-    m, orc, cfg, sr, seed = _lisennet()
+    m, orc, cfg, sr, seed = _model("lisennet")
     eng = m.engine
     eng.set_option("lisennet_stream_batch_min", 1 if sb else 0)
     hops, H = 3, cfg.hop_size
@@ -1637,7 +1652,7 @@ def test_lisennet_streaming_matches_reference_golden():
     """scripts/export_onnx.py:48-58 composition with `model: lisennet`: 10 hops x 2 streams, all 9 model caches."""
     from fastenhancer_amd.streaming import StreamingModel
     g = load_golden("lisennet")
-    m, orc, cfg, sr, seed = _lisennet()
+    m, orc, cfg, sr, seed = _model("lisennet")
     M = StreamingModel(m)
     B, hops, H = int(g["B"]), int(g["hops"]), cfg.hop_size
     x = torch.from_numpy(make_input(B, hops * H, seed + 1000, sr)).to(_dev())
@@ -1652,7 +1667,7 @@ def test_lisennet_streaming_matches_reference_golden():
     for i in range(cfg.n_caches):
         _assert_close(caches[2 + i].cpu().numpy(), g[f"stream_c{i}"], f"model cache {i}")
     # the mirror's own spec -> spec call (ONNXModel.forward) on the first hop
-    m2, *_ = _lisennet()
+    m2, *_ = _model("lisennet")
     c0 = orc.initialize_cache(B)
     spec_in, _ = orc.stft_step(make_input(B, hops * H, seed + 1000, sr)[:, :H], c0[0])
     ref, ref_c = orc.spec_forward(spec_in, c0[2:])
@@ -1668,7 +1683,7 @@ def test_lisennet_offline_matches_oracle():
     through its own features) and the kernel both see phase 0; the result is also compared with the reference's golden output on
     every frame that the first one cannot reach... which is none (GRU state), so the golden comparison is the oracle's."""
     g = load_golden("lisennet")
-    m, orc, cfg, sr, seed = _lisennet("Model")
+    m, orc, cfg, sr, seed = _model("lisennet", "Model")
     xo = make_input(int(g["B"]), int(g["hops"]) * cfg.hop_size + 37, seed + 2000, sr)
     xo[:, :int(g["offline_leading_zeros"])] = 0.0
     wav_ref, spec_ref = orc.offline_forward(xo)
@@ -1683,7 +1698,7 @@ def test_lisennet_time_pipelined_offline_agrees_with_the_serial_walk(B):
     encoder frames, per block GRU state + ConvGLU frames, decoder frame) go through a ring of per-frame slots with a counter per cache.
     Against the serial walk and the oracle (leading silence: frame 0 of the offline path is ill-conditioned, see the test above)."""
     g = load_golden("lisennet")
-    m, orc, cfg, sr, seed = _lisennet("Model")
+    m, orc, cfg, sr, seed = _model("lisennet", "Model")
     eng = m.engine
     x = make_input(B, 61 * cfg.hop_size + 9, seed + 88, sr)
     x[:, :int(g["offline_leading_zeros"])] = 0.0
@@ -1708,9 +1723,7 @@ def test_time_pipeline_width_above_the_ring_size_is_clamped(which):
     LiSenNet caches) hold 64 frames in flight - a wider request is clamped (it used to index past the rings); results equal the serial walk."""
     if which == "lisennet":
         g = load_golden("lisennet")
-        m, orc, cfg, sr, seed = _lisennet("Model")
-    else:
-        m, orc, cfg, sr, seed = _model(which, "Model")
+    m, orc, cfg, sr, seed = _model(which, "Model")
     eng = m.engine
     x = make_input(1, 150 * cfg.hop_size + 5, 4711, sr)
     if which == "lisennet":
@@ -1734,7 +1747,7 @@ def test_lisennet_stream_batched_middle_above_512_streams(B):
     STFT + features per stream, sixteen streams per workgroup, mask + iSTFT per stream).  601 streams = a last tile of 9.  Oracle parity (outputs and all nine model caches) on
     a sample that covers first / last tiles and columns, bitwise position independence on all streams (_full_size_check runs the batch again in reversed
     order); the step equals the per-stream kernel's to fp32 rounding; and a batch below the threshold keeps the per-stream kernel."""
-    m, orc, cfg, sr, seed = _lisennet()
+    m, orc, cfg, sr, seed = _model("lisennet")
     eng = m.engine
     _full_size_check(m, orc, cfg, sr, B, 3, [0, 1, 15, 16, 17, 511, min(1000, B - 11), B - 10, B - 9, B - 2, B - 1], f"lisennet B={B}")
     assert "lisennet_sb_kernel" in eng.last_step_kernel(), eng.last_step_kernel()
@@ -1759,7 +1772,7 @@ def test_lisennet_stream_batched_middle_above_512_streams(B):
 def test_lisennet_full_size(B):
     """256 streams (one workgroup per CU) and 700 (two per CU, then persistent): oracle parity on a sample, bitwise position
     independence on all streams; chunked launch == per-hop launches"""
-    m, orc, cfg, sr, seed = _lisennet()
+    m, orc, cfg, sr, seed = _model("lisennet")
     _full_size_check(m, orc, cfg, sr, B, 3, [0, 1, 17, 255, B // 2, B - 2, B - 1], f"lisennet B={B}")
     eng = m.engine
     H = cfg.hop_size
@@ -1797,7 +1810,7 @@ def test_block_variants_long_run_has_no_state_drift(name, hops, T):
 def test_baseline_models_long_run_has_no_state_drift(which):
     """60 hops (0.96 s) of two streams through the per-hop kernel against the oracle: the GRU states and the causal-conv frame caches are
     carried through the stream state the whole way (the goldens stop at 10 hops)"""
-    m, orc, cfg, sr, seed = _fspen() if which == "fspen" else _lisennet()
+    m, orc, cfg, sr, seed = _model(which)
     eng = m.engine
     B, hops, H = 2, 60, cfg.hop_size
     x = make_input(B, hops * H, 4321, sr)
@@ -1851,14 +1864,7 @@ def test_time_pipeline_stress_is_bit_reproducible_and_equals_the_serial_walk(nam
     of the time-pipelined launches (relaxed agent-scope counters + s_waitcnt vmcnt(0) + barrier, fe_kernels.hip.h): per family one batch
     size the other tests do not use (7 streams: ragged against every pipeline width), 10 repetitions that must reproduce the first bit for
     bit - the hand-off order does not change the arithmetic - and agree with one workgroup walking the frames serially."""
-    if name == "fspen":
-        m, orc, cfg, sr, seed = _fspen("Model")
-    elif name == "lisennet":
-        m, orc, cfg, sr, seed = _lisennet("Model")
-    elif name.startswith("bsrnn"):
-        m, orc, cfg, sr, seed = _bsrnn(name, "Model")
-    else:
-        m, orc, cfg, sr, seed = _model(name, "Model")
+    m, orc, cfg, sr, seed = _model(name, "Model")
     eng = m.engine
     if name in TB_SHAPES:
         eng.set_offline_engine("frame_walk")
@@ -1891,14 +1897,7 @@ def test_lds_leftovers_of_other_kernels_do_not_matter(name, B, kern):
     band's row padded to 36 floats: two words past the spectrum).  What an earlier kernel left there must not matter: with every CU's LDS filled with
     NaN before each launch (fe_debug_poison_lds) a per-hop run gives the bits of the plain run.  (Found by a 400-hop run that came back non-finite
     once, right after process start.)"""
-    if name.startswith("bsrnn"):
-        m, orc, cfg, sr, seed = _bsrnn(name)
-    elif name == "fspen":
-        m, orc, cfg, sr, seed = _fspen()
-    elif name == "lisennet":
-        m, orc, cfg, sr, seed = _lisennet()
-    else:
-        m, orc, cfg, sr, seed = _model(name)
+    m, orc, cfg, sr, seed = _model(name)
     eng = m.engine
     if kern is not None:
         eng.set_step_kernel(kern)
@@ -1925,18 +1924,11 @@ def test_lds_leftovers_do_not_matter_chunked_offline_and_stream_batched(name, B)
     """The same for the other launch shapes: a chunked step (T = 3), offline Model.forward (time-batched engine / time-pipelined walk), and the
     stream-batched steps of the large batches (BSRNN from 2048 streams - r6: num_channels = 32 too -, FSPEN from 1536, r6: LiSenNet from 513)."""
     cls = "Model" if name == "fe_nc" else "ONNXModel"
-    if name.startswith("bsrnn"):
-        m, orc, cfg, sr, seed = _bsrnn(name)
-        mo = _bsrnn(name, "Model")[0] if B < 100 else None
-    elif name == "fspen":
-        m, orc, cfg, sr, seed = _fspen()
-        mo = _fspen("Model")[0] if B < 100 else None
-    elif name == "lisennet":
-        m, orc, cfg, sr, seed = _lisennet()
-        mo = _lisennet("Model")[0] if B < 100 else None
-    else:
-        m, orc, cfg, sr, seed = _model(name, cls)
+    m, orc, cfg, sr, seed = _model(name, cls)
+    if name in MODEL_KWARGS:
         mo = m if cls == "Model" else _model(name, "Model")[0]
+    else:           # (the baselines' offline pass only at the small batches)
+        mo = _model(name, "Model")[0] if B < 100 else None
     H = cfg.hop_size
     if cls == "ONNXModel":
         eng = m.engine
@@ -1965,17 +1957,9 @@ def test_lds_leftovers_do_not_matter_chunked_offline_and_stream_batched(name, B)
 def test_uninitialised_work_buffers_do_not_matter(name, monkeypatch):
     """The caller-owned work / output buffers of fe_offline (the mirror gets them from torch.empty): every word the engines read they must have written
     first.  With torch.empty handing out NaN-filled buffers, Model.forward gives the bits of the plain run - on the time-batched engine and on the frame walk."""
-    if name.startswith("bsrnn"):
-        mo = _bsrnn(name, "Model")[0]
-        cfg, sr, seed = mo.engine.cfg, 16000, 11
-    elif name == "fspen":
-        mo = _fspen("Model")[0]
-        cfg, sr, seed = mo.engine.cfg, 16000, 12
-    elif name == "lisennet":
-        mo = _lisennet("Model")[0]
-        cfg, sr, seed = mo.engine.cfg, 16000, 13
-    else:
-        mo, orc, cfg, sr, seed = _model(name, "Model")
+    mo, orc, cfg, sr, seed = _model(name, "Model")
+    if name not in MODEL_KWARGS:          # (the baselines' inputs: seeds of their own)
+        seed = 11 if name.startswith("bsrnn") else 12 if name == "fspen" else 13
     H = cfg.hop_size
     xo = torch.from_numpy(make_input(3, 21 * H + 5, seed + 3, sr)).to(_dev())
     engines = ["auto"] if name in ("fe_nc",) or name.startswith("bsrnn") or name in ("fspen", "lisennet") else ["auto", "frame_walk"]

@@ -5,9 +5,8 @@ import numpy as np
 import pytest
 import torch
 
-from common import BSRNN_KWARGS, FSPEN_KWARGS, LISENNET_KWARGS, build_bsrnn_oracle, build_fspen_oracle, build_lisennet_oracle, build_oracle, product_config
-from fastenhancer_amd.config import BSRNNConfig, FSPENConfig, LiSenNetConfig
-from fastenhancer_amd.engine import Engine, _ptr, _stream
+from common import BSRNN_KWARGS, FSPEN_KWARGS, LISENNET_KWARGS, hip_model, product_config
+from fastenhancer_amd.engine import _ptr, _stream
 from fastenhancer_amd.serving import PacketPool, StreamPool
 
 pytestmark = pytest.mark.gpu
@@ -29,16 +28,7 @@ _ENGINES = {}
 def _engine(name, dev=0):
     """seeded random weights; the FastEnhancer shapes with the step kernel pinned (the bit-identity contract holds per kernel)"""
     if (name, dev) not in _ENGINES:
-        if name in BSRNN_KWARGS:
-            cfg, sd = BSRNNConfig.from_model_kwargs(**BSRNN_KWARGS[name][0]), build_bsrnn_oracle(name)[1]
-        elif name == "fspen":
-            cfg, sd = FSPENConfig.from_model_kwargs(**FSPEN_KWARGS[0]), build_fspen_oracle()[1]
-        elif name == "lisennet":
-            cfg, sd = LiSenNetConfig.from_model_kwargs(**LISENNET_KWARGS[0]), build_lisennet_oracle()[1]
-        else:
-            cfg, sd = product_config(name), build_oracle(name)[1]
-        eng = Engine(cfg, _dev(dev))
-        eng.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()})
+        eng = hip_model(name, device=_dev(dev)).engine
         if name in FE_SHAPES:
             eng.set_step_kernel("waves4")
         _ENGINES[(name, dev)] = eng

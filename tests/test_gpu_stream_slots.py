@@ -6,8 +6,8 @@ import numpy as np
 import pytest
 import torch
 
-from common import MODEL_KWARGS, build_oracle, load_golden, product_config, rms
-from fastenhancer_amd.engine import Engine, _ptr, _stream
+from common import MODEL_KWARGS, hip_model, load_golden, rms
+from fastenhancer_amd.engine import _ptr, _stream
 from fastenhancer_amd.serving import StreamPool
 from oracle.weightgen import make_input
 
@@ -27,10 +27,7 @@ _ENGINES = {}
 
 def _engine(name):
     if name not in _ENGINES:
-        cfg, sd, fused, orc = build_oracle(name)
-        eng = Engine(product_config(name), _dev())
-        eng.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()})
-        _ENGINES[name] = eng
+        _ENGINES[name] = hip_model(name, device=_dev()).engine
     return _ENGINES[name]
 
 

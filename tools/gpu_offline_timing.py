@@ -10,9 +10,7 @@ import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
-from common import MODEL_KWARGS, product_config  # noqa: E402
-from fastenhancer_amd.config import FEConfig  # noqa: E402
-from fastenhancer_amd.engine import Engine  # noqa: E402
+from common import MODEL_KWARGS, hip_engine, hip_model, model_kwargs, product_config  # noqa: E402
 from fastenhancer_amd.weights import default_state_dict  # noqa: E402
 
 
@@ -21,37 +19,12 @@ def main():
     secs = float(sys.argv[2]) if len(sys.argv) > 2 else 4.0
     B = int(sys.argv[3]) if len(sys.argv) > 3 else 1
     dev = torch.device("cuda:0")
-    if name.startswith("bsrnn"):       # (BSRNN: the mirror with the oracle's seeded checkpoint, as the tests build it)
-        import importlib
-        import numpy as np
-        from common import BSRNN_KWARGS, build_bsrnn_oracle
-        kw, sr, _ = BSRNN_KWARGS[name]
-        cfg, sd, _, _ = build_bsrnn_oracle(name)
-        m = importlib.import_module("fastenhancer_amd.models.bsrnn.model").Model(**kw).to(dev).eval()
-        m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
-        eng = m.engine
-    elif name == "lisennet":
-        import importlib
-        import numpy as np
-        from common import LISENNET_KWARGS, build_lisennet_oracle
-        kw, sr, _ = LISENNET_KWARGS
-        cfg, sd, _, _ = build_lisennet_oracle()
-        m = importlib.import_module("fastenhancer_amd.models.lisennet.model").Model(**kw).to(dev).eval()
-        m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
-        eng = m.engine
-    elif name == "fspen":
-        import importlib
-        import numpy as np
-        from common import FSPEN_KWARGS, build_fspen_oracle
-        kw, sr, _ = FSPEN_KWARGS
-        cfg, sd, _, _ = build_fspen_oracle()
-        m = importlib.import_module("fastenhancer_amd.models.fspen.model").Model(**kw).to(dev).eval()
-        m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
-        eng = m.engine
+    sr = model_kwargs(name)[1]
+    cfg = product_config(name)
+    if name not in MODEL_KWARGS:       # (the baselines: the mirror with the oracle's seeded checkpoint, as the tests build it)
+        eng = hip_model(name, "Model", dev).engine
     else:
-        kw, sr, _ = MODEL_KWARGS[name]
-        cfg = product_config(name)
-        eng = Engine(cfg, dev)
+        eng = hip_engine(name, dev)
         if not cfg.noncausal:
             eng.set_offline_engine("frame_walk")       # (this tool times the frame walk and its time pipeline; tools/gpu_tb_timing.py the time-batched engine)
         eng.load_state_dict(default_state_dict(cfg, torch.Generator().manual_seed(1)))

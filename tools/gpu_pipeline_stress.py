@@ -2,43 +2,24 @@
 """Stress of the time-pipelined offline launches (counters / rings / agent-scope hand-offs): every family, several batch sizes, N
 repetitions each - every repetition must reproduce the first bit for bit (the hand-off order does not change the arithmetic) and agree
 with the serial walk.  usage: tools/gpu_pipeline_stress.py [repetitions]"""
-import importlib
 import os
 import sys
 
-import numpy as np
 import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
-from common import (BSRNN_KWARGS, FSPEN_KWARGS, LISENNET_KWARGS, MODEL_KWARGS, MODEL_MODULE, build_bsrnn_oracle, build_fspen_oracle,  # noqa: E402
-                    build_lisennet_oracle, build_oracle)
+from common import hip_model, model_kwargs  # noqa: E402
 from oracle.weightgen import make_input  # noqa: E402
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 30
 dev = torch.device("cuda:0")
 bad = 0
 for name in ("fe_b", "fe_t", "fe_ln_b", "fe_tk_b", "fe_dpt_b", "fe_dprnn_b", "bsrnn_xt", "bsrnn_t", "fspen", "lisennet"):
-    if name == "fspen":
-        kw, sr, seed = FSPEN_KWARGS
-        cfg, sd, _, _ = build_fspen_oracle()
-        mod = importlib.import_module("fastenhancer_amd.models.fspen.model")
-    elif name == "lisennet":
-        kw, sr, seed = LISENNET_KWARGS
-        cfg, sd, _, _ = build_lisennet_oracle()
-        mod = importlib.import_module("fastenhancer_amd.models.lisennet.model")
-    elif name.startswith("bsrnn"):
-        kw, sr, seed = BSRNN_KWARGS[name]
-        cfg, sd, _, _ = build_bsrnn_oracle(name)
-        mod = importlib.import_module("fastenhancer_amd.models.bsrnn.model")
-    else:
-        kw, sr, seed = MODEL_KWARGS[name]
-        cfg, sd, _, _ = build_oracle(name)
-        mod = importlib.import_module(f"fastenhancer_amd.models.{MODEL_MODULE[name]}.model")
-    m = mod.Model(**kw).to(dev).eval()
-    m.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
-    eng = m.engine
+    _, sr, seed = model_kwargs(name)
+    m = hip_model(name, "Model", dev)
+    eng, cfg = m.engine, m.cfg
     if name in ("fe_b", "fe_t"):
         eng.set_offline_engine("frame_walk")
     for B in (1, 3, 7):

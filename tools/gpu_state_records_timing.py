@@ -17,9 +17,7 @@ import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
-from common import BSRNN_KWARGS, product_config  # noqa: E402
-from fastenhancer_amd.config import BSRNNConfig  # noqa: E402
-from fastenhancer_amd.engine import Engine  # noqa: E402
+from common import BSRNN_KWARGS, hip_engine, product_config  # noqa: E402
 
 
 def regions(name):
@@ -75,8 +73,7 @@ def main():
              f"# device: {torch.cuda.get_device_name(dev)}, {torch.cuda.get_device_properties(dev).multi_processor_count} CUs",
              f"{'model':>10} {'n':>4} {'record KB':>10} {'MB moved':>9} {'(a) two launches us':>20} {'GB/s':>7} {'(b) torch mover us':>19} {'GB/s':>7} {'(b)/(a)':>8}"]
     for name in args.models.split(","):
-        cfg = BSRNNConfig.from_model_kwargs(**BSRNN_KWARGS[name][0]) if name in BSRNN_KWARGS else product_config(name)
-        eng = Engine(cfg, dev)          # (no weights: state does not depend on them)
+        eng = hip_engine(name, dev)     # (no weights: state does not depend on them)
         rf = eng.record_floats
         gen = torch.Generator(device=dev).manual_seed(0)
         src = torch.randn(eng.state_floats(cap), device=dev, generator=gen)

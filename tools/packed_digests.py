@@ -20,28 +20,22 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
 from common import BSRNN_KWARGS, FSPEN_KWARGS, LISENNET_KWARGS, MODEL_KWARGS, MODEL_MODULE  # noqa: E402
-from fastenhancer_amd import config as C  # noqa: E402
-from fastenhancer_amd import weights as W  # noqa: E402
+from fastenhancer_amd.config import MODEL_CONFIGS  # noqa: E402
 from fastenhancer_amd.engine import Engine  # noqa: E402
-
-_VARIANT = {"fastenhancer.dprnn": C.dprnn_config, "fastenhancer.dptransformer": C.dpt_config, "fastenhancer.ln": C.ln_config,
-            "fastenhancer.noncausal": C.noncausal_config, "fastenhancer.time_kernel": C.time_kernel_config}
+from fastenhancer_amd.family import family_of  # noqa: E402
 
 
 def configurations(only=None, over=None):
     """name -> (config, its family's default_state_dict): the 31 shipped configurations, or those named in `only`; `over` updates the
-    FastEnhancer model_kwargs"""
+    FastEnhancer model_kwargs.  (tests/test_cpu_pack.py imports this module, and earlier revisions of the tests are run against later
+    trees: of tests/common.py only the kwargs tables, which every revision has, are used here.)"""
     out = {}
-    for name, (kw, _, _) in MODEL_KWARGS.items():
-        if only and name not in only:
-            continue
-        kw = dict(kw, **(over or {}))
-        out[name] = (_VARIANT.get(MODEL_MODULE[name], C.FEConfig.from_model_kwargs)(**kw), W.default_state_dict)
-    for name, (kw, _, _) in BSRNN_KWARGS.items():
-        out[name] = (C.BSRNNConfig.from_model_kwargs(**kw), W.bsrnn_default_state_dict)
-    out["fspen"] = (C.FSPENConfig.from_model_kwargs(**FSPEN_KWARGS[0]), W.fspen_default_state_dict)
-    out["lisennet"] = (C.LiSenNetConfig.from_model_kwargs(**LISENNET_KWARGS[0]), W.lisennet_default_state_dict)
-    return {name: v for name, v in out.items() if not only or name in only}
+    for name, (kw, _, _) in {**MODEL_KWARGS, **BSRNN_KWARGS, "fspen": FSPEN_KWARGS, "lisennet": LISENNET_KWARGS}.items():
+        if not only or name in only:
+            module = MODEL_MODULE.get(name, "bsrnn" if name in BSRNN_KWARGS else name)
+            cfg = MODEL_CONFIGS[module](**dict(kw, **(over or {}) if name in MODEL_KWARGS else {}))
+            out[name] = (cfg, family_of(cfg).default_state_dict)
+    return out
 
 
 def main():
