@@ -37,6 +37,11 @@ class fe_stream_desc(ctypes.Structure):
     _fields_ = [("slot", c_int), ("hops", c_int), ("in_offset", c_longlong), ("out_offset", c_longlong)]
 
 
+class fe_stream_levels(ctypes.Structure):
+    """one row of fe_step_streams_ctl's level table: sum of squares and peak of a stream's input / output samples of the call (16 bytes)"""
+    _fields_ = [("in_sumsq", c_float), ("in_peak", c_float), ("out_sumsq", c_float), ("out_peak", c_float)]
+
+
 # every symbol include/fastenhancer_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "fe_create": (c_int, [POINTER(fe_config), POINTER(c_void_p)]),
@@ -56,6 +61,9 @@ SYMBOLS = {
     "fe_step_slots_pinned": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),
     "fe_step_streams": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
     "fe_step_streams_pinned": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
+    "fe_step_streams_ctl": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "fe_step_streams_ctl_pinned": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p,
+                                           c_void_p]),
     "fe_step_host": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p]),
     "fe_spec_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "fe_set_time_pipeline": (c_int, [c_void_p, c_int]),

@@ -1277,14 +1277,43 @@ int fe_step_slots_pinned(fe_handle* h, const float* wav_in_host, size_t in_strid
 static_assert(sizeof(fe_stream_desc) == 24 && sizeof(fe::StreamDesc) == 24 && offsetof(fe_stream_desc, slot) == offsetof(fe::StreamDesc, slot) &&
               offsetof(fe_stream_desc, hops) == offsetof(fe::StreamDesc, hops) && offsetof(fe_stream_desc, in_offset) == offsetof(fe::StreamDesc, in_offset) &&
               offsetof(fe_stream_desc, out_offset) == offsetof(fe::StreamDesc, out_offset), "fe_stream_desc is the kernels' StreamDesc");
+static_assert(sizeof(fe_stream_levels) == 16 && sizeof(fe::StreamLevels) == 16 && offsetof(fe_stream_levels, in_peak) == offsetof(fe::StreamLevels, in_peak) &&
+              offsetof(fe_stream_levels, out_sumsq) == offsetof(fe::StreamLevels, out_sumsq) && offsetof(fe_stream_levels, out_peak) == offsetof(fe::StreamLevels, out_peak),
+              "fe_stream_levels is the kernels' StreamLevels");
+// min_gain / levels (fe_step_streams_ctl[_pinned]; null from fe_step_streams[_pinned]): the two slot-indexed tables, `bytes` each from p.  Device memory
+// is handed to the kernel as it comes, page-locked host memory as its device view; memory the device cannot reach (pageable host memory would
+// make the kernel take a page fault) is refused here, before any launch.
+static int table_view(const void* p, size_t bytes, const char* fn, const char* what, const void** dev) {
+    *dev = p;
+    if (!p) return FE_OK;
+    const char* ends[2] = {static_cast<const char*>(p), static_cast<const char*>(p) + (bytes - 1)};
+    const char* dv[2] = {nullptr, nullptr};
+    for (int i = 0; i < 2; ++i) {
+        hipPointerAttribute_t at{};
+        bool ok = hipPointerGetAttributes(&at, ends[i]) == hipSuccess && (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeHost || at.type == hipMemoryTypeManaged);
+        void* dp = const_cast<char*>(ends[i]);
+        if (ok && at.type == hipMemoryTypeHost) ok = hipHostGetDevicePointer(&dp, const_cast<char*>(ends[i]), 0) == hipSuccess && dp != nullptr;
+        (void)hipGetLastError();        // (a refused lookup must not surface as the error of a later launch)
+        if (!ok)
+            return fail(FE_ERR_INVALID_ARG, "%s: %s is neither device memory nor page-locked host memory mapped for this device (%s byte of the table)", fn, what,
+                        i ? "last" : "first");
+        dv[i] = static_cast<const char*>(dp);
+    }
+    if (dv[1] - dv[0] != ends[1] - ends[0]) return fail(FE_ERR_INVALID_ARG, "%s: %s spans more than one allocation", fn, what);
+    *dev = dv[0];
+    return FE_OK;
+}
 static int step_streams(fe_handle* h, const char* fn, bool pinned, const void* wav_in, size_t in_count, float* state_dev, int capacity,
-                        const fe_stream_desc* desc_dev, void* wav_out, size_t out_count, int n, int T_max, int format, void* stream) {
+                        const fe_stream_desc* desc_dev, void* wav_out, size_t out_count, int n, int T_max, int format, void* stream,
+                        const float* min_gain = nullptr, fe_stream_levels* levels = nullptr) {
     return slotted_step(h, fn, true,
         [&]() -> int {
             if (!wav_in || !state_dev || !desc_dev || !wav_out || n <= 0 || T_max <= 0 || capacity < n || in_count == 0 || out_count == 0)
                 return fail(FE_ERR_INVALID_ARG, "%s: bad argument (need non-null pointers to at least one element, 1 <= n <= capacity, T_max >= 1)", fn);
             if (format != FE_AUDIO_F32 && format != FE_AUDIO_S16)
                 return fail(FE_ERR_INVALID_ARG, "%s: format %d is neither FE_AUDIO_F32 (0) nor FE_AUDIO_S16 (1)", fn, format);
+            if (reinterpret_cast<size_t>(levels) & 15)
+                return fail(FE_ERR_INVALID_ARG, "%s: levels is not 16-byte aligned (the kernel writes each row as one 16-byte store)", fn);
             return FE_OK;
         },
         [&]() -> int {
@@ -1303,6 +1332,13 @@ static int step_streams(fe_handle* h, const char* fn, bool pinned, const void* w
             own.in_count = in_count; own.out_count = out_count;
             own.format = format;
             own.pinned = pinned ? 1 : 0;
+            const void* gains = nullptr;
+            const void* rows = nullptr;
+            int rc = table_view(min_gain, (size_t)capacity * sizeof(float), fn, "min_gain", &gains);
+            if (rc == FE_OK) rc = table_view(levels, (size_t)capacity * sizeof(fe_stream_levels), fn, "levels", &rows);
+            if (rc != FE_OK) return rc;
+            own.min_gain = static_cast<const float*>(gains);
+            own.levels = static_cast<fe::StreamLevels*>(const_cast<void*>(rows));
             return launch_fe_step(h, fn, fe::STEP_STREAMS, own, static_cast<const float*>(in), 0, state_dev, const_cast<float*>(static_cast<const float*>(out)), 0,
                                   n, T_max, stream);       // (the audio is typed by a.format in the kernel)
         });
@@ -1316,6 +1352,19 @@ int fe_step_streams(fe_handle* h, const void* wav_in_dev, size_t in_count, float
 int fe_step_streams_pinned(fe_handle* h, const void* wav_in_host, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,
                            void* wav_out_host, size_t out_count, int n, int T_max, int format, void* stream) {
     return step_streams(h, "fe_step_streams_pinned", true, wav_in_host, in_count, state_dev, capacity, desc_dev, wav_out_host, out_count, n, T_max, format, stream);
+}
+
+int fe_step_streams_ctl(fe_handle* h, const void* wav_in_dev, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,
+                        void* wav_out_dev, size_t out_count, int n, int T_max, int format, const float* min_gain, fe_stream_levels* levels, void* stream) {
+    return step_streams(h, "fe_step_streams_ctl", false, wav_in_dev, in_count, state_dev, capacity, desc_dev, wav_out_dev, out_count, n, T_max, format, stream,
+                        min_gain, levels);
+}
+
+int fe_step_streams_ctl_pinned(fe_handle* h, const void* wav_in_host, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,
+                               void* wav_out_host, size_t out_count, int n, int T_max, int format, const float* min_gain, fe_stream_levels* levels,
+                               void* stream) {
+    return step_streams(h, "fe_step_streams_ctl_pinned", true, wav_in_host, in_count, state_dev, capacity, desc_dev, wav_out_host, out_count, n, T_max, format,
+                        stream, min_gain, levels);
 }
 
 // The streaming state of `capacity` streams as a list of regions [rows][capacity][len], in the order of the layout (include/fastenhancer_hip.h):

@@ -270,6 +270,9 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
         const int lane = tid & 63;
         const int ws = wave & 3, wh = wave >> 2;          // SIMD slot, half
         const int li = lane & 15, lg = lane >> 4;
+        StreamCtl<STRM> ctl;                              // (STRM) the limit and the meters' partials of this stream
+        // (the meters' hand-over uses the head of PT while other waves may still read the iSTFT's quarters: PT lies beyond them)
+        static_assert(!STRM || (L::PT - L::FFT_A >= L::END_FFT && S::F1 * S::LDP >= 4 * kWaves8), "levels_put / levels_store: PT clear of the FFT buffers");
         float* cst = a.cache_stft + (size_t)sb * OVL;
         float* cis = a.cache_istft + (size_t)sb * OVL;
         const int fpar = (S::NU & 1) ? (fc & 1) : 0;
@@ -304,6 +307,14 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
             }
             // cache' = frame[H:], straight from the registers (every load of the old cache has landed: its value went to LDS above)
             if (tid >= H) cst[tid - H] = fv;
+            if constexpr (STRM) {
+                // the meters' input side: the hop is the frame's samples n >= OVL (on the waves that hold one; the others go on to the DFT)
+                if (a.levels != nullptr && 64 * (wave + 1) > OVL) {
+                    const float x = tid >= OVL ? fv : 0.0f;
+                    ctl.lv.in_ss = wave_sum(0.0f, x * x);
+                    ctl.lv.in_pk = wave_max(0.0f, fabsf(x));
+                }
+            }
             FE_CLK(1);
             float* nyq = a.dbg ? a.dbg + (size_t)b * a.dbg_stride + DebugLayout<S>::offset(0) + 2 * F0 : nullptr;
             if (wave < 4) Dft<S>::template forward<false>(q0, q3, tw, dc, wave, lane, nyq);
@@ -767,6 +778,7 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
         float* PT = smem + L::PT;
         typename Dft<S>::InvConst idc;
         float mb0 = 0.0f, mb1 = 0.0f;                  // the mask's two biases
+        if constexpr (STRM) { if (a.min_gain != nullptr) ctl.graw = a.min_gain[sb]; }     // (the suppression limit, in flight across dec_post)
         {
             FE8_BEGIN_UNIT(S::U_POST);
             const float* xa = Wx + (16 * ws + li + 1) * LDC + lg;
@@ -818,6 +830,22 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
                 q3[f] = yr;
                 q3[N / 2 + f] = yi;
             }
+            // (STRM) the suppression limit: a stream that has one does its bins again with the lifted mask, each thread over the values it has
+            // just written, through one wave-uniform branch.  The loop above stays as every other instantiation compiles it, contraction for
+            // contraction, so a stream without a limit keeps the bits of fe_step_slots.
+            if constexpr (STRM) {
+                static_assert(!DBG, "the second pass writes the iSTFT's input only: no debug dump");
+                if (a.min_gain != nullptr) ctl.m_min = stream_mask_floor(ctl.graw, a.compression);
+                if (ctl.m_min > 0.0f) {
+                    const float e = 1.0f / a.compression - 1.0f;
+                    for (int f = tid; f < F0; f += NTH) {
+                        float yr, yi;
+                        limited_bin<S>(PT, sc, f, b0, b1, ctl.m_min, e, yr, yi);
+                        q3[f] = yr;
+                        q3[N / 2 + f] = yi;
+                    }
+                }
+            }
         }
         __syncthreads();
 
@@ -834,6 +862,16 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
             const float xo = (q0[pi] + q1[pi]) * ow + oc;
             // one sample per thread: the first H go out, the rest is the new overlap tail (the old tail was read before the barrier)
             if constexpr (STRM) {
+                // the meters' output side: the H samples that go out, as floats; then the waves' partials meet in the transposed-conv buffer,
+                // idle since the mask phase
+                if (a.levels != nullptr) {
+                    if (64 * wave < H) {
+                        const float x = tid < H ? xo : 0.0f;
+                        ctl.lv.out_ss = wave_sum(0.0f, x * x);
+                        ctl.lv.out_pk = wave_max(0.0f, fabsf(x));
+                    }
+                    levels_put(PT, ctl.lv, wave, lane);
+                }
                 if (a.format) {
                     // int16 PCM: even lanes pack two samples, lane 8j gathers the four words of lanes 8j, 8j + 2, 8j + 4, 8j + 6 (every lane shuffles)
                     const int qv = pcm16_out(xo);
@@ -887,6 +925,8 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
                 }
             }
             if constexpr (PERSIST) __syncthreads();               // (the next stream's frame load reuses q0)
+            else if constexpr (STRM) { if (a.levels != nullptr) __syncthreads(); }      // (one stream per workgroup: a barrier for the meters alone)
+            if constexpr (STRM) { if (a.levels != nullptr && tid0 == 0) levels_store<kWaves8>(a.levels + sb, PT); }
         }
         FE_CLK(13);
         b += (int)gridDim.x;

@@ -347,11 +347,17 @@ struct StreamDesc {           // = fe_stream_desc of the C ABI (24 bytes)
     int slot, hops;
     long long in_offset, out_offset;
 };
+struct StreamLevels {         // = fe_stream_levels of the C ABI (16 bytes): sum of squares and max |x| of a stream's hops * H input / output samples
+    float in_sumsq, in_peak, out_sumsq, out_peak;
+};
 struct StreamFrameArgs : SlotFrameArgs {
     const StreamDesc* desc;   // [B] device memory, read when the kernel runs
     size_t in_count, out_count;   // elements of wav_in / wav_out: no access outside [0, count)
     int format;               // 0 = float32, 1 = int16 PCM (FE_AUDIO_*)
     int pinned;               // host side only (fe_impl.h: the kernel's name): the audio is page-locked host memory
+    // fe_step_streams_ctl[_pinned]; either may be null (both null: fe_step_streams).  Slot-indexed, [capacity], read / written when the kernel runs.
+    const float* min_gain;    // suppression limit: the least net amplitude gain of a bin, linear, clamped to [0, 1]; 0 / NaN = off
+    StreamLevels* levels;     // one 16-byte row per stream that advanced (16-byte aligned)
 };
 template <bool SLOT, bool STRM = false> struct KernelArgs { using type = FrameArgs; };
 template <> struct KernelArgs<true, false> { using type = SlotFrameArgs; };
@@ -799,6 +805,73 @@ __device__ __forceinline__ float row16_allreduce(float x, OP op) {
     x = op(x, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x122, 0xf, 0xf, false)));   // row_ror:2
     x = op(x, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x121, 0xf, 0xf, false)));   // row_ror:1
     return x;
+}
+
+// ---- fe_step_streams_ctl (the STRM instantiations): the suppression limit and the level meters.
+__device__ __forceinline__ float wave_uniform(float x) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x))); }
+// The limit: min_gain is the least net amplitude gain of a bin.  The gain of mask M in the un-compressed domain is |M|^(1 / c), so the mask's
+// magnitude is lifted to m_min = min_gain^c where it is below, its phase kept: M' = M max(1, m_min / |M|), and (m_min, 0) where |M| is 0 (or
+// |M|^2 below the normal range, where v_rsq_f32 has no answer).  graw: the table's entry as loaded; clamped to [0, 1], NaN = 0 = off.
+__device__ __forceinline__ float stream_mask_floor(float graw, float compression) {
+    float g = wave_uniform(graw);
+    g = g == g ? fminf(fmaxf(g, 0.0f), 1.0f) : 0.0f;
+    return wave_uniform(pow_f(g, compression));
+}
+__device__ __forceinline__ void mask_floor(float& m0, float& m1, float m_min) {
+    const float n2 = m0 * m0 + m1 * m1;
+    const float s = fmaxf(1.0f, m_min * __builtin_amdgcn_rsqf(n2));
+    const bool zero = n2 < 1.17549435e-38f;
+    m0 = zero ? m_min : m0 * s;
+    m1 = zero ? 0.0f : m1 * s;
+}
+// A limited stream's bin f, done again after the mask loop (its second pass, fe_frame_kernel / fe_frame8_kernel "mask, un-compress"): the mask as
+// the loop derives it - the two biases, the transposed conv's overlapping rows from PT ([F1][LDP]), the shape's mask function - lifted to m_min,
+// times the compressed spectrum sc, un-compressed (e = 1 / c - 1).  One text for both kernels; the mask loops themselves keep theirs: called from
+// them, even the mask's derivation alone as a helper changed the code of 14 of FastEnhancer_B's 24 non-STRM kernels.
+template <class S>
+__device__ __forceinline__ void limited_bin(const float* PT, const float* sc, int f, float b0, float b1, float m_min, float e, float& yr, float& yi) {
+    const int q = f + 2, j1 = q & 3, i1 = q >> 2;
+    float m0 = b0, m1 = b1;
+    if (i1 < S::F1) { m0 += PT[i1 * S::LDP + j1]; m1 += PT[i1 * S::LDP + 8 + j1]; }
+    if (i1 >= 1) { m0 += PT[(i1 - 1) * S::LDP + j1 + 4]; m1 += PT[(i1 - 1) * S::LDP + 8 + j1 + 4]; }
+    if constexpr (S::EPM != kMaskNone) { m0 = mask_f<S::EPM>(m0); m1 = mask_f<S::EPM>(m1); }
+    mask_floor(m0, m1, m_min);
+    const float xr = sc[2 + f], xi = sc[S::LDS_S + 2 + f];
+    yr = xr * m0 - xi * m1;
+    yi = xr * m1 + xi * m0;
+    const float g = pow_f(sqrtf(yr * yr + yi * yi), e);
+    yr *= g; yi *= g;
+}
+// The meters: a wave's partial sums of squares and peaks, wave-uniform (DPP rows, then the row swaps: the same order on every run and in every
+// instantiation), carried in scalar registers from the hop load to the end of the stream; there each wave leaves its four words in LDS
+// (levels_put, before a barrier) and thread 0 combines them, wave 0 first, and stores the stream's row in one piece (levels_store, after it).
+struct LevelAcc { float in_ss = 0.0f, in_pk = 0.0f, out_ss = 0.0f, out_pk = 0.0f; };
+// what a frame kernel carries for the two controls: nothing at all outside the STRM instantiations (not even a dead initialiser: the other
+// instantiations keep their code, instruction for instruction)
+template <bool STRM> struct StreamCtl {};
+template <> struct StreamCtl<true> {
+    LevelAcc lv;                  // the meters' partials of this wave, over the stream's hops
+    float graw = 0.0f;            // the stream's entry of min_gain, in flight across dec_post
+    float m_min = 0.0f;           // 0 = no limit: the mask loop as it is without one
+};
+__device__ __forceinline__ float wave_sum(float acc, float v) {
+    return wave_uniform(acc + rows_allreduce(row16_allreduce(v, [](float x, float y) { return x + y; }), [](float x, float y) { return x + y; }));
+}
+__device__ __forceinline__ float wave_max(float acc, float v) {
+    return wave_uniform(fmaxf(acc, rows_allreduce(row16_allreduce(v, [](float x, float y) { return fmaxf(x, y); }), [](float x, float y) { return fmaxf(x, y); })));
+}
+__device__ __forceinline__ void levels_put(float* red, const LevelAcc& lv, int wave, int lane) {
+    if (lane == 0) { red[4 * wave] = lv.in_ss; red[4 * wave + 1] = lv.in_pk; red[4 * wave + 2] = lv.out_ss; red[4 * wave + 3] = lv.out_pk; }
+}
+template <int NW>
+__device__ __forceinline__ void levels_store(StreamLevels* row, const float* red) {
+    f32x4 r = {red[0], red[1], red[2], red[3]};
+#pragma unroll
+    for (int w = 1; w < NW; ++w) {
+        r[0] += red[4 * w]; r[1] = fmaxf(r[1], red[4 * w + 1]);
+        r[2] += red[4 * w + 2]; r[3] = fmaxf(r[3], red[4 * w + 3]);
+    }
+    *reinterpret_cast<f32x4*>(row) = r;
 }
 
 // ln variant: one norm site.  buf holds the [ROWS x COLS] pre-norm values of the frame (leading dimension LD); the statistics are
@@ -1713,6 +1786,9 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
             continue;
         }
     }
+    StreamCtl<STRM> ctl;                             // (STRM) the limit and the meters' partials of this stream
+    // (the meters' eight-word hand-over uses the head of PT while other waves may still read the iSTFT's quarters: PT lies beyond them)
+    static_assert(!STRM || (L::PT - L::FFT_A >= L::END_FFT && S::F1 * S::LDP >= 4 * kWaves), "levels_put / levels_store: PT clear of the FFT buffers");
     float* cst = a.cache_stft + (size_t)sb * OVL;
     float* cis = a.cache_istft + (size_t)sb * OVL;
     constexpr int NFLAG = S::KB + (S::KT > 1 ? 2 * S::NL : 0);       // counters per stream
@@ -1866,6 +1942,17 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                     if constexpr (HIO) fv[q] = (n < OVL) ? cst[n] : hv[q];          // (the hop was requested ahead: hop_issue)
                     else fv[q] = (n < OVL) ? cst[n] : xin[n - OVL];
                     fw[q] = win[n];
+                }
+                if constexpr (STRM) {
+                    if (a.levels != nullptr) {           // (wave-uniform) the meters' input side: this hop's samples are the frame's n >= OVL
+                        float ss = 0.0f, pk = 0.0f;
+#pragma unroll
+                        for (int q = 0; q < NPT; ++q) {
+                            if (tid + q * kThreads >= OVL) { ss += fv[q] * fv[q]; pk = fmaxf(pk, fabsf(fv[q])); }
+                        }
+                        ctl.lv.in_ss = wave_sum(ctl.lv.in_ss, ss);
+                        ctl.lv.in_pk = wave_max(ctl.lv.in_pk, pk);
+                    }
                 }
                 if constexpr (STRM) {                    // ... of this stream's own count; the next stream's first only if it has one
                     if (t + 1 < t_end) hop_load(sv, t + 1);
@@ -3274,6 +3361,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
         FE_CLK(9);
         // =========================== dec_post (a15) ===========================
         float* PT = smem + L::PT;
+        if constexpr (STRM) { if (a.min_gain != nullptr) ctl.graw = a.min_gain[sb]; }       // (the suppression limit, in flight across dec_post)
         {
             FE_BEGIN_UNIT(S::U_POST);
             if constexpr (NSPLIT) {
@@ -3367,6 +3455,31 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                     }
                 }
             }
+            // (STRM) the suppression limit: a stream that has one does its bins again with the lifted mask, each thread over the values it has
+            // just written, through one wave-uniform branch.  The loop above stays as every other instantiation compiles it, contraction for
+            // contraction, so a stream without a limit keeps the bits of fe_step_slots.  (The packet step is FE_MODE_STREAM without the debug
+            // dump: audio out only.)
+            if constexpr (STRM) {
+                static_assert(!DBG && (MODE == FE_MODE_STREAM || MODE < 0), "the second pass writes the iSTFT's input only: no debug dump, no spectrum out");
+                if (a.min_gain != nullptr) ctl.m_min = stream_mask_floor(ctl.graw, a.compression);
+                if (ctl.m_min > 0.0f) {                  // (MODE < 0: fe_api.hip launches the packet step with FE_MODE_STREAM only)
+                    const float e = 1.0f / a.compression - 1.0f;
+                    for (int f = tid; f < F0; f += kThreads) {
+                        float yr, yi;
+                        limited_bin<S>(PT, sc, f, b0, b1, ctl.m_min, e, yr, yi);
+                        if constexpr (MDFT) {
+                            q3[f] = yr;
+                            q3[N / 2 + f] = yi;
+                        } else if (f == 0) {
+                            fa[0] = make_float2(yr, 0.0f);
+                            fa[F0] = make_float2(0.0f, 0.0f);
+                        } else {
+                            fa[f] = make_float2(yr, yi);
+                            fa[N - f] = make_float2(yr, -yi);
+                        }
+                    }
+                }
+            }
         }
         __syncthreads();
 
@@ -3405,6 +3518,18 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                     xo[n] = y[n].x * invN * ow[q] + oc[q];
                 }
             }
+            if constexpr (STRM) {
+                if (a.levels != nullptr) {               // (wave-uniform) the meters' output side: the frame's first H samples, as floats
+                    float ss = 0.0f, pk = 0.0f;
+#pragma unroll
+                    for (int q = 0; q < NPT; ++q) {
+                        const int n = tid + q * kThreads;                     // (the thread's own stores just above)
+                        if (n < H) { ss += xo[n] * xo[n]; pk = fmaxf(pk, fabsf(xo[n])); }
+                    }
+                    ctl.lv.out_ss = wave_sum(ctl.lv.out_ss, ss);
+                    ctl.lv.out_pk = wave_max(ctl.lv.out_pk, pk);
+                }
+            }
             __syncthreads();
             if constexpr (PIPE) {
                 // the frames overlap-add in a separate launch (istft_ola_kernel): no tail is carried from frame to frame
@@ -3439,10 +3564,13 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                 }
             }
             if constexpr (!PIPE) { for (int m = tid; m < OVL; m += kThreads) cis[m] = xo[m + H]; }
+            // (STRM) after the stream's last hop the waves' partials meet in the transposed-conv buffer, idle since the mask phase
+            if constexpr (STRM) { if (a.levels != nullptr && t + 1 == t_end) levels_put(PT, ctl.lv, wave, lane); }
             __syncthreads();
         }
         FE_CLK(13);
     }
+    if constexpr (STRM) { if (a.levels != nullptr && tid0 == 0) levels_store<kWaves>(a.levels + sb, smem + L::PT); }
     b += PIPE ? a.B : (int)gridDim.x;
     } while (PERSIST && b < a.B);
     FE_CLK(63);

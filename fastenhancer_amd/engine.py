@@ -326,8 +326,21 @@ class Engine:
         self._require_gpu()
         return self.pack_stream_desc(rows).to(self.device)
 
-    def _step_streams(self, wav_in: Tensor, state: Tensor, capacity: int, desc, wav_out: Tensor, T_max: int, pinned: bool) -> Tensor:
-        name = "fe_step_streams" + ("_pinned" if pinned else "")
+    @staticmethod
+    def _stream_table(what: str, t: Optional[Tensor], shape) -> Optional[Tensor]:
+        """min_gain [capacity] / levels [capacity, 4] of the ctl steps: float32, contiguous, on the device or in page-locked host memory"""
+        if t is None:
+            return None
+        if not isinstance(t, Tensor) or t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous float32 tensor {list(shape)}")
+        if not t.is_cuda and not (t.device.type == "cpu" and t.is_pinned()):
+            raise ValueError(f"{what} must be a device tensor or a CPU tensor in page-locked memory (pin_memory())")
+        return t
+
+    def _step_streams(self, wav_in: Tensor, state: Tensor, capacity: int, desc, wav_out: Tensor, T_max: int, pinned: bool,
+                      min_gain: Optional[Tensor] = None, levels: Optional[Tensor] = None) -> Tensor:
+        ctl = min_gain is not None or levels is not None
+        name = "fe_step_streams" + ("_ctl" if ctl else "") + ("_pinned" if pinned else "")
         for what, x in (("wav_in", wav_in), ("wav_out", wav_out)):
             if not isinstance(x, Tensor) or x.dtype not in (torch.float32, torch.int16) or not x.is_contiguous() or x.numel() == 0:
                 raise ValueError(f"{what} must be a contiguous, non-empty float32 or int16 tensor")
@@ -340,28 +353,36 @@ class Engine:
                 raise ValueError(f"{what} must be a device tensor ({name}_pinned takes page-locked host memory)")
         if T_max < 1:
             raise ValueError("T_max must be at least 1")
+        min_gain = self._stream_table("min_gain", min_gain, (capacity,))
+        levels = self._stream_table("levels", levels, (capacity, 4))
         d = self._stream_desc_tensor(desc, capacity, T_max, wav_in.numel(), wav_out.numel())
         self._require_gpu()
         assert state.is_cuda and state.numel() == self.state_floats(capacity) and state.is_contiguous()
         fmt = _lib.FE_AUDIO_S16 if wav_in.dtype == torch.int16 else _lib.FE_AUDIO_F32
+        tables = (_ptr(min_gain), _ptr(levels)) if ctl else ()
         with torch.cuda.device(self.device):
             _lib.check(getattr(self.lib, name)(self._h, _ptr(wav_in), wav_in.numel(), _ptr(state), int(capacity), _ptr(d), _ptr(wav_out), wav_out.numel(),
-                                               d.shape[0], int(T_max), fmt, _stream(self.device)), name)
-        self._desc_keep = d          # (alive until the next call - the launch is asynchronous)
+                                               d.shape[0], int(T_max), fmt, *tables, _stream(self.device)), name)
+        self._desc_keep = (d, min_gain, levels)          # (alive until the next call - the launch is asynchronous)
         if pinned:
             self._pinned_keep = (wav_in, wav_out)
         return wav_out
 
-    def step_streams(self, wav_in: Tensor, state: Tensor, capacity: int, desc, wav_out: Tensor, T_max: int = 1) -> Tensor:
+    def step_streams(self, wav_in: Tensor, state: Tensor, capacity: int, desc, wav_out: Tensor, T_max: int = 1, *,
+                     min_gain: Optional[Tensor] = None, levels: Optional[Tensor] = None) -> Tensor:
         """fe_step_streams: every stream of `desc` advances its own number of hops (0 .. T_max), reading wav_in [in_offset + t*H ...] and
         writing wav_out [out_offset + t*H ...] - flat device buffers, both float32 or both int16 PCM (full scale 32768).  desc: a list of
-        (slot, hops, in_offset, out_offset) (checked) or a CUDA int32 tensor [n, 6] (pack_stream_desc; checked by the kernel only)."""
-        return self._step_streams(wav_in, state, capacity, desc, wav_out, T_max, pinned=False)
+        (slot, hops, in_offset, out_offset) (checked) or a CUDA int32 tensor [n, 6] (pack_stream_desc; checked by the kernel only).
+        min_gain / levels (fe_step_streams_ctl, when either is given): float32 tables indexed by SLOT, on the device or in page-locked host
+        memory, read and written by the kernel when it runs.  min_gain [capacity]: the least net amplitude gain of a bin, linear in [0, 1]
+        (0 = no limit).  levels [capacity, 4]: (in_sumsq, in_peak, out_sumsq, out_peak) of every stream that advanced at least one hop."""
+        return self._step_streams(wav_in, state, capacity, desc, wav_out, T_max, pinned=False, min_gain=min_gain, levels=levels)
 
-    def step_streams_pinned(self, wav_in: Tensor, state: Tensor, capacity: int, desc, wav_out: Tensor, T_max: int = 1) -> Tensor:
+    def step_streams_pinned(self, wav_in: Tensor, state: Tensor, capacity: int, desc, wav_out: Tensor, T_max: int = 1, *,
+                            min_gain: Optional[Tensor] = None, levels: Optional[Tensor] = None) -> Tensor:
         """fe_step_streams_pinned: step_streams with wav_in / wav_out in page-locked HOST memory, read and written by the kernel over PCIe.
-        Asynchronous on the current stream: synchronise it before reading wav_out or rewriting wav_in."""
-        return self._step_streams(wav_in, state, capacity, desc, wav_out, T_max, pinned=True)
+        Asynchronous on the current stream: synchronise it before reading wav_out (or a pinned levels table) or rewriting wav_in."""
+        return self._step_streams(wav_in, state, capacity, desc, wav_out, T_max, pinned=True, min_gain=min_gain, levels=levels)
 
     def new_pinned(self, *shape: int, dtype=torch.float32) -> Tensor:
         """a zeroed page-locked host tensor (the audio of the pinned steps)"""

@@ -8,12 +8,16 @@ ready on each tick.
 PacketPool: a StreamPool for PACKET audio - int16 PCM that arrives in pieces of any length (10 or 20 ms packets against a hop of 256
 samples, with network jitter).  push() copies a packet into the stream's page-locked ring, tick() is ONE fe_step_streams_pinned launch in
 which every stream advances by the whole hops it has, pull() returns the enhanced PCM.  The kernel reads and writes the rings themselves.
+set_suppression_limit() bounds how far a stream may be attenuated and levels() reads the stream's input / output level meters: both run
+inside the same launch (fe_step_streams_ctl_pinned).
 
 Moving a stream: export() gathers the state records of open slots (fe_state_export_slots: a record is the stream's state as a capacity-1
 state buffer), adopt() opens slots for records made elsewhere, move() takes a live stream to another pool - of another engine of the same
 config, on another GPU if need be - and resize() grows or shrinks a pool in place.  PacketPool carries the stream's rings along."""
 from __future__ import annotations
 
+import math
+from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
 
 import torch
@@ -156,15 +160,52 @@ def carry_ring(src_in: Tensor, src_out: Tensor, pushed: int, stepped: int, pulle
     return pushed, stepped, pulled
 
 
+def _dbfs(amplitude: float) -> float:
+    return 20.0 * math.log10(amplitude) if amplitude > 0.0 else -math.inf
+
+
+@dataclass(frozen=True)
+class StreamLevels:
+    """What the kernel metered for one stream on its last tick with a hop: sum of squares and peak of the `samples` input samples it read
+    and of the output samples it wrote (floats, full scale 1.0; the output before its int16 quantisation).  samples = 0: nothing yet."""
+    in_sumsq: float = 0.0
+    in_peak: float = 0.0
+    out_sumsq: float = 0.0
+    out_peak: float = 0.0
+    samples: int = 0
+
+    @property
+    def in_rms_dbfs(self) -> float:
+        return _dbfs(math.sqrt(self.in_sumsq / self.samples)) if self.samples else -math.inf
+
+    @property
+    def out_rms_dbfs(self) -> float:
+        return _dbfs(math.sqrt(self.out_sumsq / self.samples)) if self.samples else -math.inf
+
+    @property
+    def in_peak_dbfs(self) -> float:
+        return _dbfs(self.in_peak)
+
+    @property
+    def out_peak_dbfs(self) -> float:
+        return _dbfs(self.out_peak)
+
+
 class PacketPool(StreamPool):
     """Streams fed by int16 PCM packets of any length.  Every slot has an input and an output ring of ring_hops * H samples in page-locked
     host memory; a stream's sample k lives at ring position k mod (ring_hops * H) of both.  Between the oldest sample not yet pulled and
-    the newest one pushed a stream may hold one ring of samples: push() refuses what would overwrite them.  No threads, no queues."""
+    the newest one pushed a stream may hold one ring of samples: push() refuses what would overwrite them.  No threads, no queues.
+    meters=True: every tick also meters each launched stream's input and output (levels()).  The level table lives in page-locked host
+    memory - tick() synchronises anyway - and the table of suppression limits, made by the first set_suppression_limit(), on the device;
+    a pool with neither launches plain fe_step_streams_pinned."""
 
-    def __init__(self, engine: Engine, capacity: int, ring_hops: int, T_max: int = 1):
+    def __init__(self, engine: Engine, capacity: int, ring_hops: int, T_max: int = 1, meters: bool = False):
         super().__init__(engine, capacity)
         if ring_hops < 1 or T_max < 1:
             raise ValueError("ring_hops and T_max must be at least 1")
+        self._gain: Optional[Tensor] = None                # [capacity] linear least gain per slot, 0 = off
+        self._levels: Optional[Tensor] = engine.new_pinned(self.capacity, 4) if meters else None
+        self._level_samples = [0] * self.capacity          # samples behind each level row (0: no row yet)
         self.H = int(engine.cfg.hop_size)
         self.ring = int(ring_hops) * self.H
         self.T_max = int(T_max)
@@ -175,17 +216,70 @@ class PacketPool(StreamPool):
         self._stepped = [0] * self.capacity
         self._pulled = [0] * self.capacity
 
+    def _reset_ctl(self, slot: int) -> None:
+        """limit off, no level row"""
+        if self._gain is not None:
+            self._gain[slot] = 0.0
+        if self._levels is not None:
+            self._levels[slot] = 0.0
+        self._level_samples[slot] = 0
+
     def open(self) -> int:
         slot = super().open()
         self._pushed[slot] = self._stepped[slot] = self._pulled[slot] = 0
+        self._reset_ctl(slot)
         return slot
 
     def adopt(self, records: Tensor) -> List[int]:
-        """StreamPool.adopt; the adopted streams start with empty rings (move() carries a stream's rings along)."""
+        """StreamPool.adopt; the adopted streams start with empty rings, no limit and no level row (move() carries a stream's rings and
+        limit along)."""
         slots = super().adopt(records)
         for slot in slots:
             self._pushed[slot] = self._stepped[slot] = self._pulled[slot] = 0
+            self._reset_ctl(slot)
         return slots
+
+    # ---- the suppression limit and the level meters (fe_step_streams_ctl_pinned)
+    @staticmethod
+    def _limit_gain(db: Optional[float]) -> float:
+        """dB (<= 0; None or -inf: off) -> the linear least gain of the kernel's table (0 = off)"""
+        if db is None:
+            return 0.0
+        db = float(db)
+        if math.isnan(db) or db > 0.0:
+            raise ValueError(f"a suppression limit is a level in dB at or below 0 (None or -inf: no limit), got {db}")
+        return 0.0 if math.isinf(db) else 10.0 ** (db / 20.0)
+
+    def set_suppression_limit(self, slot: int, db: Optional[float]) -> None:
+        """No bin of the stream is attenuated by more than `db` (-20.0: at most 20 dB of suppression) from the next tick on; None or -inf
+        lifts the limit.  Open streams start without one."""
+        self._check_open(slot)
+        self._set_gain(slot, self._limit_gain(db))
+
+    def _get_gain(self, slot: int) -> float:
+        return 0.0 if self._gain is None else float(self._gain[slot])
+
+    def _set_gain(self, slot: int, gain: float) -> None:
+        if self._gain is None:
+            if gain == 0.0:
+                return
+            self._gain = torch.zeros(self.capacity, dtype=torch.float32, device=getattr(self.engine, "device", None))
+        self._gain[slot] = gain
+
+    def suppression_limit(self, slot: int) -> Optional[float]:
+        """the stream's limit in dB, None when it has none"""
+        self._check_open(slot)
+        gain = self._get_gain(slot)
+        return 20.0 * math.log10(gain) if gain > 0.0 else None
+
+    def levels(self, slot: int) -> StreamLevels:
+        """The level row of the stream's last tick with at least one hop (StreamLevels; samples = 0 before the first)."""
+        self._check_open(slot)
+        if self._levels is None:
+            raise RuntimeError("the pool was made without meters (PacketPool(..., meters=True))")
+        if not self._level_samples[slot]:
+            return StreamLevels()
+        return StreamLevels(*(float(v) for v in self._levels[slot]), samples=self._level_samples[slot])
 
     def move(self, slot: int, dst_pool: "PacketPool") -> int:
         """StreamPool.move with the packet side: what the stream has in flight - samples pushed but not yet stepped, samples stepped but
@@ -199,9 +293,11 @@ class PacketPool(StreamPool):
         if counters[0] - counters[2] > dst_pool.ring:
             raise OverflowError(f"slot {slot}: {counters[0] - counters[2]} samples in flight do not fit the destination ring of {dst_pool.ring} samples")
         src_in, src_out = self.ring_in[slot].clone(), self.ring_out[slot].clone()      # (close() may hand the slot out again)
+        gain = self._get_gain(slot)                         # (the table's own float: the limit moves bit for bit)
         new = super().move(slot, dst_pool)
         p = carry_ring(src_in, src_out, *counters, dst_pool.ring_in[new], dst_pool.ring_out[new])
         dst_pool._pushed[new], dst_pool._stepped[new], dst_pool._pulled[new] = p
+        dst_pool._set_gain(new, gain)
         return new
 
     def resize(self, capacity: int) -> None:
@@ -220,6 +316,15 @@ class PacketPool(StreamPool):
         self.ring_in, self.ring_out = rings
         grow = [0] * (self.capacity - keep)
         self._pushed, self._stepped, self._pulled = (c[:keep] + grow for c in (self._pushed, self._stepped, self._pulled))
+        self._level_samples = self._level_samples[:keep] + grow
+        if self._gain is not None:
+            gain = torch.zeros(self.capacity, dtype=torch.float32, device=self._gain.device)
+            gain[:keep] = self._gain[:keep]
+            self._gain = gain
+        if self._levels is not None:
+            levels = self.engine.new_pinned(self.capacity, 4)
+            levels[:keep] = self._levels[:keep]
+            self._levels = levels
 
     def _check_open(self, slot: int) -> None:
         if slot not in self._open:
@@ -255,10 +360,12 @@ class PacketPool(StreamPool):
                 desc.append((slot, hops, off, off))
         if not desc:
             return desc
-        self.engine.step_streams_pinned(self.ring_in, self.state, self.capacity, desc, self.ring_out, T_max=self.T_max)
+        ctl = {} if self._gain is None and self._levels is None else dict(min_gain=self._gain, levels=self._levels)
+        self.engine.step_streams_pinned(self.ring_in, self.state, self.capacity, desc, self.ring_out, T_max=self.T_max, **ctl)
         self.engine.synchronize()
         for slot, hops, _, _ in desc:
             self._stepped[slot] += hops * self.H
+            self._level_samples[slot] = hops * self.H
         return desc
 
     def pull(self, slot: int) -> Tensor:

@@ -251,6 +251,35 @@ int fe_step_streams(fe_handle* h, const void* wav_in_dev, size_t in_count, float
 int fe_step_streams_pinned(fe_handle* h, const void* wav_in_host, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,
                            void* wav_out_host, size_t out_count, int n, int T_max, int format, void* stream);
 
+/* The packet step with two per-stream controls, both inside the frame kernels of fe_step_streams (the same kernels, the same names from
+ * fe_last_step_kernel, the same host checks, families and refusals): a limit on how far a stream may be attenuated, and input / output level meters.
+ *   min_gain: [capacity] floats indexed by state SLOT, or NULL.  min_gain[slot] is a linear amplitude in [0, 1] (-20 dB = 0.1), clamped to that range
+ *     by the kernel; 0 and NaN mean no limit.  With c = input_compression and M the complex mask of a bin (after the shape's mask function), the
+ *     net amplitude gain of the bin is |M|^(1/c); the kernel applies M' = M max(1, m_min / |M|), m_min = min_gain^c, and M' = (m_min, 0) where
+ *     |M| = 0: the phase is kept, the magnitude lifted to m_min, so no bin is attenuated by more than min_gain.  Everything downstream (complex
+ *     multiply, un-compress, iSTFT; the Nyquist bin stays zero) is unchanged.  The limit touches the output path only: a stream's GRU states,
+ *     K / V rings, conv caches and cache_stft are bit for bit those of the unlimited run; wav_out and cache_istft differ.  A stream with
+ *     min_gain 0 (or a NULL table) takes the code path of fe_step_streams: its results are those, bit for bit.
+ *   levels: [capacity] rows indexed by state SLOT, 16-byte aligned (else FE_ERR_INVALID_ARG), or NULL.  For every stream that advanced at least
+ *     one hop in the call the kernel writes row `slot`, as one 16-byte store: the sum of squares and the largest |x| of its hops * H input
+ *     samples as floats (int16: s / 32768), and of its hops * H output samples as floats, before the int16 quantisation.  Not written: the
+ *     rows of streams with 0 hops, of streams skipped by the bounds check, of slots outside [0, capacity), and of slots the call does not
+ *     name.  No atomics and a fixed order of combination: a row is bitwise reproducible from run to run and does not depend on the stream's
+ *     position in the batch, on device or pinned audio, or on int16 against float32 on s / 32768.  Peaks are exact; sums are fp32 sums.
+ *   Memory: both tables are device memory, or page-locked host memory mapped for the device; pass either kind as it is (a host pointer or
+ *     its device view).  Every call looks both ends of each non-NULL table up (hipPointerGetAttributes, and hipHostGetDevicePointer for host
+ *     memory: host time on the calling thread, no device time), hands the kernel the device view, and refuses memory the device cannot
+ *     reach, or a table that spans two allocations, with FE_ERR_INVALID_ARG before any launch.  The kernel reads min_gain when it runs: a
+ *     captured graph follows a rewritten table.  Level rows in host memory are visible once `stream` has completed.
+ * With both tables NULL the calls are fe_step_streams / fe_step_streams_pinned. */
+typedef struct fe_stream_levels { float in_sumsq, in_peak, out_sumsq, out_peak; } fe_stream_levels;   /* 16 bytes */
+int fe_step_streams_ctl(fe_handle* h, const void* wav_in_dev, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,
+                        void* wav_out_dev, size_t out_count, int n, int T_max, int format, const float* min_gain, fe_stream_levels* levels,
+                        void* stream);
+int fe_step_streams_ctl_pinned(fe_handle* h, const void* wav_in_host, size_t in_count, float* state_dev, int capacity,
+                               const fe_stream_desc* desc_dev, void* wav_out_host, size_t out_count, int n, int T_max, int format,
+                               const float* min_gain, fe_stream_levels* levels, void* stream);
+
 /* The same step for callers whose audio lives in HOST memory (the reference's scripts/test_onnx.py feeds numpy arrays hop by hop):
  * n_calls consecutive fe_step calls of T hops each, hop block c = hops c*T .. c*T+T-1 of
  *   wav_in_host [b*in_stride + t*H + n], wav_out_host [b*out_stride + t*H + n]   (page-locked for asynchronous copies; pageable works, slower)

@@ -1,0 +1,97 @@
+#!/usr/bin/env python3
+"""tools/compare_device_code.sh, function by function: which gfx950 functions of two builds differ?  (no GPU needed)
+   python tools/compare_device_code_per_kernel.py <parent csrc/_obj> <changed csrc/_obj> [--allow REGEX] > profiles/<name>_device_code.txt
+For every *.o of both directories the gfx950 code object is unbundled and split into its functions; of each function the disassembly
+(without addresses and encodings) and the kernel's note metadata (registers, spills, LDS, scratch, kernarg layout) are compared.
+--allow: a regular expression on the name (demangled where a demangler is installed, and mangled) of the functions that are meant to change; any other difference is an error (exit
+status 1).  A change that is confined to some instantiations of a kernel template reports every other function as identical."""
+import argparse
+import os
+import re
+import shutil
+import subprocess
+import sys
+import tempfile
+
+LLVM = os.environ.get("LLVM", "/opt/rocm/lib/llvm/bin")
+FILT = next((p for p in (os.path.join(LLVM, "llvm-cxxfilt"), shutil.which("c++filt")) if p and os.path.exists(p)), None)
+
+
+def run(*cmd):
+    return subprocess.run(cmd, check=True, capture_output=True, text=True).stdout
+
+
+def functions(obj, tmp):
+    """{mangled name: (disassembly, notes)} of the gfx950 code in obj; {} if there is none"""
+    fat, co = os.path.join(tmp, "x.fat"), os.path.join(tmp, "x.co")
+    for f in (fat, co):
+        if os.path.exists(f):
+            os.remove(f)
+    if subprocess.run(["objcopy", f"--dump-section=.hip_fatbin={fat}", obj], capture_output=True).returncode != 0:
+        return {}
+    subprocess.run([f"{LLVM}/clang-offload-bundler", "--type=o", f"--input={fat}", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}",
+                    "--unbundle"], capture_output=True)
+    if not os.path.exists(co) or os.path.getsize(co) == 0:
+        return {}
+    code, name = {}, None
+    for line in run(f"{LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", "--no-leading-addr", co).splitlines():
+        m = re.match(r"^[0-9a-f]* ?<(.+)>:$", line.strip())
+        if m:
+            name = m.group(1)
+            code[name] = []
+        elif name is not None:
+            code[name].append(re.sub(r"\s*// [0-9A-Fa-f]*:.*$", "", line))
+    notes = {}
+    for block in re.split(r"\n(?=\s*- \.agpr_count|\s*- \.args)", run(f"{LLVM}/llvm-readelf", "--notes", co)):
+        m = re.search(r"\.name:\s+(\S+)", block)
+        if m:
+            notes[m.group(1)] = re.sub(r"\.(symbol|name):\s+\S+", "", block)
+    return {k: ("\n".join(v), notes.get(k, "")) for k, v in code.items()}
+
+
+def figures(notes):
+    g = lambda key: (re.search(r"\.%s:\s+(\d+)" % key, notes) or [None, "-"])[1]
+    return (f"vgpr {g('vgpr_count')} agpr {g('agpr_count')} sgpr {g('sgpr_count')} sgpr-spill {g('sgpr_spill_count')} vgpr-spill {g('vgpr_spill_count')} "
+            f"lds {g('group_segment_fixed_size')} scratch {g('private_segment_fixed_size')}")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("parent")
+    ap.add_argument("changed")
+    ap.add_argument("--allow", default=None)
+    args = ap.parse_args()
+    allow = re.compile(args.allow) if args.allow else None
+    names = sorted(set(f for d in (args.parent, args.changed) for f in os.listdir(d) if f.endswith(".o")))
+    bad = total = same = allowed = 0
+    print(f"{'object':<30} {'functions':>9} {'identical':>9} {'changed':>8}")
+    with tempfile.TemporaryDirectory() as tmp:
+        for n in names:
+            pa, pb = os.path.join(args.parent, n), os.path.join(args.changed, n)
+            if not (os.path.exists(pa) and os.path.exists(pb)):
+                print(f"{n:<30} only in one build")
+                bad += 1
+                continue
+            fa, fb = functions(pa, tmp), functions(pb, tmp)
+            if not fa and not fb:
+                continue
+            diff = sorted(k for k in set(fa) | set(fb) if fa.get(k) != fb.get(k))
+            total += len(fb)
+            same += len(fb) - len([k for k in diff if k in fb])
+            print(f"{n:<30} {len(fb):>9} {len(fb) - len([k for k in diff if k in fb]):>9} {len(diff):>8}")
+            for k in diff:
+                dem = run(FILT, k).strip() if FILT else k
+                ok = allow is not None and (allow.search(dem) or allow.search(k)) is not None and k in fa and k in fb
+                allowed += ok
+                bad += not ok
+                print(f"    {'changed (meant to)' if ok else 'CHANGED'}: {dem}")
+                for side, f in (("parent", fa), ("change", fb)):
+                    if k in f:
+                        print(f"        {side}: {figures(f[k][1])}, {f[k][0].count(chr(10)) + 1} lines")
+    print()
+    print(f"{total} functions: {same} identical in code and notes, {allowed} changed as meant to, {bad} other differences")
+    sys.exit(1 if bad else 0)
+
+
+if __name__ == "__main__":
+    main()
