@@ -67,6 +67,8 @@ SYMBOLS = {
     "fe_step_host": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p]),
     "fe_spec_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "fe_set_time_pipeline": (c_int, [c_void_p, c_int]),
+    "fe_step_chunk_work_floats": (c_size_t, [c_void_p, c_int, c_int]),
+    "fe_step_chunk": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p, c_void_p]),
     "fe_set_offline_engine": (c_int, [c_void_p, c_int]),
     "fe_set_step_kernel": (c_int, [c_void_p, c_int]),
     "fe_set_option": (c_int, [c_void_p, c_char_p, c_int]),

@@ -1126,14 +1126,20 @@ static float* stream_io(Args& a, const float* wav_in, size_t in_stride, float* w
 // rest and launches.  own.capacity = the rows of the state (n for the plain flavour).  STEP_PLAIN (fe_step, the debug / profile steps): dbg, clk,
 // dbg_stride.  STEP_SLOTS / STEP_SLOTS_PINNED: slots - the launch fe_step(B = n) makes with every state address taken from (slots[b], capacity);
 // pinned: wav_in / wav_out are device views of page-locked host memory.  STEP_STREAMS: desc, in_count, out_count, format, pinned (no strides).
-static int launch_fe_step(fe_handle* h, const char* fn, fe::StepFlavour flavour, const fe::StreamFrameArgs& own, const float* wav_in, size_t in_stride,
-                          float* state, float* wav_out, size_t out_stride, int n, int T, void* stream) {
-    int rc = ensure_scratch(h, n);
-    if (rc != FE_OK) return rc;
+static fe::StreamFrameArgs fe_step_args(fe_handle* h, const fe::StreamFrameArgs& own, const float* wav_in, size_t in_stride, float* state, float* wav_out,
+                                        size_t out_stride, int n, int T) {
     fe::StreamFrameArgs a = base_args(h, n, T, own);
     const StateLayout L = state_layout(h, own.capacity);
     a.h = stream_io(a, wav_in, in_stride, wav_out, out_stride, state, L);
     a.tk = state + L.tk;
+    return a;
+}
+
+static int launch_fe_step(fe_handle* h, const char* fn, fe::StepFlavour flavour, const fe::StreamFrameArgs& own, const float* wav_in, size_t in_stride,
+                          float* state, float* wav_out, size_t out_stride, int n, int T, void* stream) {
+    int rc = ensure_scratch(h, n);
+    if (rc != FE_OK) return rc;
+    fe::StreamFrameArgs a = fe_step_args(h, own, wav_in, in_stride, state, wav_out, out_stride, n, T);
     const fe::Impl* im = step_impl(h, n, T, a.dbg || a.clk);
     if (!im->launch_step) {      // (a noncausal record; every entry point refuses those models earlier.  The slotted wording names the entry point's family, not fn, as it always has)
         const char* shape = im->name ? im->name : "?";
@@ -1641,6 +1647,58 @@ static int pipe_width(const fe_handle* h, int B, int T, bool offline = false, bo
     return p < T ? p : T;
 }
 
+// frame counters per stream of a time-pipelined launch (fe_kernels.hip.h: NFLAG)
+static size_t pipe_counters(const fe_handle* h) { return (size_t)h->d.KB + (h->d.KT > 1 ? 2 * h->d.NL : 0); }
+
+// floats of the rings a time-pipelined chunk with carried caches needs at width P: dptransformer - per (K / V cache, stream, pair) TA + P
+// slots of a head's channels; time_kernel - per (conv, stream) KT - 1 + P slots of [F1][C1]; 0 for the other variants
+static size_t pipe_ring_floats(const fe_handle* h, int B, int P) {
+    const Dims& d = h->d;
+    if (d.TA) return (size_t)2 * d.KB * B * d.F2 * d.C2 * (d.TA + P);
+    if (d.KT > 1) return (size_t)2 * d.NL * B * (d.KT - 1 + P) * d.F1 * d.C1;
+    return 0;
+}
+
+// The time-pipelined launch of a chunk that starts from the caller's model caches and leaves the new ones - fe_spec_step and fe_step_chunk.
+// a: the launch as the serial walk makes it (a.h / a.tk point into h_dev, the model caches of B streams in C ABI order); P: pipe_width's
+// answer; flags: pipe_counters() x B counters, zeroed here; ring: pipe_ring_floats(h, B, P) floats.  The GRU states are read from and
+// written to h_dev by the kernel itself.  dptransformer / time_kernel (r4v): the frames of a chunk in flight exchange their k / v (their
+// convs' inputs) through rings of L + P slots; the caller's caches go in before the launch and the chunk's last L frames come back after
+// it (ring_in_kernel / ring_out_kernel above).  *refused: the runtime refused the cooperative launch and nothing has been written that
+// the serial walk of the caller's own `a` does not overwrite or ignore.
+static int launch_pipe_carried(fe_handle* h, fe::StreamFrameArgs a, float* h_dev, int B, int T, int P, unsigned int* flags, float* ring,
+                               hipStream_t st, bool* refused) {
+    const Dims& d = h->d;
+    *refused = false;
+    FE_HIP_CHECK(hipMemsetAsync(flags, 0, (size_t)B * pipe_counters(h) * sizeof(unsigned int), st));
+    a.pipe_flags = flags;
+    a.pipe_p = P;
+    const bool rings = d.TA != 0 || d.KT > 1;
+    const int L = d.TA ? d.TA : d.KT - 1, RS = L + P;
+    const int PAIRS = d.TA ? d.F2 * 4 : 1, SZ = d.TA ? d.C2 / 4 : d.F1 * d.C1;
+    const size_t rows = (size_t)(d.TA ? 2 * d.KB : 2 * d.NL) * B * PAIRS, nfl = rows * L * SZ;
+    float* caches = d.TA ? h_dev : h_dev + (size_t)B * d.hstate();
+    float* heads = d.TA ? h_dev + (size_t)B * (d.hstate() - 1) : nullptr;     // (the ring heads sit behind the K / V caches: fe_kernels.hip.h, ring_head0)
+    const unsigned cgrid = (unsigned)((nfl + 255) / 256);
+    if (rings) {
+        hipLaunchKernelGGL(ring_in_kernel, dim3(cgrid), dim3(256), 0, st, caches, heads, ring, nfl, B, PAIRS, SZ, L, RS);
+        if (d.TA) { a.h = ring; a.tatt_base = d.TA; }
+        else { a.tk = ring; a.tk_base = d.KT - 1; }
+    }
+    hipError_t e = hipSuccess;
+    h->impl->launch_pipe(a, st, &e);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        *refused = true;
+        return FE_OK;
+    }
+    if (rings) {
+        hipLaunchKernelGGL(ring_out_kernel, dim3(cgrid), dim3(256), 0, st, ring, caches, heads, nfl, B, SZ, L, RS, T);
+        e = hipGetLastError();
+    }
+    return launch_rc(e);
+}
+
 int fe_set_time_pipeline(fe_handle* h, int frames_in_flight) {
     if (!h) return fail(FE_ERR_INVALID_ARG, "bad argument");
     // The per-frame rings in work_dev (time_kernel inputs, dptransformer K / V, LiSenNet caches) are sized for at most kMaxPipeFrames
@@ -1705,51 +1763,73 @@ int fe_spec_step(fe_handle* h, const float* spec_in_dev, float* h_dev, float* sp
     a.mode = fe::FE_MODE_SPEC;
     if (const int P = pipe_width(h, B, T, false, true)) {
         hipStream_t st = (hipStream_t)stream;
-        const size_t per = (size_t)h->d.KB + (h->d.KT > 1 ? 2 * h->d.NL : 0);      // counters per stream (fe_kernels.hip.h: NFLAG)
-        const size_t nflags = (size_t)h->max_wgs * per;
+        const size_t nflags = (size_t)h->max_wgs * pipe_counters(h);
         if (!h->pipe_flags_dev) FE_HIP_CHECK(hipMalloc(&h->pipe_flags_dev, nflags * sizeof(unsigned int)));
-        FE_HIP_CHECK(hipMemsetAsync(h->pipe_flags_dev, 0, (size_t)B * per * sizeof(unsigned int), st));
-        a.pipe_flags = h->pipe_flags_dev;
-        a.pipe_p = P;
-        // dptransformer / time_kernel (r4v): the frames of a chunk in flight exchange their k / v (their convs' inputs) through rings of
-        // L + P slots; the caller's caches go in before the launch and the chunk's last L frames come back after it (the handle keeps the
-        // rings: grow-only, a first / wider call allocates)
-        const Dims& d = h->d;
-        const bool rings = d.TA != 0 || d.KT > 1;
-        const int L = d.TA ? d.TA : d.KT - 1, RS = L + P;
-        const int PAIRS = d.TA ? d.F2 * 4 : 1, SZ = d.TA ? d.C2 / 4 : d.F1 * d.C1;
-        const size_t rows = (size_t)(d.TA ? 2 * d.KB : 2 * d.NL) * B * PAIRS, nfl = rows * L * SZ;
-        float* caches = d.TA ? h_dev : h_dev + (size_t)B * d.hstate();
-        float* heads = d.TA ? h_dev + (size_t)B * (d.hstate() - 1) : nullptr;     // (the ring heads sit behind the K / V caches: fe_kernels.hip.h, ring_head0)
-        const unsigned cgrid = (unsigned)((nfl + 255) / 256);
-        if (rings) {
-            const size_t need = rows * RS * SZ;
-            if (need > h->spec_ring_floats) {
-                if (h->spec_ring_dev) { FE_HIP_CHECK(hipFree(h->spec_ring_dev)); h->spec_ring_dev = nullptr; h->spec_ring_floats = 0; }
-                FE_HIP_CHECK(hipMalloc(&h->spec_ring_dev, need * sizeof(float)));
-                h->spec_ring_floats = need;
-            }
-            hipLaunchKernelGGL(ring_in_kernel, dim3(cgrid), dim3(256), 0, st, caches, heads, h->spec_ring_dev, nfl, B, PAIRS, SZ, L, RS);
-            if (d.TA) { a.h = h->spec_ring_dev; a.tatt_base = d.TA; }
-            else { a.tk = h->spec_ring_dev; a.tk_base = d.KT - 1; }
+        // (the handle keeps the rings of the dptransformer / time_kernel variants: grow-only, a first / wider call allocates)
+        const size_t need = pipe_ring_floats(h, B, P);
+        if (need > h->spec_ring_floats) {
+            if (h->spec_ring_dev) { FE_HIP_CHECK(hipFree(h->spec_ring_dev)); h->spec_ring_dev = nullptr; h->spec_ring_floats = 0; }
+            FE_HIP_CHECK(hipMalloc(&h->spec_ring_dev, need * sizeof(float)));
+            h->spec_ring_floats = need;
         }
-        h->impl->launch_pipe(a, st, &e);
-        if (e != hipSuccess) {     // the runtime refused co-residency (GPU shared with other work): walk the frames serially
-            (void)hipGetLastError();
-            a.pipe_p = 0;
-            a.pipe_flags = nullptr;
-            a.h = h_dev;
-            a.tk = h_dev + (size_t)B * d.hstate();
-            a.tatt_base = 0;
-            a.tk_base = 0;
-            h->impl->launch_step(a, fe::STEP_PLAIN, h->max_wgs, st, &e);
-        } else if (rings) {
-            hipLaunchKernelGGL(ring_out_kernel, dim3(cgrid), dim3(256), 0, st, h->spec_ring_dev, caches, heads, nfl, B, SZ, L, RS, T);
-            e = hipGetLastError();
-        }
-    } else
+        bool refused = false;
+        rc = launch_pipe_carried(h, a, h_dev, B, T, P, h->pipe_flags_dev, h->spec_ring_dev, st, &refused);
+        if (!refused) return rc;
+        // the runtime refused co-residency (GPU shared with other work): walk the frames serially
+    }
     h->impl->launch_step(a, fe::STEP_PLAIN, h->max_wgs, (hipStream_t)stream, &e);
     return launch_rc(e);
+}
+
+// fe_step_chunk: fe_step(B, T) with the frames of each stream on the time pipeline.  work_dev: frame counters | windowed frames [B][T][N] |
+// rings at the widest pipeline.  The size depends on the model, B and T only - not on fe_set_time_pipeline nor on the device's CUs - so
+// that it is monotone in both and a buffer sized once serves every setting.
+static bool chunk_family(const fe_handle* h) { return h->cfg.arch == FE_ARCH_FASTENHANCER && h->impl && !h->d.BD; }
+
+size_t fe_step_chunk_work_floats(const fe_handle* h, int B, int T) {
+    if (!h || B <= 0 || T < 4 || !chunk_family(h)) return 0;
+    return round4((size_t)B * pipe_counters(h)) + (size_t)B * T * h->d.NFFT + pipe_ring_floats(h, B, kMaxPipeFrames);
+}
+
+// workgroups per stream of fe_step_chunk's pipelined launch (0: fe_step's own launch).  The second launch needs T H >= N - H: the new
+// caches then hold nothing of the old ones.  T >= 4 implies it for every shipped shape but the hop-100 / n_fft-512 and hop-200 / n_fft-1024
+// ones (FastEnhancer_L, dprnn L, 48 kHz L: N - H = 4.12 H): those pipeline from T = 5 on and walk at T = 4.
+static int chunk_pipe_width(const fe_handle* h, int B, int T) {
+    if (!chunk_family(h) || (long)T * h->d.HOP < h->d.NFFT - h->d.HOP) return 0;
+    return pipe_width(h, B, T, false, true);
+}
+
+int fe_step_chunk(fe_handle* h, const float* wav_in_dev, size_t in_stride, float* state_dev, float* wav_out_dev, size_t out_stride, int B, int T,
+                  float* work_dev, void* stream) {
+    // fe_step's checks and refusals, the arguments first (as the pinned and packet steps check theirs)
+    if (!h) return fail(FE_ERR_INVALID_ARG, "null handle");
+    int rc = check_step_args(h, nullptr, "bad argument", wav_in_dev && state_dev && wav_out_dev, B, B, T, in_stride, out_stride);
+    if (rc != FE_OK) return rc;
+    if (h->cfg.arch == FE_ARCH_FASTENHANCER && h->d.BD) return fail(FE_ERR_UNSUPPORTED_CONFIG, "%s", kNoncausalNoStep);
+    const int P = chunk_pipe_width(h, B, T);
+    if (P == 0) return run_step(h, wav_in_dev, in_stride, state_dev, wav_out_dev, out_stride, B, T, nullptr, nullptr, stream);
+    if (!work_dev) return fail(FE_ERR_INVALID_ARG, "fe_step_chunk: null work buffer (fe_step_chunk_work_floats(h, %d, %d) floats)", B, T);
+    rc = check_ready(h);
+    if (rc != FE_OK) return rc;
+    KernelLogScope klog_(h);
+    rc = ensure_scratch(h, B);
+    if (rc != FE_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const Dims& d = h->d;
+    fe::StreamFrameArgs own{};
+    own.capacity = B;
+    fe::StreamFrameArgs a = fe_step_args(h, own, wav_in_dev, in_stride, state_dev, wav_out_dev, out_stride, B, T);     // (fe_step's own argument block)
+    a.frames = work_dev + round4((size_t)B * pipe_counters(h));
+    float* ring = a.frames + (size_t)B * T * d.NFFT;
+    bool refused = false;
+    rc = launch_pipe_carried(h, a, a.h, B, T, P, reinterpret_cast<unsigned int*>(work_dev), ring, st, &refused);
+    // the runtime refused co-residency (GPU shared with other work): walk the frames serially - fe_step's launch, made where fe_step makes it
+    if (refused) return launch_fe_step(h, "fe_step", fe::STEP_PLAIN, own, wav_in_dev, in_stride, state_dev, wav_out_dev, out_stride, B, T, stream);
+    if (rc != FE_OK) return rc;
+    fe::note_kernel("stream_ola_kernel");
+    hipLaunchKernelGGL(fe::stream_ola_kernel, dim3((T * d.HOP + fe::kThreads - 1) / fe::kThreads, B), dim3(fe::kThreads), 0, st,
+                       a.frames, wav_in_dev, in_stride, a.cache_stft, a.cache_istft, wav_out_dev, out_stride, d.NFFT, d.HOP, T);
+    return launch_rc(hipGetLastError());
 }
 
 // floats of the time-batched engine's work buffer: xc | skip | x | gx | hs | frames | carried GRU state, each a multiple of 4 floats

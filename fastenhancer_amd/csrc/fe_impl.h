@@ -136,7 +136,9 @@ void launch_step_impl(const StreamFrameArgs& a, StepFlavour flavour, int max_wgs
 // that the runtime guarantees (or refuses) their co-residency instead of a spin-wait deadlock.
 template <class S>
 void launch_pipe_impl(const FrameArgs& a, hipStream_t st, hipError_t* err) {
-    *err = launch_coop<&fe_frame_kernel<S, false, -1, false, true, true>>("fe_frame_kernel<time-pipelined>", dim3(a.B * a.pipe_p), dim3(kThreads), Lds<S>::BYTES, st, a);
+    // (one instantiation, the mode a run-time fact: fe_step_chunk's launch is named apart)
+    const char* name = a.mode == FE_MODE_STREAM ? "fe_frame_kernel<time-pipelined, streaming>" : "fe_frame_kernel<time-pipelined>";
+    *err = launch_coop<&fe_frame_kernel<S, false, -1, false, true, true>>(name, dim3(a.B * a.pipe_p), dim3(kThreads), Lds<S>::BYTES, st, a);
 }
 
 template <class S>

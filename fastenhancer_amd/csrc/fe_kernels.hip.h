@@ -1602,6 +1602,9 @@ __device__ __forceinline__ void attention_head(const float* G, float* Hl, int ho
 // workgroup to another goes through st_state / ld_state - a plain load or store added to a ring or state would be a silent stale read
 // (no release / acquire fence covers it).  The serial chain is
 // T x (state round trip + one GRU phase) instead of T x (whole frame): ~12 frames in flight for FastEnhancer_B.
+// FE_MODE_STREAM under PIPE (fe_step_chunk): frame t reads its samples from the call's cache_stft and wav_in, both written by nobody
+// during the launch, and stores its windowed frame to a.frames; cache_stft / cache_istft are not written here - what crosses frames on
+// the audio side is stream_ola_kernel's (stft_kernels.hip.h), a second, ordinary launch.
 // SLOT (fe_step_slots): stream b's state is slot a.slots[b] of a state sized for a.capacity streams (sb, nst below); a slot out of range
 // gets zero output rows and neither reads nor writes state.  SLOT = false: sb = b, nst = a.B - the code of the plain step.
 // HIO (fe_step_slots_pinned; SLOT only): the audio is page-locked host memory.  The hop of the next frame a workgroup runs is requested
@@ -1940,6 +1943,8 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                 for (int q = 0; q < NPT; ++q) {
                     const int n = tid + q * kThreads;
                     if constexpr (HIO) fv[q] = (n < OVL) ? cst[n] : hv[q];          // (the hop was requested ahead: hop_issue)
+                    else if constexpr (PIPE) fv[q] = (t * H + n < OVL) ? cst[t * H + n] : xin[n - OVL];   // (fe_step_chunk: chunk sample t H + n - OVL; the
+                                                                                                         //  cache is the call's own, no frame writes it)
                     else fv[q] = (n < OVL) ? cst[n] : xin[n - OVL];
                     fw[q] = win[n];
                 }
@@ -1995,7 +2000,9 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
             __syncthreads();
             FE_KVW(0, W_F0);
             if (mode == FE_MODE_STREAM) {
-                for (int m = tid; m < OVL; m += kThreads) cst[m] = MDFT ? q1[m + H] : fb[m + H].x;   // cache' = frame[H:]
+                // cache' = frame[H:]  (PIPE: the frames of a stream run side by side and all read the call's cache - stream_ola_kernel writes the new one)
+                if constexpr (!PIPE)
+                for (int m = tid; m < OVL; m += kThreads) cst[m] = MDFT ? q1[m + H] : fb[m + H].x;
                 if constexpr (!MDFT) __syncthreads();       // (the FFT's first stage overwrites fb)
             }
             FE_CLK(1);
@@ -3532,7 +3539,8 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
             }
             __syncthreads();
             if constexpr (PIPE) {
-                // the frames overlap-add in a separate launch (istft_ola_kernel): no tail is carried from frame to frame
+                // the frames overlap-add in a separate launch (istft_ola_kernel; fe_step_chunk: stream_ola_kernel, which also writes the two
+                // STFT caches): no tail is carried from frame to frame
                 float* fr = a.frames + ((size_t)b * a.T + t) * N;
                 for (int n = tid; n < N; n += kThreads) fr[n] = xo[n];
             } else if (mode == FE_MODE_STREAM) {

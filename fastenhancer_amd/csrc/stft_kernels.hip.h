@@ -178,4 +178,36 @@ __global__ void __launch_bounds__(kThreads) istft_ola_kernel(const float* __rest
     wav_out[(size_t)b * out_stride + pos] = acc / env;
 }
 
+// The audio side of fe_step_chunk after its time-pipelined launch: the STREAMING overlap-add (scripts/export_onnx.py:48-58 hop after hop) of
+// the chunk's windowed frames [B][T][N], and the two STFT caches the chunk leaves.  Position p of the chunk's overlap-add, p < T H + OVL
+// (OVL = N - H), is the old cache_istft[p] (p < OVL, else 0) plus frames[t][p - t H] of every frame of the chunk that covers p, added OLDEST
+// FIRST - the order in which the hop-by-hop walk adds them (its tail carries the older frames' sum into the newer frame).  p < T H goes to
+// wav_out, the rest is the new cache_istft; the new cache_stft is the last OVL input samples.  Needs T H >= OVL (the host side checks it):
+// then the new caches depend on no old cache value, and thread p < OVL, the only reader of the old cache_istft[p], is also the only writer
+// of the new one - no ordering between threads or workgroups is needed.  One thread per output sample; wav_in and wav_out do not overlap.
+__global__ void __launch_bounds__(kThreads) stream_ola_kernel(const float* __restrict__ frames, const float* __restrict__ wav_in, size_t in_stride,
+                                                             float* __restrict__ cache_stft, float* __restrict__ cache_istft,
+                                                             float* __restrict__ wav_out, size_t out_stride, int N, int H, int T) {
+    const int b = blockIdx.y;
+    const int p = blockIdx.x * kThreads + threadIdx.x;
+    const int OVL = N - H, n_out = T * H;
+    if (p >= n_out) return;
+    const float* fr = frames + (size_t)b * T * N;
+    // the sum at position q: frames ceil((q - N + 1) / H) .. min(q / H, T - 1) on top of `acc`
+    auto ola = [&](int q, float acc) {
+        int t_lo = (q - N + H) / H;
+        t_lo = t_lo < 0 ? 0 : t_lo;
+        int t_hi = q / H;
+        t_hi = t_hi > T - 1 ? T - 1 : t_hi;
+        for (int tt = t_lo; tt <= t_hi; ++tt) acc = fr[(size_t)tt * N + (q - tt * H)] + acc;
+        return acc;
+    };
+    float* cis = cache_istft + (size_t)b * OVL;
+    wav_out[(size_t)b * out_stride + p] = ola(p, p < OVL ? cis[p] : 0.0f);
+    if (p < OVL) {
+        cis[p] = ola(n_out + p, 0.0f);
+        cache_stft[(size_t)b * OVL + p] = wav_in[(size_t)b * in_stride + (n_out - OVL + p)];
+    }
+}
+
 }  // namespace fe

@@ -166,6 +166,52 @@ class Engine:
         """wav_in [B, T*H] (row stride free) -> wav_out [B, T*H]; state updated in place."""
         return self._step(wav_in, state, wav_out, T)
 
+    # ---- few streams, many hops: chunks on the time pipeline (fe_step_chunk)
+    def chunk_work_floats(self, B: int, T: int) -> int:
+        """fe_step_chunk_work_floats: floats of scratch step_chunk needs for at most B streams of at most T hops (0: none)."""
+        return int(self.lib.fe_step_chunk_work_floats(self._h, int(B), int(T)))
+
+    def step_chunk(self, wav_in: Tensor, state: Tensor, wav_out: Optional[Tensor] = None, T: Optional[int] = None, work: Optional[Tensor] = None) -> Tensor:
+        """fe_step_chunk: step(wav_in, state, wav_out, T) with the T hops of each stream on the time pipeline - a recording, or a stream with
+        a backlog.  wav_in [B, T*H] (row stride free; T defaults to wav_in.shape[1] // H) -> wav_out [B, T*H], which must not overlap wav_in;
+        state updated in place.  Results agree with step() to fp32 rounding.  work: a float32 device tensor of at least
+        chunk_work_floats(B, T) floats (the form for graph capture); None: a scratch tensor kept on the engine, grown when needed."""
+        H = self.cfg.hop_size
+        if not isinstance(wav_in, Tensor) or wav_in.dim() != 2 or wav_in.dtype != torch.float32 or wav_in.stride(1) != 1:
+            raise ValueError("wav_in must be a 2-D float32 tensor [B, T*H] with unit stride along the samples")
+        B = wav_in.shape[0]
+        if T is None:
+            T = wav_in.shape[1] // H
+        T = operator.index(T)
+        if B < 1 or T < 1 or wav_in.shape[1] != T * H:
+            raise ValueError(f"wav_in must be [B, T*H] = [B, {T * H}] with B >= 1 and T >= 1, got {tuple(wav_in.shape)}")
+        if wav_out is not None and (not isinstance(wav_out, Tensor) or wav_out.dtype != torch.float32 or tuple(wav_out.shape) != (B, T * H)
+                                    or wav_out.stride(1) != 1):
+            raise ValueError(f"wav_out must be a float32 tensor [{B}, {T * H}] with unit stride along the samples")
+        if not isinstance(state, Tensor) or state.dtype != torch.float32 or state.dim() != 1 or not state.is_contiguous():
+            raise ValueError("state must be a contiguous 1-D float32 tensor (new_state(B))")
+        if work is not None and (not isinstance(work, Tensor) or work.dtype != torch.float32 or not work.is_contiguous()):
+            raise ValueError("work must be a contiguous float32 tensor of chunk_work_floats(B, T) floats")
+        self._require_gpu()
+        if not wav_in.is_cuda or not state.is_cuda or (wav_out is not None and not wav_out.is_cuda) or (work is not None and not work.is_cuda):
+            raise ValueError("wav_in, state, wav_out and work must be device tensors")
+        if state.numel() != self.state_floats(B):
+            raise ValueError(f"state has {state.numel()} floats, a state of {B} streams {self.state_floats(B)}")
+        need = self.chunk_work_floats(B, T)
+        if work is None:
+            if need > 0:
+                if getattr(self, "_chunk_work", None) is None or self._chunk_work.numel() < need:
+                    self._chunk_work = torch.empty(need, dtype=torch.float32, device=self.device)
+                work = self._chunk_work
+        elif work.numel() < need:
+            raise ValueError(f"work has {work.numel()} floats, chunk_work_floats({B}, {T}) = {need}")
+        if wav_out is None:
+            wav_out = torch.empty(B, T * H, dtype=torch.float32, device=wav_in.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.fe_step_chunk(self._h, _ptr(wav_in), wav_in.stride(0) if B > 1 else T * H, _ptr(state), _ptr(wav_out),
+                                              wav_out.stride(0) if B > 1 else T * H, B, T, _ptr(work), _stream(self.device)), "fe_step_chunk")
+        return wav_out
+
     def _slot_tensor(self, slots, capacity: int) -> Tensor:
         """slots -> a device int32 tensor for fe_step_slots / fe_state_reset_slots.  A CUDA int32 tensor is passed through unchecked (the form
         for graph capture: its contents may change from replay to replay); a list or CPU tensor is checked here first - integers in

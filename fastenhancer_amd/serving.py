@@ -70,6 +70,22 @@ class StreamPool:
                 raise ValueError(f"slot {s} is not open")
         return self.engine.step_slots_pinned(wav_in, self.state, self.capacity, list(slots), wav_out=wav_out, T=T)
 
+    def catch_up(self, slot: int, wav_in: Tensor, T: Optional[int] = None) -> Tensor:
+        """A live stream that comes back with a backlog: wav_in [T*H] or [1, T*H] (T defaults to its length // H) -> the T*H output samples
+        [1, T*H], the slot's state advanced by T hops - on the time pipeline (Engine.step_chunk) instead of hop after hop.  The slot's state
+        record is a capacity-1 state: it is exported, stepped as a batch of one, and imported back; no other slot is read or written.
+        The result agrees with step() over the same hops to fp32 rounding."""
+        if slot not in self._open:
+            raise ValueError(f"slot {slot} is not open")
+        if wav_in.dim() == 1:
+            wav_in = wav_in.unsqueeze(0)
+        if wav_in.dim() != 2 or wav_in.shape[0] != 1:
+            raise ValueError("catch_up takes the backlog of ONE stream: wav_in [T*H] or [1, T*H]")
+        rec = self.engine.export_slots(self.state, self.capacity, [slot])
+        out = self.engine.step_chunk(wav_in, rec.view(-1), T=T)
+        self.engine.import_slots(self.state, self.capacity, [slot], rec)
+        return out
+
     # ---- moving live streams (fe_state_export_slots / fe_state_import_slots)
     def export(self, slots: Sequence[int], pinned: bool = False) -> Tensor:
         """The state records [n, record_floats] of the named open slots, on the engine's device or (pinned) in page-locked host memory - then

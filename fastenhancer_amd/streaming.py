@@ -103,14 +103,16 @@ class StreamingModel:
 
 
 @torch.no_grad()
-def enhance_stream(model, wav: Tensor, frames_per_call: int = 1) -> Tensor:
+def enhance_stream(model, wav: Tensor, frames_per_call: int = 1, chunk_hops: tp.Optional[int] = None) -> Tensor:
     """Driver loop of scripts/test_onnx.py:11-60 for wav [B, L] on the model's device:
     clip to [-1,1], right-pad n_fft zeros, run hop by hop (or ``frames_per_call`` hops per
-    launch), drop the n_fft-hop samples of latency, clip."""
+    launch), drop the n_fft-hop samples of latency, clip.
+    ``chunk_hops`` (None = the loops above, exactly; with a number, audio in host memory is copied to the device first and the result is a device tensor, not the pinned host tensor of the loop above): the recording goes through Engine.step_chunk in chunks of that
+    many hops, each on the time pipeline - the same result to fp32 rounding, many times faster for one or a few recordings."""
     cfg: FEConfig = model.cfg
     eng: Engine = model.engine
     N, H = cfg.n_fft, cfg.hop_size
-    if not wav.is_cuda:
+    if not wav.is_cuda and chunk_hops is None:
         # audio in host memory (how scripts/test_onnx.py holds it): hop blocks go over PCIe under the kernels of their neighbours
         # (fe_step_host); the result comes back in pinned host memory
         wav = wav.to(torch.float32).clamp(-1, 1)
@@ -135,9 +137,17 @@ def enhance_stream(model, wav: Tensor, frames_per_call: int = 1) -> Tensor:
     out = torch.empty(B, total, dtype=torch.float32, device=eng.device)
     state = eng.new_state(B)
     t = 0
-    while t < n_hops:
-        T = min(frames_per_call, n_hops - t)
-        eng.step(padded[:, t * H:(t + T) * H], state, out[:, t * H:(t + T) * H], T=T)
-        t += T
+    if chunk_hops is not None:
+        if int(chunk_hops) < 1:
+            raise ValueError("chunk_hops must be at least 1")
+        while t < n_hops:
+            T = min(int(chunk_hops), n_hops - t)
+            eng.step_chunk(padded[:, t * H:(t + T) * H], state, out[:, t * H:(t + T) * H], T=T)
+            t += T
+    else:
+        while t < n_hops:
+            T = min(frames_per_call, n_hops - t)
+            eng.step(padded[:, t * H:(t + T) * H], state, out[:, t * H:(t + T) * H], T=T)
+            t += T
     s = N - H
     return out[:, s:s + length].clamp(-1.0, 1.0)

@@ -307,6 +307,32 @@ int fe_spec_step(fe_handle* h, const float* spec_in_dev, float* h_dev, float* sp
  * a ring of per-frame slots). */
 int fe_set_time_pipeline(fe_handle* h, int frames_in_flight);
 
+/* fe_step for FEW streams and MANY hops - a recording, or a live stream that comes back with a backlog: fe_step(h, ..., B, T, stream) with
+ * the T frames of each stream spread over the time pipeline instead of walked by one workgroup.  Same rows (wav_in [b*in_stride + t*H + n],
+ * wav_out likewise), same state buffer (fe_state_floats(h, B), updated in place), same argument checks, error codes and refusals as fe_step
+ * (the arguments are checked before the handle's weights; the noncausal model is refused with fe_step's message).
+ *   Results: those of fe_step to fp32 rounding, for wav_out and every state tensor (the frames' sums are formed in another order);
+ *     cache_stft, a copy of input samples, bit for bit.  The state it leaves is valid for every other entry point: fe_step, fe_step_slots on
+ *     a capacity-B buffer, export / import; a dptransformer state is a valid ring (head = 0, oldest frame first).
+ *   wav_in and wav_out MUST NOT overlap (fe_step reads a hop before it writes it; here the second launch reads wav_in for the new
+ *     cache_stft after the first has run).
+ *   work_dev: fe_step_chunk_work_floats(h, B, T) floats of scratch - frame counters, the windowed output frames [B][T][N] and, for the
+ *     time_kernel / dptransformer models, the rings their frames exchange conv inputs / K-V through.  The size depends on the model, B and
+ *     T only and is monotone in both: a buffer sized for (B, T) serves every call with at most B streams and at most T hops, whatever
+ *     fe_set_time_pipeline says.  It is an argument, not a buffer of the handle: the call allocates nothing and can be captured in a graph.
+ *     0 for T < 4, for BSRNN / FSPEN / LiSenNet and for a null handle: work_dev may then be NULL.
+ *   Dispatch: the width of the pipeline is fe_spec_step's (T >= 4, at most half as many streams as CUs, fe_set_time_pipeline not 0 or 1),
+ *     and the chunk must cover the overlap: T * H >= N - H.  T >= 4 gives that for every shipped shape except hop 100 / n_fft 512
+ *     (FastEnhancer_L, dprnn L) and hop 200 / n_fft 1024 (48 kHz L), where N - H = 4.12 H: those need T >= 5.
+ *     Where that is 0 - and for BSRNN, FSPEN and LiSenNet, whose streaming steps are not pipelined - the call makes the very launch fe_step
+ *     makes: bit-identical results.  A cooperative launch the runtime refuses falls back to the same walk.
+ *   Two launches: the pipelined frame kernel, whose frames read the call's cache_stft / wav_in and store their windowed output to work_dev,
+ *     then stream_ola_kernel - the streaming overlap-add (old cache_istft, then the covering frames, oldest first) and the two new STFT
+ *     caches.  fe_last_step_kernel: "fe_frame_kernel<time-pipelined, streaming> + stream_ola_kernel [shape B]". */
+size_t fe_step_chunk_work_floats(const fe_handle* h, int B, int T);
+int fe_step_chunk(fe_handle* h, const float* wav_in_dev, size_t in_stride, float* state_dev, float* wav_out_dev, size_t out_stride,
+                  int B, int T, float* work_dev, void* stream);
+
 /* Engine of fe_offline for the default and noncausal FastEnhancer models:
  *   FE_OFFLINE_TIME_BATCHED (the default where compiled; the only engine of the noncausal model): the network is cut at the
  *     blocks' time GRUs and every piece runs over ALL frames of ALL utterances, layer by layer, as the reference's own offline
