@@ -186,8 +186,11 @@ struct fe_handle {
     unsigned int* tb_prog_dev = nullptr;      // fused stages: the scan workgroups' frame counters [KB][2 * max_wgs]
     std::vector<Section> sections;
     size_t blob_floats = 0;
-    float* packed_dev = nullptr;
-    float* tables_dev = nullptr;   // [window | window_istft | twiddle] for the stand-alone STFT launches (lazy)
+    float* packed_dev = nullptr;   // the weight banks: n_banks packed buffers, bank k at packed_dev + k * bank_stride (allocated by the first load)
+    int n_banks = 1;               // fe_set_weight_banks
+    size_t bank_stride = 0;        // floats from one bank to the next: the packed size rounded up to 64 floats (set with packed_dev)
+    std::vector<char> bank_loaded = std::vector<char>(1, 0);      // [n_banks]; bank 0's is `loaded`
+    float* tables_dev = nullptr;  // [window | window_istft | twiddle] for the stand-alone STFT launches (lazy)
     float* skip_dev = nullptr;     // scratch for shapes whose skips do not fit in LDS
     int skip_streams = 0;
     bool loaded = false;
@@ -1025,8 +1028,51 @@ int fe_debug_pack_weights(fe_handle* h, const float* blob_host, size_t nfloats, 
     return FE_OK;
 }
 
-int fe_load_weights(fe_handle* h, const float* blob_dev, size_t nfloats, void* stream) {
+// the families fe_set_weight_banks(n > 1) serves: FastEnhancer's streaming models (what the packet step runs); else the family's name
+static const char* banks_unsupported(const fe_handle* h) {
+    switch (h->cfg.arch) {
+    case FE_ARCH_BSRNN: return "BSRNN";
+    case FE_ARCH_FSPEN: return "FSPEN";
+    case FE_ARCH_LISENNET: return "LiSenNet";
+    default: return h->d.BD ? "noncausal FastEnhancer" : nullptr;
+    }
+}
+
+int fe_weight_banks(const fe_handle* h) { return h ? h->n_banks : 0; }
+
+int fe_set_weight_banks(fe_handle* h, int n_banks, void* stream) {
+    if (!h) return fail(FE_ERR_INVALID_ARG, "null handle");
+    if (n_banks < 1 || n_banks > FE_MAX_WEIGHT_BANKS)
+        return fail(FE_ERR_INVALID_ARG, "fe_set_weight_banks: n_banks %d outside [1, FE_MAX_WEIGHT_BANKS = %d]", n_banks, FE_MAX_WEIGHT_BANKS);
+    if (n_banks > 1)
+        if (const char* family = banks_unsupported(h))
+            return fail(FE_ERR_UNSUPPORTED_CONFIG, "fe_set_weight_banks: weight banks are built for the FastEnhancer streaming models (default, time_kernel, ln, "
+                        "dprnn, dptransformer), which fe_step_streams_banked steps; this is a %s handle (one bank)", family);
+    if (n_banks == h->n_banks) return FE_OK;
+    if (h->packed_dev) {      // the banks that survive move to an allocation of the new size; every launch that reads the old one has completed before it goes
+        const size_t keep = (size_t)std::min(n_banks, h->n_banks) * h->bank_stride;
+        float* fresh = nullptr;
+        FE_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+        FE_HIP_CHECK(hipMalloc(&fresh, (size_t)n_banks * h->bank_stride * sizeof(float)));
+        hipError_t e = hipMemset(fresh, 0, (size_t)n_banks * h->bank_stride * sizeof(float));
+        if (e == hipSuccess) e = hipMemcpy(fresh, h->packed_dev, keep * sizeof(float), hipMemcpyDeviceToDevice);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) { (void)hipFree(fresh); return fail(FE_ERR_HIP, "fe_set_weight_banks: %s", hipGetErrorString(e)); }
+        float* old = h->packed_dev;
+        h->packed_dev = fresh;         // (the handle owns the new allocation whatever the free of the old one says)
+        h->bank_loaded.resize((size_t)n_banks, 0);
+        h->n_banks = n_banks;
+        FE_HIP_CHECK(hipFree(old));
+        return FE_OK;
+    }
+    h->bank_loaded.resize((size_t)n_banks, 0);
+    h->n_banks = n_banks;
+    return FE_OK;
+}
+
+int fe_load_weights_bank(fe_handle* h, int bank, const float* blob_dev, size_t nfloats, void* stream) {
     if (!h || !blob_dev) return fail(FE_ERR_INVALID_ARG, "null argument");
+    if (bank < 0 || bank >= h->n_banks) return fail(FE_ERR_INVALID_ARG, "bank %d outside [0, %d) (fe_set_weight_banks)", bank, h->n_banks);
     if (nfloats != h->blob_floats) return fail(FE_ERR_INVALID_ARG, "blob has %zu floats, expected %zu", nfloats, h->blob_floats);
     hipStream_t st = (hipStream_t)stream;
     std::vector<float> blob(nfloats);
@@ -1035,15 +1081,25 @@ int fe_load_weights(fe_handle* h, const float* blob_dev, size_t nfloats, void* s
     std::vector<float> packed;
     int rc = pack_blob(h, blob.data(), &packed);
     if (rc != FE_OK) return rc;
-    if (h->packed_dev) { FE_HIP_CHECK(hipFree(h->packed_dev)); h->packed_dev = nullptr; }
-    FE_HIP_CHECK(hipMalloc(&h->packed_dev, packed.size() * sizeof(float)));
-    FE_HIP_CHECK(hipMemcpyAsync(h->packed_dev, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    const size_t stride = (packed.size() + 63) & ~(size_t)63;
+    if (h->packed_dev && h->n_banks == 1 && stride != h->bank_stride) { FE_HIP_CHECK(hipFree(h->packed_dev)); h->packed_dev = nullptr; }
+    if (h->packed_dev && stride != h->bank_stride) return fail(FE_ERR_INVALID_ARG, "packed buffer of %zu floats in banks of %zu", packed.size(), h->bank_stride);
+    if (h->packed_dev && h->n_banks == 1) FE_HIP_CHECK(hipDeviceSynchronize());      // (a one-bank handle's load waits for every launch that reads the buffer, as it always has)
+    if (!h->packed_dev) {     // the first load of the handle allocates all banks; later loads write their bank in place
+        FE_HIP_CHECK(hipMalloc(&h->packed_dev, (size_t)h->n_banks * stride * sizeof(float)));
+        FE_HIP_CHECK(hipMemsetAsync(h->packed_dev, 0, (size_t)h->n_banks * stride * sizeof(float), st));
+        h->bank_stride = stride;
+    }
+    FE_HIP_CHECK(hipMemcpyAsync(h->packed_dev + (size_t)bank * stride, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice, st));
     FE_HIP_CHECK(hipStreamSynchronize(st));
     rc = ensure_scratch(h, 0);
     if (rc != FE_OK) return rc;
-    h->loaded = true;
+    h->bank_loaded[(size_t)bank] = 1;
+    if (bank == 0) h->loaded = true;
     return FE_OK;
 }
+
+int fe_load_weights(fe_handle* h, const float* blob_dev, size_t nfloats, void* stream) { return fe_load_weights_bank(h, 0, blob_dev, nfloats, stream); }
 
 // time_kernel variant: floats of the causal convs' frame caches per stream (2 NL layers x [KT-1][F1][C1])
 static size_t tk_floats(const fe_handle* h) {
@@ -1311,7 +1367,7 @@ static int table_view(const void* p, size_t bytes, const char* fn, const char* w
 }
 static int step_streams(fe_handle* h, const char* fn, bool pinned, const void* wav_in, size_t in_count, float* state_dev, int capacity,
                         const fe_stream_desc* desc_dev, void* wav_out, size_t out_count, int n, int T_max, int format, void* stream,
-                        const float* min_gain = nullptr, fe_stream_levels* levels = nullptr) {
+                        const float* min_gain = nullptr, fe_stream_levels* levels = nullptr, const int* bank = nullptr) {
     return slotted_step(h, fn, true,
         [&]() -> int {
             if (!wav_in || !state_dev || !desc_dev || !wav_out || n <= 0 || T_max <= 0 || capacity < n || in_count == 0 || out_count == 0)
@@ -1340,11 +1396,21 @@ static int step_streams(fe_handle* h, const char* fn, bool pinned, const void* w
             own.pinned = pinned ? 1 : 0;
             const void* gains = nullptr;
             const void* rows = nullptr;
+            const void* banks = nullptr;
             int rc = table_view(min_gain, (size_t)capacity * sizeof(float), fn, "min_gain", &gains);
             if (rc == FE_OK) rc = table_view(levels, (size_t)capacity * sizeof(fe_stream_levels), fn, "levels", &rows);
+            if (rc == FE_OK) rc = table_view(bank, (size_t)capacity * sizeof(int), fn, "bank", &banks);
             if (rc != FE_OK) return rc;
             own.min_gain = static_cast<const float*>(gains);
             own.levels = static_cast<fe::StreamLevels*>(const_cast<void*>(rows));
+            if (bank) {       // (the table's contents are the kernel's to read: every bank it may name must hold a checkpoint)
+                for (int k = 0; k < h->n_banks; ++k)
+                    if (!h->bank_loaded[(size_t)k])
+                        return fail(FE_ERR_NO_WEIGHTS, "%s: bank %d of the handle's %d has no weights (fe_load_weights_bank)", fn, k, h->n_banks);
+                own.bank = static_cast<const int*>(banks);
+                own.n_banks = h->n_banks;
+                own.bank_stride = h->bank_stride;
+            }
             return launch_fe_step(h, fn, fe::STEP_STREAMS, own, static_cast<const float*>(in), 0, state_dev, const_cast<float*>(static_cast<const float*>(out)), 0,
                                   n, T_max, stream);       // (the audio is typed by a.format in the kernel)
         });
@@ -1371,6 +1437,21 @@ int fe_step_streams_ctl_pinned(fe_handle* h, const void* wav_in_host, size_t in_
                                void* stream) {
     return step_streams(h, "fe_step_streams_ctl_pinned", true, wav_in_host, in_count, state_dev, capacity, desc_dev, wav_out_host, out_count, n, T_max, format,
                         stream, min_gain, levels);
+}
+
+// bank == NULL: the launch fe_step_streams_ctl[_pinned] makes (one code path: step_streams)
+int fe_step_streams_banked(fe_handle* h, const void* wav_in_dev, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,
+                           void* wav_out_dev, size_t out_count, int n, int T_max, int format, const float* min_gain, fe_stream_levels* levels,
+                           const int* bank, void* stream) {
+    return step_streams(h, "fe_step_streams_banked", false, wav_in_dev, in_count, state_dev, capacity, desc_dev, wav_out_dev,
+                        out_count, n, T_max, format, stream, min_gain, levels, bank);
+}
+
+int fe_step_streams_banked_pinned(fe_handle* h, const void* wav_in_host, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,
+                                  void* wav_out_host, size_t out_count, int n, int T_max, int format, const float* min_gain, fe_stream_levels* levels,
+                                  const int* bank, void* stream) {
+    return step_streams(h, "fe_step_streams_banked_pinned", true, wav_in_host, in_count, state_dev, capacity, desc_dev,
+                        wav_out_host, out_count, n, T_max, format, stream, min_gain, levels, bank);
 }
 
 // The streaming state of `capacity` streams as a list of regions [rows][capacity][len], in the order of the layout (include/fastenhancer_hip.h):

@@ -111,9 +111,12 @@ __device__ __forceinline__ void conv8_pair(int wh, AF&& af, BF&& bf, BI&& bias, 
 // stream's once the current one's has been taken), and the output row goes out in non-temporal 16-byte stores.  STRM (fe_step_streams /
 // fe_step_streams_pinned; HIO only): slot, hop count (0 or 1 here) and audio offsets come from the stream's descriptor (stream_view), the audio is
 // float32 or int16 PCM (a.format, wave-uniform); a stream without a hop is skipped and no hop of it is requested, as in fe_frame_kernel
-template <class S, bool DBG, bool PERSIST, bool SLOT = false, bool HIO = false, bool STRM = false>
+// BANK (fe_step_streams_banked[_pinned] with a bank table; STRM only): the stream's weights are bank a.bank[slot] of the handle's banks, in an
+// instantiation of its own as in fe_frame_kernel
+template <class S, bool DBG, bool PERSIST, bool SLOT = false, bool HIO = false, bool STRM = false, bool BANK = false>
 __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(2, 2))) fe_frame8_kernel(typename KernelArgs<SLOT, STRM>::type a_in) {
     static_assert(Wg8<S>::OK, "fe_frame8_kernel: shape outside the 512-thread kernel's plan");
+    static_assert(!BANK || STRM, "weight banks: the packet-audio instantiations only");
     static_assert(!HIO || (SLOT && !DBG), "host audio: slotted production instantiations only");
     static_assert(!STRM || HIO, "packet audio: the host-audio instantiations only");
     typename KernelArgs<SLOT, STRM>::type a = a_in;
@@ -151,9 +154,19 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
     };
     hop_issue((int)blockIdx.x);
     const float* __restrict__ wp = a.wp;
+    // (BANK) the bank whose unit 0 is staged for the stream to come, as in fe_frame_kernel: the prologue's requests - units 0 and 1 - follow
+    // the first stream's bank (descriptor -> bank[slot] -> weight request, in the banked instantiations only)
+    int bank_staged = 0;
+    if constexpr (BANK) {
+        if (a.bank != nullptr) {       // (the run-time test stays: the note at fe_frame_kernel's BANK)
+            const int k0 = stream_bank<BANK>(a, stream_view<S::HOP>(a, (int)blockIdx.x));
+            bank_staged = k0 < 0 ? 0 : k0;
+            wp = a.wp + (size_t)bank_staged * a.bank_stride;
+        }
+    }
     WSrc<true> wb;
     constexpr PackedOffsets o = Pack<S>::v;
-    wb.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.wp), 0, o.total * 4, 0x00020000);
+    wb.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wp), 0, o.total * 4, 0x00020000);
     wb.lane4 = lane * 4;
     wb.li4 = (lane & 15) * 4;
     wb.lds = nullptr;
@@ -243,12 +256,34 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
             sb = a.slots[b];
             nst = a.capacity;
             if constexpr (STRM) {
-                if (sv.hops == 0 || (unsigned)sb >= (unsigned)nst) {      // (wave-uniform) no hop: nothing; no state: the stream's output row is zero
+                const int bk = stream_bank<BANK>(a, sv);       // (!BANK: 0; -1: a bank out of range - the stream is one without state)
+                if (sv.hops == 0 || (unsigned)sb >= (unsigned)nst || bk < 0) {      // (wave-uniform) no hop: nothing; no state: the stream's output row is zero
                     if (sv.hops) stream_zero_row(a.wav_out, a.format, sv.out_off, H, tid0, NTH);
                     __builtin_amdgcn_s_waitcnt(0);       // (the weight stages issued for this stream have landed before the next one or the end)
                     b += (int)gridDim.x;
                     hop_issue(b);
                     continue;
+                }
+                if (BANK && a.bank != nullptr) {
+                    // the stream's own bank from here on: wp, the resource of every weight fetch and of the staging jobs (jb1 / jb2 copy it below)
+                    wp = a.wp + (size_t)bk * a.bank_stride;
+                    wb.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wp), 0, o.total * 4, 0x00020000);
+                    job.rsrc = wb.rsrc;
+                    if constexpr (PERSIST) {
+                        if (bk != bank_staged) {
+                            // unit 0 was staged from another bank (the last phase of the stream before, or the prologue): fetch this bank's into the
+                            // buffer stream fc consumes it from - nothing reads that buffer since the stage that filled it; the barrier orders these
+                            // LDS stores before enc_pre's reads.  (Unit 1 rides in enc_pre, with the resource set above.)
+                            DmaJobT<NPW> jr = job;
+                            jr.l = smem + (((S::NU & 1) && (fc & 1)) ? W8::WB1 : W8::WB0);
+                            jr.soff = (o.u_off[0] + wave0 * 256) * 4;
+                            const StageSide<NPW, o.u_size[0] / 256, kWaves8> str{&jr};
+                            str(0, 1);
+                            str.commit();
+                            __syncthreads();
+                        }
+                    }
+                    bank_staged = bk;
                 }
             } else
             if ((unsigned)sb >= (unsigned)nst) {         // (wave-uniform) no state: the stream's output row is zero

@@ -42,12 +42,13 @@ struct Impl {
 // What fe_last_step_kernel reports for the instantiation a launcher picked: the kernel's name, then in angle brackets and joined by ", " whichever
 // apply of "LOW=n", what it is (debug, per-hop, ...), "slots" or "streams" (the SLOT / STRM instantiations), "pinned" and "s16" - put together at
 // compile time, so that fe::note_kernel still gets a constant string.  HIO says where a slotted step's audio lives; for the STRM instantiations
-// that and the audio's format are run-time facts of the call (a.pinned, a.format), hence a name for each of the four: s[pinned + 2 * s16].
-struct KernelNames { char s[4][80] = {}; };
+// that, the audio's format and a bank table (fe_step_streams_banked) are run-time facts of the call (a.pinned, a.format, a.bank), hence a name for
+// each of the eight: s[pinned + 2 * s16 + 4 * banks].
+struct KernelNames { char s[8][80] = {}; };
 constexpr KernelNames kernel_names(const char* kernel, int low, const char* what, const char* flavour) {
     KernelNames n;
-    for (int v = 0; v < 4; ++v) {
-        const char* parts[] = {low == 2 ? "LOW=2" : low == 1 ? "LOW=1" : "", what, flavour, v & 1 ? "pinned" : "", v & 2 ? "s16" : ""};
+    for (int v = 0; v < 8; ++v) {
+        const char* parts[] = {low == 2 ? "LOW=2" : low == 1 ? "LOW=1" : "", what, flavour, v & 1 ? "pinned" : "", v & 2 ? "s16" : "", v & 4 ? "banks" : ""};
         int k = 0;
         auto put = [&](const char* p) { while (*p) n.s[v][k++] = *p++; };
         put(kernel);
@@ -61,19 +62,27 @@ constexpr KernelNames kernel_names(const char* kernel, int low, const char* what
 constexpr bool same_text(const char* a, const char* b) { for (; *a == *b; ++a, ++b) if (!*a) return true; return false; }
 static_assert(same_text(kernel_names("fe_frame8_kernel", 0, "", "").s[0], "fe_frame8_kernel") &&
               same_text(kernel_names("fe_frame8_kernel", 0, "persistent", "slots").s[1], "fe_frame8_kernel<persistent, slots, pinned>") &&
-              same_text(kernel_names("fe_frame_kernel", 2, "per-hop, persistent", "streams").s[3], "fe_frame_kernel<LOW=2, per-hop, persistent, streams, pinned, s16>"),
-              "the texts fe_last_step_kernel has always reported (the last one is the longest: 65 characters)");
+              same_text(kernel_names("fe_frame_kernel", 2, "per-hop, persistent", "streams").s[3], "fe_frame_kernel<LOW=2, per-hop, persistent, streams, pinned, s16>") &&
+              same_text(kernel_names("fe_frame_kernel", 2, "per-hop, persistent", "streams").s[7], "fe_frame_kernel<LOW=2, per-hop, persistent, streams, pinned, s16, banks>"),
+              "the texts fe_last_step_kernel has always reported, and the banked call's (the last one is the longest: 72 characters)");
 template <bool WG8, int LOW, bool DBG, bool T1, bool PERSIST, bool SLOT, bool HIO, bool STRM, class Args>
 const char* kernel_name_of(const Args& a) {      // WG8: fe_frame8_kernel (no LOW shapes, no generic form), else fe_frame_kernel
     static constexpr KernelNames names = kernel_names(WG8 ? "fe_frame8_kernel" : "fe_frame_kernel", LOW,
         DBG ? "debug" : WG8 ? (PERSIST ? "persistent" : "") : !T1 ? "generic" : PERSIST ? "per-hop, persistent" : "per-hop", STRM ? "streams" : SLOT ? "slots" : "");
-    if constexpr (STRM) return names.s[(a.pinned != 0) + 2 * (a.format != 0)];
+    if constexpr (STRM) return names.s[(a.pinned != 0) + 2 * (a.format != 0) + 4 * (a.bank != nullptr)];
     else return names.s[HIO];
 }
 
+// (STRM: a call with a bank table runs the BANK instantiation of the same choice - a.bank decides here, per launch)
 template <class S, bool DBG, int MODE, bool T1, bool PERSIST, bool SLOT = false, bool HIO = false, bool STRM = false>
 void launch_one(const typename KernelArgs<SLOT, STRM>::type& a, int grid_x, hipStream_t st, hipError_t* err) {
     const char* name = kernel_name_of<false, S::LOW, DBG, T1, PERSIST, SLOT, HIO, STRM>(a);
+    if constexpr (STRM) {
+        if (a.bank != nullptr) {
+            *err = launch<&fe_frame_kernel<S, DBG, MODE, T1, PERSIST, false, SLOT, HIO, STRM, true>>(name, dim3(grid_x), dim3(kThreads), Lds<S>::BYTES, st, a);
+            return;
+        }
+    }
     *err = launch<&fe_frame_kernel<S, DBG, MODE, T1, PERSIST, false, SLOT, HIO, STRM>>(name, dim3(grid_x), dim3(kThreads), Lds<S>::BYTES, st, a);
 }
 
@@ -83,6 +92,12 @@ void launch_one(const typename KernelArgs<SLOT, STRM>::type& a, int grid_x, hipS
 template <class S, bool DBG, bool PERSIST, bool SLOT = false, bool HIO = false, bool STRM = false>
 void launch_one8(const typename KernelArgs<SLOT, STRM>::type& a, int grid_x, hipStream_t st, hipError_t* err) {
     const char* name = kernel_name_of<true, 0, DBG, true, PERSIST, SLOT, HIO, STRM>(a);
+    if constexpr (STRM) {
+        if (a.bank != nullptr) {
+            *err = launch<&fe_frame8_kernel<S, DBG, PERSIST, SLOT, HIO, STRM, true>>(name, dim3(grid_x), dim3(kThreads8), Wg8<S>::BYTES, st, a);
+            return;
+        }
+    }
     *err = launch<&fe_frame8_kernel<S, DBG, PERSIST, SLOT, HIO, STRM>>(name, dim3(grid_x), dim3(kThreads8), Wg8<S>::BYTES, st, a);
 }
 

@@ -358,6 +358,12 @@ struct StreamFrameArgs : SlotFrameArgs {
     // fe_step_streams_ctl[_pinned]; either may be null (both null: fe_step_streams).  Slot-indexed, [capacity], read / written when the kernel runs.
     const float* min_gain;    // suppression limit: the least net amplitude gain of a bin, linear, clamped to [0, 1]; 0 / NaN = off
     StreamLevels* levels;     // one 16-byte row per stream that advanced (16-byte aligned)
+    // fe_step_streams_banked[_pinned]; null from every other entry point (everything then reads a.wp = bank 0).  Slot-indexed, [capacity], read when
+    // the kernel runs: the stream of slot s runs on the packed buffer a.wp + bank[s] * bank_stride; a bank outside [0, n_banks) skips the stream
+    // as a slot out of range does.
+    const int* bank;
+    int n_banks;
+    size_t bank_stride;       // floats between two banks (a multiple of 64: every bank base keeps the 256-byte alignment of the allocation)
 };
 template <bool SLOT, bool STRM = false> struct KernelArgs { using type = FrameArgs; };
 template <> struct KernelArgs<true, false> { using type = SlotFrameArgs; };
@@ -408,6 +414,17 @@ __device__ __forceinline__ StreamView stream_view(const StreamFrameArgs& a, int 
         v.hops = (in_ok && out_ok) ? hops : 0;
     }
     return v;
+}
+// The weight bank of the stream with view v, wave-uniform: 0 in the instantiations without a bank table (!BANK: a.wp itself); -1 - the stream is
+// skipped - where the table names a bank outside [0, n_banks).  The table is read only for a stream that has a hop and a state slot in range
+// (it is [capacity]).
+template <bool BANK>
+__device__ __forceinline__ int stream_bank(const StreamFrameArgs& a, const StreamView& v) {
+    if constexpr (!BANK) return 0;
+    if (a.bank == nullptr) return 0;       // (never in a BANK launch: see the note at fe_frame_kernel's BANK)
+    if (v.hops == 0 || (unsigned)v.slot >= (unsigned)a.capacity) return -1;
+    const int k = __builtin_amdgcn_readfirstlane(a.bank[v.slot]);
+    return (unsigned)k < (unsigned)a.n_banks ? k : -1;
 }
 // int16 PCM, full scale 32768.  In: s / 32768 (exact).  Out: clamp(rint(y * 32768), -32768, 32767), ties to even, NaN -> 0.
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -1614,10 +1631,18 @@ __device__ __forceinline__ void attention_head(const float* G, float* Hl, int ho
 // both): stream b advances sv.hops <= a.T hops (stream_view: its descriptor, clamped and bounds-checked), reads and writes its audio at its own
 // element offsets, as float32 or int16 PCM (a.format, a wave-uniform branch at the two I/O sites); a stream with no hop is skipped, and the hop
 // requested ahead is never one beyond a stream's own count.
-template <class S, bool DBG, int MODE, bool T1, bool PERSIST, bool PIPE = false, bool SLOT = false, bool HIO = false, bool STRM = false>
+// BANK (fe_step_streams_banked[_pinned] with a bank table; STRM only): stream b's weights are bank a.bank[slot] of the handle's banks.  An
+// instantiation of its own and not a null test of a.bank: with the weight base and the buffer resource loop-variant, the persistent packet
+// instantiations of shape B spill 21 to 28 more SGPRs (49 -> 70, 26 -> 47, 104 -> 132) and fe_step_streams_ctl measured 0.45 % slower - the
+// calls without a table keep the code they had.  The BANK instantiations keep the table's null test at run time although fe_impl.h launches
+// them with a table only: written without it, the persistent LOW = 2 instantiation of 48 kHz B at hop 480 computed wrong rows for the second
+// live stream of a workgroup's walk even with every stream on bank 0 (source-equivalent code; the cause was not found in its assembly), and
+// with the test it gives the bits of the instantiation without banks (tests/test_gpu_weight_banks.py, the cases above the CU count).
+template <class S, bool DBG, int MODE, bool T1, bool PERSIST, bool PIPE = false, bool SLOT = false, bool HIO = false, bool STRM = false, bool BANK = false>
 __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(Lds<S>::OCC, Lds<S>::OCC))) fe_frame_kernel(typename KernelArgs<SLOT, STRM>::type a_in) {
     static_assert(!HIO || (SLOT && !PIPE && !DBG), "host audio: slotted streaming instantiations only");
     static_assert(!STRM || HIO, "packet audio: the host-audio instantiations only");
+    static_assert(!BANK || STRM, "weight banks: the packet-audio instantiations only");
     typename KernelArgs<SLOT, STRM>::type a = a_in;
 #ifdef FE_PROBE_HOT          // measurement builds: the production instantiations keep the cycle probes (tools/gpu_phases.py ... 1)
     if constexpr (!DBG) a.dbg = nullptr;
@@ -1672,10 +1697,21 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
     };
     hop_issue((int)blockIdx.x, 0);
     const float* __restrict__ wp = a.wp;
+    // (BANK) the bank whose unit 0 is staged for the stream to come: the prologue asks for its first stream's (the one dependent chain ahead
+    // of the first weight request, in the banked instantiations only; bank 0 where that stream will be skipped), the last phase of a stream
+    // for the stream's own, and a stream that finds another bank staged than its own stages unit 0 again (below)
+    int bank_staged = 0;
+    if constexpr (BANK) {
+        if (a.bank != nullptr) {
+            const int k0 = stream_bank<BANK>(a, stream_view<S::HOP>(a, (int)blockIdx.x));
+            bank_staged = k0 < 0 ? 0 : k0;
+            wp = a.wp + (size_t)bank_staged * a.bank_stride;
+        }
+    }
     WSrc<Lds<S>::STAGED> wb;
     constexpr PackedOffsets o = Pack<S>::v;
     static_assert(o.n_units == S::NU, "unit count");
-    wb.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.wp), 0, o.total * 4, 0x00020000);
+    wb.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wp), 0, o.total * 4, 0x00020000);
     wb.lane4 = lane * 4;
     wb.li4 = (lane & 15) * 4;
     wb.lds = nullptr;
@@ -1770,12 +1806,35 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
         sb = a.slots[b];
         nst = a.capacity;
         if constexpr (STRM) {
-            if (sv.hops == 0 || (unsigned)sb >= (unsigned)nst) {      // (wave-uniform) no hop: nothing; no state: its sv.hops output rows are zero
+            const int bk = stream_bank<BANK>(a, sv);       // (!BANK: 0; -1: a bank out of range - the stream is one without state)
+            if (sv.hops == 0 || (unsigned)sb >= (unsigned)nst || bk < 0) {      // (wave-uniform) no hop: nothing; no state: its sv.hops output rows are zero
                 if (sv.hops) stream_zero_row(a.wav_out, a.format, sv.out_off, sv.hops * S::HOP, tid, kThreads);
                 __builtin_amdgcn_s_waitcnt(0);       // (the weight stage issued for this stream has landed before the next one or the end)
                 b += (int)gridDim.x;
                 hop_issue(b, 0);
                 continue;
+            }
+            if (BANK && a.bank != nullptr) {
+                // every weight access of the stream goes through wp / wb.rsrc / job.rsrc: the stream's own bank from here on - the units it stages
+                // for its own next frame and, after its last one, for the next stream included (bank_staged)
+                wp = a.wp + (size_t)bk * a.bank_stride;
+                wb.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wp), 0, o.total * 4, 0x00020000);
+                job.rsrc = wb.rsrc;
+                if constexpr (PERSIST && L::STAGED) {
+                    if (bk != bank_staged) {
+                        // unit 0 was staged from the bank of the stream before (or of a skipped first stream's stand-in): fetch this bank's into
+                        // the buffer frame fc consumes it from.  Nothing reads that buffer since the stage that filled it; the barrier orders
+                        // these LDS stores before enc_pre's reads.
+                        DmaJobT<NPW> jr = job;
+                        jr.l = smem + (((S::NU & 1) && (fc & 1)) ? L::WB1 : L::WB0);
+                        jr.soff = (o.u_off[0] + wave * 256) * 4;
+                        const StageSide<NPW, o.u_size[0] / 256> str{&jr};
+                        str(0, 1);
+                        str.commit();
+                        __syncthreads();
+                    }
+                }
+                bank_staged = bk;
             }
         } else
         if ((unsigned)sb >= (unsigned)nst) {         // (wave-uniform) no state: the stream's output rows are zero

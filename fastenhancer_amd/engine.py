@@ -81,12 +81,39 @@ class Engine:
             blob[off:off + cnt] = t
         return blob
 
-    def load_blob(self, blob_dev: Tensor):
+    @property
+    def weight_banks(self) -> int:
+        """fe_weight_banks: checkpoints the handle holds side by side (1 unless set_weight_banks asked for more)"""
+        return int(self.lib.fe_weight_banks(self._h))
+
+    def set_weight_banks(self, n: int) -> None:
+        """fe_set_weight_banks: room for n checkpoints of this shape (1 .. 64), bank 0 being what every other step reads; the banks that
+        survive keep their contents.  Load-time work: it may synchronise the current stream and must not be called inside a capture."""
+        n = operator.index(n)
+        if self.device is not None and self.device.type == "cuda" and torch.cuda.is_available():
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.fe_set_weight_banks(self._h, n, _stream(self.device)), "fe_set_weight_banks")
+        else:       # (no GPU: the arguments are still checked; nothing is loaded, so there is nothing to move)
+            _lib.check(self.lib.fe_set_weight_banks(self._h, n, None), "fe_set_weight_banks")
+
+    def _bank(self, bank) -> int:
+        bank = operator.index(bank)
+        if not 0 <= bank < self.weight_banks:
+            raise ValueError(f"bank {bank} is outside [0, {self.weight_banks}) (set_weight_banks)")
+        return bank
+
+    def load_blob(self, blob_dev: Tensor, bank: int = 0):
+        """fe_load_weights_bank: the blob into bank `bank`, in place (bank 0: fe_load_weights)"""
+        bank = self._bank(bank)
         self._require_gpu()
         assert blob_dev.is_cuda and blob_dev.dtype == torch.float32 and blob_dev.is_contiguous()
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.fe_load_weights(self._h, _ptr(blob_dev), blob_dev.numel(), _stream(self.device)), "fe_load_weights")
-        self.loaded = True
+            if bank == 0:
+                _lib.check(self.lib.fe_load_weights(self._h, _ptr(blob_dev), blob_dev.numel(), _stream(self.device)), "fe_load_weights")
+            else:
+                _lib.check(self.lib.fe_load_weights_bank(self._h, bank, _ptr(blob_dev), blob_dev.numel(), _stream(self.device)), "fe_load_weights_bank")
+        if bank == 0:
+            self.loaded = True
 
     def pack_blob(self, blob_cpu: Tensor) -> Tensor:
         """the buffer the kernels read, packed on the CPU from a make_blob() blob: what load_blob uploads (fe_debug_pack_weights; needs no GPU)."""
@@ -97,9 +124,10 @@ class Engine:
         _lib.check(self.lib.fe_debug_pack_weights(self._h, _ptr(blob_cpu), blob_cpu.numel(), _ptr(out), out.numel(), byref(n)), "fe_debug_pack_weights")
         return out
 
-    def load_state_dict(self, state_dict: Mapping[str, Tensor], strict: bool = True):
+    def load_state_dict(self, state_dict: Mapping[str, Tensor], strict: bool = True, bank: int = 0):
+        bank = self._bank(bank)
         blob = self.make_blob(state_dict, strict=strict)
-        self.load_blob(blob.to(self.device))
+        self.load_blob(blob.to(self.device), bank)
 
     # ------------------------------------------------------------------ state
     def _require_gpu(self):
@@ -383,10 +411,21 @@ class Engine:
             raise ValueError(f"{what} must be a device tensor or a CPU tensor in page-locked memory (pin_memory())")
         return t
 
+    @staticmethod
+    def _bank_table(t: Optional[Tensor], capacity: int) -> Optional[Tensor]:
+        """bank [capacity] of the banked steps: int32, contiguous, on the device or in page-locked host memory"""
+        if t is None:
+            return None
+        if not isinstance(t, Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (capacity,) or not t.is_contiguous():
+            raise ValueError(f"bank must be a contiguous int32 tensor [{capacity}]")
+        if not t.is_cuda and not (t.device.type == "cpu" and t.is_pinned()):
+            raise ValueError("bank must be a device tensor or a CPU tensor in page-locked memory (pin_memory())")
+        return t
+
     def _step_streams(self, wav_in: Tensor, state: Tensor, capacity: int, desc, wav_out: Tensor, T_max: int, pinned: bool,
-                      min_gain: Optional[Tensor] = None, levels: Optional[Tensor] = None) -> Tensor:
+                      min_gain: Optional[Tensor] = None, levels: Optional[Tensor] = None, bank: Optional[Tensor] = None) -> Tensor:
         ctl = min_gain is not None or levels is not None
-        name = "fe_step_streams" + ("_ctl" if ctl else "") + ("_pinned" if pinned else "")
+        name = "fe_step_streams" + ("_banked" if bank is not None else "_ctl" if ctl else "") + ("_pinned" if pinned else "")
         for what, x in (("wav_in", wav_in), ("wav_out", wav_out)):
             if not isinstance(x, Tensor) or x.dtype not in (torch.float32, torch.int16) or not x.is_contiguous() or x.numel() == 0:
                 raise ValueError(f"{what} must be a contiguous, non-empty float32 or int16 tensor")
@@ -401,34 +440,38 @@ class Engine:
             raise ValueError("T_max must be at least 1")
         min_gain = self._stream_table("min_gain", min_gain, (capacity,))
         levels = self._stream_table("levels", levels, (capacity, 4))
+        bank = self._bank_table(bank, capacity)
         d = self._stream_desc_tensor(desc, capacity, T_max, wav_in.numel(), wav_out.numel())
         self._require_gpu()
         assert state.is_cuda and state.numel() == self.state_floats(capacity) and state.is_contiguous()
         fmt = _lib.FE_AUDIO_S16 if wav_in.dtype == torch.int16 else _lib.FE_AUDIO_F32
-        tables = (_ptr(min_gain), _ptr(levels)) if ctl else ()
+        tables = (_ptr(min_gain), _ptr(levels), _ptr(bank)) if bank is not None else (_ptr(min_gain), _ptr(levels)) if ctl else ()
         with torch.cuda.device(self.device):
             _lib.check(getattr(self.lib, name)(self._h, _ptr(wav_in), wav_in.numel(), _ptr(state), int(capacity), _ptr(d), _ptr(wav_out), wav_out.numel(),
                                                d.shape[0], int(T_max), fmt, *tables, _stream(self.device)), name)
-        self._desc_keep = (d, min_gain, levels)          # (alive until the next call - the launch is asynchronous)
+        self._desc_keep = (d, min_gain, levels, bank)    # (alive until the next call - the launch is asynchronous)
         if pinned:
             self._pinned_keep = (wav_in, wav_out)
         return wav_out
 
     def step_streams(self, wav_in: Tensor, state: Tensor, capacity: int, desc, wav_out: Tensor, T_max: int = 1, *,
-                     min_gain: Optional[Tensor] = None, levels: Optional[Tensor] = None) -> Tensor:
+                     min_gain: Optional[Tensor] = None, levels: Optional[Tensor] = None, bank: Optional[Tensor] = None) -> Tensor:
         """fe_step_streams: every stream of `desc` advances its own number of hops (0 .. T_max), reading wav_in [in_offset + t*H ...] and
         writing wav_out [out_offset + t*H ...] - flat device buffers, both float32 or both int16 PCM (full scale 32768).  desc: a list of
         (slot, hops, in_offset, out_offset) (checked) or a CUDA int32 tensor [n, 6] (pack_stream_desc; checked by the kernel only).
         min_gain / levels (fe_step_streams_ctl, when either is given): float32 tables indexed by SLOT, on the device or in page-locked host
         memory, read and written by the kernel when it runs.  min_gain [capacity]: the least net amplitude gain of a bin, linear in [0, 1]
-        (0 = no limit).  levels [capacity, 4]: (in_sumsq, in_peak, out_sumsq, out_peak) of every stream that advanced at least one hop."""
-        return self._step_streams(wav_in, state, capacity, desc, wav_out, T_max, pinned=False, min_gain=min_gain, levels=levels)
+        (0 = no limit).  levels [capacity, 4]: (in_sumsq, in_peak, out_sumsq, out_peak) of every stream that advanced at least one hop.
+        bank (fe_step_streams_banked, when given): an int32 table [capacity] indexed by SLOT, device or page-locked host memory, read by the
+        kernel when it runs: the weight bank (set_weight_banks, load_state_dict(bank=)) the stream of that slot runs on; every bank of the
+        engine must be loaded; a bank out of range makes the stream one without state (zero rows)."""
+        return self._step_streams(wav_in, state, capacity, desc, wav_out, T_max, pinned=False, min_gain=min_gain, levels=levels, bank=bank)
 
     def step_streams_pinned(self, wav_in: Tensor, state: Tensor, capacity: int, desc, wav_out: Tensor, T_max: int = 1, *,
-                            min_gain: Optional[Tensor] = None, levels: Optional[Tensor] = None) -> Tensor:
+                            min_gain: Optional[Tensor] = None, levels: Optional[Tensor] = None, bank: Optional[Tensor] = None) -> Tensor:
         """fe_step_streams_pinned: step_streams with wav_in / wav_out in page-locked HOST memory, read and written by the kernel over PCIe.
         Asynchronous on the current stream: synchronise it before reading wav_out (or a pinned levels table) or rewriting wav_in."""
-        return self._step_streams(wav_in, state, capacity, desc, wav_out, T_max, pinned=True, min_gain=min_gain, levels=levels)
+        return self._step_streams(wav_in, state, capacity, desc, wav_out, T_max, pinned=True, min_gain=min_gain, levels=levels, bank=bank)
 
     def new_pinned(self, *shape: int, dtype=torch.float32) -> Tensor:
         """a zeroed page-locked host tensor (the audio of the pinned steps)"""

@@ -9,7 +9,8 @@ PacketPool: a StreamPool for PACKET audio - int16 PCM that arrives in pieces of 
 samples, with network jitter).  push() copies a packet into the stream's page-locked ring, tick() is ONE fe_step_streams_pinned launch in
 which every stream advances by the whole hops it has, pull() returns the enhanced PCM.  The kernel reads and writes the rings themselves.
 set_suppression_limit() bounds how far a stream may be attenuated and levels() reads the stream's input / output level meters: both run
-inside the same launch (fe_step_streams_ctl_pinned).
+inside the same launch (fe_step_streams_ctl_pinned).  open(bank=) / set_bank() put a stream on another of the engine's weight banks - another
+checkpoint of the same shape - still in that one launch (fe_step_streams_banked_pinned).
 
 Moving a stream: export() gathers the state records of open slots (fe_state_export_slots: a record is the stream's state as a capacity-1
 state buffer), adopt() opens slots for records made elsewhere, move() takes a live stream to another pool - of another engine of the same
@@ -17,6 +18,7 @@ config, on another GPU if need be - and resize() grows or shrinks a pool in plac
 from __future__ import annotations
 
 import math
+import operator
 from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
 
@@ -213,13 +215,15 @@ class PacketPool(StreamPool):
     the newest one pushed a stream may hold one ring of samples: push() refuses what would overwrite them.  No threads, no queues.
     meters=True: every tick also meters each launched stream's input and output (levels()).  The level table lives in page-locked host
     memory - tick() synchronises anyway - and the table of suppression limits, made by the first set_suppression_limit(), on the device;
-    a pool with neither launches plain fe_step_streams_pinned."""
+    a pool with neither launches plain fe_step_streams_pinned.  The table of weight banks, made by the first open(bank=) / set_bank() that
+    names a bank other than 0, lives on the device too; a pool that never names one launches what it launched without banks."""
 
     def __init__(self, engine: Engine, capacity: int, ring_hops: int, T_max: int = 1, meters: bool = False):
         super().__init__(engine, capacity)
         if ring_hops < 1 or T_max < 1:
             raise ValueError("ring_hops and T_max must be at least 1")
         self._gain: Optional[Tensor] = None                # [capacity] linear least gain per slot, 0 = off
+        self._bank: Optional[Tensor] = None                # [capacity] int32 weight bank per slot (None: every stream on bank 0)
         self._levels: Optional[Tensor] = engine.new_pinned(self.capacity, 4) if meters else None
         self._level_samples = [0] * self.capacity          # samples behind each level row (0: no row yet)
         self.H = int(engine.cfg.hop_size)
@@ -240,20 +244,54 @@ class PacketPool(StreamPool):
             self._levels[slot] = 0.0
         self._level_samples[slot] = 0
 
-    def open(self) -> int:
+    def open(self, bank: int = 0) -> int:
+        """StreamPool.open; the stream runs on weight bank `bank` of the engine (ValueError, and no slot is opened, outside its banks)."""
+        bank = self._check_bank(bank, self.engine)
         slot = super().open()
         self._pushed[slot] = self._stepped[slot] = self._pulled[slot] = 0
         self._reset_ctl(slot)
+        self._set_bank(slot, bank)
         return slot
 
     def adopt(self, records: Tensor) -> List[int]:
-        """StreamPool.adopt; the adopted streams start with empty rings, no limit and no level row (move() carries a stream's rings and
-        limit along)."""
+        """StreamPool.adopt; the adopted streams start with empty rings, no limit and no level row, on bank 0 (move() carries a stream's
+        rings, limit and bank along)."""
         slots = super().adopt(records)
         for slot in slots:
             self._pushed[slot] = self._stepped[slot] = self._pulled[slot] = 0
             self._reset_ctl(slot)
+            self._set_bank(slot, 0)
         return slots
+
+    # ---- weight banks: streams of one pool on different checkpoints (fe_step_streams_banked_pinned)
+    @staticmethod
+    def _check_bank(bank, engine) -> int:
+        n = int(getattr(engine, "weight_banks", 1))
+        try:
+            k = -1 if isinstance(bank, bool) else operator.index(bank)
+        except TypeError:
+            k = -1
+        if not 0 <= k < n:
+            raise ValueError(f"bank {bank!r} is outside the engine's banks [0, {n})")
+        return k
+
+    def _set_bank(self, slot: int, bank: int) -> None:
+        if self._bank is None:
+            if bank == 0:
+                return
+            self._bank = torch.zeros(self.capacity, dtype=torch.int32, device=getattr(self.engine, "device", None))
+        self._bank[slot] = bank
+
+    def set_bank(self, slot: int, bank: int) -> None:
+        """The stream runs on weight bank `bank` from the next tick on.  (Its state carries over - the layout is the same - but what a
+        stream sounds like across a change of checkpoint is the checkpoints' business.)"""
+        self._check_open(slot)
+        self._set_bank(slot, self._check_bank(bank, self.engine))
+
+    def bank(self, slot: int) -> int:
+        """the weight bank the stream runs on"""
+        self._check_open(slot)
+        return 0 if self._bank is None else int(self._bank[slot])
 
     # ---- the suppression limit and the level meters (fe_step_streams_ctl_pinned)
     @staticmethod
@@ -305,6 +343,7 @@ class PacketPool(StreamPool):
         if not isinstance(dst_pool, PacketPool):
             raise TypeError("a packet stream moves to a PacketPool")
         self._check_move(slot, dst_pool)
+        bank = self._check_bank(self.bank(slot), dst_pool.engine)       # (the destination engine must have the stream's bank)
         counters = (self._pushed[slot], self._stepped[slot], self._pulled[slot])
         if counters[0] - counters[2] > dst_pool.ring:
             raise OverflowError(f"slot {slot}: {counters[0] - counters[2]} samples in flight do not fit the destination ring of {dst_pool.ring} samples")
@@ -314,6 +353,7 @@ class PacketPool(StreamPool):
         p = carry_ring(src_in, src_out, *counters, dst_pool.ring_in[new], dst_pool.ring_out[new])
         dst_pool._pushed[new], dst_pool._stepped[new], dst_pool._pulled[new] = p
         dst_pool._set_gain(new, gain)
+        dst_pool._set_bank(new, bank)
         return new
 
     def resize(self, capacity: int) -> None:
@@ -337,6 +377,10 @@ class PacketPool(StreamPool):
             gain = torch.zeros(self.capacity, dtype=torch.float32, device=self._gain.device)
             gain[:keep] = self._gain[:keep]
             self._gain = gain
+        if self._bank is not None:
+            bank = torch.zeros(self.capacity, dtype=torch.int32, device=self._bank.device)
+            bank[:keep] = self._bank[:keep]
+            self._bank = bank
         if self._levels is not None:
             levels = self.engine.new_pinned(self.capacity, 4)
             levels[:keep] = self._levels[:keep]
@@ -377,6 +421,8 @@ class PacketPool(StreamPool):
         if not desc:
             return desc
         ctl = {} if self._gain is None and self._levels is None else dict(min_gain=self._gain, levels=self._levels)
+        if self._bank is not None:
+            ctl["bank"] = self._bank
         self.engine.step_streams_pinned(self.ring_in, self.state, self.capacity, desc, self.ring_out, T_max=self.T_max, **ctl)
         self.engine.synchronize()
         for slot, hops, _, _ in desc:

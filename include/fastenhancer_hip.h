@@ -280,6 +280,42 @@ int fe_step_streams_ctl_pinned(fe_handle* h, const void* wav_in_host, size_t in_
                                const fe_stream_desc* desc_dev, void* wav_out_host, size_t out_count, int n, int T_max, int format,
                                const float* min_gain, fe_stream_levels* levels, void* stream);
 
+/* Weight banks: the streams of one packet batch on different checkpoints of the handle's shape (a canary, per-customer fine-tunes, a roll-out
+ * under live streams) - one handle, one state buffer and one launch per tick for all of them.
+ *   The banks of a handle sit in ONE device allocation, n_banks packed buffers at a fixed stride (the packed size rounded up, so that every
+ *     bank base keeps the alignment of the kernels' 16-byte fetches).  Bank 0 is what fe_load_weights loads and what every other entry point
+ *     reads: fe_step*, fe_step_slots*, fe_step_streams[_ctl][_pinned], fe_step_chunk, fe_spec_step and fe_offline keep their results bit for bit.
+ *   fe_set_weight_banks: 1 (what fe_create leaves) .. FE_MAX_WEIGHT_BANKS, else FE_ERR_INVALID_ARG.  The contents of the banks that survive,
+ *     [0, min(old, new)), are kept.  Like fe_load_weights it may synchronise `stream` and allocates: load-time work, not inside a capture.
+ *     Arguments are checked before any device work.  n_banks > 1 is for the FastEnhancer streaming models (default, time_kernel, ln, dprnn,
+ *     dptransformer); BSRNN, FSPEN, LiSenNet and the noncausal model get FE_ERR_UNSUPPORTED_CONFIG with a message that names the family;
+ *     n_banks == 1 is FE_OK for all of them.
+ *   fe_load_weights_bank: fe_load_weights into bank `bank` (outside [0, n_banks): FE_ERR_INVALID_ARG), in place: no other bank's bytes are
+ *     written and the allocation does not move, so a launch that reads other banks and was enqueued earlier on the same stream stays valid -
+ *     load bank k while the others serve.  fe_load_weights(h, ...) is fe_load_weights_bank(h, 0, ...).
+ *   fe_step_streams_banked[_pinned]: fe_step_streams_ctl[_pinned] with one more slot-indexed table.
+ *     bank: [capacity] int32 indexed by state SLOT, or NULL: bank[slot] names the bank the stream of that slot runs on.  Device memory or
+ *       page-locked host memory mapped for the device, looked up and refused as min_gain is.  The kernel reads the table when it runs: a
+ *       captured graph follows a rewritten table.
+ *     bank == NULL: the call is fe_step_streams_ctl[_pinned] - the same code path, the same bits.
+ *     FE_ERR_NO_WEIGHTS unless EVERY bank 0 .. n_banks - 1 is loaded (the host cannot see the table's contents).
+ *     A stream whose bank[slot] lies outside [0, n_banks) is treated as a stream whose slot lies outside [0, capacity): its output rows are
+ *       zero, no state is touched and no level row is written.
+ *     Each stream's output rows, state and level row are, bit for bit, what fe_step_streams_ctl gives that stream on a one-bank handle loaded
+ *       with its bank's checkpoint, under the same kernel.  fe_last_step_kernel adds "banks" inside the brackets (after "streams" / "pinned" /
+ *       "s16") when bank != NULL.
+ *     Moving a live stream from one bank to another is allowed (the state layout is the same) and undefined beyond "no fault". */
+#define FE_MAX_WEIGHT_BANKS 64
+int fe_set_weight_banks(fe_handle* h, int n_banks, void* stream);
+int fe_weight_banks(const fe_handle* h);
+int fe_load_weights_bank(fe_handle* h, int bank, const float* blob_dev, size_t nfloats, void* stream);
+int fe_step_streams_banked(fe_handle* h, const void* wav_in_dev, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,
+                           void* wav_out_dev, size_t out_count, int n, int T_max, int format, const float* min_gain, fe_stream_levels* levels,
+                           const int* bank, void* stream);
+int fe_step_streams_banked_pinned(fe_handle* h, const void* wav_in_host, size_t in_count, float* state_dev, int capacity,
+                                  const fe_stream_desc* desc_dev, void* wav_out_host, size_t out_count, int n, int T_max, int format,
+                                  const float* min_gain, fe_stream_levels* levels, const int* bank, void* stream);
+
 /* The same step for callers whose audio lives in HOST memory (the reference's scripts/test_onnx.py feeds numpy arrays hop by hop):
  * n_calls consecutive fe_step calls of T hops each, hop block c = hops c*T .. c*T+T-1 of
  *   wav_in_host [b*in_stride + t*H + n], wav_out_host [b*out_stride + t*H + n]   (page-locked for asynchronous copies; pageable works, slower)
