@@ -63,13 +63,47 @@ struct Wg8 {
     static constexpr bool OK = OK0 && PLAN_OK;
 };
 
+// Address windows.  fp32 MFMAs and the vector ALU share the SIMD's datapath, so every v_add / v_mul / v_or that forms an LDS address is
+// paid in matrix time.  The per-lane part of the frame's few address patterns is therefore formed ONCE, as a 32-bit LDS pointer
+// the compiler cannot take apart again (the empty asm: otherwise it re-derives lane * 4 | constant, row * LDC, ... next to every use); a
+// phase then reaches its operands as window + compile-time constant, which the ds instructions carry as their 16-bit immediate offset.
+using LdsF = __attribute__((address_space(3))) float;
+using LdsV4 = __attribute__((address_space(3))) f32x4;
+__device__ __forceinline__ LdsF* lds_ptr(const float* p) { return (LdsF*)p; }          // (p points into LDS)
+__device__ __forceinline__ LdsF* lds_window(const float* p) {
+    LdsF* q = lds_ptr(p);
+    asm volatile("" : "+v"(q));
+    return q;
+}
+__device__ __forceinline__ f32x4 lds_v4(const LdsF* p) { return *reinterpret_cast<const LdsV4*>(p); }
+// StageSide (the weight-staging side job of a GEMM) whose commit() writes through a window: w = &destination[wave * 256 + lane * 4] of piece 0
+template <int NPW, int NP>
+struct Stage8 : StageSide<NPW, NP, kWaves8> {
+    LdsF* w;
+    __device__ __forceinline__ void commit() const {
+        using B = StageSide<NPW, NP, kWaves8>;
+#pragma unroll
+        for (int i = 0; i < B::NPI; ++i) {
+            const int p = this->j->wave + kWaves8 * i;
+            if (kWaves8 * i + kWaves8 - 1 < NP || p < NP) *reinterpret_cast<LdsV4*>(w + i * (kWaves8 * 256)) = this->j->r[i];
+        }
+    }
+};
+// An accumulator that starts as the splat of one LDS word: one read and three v_mov.  (Four reads of the word straight into the
+// accumulator's registers - no vector ALU instruction at all - were measured: 31.25 us against 30.65 us, the LDS pipe is the dearer one here.)
+__device__ __forceinline__ f32x4 lds_splat(const float* p) {
+    const float b = *p;
+    return f32x4{b, b, b, b};
+}
+
 // One conv-layout GEMM job of a wave: row tile mt x the NT channel tiles J0 .. J0 + NT - 1, K = 4 KS.
 //   af(ks) -> A fragment element, bf(j, ks) -> B fragment element of ABSOLUTE tile j, bias(j) -> accumulator start.
-// Epilogue: optional activation (Shape::EPA, scaled trunk; ap: its constant), store to out[(row0 + m)][col] for col < NCOLS.
+// Epilogue: optional activation (Shape::EPA, scaled trunk; ap: its constant), store to out[(row0 + m)][col] for col < NCOLS:
+//   dst = &out[row0 + 16 mt + 4 lg][li], this lane's first element (the C-store window of the frame plus a constant, or formed in place).
 template <class S, int NT, int J0, int KS, int NCOLS, int LDO, bool ACT, class AF, class BF, class BI, class SIDE>
-__device__ __forceinline__ void conv8(AF&& af, BF&& bf, BI&& bias, const SIDE& side, float* out, int row0, int mt, int lane, float ap = 0.0f) {
+__device__ __forceinline__ void conv8(AF&& af, BF&& bf, BI&& bias, const SIDE& side, LdsF* dst, int lane, float ap = 0.0f) {
     if constexpr (NT > 0) {
-        const int li = lane & 15, lg = lane >> 4;
+        const int li = lane & 15;
         f32x4 acc[1][NT];
 #pragma unroll
         for (int j = 0; j < NT; ++j) acc[0][j] = bias(J0 + j);
@@ -81,10 +115,9 @@ __device__ __forceinline__ void conv8(AF&& af, BF&& bf, BI&& bias, const SIDE& s
             if (col < NCOLS) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const int m = 16 * mt + 4 * lg + r;
                     float v = acc[0][j][r];
                     if (ACT) v = act_scaled_f<S::EPA>(v, ap);
-                    out[(row0 + m) * LDO + col] = v;
+                    dst[r * LDO + 16 * (J0 + j)] = v;
                 }
             }
         }
@@ -98,10 +131,11 @@ __device__ __forceinline__ void conv8(AF&& af, BF&& bf, BI&& bias, const SIDE& s
 }
 // the pair split: wh = 0 takes the tiles [0, NA), wh = 1 the tiles [NA, NA + NB)
 template <class S, int NA, int NB, int KS, int NCOLS, int LDO, bool ACT, class AF, class BF, class BI, class SIDE>
-__device__ __forceinline__ void conv8_pair(int wh, AF&& af, BF&& bf, BI&& bias, const SIDE& side, float* out, int row0, int mt, int lane,
-                                           float ap = 0.0f) {
-    if (wh == 0) conv8<S, NA, 0, KS, NCOLS, LDO, ACT>(af, bf, bias, side, out, row0, mt, lane, ap);
-    else conv8<S, NB, NA, KS, NCOLS, LDO, ACT>(af, bf, bias, side, out, row0, mt, lane, ap);
+__device__ __forceinline__ void conv8_pair(int wh, AF&& af, BF&& bf, BI&& bias, const SIDE& side, LdsF* dst, int lane, float ap = 0.0f) {
+    // (with the store addresses window + constant, the last activation + store of the two roles differ in operands only and the compiler
+    // sinks that chain into a common tail behind the epilogue; keeping it in the roles was measured 0.2 us slower)
+    if (wh == 0) conv8<S, NA, 0, KS, NCOLS, LDO, ACT>(af, bf, bias, side, dst, lane, ap);
+    else conv8<S, NB, NA, KS, NCOLS, LDO, ACT>(af, bf, bias, side, dst, lane, ap);
 }
 
 // DBG: per-stage dumps (fe_debug_step) and the phase cycle probes (fe_profile_step).  PERSIST: more streams than CUs,
@@ -174,6 +208,26 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
     wb.k4d = 0;
     float ap = 0.0f;                                 // the activation's constant (Shape::EPP)
     if constexpr (S::EPP) ap = wp[o.act_p];
+    // ---- the frame's address windows (lds_window), formed here while the prologue's loads are in flight:
+    //   wl0 / wl1  staged B (or A) fragment `+ lane` of the weight buffers WB0 / WB1 - every unit, and every block slot, lies within 64 KB of
+    //              its buffer's start                        wq0 / wq1  their 4x replicated bias tables, `+ 4 (lane & 15)`
+    //   stC        C / D store of the conv-layout GEMMs, &[16 ws + 4 lg][li] of an [..][LDC] buffer at LDS offset 0: the skips and both decoder
+    //              buffers end below 64 KB                   stX  the token GEMMs' store into X, &X[16 wh + 4 lg][min(col, C2)] (tok_dst)
+    LdsF* const wl0 = lds_window(smem + W8::WB0 + lane);
+    LdsF* const wl1 = lds_window(smem + W8::WB1 + lane);
+    //   stG / stS  the GRU epilogue of waves 0 - 3 (row tile wave & 1, channel group wave >> 1): &Hl[16 g_rt + 4 lg][ch] - Hs lies a constant
+    //              behind it - and the same element of block 0 in the state stash
+    LdsF* const stG = lds_window(smem + L::HL + (16 * (wave0 & 1) + 4 * (lane >> 4)) * LDX + 16 * (wave0 >> 1) + (lane & 15));
+    LdsF* const stS = lds_window(smem + W8::HST + (16 * (wave0 & 1) + 4 * (lane >> 4)) * C2 + 16 * (wave0 >> 1) + (lane & 15));
+    //   sw0 / sw1  this thread's 16 bytes of piece `wave` of a unit staged into WB0 / WB1 (Stage8::commit)
+    LdsF* const sw0 = lds_window(smem + W8::WB0 + wave0 * 256 + lane * 4);
+    LdsF* const sw1 = lds_window(smem + W8::WB1 + wave0 * 256 + lane * 4);
+    auto swin = [&](int dst_floats) { return dst_floats >= W8::WB1 ? sw1 + (dst_floats - W8::WB1) : sw0 + (dst_floats - W8::WB0); };
+    LdsF* const wq0 = lds_window(smem + W8::WB0 + 4 * (lane & 15));
+    LdsF* const wq1 = lds_window(smem + W8::WB1 + 4 * (lane & 15));
+    LdsF* const stC = lds_window(smem + (16 * (wave0 & 3) + 4 * (lane >> 4)) * LDC + (lane & 15));
+    LdsF* const stX = lds_window(smem + L::X + (16 * (wave0 >> 2) + 4 * (lane >> 4)) * LDX +
+                                 (16 * (wave0 & 3) + (lane & 15) < C2 ? 16 * (wave0 & 3) + (lane & 15) : C2));
 
     // ---- one-time: the zero halos (compressed spectrum, skip buffers), twiddles, weight unit 0.
     // !PERSIST (one stream per workgroup): everything the front of the frame waits for is requested HERE, in one memory round trip
@@ -313,6 +367,11 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
         const int fpar = (S::NU & 1) ? (fc & 1) : 0;
 #define FE8_BEGIN_UNIT(U)                                                                          \
         constexpr int fe_un_ = ((U) + 1 == S::NU) ? 0 : (U) + 1;                                   \
+        /* (NU is even - Wg8::PLAN_OK -, so unit U is read from WB0 / WB1 by its parity: a compile-time choice of window) */ \
+        constexpr int ub_ = o.u_off[(U)];                                                          \
+        LdsF* const wl_ = ((U) & 1) ? wl1 : wl0;                                                   \
+        LdsF* const wq_ = ((U) & 1) ? wq1 : wq0;                                                   \
+        (void)ub_; (void)wl_; (void)wq_;                                                           \
         {                                                                                          \
             const int slot_ = ((U) & 1) ^ fpar;                                                    \
             job.l = smem + (slot_ ? W8::WB0 : W8::WB1);                                            \
@@ -320,7 +379,7 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
             wb.lds = smem + (slot_ ? W8::WB1 : W8::WB0);                                           \
             wb.base = o.u_off[(U)];                                                                \
         }                                                                                          \
-        const StageSide<NPW, ((!PERSIST && ((U) + 1 == S::NU || (U) == 0)) || (U) == S::U_RFPRE + 1) ? 0 : o.u_size[fe_un_] / 256, kWaves8> stage{&job}
+        const Stage8<NPW, ((!PERSIST && ((U) + 1 == S::NU || (U) == 0)) || (U) == S::U_RFPRE + 1) ? 0 : o.u_size[fe_un_] / 256> stage{{&job}, ((U) & 1) ? sw0 : sw1}
         FE_CLK(0);
         // =========================== STFT (a1-a3) ===========================
         // LDS quarters of the FFT arena: q0 windowed frame / iSTFT partial sums, q1 iSTFT partial sums, q3 spectrum {Re[N/2], Im[N/2]}
@@ -380,15 +439,13 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
         // =========================== enc_pre (a5): strided conv as a K = 16 GEMM ===========================
         {
             FE8_BEGIN_UNIT(0);
+            // A[row][kk] = sc[c][4 (row + tp) + s] with kk = 4 ks + lg = 8 tp + 2 s + c: lg gives c and the low bit of s, ks the rest - a
+            // per-lane base and a compile-time offset per k-step
+            const float* const a0 = sc + (lg & 1) * S::LDS_S + 4 * (16 * ws + li) + (lg >> 1);
             conv8_pair<S, W8::NTA, W8::NTB, 4, C1, LDC, true>(
-                wh,
-                [&](int ks) {
-                    const int kk = 4 * ks + lg;
-                    const int c = kk & 1, s = (kk >> 1) & 3, tp = kk >> 3;
-                    return sc[c * S::LDS_S + 4 * (16 * ws + li + tp) + s];
-                },
-                [&](int j, int ks) { return wb.at(o.enc_pre_w + (j * 4 + ks) * 64); },
-                [&](int j) { return wb.at16x4(o.enc_pre_b + j * 64); }, stage, Ebuf, 1, ws, lane, ap);
+                wh, [&](int ks) { return a0[4 * (ks >> 1) + 2 * (ks & 1)]; },
+                [&](int j, int ks) -> float { return wl_[o.enc_pre_w - ub_ + (j * 4 + ks) * 64]; },
+                [&](int j) { return lds_v4(wq_ + (o.enc_pre_b - ub_ + j * 64)); }, stage, stC + (L::E + LDC), lane, ap);
         }
         __syncthreads();
         dbg_dump<S, NTH>(a, b, 2, Ebuf + LDC, LDC);
@@ -405,8 +462,8 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
                 const float* const t0 = in + (16 * ws + li) * LDC + lg;
                 conv8_pair<S, W8::NTA, W8::NTB, 3 * S::KS_C, C1, LDC, true>(
                     wh, [&](int ks) { return t0[(ks / S::KS_C) * LDC + 4 * (ks % S::KS_C)]; },
-                    [&](int j, int ks) { return wb.at(o.enc_w[l] + (j * (3 * S::KS_C) + ks) * 64); },
-                    [&](int j) { return wb.at16x4(o.enc_b[l] + j * 64); }, stage, out, 1, ws, lane, ap);
+                    [&](int j, int ks) -> float { return wl_[o.enc_w[l] - ub_ + (j * (3 * S::KS_C) + ks) * 64]; },
+                    [&](int j) { return lds_v4(wq_ + (o.enc_b[l] - ub_ + j * 64)); }, stage, stC + (L::E + (l + 1) * S::ACT + LDC), lane, ap);
             }
             if (l == 0) FE_CLK(42);
             __syncthreads();
@@ -437,22 +494,19 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
         const float* const sGx = smem + W8::WB0 + 1 * W8::SLOT;
         const float* const sGh = smem + W8::WB0 + 3 * W8::SLOT;
         const float* const sF = smem + W8::WB0 + 0 * W8::SLOT;
-        const float* const sQ = smem + W8::WB0 + 2 * W8::SLOT;
+        static_assert(W8::WB1 == W8::WB0 + 2 * W8::SLOT, "slots 2 (qkv) and 3 are reached through WB1's window");
         constexpr int NPWB = W8::NPWB;
         DmaJobT<NPWB> jb1, jb2;                        // staging jobs of the block units (two may ride in one GEMM)
         jb1.rsrc = wb.rsrc; jb1.wave = wave; jb1.lane = lane; jb1.l = smem; jb1.soff = 0;
         jb2 = jb1;
         auto stage_to = [&](DmaJobT<NPWB>& j, int src_floats, int dst_floats) { j.l = smem + dst_floats; j.soff = (src_floats + wave * 256) * 4; };
         constexpr int u8_stride = S::KB > 1 ? o.u8_gx[1] - o.u8_gx[0] : 0;
-        using StG = StageSide<NPWB, S::U8_G / 256, kWaves8>;
-        using StF = StageSide<NPWB, S::U8_F / 256, kWaves8>;
-        using StQ = StageSide<NPWB, S::U8_Q / 256, kWaves8>;
+        using StG = Stage8<NPWB, S::U8_G / 256>;
+        using StF = Stage8<NPWB, S::U8_F / 256>;
+        using StQ = Stage8<NPWB, S::U8_Q / 256>;
         float pe_r[4];
-        // unpredicated epilogue stores into the [F2P][C2 + 2] token buffers (pad rows are real rows, lanes past C2 aim at the pad column)
-        auto tok_dst = [&](float* base) {
-            const int col = 16 * ws + li;
-            return base + (16 * wh + 4 * lg) * LDX + (col < C2 ? col : C2);
-        };
+        // unpredicated epilogue stores into the [F2P][C2 + 2] token buffer X (pad rows are real rows, lanes past C2 aim at the pad column):
+        // stX, the prologue's window &X[16 wh + 4 lg][min(16 ws + li, C2)]
         int hs_off[HPT];
 #pragma unroll
         for (int q = 0; q < HPT; ++q) {
@@ -465,12 +519,12 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
             const float* Ein = Ebuf + S::NL * S::ACT + LDC;   // row 0 = bin 0
             FE8_BEGIN_UNIT(S::U_RFPRE);
             stage_to(jb1, o.u8_gx[0], W8::WB0 + 1 * W8::SLOT);          // block 0's GRU input weights -> slot 1
-            const StG stg{&jb1};
+            const StG stg{{&jb1}, swin(W8::WB0 + 1 * W8::SLOT)};
             f32x4 acc[1][1];
             acc_init_zero<1, 1>(acc);
             const int nt = ws < S::NTC ? ws : S::NTC - 1;
             mma_panel<1, 1, KS, PDK>(
-                acc, [&](int, int ks) { return wb.at(o.rfpre_lin + (wh * KS + ks) * 64); },
+                acc, [&](int, int ks) -> float { return wl_[o.rfpre_lin - ub_ + (wh * KS + ks) * 64]; },
                 [&](int, int ks) { return Ein[(4 * ks + lg) * LDC + 16 * nt + li]; }, side2(stage, stg));
             stage.commit();
             stg.commit();
@@ -485,24 +539,24 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
             // X[f2][c2] = Y1[f2][:] . Wc[c2][:] + b
             FE8_BEGIN_UNIT(S::U_RFPRE + 1);
             stage_to(jb1, o.u8_gh[0], W8::WB0 + 3 * W8::SLOT);          // ... and the hidden weights -> slot 3
-            const StG stg{&jb1};
+            const StG stg{{&jb1}, swin(W8::WB0 + 3 * W8::SLOT)};
             float hpre[HPT];
             const float* hg0 = a.h + (size_t)sb * (F2 * C2);
 #pragma unroll
             for (int q = 0; q < HPT; ++q) { const int i = tid + q * NTH; hpre[q] = hg0[i < F2 * C2 ? i : F2 * C2 - 1]; }
             f32x4 acc[1][1];
             const int nt = ws < S::NT2 ? ws : S::NT2 - 1;
-            acc[0][0] = wb.at16x4(o.rfpre_b + nt * 64);
+            acc[0][0] = lds_v4(wq_ + (o.rfpre_b - ub_ + nt * 64));
             const float* ya = Y1 + (16 * wh + li) * LDC + lg;
+            const LdsF* const wt = wl_ + (o.rfpre_w - ub_ + nt * (S::KS_C * 64));
             mma_panel<1, 1, S::KS_C, PDK>(
                 acc, [&](int, int ks) { return ya[4 * ks]; },
-                [&](int, int ks) { return wb.at(o.rfpre_w + (nt * S::KS_C + ks) * 64); }, stg);
+                [&](int, int ks) -> float { return wt[ks * 64]; }, stg);
             (void)stage;
             stg.commit();
             xr = acc[0][0];
-            float* xd = tok_dst(Xb);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) xd[r * LDX] = acc[0][0][r];
+            for (int r = 0; r < 4; ++r) stX[r * LDX] = acc[0][0][r];
 #pragma unroll
             for (int q = 0; q < HPT; ++q) Hs[hs_off[q]] = hpre[q];
         }
@@ -522,8 +576,8 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
                 // Staged meanwhile: this block's rnn_fc -> slot 0 and qkv -> slot 2.
                 stage_to(jb1, o.u8_f1[0] + ub, W8::WB0 + 0 * W8::SLOT);
                 stage_to(jb2, o.u8_q[0] + ub, W8::WB0 + 2 * W8::SLOT);
-                const StF st1{&jb1};
-                const StQ st2{&jb2};
+                const StF st1{{&jb1}, swin(W8::WB0 + 0 * W8::SLOT)};
+                const StQ st2{{&jb2}, swin(W8::WB0 + 2 * W8::SLOT)};
                 const auto sideg = side2(st1, st2);
                 if (k == 0) {
 #pragma unroll
@@ -534,8 +588,8 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
                 }
                 const float* xa = Xb + (16 * g_rt + li) * LDX + lg;
                 const float* ha = Hs + (16 * g_rt + li) * LDX + lg;
-                const float* wx = sGx + g_t0 * (K2 * 64) + lane;
-                const float* wh_ = sGh + g_t0 * (K2 * 64) + lane;
+                const LdsF* const wx = wl0 + (1 * W8::SLOT + g_t0 * (K2 * 64));         // = sGx + .. + lane
+                const LdsF* const wh_ = wl1 + (1 * W8::SLOT + g_t0 * (K2 * 64));        // = sGh + .. + lane (slot 3 = WB1 + SLOT)
                 const float* bx = sGx + S::G8_NT * K2 * 64 + g_t0 * 16 + li;
                 const float* bh = sGh + S::G8_NT * K2 * 64 + g_t0 * 16 + li;
                 __builtin_amdgcn_sched_barrier(0);
@@ -545,14 +599,13 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
                     const int ch = 16 * (wave >> 1) + li;
                     float hprev[4];                      // previous state of this lane's outputs: in flight under the GEMM
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) hprev[r] = Hs[(16 * g_rt + 4 * lg + r) * LDX + ch];
-                    const float b0 = bx[0], b1 = bx[16], b2 = bx[32], b3 = bh[32];
-                    f32x4 ar = f32x4{b0, b0, b0, b0}, az = f32x4{b1, b1, b1, b1};
-                    f32x4 anx = f32x4{b2, b2, b2, b2}, anh = f32x4{b3, b3, b3, b3};
+                    for (int r = 0; r < 4; ++r) hprev[r] = stG[(L::HS - L::HL) + r * LDX];           // = Hs[(16 g_rt + 4 lg + r) LDX + ch]
+                    f32x4 ar = lds_splat(bx), az = lds_splat(bx + 16);
+                    f32x4 anx = lds_splat(bx + 32), anh = lds_splat(bh + 32);
                     mma_panel_sel<1, 3, 2 * K2, PDK>(
                         [&](int, int j, int ks) -> f32x4& { return j == 0 ? ar : (j == 1 ? az : (ks < K2 ? anx : anh)); },
                         [&](int, int ks) { return ks < K2 ? xa[4 * ks] : ha[4 * (ks - K2)]; },
-                        [&](int j, int ks) { return ks < K2 ? wx[(j * K2 + ks) * 64] : wh_[(j * K2 + (ks - K2)) * 64]; }, sideg);
+                        [&](int j, int ks) -> float { return ks < K2 ? wx[(j * K2 + ks) * 64] : wh_[(j * K2 + (ks - K2)) * 64]; }, sideg);
                     __builtin_amdgcn_sched_barrier(0);
                     if (k == 0) FE_CLK(46);
                     float hn[4];
@@ -567,8 +620,8 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             const int row = 16 * g_rt + 4 * lg + r;
-                            Hl[row * LDX + ch] = hn[r];
-                            if constexpr (W8::HSTASH) smem[W8::HST + k * (F2 * C2) + row * C2 + ch] = hn[r];
+                            stG[r * LDX] = hn[r];                                                    // = Hl[row * LDX + ch]
+                            if constexpr (W8::HSTASH) stS[k * (F2 * C2) + r * C2] = hn[r];              // = stash[k][row][ch]
                             else hg[row * C2 + ch] = hn[r];
                         }
                     }
@@ -586,17 +639,15 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
                     f32x4 s0, s1 = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
                     __builtin_amdgcn_s_setprio(3);
                     if (!hhalf) {
-                        const float b0 = bx[0];
-                        s0 = f32x4{b0, b0, b0, b0};
+                        s0 = lds_splat(bx);
                         mma_panel_sel<1, 1, K2, PDK>([&](int, int, int ks) -> f32x4& { return (ks & 1) ? s1 : s0; },
-                                                     [&](int, int ks) { return xa[4 * ks]; }, [&](int, int ks) { return wx[ks * 64]; }, sideg);
+                                                     [&](int, int ks) { return xa[4 * ks]; }, [&](int, int ks) -> float { return wx[ks * 64]; }, sideg);
                     } else {
-                        const float b1 = bh[0];
-                        s0 = f32x4{b1, b1, b1, b1};
+                        s0 = lds_splat(bh);
                         // (the chains go by the parity of the k-step of the whole 2 K2-step x | h panel: K2 is odd here, so the biased chain takes
                         // the h half's odd local steps)
                         mma_panel_sel<1, 1, K2, PDK>([&](int, int, int ks) -> f32x4& { return ((ks + K2) & 1) ? s1 : s0; },
-                                                     [&](int, int ks) { return ha[4 * ks]; }, [&](int, int ks) { return wh_[ks * 64]; }, sideg);
+                                                     [&](int, int ks) { return ha[4 * ks]; }, [&](int, int ks) -> float { return wh_[ks * 64]; }, sideg);
                     }
                     // (the priority stays raised through the hand-over and the gate math: at priority 0 every instruction of this dependent chain
                     // waited for a gap between the MFMAs of the SIMD's 54-MFMA job - 1.5 k cycles for ~35 instructions, and this wave arrived last)
@@ -648,24 +699,22 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
             {
                 // x += rnn_fc(h') (+ pe in block 0); staged meanwhile: the next block's GRU input weights -> slot 1
                 stage_to(jb1, o.u8_gx[0] + ub + u8_stride, W8::WB0 + 1 * W8::SLOT);
-                const StG stn{&jb1};
+                const StG stn{{&jb1}, swin(W8::WB0 + 1 * W8::SLOT)};
                 f32x4 acc[1][1];
-                const float bj = sF[S::NT2 * K2 * 64 + ntf * 16 + li];
-                acc[0][0] = f32x4{bj, bj, bj, bj};
+                acc[0][0] = lds_splat(sF + S::NT2 * K2 * 64 + ntf * 16 + li);
                 const float* hla = Hl + (16 * wh + li) * LDX + lg;
-                const float* wf = sF + ntf * (K2 * 64) + lane;
+                const LdsF* const wf = wl0 + ntf * (K2 * 64);                           // = sF + .. + lane
                 if (k + 1 < S::KB) {
-                    mma_panel<1, 1, K2, PDK>(acc, [&](int, int ks) { return hla[4 * ks]; }, [&](int, int ks) { return wf[ks * 64]; }, stn);
+                    mma_panel<1, 1, K2, PDK>(acc, [&](int, int ks) { return hla[4 * ks]; }, [&](int, int ks) -> float { return wf[ks * 64]; }, stn);
                     stn.commit();
                 } else
-                    mma_panel<1, 1, K2, PDK>(acc, [&](int, int ks) { return hla[4 * ks]; }, [&](int, int ks) { return wf[ks * 64]; }, NoSide{});
-                float* xd = tok_dst(Xb);
+                    mma_panel<1, 1, K2, PDK>(acc, [&](int, int ks) { return hla[4 * ks]; }, [&](int, int ks) -> float { return wf[ks * 64]; }, NoSide{});
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     float v = acc[0][0][r] + xr[r];
                     if (k == 0) v += pe_r[r];
                     xr[r] = v;
-                    xd[r * LDX] = v;
+                    stX[r * LDX] = v;
                 }
             }
             __syncthreads();
@@ -674,17 +723,17 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
             {
                 // qkv = x W_qkv^T -> Gi (columns per head interleaved [h][q|k|v][hd]); staged meanwhile: attn_fc -> slot 0
                 stage_to(jb1, o.u8_f2[0] + ub, W8::WB0 + 0 * W8::SLOT);
-                const StF st1{&jb1};
+                const StF st1{{&jb1}, swin(W8::WB0 + 0 * W8::SLOT)};
                 f32x4 acc[1][NTPW3];
                 acc_init_zero<1, NTPW3>(acc);
                 __builtin_amdgcn_sched_barrier(0);
                 if (k == 0) FE_CLK(50);
                 const float* xa = Xb + (16 * wh + li) * LDX + lg;
                 mma_panel<1, NTPW3, K2, PDK>(acc, [&](int, int ks) { return xa[4 * ks]; },
-                                             [&](int j, int ks) {
+                                             [&](int j, int ks) -> float {
                                                  int nt = ws + 4 * j;
                                                  nt = nt < S::NT3 ? nt : S::NT3 - 1;
-                                                 return sQ[(nt * K2 + ks) * 64 + lane];
+                                                 return wl1[(nt * K2 + ks) * 64];                // = sQ[.. + lane] (slot 2 = WB1)
                                              }, st1);
                 st1.commit();
                 __builtin_amdgcn_sched_barrier(0);
@@ -715,31 +764,29 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
                     for (int q = 0; q < HPT; ++q) { const int i = tid + q * NTH; hpre[q] = hgn[i < F2 * C2 ? i : F2 * C2 - 1]; }
                 }
                 f32x4 acc[1][1];
-                const float bj = sF[S::NT2 * K2 * 64 + ntf * 16 + li];
-                acc[0][0] = f32x4{bj, bj, bj, bj};
+                acc[0][0] = lds_splat(sF + S::NT2 * K2 * 64 + ntf * 16 + li);
                 const float* hla = Hl + (16 * wh + li) * LDX + lg;
-                const float* wf = sF + ntf * (K2 * 64) + lane;
+                const LdsF* const wf = wl0 + ntf * (K2 * 64);                           // = sF + .. + lane
                 if (k + 1 < S::KB) {
                     stage_to(jb1, o.u8_gh[0] + ub + u8_stride, W8::WB0 + 3 * W8::SLOT);
-                    const StG stn{&jb1};
-                    mma_panel<1, 1, K2, PDK>(acc, [&](int, int ks) { return hla[4 * ks]; }, [&](int, int ks) { return wf[ks * 64]; }, stn);
+                    const StG stn{{&jb1}, swin(W8::WB0 + 3 * W8::SLOT)};
+                    mma_panel<1, 1, K2, PDK>(acc, [&](int, int ks) { return hla[4 * ks]; }, [&](int, int ks) -> float { return wf[ks * 64]; }, stn);
                     stn.commit();
                 } else {
                     stage_to(jb1, o.u_off[S::U_RFPOST], W8::WB1);
-                    const StageSide<NPWB, o.u_size[S::U_RFPOST] / 256, kWaves8> stn{&jb1};
-                    mma_panel<1, 1, K2, PDK>(acc, [&](int, int ks) { return hla[4 * ks]; }, [&](int, int ks) { return wf[ks * 64]; }, stn);
+                    const Stage8<NPWB, o.u_size[S::U_RFPOST] / 256> stn{{&jb1}, swin(W8::WB1)};
+                    mma_panel<1, 1, K2, PDK>(acc, [&](int, int ks) { return hla[4 * ks]; }, [&](int, int ks) -> float { return wf[ks * 64]; }, stn);
                     stn.commit();
                 }
                 if (k + 1 < S::KB) {
 #pragma unroll
                     for (int q = 0; q < HPT; ++q) Hs[hs_off[q]] = hpre[q];
                 }
-                float* xd = tok_dst(Xb);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const float v = acc[0][0][r] + xr[r];
                     xr[r] = v;
-                    xd[r * LDX] = v;
+                    stX[r * LDX] = v;
                 }
             }
             __syncthreads();
@@ -754,9 +801,9 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
             constexpr int KS = F2 / 4;
             FE8_BEGIN_UNIT(S::U_RFPOST);
             conv8_pair<S, W8::N2A, W8::N2B, KS, C2, LDX, false>(
-                wh, [&](int ks) { return wb.at(o.rfpost_lin + (ws * KS + ks) * 64); },
+                wh, [&](int ks) -> float { return wl_[o.rfpost_lin - ub_ + (ws * KS + ks) * 64]; },
                 [&](int j, int ks) { return Xb[(4 * ks + lg) * LDX + 16 * j + li]; },
-                [&](int) { return f32x4{0.0f, 0.0f, 0.0f, 0.0f}; }, stage, Y2, 0, ws, lane);
+                [&](int) { return f32x4{0.0f, 0.0f, 0.0f, 0.0f}; }, stage, lds_ptr(Y2 + (16 * ws + 4 * lg) * LDX + li), lane);
         }
         __syncthreads();
         // rf_post's 1x1 conv is folded into decoder layer 0's 1x1 on the host (fe_api.hip::pack_weights): that layer reads Y2 as its
@@ -792,8 +839,8 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
                 const float* sk = skip + (16 * ws + li + 1) * LDC + lg;
                 conv8_pair<S, W8::NTA, W8::NTB, K0 + S::KS_C, C1, LDC, true>(
                     wh, [&](int ks) { return ks < K0 ? xa[4 * ks] : sk[4 * (ks - K0)]; },
-                    [&](int j, int ks) { return wb.at(o.dec1_w[l] + (j * (K0 + S::KS_C) + ks) * 64); },
-                    [&](int j) { return wb.at16x4(o.dec1_b[l] + j * 64); }, stage, Wy, 1, ws, lane, ap);
+                    [&](int j, int ks) -> float { return wl_[o.dec1_w[l] - ub_ + (j * (K0 + S::KS_C) + ks) * 64]; },
+                    [&](int j) { return lds_v4(wq_ + (o.dec1_b[l] - ub_ + j * 64)); }, stage, stC + (L::W0 + LDC), lane, ap);
             }
             __syncthreads();
             {
@@ -801,8 +848,8 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
                 const float* const t0 = Wy + (16 * ws + li) * LDC + lg;
                 conv8_pair<S, W8::NTA, W8::NTB, 3 * S::KS_C, C1, LDC, true>(
                     wh, [&](int ks) { return t0[(ks / S::KS_C) * LDC + 4 * (ks % S::KS_C)]; },
-                    [&](int j, int ks) { return wb.at(o.dec3_w[l] + (j * (3 * S::KS_C) + ks) * 64); },
-                    [&](int j) { return wb.at16x4(o.dec3_b[l] + j * 64); }, stage, Wx, 1, ws, lane, ap);
+                    [&](int j, int ks) -> float { return wl_[o.dec3_w[l] - ub_ + (j * (3 * S::KS_C) + ks) * 64]; },
+                    [&](int j) { return lds_v4(wq_ + (o.dec3_b[l] - ub_ + j * 64)); }, stage, stC + (L::W1 + LDC), lane, ap);
             }
             __syncthreads();
             dbg_dump<S, NTH>(a, b, 5 + S::NL + 2 * S::KB + l, Wx + LDC, LDC);
@@ -820,8 +867,8 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
             const float* sk = Ebuf + (16 * ws + li + 1) * LDC + lg;
             conv8_pair<S, W8::NTA, W8::NTB, 2 * S::KS_C, C1, LDC, true>(
                 wh, [&](int ks) { return ks < S::KS_C ? xa[4 * ks] : sk[4 * (ks - S::KS_C)]; },
-                [&](int j, int ks) { return wb.at(o.post1_w + (j * (2 * S::KS_C) + ks) * 64); },
-                [&](int j) { return wb.at16x4(o.post1_b + j * 64); }, stage, Wy, 1, ws, lane, ap);
+                [&](int j, int ks) -> float { return wl_[o.post1_w - ub_ + (j * (2 * S::KS_C) + ks) * 64]; },
+                [&](int j) { return lds_v4(wq_ + (o.post1_b - ub_ + j * 64)); }, stage, stC + (L::W0 + LDC), lane, ap);
         }
         __syncthreads();
         {
@@ -829,8 +876,8 @@ __global__ void __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(
             FE8_BEGIN_UNIT(S::U_POST + 1);
             const float* xa = Wy + (16 * ws + li + 1) * LDC + lg;
             conv8_pair<S, 1, 0, S::KS_C, 16, S::LDP, false>(
-                wh, [&](int ks) { return xa[4 * ks]; }, [&](int j, int ks) { return wb.at(o.post_t_w + (j * S::KS_C + ks) * 64); },
-                [&](int) { return f32x4{0.0f, 0.0f, 0.0f, 0.0f}; }, stage, PT, 0, ws, lane);
+                wh, [&](int ks) { return xa[4 * ks]; }, [&](int j, int ks) -> float { return wl_[o.post_t_w - ub_ + (j * S::KS_C + ks) * 64]; },
+                [&](int) { return f32x4{0.0f, 0.0f, 0.0f, 0.0f}; }, stage, lds_ptr(PT + (16 * ws + 4 * lg) * S::LDP + li), lane);
             if (wave < 4) Dft<S>::load(idc, wb, o, wave);         // iSTFT constants, in flight during the mask phase
             mb0 = wb.scalar(o.post_t_b);
             mb1 = wb.scalar(o.post_t_b + 1);
