@@ -169,8 +169,6 @@ struct fe_handle {
         step_kernel = env_int("FE_WG8", FE_STEP_KERNEL_WG8, FE_STEP_KERNEL_WAVES4, FE_STEP_KERNEL_WG8_PERSIST);
     }
     unsigned int* pipe_flags_dev = nullptr;   // fe_spec_step's frame counters [max_wgs][KB] (fe_offline keeps its own in the work buffer)
-    std::vector<hipStream_t> tb_streams;      // time-batched engine: the streams its nodes are spread over (lazy; tb_run)
-    std::vector<hipEvent_t> tb_events;        // ... and its event pool
     unsigned long long* tb_probe_dev = nullptr;   // FE_TB_PROBE builds: phase clocks [4][kProbeSlots]
     hipStream_t host_streams[2] = {nullptr, nullptr};     // fe_step_host: copy-in / copy-out streams (lazy)
     hipEvent_t host_events[7] = {};                       // ... and its events
@@ -183,7 +181,6 @@ struct fe_handle {
     float* sb_dev = nullptr;                  // stream-batched per-hop step of BSRNN / FSPEN / LiSenNet: its scratch (ensure_sb_scratch)
     int sb_streams = 0;                       // (grow-only, sized by fe_state_init / the first step of a larger batch)
     size_t tb_work_floats = 0;
-    unsigned int* tb_prog_dev = nullptr;      // fused stages: the scan workgroups' frame counters [KB][2 * max_wgs]
     std::vector<Section> sections;
     size_t blob_floats = 0;
     float* packed_dev = nullptr;   // the weight banks: n_banks packed buffers, bank k at packed_dev + k * bank_stride (allocated by the first load)
@@ -972,10 +969,7 @@ void fe_destroy(fe_handle* h) {
     if (h->skip_dev) (void)hipFree(h->skip_dev);
     if (h->tables_dev) (void)hipFree(h->tables_dev);
     if (h->pipe_flags_dev) (void)hipFree(h->pipe_flags_dev);
-    for (hipStream_t s : h->tb_streams) (void)hipStreamDestroy(s);
-    for (hipEvent_t e : h->tb_events) (void)hipEventDestroy(e);
     if (h->tb_probe_dev) (void)hipFree(h->tb_probe_dev);
-    if (h->tb_prog_dev) (void)hipFree(h->tb_prog_dev);
     if (h->tb_work_dev) (void)hipFree(h->tb_work_dev);
     if (h->spec_ring_dev) (void)hipFree(h->spec_ring_dev);
     if (h->sb_dev) (void)hipFree(h->sb_dev);
@@ -1789,7 +1783,7 @@ int fe_set_time_pipeline(fe_handle* h, int frames_in_flight) {
 }
 
 static size_t tb_work_floats(const fe_handle* h, int B, int T, size_t* off);
-static int tb_run(fe_handle* h, fe::tb::TbArgs a0, float* work_dev, int B, int T, hipStream_t st);
+static int tb_run(fe_handle* h, fe::tb::TbArgs a, float* work_dev, int B, int T, hipStream_t st);
 static int pipe_width(const fe_handle* h, int B, int T, bool offline, bool spec_rings);
 
 // spec -> spec chunks on the time-batched engine: when asked for (FE_OFFLINE_TIME_BATCHED), or - AUTO - for long chunks of batches that
@@ -1913,10 +1907,11 @@ int fe_step_chunk(fe_handle* h, const float* wav_in_dev, size_t in_stride, float
     return launch_rc(hipGetLastError());
 }
 
-// floats of the time-batched engine's work buffer: xc | skip | x | gx | hs | frames | carried GRU state, each a multiple of 4 floats
+// floats of the time-batched engine's work buffer: xc | skip | x | gx | hs | frames | spare, each a multiple of 4 floats
 static size_t tb_work_floats(const fe_handle* h, int B, int T, size_t* off /*[7] or nullptr*/) {
     const Dims& d = h->d;
     const size_t NF = (size_t)B * T, nd = d.BD ? 2 : 1;
+    // (the seventh region held the GRU state carried between time chunks; nothing writes it any more - kept so that the sizes callers were given stay what they are)
     const size_t sz[7] = {NF * 2 * d.F0, NF * (d.NL + 1) * d.F1 * d.C1, NF * d.F2 * d.C2, nd * NF * d.F2 * 3 * d.C2, NF * d.F2 * nd * d.C2, NF * d.NFFT,
                           (size_t)d.KB * nd * B * d.F2 * d.C2};
     size_t cur = 0;
@@ -1927,126 +1922,42 @@ static size_t tb_work_floats(const fe_handle* h, int B, int T, size_t* off /*[7]
     return cur;
 }
 
-// The time-batched engine's schedule.  The call's B x T frames are cut into NODES - G groups of utterances x NC chunks of
-// consecutive frames - and every node runs the chain  enc -> (scan k -> blk k) x KB -> dec  on its own slice of the work buffers.
-// Only the scans are serial in time: scan k of chunk c starts from the state scan k of chunk c - 1 left (an event), everything
-// else of a node depends on the node alone.  The nodes are spread round-robin over a few HIP streams of the handle, so that
-// the latency-bound scans of one node (16 rows per workgroup, one recurrence step after the other) run UNDER the GEMM passes
-// of the others instead of leaving the chip idle between them, and - a single utterance - the scans of consecutive blocks
-// pipeline through the chunks.  The noncausal model's reverse scan needs all frames of an utterance: utterance groups only.
-struct TbPlan { int G, NC, NS, stagger, fuse; };
-
-static TbPlan tb_plan(const fe_handle* h, int B, int T) {
-    auto env = [](const char* n, int dflt) { const char* v = std::getenv(n); return v ? std::atoi(v) : dflt; };
-    TbPlan p;
-    // Measured (profiles/r3d_tb_node_plans.txt): on this runtime the streams of one process share 3-4 hardware queues and kernels that
-    // overlap slow each other down by what the overlap hides - every multi-node plan came out slower than ONE node.  The default is
-    // therefore one node; FE_TB_NC / FE_TB_G / FE_TB_STREAMS keep the cut available (results are bit-identical by construction).
-    p.NC = std::max(1, std::min(T, env("FE_TB_NC", 1)));
-    if (h->d.BD) p.NC = 1;
-    p.G = std::max(1, std::min(B, env("FE_TB_G", 1)));
-    p.NS = std::max(1, std::min(8, env("FE_TB_STREAMS", 4)));
-    p.NS = std::min(p.NS, p.G * p.NC);
-    p.stagger = env("FE_TB_STAGGER", 1);
-    // FE_TB_FUSE=1: scan + block tiles of a block in ONE cooperative launch (tb_stage_kernel: the tiles follow the scan frame by frame
-    // behind its progress counters) where tb_launch accepts it.  Parity-green, but measured slower than the two launches it replaces
-    // (profiles/r3g_tb_fused_stage.txt): off by default.
-    p.fuse = env("FE_TB_FUSE", 0);
-    if (p.G * p.NC > 1) p.fuse = 0;
-    if (std::getenv("FE_TB_STAGES")) { p.G = p.NC = p.NS = 1; p.fuse = 0; }
-    return p;
-}
-
-static int tb_run(fe_handle* h, fe::tb::TbArgs a0, float* work_dev, int B, int T, hipStream_t st) {
+// The time-batched engine's schedule: one chain on the caller's stream, enc -> (scan k -> blk k) x KB -> dec, over all B x T frames of the
+// call.  Only the scans are serial in time.  (Cutting the call into nodes over several streams, and a fused scan + tile stage, were
+// measured and lost: profiles/r3d_tb_node_plans.txt, profiles/r3g_tb_fused_stage.txt.)
+static int tb_run(fe_handle* h, fe::tb::TbArgs a, float* work_dev, int B, int T, hipStream_t st) {
     const Dims& d = h->d;
     const fe::tb::TbImpl* tbi = h->impl->tb;
-    const TbPlan p = tb_plan(h, B, T);
-    const int nodes = p.G * p.NC;
     size_t off[7];
     tb_work_floats(h, B, T, off);
-    const size_t nd = d.BD ? 2 : 1;
-    a0.Bfull = B; a0.Tfull = T;
 #ifdef FE_TB_PROBE
     if (!h->tb_probe_dev) {
         FE_HIP_CHECK(hipMalloc(&h->tb_probe_dev, 4 * fe::tb::kProbeSlots * sizeof(unsigned long long)));
         FE_HIP_CHECK(hipMemset(h->tb_probe_dev, 0, 4 * fe::tb::kProbeSlots * sizeof(unsigned long long)));
     }
-    a0.probe = h->tb_probe_dev;
+    a.probe = h->tb_probe_dev;
 #endif
-    const bool caller_state = a0.hstate != nullptr;     // caches handed in: read by the first chunk (h_init), left updated by the last
-    if (!caller_state && p.NC > 1) a0.hstate = work_dev + off[6];
-    a0.frames = work_dev + off[5];
-    hipError_t e = hipSuccess;
-    if (p.fuse) {
-        const size_t nprog = (size_t)d.KB * h->max_wgs * fe::tb::kProgStride;        // (a 128-byte line per scan workgroup)
-        if (!h->tb_prog_dev) FE_HIP_CHECK(hipMalloc(&h->tb_prog_dev, nprog * sizeof(unsigned int)));
-        FE_HIP_CHECK(hipMemsetAsync(h->tb_prog_dev, 0, nprog * sizeof(unsigned int), st));
-    }
+    a.B = B; a.T = T; a.NF = B * T;
+    a.b0 = a.t0 = 0; a.Bfull = B; a.Tfull = T;
+    a.h_init = (a.hstate != nullptr && a.h_init) ? 1 : 0;     // caches handed in (fe_spec_step): read by the scans, left updated
+    a.xc = work_dev + off[0];
+    a.skip = work_dev + off[1];
+    a.x = work_dev + off[2];
+    a.gx = work_dev + off[3];
+    a.hs = work_dev + off[4];
+    a.frames = work_dev + off[5];
+    if (a.NF == 0) return FE_OK;
     // (FE_TB_STAGES=n: stop after n launches - tools/gpu_tb_check.py reads the intermediate buffers out of work_dev)
     const char* lim_s = std::getenv("FE_TB_STAGES");
     int lim = lim_s ? std::atoi(lim_s) : 1 << 30;
-    const bool multi = p.NS > 1;
-    if (multi) {
-        while ((int)h->tb_streams.size() < p.NS) {
-            hipStream_t s;
-            FE_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-            h->tb_streams.push_back(s);
-        }
-        const size_t nev = 1 + (size_t)p.NS + (size_t)nodes * (d.KB + 1);
-        while (h->tb_events.size() < nev) {
-            hipEvent_t ev;
-            FE_HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-            h->tb_events.push_back(ev);
-        }
-        FE_HIP_CHECK(hipEventRecord(h->tb_events[0], st));
-        for (int s = 0; s < p.NS; ++s) FE_HIP_CHECK(hipStreamWaitEvent(h->tb_streams[s], h->tb_events[0], 0));
+    hipError_t e = hipSuccess;
+    if (lim-- > 0) tbi->launch(fe::tb::TB_ENC, a, h->max_wgs, st, &e);
+    for (int k = 0; k < d.KB && e == hipSuccess; ++k) {
+        a.k = k;
+        if (lim-- > 0) tbi->launch(fe::tb::TB_SCAN, a, h->max_wgs, st, &e);
+        if (e == hipSuccess && lim-- > 0) tbi->launch(fe::tb::TB_BLK, a, h->max_wgs, st, &e);
     }
-    auto scan_event = [&](int node, int k) { return h->tb_events[1 + p.NS + (size_t)node * (d.KB + 1) + k]; };
-    auto enc_event = [&](int node) { return h->tb_events[1 + p.NS + (size_t)node * (d.KB + 1) + d.KB]; };
-    size_t fbase = 0;                            // frames of the nodes before this one: its offset into the work buffers
-    for (int g = 0; g < p.G && e == hipSuccess; ++g) {
-        const int b0 = (int)((long)B * g / p.G), b1 = (int)((long)B * (g + 1) / p.G);
-        for (int c = 0; c < p.NC && e == hipSuccess; ++c) {
-            const int t0 = (int)((long)T * c / p.NC), t1 = (int)((long)T * (c + 1) / p.NC);
-            const int node = g * p.NC + c, sidx = node % p.NS;
-            hipStream_t ns = multi ? h->tb_streams[sidx] : st;
-            fe::tb::TbArgs a = a0;
-            a.B = b1 - b0; a.T = t1 - t0; a.NF = a.B * a.T; a.b0 = b0; a.t0 = t0;
-            a.h_init = (c > 0 || (caller_state && a0.h_init)) ? 1 : 0;
-            a.xc = work_dev + off[0] + fbase * 2 * d.F0;
-            a.skip = work_dev + off[1] + fbase * (size_t)(d.NL + 1) * d.F1 * d.C1;
-            a.x = work_dev + off[2] + fbase * (size_t)d.F2 * d.C2;
-            a.gx = work_dev + off[3] + nd * fbase * (size_t)d.F2 * 3 * d.C2;
-            a.hs = work_dev + off[4] + fbase * (size_t)d.F2 * nd * d.C2;
-            fbase += (size_t)a.NF;
-            if (a.NF == 0) continue;
-            // stagger: a node's encoder pass starts when the previous node's has finished - nodes that start together run in lockstep
-            // (GEMM passes together, then all of them in their scans with the chip idle)
-            if (multi && p.stagger && node > 0 && (node - 1) % p.NS != sidx) FE_HIP_CHECK(hipStreamWaitEvent(ns, enc_event(node - 1), 0));
-            if (lim-- > 0) tbi->launch(fe::tb::TB_ENC, a, h->max_wgs, ns, &e);
-            if (multi && p.stagger && node + 1 < nodes) FE_HIP_CHECK(hipEventRecord(enc_event(node), ns));
-            for (int k = 0; k < d.KB && e == hipSuccess; ++k) {
-                a.k = k;
-                if (p.fuse) {
-                    a.prog = h->tb_prog_dev + (size_t)k * h->max_wgs * fe::tb::kProgStride;
-                    hipError_t ef = hipSuccess;
-                    tbi->launch(fe::tb::TB_STAGE, a, h->max_wgs, ns, &ef);
-                    if (ef == hipSuccess) continue;             // (refused: not a fusable shape / batch, or no co-residency - two launches)
-                }
-                if (multi && c > 0 && (node - 1) % p.NS != sidx) FE_HIP_CHECK(hipStreamWaitEvent(ns, scan_event(node - 1, k), 0));
-                if (lim-- > 0) tbi->launch(fe::tb::TB_SCAN, a, h->max_wgs, ns, &e);
-                if (multi && c + 1 < p.NC) FE_HIP_CHECK(hipEventRecord(scan_event(node, k), ns));
-                if (e == hipSuccess && lim-- > 0) tbi->launch(fe::tb::TB_BLK, a, h->max_wgs, ns, &e);
-            }
-            if (e == hipSuccess && lim-- > 0) tbi->launch(fe::tb::TB_DEC, a, h->max_wgs, ns, &e);
-        }
-    }
-    if (multi) {
-        for (int s = 0; s < p.NS; ++s) {
-            FE_HIP_CHECK(hipEventRecord(h->tb_events[1 + s], h->tb_streams[s]));
-            FE_HIP_CHECK(hipStreamWaitEvent(st, h->tb_events[1 + s], 0));
-        }
-    }
+    if (e == hipSuccess && lim-- > 0) tbi->launch(fe::tb::TB_DEC, a, h->max_wgs, st, &e);
     return launch_rc(e);
 }
 

@@ -47,23 +47,21 @@ struct TbArgs {
     float* gx;                  // [ND][NF][3 C2][F2]  W_ih x + b_ih (+ b_hh for r, z)
     float* hs;                  // [NF][ND*C2][F2]  GRU outputs
     float* hstate;              // [KB][B*F2][C2] carried GRU state (spec -> spec with caches), or nullptr: zero initial state
-    int B, T, NF;               // the NODE's utterances, frames per utterance and B * T: the work buffers are indexed by the node-local frame b * T + t
-    int b0, t0;                 // the node's first utterance / first frame within the whole call (input / output addressing, carried state)
-    int Bfull, Tfull;           // utterances and frames per utterance of the whole call
-    int h_init;                 // tb_scan_kernel: 1 = start from hstate (a later time chunk, or caches handed in), 0 = zero initial state
+    int B, T, NF;               // the launch's utterances, frames per utterance and B * T: the work buffers are indexed by the frame b * T + t
+    int b0, t0;                 // the launch's first utterance / first frame within the whole call (input / output addressing, carried state): tb_run passes 0, 0
+    int Bfull, Tfull;           // utterances and frames per utterance of the whole call: tb_run passes B, T
+    int h_init;                 // tb_scan_kernel: 1 = start from hstate (caches handed in), 0 = zero initial state
     int Tw;                     // offline: samples per utterance
     const int* Tw_b;            // offline, ragged batch (fe_offline_ragged): samples of utterance b, [Bfull], every one <= Tw (the batch is laid out for
                                 // Tw: frames past an utterance's own 1 + Tw_b / H are computed on clamped input and never reach its output); nullptr: all Tw
     int mode;                   // FE_MODE_OFFLINE / FE_MODE_SPEC
     int k;                      // block index (tb_scan_kernel, tb_blk_kernel)
     float compression;
-    unsigned int* prog;         // fused stage (tb_stage_kernel): frames finished by each 16-row scan workgroup of this block [n scan workgroups]
-    int nscan;                  // fused stage: workgroups 0 .. nscan - 1 of the launch run the scan, the others the block's tiles
     unsigned long long* probe;  // FE_TB_PROBE builds (tools/gpu_tb_phases.py): cycles per phase of workgroup 0, [stage][kProbeSlots]; else nullptr
 };
 
 constexpr int kProbeSlots = 32;
-enum { TB_ENC = 0, TB_SCAN = 1, TB_BLK = 2, TB_DEC = 3, TB_STAGE = 4 };     // (TB_STAGE: scan + block tiles of one block in one launch)
+enum { TB_ENC = 0, TB_SCAN = 1, TB_BLK = 2, TB_DEC = 3 };
 #ifdef FE_TB_PROBE
 // phase clocks: workgroup 0's thread 0 adds the cycles since the previous mark to slot i (s_memtime, after the phase's barrier)
 #define TB_PROBE_INIT(stage) unsigned long long* const tb_pr_ = (a.probe != nullptr && blockIdx.x == 0 && threadIdx.x == 0) ? a.probe + (stage) * kProbeSlots : nullptr; \
@@ -572,14 +570,7 @@ __global__ void __launch_bounds__(kThreads) tb_enc_kernel(TbArgs a) {
 // gx, was batched over all frames): A = h_{t-1} from LDS (double-buffered: one barrier per step), r / z / n of a (row, channel)
 // land in the same lane, the gate math runs in the epilogue, h_t goes to LDS (next step's A operand), to the registers (next
 // step's z h term) and to hs in global memory.  gx of step t + 1 is fetched while step t computes.
-// PUB > 0 (the fused stage): every PUB steps - and after the last one - the workgroup publishes how many frames of its 16 rows are in hs.
-// hs is written with agent-scope stores (they go to the coherence point, not into this XCD's L2); every wave drains its stores
-// (vmcnt(0)), the step's barrier, then one agent-scope store of the counter.  The consumer polls the counter and reads hs with
-// agent-scope loads as well.  No release / acquire FENCE on either side: measured, one L2 write-back per publish and one cache
-// invalidate per tile made the fused stage 3x slower than the two launches it replaces (profiles/r3g_tb_fused_stage.txt).
-constexpr int kScanPub = 32;
-constexpr int kProgStride = 32;      // ints between two scan workgroups' counters: a 128-byte line each (pollers and publisher meet on one line only)
-template <class S, int PUB>
+template <class S>
 __device__ __forceinline__ void scan_role(const TbArgs& a, int rg, int dir, float (*hbuf)[16 * S::LDX]) {
     constexpr int C2 = S::C2, F2 = S::F2, KS = S::KS_2, NT2 = S::NT2, LDX = S::LDX, N3 = S::N3;
     constexpr int NTPW = ceil_div(NT2, kWaves);
@@ -711,25 +702,11 @@ __device__ __forceinline__ void scan_role(const TbArgs& a, int rg, int dir, floa
                 hprev[j][r] = hv;
                 hn[(4 * lg + r) * LDX + hcol[j]] = hv;
             }
-            if (cokj[j] && rok[0]) {
-                float* hd = hsp[j];
-                if constexpr (PUB > 0) {            // (read by other workgroups of the SAME launch: agent-scope accesses on both sides, no cache in between)
-                    // one 16-byte store with the system-coherent bits (what a relaxed agent-scope atomic store of each float would set)
-                    const f32x4 hv4 = {hprev[j][0], hprev[j][1], hprev[j][2], hprev[j][3]};
-                    asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" : : "v"(hd), "v"(hv4) : "memory");
-                } else
-                *reinterpret_cast<float4*>(hd) = make_float4(hprev[j][0], hprev[j][1], hprev[j][2], hprev[j][3]);
-            }
+            if (cokj[j] && rok[0]) *reinterpret_cast<float4*>(hsp[j]) = make_float4(hprev[j][0], hprev[j][1], hprev[j][2], hprev[j][3]);
             hsp[j] += hstep;
         }
         if (st + GD < a.T) load_gx(d);          // the x half GD steps ahead, into the slot this step has just used up
         cur ^= 1;
-        if constexpr (PUB > 0) {
-            const bool pub = ((st + 1) % PUB == 0) || st + 1 == a.T;
-            if (pub) __builtin_amdgcn_s_waitcnt(0x0f70);         // vmcnt(0): this wave's hs stores have left the CU
-            __syncthreads();
-            if (pub && tid == 0) __hip_atomic_store(a.prog + rg * kProgStride, (unsigned int)(st + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else
         __syncthreads();
     }
     }
@@ -748,7 +725,7 @@ __device__ __forceinline__ void scan_role(const TbArgs& a, int rg, int dir, floa
 template <class S>
 __global__ void __launch_bounds__(kThreads) tb_scan_kernel(TbArgs a) {
     __shared__ float hbuf[2][16 * S::LDX];
-    scan_role<S, 0>(a, blockIdx.x, blockIdx.y, hbuf);
+    scan_role<S>(a, blockIdx.x, blockIdx.y, hbuf);
 }
 
 // The same recurrence for FEW rows (a handful of utterances: 16 rows per workgroup leave most of the chip idle and each step is a
@@ -814,7 +791,7 @@ __global__ void __launch_bounds__(kThreads) tb_scan4_kernel(TbArgs a) {
         hprev[s] = v;
         if (ok[s]) hbuf[0][q * LDR + (ch[s] / KQ) * KP + ch[s] % KQ] = v;
     }
-    // (the step costs its instruction count - see scan_role: running pointers, scaled pre-activations, the slot refilled after its use)
+    // (the step costs its instruction count - see tb_scan_kernel: running pointers, scaled pre-activations, the slot refilled after its use)
     const int t_first = dir ? a.T - 1 : 0, dt = dir ? -1 : 1;
     float gxv[NSET][3];
     const float* gxp[NSET];
@@ -913,16 +890,12 @@ struct BlkLds {
     static constexpr bool PERHEAD = (size_t)FULL * 4 > 160 * 1024;
     static constexpr int LDGX = PERHEAD ? 3 * S::HD + 2 : S::LDG;
     static constexpr int TOTAL = U + cmax(TT::ROWS_P * LDH, TT::ROWS_P * (S::LDX + LDGX));
-    static constexpr size_t BYTES = (size_t)TOTAL * 4 + 16;      // (+ one word: the fused stage's "next tile is ready" flag)
+    static constexpr size_t BYTES = (size_t)TOTAL * 4;
     static constexpr bool OK = BYTES <= 160 * 1024;
     static constexpr int OCC = 2 * BYTES <= 160 * 1024 ? 2 : 1;   // workgroups per CU the plan allows: the register budget follows it
 };
 
-// FUSED (tb_stage_kernel): the tiles are walked TIME-major (tile n = frames tt FT .. of utterance n % B, tt = n / B) and a tile
-// waits until the scan workgroups of its utterance's rows have published its frames (a.prog; one lane polls with agent-scope loads,
-// the barrier hands the result to the workgroup; the tile's hs then comes in with agent-scope loads, x - written by the previous
-// launch - with plain ones).
-template <class S, int FT, bool FUSED>
+template <class S, int FT>
 __device__ __forceinline__ void blk_body(const TbArgs& a, float* smem, const int wgid, const int nwg) {
     using L = BlkLds<S, FT>;
     using TT = TokTiling<S, FT>;
@@ -937,40 +910,12 @@ __device__ __forceinline__ void blk_body(const TbArgs& a, float* smem, const int
     float* const Hs = smem + L::HS;
     float* const Hl = smem + L::HL;
     float* const Gi = smem + L::GI;
-    const int TPU = (a.T + FT - 1) / FT;                      // FUSED: tiles per utterance
-    const int ntiles = FUSED ? a.B * TPU : (a.NF + FT - 1) / FT;
-    // tile -> its first frame (node-local index b * T + t) and the number of valid frames
+    const int ntiles = (a.NF + FT - 1) / FT;                  // tile tl: frames tl FT .. (index b * T + t), the last one partial
+    // tile -> its first frame (index b * T + t) and the number of valid frames
     auto tile_frames = [&](int tl, int& nv) -> int {
-        if constexpr (FUSED) {
-            const int tt = tl / a.B, b = tl - tt * a.B, t0 = tt * FT;
-            nv = a.T - t0 < FT ? a.T - t0 : FT;
-            return b * a.T + t0;
-        } else {
-            const int g0 = tl * FT;
-            nv = a.NF - g0 < FT ? a.NF - g0 : FT;
-            return g0;
-        }
-    };
-    // FUSED: has the scan published the tile's frames for every row of its utterance?  (thread 0; wait = poll until it has)
-    auto tile_ready = [&](int tl, bool wait) -> bool {
-        const int tt = tl / a.B, b = tl - tt * a.B;
-        const unsigned int need = (unsigned int)((tt + 1) * FT < a.T ? (tt + 1) * FT : a.T);
-        const int rg0 = (b * S::F2) / 16, rg1 = (b * S::F2 + S::F2 - 1) / 16;
-        bool ok = true;
-        for (int rg = rg0; rg <= rg1; ++rg) {
-            int spins = 0;
-            while (__hip_atomic_load(a.prog + rg * kProgStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need) {
-                if (!wait || ++spins > (1 << 20)) { ok = false; break; }
-                __builtin_amdgcn_s_sleep(16);
-            }
-        }
-        return ok;
-    };
-    auto wait_tile = [&](int tl) {
-        if constexpr (FUSED) {
-            if (threadIdx.x == 0) (void)tile_ready(tl, true);
-            __syncthreads();
-        }
+        const int g0 = tl * FT;
+        nv = a.NF - g0 < FT ? a.NF - g0 : FT;
+        return g0;
     };
     TB_PROBE_INIT(TB_BLK);
     // Small blocks (T, B, S): this wave's column tiles of EVERY weight matrix of the block stay in registers for the whole launch,
@@ -1044,14 +989,7 @@ __device__ __forceinline__ void blk_body(const TbArgs& a, float* smem, const int
                 int i = tid + q * kThreads;
                 i = i < HQ ? i : HQ - 1;
                 const int fr = i / (HW * F4), fs = fr < nv ? fr : nv - 1;
-                const float* hp = hg + (size_t)(i - fr * (HW * F4) + fs * (HW * F4)) * 4;
-                if constexpr (FUSED) {       // (written by the scan workgroups of this launch: agent-scope loads)
-                    ph[q].x = __hip_atomic_load(hp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    ph[q].y = __hip_atomic_load(hp + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    ph[q].z = __hip_atomic_load(hp + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    ph[q].w = __hip_atomic_load(hp + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                } else
-                ph[q] = *reinterpret_cast<const float4*>(hp);
+                ph[q] = *reinterpret_cast<const float4*>(hg + (size_t)(i - fr * (HW * F4) + fs * (HW * F4)) * 4);
             }
         };
         auto park_tile = [&]() {
@@ -1072,7 +1010,7 @@ __device__ __forceinline__ void blk_body(const TbArgs& a, float* smem, const int
                 d[0] = ph[q].x; d[LDH] = ph[q].y; d[2 * LDH] = ph[q].z; d[3 * LDH] = ph[q].w;
             }
         };
-        if (wgid < ntiles) { wait_tile(wgid); fetch_tile(wgid); park_tile(); }
+        if (wgid < ntiles) { fetch_tile(wgid); park_tile(); }
         __syncthreads();
         TB_MARK(0);
 #pragma unroll 1
@@ -1081,12 +1019,7 @@ __device__ __forceinline__ void blk_body(const TbArgs& a, float* smem, const int
             const int g0 = tile_frames(tile, nvalid);
             const int rows_valid = nvalid * F2;
             const int nxt = tile + nwg;
-            // the next tile rides under this one's phases - FUSED: if the scan is already past it (asked once, by thread 0; the answer
-            // crosses the first phase's barrier in LDS), else it is fetched after this tile
-            bool pre = !FUSED;
-            if constexpr (FUSED) {
-                if (nxt < ntiles && threadIdx.x == 0) smem[L::TOTAL] = tile_ready(nxt, false) ? 1.0f : 0.0f;
-            } else if (nxt < ntiles) fetch_tile(nxt);
+            if (nxt < ntiles) fetch_tile(nxt);                   // the next tile rides under this one's phases
             // ---- x += rnn_fc(h) (+ pe in block 0)   (model.py:273-280; noncausal: K = 2 C2)
             {
                 f32x4 acc[MTT][NTPW2];
@@ -1113,9 +1046,6 @@ __device__ __forceinline__ void blk_body(const TbArgs& a, float* smem, const int
             }
             __syncthreads();
             TB_MARK(1);
-            if constexpr (FUSED) {
-                if (nxt < ntiles) { pre = smem[L::TOTAL] != 0.0f; if (pre) fetch_tile(nxt); }
-            }
             // ---- qkv = x W_qkv^T  (rows per head interleaved [h][q|k|v][hd], model.py:142-146)
             {
                 f32x4 acc[MTT][NTPW3];
@@ -1191,17 +1121,12 @@ __device__ __forceinline__ void blk_body(const TbArgs& a, float* smem, const int
             }
             __syncthreads();                                     // (every wave is done with Xb / Hl / Gi)
             TB_MARK(5);
-            if (nxt < ntiles) {
-                if (!pre) { wait_tile(nxt); fetch_tile(nxt); }
-                park_tile();
-            }
+            if (nxt < ntiles) park_tile();
             __syncthreads();
             TB_MARK(0);
         }
         return;
     }
-    static_assert(!FUSED || REGW, "the fused stage is built on the register-resident block path");
-    if constexpr (!FUSED) {
     const int wave_outer = wave;
 #pragma unroll 1
     for (int tile = wgid; tile < ntiles; tile += nwg) {
@@ -1362,34 +1287,12 @@ __device__ __forceinline__ void blk_body(const TbArgs& a, float* smem, const int
         __syncthreads();
         TB_MARK(5);                 // gx of the next block
     }
-    }
 }
 
 template <class S, int FT>
 __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(BlkLds<S, FT>::OCC, BlkLds<S, FT>::OCC))) tb_blk_kernel(TbArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    blk_body<S, FT, false>(a, smem, blockIdx.x, gridDim.x);
-}
-
-// One block stage in ONE launch: workgroups 0 .. nscan - 1 run the time scan of block k (16 rows each), the others the block's tiles
-// behind it.  The scan is a latency chain that leaves most of the chip idle and the tile pass cannot start before it - unless the
-// tiles follow the scan frame by frame: a stage then takes about as long as its scan alone.  All workgroups must be co-resident (the
-// tile workgroups spin on the scan's counters): a cooperative launch, sized by tb_launch.
-template <class S, int FT>
-constexpr bool stage_fusable() {
-    constexpr int NTPW2 = ceil_div(S::NT2, kWaves), NTPW3 = ceil_div(S::NT3, kWaves);
-    constexpr int WREGS = NTPW2 * S::ND * S::KS_2 + NTPW3 * S::KS_2 + NTPW2 * S::KS_2 + S::ND * NTPW3 * S::KS_2;
-    return !S::BIDIR && !BlkLds<S, FT>::PERHEAD && WREGS <= 100 && TokTiling<S, FT>::MTT * NTPW3 <= 8 && BlkLds<S, FT>::OCC == 2;
-}
-
-template <class S, int FT>
-__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) tb_stage_kernel(TbArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    if constexpr (stage_fusable<S, FT>()) {
-        __shared__ float hbuf[2][16 * S::LDX];
-        if ((int)blockIdx.x < a.nscan) scan_role<S, kScanPub>(a, blockIdx.x, 0, hbuf);
-        else blk_body<S, FT, true>(a, smem, (int)blockIdx.x - a.nscan, (int)gridDim.x - a.nscan);
-    }
+    blk_body<S, FT>(a, smem, blockIdx.x, gridDim.x);
 }
 
 // ------------------------------------------------------------------------------------------ decoder segment
@@ -1676,9 +1579,7 @@ void tb_launch(int stage, const TbArgs& a, int max_wgs, hipStream_t st, hipError
     } else if (stage == TB_SCAN) {
         // 16 rows per workgroup when that fills the chip (the MFMA throughput of the 16x16x4 tiles is what counts then), else 4
         static const int force = [] { const char* v = std::getenv("FE_TB_SCAN_ROWS"); return v ? std::atoi(v) : 0; }();
-        const int wg16 = ((a.B * S::F2 + 15) / 16) * S::ND;
         const int wg4 = (a.B * S::F2 / 4) * S::ND;
-        (void)wg16;
         const bool rows16 = force == 16 || (force != 4 && 4 * wg4 > 5 * max_wgs);      // (two 4-row workgroups on a CU take turns on its SIMDs: no gain beyond ~1 per CU)
         note_kernel(rows16 ? "tb_scan_kernel" : "tb_scan4_kernel");
         if (rows16)
@@ -1686,22 +1587,6 @@ void tb_launch(int stage, const TbArgs& a, int max_wgs, hipStream_t st, hipError
         else
             hipLaunchKernelGGL((tb_scan4_kernel<S>), dim3(a.B * S::F2 / 4, S::ND), dim3(kThreads), 0, st, a);
         *err = hipGetLastError();
-    } else if (stage == TB_STAGE) {
-        // the fused stage: only where the 16-row scan is the one in use, its workgroups leave room for tile workgroups on every CU, and the
-        // block runs on the register-resident path; anything else is refused (the caller launches scan and tiles one after the other)
-        if constexpr (!stage_fusable<S, C::FT_B>()) { *err = hipErrorNotSupported; return; } else {
-            const int nscan = (a.B * S::F2 + 15) / 16, wg4 = a.B * S::F2 / 4;
-            const int TPU = (a.T + C::FT_B - 1) / C::FT_B, ntiles = a.B * TPU;
-            const int room = 2 * max_wgs - nscan - 16;           // (a margin: the co-residency the runtime grants is sized by its own occupancy estimate)
-            if (!(4 * wg4 > 5 * max_wgs) || nscan > max_wgs || room < max_wgs / 2 || a.prog == nullptr) { *err = hipErrorNotSupported; return; }
-            TbArgs args = a;
-            args.nscan = nscan;
-            int grid = nscan + (ntiles < room ? ntiles : room);
-            static const int dbg = [] { const char* v = std::getenv("FE_TB_FUSE_DEBUG"); return v ? std::atoi(v) : 0; }();
-            if (dbg == 1) grid = nscan;          // (timing experiment: the scan role alone, with its agent-scope stores and publishes; results are garbage)
-            // (a refusal leaves no error behind and notes nothing: the caller launches scan and tiles separately)
-            *err = launch_coop<&tb_stage_kernel<S, C::FT_B>, true>("tb_stage_kernel", dim3(grid), dim3(kThreads), BlkLds<S, C::FT_B>::BYTES, st, args);
-        }
     } else if (stage == TB_BLK) {
         constexpr size_t lds = BlkLds<S, C::FT_B>::BYTES;
         *err = launch<&tb_blk_kernel<S, C::FT_B>>("tb_blk_kernel", dim3(grid_for(C::FT_B, lds)), dim3(kThreads), lds, st, a);

@@ -1038,42 +1038,82 @@ def test_spec_chunks_on_the_time_batched_engine_carry_the_caches(name):
         _assert_close(got.cpu().numpy(), want, "GRU cache after the chunks")
 
 
-def test_time_batched_optional_schedules_agree_with_the_default():
-    """The time-batched engine's opt-in schedules (measured slower, DESIGN 3c - but they must stay correct): the call cut into nodes
-    (time chunks / utterance groups over the handle's streams, FE_TB_NC / FE_TB_G / FE_TB_STREAMS) and the fused block stage (scan and
-    tile pass of a block in one cooperative launch behind progress counters, FE_TB_FUSE=1), on a batch large enough for the 16-row
-    scan (the fused stage's regime)."""
-    import os
+def _scan16_batch(eng):
+    """The smallest batch (a multiple of 4) for which the time-batched engine scans 16 rows per workgroup while half of it scans 4:
+    tb_launch's rule is 4 * (B * F2 / 4) > 5 * CUs (256 CUs, F2 = 24: 56 and 28)."""
+    cus = torch.cuda.get_device_properties(_dev()).multi_processor_count
+    F2 = eng.cfg.rf_freq
+
+    def rows16(b):
+        return 4 * (b * F2 // 4) > 5 * cus
+
+    B = next(b for b in range(4, 1 << 16, 4) if rows16(b))
+    assert not rows16(B // 2), (B, cus, F2)
+    return B
+
+
+def _scan_kernels(eng):
+    """which of the two scan kernels the last call launched: (16-row, 4-row)"""
+    k = eng.last_step_kernel()
+    return "tb_scan_kernel" in k, "tb_scan4_kernel" in k
+
+
+def test_time_batched_scan_kernels_agree_and_the_launch_is_deterministic():
+    """The time-batched engine's two scans - 16 (utterance, sub-band) rows per workgroup on 16x16x4 MFMAs, 4 rows on 4x4x1 - compute the same
+    recurrence: a batch large enough for the 16-row scan in one call against its two halves, each small enough for the 4-row scan, in a call
+    of their own (fe_last_step_kernel says which scan ran).  Different summation orders: 2e-5 of the largest value.  And the call repeated
+    gives the same bits."""
     m, orc, cfg, sr, seed = _model("fe_b", "Model")
     eng = m.engine
     eng.set_offline_engine("time_batched")
-    B, T1 = 56, 37
-    xd = torch.from_numpy(make_input(B, T1 * cfg.hop_size + 5, 909, sr)).to(_dev())
-    keys = ("FE_TB_NC", "FE_TB_G", "FE_TB_STREAMS", "FE_TB_FUSE")
-    saved = {k: os.environ.pop(k, None) for k in keys}
     try:
+        B = _scan16_batch(eng)
+        xd = torch.from_numpy(make_input(B, 37 * cfg.hop_size + 5, 909, sr)).to(_dev())
         w0, s0 = [t.clone() for t in m(xd)]
-        os.environ.update(FE_TB_NC="3", FE_TB_G="1", FE_TB_STREAMS="2")          # time chunks: the same kernels on the same rows
-        w1, s1 = [t.clone() for t in m(xd)]
-        assert torch.equal(w1, w0) and torch.equal(s1, s0), "time-chunked nodes changed the result"
-        os.environ.update(FE_TB_NC="2", FE_TB_G="2", FE_TB_STREAMS="3")          # utterance groups: a group of 28 scans four rows per workgroup
-        w2, s2 = [t.clone() for t in m(xd)]
-        assert float((w2 - w0).abs().max()) <= 2e-5 * max(1.0, float(w0.abs().max()))
-        assert float((s2 - s0).abs().max()) <= 2e-5 * max(1.0, float(s0.abs().max()))
-        for k in keys[:3]:
-            os.environ.pop(k, None)
-        os.environ["FE_TB_FUSE"] = "1"
-        w3, s3 = [t.clone() for t in m(xd)]
-        w3b, _ = m(xd)
-        assert torch.equal(w3, w3b), "fused stage is not deterministic"
-        assert float((w3 - w0).abs().max()) <= 2e-5 * max(1.0, float(w0.abs().max()))
-        assert float((s3 - s0).abs().max()) <= 2e-5 * max(1.0, float(s0.abs().max()))
+        assert _scan_kernels(eng) == (True, False), eng.last_step_kernel()
+        w0b, s0b = m(xd)
+        assert torch.equal(w0b, w0) and torch.equal(s0b, s0), "time-batched launch is not deterministic"
+        halves = []
+        for part in (xd[:B // 2], xd[B // 2:]):
+            halves.append([t.clone() for t in m(part.contiguous())])
+            assert _scan_kernels(eng) == (False, True), eng.last_step_kernel()
+        w1, s1 = (torch.cat([h[i] for h in halves]) for i in range(2))
+        assert float((w1 - w0).abs().max()) <= 2e-5 * max(1.0, float(w0.abs().max()))
+        assert float((s1 - s0).abs().max()) <= 2e-5 * max(1.0, float(s0.abs().max()))
     finally:
-        for k in keys:
-            os.environ.pop(k, None)
-            if saved[k] is not None:
-                os.environ[k] = saved[k]
-    eng.set_offline_engine("auto")
+        eng.set_offline_engine("auto")
+
+
+@pytest.mark.parametrize("scan_rows", [4, 16])
+def test_time_batched_spec_chunks_do_not_change_a_bit(scan_rows):
+    """Cutting time into chunks changes nothing: fe_spec_step on the time-batched engine, 37 frames in one chunk against chunks of
+    12 + 12 + 13 with the caches threaded through.  The chunks run the same kernels on the same rows - a frame is a row of the layer GEMMs,
+    whatever tile it falls into, and a scan row is walked by the same lanes - and the GRU state crosses the chunk boundary in fp32, as it
+    crosses a step inside the scan: outputs and final caches are equal bit for bit.  3 utterances: the 4-row scan; the batch of
+    _scan16_batch: the 16-row scan."""
+    mo, orc, cfg, sr, seed = _model("fe_b")
+    eng = mo.engine
+    eng.set_offline_engine("time_batched")
+    try:
+        B = 3 if scan_rows == 4 else _scan16_batch(eng)
+        T = 37
+        gen = torch.Generator().manual_seed(1337)
+        spec = torch.randn(B, cfg.n_fft // 2 + 1, T, 2, generator=gen).to(_dev())
+        want = (scan_rows == 16, scan_rows == 4)
+        y0, *c0 = mo(spec, *mo.initialize_cache(spec[:, :, :1]))
+        assert _scan_kernels(eng) == want, eng.last_step_kernel()
+        caches = mo.initialize_cache(spec[:, :, :1])
+        ys = []
+        for t0, t1 in ((0, 12), (12, 24), (24, 37)):
+            y, *caches = mo(spec[:, :, t0:t1].contiguous(), *caches)
+            assert _scan_kernels(eng) == want, eng.last_step_kernel()
+            ys.append(y.clone())
+        assert torch.equal(torch.cat(ys, dim=2), y0), "time chunks changed the output"
+        assert len(caches) == len(c0)
+        for i, (p_, q_) in enumerate(zip(caches, c0)):
+            assert torch.equal(p_, q_), f"time chunks changed cache {i}"
+    finally:
+        eng.set_offline_engine("auto")
 
 
 @pytest.mark.parametrize("name", NONCAUSAL)

@@ -1,10 +1,15 @@
 #!/usr/bin/env python3
 """tools/compare_device_code.sh, function by function: which gfx950 functions of two builds differ?  (no GPU needed)
-   python tools/compare_device_code_per_kernel.py <parent csrc/_obj> <changed csrc/_obj> [--allow REGEX] > profiles/<name>_device_code.txt
+   python tools/compare_device_code_per_kernel.py <parent csrc/_obj> <changed csrc/_obj> [--allow REGEX] [--removed REGEX] [--kernarg REGEX] > profiles/<name>_device_code.txt
 For every *.o of both directories the gfx950 code object is unbundled and split into its functions; of each function the disassembly
 (without addresses and encodings) and the kernel's note metadata (registers, spills, LDS, scratch, kernarg layout) are compared.
 --allow: a regular expression on the name (demangled where a demangler is installed, and mangled) of the functions that are meant to change; any other difference is an error (exit
-status 1).  A change that is confined to some instantiations of a kernel template reports every other function as identical."""
+status 1).  A change that is confined to some instantiations of a kernel template reports every other function as identical.
+--removed: the functions that are meant to disappear (in the parent only); without it a function of one build only is an error.
+--kernarg: the functions whose argument block is meant to change and nothing else: their disassembly and every note field but the kernarg
+layout (.kernarg_segment_size, the .args list) must be identical.  One thing in the code follows the layout: the hidden arguments (grid size,
+...) lie behind the explicit ones, so a kernel that reads one addresses it through an immediate that moves with the block's size.  Such a line
+may differ in that one immediate, by exactly the change of .kernarg_segment_size, in a scalar load or scalar add; the lines are counted."""
 import argparse
 import os
 import re
@@ -49,6 +54,47 @@ def functions(obj, tmp):
     return {k: ("\n".join(v), notes.get(k, "")) for k, v in code.items()}
 
 
+def without_kernarg(notes):
+    """the note block without .kernarg_segment_size and the .args list (the lines indented deeper than the .args key)"""
+    out, col = [], None
+    for line in notes.splitlines():
+        if col is not None and (not line.strip() or len(line) - len(line.lstrip()) > col):
+            continue
+        col = line.index(".args:") if line.strip() in (".args:", "- .args:") else None
+        if col is None and ".kernarg_segment_size:" not in line:
+            out.append(line)
+    return "\n".join(out)
+
+
+def kernarg_size(notes):
+    m = re.search(r"\.kernarg_segment_size:\s+(\d+)", notes)
+    return int(m.group(1)) if m else None
+
+
+def kernarg_offset_lines(a, b):
+    """number of lines in which the disassemblies a (parent) and b differ, if each of them is one scalar load / add whose only difference is
+    an immediate moved by the change of the kernarg size; None if the functions differ in any other way"""
+    ca, cb = a[0].splitlines(), b[0].splitlines()
+    sa, sb = kernarg_size(a[1]), kernarg_size(b[1])
+    if len(ca) != len(cb) or sa is None or sb is None:
+        return None
+    n = 0
+    for la, lb in zip(ca, cb):
+        if la == lb:
+            continue
+        ta, tb = la.replace(",", " ").split(), lb.replace(",", " ").split()
+        d = [i for i in range(len(ta)) if i >= len(tb) or ta[i] != tb[i]]
+        if len(ta) != len(tb) or len(d) != 1 or d[0] == 0 or not re.match(r"s_(load_dword|add_u32|add_i32)", ta[0]):
+            return None
+        try:
+            if int(ta[d[0]], 0) - int(tb[d[0]], 0) != sa - sb:
+                return None
+        except ValueError:
+            return None
+        n += 1
+    return n
+
+
 def figures(notes):
     g = lambda key: (re.search(r"\.%s:\s+(\d+)" % key, notes) or [None, "-"])[1]
     return (f"vgpr {g('vgpr_count')} agpr {g('agpr_count')} sgpr {g('sgpr_count')} sgpr-spill {g('sgpr_spill_count')} vgpr-spill {g('vgpr_spill_count')} "
@@ -60,10 +106,13 @@ def main():
     ap.add_argument("parent")
     ap.add_argument("changed")
     ap.add_argument("--allow", default=None)
+    ap.add_argument("--removed", default=None)
+    ap.add_argument("--kernarg", default=None)
     args = ap.parse_args()
-    allow = re.compile(args.allow) if args.allow else None
+    allow, removed, kernarg = (re.compile(r) if r else None for r in (args.allow, args.removed, args.kernarg))
+    hit = lambda rx, dem, k: rx is not None and (rx.search(dem) or rx.search(k)) is not None
     names = sorted(set(f for d in (args.parent, args.changed) for f in os.listdir(d) if f.endswith(".o")))
-    bad = total = same = allowed = 0
+    bad = total = same = allowed = gone = args_only = 0
     print(f"{'object':<30} {'functions':>9} {'identical':>9} {'changed':>8}")
     with tempfile.TemporaryDirectory() as tmp:
         for n in names:
@@ -81,7 +130,17 @@ def main():
             print(f"{n:<30} {len(fb):>9} {len(fb) - len([k for k in diff if k in fb]):>9} {len(diff):>8}")
             for k in diff:
                 dem = run(FILT, k).strip() if FILT else k
-                ok = allow is not None and (allow.search(dem) or allow.search(k)) is not None and k in fa and k in fb
+                if k in fa and k not in fb and hit(removed, dem, k):
+                    gone += 1
+                    print(f"    removed (meant to): {dem}")
+                    continue
+                moved = kernarg_offset_lines(fa[k], fb[k]) if k in fa and k in fb and hit(kernarg, dem, k) else None
+                if moved is not None and without_kernarg(fa[k][1]) == without_kernarg(fb[k][1]):
+                    args_only += 1
+                    code = "code identical" if moved == 0 else f"code identical but for {moved} immediate(s) that address hidden arguments"
+                    print(f"    kernarg layout only (meant to): {dem}: {code}, the other notes identical, kernarg bytes {kernarg_size(fa[k][1])} -> {kernarg_size(fb[k][1])}")
+                    continue
+                ok = hit(allow, dem, k) and k in fa and k in fb
                 allowed += ok
                 bad += not ok
                 print(f"    {'changed (meant to)' if ok else 'CHANGED'}: {dem}")
@@ -89,7 +148,8 @@ def main():
                     if k in f:
                         print(f"        {side}: {figures(f[k][1])}, {f[k][0].count(chr(10)) + 1} lines")
     print()
-    print(f"{total} functions: {same} identical in code and notes, {allowed} changed as meant to, {bad} other differences")
+    print(f"{total} functions: {same} identical in code and notes, {args_only} with another kernarg layout only, {allowed} changed as meant to, "
+          f"{gone} removed as meant to, {bad} other differences")
     sys.exit(1 if bad else 0)
 
 

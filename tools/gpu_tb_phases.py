@@ -25,7 +25,6 @@ NAMES = {
 
 def main():
     name, secs, B = sys.argv[1], float(sys.argv[2]), int(sys.argv[3])
-    os.environ["FE_TB_NC"] = os.environ["FE_TB_G"] = os.environ["FE_TB_STREAMS"] = "1"
     kw, sr, _ = MODEL_KWARGS[name]
     dev = torch.device("cuda:0")
     cfg = product_config(name)

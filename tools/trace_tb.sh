@@ -1,6 +1,6 @@
 #!/bin/bash
 # kernel timeline of fe_offline on the time-batched engine (rocprofv3 --kernel-trace): which launches overlap
-#   tools/trace_tb.sh <tag> <shape> <seconds> <utterances>   (plan through FE_TB_NC / FE_TB_G / FE_TB_STREAMS)  -> gpurun_out/<tag>_trace.csv
+#   tools/trace_tb.sh <tag> <shape> <seconds> <utterances>  -> <tag>_timeline.txt in the output directory
 set -u
 TAG=$1; SHAPE=${2:-fe_b}; SECS=${3:-4}; UTT=${4:-64}
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
