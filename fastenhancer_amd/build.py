@@ -19,13 +19,6 @@ CSRC = os.path.join(HERE, "csrc")
 _TAG = os.environ.get("FE_BUILD_TAG", "")
 OBJ = os.path.join(CSRC, "_obj" + ("_" + _TAG if _TAG else ""))
 LIB = os.path.join(HERE, "libfastenhancer_hip.so") if not _TAG else os.path.join(os.path.dirname(HERE), "ab", f"lib_{_TAG}.so")
-FE_DEPS = ["fe_kernels.hip.h", "fe_launch.h", "fe_frame8.hip.h", "fe_impl.h", "tb_kernels.hip.h"]
-BSRNN_DEPS = ["fe_kernels.hip.h", "fe_launch.h", "bsrnn_kernels.hip.h", "bsrnn_sb_kernels.hip.h", "bsrnn_ov_kernels.hip.h"]
-FSPEN_DEPS = ["fe_kernels.hip.h", "fe_launch.h", "fspen_kernels.hip.h", "fspen_sb_kernels.hip.h"]
-LISENNET_DEPS = ["fe_kernels.hip.h", "fe_launch.h", "fspen_kernels.hip.h", "fspen_sb_kernels.hip.h", "lisennet_kernels.hip.h", "lisennet_sb_kernels.hip.h"]
-API_DEPS = ["fe_kernels.hip.h", "fe_launch.h", "fe_frame8.hip.h", "fe_impl.h", "tb_kernels.hip.h", "fe_shapes.def", "bsrnn_kernels.hip.h", "bsrnn_sb_kernels.hip.h", "bsrnn_ov_kernels.hip.h", "fe_bsrnn_shapes.def", "stft_kernels.hip.h", "fspen_kernels.hip.h", "fspen_sb_kernels.hip.h", "lisennet_kernels.hip.h", "lisennet_sb_kernels.hip.h",
-            "fe_api_bsrnn.inc", "fe_api_fspen.inc", "fe_api_lisennet.inc", "fe_fragments.h",
-            os.path.join("..", "..", "include", "fastenhancer_hip.h")]
 # -amdgpu-mfma-vgpr-form: MFMA accumulators in VGPRs instead of AGPRs - every epilogue read of an AGPR accumulator is a
 # v_accvgpr_read, a VALU instruction that the fp32 matrix path cannot overlap (~600 of them per wave and frame on
 # FastEnhancer_B: +1.8 %, 48 kHz B +2.6 %, T +2.3 %, the big shapes +1 %).
@@ -145,6 +138,31 @@ def _digest(paths, extra="") -> str:
     return h.hexdigest()[:16]
 
 
+_INCLUDE = re.compile(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', re.M)
+
+
+def deps(src):
+    """The files a translation unit is rebuilt for: `src` and, transitively, every file its quoted `#include "..."` lines name (a path is
+    relative to the including file; the lines of both branches of an #ifdef count), sorted.  An include that arrives as a macro
+    (FE_SHAPES_DEF, FE_LOCAL_DEF) is not seen here: build() names those files itself."""
+    seen, todo = set(), [os.path.abspath(src)]
+    while todo:
+        f = todo.pop()
+        if f in seen:
+            continue
+        seen.add(f)
+        for inc in _INCLUDE.findall(open(f).read()):
+            p = os.path.normpath(os.path.join(os.path.dirname(f), inc))
+            if os.path.exists(p):       # (a name found on the compiler's search path instead is not a source of this tree)
+                todo.append(p)
+    return sorted(seen)
+
+
+def pool_size(njobs: int) -> int:
+    """Compiler processes at a time: MAX_JOBS where it is set (a job's share of a machine), else one per CPU"""
+    return max(1, min(njobs, int(os.environ.get("MAX_JOBS", os.cpu_count() or 2))))
+
+
 def source_key() -> str:
     """Digest of every source the library is built from (csrc/*, the C-ABI header): libfastenhancer_hip.so carries it as fe_build_key(), and
     fastenhancer_amd._lib.load() refuses an in-tree library whose key is not the tree's - a stale build cannot pass for the shipped sources."""
@@ -173,36 +191,36 @@ def _compile(job):
 def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(OBJ, exist_ok=True)
     os.makedirs(os.path.dirname(LIB), exist_ok=True)
-    common = [os.path.join(CSRC, d) for d in FE_DEPS]
-    common_b = [os.path.join(CSRC, d) for d in BSRNN_DEPS]
-    common_api = [os.path.join(CSRC, d) for d in API_DEPS] + ([LOCAL_DEF] if os.path.exists(LOCAL_DEF) else [])
     jobs = []
     api = os.path.join(CSRC, "fe_api.hip")
+    common_api = deps(api) + ([LOCAL_DEF] if os.path.exists(LOCAL_DEF) else [])
     api_defs = [f'-DFE_LOCAL_DEF="{LOCAL_DEF}"'] if os.path.exists(LOCAL_DEF) else []
     if SHAPES_DEF:
         api_defs = [f'-DFE_SHAPES_DEF="{os.path.abspath(SHAPES_DEF)}"']
         common_api.append(os.path.abspath(SHAPES_DEF))
-    jobs.append((api, os.path.join(OBJ, "fe_api.o"), api_defs, os.path.join(OBJ, "fe_api.stamp"), _digest(common_api + [api], " ".join(FLAGS + api_defs))))
+    jobs.append((api, os.path.join(OBJ, "fe_api.o"), api_defs, os.path.join(OBJ, "fe_api.stamp"), _digest(common_api, " ".join(FLAGS + api_defs))))
     tmpl = os.path.join(CSRC, "fe_shape.hip.in")
+    common = deps(tmpl)
     for name, args in shapes():
         defs = [f"-DFE_SHAPE_NAME={name}", f"-DFE_SHAPE_ARGS={args}"]
         jobs.append((tmpl, os.path.join(OBJ, f"fe_shape_{name}.o"), defs, os.path.join(OBJ, f"fe_shape_{name}.stamp"),
-                     _digest(common + [tmpl], " ".join(FLAGS + defs))))
+                     _digest(common, " ".join(FLAGS + defs))))
     tmpl_b = os.path.join(CSRC, "fe_bsrnn_shape.hip.in")
+    common_b = deps(tmpl_b)
     for name, args in shapes("fe_bsrnn_shapes.def", "XB"):
         defs = [f"-DFE_SHAPE_NAME={name}", f"-DFE_SHAPE_ARGS={args}"]
         jobs.append((tmpl_b, os.path.join(OBJ, f"fe_bsrnn_{name}.o"), defs, os.path.join(OBJ, f"fe_bsrnn_{name}.stamp"),
-                     _digest(common_b + [tmpl_b], " ".join(FLAGS + defs))))
+                     _digest(common_b, " ".join(FLAGS + defs))))
     # The two VALU-only models are compiled without the SLP vectoriser: it pairs the FMAs of two outputs into v_pk_fma_f32 whose packed
     # operand it then has to assemble with one or two v_mov_b32 each (811 moves in FSPEN's hot kernel): FSPEN +7 % at 4096 streams,
     # +2 % at 256, LiSenNet +1 % (profiles/r3z_no_slp_ab.txt; the MFMA kernels and BSRNN lose 0.2-1.3 % without it and keep it).
     valu_defs = ["-fno-slp-vectorize"]
     fsp = os.path.join(CSRC, "fe_fspen.hip")
     jobs.append((fsp, os.path.join(OBJ, "fe_fspen.o"), valu_defs, os.path.join(OBJ, "fe_fspen.stamp"),
-                 _digest([os.path.join(CSRC, d) for d in FSPEN_DEPS] + [fsp], " ".join(FLAGS + valu_defs))))
+                 _digest(deps(fsp), " ".join(FLAGS + valu_defs))))
     lsn = os.path.join(CSRC, "fe_lisennet.hip")
     jobs.append((lsn, os.path.join(OBJ, "fe_lisennet.o"), valu_defs, os.path.join(OBJ, "fe_lisennet.stamp"),
-                 _digest([os.path.join(CSRC, d) for d in LISENNET_DEPS] + [lsn], " ".join(FLAGS + valu_defs))))
+                 _digest(deps(lsn), " ".join(FLAGS + valu_defs))))
     # fe_build_key(): the digest of the sources, compiled into the library (a translation unit of its own: seconds)
     bk = os.path.join(OBJ, "fe_build_key.cpp")
     skey = source_key()
@@ -214,9 +232,8 @@ def build(force: bool = False, verbose: bool = True) -> str:
         for j in jobs:
             if os.path.exists(j[3]):
                 os.remove(j[3])
-    workers = max(1, min(len(jobs), (os.cpu_count() or 2)))
     rebuilt = False
-    with concurrent.futures.ThreadPoolExecutor(workers) as ex:
+    with concurrent.futures.ThreadPoolExecutor(pool_size(len(jobs))) as ex:
         for obj, did in ex.map(_compile, jobs):
             rebuilt |= did
             if verbose and did:

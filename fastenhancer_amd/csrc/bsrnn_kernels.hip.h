@@ -174,10 +174,9 @@ struct BLds {
 // GEMM pipelines like the larger shapes), shorter MLP weight rings - the other workgroup covers those latencies.
 // PIPE: time pipelining of an offline launch (the per-hop kernel's scheme, fe_kernels.hip.h): everything in a frame but the time-LSTM's
 // (h, c) per layer is independent of the other frames, so the frames of an utterance are spread over pipe_p CO-RESIDENT workgroups
-// (cooperative launch) and the state is handed from frame t - 1 to frame t through `lstm` - agent-scope stores, drained, then an
-// agent-scope store of a per-(utterance, layer) frame counter; the consumer polls the counter and fetches the state with agent-scope
-// loads right before the layer's gate GEMM (state AND counter through agent-scope accesses: no release / acquire fence, which on this
-// part writes back / invalidates whole caches).  The serial chain per frame and layer is wait -> fetch -> gates -> publish; the band
+// (cooperative launch) and the state is handed from frame t - 1 to frame t through `lstm` by the protocol of fe_handover.h, a counter
+// per (utterance, layer); the consumer waits and fetches right before the layer's gate GEMM.  The serial chain per frame and layer is
+// wait -> fetch -> gates -> publish; the band
 // recurrence, the fc layers and the mask MLPs - 9/10 of a frame - run in parallel across the frames in flight.
 // PART (the per-hop step split in three launches, blaunch_split): every workgroup of the fused kernel streams the mask decoder's 780 KB
 // (xt) of weights from L2 once per frame - each weight is used ONCE per stream (M = 1) - and that is 40 k of a frame's 240 k cycles at
@@ -291,14 +290,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
 
     int b = PIPE ? (int)blockIdx.x / a.pipe_p : (int)blockIdx.x;
     const int t_first = PIPE ? (int)blockIdx.x - b * a.pipe_p : 0, t_step = PIPE ? a.pipe_p : 1;
-    auto ld_state = [](const float* p) -> float {
-        if constexpr (PIPE) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else return *p;
-    };
-    auto st_state = [](float* p, float v) {
-        if constexpr (PIPE) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else *p = v;
-    };
+    using HO = HandOver<PIPE>;                       // (h, c) exchange between the workgroups of an utterance (fe_handover.h)
 #pragma unroll 1
     do {
     // An opaque zero per stream: the per-thread weight addresses of the phases far down the frame (band split, mask MLPs) do not depend on the
@@ -434,16 +426,9 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
             if (l == 0) BE_CLK(2);
             if constexpr (PIPE) {
                 // frame t - 1's state of this layer: wait for it, fetch h into the GEMM's A operand buffer (c is fetched in the epilogue's place)
-                if (t > 0) {
-                    if (tid == 0) {
-                        int spins = 0;
-                        while (__hip_atomic_load(pflag + l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned int)t && ++spins < (1 << 24)) __builtin_amdgcn_s_sleep(1);
-                        if (spins >= (1 << 24)) __builtin_trap();      // (a producer that never shows up: fail the launch loudly, never run on stale state)
-                    }
-                    __syncthreads();
-                }
+                HO::wait(pflag, l, t);
 #pragma unroll
-                for (int q = 0; q < HPT; ++q) { const int i = tid + q * kThreads; hpre[q] = ld_state(hg + (i < kBands * HH ? i : kBands * HH - 1)); }
+                for (int q = 0; q < HPT; ++q) { const int i = tid + q * kThreads; hpre[q] = HO::ld(hg + (i < kBands * HH ? i : kBands * HH - 1)); }
 #pragma unroll
                 for (int q = 0; q < HPT; ++q) {
                     const int i = tid + q * kThreads, r = i / HH;
@@ -461,7 +446,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
                     float cprev[4];
                     const int j = 16 * ct + li;
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) { const int row = 16 * mt + 4 * lg + r; cprev[r] = ld_state(cg + (row < kBands ? row : kBands - 1) * HH + j); }
+                    for (int r = 0; r < 4; ++r) { const int row = 16 * mt + 4 * lg + r; cprev[r] = HO::ld(cg + (row < kBands ? row : kBands - 1) * HH + j); }
                     f32x4 acc[1][4];
 #pragma unroll
                     for (int g = 0; g < 4; ++g) { const float bv = wtbf(g); acc[0][g] = f32x4{bv, bv, bv, bv}; }
@@ -503,13 +488,9 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
                 for (int q = 0; q < HPT; ++q) {
                     const int i = tid + q * kThreads, ic = i < kBands * HH ? i : kBands * HH - 1, r = ic / HH, c = ic - r * HH;
                     const float hv = Hn[r * LDH + c], cv = Cn[r * LDH + c];
-                    if (i < kBands * HH) { st_state(hg + i, hv); st_state(cg + i, cv); }
+                    if (i < kBands * HH) { HO::st(hg + i, hv); HO::st(cg + i, cv); }
                 }
-                if constexpr (PIPE) {      // publish: every thread's state stores have left the CU, then one store of the counter
-                    __builtin_amdgcn_s_waitcnt(0x0f70);          // vmcnt(0)
-                    __syncthreads();
-                    if (tid == 0) __hip_atomic_store(pflag + l, (unsigned int)(t + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
+                HO::publish(pflag, l, t);
             }
             if (l == 0) BE_CLK(3);
             {
@@ -1067,7 +1048,7 @@ struct BMlpLds {
 // One wave's share of the mask decoder for sixteen streams (s0 .. s0 + 15) of one (kind, band): layer 1, then the layer-2 items
 // it0, it0 + its, ... (nitw of them; an item = a column tile of the band's rows x a burst of KB k-steps) of `tpw` consecutive stream tiles.
 // AGENT (r6, the fused per-hop step: bsrnn_ov_kernels.hip.h): the band features were written, and the pre-activations will be read, by
-// OTHER workgroups of the same launch - agent-scope loads / stores (the hand-over protocol of the time-pipelined kernels: no fences).
+// OTHER workgroups of the same launch - HandOver<AGENT>::ld / st (fe_handover.h: agent-scope accesses, no fences).
 template <class S, bool AGENT>
 __device__ __forceinline__ void bsrnn_mlp_wave(const BArgs& a, float* h1, int kind, int band, int tile0, int tpw, int it0, int its, int nitw, int lane) {
     constexpr int C = S::C, O1 = 4 * C, R4 = C / 4, NT1 = O1 / 16, KS2 = O1 / 4, LDH = BMlpLds<S>::LDH;
@@ -1104,8 +1085,7 @@ __device__ __forceinline__ void bsrnn_mlp_wave(const BArgs& a, float* h1, int ki
         float av[R4];
 #pragma unroll
         for (int ks = 0; ks < R4; ++ks) {
-            if constexpr (AGENT) av[ks] = __hip_atomic_load(xa + 4 * ks, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            else av[ks] = xa[4 * ks];
+            av[ks] = HandOver<AGENT>::ld(xa + 4 * ks);
         }
         const float* w1 = wp + o.m_w1[kind] + (size_t)band * R4 * O1 * 4 + li * 4 + lg;
         const float* b1 = wp + o.m_b1[kind] + band * O1 + li;
@@ -1164,8 +1144,7 @@ __device__ __forceinline__ void bsrnn_mlp_wave(const BArgs& a, float* h1, int ki
                         for (int r = 0; r < 4; ++r) {
                             const int st = s0 + 4 * lg + r;
                             if (cok && st < a.B) {
-                                if constexpr (AGENT) __hip_atomic_store(pre + (size_t)st * (2 * kMlpRows) + row, acc[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                else pre[(size_t)st * (2 * kMlpRows) + row] = acc[r];
+                                HandOver<AGENT>::st(pre + (size_t)st * (2 * kMlpRows) + row, acc[r]);
                             }
                         }
                     }
@@ -1223,8 +1202,7 @@ __device__ __forceinline__ void bsrnn_mlp_wave_multi(const BArgs& a, float* h1, 
         const float* xa = a.mlp_x + ((size_t)srow * kBands + band) * C + lg;
 #pragma unroll
         for (int ks = 0; ks < R4; ++ks) {
-            if constexpr (AGENT) av[ks] = __hip_atomic_load(xa + 4 * ks, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            else av[ks] = xa[4 * ks];
+            av[ks] = HandOver<AGENT>::ld(xa + 4 * ks);
         }
     };
     float avn[R4];
@@ -1296,8 +1274,7 @@ __device__ __forceinline__ void bsrnn_mlp_wave_multi(const BArgs& a, float* h1, 
                         for (int r = 0; r < 4; ++r) {
                             const int st = s0 + 4 * lg + r;
                             if (cok && st < a.B) {
-                                if constexpr (AGENT) __hip_atomic_store(pre + (size_t)st * (2 * kMlpRows) + row, acc[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                else pre[(size_t)st * (2 * kMlpRows) + row] = acc[r];
+                                HandOver<AGENT>::st(pre + (size_t)st * (2 * kMlpRows) + row, acc[r]);
                             }
                         }
                     }

@@ -80,8 +80,8 @@ __device__ __forceinline__ int ov_band(int i) {
 // memory per tile and barrier: every barrier instance advances it by exactly 16 (the first workgroup of a short last tile arrives for the absent
 // ones), so the instance a workgroup takes part in is old / 16 and it is over at (old / 16 + 1) * 16 - no reset, no generation word, no epoch in the
 // kernel arguments (a captured HIP graph replays the same arguments), unsigned wrap-around included.  Data handed across the barrier goes through
-// agent-scope stores drained with s_waitcnt vmcnt(0) before the arrival, and agent-scope loads after it (the protocol of the time-pipelined
-// kernels: no release / acquire fences, which write back / invalidate whole caches on this part).  All workgroups of the launch are
+// agent-scope stores drained with s_waitcnt vmcnt(0) before the arrival, and agent-scope loads after it (the data side of the time-pipelined
+// kernels' protocol, fe_handover.h: no release / acquire fences, which write back / invalidate whole caches on this part).  All workgroups of the launch are
 // co-resident: one per CU, at most #CUs of them, launched cooperatively.
 __device__ __forceinline__ void ov_group_barrier(unsigned int* cnt, unsigned int arrive) {
     __builtin_amdgcn_s_waitcnt(0x0f70);          // vmcnt(0): this thread's stores have left the CU

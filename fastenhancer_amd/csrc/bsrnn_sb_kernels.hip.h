@@ -76,8 +76,8 @@ struct SbArgs {
     int total;                    // floats of the packed buffer
 };
 
-// sigma / tanh of pre-scaled pre-activations (the packer multiplies the i, f, o rows by -log2 e and the g rows by -2 log2 e)
-__device__ __forceinline__ float sb_sig(float pre) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(pre)); }
+// sigma / tanh of pre-scaled pre-activations (the packer multiplies the i, f, o rows by -log2 e and the g rows by -2 log2 e): sigmoid_pre and,
+// the g rows having the other sign than tanh_pre wants,
 __device__ __forceinline__ float sb_tanh_pre(float pre) { return __builtin_fmaf(2.0f, __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(pre)), -1.0f); }
 
 template <class S>
@@ -188,7 +188,7 @@ __global__ void __launch_bounds__(kSbThreads) __attribute__((amdgpu_waves_per_eu
                 float hn[KSH], cn[KSH];
 #pragma unroll
                 for (int t = 0; t < KSH; ++t) {                              // gate order i, f, g, o (nn.LSTMCell)
-                    const float ig = sb_sig(acc[t][0]), fg = sb_sig(acc[t][1]), gg = sb_tanh_pre(acc[t][2]), og = sb_sig(acc[t][3]);
+                    const float ig = sigmoid_pre(acc[t][0]), fg = sigmoid_pre(acc[t][1]), gg = sb_tanh_pre(acc[t][2]), og = sigmoid_pre(acc[t][3]);
                     cn[t] = fg * cp[t] + ig * gg;
                     hn[t] = og * tanh_f(cn[t]);
                 }
@@ -273,7 +273,7 @@ __global__ void __launch_bounds__(kSbThreads) __attribute__((amdgpu_waves_per_eu
                         for (int tt = 0; tt < TPW; ++tt) acc[tt] = FE_MFMA(Wt[tt][KSC + ks], hp[ks], acc[tt]);
 #pragma unroll
                     for (int tt = 0; tt < TPW; ++tt) {                           // gate order i, f, g, o (nn.LSTMCell)
-                        const float ig = sb_sig(acc[tt][0]), fg = sb_sig(acc[tt][1]), gg = sb_tanh_pre(acc[tt][2]), og = sb_sig(acc[tt][3]);
+                        const float ig = sigmoid_pre(acc[tt][0]), fg = sigmoid_pre(acc[tt][1]), gg = sb_tanh_pre(acc[tt][2]), og = sigmoid_pre(acc[tt][3]);
                         const float cn = fg * cp[tt] + ig * gg;
                         const float hn = og * tanh_f(cn);
                         if (sok) cg[soff(j) + wave * TPW + tt] = cn;
@@ -356,7 +356,7 @@ __global__ void __launch_bounds__(kSbThreads) __attribute__((amdgpu_waves_per_eu
                 float* yg = a.y + yoff(d, j);
 #pragma unroll
                 for (int tt = 0; tt < NTW; ++tt) {
-                    const float ig = sb_sig(acc[tt][0]), fg = sb_sig(acc[tt][1]), gg = sb_tanh_pre(acc[tt][2]), og = sb_sig(acc[tt][3]);
+                    const float ig = sigmoid_pre(acc[tt][0]), fg = sigmoid_pre(acc[tt][1]), gg = sb_tanh_pre(acc[tt][2]), og = sigmoid_pre(acc[tt][3]);
                     cst[tt] = fg * cst[tt] + ig * gg;
                     const float hv = og * tanh_f(cst[tt]);
                     const int t = wq + 4 * tt;
@@ -522,7 +522,7 @@ __global__ void __launch_bounds__(kSbThreads) __attribute__((amdgpu_waves_per_eu
                             for (int tt = 0; tt < 2; ++tt) acc[tt] = FE_MFMA(Wt[tt][(KSC + ks) / 4][ks % 4], hp[ks], acc[tt]);
 #pragma unroll
                         for (int tt = 0; tt < 2; ++tt) {                   // gate order i, f, g, o (nn.LSTMCell)
-                            const float ig = sb_sig(acc[tt][0]), fg = sb_sig(acc[tt][1]), gg = sb_tanh_pre(acc[tt][2]), og = sb_sig(acc[tt][3]);
+                            const float ig = sigmoid_pre(acc[tt][0]), fg = sigmoid_pre(acc[tt][1]), gg = sb_tanh_pre(acc[tt][2]), og = sigmoid_pre(acc[tt][3]);
                             const float cn = fg * cp[tt] + ig * gg;
                             const float hn = og * tanh_f(cn);
                             if (sok) cg[soff(j) + t0 + tt] = cn;
@@ -619,7 +619,7 @@ __global__ void __launch_bounds__(kSbThreads) __attribute__((amdgpu_waves_per_eu
                 f32x4 yv;
 #pragma unroll
                 for (int tt = 0; tt < 4; ++tt) {
-                    const float ig = sb_sig(acc[tt][0]), fg = sb_sig(acc[tt][1]), gg = sb_tanh_pre(acc[tt][2]), og = sb_sig(acc[tt][3]);
+                    const float ig = sigmoid_pre(acc[tt][0]), fg = sigmoid_pre(acc[tt][1]), gg = sb_tanh_pre(acc[tt][2]), og = sigmoid_pre(acc[tt][3]);
                     cst[tt] = fg * cst[tt] + ig * gg;
                     const float hv = og * tanh_f(cst[tt]);
                     hnx[(4 * (wave * 4 + tt) + lg) * NS + li] = hv;         // unit KSH lg + t <-> position 4 t + lg

@@ -25,6 +25,7 @@
 #include <utility>
 
 #include "fe_launch.h"      // note_kernel, launch / launch_coop: how every kernel below is enqueued
+#include "fe_handover.h"    // HandOver<PIPE>: how the workgroups of a time-pipelined launch hand data to each other
 
 #ifndef FE_OCC_SMALL
 #define FE_OCC_SMALL 3
@@ -874,6 +875,12 @@ template <> struct StreamCtl<true> {
 __device__ __forceinline__ float wave_sum(float acc, float v) {
     return wave_uniform(acc + rows_allreduce(row16_allreduce(v, [](float x, float y) { return x + y; }), [](float x, float y) { return x + y; }));
 }
+// sum over the four lane groups (lanes li, li + 16, li + 32, li + 48)
+__device__ __forceinline__ float sum_lg(float v) {
+    v += __shfl_xor(v, 16, 64);
+    v += __shfl_xor(v, 32, 64);
+    return v;
+}
 __device__ __forceinline__ float wave_max(float acc, float v) {
     return wave_uniform(fmaxf(acc, rows_allreduce(row16_allreduce(v, [](float x, float y) { return fmaxf(x, y); }), [](float x, float y) { return fmaxf(x, y); })));
 }
@@ -1611,14 +1618,8 @@ __device__ __forceinline__ void attention_head(const float* G, float* Hl, int ho
 // pipeline (the last phase of a stream's last frame stages unit 0 for the next stream) - instead of paying the kernel
 // prologue and a workgroup launch per stream.  PERSIST = false: one stream per workgroup, no stream loop.
 // PIPE (offline / spec -> spec with T >> 1): the frames of ONE stream are spread over P co-resident workgroups (one per
-// CU), workgroup p running frames p, p + P, ...  Everything in a frame but the GRU state is independent of the other
-// frames, so the workgroups run their frames concurrently, staggered by the one true dependency: frame t's GRU in block
-// k needs h_k(t-1).  The producer publishes it through global memory: agent-scope (sc1) stores of the state, drained with
-// s_waitcnt vmcnt(0) + the phase barrier, then a RELAXED agent-scope store of a per-(stream, block) frame counter; the consumer polls
-// the counter (relaxed, agent scope) and then fetches the state with agent-scope loads.  INVARIANT: every datum handed from one
-// workgroup to another goes through st_state / ld_state - a plain load or store added to a ring or state would be a silent stale read
-// (no release / acquire fence covers it).  The serial chain is
-// T x (state round trip + one GRU phase) instead of T x (whole frame): ~12 frames in flight for FastEnhancer_B.
+// CU), workgroup p running frames p, p + P, ...; frame t's GRU in block k needs h_k(t-1), handed over by the protocol of
+// fe_handover.h (HO below; its invariant: every datum handed from one workgroup to another goes through HO::st / HO::ld).
 // FE_MODE_STREAM under PIPE (fe_step_chunk): frame t reads its samples from the call's cache_stft and wav_in, both written by nobody
 // during the launch, and stores its windowed frame to a.frames; cache_stft / cache_istft are not written here - what crosses frames on
 // the audio side is stream_ola_kernel's (stft_kernels.hip.h), a second, ordinary launch.
@@ -1784,15 +1785,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
     int b = PIPE ? (int)blockIdx.x / a.pipe_p : (int)blockIdx.x;
     const int t_first = PIPE ? (int)blockIdx.x - b * a.pipe_p : 0, t_step = PIPE ? a.pipe_p : 1;
     int fc = 0;                                      // frames done by this workgroup (staging-buffer parity)
-    // GRU state exchange between the workgroups of a stream (PIPE): agent-scope accesses (not served from a stale L1 / L2 line)
-    auto ld_state = [](const float* p) -> float {
-        if constexpr (PIPE) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else return *p;
-    };
-    auto st_state = [](float* p, float v) {
-        if constexpr (PIPE) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else *p = v;
-    };
+    using HO = HandOver<PIPE>;                       // state exchange between the workgroups of a stream (fe_handover.h)
 #pragma unroll 1
     do {
     int sb = b;                                      // the stream's state slot
@@ -1854,26 +1847,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
     float* cst = a.cache_stft + (size_t)sb * OVL;
     float* cis = a.cache_istft + (size_t)sb * OVL;
     constexpr int NFLAG = S::KB + (S::KT > 1 ? 2 * S::NL : 0);       // counters per stream
-    unsigned int* pflag = PIPE ? a.pipe_flags + (size_t)b * NFLAG : nullptr;
-    // wait until the block-k state of frame t-1 is published (all threads call; thread 0 polls)
-    auto pipe_wait = [&](int k, int t) {
-        if constexpr (PIPE) {
-            if (t > 0) {
-                if (tid == 0) {
-                    while (__hip_atomic_load(pflag + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned int)t) __builtin_amdgcn_s_sleep(1);
-                }
-                __syncthreads();
-            }
-        }
-    };
-    // publish frame t's block-k state: every thread's state stores have left the CU, then one release store of the counter
-    auto pipe_publish = [&](int k, int t) {
-        if constexpr (PIPE) {
-            __builtin_amdgcn_s_waitcnt(0x0f70);          // vmcnt(0) (gfx9 encoding: lgkmcnt / expcnt left alone)
-            __syncthreads();
-            if (tid == 0) __hip_atomic_store(pflag + k, (unsigned int)(t + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    };
+    unsigned int* pflag = PIPE ? a.pipe_flags + (size_t)b * NFLAG : nullptr;      // block k's state: pflag + k; conv ring l: pflag + KB + l
 
     int ring_head0 = 0;                              // dptransformer: slot of the oldest cached frame when this launch starts
     if constexpr (S::TATT && !PIPE) ring_head0 = (int)a.h[(size_t)nst * S::KB * S::HSTATE + sb];
@@ -2167,19 +2141,14 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                 if constexpr (sub == 0) {
                     acc_init_bias<S::MTPW, S::NTC>(acc, wb, b_off, 0, 1, S::NTC);
                     if constexpr (PIPE) {
-                        if (t > 0) {
-                            if (tid == 0) {
-                                while (__hip_atomic_load(pflag + S::KB + lidx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned int)t) __builtin_amdgcn_s_sleep(1);
-                            }
-                            __syncthreads();
-                        }
+                        HO::wait_unbounded(pflag, S::KB + lidx, t);
 #pragma unroll
                         for (int q = 0; q < CPT; ++q) {
                             const int e4 = tid + q * kThreads, slot = e4 / Q4, r = e4 - slot * Q4;
                             const int fr = t + a.tk_base - (KT - 1) + slot;        // slot 0 = the oldest frame of the window (ring index)
                             const float* src = ringb + (size_t)((fr < 0 ? 0 : fr) % RS) * (F1 * C1) + 4 * r;
                             float4 v;
-                            v.x = ld_state(src); v.y = ld_state(src + 1); v.z = ld_state(src + 2); v.w = ld_state(src + 3);
+                            v.x = HO::ld(src); v.y = HO::ld(src + 1); v.z = HO::ld(src + 2); v.w = HO::ld(src + 3);
                             creg[q] = fr < 0 ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : v;      // (before the utterance: the zero cache of Model.forward)
                         }
                     } else {
@@ -2211,16 +2180,14 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                         constexpr float un = 1.0f / kSiluScale;
                         if constexpr (PIPE) {
                             float* dst = ringb + (size_t)((t + a.tk_base) % RS) * (F1 * C1) + 4 * r;
-                            st_state(dst, v0.x * un); st_state(dst + 1, v0.y * un); st_state(dst + 2, v1.x * un); st_state(dst + 3, v1.y * un);
+                            HO::st(dst, v0.x * un); HO::st(dst + 1, v0.y * un); HO::st(dst + 2, v1.x * un); HO::st(dst + 3, v1.y * un);
                         } else
                         tkg[(KT - 2) * Q4 + r] = make_float4(v0.x * un, v0.y * un, v1.x * un, v1.y * un);
                     }
-                    if constexpr (PIPE) __builtin_amdgcn_s_waitcnt(0x0f70);      // vmcnt(0): this thread's slot stores have left the CU
+                    HO::drain();                                                    // this thread's slot stores have left the CU
                 }
                 if constexpr (sub + 1 < KT) __syncthreads();
-                if constexpr (PIPE && sub == 0) {
-                    if (tid == 0) __hip_atomic_store(pflag + S::KB + lidx, (unsigned int)(t + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
+                if constexpr (sub == 0) HO::signal(pflag, S::KB + lidx, t);
             });
             conv_store<S, S::NTC, C1, LDC, true>(acc, out, 1, wave, lane, nullptr, ap);
             }
@@ -2578,13 +2545,13 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                         for (int e = tid; e < PAIRS * HD; e += kThreads) {
                             const int p = e / HD, d = e - p * HD, f = p / S::NH, hh = p - f * S::NH;
                             const float* qk = Gi + f * LDG + hh * 3 * HD;
-                            st_state(kc + ((size_t)p * RS + slot) * HD + d, qk[HD + d]);
-                            st_state(vc + ((size_t)p * RS + slot) * HD + d, qk[2 * HD + d]);
+                            HO::st(kc + ((size_t)p * RS + slot) * HD + d, qk[HD + d]);
+                            HO::st(vc + ((size_t)p * RS + slot) * HD + d, qk[2 * HD + d]);
                         }
                     }
                     // (wait first, then count: the counter must never step back - frame t + 1 may get here before frame t)
-                    pipe_wait(k, t);
-                    pipe_publish(k, t);
+                    HO::wait_unbounded(pflag, k, t);
+                    HO::publish(pflag, k, t);
                     const int grp = tid >> 4, l16 = tid & 15;
                     const int mask_lo = wbase ? 0 : (LBK - t > 0 ? LBK - t : 0);
                     const float sc = __builtin_amdgcn_rsqf((float)HD);
@@ -2607,13 +2574,13 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                         const float* vp = vc + (size_t)p * (RS * HD);
                         float k0[HD], k1[HD], v0[HD], v1[HD];
 #pragma unroll
-                        for (int d = 0; d < HD; ++d) k0[d] = ld_state(kp + sl0 * HD + d);
+                        for (int d = 0; d < HD; ++d) k0[d] = HO::ld(kp + sl0 * HD + d);
 #pragma unroll
-                        for (int d = 0; d < HD; ++d) k1[d] = ld_state(kp + sl1 * HD + d);
+                        for (int d = 0; d < HD; ++d) k1[d] = HO::ld(kp + sl1 * HD + d);
 #pragma unroll
-                        for (int d = 0; d < HD; ++d) v0[d] = ld_state(vp + sl0 * HD + d);
+                        for (int d = 0; d < HD; ++d) v0[d] = HO::ld(vp + sl0 * HD + d);
 #pragma unroll
-                        for (int d = 0; d < HD; ++d) v1[d] = ld_state(vp + sl1 * HD + d);
+                        for (int d = 0; d < HD; ++d) v1[d] = HO::ld(vp + sl1 * HD + d);
                         // (carried caches: a slot whose first K element is +inf marks a frame before a cache-less start)
                         const bool m0 = mf0 || (wbase != 0 && k0[0] == __builtin_inff());
                         const bool m1 = mf1 || (wbase != 0 && j1 < LBK && k1[0] == __builtin_inff());
@@ -2794,9 +2761,9 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                 auto pipe_fetch_state = [&]() {
                     if constexpr (PIPE) {
                         float hq_[HPT];
-                        pipe_wait(k, t);
+                        HO::wait_unbounded(pflag, k, t);
 #pragma unroll
-                        for (int q = 0; q < HPT; ++q) { const int i = tid + q * kThreads; hq_[q] = ld_state(hg + (i < F2 * C2 ? i : F2 * C2 - 1)); }
+                        for (int q = 0; q < HPT; ++q) { const int i = tid + q * kThreads; hq_[q] = HO::ld(hg + (i < F2 * C2 ? i : F2 * C2 - 1)); }
 #pragma unroll
                         for (int q = 0; q < HPT; ++q) {
                             Hs[hs_off[q]] = hq_[q];
@@ -2899,7 +2866,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
 #pragma unroll
                         for (int q = 0; q < HPT; ++q) {
                             const int e = tid + q * kThreads;
-                            if ((q + 1) * kThreads <= F2 * C2 || e < F2 * C2) { Hl[eo[q]] = hn[q]; st_state(hg + e, hn[q]); }
+                            if ((q + 1) * kThreads <= F2 * C2 || e < F2 * C2) { Hl[eo[q]] = hn[q]; HO::st(hg + e, hn[q]); }
                         }
                     }
                 } else if constexpr (GBAL) {
@@ -2946,7 +2913,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                                         const float hp = Hs[row * LDX + c];
                                         const float hn = (1.0f - zz) * nn + zz * hp;
                                         Hl[row * LDX + c] = hn;
-                                        st_state(hg + row * C2 + c, hn);
+                                        HO::st(hg + row * C2 + c, hn);
                                     }
                                 }
                         }
@@ -2996,7 +2963,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                                     const float nn = tanh_f(ax[i][2][r] + rr * ah[i][2][r]);
                                     const float hn = (1.0f - zz) * nn + zz * hprev[i][r];
                                     Hl[row * LDX + c] = hn;
-                                    st_state(hg + row * C2 + c, hn);
+                                    HO::st(hg + row * C2 + c, hn);
                                 }
                             }
                             }
@@ -3004,7 +2971,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                 }
             }
             if (k == 0) FE_CLK(47);
-            if constexpr (PIPE && !S::TATT) pipe_publish(k, t);      // (its barrier is this phase's barrier; dptransformer: published above)
+            if constexpr (PIPE && !S::TATT) HO::publish(pflag, k, t);      // (its barrier is this phase's barrier; dptransformer: published above)
             else __syncthreads();
             if (k == 0) FE_CLK(21);
             if (k == 0) FE_CLK(22);

@@ -286,8 +286,8 @@ __device__ __forceinline__ float row_dot(const float (&w)[12], float h, float ac
 #define FS_CLK(i) do { if constexpr (PROF) { if (blockIdx.x == 0 && threadIdx.x == 0) a.clk[(i)] = __builtin_readcyclecounter(); } } while (0)
 
 // PIPE: time pipelining of an offline launch (as for FastEnhancer / BSRNN): the only thing a frame needs from the previous one are the
-// inter-GRU states (24 x [4][16] per stream), handed over per DPE block through `gru` - agent-scope stores, drained, a counter per
-// (utterance, block); the consumer polls the counter and fetches the states right before the block's inter GRUs.
+// inter-GRU states (24 x [4][16] per stream), handed over per DPE block through `gru` by the protocol of fe_handover.h, a counter per
+// (utterance, block); the consumer waits and fetches the states right before the block's inter GRUs.
 // PART: 0 the whole frame; 1 the front (STFT, sub-band encoder, fullband_encoder.0-1: its LDS regions to global memory); 2 the tail
 // (sub-band decoder, fullband_decoder.2, masks, iSTFT) - the per-hop step of large batches runs 1 -> fspen_sb_dpe_kernel (fullband_encoder.2,
 // fullband_encoder_post, feature merge, 3 x DPE, feature split, fullband_decoder.0-1 - batched over the streams, fspen_sb_kernels.hip.h) -> 2
@@ -325,14 +325,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(P
 
     int b = PIPE ? (int)blockIdx.x / a.pipe_p : (int)blockIdx.x;
     const int t_first = PIPE ? (int)blockIdx.x - b * a.pipe_p : 0, t_step = PIPE ? a.pipe_p : 1;
-    auto ld_state = [](const float* p) -> float {
-        if constexpr (PIPE) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else return *p;
-    };
-    auto st_state = [](float* p, float v) {
-        if constexpr (PIPE) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else *p = v;
-    };
+    using HO = HandOver<PIPE>;                       // inter-GRU state exchange between the workgroups of an utterance (fe_handover.h)
 #pragma unroll 1
     do {
     // (per-stream pointers are derived from the kernel arguments where they are used, not kept live through the frame)
@@ -751,18 +744,11 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(P
             if (blk == 0) FS_CLK(10);
             if constexpr (PIPE) {
                 // frame t - 1's inter-GRU states of this block: wait for them, fetch them into hprev
-                if (t > 0) {
-                    if (tid == 0) {
-                        int spins = 0;
-                        while (__hip_atomic_load(a.pipe_flags + (size_t)b * S::NB + blk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned int)t && ++spins < (1 << 24)) __builtin_amdgcn_s_sleep(1);
-                        if (spins >= (1 << 24)) __builtin_trap();      // (a producer that never shows up: fail the launch loudly, never run on stale state)
-                    }
-                    __syncthreads();
-                }
+                HO::wait(a.pipe_flags + (size_t)b * S::NB, blk, t, tid);      // (tid: the frame loop's copy of the thread index, see above)
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
                     const int f = (tid >> 4) + 16 * q, g = f >> 2;
-                    hprev[f * 16 + (tid & 15)] = ld_state(a.gru + (((size_t)(blk * S::G + g) * a.B + b) * S::FG + (f & 3)) * S::C + (tid & 15));
+                    hprev[f * 16 + (tid & 15)] = HO::ld(a.gru + (((size_t)(blk * S::G + g) * a.B + b) * S::FG + (f & 3)) * S::C + (tid & 15));
                 }
                 __syncthreads();
             }
@@ -788,7 +774,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(P
                     const float n = tanh_f(in_ + r * hnn);
                     const float hnew = (1.0f - z) * n + z * hprev[f * 16 + c];
                     hn[f * 16 + c] = hnew;
-                    st_state(a.gru + (((size_t)(blk * S::G + ig_) * a.B + b) * S::FG + fl) * S::C + c, hnew);
+                    HO::st(a.gru + (((size_t)(blk * S::G + ig_) * a.B + b) * S::FG + fl) * S::C + c, hnew);
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -800,11 +786,9 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(P
                 for (int k = 0; k < 16; ++k) ifc_w[q][k] = wg[P::G_FC_W + k * 16 + (tid & 15)];
                 ifc_b[q] = wg[P::G_FC_B + (tid & 15)];
             }
-            if constexpr (PIPE) __builtin_amdgcn_s_waitcnt(0x0f70);      // vmcnt(0): this thread's state stores have left the CU
+            HO::drain();                 // this thread's state stores have left the CU (the inter_fc weight loads above land under the same wait)
             __syncthreads();
-            if constexpr (PIPE) {
-                if (tid == 0) __hip_atomic_store(a.pipe_flags + (size_t)b * S::NB + blk, (unsigned int)(t + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            HO::signal(a.pipe_flags + (size_t)b * S::NB, blk, t, tid);
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
                 const int f = (tid >> 4) + 16 * q, c = tid & 15;

@@ -60,16 +60,6 @@ struct FSbArgs {
     unsigned long long* clk;  // fe_profile_step: cycle counters of workgroup 0 (slots 32 ..), else null
 };
 
-__device__ __forceinline__ float fsb_sig(float pre) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(pre)); }                            // pre = -log2e x
-__device__ __forceinline__ float fsb_tanh(float pre) { return __builtin_fmaf(-2.0f, __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(pre)), 1.0f); }   // pre = 2 log2e x
-
-// sum over the four lane groups (lanes li, li + 16, li + 32, li + 48)
-__device__ __forceinline__ float fsb_sum_lg(float v) {
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    return v;
-}
-
 template <class S>      // (S = FShape<HOP>: the DPE does not depend on it - a template so that the kernel is emitted by the translation unit that launches it)
 __global__ void __launch_bounds__(kFsbThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) fspen_sb_dpe_kernel(FSbArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -300,8 +290,8 @@ __global__ void __launch_bounds__(kFsbThreads) __attribute__((amdgpu_waves_per_e
                 return p;
             };
             auto gates = [&](const f32x4& acc, float h) {
-                const float rg = fsb_sig(acc[0]), zg = fsb_sig(acc[1]);
-                const float ng = fsb_tanh(__builtin_fmaf(rg, acc[3], acc[2]));
+                const float rg = sigmoid_pre(acc[0]), zg = sigmoid_pre(acc[1]);
+                const float ng = tanh_pre(__builtin_fmaf(rg, acc[3], acc[2]));
                 return __builtin_fmaf(zg, h - ng, ng);                      // (1 - z) n + z h
             };
             // One workgroup barrier per step for both directions.  On gfx950 the fp32 MFMAs and the vector ALU share a SIMD's datapath:
@@ -372,7 +362,7 @@ __global__ void __launch_bounds__(kFsbThreads) __attribute__((amdgpu_waves_per_e
             float s0 = 0.0f;
 #pragma unroll
             for (int fl = 0; fl < 4; ++fl) s0 += (y[fl][0] + y[fl][1]) + (y[fl][2] + y[fl][3]);
-            s0 = fsb_sum_lg(s0);
+            s0 = sum_lg(s0);
             if (lg == 0) red[wave * 16 + li] = s0;
             __syncthreads();
             float mean = 0.0f;
@@ -384,7 +374,7 @@ __global__ void __launch_bounds__(kFsbThreads) __attribute__((amdgpu_waves_per_e
             for (int fl = 0; fl < 4; ++fl)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) { y[fl][r] -= mean; s1 = __builtin_fmaf(y[fl][r], y[fl][r], s1); }
-            s1 = fsb_sum_lg(s1);
+            s1 = sum_lg(s1);
             if (lg == 0) red[128 + wave * 16 + li] = s1;
             __syncthreads();
             float var = 0.0f;
@@ -413,8 +403,8 @@ __global__ void __launch_bounds__(kFsbThreads) __attribute__((amdgpu_waves_per_e
             for (int fl = 0; fl < 4; ++fl)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const float rg = fsb_sig(ar[fl][r]), zg = fsb_sig(az[fl][r]);
-                    const float ng = fsb_tanh(__builtin_fmaf(rg, anh[fl][r], anx[fl][r]));
+                    const float rg = sigmoid_pre(ar[fl][r]), zg = sigmoid_pre(az[fl][r]);
+                    const float ng = tanh_pre(__builtin_fmaf(rg, anh[fl][r], anx[fl][r]));
                     hn[fl][r] = __builtin_fmaf(zg, hp[fl][r] - ng, ng);
                     if (live) st0[fl * 16 + 4 * r + lg] = hn[fl][r];
                 }

@@ -168,8 +168,8 @@ namespace fe {
 // PIPE: time pipelining of an offline launch.  A frame needs the previous frame's value of NINE caches (the phase, three encoder frames,
 // per block the GRU state and the ConvGLU's two frames, the decoder frame) - each is read and replaced at ONE place of the frame.  The
 // frames in flight keep their caches in a ring of pipe_p + 2 slots per utterance (slot = frame mod RS, cache layout); a site waits for
-// the previous frame's count of that cache, reads slot t - 1 (the ConvGLU: t - 2 and t - 1), writes slot t and counts it - agent-scope
-// accesses on both sides, one counter per (utterance, cache).
+// the previous frame's count of that cache, reads slot t - 1 (the ConvGLU: t - 2 and t - 1), writes slot t and counts it - the protocol
+// of fe_handover.h, one counter per (utterance, cache).
 // PART (r6): 0 = the whole frame; 1 = STFT .. encoder.conv_2 of a per-hop step whose middle runs batched over the streams (lisennet_sb_kernel): x2, its
 // cached frame and the compressed spectrum go to the carry; 2 = that step's tail (decoder cache, mask conv .. iSTFT) from the carry's up3 output.
 template <class S, bool PROF, bool DBG, bool PIPE = false, int PART = 0>
@@ -198,14 +198,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((
     int b = PIPE ? (int)blockIdx.x / a.pipe_p : (int)blockIdx.x;
     const int t_first = PIPE ? (int)blockIdx.x - b * a.pipe_p : 0, t_step = PIPE ? a.pipe_p : 1;
     constexpr int NSITE = 5 + 2 * S::NB;
-    auto ld_state = [](const float* p) -> float {
-        if constexpr (PIPE) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else return *p;
-    };
-    auto st_state = [](float* p, float v) {
-        if constexpr (PIPE) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else *p = v;
-    };
+    using HO = HandOver<PIPE>;                       // cache exchange between the workgroups of an utterance (fe_handover.h)
 #pragma unroll 1
     do {
     float* dbg = DBG ? a.dbg + (size_t)b * a.dbg_stride : nullptr;
@@ -235,25 +228,8 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((
         auto cprev = [&](int off, int back) -> const float* { return ringb + (size_t)((t - back < 0 ? 0 : t - back) % RS) * S::CACHE_FLOATS + off; };
         auto ccur = [&](int off) -> float* { return ringb + (size_t)(t % RS) * S::CACHE_FLOATS + off; };
         unsigned int* const pflag = PIPE ? a.pipe_flags + (size_t)b * NSITE : nullptr;
-        auto cwait = [&](int site) {          // frame t - 1 has left cache `site` (all threads call)
-            if constexpr (PIPE) {
-                if (t > 0) {
-                    if (threadIdx.x == 0) {
-                        int spins = 0;
-                        while (__hip_atomic_load(pflag + site, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned int)t && ++spins < (1 << 24)) __builtin_amdgcn_s_sleep(1);
-                        if (spins >= (1 << 24)) __builtin_trap();      // (a producer that never shows up: fail the launch loudly, never run on stale state)
-                    }
-                    __syncthreads();
-                }
-            }
-        };
-        auto cpub = [&](int site) {           // this frame's value of cache `site` is in its slot (includes a barrier)
-            if constexpr (PIPE) {
-                __builtin_amdgcn_s_waitcnt(0x0f70);          // vmcnt(0)
-                __syncthreads();
-                if (threadIdx.x == 0) __hip_atomic_store(pflag + site, (unsigned int)(t + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        };
+        auto cwait = [&](int site) { HO::wait(pflag, site, t); };          // frame t - 1 has left cache `site` (all threads call)
+        auto cpub = [&](int site) { HO::publish(pflag, site, t); };        // this frame's value of cache `site` is in its slot (includes a barrier)
         // loop-variant zeros on the weight pointer and the thread index (see fspen_kernels.hip.h)
         int lz = 0, lzv = 0;
         asm volatile("" : "+s"(lz));
@@ -363,12 +339,12 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((
                 const float re = sp[2 * f], im = sp[2 * f + 1], ph = phs[f];
                 const float dgd = sgn * (ph - (f > 0 ? phs[f - 1] : 0.0f));
                 float pprev;
-                if constexpr (PIPE) pprev = t > 0 ? ld_state(cprev(0, 1) + f) : 0.0f; else pprev = cpha[f];
+                if constexpr (PIPE) pprev = t > 0 ? HO::ld(cprev(0, 1) + f) : 0.0f; else pprev = cpha[f];
                 const float dif = sgn * (ph - pprev) - 6.283185307179586f * ((float)H / (float)N) * (float)f;
                 feat[f] = sqrtf(re * re + im * im);
                 feat[260 + f] = atan2f(sinf(dgd), cosf(dgd)) * kInvPi;
                 feat[520 + f] = atan2f(sinf(dif), cosf(dif)) * kInvPi;
-                if constexpr (PIPE) st_state(ccur(0) + f, ph); else cpha[f] = ph;
+                if constexpr (PIPE) HO::st(ccur(0) + f, ph); else cpha[f] = ph;
             }
         }
         if constexpr (PIPE) cpub(0); else
@@ -398,8 +374,8 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((
                 float y = (v[cnt] - mean) * rstd * wp[P::C1_G + f] + wp[P::C1_BE + f];
                 y = y >= 0.0f ? y : y * wp[P::C1_P + o];
                 if constexpr (PIPE) {
-                    x1p[o * 260 + f] = t > 0 ? ld_state(cprev(S::K_PHA, 1) + i) : 0.0f;
-                    st_state(ccur(S::K_PHA) + i, y);
+                    x1p[o * 260 + f] = t > 0 ? HO::ld(cprev(S::K_PHA, 1) + i) : 0.0f;
+                    HO::st(ccur(S::K_PHA) + i, y);
                 } else {
                 x1p[o * 260 + f] = c2[i];           // previous frame (the cache) in, this frame out
                 c2[i] = y;
@@ -472,8 +448,8 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((
                     out[o * FO + f] = y;
                     if (cache_io) {
                         if constexpr (PIPE) {
-                            prev_out[o * FO + f] = t > 0 ? ld_state(cprev(site_off, 1) + o * FO + f) : 0.0f;
-                            st_state(ccur(site_off) + o * FO + f, y);
+                            prev_out[o * FO + f] = t > 0 ? HO::ld(cprev(site_off, 1) + o * FO + f) : 0.0f;
+                            HO::st(ccur(site_off) + o * FO + f, y);
                         } else { prev_out[o * FO + f] = cache_io[o * FO + f]; cache_io[o * FO + f] = y; }
                     }
                 }
@@ -629,7 +605,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((
                 cwait(4 + 2 * blk);
                 const int hoff = OFF_BLK + blk * (S::K_H + S::K_GLU);
 #pragma unroll
-                for (int q = 0; q < 3; ++q) hp[tid + 256 * q] = t > 0 ? ld_state(cprev(hoff, 1) + tid + 256 * q) : 0.0f;
+                for (int q = 0; q < 3; ++q) hp[tid + 256 * q] = t > 0 ? HO::ld(cprev(hoff, 1) + tid + 256 * q) : 0.0f;
                 __syncthreads();
             }
             {   // ONE GRU for all sub-bands: thread (hidden unit c, row group fg) keeps the unit's three gate rows (3 x (16 + 24) weights)
@@ -665,7 +641,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((
                     const float n = tanh_f(in_ + rg * hnn);
                     const float hnew = (1.0f - z) * n + z * hp[f * 24 + c];
                     hn[f * 24 + c] = hnew;
-                    if constexpr (PIPE) st_state(ccur(OFF_BLK + blk * (S::K_H + S::K_GLU)) + f * 24 + c, hnew); else
+                    if constexpr (PIPE) HO::st(ccur(OFF_BLK + blk * (S::K_H + S::K_GLU)) + f * 24 + c, hnew); else
                     ch[f * 24 + c] = hnew;
                 }
             }
@@ -700,7 +676,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((
                     for (int q = 0; q < 8; ++q) {
                         const int i = tid + 256 * q, chn = i >> 6, dt = (i >> 5) & 1, f = i & 31;
                         const int back = 2 - dt;                                    // dt = 0: frame t - 2, dt = 1: frame t - 1
-                        cpre[q] = t - back >= 0 ? ld_state(cprev(goff, back) + chn * 32 + f) : 0.0f;
+                        cpre[q] = t - back >= 0 ? HO::ld(cprev(goff, back) + chn * 32 + f) : 0.0f;
                     }
                 } else {
 #pragma unroll
@@ -741,7 +717,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((
                         acc = fmaf(wd[P::B_DW + (dt * 3 + df) * 32 + chn], ok ? xv : 0.0f, acc);
                     }
                 gg[i] = mish_f(acc) * vv[i];
-                if constexpr (PIPE) st_state(ccur(OFF_BLK + blk * (S::K_H + S::K_GLU) + S::K_H) + chn * 32 + f, xx[(64 + chn) * 32 + f]); else {
+                if constexpr (PIPE) HO::st(ccur(OFF_BLK + blk * (S::K_H + S::K_GLU) + S::K_H) + chn * 32 + f, xx[(64 + chn) * 32 + f]); else {
                 cg[(chn * 2 + 0) * 32 + f] = xx[(32 + chn) * 32 + f];
                 cg[(chn * 2 + 1) * 32 + f] = xx[(64 + chn) * 32 + f];
                 }
@@ -827,7 +803,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((
             if constexpr (PIPE) {
                 cwait(4 + 2 * S::NB);
                 const int doff = OFF_BLK + S::NB * (S::K_H + S::K_GLU);
-                for (int i = tid; i < 4 * 256; i += kThreads) { u3p[i] = t > 0 ? ld_state(cprev(doff, 1) + i) : 0.0f; st_state(ccur(doff) + i, u3[i]); }
+                for (int i = tid; i < 4 * 256; i += kThreads) { u3p[i] = t > 0 ? HO::ld(cprev(doff, 1) + i) : 0.0f; HO::st(ccur(doff) + i, u3[i]); }
                 cpub(4 + 2 * S::NB);
             } else {
             for (int i = tid; i < 4 * 256; i += kThreads) { u3p[i] = cd[i]; cd[i] = u3[i]; }

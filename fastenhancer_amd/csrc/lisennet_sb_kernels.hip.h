@@ -125,8 +125,6 @@ struct LSbArgs {
     unsigned long long* clk;  // fe_profile_step: cycle counters of workgroup 0 (slots 32 ..), else null
 };
 
-__device__ __forceinline__ float lsb_sig(float pre) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(pre)); }                              // pre = -log2e x
-__device__ __forceinline__ float lsb_tanh(float pre) { return __builtin_fmaf(-2.0f, __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(pre)), 1.0f); }   // pre = 2 log2e x
 // mish(x) = x tanh(softplus(x)) with tanh(ln(1 + n)) = n (n + 2) / (n (n + 2) + 2), n = e^x: one exponential and one reciprocal (lisennet_frame_kernel's
 // mish_f goes through log1p, exp and tanh: ~8 x the vector instructions, and the conv_glu of sixteen streams is 16 384 evaluations per block);
 // no cancellation for x -> -inf (n (n + 2) -> 2 n), x > 20: the factor is 1 to fp32 (and n^2 would overflow from x = 44)
@@ -136,11 +134,6 @@ __device__ __forceinline__ float lsb_mish(float x) {
     float y = x * (t * __builtin_amdgcn_rcpf(t + 2.0f));
     asm volatile("" : "+v"(y));          // (keeps the evaluations in program order: scheduled freely, the conv_glu passes - straight-line code - spilled 58 registers)
     return y;
-}
-__device__ __forceinline__ float lsb_sum_lg(float v) {
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    return v;
 }
 
 // per-lane source offsets (floats, relative to the tile's carry) of a convolution's quads at output position 0: pair 4 m + lg = (source, tap, group)
@@ -186,7 +179,7 @@ __global__ void __launch_bounds__(kLsbThreads) __attribute__((amdgpu_waves_per_e
     auto cache_ptr = [&](int off_sum, int per_stream) -> float* { return a.cache + (size_t)off_sum * a.B + (size_t)bn * per_stream; };
     // sum over a stream's values held by the lanes li, li + 16, .. of all eight waves (one barrier; slot 0 / 1 alternate)
     auto tile_sum = [&](float v, int slot) {
-        v = lsb_sum_lg(v);
+        v = sum_lg(v);
         if (lg == 0) red[slot * 128 + wave * 16 + li] = v;
         __syncthreads();
         float t = 0.0f;
@@ -629,8 +622,8 @@ __global__ void __launch_bounds__(kLsbThreads) __attribute__((amdgpu_waves_per_e
                 return p;
             };
             auto gates = [&](const f32x4& acc, float h) {
-                const float rg = lsb_sig(acc[0]), zg = lsb_sig(acc[1]);
-                const float ng = lsb_tanh(__builtin_fmaf(rg, acc[3], acc[2]));
+                const float rg = sigmoid_pre(acc[0]), zg = sigmoid_pre(acc[1]);
+                const float ng = tanh_pre(__builtin_fmaf(rg, acc[3], acc[2]));
                 return __builtin_fmaf(zg, h - ng, ng);                      // (1 - z) n + z h
             };
             const int hslot = lg < 3 ? 3 * q + lg : 12 + q;                 // (lane group 3: idle rows -> the unused slots 12 .. 15)
@@ -768,8 +761,8 @@ __global__ void __launch_bounds__(kLsbThreads) __attribute__((amdgpu_waves_per_e
                         f32x4 hn;
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
-                            const float rg = lsb_sig(ar[e][r]), zg = lsb_sig(az[e][r]);
-                            const float ng = lsb_tanh(__builtin_fmaf(rg, anh[e][r], anx[e][r]));
+                            const float rg = sigmoid_pre(ar[e][r]), zg = sigmoid_pre(az[e][r]);
+                            const float ng = tanh_pre(__builtin_fmaf(rg, anh[e][r], anx[e][r]));
                             hn[r] = __builtin_fmaf(zg, hp[fl][t][r] - ng, ng);
                         }
                         // (the old state of both tiles is in registers; no other lane reads these rows)
