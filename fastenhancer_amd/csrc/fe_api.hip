@@ -1359,9 +1359,16 @@ static int table_view(const void* p, size_t bytes, const char* fn, const char* w
     *dev = dv[0];
     return FE_OK;
 }
+// chunk (fe_step_streams_chunk[_pinned]): the same call with each stream's hops on the time pipeline where streams_chunk_pipe_width says so and
+// the runtime accepts the cooperative launch (launch_streams_chunk, below fe_step_chunk); otherwise - and always after the same checks - the
+// launch of the packet step itself.
+static int streams_chunk_pipe_width(const fe_handle* h, int n, int T_max);
+static int launch_streams_chunk(fe_handle* h, const fe::StreamFrameArgs& own, const float* wav_in, float* state, float* wav_out, int n, int T_max, int P,
+                                float* work_dev, void* stream, bool* refused);
 static int step_streams(fe_handle* h, const char* fn, bool pinned, const void* wav_in, size_t in_count, float* state_dev, int capacity,
                         const fe_stream_desc* desc_dev, void* wav_out, size_t out_count, int n, int T_max, int format, void* stream,
-                        const float* min_gain = nullptr, fe_stream_levels* levels = nullptr, const int* bank = nullptr) {
+                        const float* min_gain = nullptr, fe_stream_levels* levels = nullptr, const int* bank = nullptr, bool chunk = false,
+                        float* work_dev = nullptr) {
     return slotted_step(h, fn, true,
         [&]() -> int {
             if (!wav_in || !state_dev || !desc_dev || !wav_out || n <= 0 || T_max <= 0 || capacity < n || in_count == 0 || out_count == 0)
@@ -1404,6 +1411,14 @@ static int step_streams(fe_handle* h, const char* fn, bool pinned, const void* w
                 own.bank = static_cast<const int*>(banks);
                 own.n_banks = h->n_banks;
                 own.bank_stride = h->bank_stride;
+            }
+            if (const int P = chunk ? streams_chunk_pipe_width(h, n, T_max) : 0) {
+                if (!work_dev) return fail(FE_ERR_INVALID_ARG, "%s: null work buffer (fe_step_streams_chunk_work_floats(h, %d, %d) floats)", fn, n, T_max);
+                bool refused = false;
+                rc = launch_streams_chunk(h, own, static_cast<const float*>(in), state_dev, const_cast<float*>(static_cast<const float*>(out)), n, T_max, P,
+                                          work_dev, stream, &refused);
+                if (!refused) return rc;
+                // the runtime refused co-residency (GPU shared with other work): the packet step's own launch
             }
             return launch_fe_step(h, fn, fe::STEP_STREAMS, own, static_cast<const float*>(in), 0, state_dev, const_cast<float*>(static_cast<const float*>(out)), 0,
                                   n, T_max, stream);       // (the audio is typed by a.format in the kernel)
@@ -1905,6 +1920,67 @@ int fe_step_chunk(fe_handle* h, const float* wav_in_dev, size_t in_stride, float
     hipLaunchKernelGGL(fe::stream_ola_kernel, dim3((T * d.HOP + fe::kThreads - 1) / fe::kThreads, B), dim3(fe::kThreads), 0, st,
                        a.frames, wav_in_dev, in_stride, a.cache_stft, a.cache_istft, wav_out_dev, out_stride, d.NFFT, d.HOP, T);
     return launch_rc(hipGetLastError());
+}
+
+// fe_step_streams_chunk: the packet step with each stream's hops on the time pipeline.  work_dev: frame counters | windowed frames
+// [n][T_max][N].  Built for the models whose frames exchange the GRU state only (default, ln, dprnn): the ring variants' ring_in_kernel /
+// ring_out_kernel are not slotted, so time_kernel and dptransformer take the packet step itself, like every call the pipeline cannot take.
+static bool streams_chunk_family(const fe_handle* h) { return chunk_family(h) && h->d.KT == 1 && !h->d.TA && h->impl->launch_streams_pipe != nullptr; }
+
+size_t fe_step_streams_chunk_work_floats(const fe_handle* h, int n, int T_max) {
+    if (!h || n <= 0 || T_max < 4 || !streams_chunk_family(h)) return 0;
+    return round4((size_t)n * pipe_counters(h)) + (size_t)n * T_max * h->d.NFFT;
+}
+
+// workgroups per call stream of fe_step_streams_chunk's pipelined launch (0: the packet step's own launch).  Any hop count 0 .. T_max is
+// served on the pipeline - the host cannot see the descriptors - so there is no T H >= N - H condition here: stream_ola_streams_kernel
+// orders its cache reads before its cache writes instead.
+static int streams_chunk_pipe_width(const fe_handle* h, int n, int T_max) {
+    if (n <= 0 || !streams_chunk_family(h)) return 0;
+    return pipe_width(h, n, T_max);
+}
+
+// own: the packet step's fields as step_streams has set them; wav_in / wav_out: device views.  A linear chain on the caller's stream - the
+// counters' zeroing (stft_kernels.hip.h: a kernel, not a memset node), the cooperative frame kernel, the audio kernel - that allocates nothing
+// (ensure_scratch allocated at fe_load_weights).
+// *refused: the runtime refused the cooperative launch; only the counters have been written.
+static int launch_streams_chunk(fe_handle* h, const fe::StreamFrameArgs& own, const float* wav_in, float* state, float* wav_out, int n, int T_max, int P,
+                                float* work_dev, void* stream, bool* refused) {
+    *refused = false;
+    int rc = ensure_scratch(h, n);
+    if (rc != FE_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    fe::StreamFrameArgs a = fe_step_args(h, own, wav_in, 0, state, wav_out, 0, n, T_max);
+    a.pipe_flags = reinterpret_cast<unsigned int*>(work_dev);
+    a.frames = work_dev + round4((size_t)n * pipe_counters(h));
+    a.pipe_p = P;
+    const int nflags = (int)((size_t)n * pipe_counters(h));
+    hipLaunchKernelGGL(fe::zero_counters_kernel, dim3((nflags + fe::kThreads - 1) / fe::kThreads), dim3(fe::kThreads), 0, st, a.pipe_flags, nflags);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return launch_rc(e);
+    if (h->impl->launch_streams_pipe(a, st) != hipSuccess) {
+        (void)hipGetLastError();
+        *refused = true;
+        return FE_OK;
+    }
+    h->last_shape = h->impl->name;
+    fe::note_kernel("stream_ola_streams_kernel");
+    hipLaunchKernelGGL(fe::stream_ola_streams_kernel, dim3(n), dim3(fe::kThreads), 0, st, a, h->d.NFFT, h->d.HOP);
+    return launch_rc(hipGetLastError());
+}
+
+int fe_step_streams_chunk(fe_handle* h, const void* wav_in_dev, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,
+                          void* wav_out_dev, size_t out_count, int n, int T_max, int format, const float* min_gain, fe_stream_levels* levels,
+                          const int* bank, float* work_dev, void* stream) {
+    return step_streams(h, "fe_step_streams_chunk", false, wav_in_dev, in_count, state_dev, capacity, desc_dev, wav_out_dev, out_count, n, T_max, format,
+                        stream, min_gain, levels, bank, true, work_dev);
+}
+
+int fe_step_streams_chunk_pinned(fe_handle* h, const void* wav_in_host, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,
+                                 void* wav_out_host, size_t out_count, int n, int T_max, int format, const float* min_gain, fe_stream_levels* levels,
+                                 const int* bank, float* work_dev, void* stream) {
+    return step_streams(h, "fe_step_streams_chunk_pinned", true, wav_in_host, in_count, state_dev, capacity, desc_dev, wav_out_host, out_count, n, T_max,
+                        format, stream, min_gain, levels, bank, true, work_dev);
 }
 
 // floats of the time-batched engine's work buffer: xc | skip | x | gx | hs | frames | spare, each a multiple of 4 floats

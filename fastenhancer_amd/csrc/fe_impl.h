@@ -37,6 +37,9 @@ struct Impl {
     const char* name = nullptr;      // the line of fe_shapes.def this record was compiled from (fe_shape.hip.in): part of fe_last_step_kernel's answer
     bool many_one_round = true;      // companion: used from the first stream above the shape's own plan (false: only beyond occ x #CUs streams, as persistent workgroups)
     int EP = 0;                      // Shape::EP: activation + 8 * mask (FE_ACT_* / FE_MASK_*); 0 = SiLU, no mask function
+    // the packet step's time-pipelined launch (fe_step_streams_chunk: a.pipe_p workgroups per call stream; cooperative, a refusal leaves no
+    // error behind and notes no kernel); nullptr for the shapes it is not built for (TATT, KT > 1, BIDIR, the low-LDS companions)
+    hipError_t (*launch_streams_pipe)(const StreamFrameArgs&, hipStream_t) = nullptr;
 };
 
 // What fe_last_step_kernel reports for the instantiation a launcher picked: the kernel's name, then in angle brackets and joined by ", " whichever
@@ -156,6 +159,18 @@ void launch_pipe_impl(const FrameArgs& a, hipStream_t st, hipError_t* err) {
     *err = launch_coop<&fe_frame_kernel<S, false, -1, false, true, true>>(name, dim3(a.B * a.pipe_p), dim3(kThreads), Lds<S>::BYTES, st, a);
 }
 
+// The packet step on the time pipeline (PIPE + SLOT + STRM; the BANK instantiation for a call with a bank table, as launch_one chooses).  The
+// name is the packet step's with "time-pipelined" for what it is: fe_frame_kernel<time-pipelined, streams[, pinned][, s16][, banks]>.
+template <class S>
+hipError_t launch_streams_pipe_impl(const StreamFrameArgs& a, hipStream_t st) {
+    static constexpr KernelNames names = kernel_names("fe_frame_kernel", S::LOW, "time-pipelined", "streams");
+    const char* name = names.s[(a.pinned != 0) + 2 * (a.format != 0) + 4 * (a.bank != nullptr)];
+    const dim3 grid(a.B * a.pipe_p), block(kThreads);
+    if (a.bank != nullptr)
+        return launch_coop<&fe_frame_kernel<S, false, FE_MODE_STREAM, false, true, true, true, false, true, true>, true>(name, grid, block, Lds<S>::BYTES, st, a);
+    return launch_coop<&fe_frame_kernel<S, false, FE_MODE_STREAM, false, true, true, true, false, true, false>, true>(name, grid, block, Lds<S>::BYTES, st, a);
+}
+
 template <class S>
 void dbg_stage_impl(int s, int* rows, int* cols, size_t* off) {
     *rows = DebugLayout<S>::rows(s);
@@ -185,6 +200,7 @@ Impl make_impl() {
             DebugLayout<S>::total(), DebugLayout<S>::n_stages, &Pack<S>::v, &launch_step_impl<S>, &launch_pipe_impl<S>, &dbg_stage_impl<S>};
     im.many_one_round = Lds<S>::MANY_ONE_ROUND;
     im.EP = S::EP;
+    if constexpr (!S::TATT && S::KT == 1 && S::LOW == 0) im.launch_streams_pipe = &launch_streams_pipe_impl<S>;
     return im;
     }
 }

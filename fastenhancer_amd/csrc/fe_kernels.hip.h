@@ -1639,10 +1639,19 @@ __device__ __forceinline__ void attention_head(const float* G, float* Hl, int ho
 // them with a table only: written without it, the persistent LOW = 2 instantiation of 48 kHz B at hop 480 computed wrong rows for the second
 // live stream of a workgroup's walk even with every stream on bank 0 (source-equivalent code; the cause was not found in its assembly), and
 // with the test it gives the bits of the instantiation without banks (tests/test_gpu_weight_banks.py, the cases above the CU count).
+// PIPE + SLOT + STRM (fe_step_streams_chunk[_pinned]; MODE = FE_MODE_STREAM, no HIO): the packet step's time-pipelined form.  Workgroup
+// blockIdx.x serves call stream b = blockIdx.x / pipe_p and the frames p, p + P, ... < hops of that stream's own stream_view - all P
+// workgroups of a stream read the same descriptor and derive the same view - at state slot (sv.slot, a.capacity): frame 0's GRU state is
+// the slot's, every frame leaves its state there through HO::st, the next one takes it through HO::ld.  Frame t's samples are chunk
+// positions t H + n - OVL: below 0 the slot's cache_stft, else stream_sample at the stream's in_off.  The bank is chosen once, in the
+// prologue.  Streams without a hop or without state compute nothing; zero rows, output rows, the two STFT caches and the level row are
+// stream_ola_streams_kernel's (stft_kernels.hip.h).  Not built for the TATT / KT > 1 / BIDIR shapes nor the low-LDS companions.
 template <class S, bool DBG, int MODE, bool T1, bool PERSIST, bool PIPE = false, bool SLOT = false, bool HIO = false, bool STRM = false, bool BANK = false>
 __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(Lds<S>::OCC, Lds<S>::OCC))) fe_frame_kernel(typename KernelArgs<SLOT, STRM>::type a_in) {
     static_assert(!HIO || (SLOT && !PIPE && !DBG), "host audio: slotted streaming instantiations only");
-    static_assert(!STRM || HIO, "packet audio: the host-audio instantiations only");
+    static_assert(!STRM || HIO || PIPE, "packet audio: the host-audio instantiations and the time-pipelined packet form only");
+    static_assert(!(PIPE && SLOT) || (STRM && MODE == FE_MODE_STREAM && PERSIST && !T1 && !S::TATT && S::KT == 1 && S::LOW == 0),
+                  "time-pipelined packet step: streaming mode, the shapes whose frames exchange the GRU state only");
     static_assert(!BANK || STRM, "weight banks: the packet-audio instantiations only");
     typename KernelArgs<SLOT, STRM>::type a = a_in;
 #ifdef FE_PROBE_HOT          // measurement builds: the production instantiations keep the cycle probes (tools/gpu_phases.py ... 1)
@@ -1673,7 +1682,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
     StreamView sv{-1, 0, 0, 0};                      // (STRM) the stream this workgroup is running
     // (STRM) hop tt of the stream with view v into hv - nothing is requested where the stream has no such hop
     auto hop_load = [&](const StreamView& v, int tt) {
-        if constexpr (STRM) {
+        if constexpr (STRM && !PIPE) {
             const bool ok = tt < v.hops;
             const long long x0 = ok ? v.in_off + (long long)tt * H - OVL : 0;
 #pragma unroll
@@ -1684,6 +1693,8 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
         }
     };
     auto hop_issue = [&](int bb, int tt) {
+        if constexpr (STRM && PIPE) { (void)bb; (void)tt; }       // (no hop is requested ahead: a frame fetches its own samples)
+        else
         if constexpr (STRM) hop_load(stream_view<H>(a, bb), tt);
         else
         if constexpr (HIO) {
@@ -1704,7 +1715,8 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
     int bank_staged = 0;
     if constexpr (BANK) {
         if (a.bank != nullptr) {
-            const int k0 = stream_bank<BANK>(a, stream_view<S::HOP>(a, (int)blockIdx.x));
+            // (PIPE: a workgroup serves one stream - this is its bank for good, chosen before the first weight request)
+            const int k0 = stream_bank<BANK>(a, stream_view<S::HOP>(a, PIPE ? (int)blockIdx.x / a.pipe_p : (int)blockIdx.x));
             bank_staged = k0 < 0 ? 0 : k0;
             wp = a.wp + (size_t)bank_staged * a.bank_stride;
         }
@@ -1791,7 +1803,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
     int sb = b;                                      // the stream's state slot
     int nst = a.B;                                   // streams the state is sized for
     if constexpr (SLOT) {
-        static_assert(!PIPE && !DBG, "slotted step: per-hop / generic streaming instantiations only");
+        static_assert((!PIPE || STRM) && !DBG, "slotted step: per-hop / generic streaming instantiations, and the time-pipelined packet form");
         if constexpr (STRM) {
             sv = stream_view<H>(a, b);
             sb = sv.slot;
@@ -1800,6 +1812,15 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
         nst = a.capacity;
         if constexpr (STRM) {
             const int bk = stream_bank<BANK>(a, sv);       // (!BANK: 0; -1: a bank out of range - the stream is one without state)
+            if constexpr (PIPE) {
+                // the time-pipelined form: a stream without a hop or without state computes nothing here (its zero rows are
+                // stream_ola_streams_kernel's), and a workgroup whose first frame lies beyond the stream's hops leaves without touching a counter
+                if (t_first >= sv.hops || (unsigned)sb >= (unsigned)nst || bk < 0) {
+                    __builtin_amdgcn_s_waitcnt(0);       // (the weight stage issued in the prologue has landed before the end)
+                    b += a.B;
+                    continue;
+                }
+            } else
             if (sv.hops == 0 || (unsigned)sb >= (unsigned)nst || bk < 0) {      // (wave-uniform) no hop: nothing; no state: its sv.hops output rows are zero
                 if (sv.hops) stream_zero_row(a.wav_out, a.format, sv.out_off, sv.hops * S::HOP, tid, kThreads);
                 __builtin_amdgcn_s_waitcnt(0);       // (the weight stage issued for this stream has landed before the next one or the end)
@@ -1813,7 +1834,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                 wp = a.wp + (size_t)bk * a.bank_stride;
                 wb.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wp), 0, o.total * 4, 0x00020000);
                 job.rsrc = wb.rsrc;
-                if constexpr (PERSIST && L::STAGED) {
+                if constexpr (PERSIST && !PIPE && L::STAGED) {      // (PIPE: the prologue staged this very stream's bank)
                     if (bk != bank_staged) {
                         // unit 0 was staged from the bank of the stream before (or of a skipped first stream's stand-in): fetch this bank's into
                         // the buffer frame fc consumes it from.  Nothing reads that buffer since the stage that filled it; the barrier orders
@@ -1976,12 +1997,14 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                 for (int q = 0; q < NPT; ++q) {
                     const int n = tid + q * kThreads;
                     if constexpr (HIO) fv[q] = (n < OVL) ? cst[n] : hv[q];          // (the hop was requested ahead: hop_issue)
+                    else if constexpr (PIPE && STRM)     // (the packet chunk: position t H + n - OVL of the stream's own range, int16 or float)
+                        fv[q] = (t * H + n < OVL) ? cst[t * H + n] : stream_sample(a.wav_in, a.format, sv.in_off + (long long)(t * H + n - OVL));
                     else if constexpr (PIPE) fv[q] = (t * H + n < OVL) ? cst[t * H + n] : xin[n - OVL];   // (fe_step_chunk: chunk sample t H + n - OVL; the
                                                                                                          //  cache is the call's own, no frame writes it)
                     else fv[q] = (n < OVL) ? cst[n] : xin[n - OVL];
                     fw[q] = win[n];
                 }
-                if constexpr (STRM) {
+                if constexpr (STRM && !PIPE) {           // (PIPE: the level row is stream_ola_streams_kernel's)
                     if (a.levels != nullptr) {           // (wave-uniform) the meters' input side: this hop's samples are the frame's n >= OVL
                         float ss = 0.0f, pk = 0.0f;
 #pragma unroll
@@ -1992,7 +2015,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                         ctl.lv.in_pk = wave_max(ctl.lv.in_pk, pk);
                     }
                 }
-                if constexpr (STRM) {                    // ... of this stream's own count; the next stream's first only if it has one
+                if constexpr (STRM && !PIPE) {           // ... of this stream's own count; the next stream's first only if it has one
                     if (t + 1 < t_end) hop_load(sv, t + 1);
                     else hop_issue(b + (int)gridDim.x, 0);
                 } else
@@ -3551,7 +3574,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
                     xo[n] = y[n].x * invN * ow[q] + oc[q];
                 }
             }
-            if constexpr (STRM) {
+            if constexpr (STRM && !PIPE) {
                 if (a.levels != nullptr) {               // (wave-uniform) the meters' output side: the frame's first H samples, as floats
                     float ss = 0.0f, pk = 0.0f;
 #pragma unroll
@@ -3599,12 +3622,12 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(L
             }
             if constexpr (!PIPE) { for (int m = tid; m < OVL; m += kThreads) cis[m] = xo[m + H]; }
             // (STRM) after the stream's last hop the waves' partials meet in the transposed-conv buffer, idle since the mask phase
-            if constexpr (STRM) { if (a.levels != nullptr && t + 1 == t_end) levels_put(PT, ctl.lv, wave, lane); }
+            if constexpr (STRM && !PIPE) { if (a.levels != nullptr && t + 1 == t_end) levels_put(PT, ctl.lv, wave, lane); }
             __syncthreads();
         }
         FE_CLK(13);
     }
-    if constexpr (STRM) { if (a.levels != nullptr && tid0 == 0) levels_store<kWaves>(a.levels + sb, smem + L::PT); }
+    if constexpr (STRM && !PIPE) { if (a.levels != nullptr && tid0 == 0) levels_store<kWaves>(a.levels + sb, smem + L::PT); }
     b += PIPE ? a.B : (int)gridDim.x;
     } while (PERSIST && b < a.B);
     FE_CLK(63);

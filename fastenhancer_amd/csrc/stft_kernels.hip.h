@@ -210,4 +210,119 @@ __global__ void __launch_bounds__(kThreads) stream_ola_kernel(const float* __res
     }
 }
 
+// stream_view (fe_kernels.hip.h) with the hop a run-time value: this file's kernels are not compiled per shape.  The same clamp and the same
+// bounds check, word for word - the frame kernel's workgroups and the audio kernel below must make the same stream of a descriptor.
+__device__ __forceinline__ StreamView stream_view_rt(const StreamFrameArgs& a, int b, int H) {
+    StreamView v{-1, 0, 0, 0};
+    if (b < a.B) {
+        const int* p = reinterpret_cast<const int*>(a.desc + b);
+        int w[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) w[i] = __builtin_amdgcn_readfirstlane(p[i]);
+        v.slot = w[0];
+        const int hops = w[1] < 0 ? 0 : (w[1] > a.T ? a.T : w[1]);
+        v.in_off = (long long)(((unsigned long long)(unsigned)w[3] << 32) | (unsigned)w[2]);
+        v.out_off = (long long)(((unsigned long long)(unsigned)w[5] << 32) | (unsigned)w[4]);
+        const unsigned long long len = (unsigned long long)hops * (unsigned long long)H;
+        const bool in_ok = v.in_off >= 0 && (unsigned long long)v.in_off <= a.in_count && a.in_count - (unsigned long long)v.in_off >= len;
+        const bool out_ok = v.out_off >= 0 && (unsigned long long)v.out_off <= a.out_count && a.out_count - (unsigned long long)v.out_off >= len;
+        v.hops = (in_ok && out_ok) ? hops : 0;
+    }
+    return v;
+}
+
+// The frame counters of fe_step_streams_chunk's pipelined launch, zeroed by a launch of their own ahead of it.  Not a memset: captured into
+// a graph, the memset node of n x counters words (36 bytes for three streams of FastEnhancer_B) left the counters of later replays unzeroed
+// or holding other values on the runtime this was developed on - the frames then ran ahead of their predecessors' state - while a kernel
+// node replays as it was captured.
+__global__ void __launch_bounds__(kThreads) zero_counters_kernel(unsigned int* __restrict__ flags, int n) {
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    if (i < n) flags[i] = 0u;
+}
+
+// The audio side of fe_step_streams_chunk after its time-pipelined launch: stream_ola_kernel for the packet step - every stream at its own hop
+// count T = hops, its own element offsets, float32 or int16, at its state slot.  One workgroup per call stream, looping over the stream's
+// T H + OVL overlap-add positions (OVL = N - H): position p is the old cache_istft[p] (p < OVL, else 0) plus frames[t][p - t H] of every
+// frame that covers p, added OLDEST FIRST as the hop-by-hop walk adds them; p < T H is output, the rest the new cache_istft; the new
+// cache_stft is the last OVL samples of [old cache_stft | the stream's T H input samples].  ANY T >= 1: with T H < OVL the new caches hold
+// shifted old cache values, so the workgroup loads both old caches into LDS, meets at a barrier and only then stores - every read of a
+// stream's old caches is ordered before every write of its new ones.  Output goes through the packet step's quantiser and row stores
+// (stream_store_row) in tiles of kOlaTile positions, a multiple of 16 bytes in either format, so every tile has the alignment of the first.
+// A stream without a hop (0 hops, or skipped by the bounds check) writes nothing; one without state (slot or bank out of range) gets zero
+// rows.  The level row: per-thread partials over the thread's own positions in a fixed order, the wave reductions of the frame kernels, the
+// waves' words through LDS, wave 0 first, one 16-byte store (levels_put / levels_store) - no atomics, the same bits on every run.
+// a: the frame kernel's argument block (a.frames [B][a.T][N], a.T = T_max).  wav_in and wav_out do not overlap.
+constexpr int kOlaTile = 4 * kThreads;
+__global__ void __launch_bounds__(kThreads) stream_ola_streams_kernel(StreamFrameArgs a, int N, int H) {
+    __shared__ float old_cis[1024], old_cst[1024], tile[kOlaTile], red[4 * kWaves];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const StreamView sv = stream_view_rt(a, b, H);
+    if (sv.hops == 0) return;                                   // (wave-uniform, as the two below)
+    const int sb = sv.slot;
+    if ((unsigned)sb >= (unsigned)a.capacity || stream_bank<true>(a, sv) < 0) {
+        stream_zero_row(a.wav_out, a.format, sv.out_off, sv.hops * H, tid, kThreads);
+        return;
+    }
+    const int OVL = N - H, T = sv.hops, n_out = T * H, total = n_out + OVL;
+    float* cis = a.cache_istft + (size_t)sb * OVL;
+    float* cst = a.cache_stft + (size_t)sb * OVL;
+    for (int m = tid; m < OVL; m += kThreads) { old_cis[m] = cis[m]; old_cst[m] = cst[m]; }
+    __syncthreads();
+    // the new cache_stft: chunk positions n_out - OVL + m, below 0 the old cache
+    for (int m = tid; m < OVL; m += kThreads) {
+        const int q = n_out - OVL + m;
+        cst[m] = q < 0 ? old_cst[q + OVL] : stream_sample(a.wav_in, a.format, sv.in_off + q);
+    }
+    const bool meters = a.levels != nullptr;
+    LevelAcc lv;
+    if (meters) {
+        float ss = 0.0f, pk = 0.0f;
+        for (int i = tid; i < n_out; i += kThreads) {
+            const float x = stream_sample(a.wav_in, a.format, sv.in_off + i);
+            ss += x * x;
+            pk = fmaxf(pk, fabsf(x));
+        }
+        lv.in_ss = wave_sum(0.0f, ss);
+        lv.in_pk = wave_max(0.0f, pk);
+    }
+    const float* fr = a.frames + (size_t)b * a.T * N;
+    // the sum at position q: frames ceil((q - N + 1) / H) .. min(q / H, T - 1) on top of `acc`
+    auto ola = [&](int q, float acc) {
+        int t_lo = (q - N + H) / H;
+        t_lo = t_lo < 0 ? 0 : t_lo;
+        int t_hi = q / H;
+        t_hi = t_hi > T - 1 ? T - 1 : t_hi;
+        for (int tt = t_lo; tt <= t_hi; ++tt) acc = fr[(size_t)tt * N + (q - tt * H)] + acc;
+        return acc;
+    };
+    float oss = 0.0f, opk = 0.0f;
+    for (int p0 = 0; p0 < total; p0 += kOlaTile) {              // (the trip count is the workgroup's: the barriers are uniform)
+#pragma unroll
+        for (int j = 0; j < kOlaTile / kThreads; ++j) {
+            const int p = p0 + tid + j * kThreads;
+            if (p < total) {
+                const float y = ola(p, p < OVL ? old_cis[p] : 0.0f);
+                if (p < n_out) {
+                    tile[p - p0] = y;
+                    oss += y * y;
+                    opk = fmaxf(opk, fabsf(y));
+                } else {
+                    cis[p - n_out] = y;
+                }
+            }
+        }
+        __syncthreads();
+        const int cnt = n_out - p0 < kOlaTile ? n_out - p0 : kOlaTile;
+        if (cnt > 0) stream_store_row(a.wav_out, a.format, sv.out_off + p0, tile, cnt, tid, kThreads);
+        __syncthreads();
+    }
+    if (meters) {
+        lv.out_ss = wave_sum(0.0f, oss);
+        lv.out_pk = wave_max(0.0f, opk);
+        levels_put(red, lv, tid >> 6, tid & 63);
+        __syncthreads();
+        if (tid == 0) levels_store<kWaves>(a.levels + sb, red);
+    }
+}
+
 }  // namespace fe

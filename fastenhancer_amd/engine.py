@@ -423,9 +423,12 @@ class Engine:
         return t
 
     def _step_streams(self, wav_in: Tensor, state: Tensor, capacity: int, desc, wav_out: Tensor, T_max: int, pinned: bool,
-                      min_gain: Optional[Tensor] = None, levels: Optional[Tensor] = None, bank: Optional[Tensor] = None) -> Tensor:
+                      min_gain: Optional[Tensor] = None, levels: Optional[Tensor] = None, bank: Optional[Tensor] = None, chunk: bool = False,
+                      work: Optional[Tensor] = None) -> Tensor:
         ctl = min_gain is not None or levels is not None
         name = "fe_step_streams" + ("_banked" if bank is not None else "_ctl" if ctl else "") + ("_pinned" if pinned else "")
+        if chunk:       # (one entry point, every table an argument that may be NULL)
+            name = "fe_step_streams_chunk" + ("_pinned" if pinned else "")
         for what, x in (("wav_in", wav_in), ("wav_out", wav_out)):
             if not isinstance(x, Tensor) or x.dtype not in (torch.float32, torch.int16) or not x.is_contiguous() or x.numel() == 0:
                 raise ValueError(f"{what} must be a contiguous, non-empty float32 or int16 tensor")
@@ -441,15 +444,37 @@ class Engine:
         min_gain = self._stream_table("min_gain", min_gain, (capacity,))
         levels = self._stream_table("levels", levels, (capacity, 4))
         bank = self._bank_table(bank, capacity)
+        if chunk and work is not None:
+            if not isinstance(work, Tensor) or work.dtype != torch.float32 or not work.is_contiguous():
+                raise ValueError("work must be a contiguous float32 tensor of streams_chunk_work_floats(n, T_max) floats")
+            # (the windowed frames [n][T_max][N] at least, where the model pipelines at all: known without the library)
+            n_desc = desc.shape[0] if isinstance(desc, Tensor) else len(desc)
+            c = self.cfg      # (the default, ln and dprnn models: the ring variants, the noncausal model and the baselines never pipeline this call)
+            pipelines = hasattr(c, "rf_blocks") and not getattr(c, "dpt", False) and getattr(c, "kernel_size_time", 1) == 1 and not getattr(c, "noncausal", False)
+            if T_max >= 4 and pipelines and work.numel() < n_desc * T_max * c.n_fft:
+                raise ValueError(f"work has {work.numel()} floats, {n_desc} streams of up to {T_max} hops need at least {n_desc * T_max * self.cfg.n_fft} "
+                                 "(streams_chunk_work_floats)")
         d = self._stream_desc_tensor(desc, capacity, T_max, wav_in.numel(), wav_out.numel())
         self._require_gpu()
         assert state.is_cuda and state.numel() == self.state_floats(capacity) and state.is_contiguous()
         fmt = _lib.FE_AUDIO_S16 if wav_in.dtype == torch.int16 else _lib.FE_AUDIO_F32
         tables = (_ptr(min_gain), _ptr(levels), _ptr(bank)) if bank is not None else (_ptr(min_gain), _ptr(levels)) if ctl else ()
+        if chunk:
+            need = self.streams_chunk_work_floats(d.shape[0], T_max)
+            if work is None:
+                if need > 0:        # (a scratch tensor kept on the engine, grown when needed; pass `work` inside a graph capture)
+                    if getattr(self, "_streams_chunk_work", None) is None or self._streams_chunk_work.numel() < need:
+                        self._streams_chunk_work = torch.empty(need, dtype=torch.float32, device=self.device)
+                    work = self._streams_chunk_work
+            elif not work.is_cuda:
+                raise ValueError("work must be a device tensor")
+            elif work.numel() < need:
+                raise ValueError(f"work has {work.numel()} floats, streams_chunk_work_floats({d.shape[0]}, {T_max}) is {need}")
+            tables = (_ptr(min_gain), _ptr(levels), _ptr(bank), _ptr(work))
         with torch.cuda.device(self.device):
             _lib.check(getattr(self.lib, name)(self._h, _ptr(wav_in), wav_in.numel(), _ptr(state), int(capacity), _ptr(d), _ptr(wav_out), wav_out.numel(),
                                                d.shape[0], int(T_max), fmt, *tables, _stream(self.device)), name)
-        self._desc_keep = (d, min_gain, levels, bank)    # (alive until the next call - the launch is asynchronous)
+        self._desc_keep = (d, min_gain, levels, bank, work)    # (alive until the next call - the launch is asynchronous)
         if pinned:
             self._pinned_keep = (wav_in, wav_out)
         return wav_out
@@ -472,6 +497,31 @@ class Engine:
         """fe_step_streams_pinned: step_streams with wav_in / wav_out in page-locked HOST memory, read and written by the kernel over PCIe.
         Asynchronous on the current stream: synchronise it before reading wav_out (or a pinned levels table) or rewriting wav_in."""
         return self._step_streams(wav_in, state, capacity, desc, wav_out, T_max, pinned=True, min_gain=min_gain, levels=levels, bank=bank)
+
+    # ---- the packet step on the time pipeline: streams that come back with a backlog (fe_step_streams_chunk[_pinned])
+    def streams_chunk_work_floats(self, n: int, T_max: int) -> int:
+        """fe_step_streams_chunk_work_floats: floats of scratch step_streams_chunk needs for at most n streams of at most T_max hops (0: none)."""
+        return int(self.lib.fe_step_streams_chunk_work_floats(self._h, int(n), int(T_max)))
+
+    def step_streams_chunk(self, wav_in: Tensor, state: Tensor, capacity: int, desc, wav_out: Tensor, T_max: int, *,
+                           min_gain: Optional[Tensor] = None, levels: Optional[Tensor] = None, bank: Optional[Tensor] = None,
+                           work: Optional[Tensor] = None) -> Tensor:
+        """fe_step_streams_chunk: step_streams(..., min_gain=, levels=, bank=) with the hops of EACH stream spread over the time pipeline - the
+        same descriptors, slots, formats, limit, meters and banks, in place on the capacity-sized state.  Results agree with step_streams to
+        fp32 rounding (cache_stft bit for bit); wav_in and wav_out must not overlap.  Where nothing is pipelined (T_max < 4, more than
+        #CUs / 2 streams, set_time_pipeline(0 | 1), the time_kernel / dptransformer models) the call is step_streams itself, bit for bit
+        (last_step_kernel() says which ran).  work: a float32 device tensor of at least streams_chunk_work_floats(n, T_max) floats (the form
+        for graph capture); None: a scratch tensor kept on the engine, grown when needed."""
+        return self._step_streams(wav_in, state, capacity, desc, wav_out, T_max, pinned=False, min_gain=min_gain, levels=levels, bank=bank,
+                                  chunk=True, work=work)
+
+    def step_streams_chunk_pinned(self, wav_in: Tensor, state: Tensor, capacity: int, desc, wav_out: Tensor, T_max: int, *,
+                                  min_gain: Optional[Tensor] = None, levels: Optional[Tensor] = None, bank: Optional[Tensor] = None,
+                                  work: Optional[Tensor] = None) -> Tensor:
+        """fe_step_streams_chunk_pinned: step_streams_chunk with wav_in / wav_out in page-locked HOST memory (the completion rule of
+        step_streams_pinned: synchronise the stream before reading wav_out or rewriting wav_in)."""
+        return self._step_streams(wav_in, state, capacity, desc, wav_out, T_max, pinned=True, min_gain=min_gain, levels=levels, bank=bank,
+                                  chunk=True, work=work)
 
     def new_pinned(self, *shape: int, dtype=torch.float32) -> Tensor:
         """a zeroed page-locked host tensor (the audio of the pinned steps)"""

@@ -216,12 +216,21 @@ class PacketPool(StreamPool):
     meters=True: every tick also meters each launched stream's input and output (levels()).  The level table lives in page-locked host
     memory - tick() synchronises anyway - and the table of suppression limits, made by the first set_suppression_limit(), on the device;
     a pool with neither launches plain fe_step_streams_pinned.  The table of weight banks, made by the first open(bank=) / set_bank() that
-    names a bank other than 0, lives on the device too; a pool that never names one launches what it launched without banks."""
+    names a bank other than 0, lives on the device too; a pool that never names one launches what it launched without banks.
+    backlog_hops = K >= 4: a stream that holds more than T_max complete hops (up to its ring end) - one that comes back after a stall -
+    is taken out of the tick's ordinary launch and served, up to K hops a tick, by a second launch on the time pipeline
+    (Engine.step_streams_chunk_pinned: same slot, bank, limit and meters), so the other streams' launch stays T_max hops long.  0 (the
+    default): one launch, as ever."""
 
-    def __init__(self, engine: Engine, capacity: int, ring_hops: int, T_max: int = 1, meters: bool = False):
+    def __init__(self, engine: Engine, capacity: int, ring_hops: int, T_max: int = 1, meters: bool = False, backlog_hops: int = 0):
         super().__init__(engine, capacity)
         if ring_hops < 1 or T_max < 1:
             raise ValueError("ring_hops and T_max must be at least 1")
+        backlog_hops = operator.index(backlog_hops)
+        if backlog_hops != 0 and (backlog_hops < 4 or backlog_hops <= T_max):
+            raise ValueError("backlog_hops is 0 (off) or at least 4 hops (what the time pipeline takes) and more than T_max")
+        self.backlog_hops = backlog_hops
+        self._backlog_work: Optional[Tensor] = None        # the chunk launch's scratch, made once for (capacity, backlog_hops)
         self._gain: Optional[Tensor] = None                # [capacity] linear least gain per slot, 0 = off
         self._bank: Optional[Tensor] = None                # [capacity] int32 weight bank per slot (None: every stream on bank 0)
         self._levels: Optional[Tensor] = engine.new_pinned(self.capacity, 4) if meters else None
@@ -262,6 +271,20 @@ class PacketPool(StreamPool):
             self._reset_ctl(slot)
             self._set_bank(slot, 0)
         return slots
+
+    def catch_up(self, slot: int, wav_in: Tensor, T: Optional[int] = None) -> Tensor:
+        """StreamPool.catch_up for a stream on bank 0 without a suppression limit (it takes float audio past the rings, leaves the
+        counters and the level row alone, and runs on bank 0 without a limit: Engine.step_chunk knows neither).  A stream on another bank or
+        with a limit is refused - its audio would be enhanced by another checkpoint, or unlimited: serve its backlog through the rings with
+        PacketPool(..., backlog_hops=K)."""
+        self._check_open(slot)
+        if self._bank is not None and int(self._bank[slot]) != 0:
+            raise ValueError(f"slot {slot} runs on weight bank {int(self._bank[slot])} and catch_up on bank 0: push the backlog and let tick() serve it "
+                             "(PacketPool(..., backlog_hops=K))")
+        if self._get_gain(slot) != 0.0:
+            raise ValueError(f"slot {slot} has a suppression limit, which catch_up does not apply: push the backlog and let tick() serve it "
+                             "(PacketPool(..., backlog_hops=K))")
+        return super().catch_up(slot, wav_in, T)
 
     # ---- weight banks: streams of one pool on different checkpoints (fe_step_streams_banked_pinned)
     @staticmethod
@@ -363,6 +386,7 @@ class PacketPool(StreamPool):
         super().resize(capacity)
         if self.capacity == old:
             return
+        self._backlog_work = None                           # (sized for the capacity: made again by the next backlog tick)
         keep = min(old, self.capacity)
         rings = []
         for ring in (self.ring_in, self.ring_out):
@@ -409,21 +433,33 @@ class PacketPool(StreamPool):
 
     def tick(self) -> List[Tuple[int, int, int, int]]:
         """One launch for every open stream with at least one complete hop: each advances min(complete hops, hops up to the ring end,
-        T_max); the rest waits for the next tick.  Waits for the launch (the rings are host memory the caller reads next).  Returns the
-        descriptors (slot, hops, in_offset, out_offset) it launched - [] when no stream had a hop, and then nothing is launched."""
-        desc = []
+        T_max); the rest waits for the next tick.  With backlog_hops = K, a stream whose complete hops up to the ring end exceed T_max
+        advances min(complete hops, hops up to the ring end, K) in a second launch on the same stream, on the time pipeline.  Waits once,
+        for both (the rings are host memory the caller reads next).  Returns the descriptors (slot, hops, in_offset, out_offset) it
+        launched, the ordinary launch's first - [] when no stream had a hop, and then nothing is launched."""
+        desc, backlog = [], []
         for slot in sorted(self._open):
             pos = self._stepped[slot] % self.ring
-            hops = min((self._pushed[slot] - self._stepped[slot]) // self.H, (self.ring - pos) // self.H, self.T_max)
-            if hops > 0:
-                off = slot * self.ring + pos
-                desc.append((slot, hops, off, off))
-        if not desc:
+            ready = min((self._pushed[slot] - self._stepped[slot]) // self.H, (self.ring - pos) // self.H)
+            off = slot * self.ring + pos
+            if self.backlog_hops and ready > self.T_max:
+                backlog.append((slot, min(ready, self.backlog_hops), off, off))
+            elif ready > 0:
+                desc.append((slot, min(ready, self.T_max), off, off))
+        if not desc and not backlog:
             return desc
         ctl = {} if self._gain is None and self._levels is None else dict(min_gain=self._gain, levels=self._levels)
         if self._bank is not None:
             ctl["bank"] = self._bank
-        self.engine.step_streams_pinned(self.ring_in, self.state, self.capacity, desc, self.ring_out, T_max=self.T_max, **ctl)
+        if desc:
+            self.engine.step_streams_pinned(self.ring_in, self.state, self.capacity, desc, self.ring_out, T_max=self.T_max, **ctl)
+        if backlog:
+            if self._backlog_work is None:
+                need = self.engine.streams_chunk_work_floats(self.capacity, self.backlog_hops)
+                self._backlog_work = torch.empty(max(need, 1), dtype=torch.float32, device=getattr(self.engine, "device", None))
+            self.engine.step_streams_chunk_pinned(self.ring_in, self.state, self.capacity, backlog, self.ring_out, T_max=self.backlog_hops,
+                                                  min_gain=self._gain, levels=self._levels, bank=self._bank, work=self._backlog_work)
+            desc = desc + backlog
         self.engine.synchronize()
         for slot, hops, _, _ in desc:
             self._stepped[slot] += hops * self.H

@@ -369,6 +369,39 @@ size_t fe_step_chunk_work_floats(const fe_handle* h, int B, int T);
 int fe_step_chunk(fe_handle* h, const float* wav_in_dev, size_t in_stride, float* state_dev, float* wav_out_dev, size_t out_stride,
                   int B, int T, float* work_dev, void* stream);
 
+/* The packet step's time-pipelined form - a stream of a packet batch that comes back with a backlog: fe_step_streams_banked[_pinned] with the
+ * hops of EACH stream spread over co-resident workgroups instead of walked by one.  Same descriptors, slots, formats, limit, meters and banks,
+ * in place on the capacity-sized state buffer.
+ *   Meaning: for every stream of the call, what fe_step_streams_banked[_pinned] gives for the same arguments.  Unchanged: the kernel reads the
+ *     descriptors when it runs; hops is clamped to [0, T_max]; a stream whose input or output range leaves [0, count) is skipped like a 0-hop
+ *     stream (checked in the kernel, on both sides); a slot outside [0, capacity) or a bank outside [0, n_banks) gives zero output rows, no
+ *     state write and no level row; min_gain, levels and bank may each be NULL; FE_ERR_NO_WEIGHTS unless every bank is loaded when
+ *     bank != NULL; the int16 conversion rules; the host checks, all before any device work.  BSRNN, FSPEN, LiSenNet and the noncausal model
+ *     are refused as fe_step_streams refuses them.
+ *   Results: output samples and every state tensor of the named slots agree with the serial packet step to fp32 rounding (the frames' sums
+ *     are formed in another order); cache_stft, a copy of input samples, bit for bit; every float of state_dev that belongs to a slot the
+ *     call does not advance is left bit for bit.  Level rows: in_peak is exact, the other three words agree to rounding; a row is formed
+ *     without atomics in a fixed order - bitwise reproducible from run to run at a fixed pipeline width.
+ *   Any hop count 0 .. T_max of a stream is served on the pipeline (the host cannot see the descriptors), 1, 2, 3 hops and
+ *     hops * H < N - H included: the audio kernel orders every read of a stream's old STFT caches before every write of its new ones.
+ *   wav_in and wav_out MUST NOT overlap, as for fe_step_chunk.
+ *   work_dev: fe_step_streams_chunk_work_floats(h, n, T_max) floats - frame counters and the windowed frames [n][T_max][N].  The size depends on
+ *     the model, n and T_max only and is monotone in both.  0 where the call never pipelines (T_max < 4, the ring variants, the baseline
+ *     families, a null handle): work_dev may then be NULL.  The call allocates nothing and may be captured into a graph: a linear chain of
+ *     three kernels (the counters are zeroed by a small kernel: a captured memset node of their odd byte count did not replay reliably).
+ *   It does not pipeline - and then IS fe_step_streams_banked[_pinned] with the same arguments, bit for bit, which fe_last_step_kernel shows -
+ *     when the pipeline's width is 0 (T_max < 4, 2 n > #CUs, fe_set_time_pipeline(0 or 1)); for the ring variants (time_kernel,
+ *     dptransformer: the kernels that move their rings are not slotted); when the runtime refuses the cooperative launch.
+ *   fe_last_step_kernel on the pipelined path: "fe_frame_kernel<time-pipelined, streams[, pinned][, s16][, banks]> + stream_ola_streams_kernel"
+ *     (the counters' zeroing is not named). */
+size_t fe_step_streams_chunk_work_floats(const fe_handle* h, int n, int T_max);
+int fe_step_streams_chunk(fe_handle* h, const void* wav_in_dev, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,
+                          void* wav_out_dev, size_t out_count, int n, int T_max, int format, const float* min_gain, fe_stream_levels* levels,
+                          const int* bank, float* work_dev, void* stream);
+int fe_step_streams_chunk_pinned(fe_handle* h, const void* wav_in_host, size_t in_count, float* state_dev, int capacity,
+                                 const fe_stream_desc* desc_dev, void* wav_out_host, size_t out_count, int n, int T_max, int format,
+                                 const float* min_gain, fe_stream_levels* levels, const int* bank, float* work_dev, void* stream);
+
 /* Engine of fe_offline for the default and noncausal FastEnhancer models:
  *   FE_OFFLINE_TIME_BATCHED (the default where compiled; the only engine of the noncausal model): the network is cut at the
  *     blocks' time GRUs and every piece runs over ALL frames of ALL utterances, layer by layer, as the reference's own offline

@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """tools/compare_device_code.sh, function by function: which gfx950 functions of two builds differ?  (no GPU needed)
-   python tools/compare_device_code_per_kernel.py <parent csrc/_obj> <changed csrc/_obj> [--allow REGEX] [--removed REGEX] [--kernarg REGEX] > profiles/<name>_device_code.txt
+   python tools/compare_device_code_per_kernel.py <parent csrc/_obj> <changed csrc/_obj> [--allow REGEX] [--removed REGEX] [--added REGEX] [--kernarg REGEX] > profiles/<name>_device_code.txt
 For every *.o of both directories the gfx950 code object is unbundled and split into its functions; of each function the disassembly
 (without addresses and encodings) and the kernel's note metadata (registers, spills, LDS, scratch, kernarg layout) are compared.
 --allow: a regular expression on the name (demangled where a demangler is installed, and mangled) of the functions that are meant to change; any other difference is an error (exit
 status 1).  A change that is confined to some instantiations of a kernel template reports every other function as identical.
 --removed: the functions that are meant to disappear (in the parent only); without it a function of one build only is an error.
+--added: the functions that are meant to be new (in the changed build only): listed with their resource figures.
 --kernarg: the functions whose argument block is meant to change and nothing else: their disassembly and every note field but the kernarg
 layout (.kernarg_segment_size, the .args list) must be identical.  One thing in the code follows the layout: the hidden arguments (grid size,
 ...) lie behind the explicit ones, so a kernel that reads one addresses it through an immediate that moves with the block's size.  Such a line
@@ -50,7 +51,13 @@ def functions(obj, tmp):
     for block in re.split(r"\n(?=\s*- \.agpr_count|\s*- \.args)", run(f"{LLVM}/llvm-readelf", "--notes", co)):
         m = re.search(r"\.name:\s+(\S+)", block)
         if m:
-            notes[m.group(1)] = re.sub(r"\.(symbol|name):\s+\S+", "", block)
+            # (the list's last block runs on into the note's footer - amdhsa.target, amdhsa.version - which is no kernel's)
+            notes[m.group(1)] = re.sub(r"\.(symbol|name):\s+\S+", "", re.split(r"\n\s*amdhsa\.target:", block)[0])
+    # (the padding between one function's end and the next one's alignment - "..." and blank lines - belongs to neither: a function
+    #  added behind another one must not make that one look changed)
+    for v in code.values():
+        while v and v[-1].strip() in ("", "..."):
+            v.pop()
     return {k: ("\n".join(v), notes.get(k, "")) for k, v in code.items()}
 
 
@@ -107,12 +114,13 @@ def main():
     ap.add_argument("changed")
     ap.add_argument("--allow", default=None)
     ap.add_argument("--removed", default=None)
+    ap.add_argument("--added", default=None)
     ap.add_argument("--kernarg", default=None)
     args = ap.parse_args()
-    allow, removed, kernarg = (re.compile(r) if r else None for r in (args.allow, args.removed, args.kernarg))
+    allow, removed, kernarg, added = (re.compile(r) if r else None for r in (args.allow, args.removed, args.kernarg, args.added))
     hit = lambda rx, dem, k: rx is not None and (rx.search(dem) or rx.search(k)) is not None
     names = sorted(set(f for d in (args.parent, args.changed) for f in os.listdir(d) if f.endswith(".o")))
-    bad = total = same = allowed = gone = args_only = 0
+    bad = total = same = allowed = gone = args_only = new = 0
     print(f"{'object':<30} {'functions':>9} {'identical':>9} {'changed':>8}")
     with tempfile.TemporaryDirectory() as tmp:
         for n in names:
@@ -134,6 +142,11 @@ def main():
                     gone += 1
                     print(f"    removed (meant to): {dem}")
                     continue
+                if k in fb and k not in fa and hit(added, dem, k):
+                    new += 1
+                    print(f"    added (meant to): {dem}")
+                    print(f"        change: {figures(fb[k][1])}, {fb[k][0].count(chr(10)) + 1} lines")
+                    continue
                 moved = kernarg_offset_lines(fa[k], fb[k]) if k in fa and k in fb and hit(kernarg, dem, k) else None
                 if moved is not None and without_kernarg(fa[k][1]) == without_kernarg(fb[k][1]):
                     args_only += 1
@@ -149,7 +162,7 @@ def main():
                         print(f"        {side}: {figures(f[k][1])}, {f[k][0].count(chr(10)) + 1} lines")
     print()
     print(f"{total} functions: {same} identical in code and notes, {args_only} with another kernarg layout only, {allowed} changed as meant to, "
-          f"{gone} removed as meant to, {bad} other differences")
+          f"{gone} removed as meant to, {new} added as meant to, {bad} other differences")
     sys.exit(1 if bad else 0)
 
 
