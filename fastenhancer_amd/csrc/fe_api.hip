@@ -687,6 +687,9 @@ struct StateRegion {
 };
 constexpr int kMaxStateRegions = 12;      // (LiSenNet: the two STFT caches + nine model caches)
 
+// frames in flight per stream that the rings of every time pipeline's work buffer are sized for (fe_set_time_pipeline clamps to it)
+constexpr int kMaxPipeFrames = 64;
+
 // the baseline families' host sides (weight sections, handle creation, packers, launches, the traits the paths below take): one file each
 #include "fe_api_bsrnn.inc"
 #include "fe_api_fspen.inc"
@@ -814,12 +817,45 @@ static int ola(fe_handle* h, const float* frames, float* wav_out, size_t out_str
     return launch_rc(e);
 }
 
-// A baseline family's fe_offline work buffer: overlap-add tail | model state | time-pipeline frame counters (these three zeroed by
-// fe_offline) | windowed frames [B][T][N] | the family's ring (Family::ring_floats).  fe_offline_work_floats sizes it for the time-pipelined
-// launch whatever fe_set_time_pipeline says at the time of that call.
+// The work buffers of the time pipeline: like state_layout() for the streaming state, one function lays each buffer out, and both its
+// *_work_floats query and its entry point call it.  The pipeline's own region, in floats from its start: frame counters [rows][counters]
+// (at 0; rounded up to 4 floats) | windowed frames [rows][T][N] | the rings of the frames in flight (ring_floats; 0 for variants without).
+struct PipeLayout { size_t frames, ring, total; };
+static PipeLayout pipe_layout(const fe_handle* h, size_t rows, int T, size_t counters, size_t ring_floats) {
+    const size_t frames = round4(rows * counters), ring = frames + rows * T * h->d.NFFT;
+    return {frames, ring, ring + ring_floats};
+}
+
+// fe_offline on the frame walk: overlap-add tail [B][N-H] (at 0) | the model's state (state_floats) | the pipeline's region p.  The call
+// zeroes the first `pipe` floats for the serial walk, pipe + p.frames - the counters too - for the pipelined launch.
+struct OfflineLayout { size_t state, pipe; PipeLayout p; size_t total; };
+static OfflineLayout offline_layout(const fe_handle* h, int B, int T, size_t state_floats, size_t counters, size_t ring_floats) {
+    const size_t state = (size_t)B * (h->d.NFFT - h->d.HOP), pipe = state + state_floats;
+    const PipeLayout p = pipe_layout(h, B, T, counters, ring_floats);
+    return {state, pipe, p, pipe + p.total};
+}
+
+// The pipelined form of a launch: a COPY of the serial walk's argument block, pointed at the pipeline's region.  The caller keeps its own
+// block and, where the runtime refuses the cooperative launch, walks with it as it is.
+template <class Args>
+Args pipe_args(Args a, float* region, const PipeLayout& L, int P) {
+    a.pipe_flags = reinterpret_cast<unsigned int*>(region);
+    a.frames = region + L.frames;
+    a.pipe_p = P;
+    return a;
+}
+
+// a cooperative launch the runtime refused (no co-residency: GPU shared with other work) leaves its error behind: cleared here
+static bool coop_refused(hipError_t e) {
+    if (e != hipSuccess) (void)hipGetLastError();
+    return e != hipSuccess;
+}
+
+// A baseline family's fe_offline work buffer (the state rounded up to 4 floats; the ring is Family::ring_floats per utterance).
+// fe_offline_work_floats sizes it for the time-pipelined launch whatever fe_set_time_pipeline says at the time of that call.
 template <class Fam>
-size_t baseline_zeroed_floats(Fam, const fe_handle* h, int B) {
-    return (size_t)B * (size_t)(h->d.NFFT - h->d.HOP) + round4(Fam::state_floats(h, B)) + round4((size_t)B * Fam::counters(h));
+OfflineLayout baseline_layout(Fam, const fe_handle* h, int B, int T) {
+    return offline_layout(h, B, T, round4(Fam::state_floats(h, B)), Fam::counters(h), (size_t)B * Fam::ring_floats(h));
 }
 
 // frames in flight per utterance of a baseline family's time-pipelined offline launch (0: one workgroup walks the frames of an utterance)
@@ -837,7 +873,8 @@ template <class Fam>
 int baseline_offline(Fam, fe_handle* h, const float* noisy_dev, int B, int Tw, float* wav_hat_dev, float* spec_hat_dev, float* work_dev, hipStream_t st) {
     const Dims& d = h->d;
     const int T = 1 + Tw / d.HOP;
-    FE_HIP_CHECK(hipMemsetAsync(work_dev, 0, baseline_zeroed_floats(Fam{}, h, B) * sizeof(float), st));
+    const OfflineLayout L = baseline_layout(Fam{}, h, B, T);
+    FE_HIP_CHECK(hipMemsetAsync(work_dev, 0, (L.pipe + L.p.frames) * sizeof(float), st));      // (the counters too, whichever launch follows)
     typename Fam::Args a = Fam::args(h, B, T);
     a.mode = fe::FE_MODE_OFFLINE;
     a.Tw = Tw;
@@ -845,21 +882,16 @@ int baseline_offline(Fam, fe_handle* h, const float* noisy_dev, int B, int Tw, f
     a.wav_out = wav_hat_dev; a.out_stride = (size_t)d.HOP * (T - 1);
     a.spec_out = spec_hat_dev;
     a.cache_istft = work_dev; a.cache_stft = work_dev;
-    Fam::state(a) = work_dev + (size_t)B * (d.NFFT - d.HOP);
+    Fam::state(a) = work_dev + L.state;
     if (const int P = baseline_pipe_width(Fam{}, h, B, T)) {
         // the frames of an utterance over P co-resident workgroups (the family's PIPE kernel); refused co-residency: the serial walk
         const int rc = ensure_tables(h, st);
         if (rc != FE_OK) return rc;
-        float* flags = Fam::state(a) + round4(Fam::state_floats(h, B));
-        a.pipe_flags = reinterpret_cast<unsigned int*>(flags);
-        a.frames = flags + round4((size_t)B * Fam::counters(h));
-        Fam::set_ring(a, a.frames + (size_t)B * T * d.NFFT);
-        a.pipe_p = P;
+        typename Fam::Args p = pipe_args(a, work_dev + L.pipe, L.p, P);
+        Fam::set_ring(p, work_dev + L.pipe + L.p.ring);
         hipError_t e = hipSuccess;
-        Fam::impl(h)->launch_pipe(a, st, &e);
-        if (e == hipSuccess) return ola(h, a.frames, wav_hat_dev, (size_t)d.HOP * (T - 1), B, T, st);
-        (void)hipGetLastError();
-        a.pipe_flags = nullptr; a.frames = nullptr; Fam::set_ring(a, nullptr); a.pipe_p = 0;
+        Fam::impl(h)->launch_pipe(p, st, &e);
+        if (!coop_refused(e)) return ola(h, p.frames, wav_hat_dev, a.out_stride, B, T, st);
     }
     return Fam::launch(h, a, st);
 }
@@ -1714,15 +1746,11 @@ int fe_profile_step(fe_handle* h, const float* wav_in_dev, size_t in_stride, flo
     return run_step(h, wav_in_dev, in_stride, state_dev, wav_out_dev, out_stride, B, T, nullptr, clk_dev, stream);
 }
 
-constexpr int kMaxPipeFrames = 64;      // frames in flight per stream the work-buffer rings are sized for
-
-// workgroups per stream of a time-pipelined launch (0: one workgroup walks the frames of a stream)
-static int pipe_width(const fe_handle* h, int B, int T, bool offline = false, bool spec_rings = false) {
+// workgroups per stream of a time-pipelined launch (0: one workgroup walks the frames of a stream).  The ring variants (time_kernel: its
+// convs' inputs, dptransformer: K / V, handed from frame to frame through rings) pipeline wherever their caller supplies the rings, and
+// every caller does: fe_offline and fe_step_chunk in their work buffers, fe_spec_step in the handle's (r4v); the packet chunk never asks.
+static int pipe_width(const fe_handle* h, int B, int T) {
     if (!h->impl || h->pipe_frames == 0 || h->pipe_frames == 1 || T < 4 || 2 * B > h->max_wgs) return 0;
-    // (time_kernel variant: its convs' inputs are handed from frame to frame through rings - in fe_offline's work buffer, or (r4v) the handle's
-    //  for a spec -> spec step with caches)
-    if (h->d.KT > 1 && !offline && !spec_rings) return 0;
-    if (h->d.TA && !offline && !spec_rings) return 0;   // (dptransformer: per-frame K / V rings - fe_offline's work buffer, or the handle's for fe_spec_step, r4v)
     // automatic width: a hand-off (counter round trip + state fetch + the h half of the GRU + gates + publish) takes
     // ~2.6 us whatever the model; a frame takes ~4 us per MFLOP/frame at the measured kernel efficiency: that many frames
     // are worth having in flight (measured optimum: T 8-12, B 16, 48 kHz B 24, L > 24), more only adds pollers
@@ -1730,7 +1758,7 @@ static int pipe_width(const fe_handle* h, int B, int T, bool offline = false, bo
     if (want < 0) {
         want = (int)(fe_flops_per_frame(h) / 6.0e5) + 2;
         if (h->d.TA) want *= 2;     // (dptransformer: a frame spends half its time streaming its K / V window - measured 16 -> 32 in flight: 1.37 -> 0.73 ms)
-        want = want < 8 ? 8 : (want > 64 ? 64 : want);
+        want = want < 8 ? 8 : (want > kMaxPipeFrames ? kMaxPipeFrames : want);
     }
     int p = h->max_wgs / B;
     p = p < want ? p : want;
@@ -1749,22 +1777,43 @@ static size_t pipe_ring_floats(const fe_handle* h, int B, int P) {
     return 0;
 }
 
+// FastEnhancer's pipeline region, the rings at the widest pipeline: the work buffer of fe_step_chunk and of fe_step_streams_chunk (whose
+// models have no rings).  The size depends on the model, rows and T only - not on fe_set_time_pipeline nor on the device's CUs - so that
+// it is monotone in both and a buffer sized once serves every setting.
+static PipeLayout fe_pipe_layout(const fe_handle* h, int rows, int T) {
+    return pipe_layout(h, rows, T, pipe_counters(h), pipe_ring_floats(h, rows, kMaxPipeFrames));
+}
+
+// FastEnhancer's fe_offline on the frame walk: the state is h (GRU states or K / V caches) | tk (the time_kernel conv caches), not rounded
+static OfflineLayout fe_walk_layout(const fe_handle* h, int B, int T) {
+    return offline_layout(h, B, T, (size_t)B * (h->d.hstate() + tk_floats(h)), pipe_counters(h), pipe_ring_floats(h, B, kMaxPipeFrames));
+}
+
+// The time-batched engine's work buffer, each region a multiple of 4 floats.  (`spare` held the GRU state carried between time chunks;
+// nothing writes it any more - it stays in the total so that the sizes callers were given stay what they are.)
+struct TbLayout { size_t xc, skip, x, gx, hs, frames, spare, total; };
+static TbLayout tb_layout(const fe_handle* h, int B, int T) {
+    const Dims& d = h->d;
+    const size_t NF = (size_t)B * T, nd = d.BD ? 2 : 1;
+    size_t cur = 0;
+    auto region = [&](size_t floats) { const size_t at = cur; cur += round4(floats); return at; };
+    return {region(NF * 2 * d.F0), region(NF * (d.NL + 1) * d.F1 * d.C1), region(NF * d.F2 * d.C2), region(nd * NF * d.F2 * 3 * d.C2),
+            region(NF * d.F2 * nd * d.C2), region(NF * d.NFFT), region((size_t)d.KB * nd * B * d.F2 * d.C2), cur};      // (in this order)
+}
+
 // The time-pipelined launch of a chunk that starts from the caller's model caches and leaves the new ones - fe_spec_step and fe_step_chunk.
-// a: the launch as the serial walk makes it (a.h / a.tk point into h_dev, the model caches of B streams in C ABI order); P: pipe_width's
-// answer; flags: pipe_counters() x B counters, zeroed here; ring: pipe_ring_floats(h, B, P) floats.  The GRU states are read from and
-// written to h_dev by the kernel itself.  dptransformer / time_kernel (r4v): the frames of a chunk in flight exchange their k / v (their
-// convs' inputs) through rings of L + P slots; the caller's caches go in before the launch and the chunk's last L frames come back after
-// it (ring_in_kernel / ring_out_kernel above).  *refused: the runtime refused the cooperative launch and nothing has been written that
-// the serial walk of the caller's own `a` does not overwrite or ignore.
-static int launch_pipe_carried(fe_handle* h, fe::StreamFrameArgs a, float* h_dev, int B, int T, int P, unsigned int* flags, float* ring,
-                               hipStream_t st, bool* refused) {
+// a: the serial walk's launch (a.h / a.tk point into h_dev, the model caches of B streams in C ABI order) with the pipeline's fields set -
+// a.pipe_p: pipe_width's answer; a.pipe_flags: pipe_counters() x B counters, zeroed here; ring: pipe_ring_floats(h, B, a.pipe_p) floats.
+// The GRU states are read from and written to h_dev by the kernel itself.  dptransformer / time_kernel (r4v): the frames of a chunk in
+// flight exchange their k / v (their convs' inputs) through rings of L + P slots; the caller's caches go in before the launch and the
+// chunk's last L frames come back after it (ring_in_kernel / ring_out_kernel above).  *refused: the runtime refused the cooperative
+// launch and nothing has been written that the serial walk of the caller's own block does not overwrite or ignore.
+static int launch_pipe_carried(fe_handle* h, fe::StreamFrameArgs a, float* h_dev, int B, int T, float* ring, hipStream_t st, bool* refused) {
     const Dims& d = h->d;
     *refused = false;
-    FE_HIP_CHECK(hipMemsetAsync(flags, 0, (size_t)B * pipe_counters(h) * sizeof(unsigned int), st));
-    a.pipe_flags = flags;
-    a.pipe_p = P;
+    FE_HIP_CHECK(hipMemsetAsync(a.pipe_flags, 0, (size_t)B * pipe_counters(h) * sizeof(unsigned int), st));
     const bool rings = d.TA != 0 || d.KT > 1;
-    const int L = d.TA ? d.TA : d.KT - 1, RS = L + P;
+    const int L = d.TA ? d.TA : d.KT - 1, RS = L + a.pipe_p;
     const int PAIRS = d.TA ? d.F2 * 4 : 1, SZ = d.TA ? d.C2 / 4 : d.F1 * d.C1;
     const size_t rows = (size_t)(d.TA ? 2 * d.KB : 2 * d.NL) * B * PAIRS, nfl = rows * L * SZ;
     float* caches = d.TA ? h_dev : h_dev + (size_t)B * d.hstate();
@@ -1777,11 +1826,7 @@ static int launch_pipe_carried(fe_handle* h, fe::StreamFrameArgs a, float* h_dev
     }
     hipError_t e = hipSuccess;
     h->impl->launch_pipe(a, st, &e);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        *refused = true;
-        return FE_OK;
-    }
+    if ((*refused = coop_refused(e))) return FE_OK;
     if (rings) {
         hipLaunchKernelGGL(ring_out_kernel, dim3(cgrid), dim3(256), 0, st, ring, caches, heads, nfl, B, SZ, L, RS, T);
         e = hipGetLastError();
@@ -1797,9 +1842,7 @@ int fe_set_time_pipeline(fe_handle* h, int frames_in_flight) {
     return FE_OK;
 }
 
-static size_t tb_work_floats(const fe_handle* h, int B, int T, size_t* off);
 static int tb_run(fe_handle* h, fe::tb::TbArgs a, float* work_dev, int B, int T, hipStream_t st);
-static int pipe_width(const fe_handle* h, int B, int T, bool offline, bool spec_rings);
 
 // spec -> spec chunks on the time-batched engine: when asked for (FE_OFFLINE_TIME_BATCHED), or - AUTO - for long chunks of batches that
 // the time pipeline cannot take (more than #CUs / 2 streams: each workgroup would walk its T frames alone) or that are simply large
@@ -1828,7 +1871,7 @@ int fe_spec_step(fe_handle* h, const float* spec_in_dev, float* h_dev, float* sp
     if (use_tb_spec(h, B, T)) {
         // the chunk as one encoder pass, per block a scan that starts from the caller's GRU state and leaves the new one + a tile pass,
         // one decoder pass (fe_spec_step has no work buffer argument: the handle keeps a grow-only one - a first / larger call allocates)
-        const size_t need = tb_work_floats(h, B, T, nullptr);
+        const size_t need = tb_layout(h, B, T).total;
         if (need > h->tb_work_floats) {
             if (h->tb_work_dev) { FE_HIP_CHECK(hipFree(h->tb_work_dev)); h->tb_work_dev = nullptr; h->tb_work_floats = 0; }
             FE_HIP_CHECK(hipMalloc(&h->tb_work_dev, need * sizeof(float)));
@@ -1851,7 +1894,7 @@ int fe_spec_step(fe_handle* h, const float* spec_in_dev, float* h_dev, float* sp
     a.tk = h_dev + (size_t)B * h->d.hstate();
     hipError_t e = hipSuccess;
     a.mode = fe::FE_MODE_SPEC;
-    if (const int P = pipe_width(h, B, T, false, true)) {
+    if (const int P = pipe_width(h, B, T)) {
         hipStream_t st = (hipStream_t)stream;
         const size_t nflags = (size_t)h->max_wgs * pipe_counters(h);
         if (!h->pipe_flags_dev) FE_HIP_CHECK(hipMalloc(&h->pipe_flags_dev, nflags * sizeof(unsigned int)));
@@ -1862,8 +1905,11 @@ int fe_spec_step(fe_handle* h, const float* spec_in_dev, float* h_dev, float* sp
             FE_HIP_CHECK(hipMalloc(&h->spec_ring_dev, need * sizeof(float)));
             h->spec_ring_floats = need;
         }
+        fe::StreamFrameArgs p = a;
+        p.pipe_flags = h->pipe_flags_dev;
+        p.pipe_p = P;
         bool refused = false;
-        rc = launch_pipe_carried(h, a, h_dev, B, T, P, h->pipe_flags_dev, h->spec_ring_dev, st, &refused);
+        rc = launch_pipe_carried(h, p, h_dev, B, T, h->spec_ring_dev, st, &refused);
         if (!refused) return rc;
         // the runtime refused co-residency (GPU shared with other work): walk the frames serially
     }
@@ -1871,14 +1917,12 @@ int fe_spec_step(fe_handle* h, const float* spec_in_dev, float* h_dev, float* sp
     return launch_rc(e);
 }
 
-// fe_step_chunk: fe_step(B, T) with the frames of each stream on the time pipeline.  work_dev: frame counters | windowed frames [B][T][N] |
-// rings at the widest pipeline.  The size depends on the model, B and T only - not on fe_set_time_pipeline nor on the device's CUs - so
-// that it is monotone in both and a buffer sized once serves every setting.
+// fe_step_chunk: fe_step(B, T) with the frames of each stream on the time pipeline.  work_dev: fe_pipe_layout(h, B, T).
 static bool chunk_family(const fe_handle* h) { return h->cfg.arch == FE_ARCH_FASTENHANCER && h->impl && !h->d.BD; }
 
 size_t fe_step_chunk_work_floats(const fe_handle* h, int B, int T) {
     if (!h || B <= 0 || T < 4 || !chunk_family(h)) return 0;
-    return round4((size_t)B * pipe_counters(h)) + (size_t)B * T * h->d.NFFT + pipe_ring_floats(h, B, kMaxPipeFrames);
+    return fe_pipe_layout(h, B, T).total;
 }
 
 // workgroups per stream of fe_step_chunk's pipelined launch (0: fe_step's own launch).  The second launch needs T H >= N - H: the new
@@ -1886,7 +1930,7 @@ size_t fe_step_chunk_work_floats(const fe_handle* h, int B, int T) {
 // ones (FastEnhancer_L, dprnn L, 48 kHz L: N - H = 4.12 H): those pipeline from T = 5 on and walk at T = 4.
 static int chunk_pipe_width(const fe_handle* h, int B, int T) {
     if (!chunk_family(h) || (long)T * h->d.HOP < h->d.NFFT - h->d.HOP) return 0;
-    return pipe_width(h, B, T, false, true);
+    return pipe_width(h, B, T);
 }
 
 int fe_step_chunk(fe_handle* h, const float* wav_in_dev, size_t in_stride, float* state_dev, float* wav_out_dev, size_t out_stride, int B, int T,
@@ -1908,11 +1952,11 @@ int fe_step_chunk(fe_handle* h, const float* wav_in_dev, size_t in_stride, float
     const Dims& d = h->d;
     fe::StreamFrameArgs own{};
     own.capacity = B;
-    fe::StreamFrameArgs a = fe_step_args(h, own, wav_in_dev, in_stride, state_dev, wav_out_dev, out_stride, B, T);     // (fe_step's own argument block)
-    a.frames = work_dev + round4((size_t)B * pipe_counters(h));
-    float* ring = a.frames + (size_t)B * T * d.NFFT;
+    const PipeLayout L = fe_pipe_layout(h, B, T);
+    // (fe_step's own argument block, pointed at the work buffer)
+    const fe::StreamFrameArgs a = pipe_args(fe_step_args(h, own, wav_in_dev, in_stride, state_dev, wav_out_dev, out_stride, B, T), work_dev, L, P);
     bool refused = false;
-    rc = launch_pipe_carried(h, a, a.h, B, T, P, reinterpret_cast<unsigned int*>(work_dev), ring, st, &refused);
+    rc = launch_pipe_carried(h, a, a.h, B, T, work_dev + L.ring, st, &refused);
     // the runtime refused co-residency (GPU shared with other work): walk the frames serially - fe_step's launch, made where fe_step makes it
     if (refused) return launch_fe_step(h, "fe_step", fe::STEP_PLAIN, own, wav_in_dev, in_stride, state_dev, wav_out_dev, out_stride, B, T, stream);
     if (rc != FE_OK) return rc;
@@ -1922,14 +1966,14 @@ int fe_step_chunk(fe_handle* h, const float* wav_in_dev, size_t in_stride, float
     return launch_rc(hipGetLastError());
 }
 
-// fe_step_streams_chunk: the packet step with each stream's hops on the time pipeline.  work_dev: frame counters | windowed frames
-// [n][T_max][N].  Built for the models whose frames exchange the GRU state only (default, ln, dprnn): the ring variants' ring_in_kernel /
+// fe_step_streams_chunk: the packet step with each stream's hops on the time pipeline.  work_dev: fe_pipe_layout(h, n, T_max).  Built
+// for the models whose frames exchange the GRU state only (default, ln, dprnn): the ring variants' ring_in_kernel /
 // ring_out_kernel are not slotted, so time_kernel and dptransformer take the packet step itself, like every call the pipeline cannot take.
 static bool streams_chunk_family(const fe_handle* h) { return chunk_family(h) && h->d.KT == 1 && !h->d.TA && h->impl->launch_streams_pipe != nullptr; }
 
 size_t fe_step_streams_chunk_work_floats(const fe_handle* h, int n, int T_max) {
     if (!h || n <= 0 || T_max < 4 || !streams_chunk_family(h)) return 0;
-    return round4((size_t)n * pipe_counters(h)) + (size_t)n * T_max * h->d.NFFT;
+    return fe_pipe_layout(h, n, T_max).total;
 }
 
 // workgroups per call stream of fe_step_streams_chunk's pipelined launch (0: the packet step's own launch).  Any hop count 0 .. T_max is
@@ -1950,19 +1994,12 @@ static int launch_streams_chunk(fe_handle* h, const fe::StreamFrameArgs& own, co
     int rc = ensure_scratch(h, n);
     if (rc != FE_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    fe::StreamFrameArgs a = fe_step_args(h, own, wav_in, 0, state, wav_out, 0, n, T_max);
-    a.pipe_flags = reinterpret_cast<unsigned int*>(work_dev);
-    a.frames = work_dev + round4((size_t)n * pipe_counters(h));
-    a.pipe_p = P;
+    const fe::StreamFrameArgs a = pipe_args(fe_step_args(h, own, wav_in, 0, state, wav_out, 0, n, T_max), work_dev, fe_pipe_layout(h, n, T_max), P);
     const int nflags = (int)((size_t)n * pipe_counters(h));
     hipLaunchKernelGGL(fe::zero_counters_kernel, dim3((nflags + fe::kThreads - 1) / fe::kThreads), dim3(fe::kThreads), 0, st, a.pipe_flags, nflags);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return launch_rc(e);
-    if (h->impl->launch_streams_pipe(a, st) != hipSuccess) {
-        (void)hipGetLastError();
-        *refused = true;
-        return FE_OK;
-    }
+    if ((*refused = coop_refused(h->impl->launch_streams_pipe(a, st)))) return FE_OK;
     h->last_shape = h->impl->name;
     fe::note_kernel("stream_ola_streams_kernel");
     hipLaunchKernelGGL(fe::stream_ola_streams_kernel, dim3(n), dim3(fe::kThreads), 0, st, a, h->d.NFFT, h->d.HOP);
@@ -1983,29 +2020,13 @@ int fe_step_streams_chunk_pinned(fe_handle* h, const void* wav_in_host, size_t i
                         format, stream, min_gain, levels, bank, true, work_dev);
 }
 
-// floats of the time-batched engine's work buffer: xc | skip | x | gx | hs | frames | spare, each a multiple of 4 floats
-static size_t tb_work_floats(const fe_handle* h, int B, int T, size_t* off /*[7] or nullptr*/) {
-    const Dims& d = h->d;
-    const size_t NF = (size_t)B * T, nd = d.BD ? 2 : 1;
-    // (the seventh region held the GRU state carried between time chunks; nothing writes it any more - kept so that the sizes callers were given stay what they are)
-    const size_t sz[7] = {NF * 2 * d.F0, NF * (d.NL + 1) * d.F1 * d.C1, NF * d.F2 * d.C2, nd * NF * d.F2 * 3 * d.C2, NF * d.F2 * nd * d.C2, NF * d.NFFT,
-                          (size_t)d.KB * nd * B * d.F2 * d.C2};
-    size_t cur = 0;
-    for (int i = 0; i < 7; ++i) {
-        if (off) off[i] = cur;
-        cur += (sz[i] + 3) & ~(size_t)3;
-    }
-    return cur;
-}
-
 // The time-batched engine's schedule: one chain on the caller's stream, enc -> (scan k -> blk k) x KB -> dec, over all B x T frames of the
 // call.  Only the scans are serial in time.  (Cutting the call into nodes over several streams, and a fused scan + tile stage, were
 // measured and lost: profiles/r3d_tb_node_plans.txt, profiles/r3g_tb_fused_stage.txt.)
 static int tb_run(fe_handle* h, fe::tb::TbArgs a, float* work_dev, int B, int T, hipStream_t st) {
     const Dims& d = h->d;
     const fe::tb::TbImpl* tbi = h->impl->tb;
-    size_t off[7];
-    tb_work_floats(h, B, T, off);
+    const TbLayout L = tb_layout(h, B, T);
 #ifdef FE_TB_PROBE
     if (!h->tb_probe_dev) {
         FE_HIP_CHECK(hipMalloc(&h->tb_probe_dev, 4 * fe::tb::kProbeSlots * sizeof(unsigned long long)));
@@ -2016,12 +2037,12 @@ static int tb_run(fe_handle* h, fe::tb::TbArgs a, float* work_dev, int B, int T,
     a.B = B; a.T = T; a.NF = B * T;
     a.b0 = a.t0 = 0; a.Bfull = B; a.Tfull = T;
     a.h_init = (a.hstate != nullptr && a.h_init) ? 1 : 0;     // caches handed in (fe_spec_step): read by the scans, left updated
-    a.xc = work_dev + off[0];
-    a.skip = work_dev + off[1];
-    a.x = work_dev + off[2];
-    a.gx = work_dev + off[3];
-    a.hs = work_dev + off[4];
-    a.frames = work_dev + off[5];
+    a.xc = work_dev + L.xc;
+    a.skip = work_dev + L.skip;
+    a.x = work_dev + L.x;
+    a.gx = work_dev + L.gx;
+    a.hs = work_dev + L.hs;
+    a.frames = work_dev + L.frames;
     if (a.NF == 0) return FE_OK;
     // (FE_TB_STAGES=n: stop after n launches - tools/gpu_tb_check.py reads the intermediate buffers out of work_dev)
     const char* lim_s = std::getenv("FE_TB_STAGES");
@@ -2119,9 +2140,7 @@ static int offline_tb(fe_handle* h, const float* noisy_dev, size_t in_stride, co
     a.compression = h->cfg.input_compression;
     rc = tb_run(h, a, work_dev, B, T, st);
     if (rc != FE_OK) return rc;
-    size_t off[7];
-    tb_work_floats(h, B, T, off);
-    return ola(h, work_dev + off[5], wav_hat_dev, out_stride, B, T, st, Tw_b_dev);
+    return ola(h, work_dev + tb_layout(h, B, T).frames, wav_hat_dev, out_stride, B, T, st, Tw_b_dev);
 }
 
 size_t fe_offline_work_floats(const fe_handle* h, int B, int Tw) {
@@ -2129,30 +2148,20 @@ size_t fe_offline_work_floats(const fe_handle* h, int B, int Tw) {
     const Dims& d = h->d;
     const int T = 1 + Tw / d.HOP;
     size_t n = 0;
-    if (visit_baseline(h->cfg.arch, [&](auto F) {
-            n = baseline_zeroed_floats(F, h, B) + (size_t)B * T * d.NFFT + (size_t)B * F.ring_floats(h);
-        }))
-        return n;
-    if (h->impl && h->impl->tb) {
-        // Sized for the engine the CURRENT fe_set_offline_engine setting selects (FastEnhancer_L x 16 x 4 s: the time-batched buffers are
-        // 3 GB against the frame walk's 25 MB), and MONOTONE in B under that setting: a buffer sized for B serves every batch of at most B
-        // utterances of at most Tw samples.  Under AUTO the big shapes walk from 8 utterances on but take the time-batched engine below
-        // that, so their size covers the time-batched need of min(B, 7) as well.  After fe_set_offline_engine: query again (header).
-        const size_t walk = d.BD ? 0 : (size_t)B * ((size_t)(d.NFFT - d.HOP) + d.hstate() + tk_floats(h)) + (((size_t)B * d.KB + 3) & ~(size_t)3) + (size_t)B * T * d.NFFT;
-        if (d.BD || use_tb_offline(h, B)) return std::max(walk, tb_work_floats(h, B, T, nullptr));
-        if (h->offline_engine == FE_OFFLINE_AUTO) return std::max(walk, tb_work_floats(h, std::min(B, kAutoWalkFrom - 1), T, nullptr));
-        return walk;
-    }
-    // GRU state (zero initial state, model.py:626-627) + overlap-add tail, both zeroed by fe_offline; time-pipelined
-    // launches: + the frame counters [B][KB] and the windowed output frames [B][T][N]
-    n = (size_t)B * ((size_t)(d.NFFT - d.HOP) + d.hstate() + tk_floats(h));
-    // (whatever fe_set_time_pipeline says at the time of THIS call: a buffer sized with the pipeline off must still do when it is on)
-    if (h->impl && T >= 4) {
-        n += (((size_t)B * (d.KB + (d.KT > 1 ? 2 * d.NL : 0)) + 3) & ~(size_t)3) + (size_t)B * T * d.NFFT;
-        if (d.KT > 1) n += (size_t)B * 2 * d.NL * (64 + d.KT - 1) * d.F1 * d.C1;      // the time convs' input rings at the widest pipeline
-        if (d.TA) n += (size_t)B * 2 * d.KB * d.F2 * d.C2 * (d.TA + 64);                // the K / V rings at the widest pipeline
-    }
-    return n;
+    if (visit_baseline(h->cfg.arch, [&](auto F) { n = baseline_layout(F, h, B, T).total; })) return n;
+    // FastEnhancer.  The frame walk's buffer with the pipeline's region, whatever fe_set_time_pipeline says at the time of THIS call: a
+    // buffer sized with the pipeline off must still do when it is on.  (The shapes with a time-batched engine include the region for every
+    // T, the others from the pipeline's 4 frames on: the sizes callers have been given, pinned by tests/golden/host_queries.json.)
+    const OfflineLayout L = fe_walk_layout(h, B, T);
+    const size_t walk = d.BD ? 0 : (h->impl->tb || T >= 4) ? L.total : L.pipe;
+    if (!h->impl->tb) return walk;
+    // Sized for the engine the CURRENT fe_set_offline_engine setting selects (FastEnhancer_L x 16 x 4 s: the time-batched buffers are
+    // 3 GB against the frame walk's 25 MB), and MONOTONE in B under that setting: a buffer sized for B serves every batch of at most B
+    // utterances of at most Tw samples.  Under AUTO the big shapes walk from 8 utterances on but take the time-batched engine below
+    // that, so their size covers the time-batched need of min(B, 7) as well.  After fe_set_offline_engine: query again (header).
+    if (d.BD || use_tb_offline(h, B)) return std::max(walk, tb_layout(h, B, T).total);
+    if (h->offline_engine == FE_OFFLINE_AUTO) return std::max(walk, tb_layout(h, std::min(B, kAutoWalkFrom - 1), T).total);
+    return walk;
 }
 
 int fe_offline(fe_handle* h, const float* noisy_dev, int B, int Tw, float* wav_hat_dev, float* spec_hat_dev, float* work_dev,
@@ -2168,11 +2177,10 @@ int fe_offline(fe_handle* h, const float* noisy_dev, int B, int Tw, float* wav_h
     if (visit_baseline(h->cfg.arch, [&](auto F) { rc = baseline_offline(F, h, noisy_dev, B, Tw, wav_hat_dev, spec_hat_dev, work_dev, st); })) return rc;
     const int T = 1 + Tw / d.HOP;
     if (use_tb_offline(h, B)) return offline_tb(h, noisy_dev, (size_t)Tw, nullptr, Tw, B, wav_hat_dev, (size_t)d.HOP * (T - 1), spec_hat_dev, work_dev, st);
-    {   // zero the state, the tail and the frame counters (not the frames: every element is written)
-        size_t nz = (size_t)B * ((size_t)(d.NFFT - d.HOP) + d.hstate() + tk_floats(h));
-        if (pipe_width(h, B, T, true)) nz += ((size_t)B * (d.KB + (d.KT > 1 ? 2 * d.NL : 0)) + 3) & ~(size_t)3;
-        FE_HIP_CHECK(hipMemsetAsync(work_dev, 0, nz * sizeof(float), st));
-    }
+    const OfflineLayout L = fe_walk_layout(h, B, T);
+    const int P = pipe_width(h, B, T);
+    // zero the tail and the state (zero initial state, model.py:626-627), and the frame counters of a pipelined launch
+    FE_HIP_CHECK(hipMemsetAsync(work_dev, 0, (L.pipe + (P ? L.p.frames : 0)) * sizeof(float), st));
     rc = ensure_scratch(h, B);
     if (rc != FE_OK) return rc;
     fe::StreamFrameArgs a = base_args(h, B, T);
@@ -2185,33 +2193,18 @@ int fe_offline(fe_handle* h, const float* noisy_dev, int B, int Tw, float* wav_h
     a.spec_out = spec_hat_dev;
     a.cache_istft = work_dev;
     a.cache_stft = work_dev;   // unused in this mode
-    a.h = work_dev + (size_t)B * (d.NFFT - d.HOP);
+    a.h = work_dev + L.state;
     a.tk = a.h + (size_t)B * d.hstate();
     hipError_t e = hipSuccess;
-    if (const int P = pipe_width(h, B, T, true)) {
+    if (P) {
         rc = ensure_tables(h, st);
         if (rc != FE_OK) return rc;
-        // work buffer: tail | GRU states | time-conv caches (serial walk) | frame counters | windowed frames | time-conv input rings
-        float* const tk_serial = a.tk;
-        float* flags = a.tk + (size_t)B * tk_floats(h);
-        a.pipe_flags = reinterpret_cast<unsigned int*>(flags);
-        a.frames = flags + (((size_t)B * (d.KB + (d.KT > 1 ? 2 * d.NL : 0)) + 3) & ~(size_t)3);
-        if (d.KT > 1) a.tk = a.frames + (size_t)B * T * d.NFFT;      // (PIPE: rings of P + KT - 1 slots per conv and stream)
-        float* const h_serial = a.h;
-        if (d.TA) a.h = a.frames + (size_t)B * T * d.NFFT;           // (PIPE: K / V rings of L + P slots per pair)
-        a.pipe_p = P;
-        h->impl->launch_pipe(a, st, &e);
-        if (e != hipSuccess) {     // the runtime refused co-residency (GPU shared with other work): walk the frames serially
-            (void)hipGetLastError();
-            a.pipe_p = 0;
-            a.pipe_flags = nullptr;
-            a.frames = nullptr;
-            a.tk = tk_serial;
-            a.h = h_serial;
-            h->impl->launch_step(a, fe::STEP_PLAIN, h->max_wgs, st, &e);
-            return launch_rc(e);
-        }
-        return ola(h, a.frames, wav_hat_dev, (size_t)d.HOP * (T - 1), B, T, st);
+        fe::StreamFrameArgs p = pipe_args(a, work_dev + L.pipe, L.p, P);
+        if (d.KT > 1) p.tk = work_dev + L.pipe + L.p.ring;      // (PIPE: rings of P + KT - 1 slots per conv and stream)
+        if (d.TA) p.h = work_dev + L.pipe + L.p.ring;           // (PIPE: K / V rings of L + P slots per pair)
+        h->impl->launch_pipe(p, st, &e);
+        if (!coop_refused(e)) return ola(h, p.frames, wav_hat_dev, a.out_stride, B, T, st);
+        // the runtime refused co-residency (GPU shared with other work): walk the frames serially
     }
     h->impl->launch_step(a, fe::STEP_PLAIN, h->max_wgs, st, &e);
     return launch_rc(e);
@@ -2263,7 +2256,7 @@ static bool ragged_uses_tb(const fe_handle* h) {
 
 // scratch of the call's engine: the batched pass, or the one-by-one fallback's largest single call (fe_offline_work_floats is monotone in B)
 static size_t ragged_base_floats(const fe_handle* h, int B, int Tw_max) {
-    if (ragged_uses_tb(h)) return tb_work_floats(h, B, 1 + Tw_max / h->d.HOP, nullptr);
+    if (ragged_uses_tb(h)) return tb_layout(h, B, 1 + Tw_max / h->d.HOP).total;
     return std::max(fe_offline_work_floats(h, B, Tw_max), fe_offline_work_floats(h, 1, Tw_max));
 }
 
@@ -2271,7 +2264,7 @@ size_t fe_offline_ragged_work_floats(const fe_handle* h, int B, int Tw_max) {
     if (!h || B <= 0 || Tw_max <= 0) return 0;
     const int Tmax = 1 + Tw_max / h->d.HOP;
     // the call's scratch, the per-utterance lengths, one utterance's spec_hat (the one-by-one fallback)
-    return ragged_base_floats(h, B, Tw_max) + (((size_t)B + 3) & ~(size_t)3) + (size_t)offline_spec_rows(h) * Tmax * 2;
+    return ragged_base_floats(h, B, Tw_max) + round4((size_t)B) + (size_t)offline_spec_rows(h) * Tmax * 2;
 }
 
 int fe_offline_ragged(fe_handle* h, const float* noisy_dev, size_t in_stride, const int* Tw_host, int B, float* wav_hat_dev, size_t out_stride,
@@ -2300,7 +2293,7 @@ int fe_offline_ragged(fe_handle* h, const float* noisy_dev, size_t in_stride, co
     }
     // no batched form for this model / engine setting (the frame walk and its time pipeline take ONE length per launch): one by one
     const int F = offline_spec_rows(h);
-    float* spec_tmp = work_dev + base + (((size_t)B + 3) & ~(size_t)3);
+    float* spec_tmp = work_dev + base + round4((size_t)B);
     for (int b = 0; b < B; ++b) {
         const int Tb = 1 + Tw_host[b] / d.HOP;
         float* dst = spec_hat_dev + (size_t)b * F * Tmax * 2;

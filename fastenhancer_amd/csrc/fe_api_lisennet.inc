@@ -21,8 +21,8 @@ struct LisennetFamily {
     }
     static size_t counters(const fe_handle* h) { return h->limpl->nsite; }      // time-pipeline frame counters per stream
     static constexpr int kPipeFrames = 32;
-    // the time pipeline's ring of the caches of the frames in flight (LArgs::ring), sized for the widest pipeline: 64 + 2 slots per stream
-    static size_t ring_floats(const fe_handle* h) { return 66 * h->limpl->cache_floats; }
+    // the time pipeline's ring of the caches of the frames in flight (LArgs::ring), sized for the widest pipeline: two more slots than frames
+    static size_t ring_floats(const fe_handle* h) { return (size_t)(kMaxPipeFrames + 2) * h->limpl->cache_floats; }
     static void set_ring(Args& a, float* ring) { a.ring = ring; }
     static size_t xp_floats(const fe_handle*) { return 0; }
     static Args args(fe_handle* h, int B, int T);

@@ -20,6 +20,8 @@ NAMES = FE_NAMES + BSRNN_NAMES + ("fspen", "lisennet")
 STATE_B = (1, 3, 256, 257, 2049)
 WORK_B = (1, 3, 8, 16, 600)
 WORK_HOPS = (1, 4, 37, 250)          # Tw = hops * hop + 7: from below the time pipeline's 4 frames to 4 s at 16 kHz
+CHUNK_B = (1, 3, 16, 200)            # streams (fe_step_chunk: B, fe_step_streams_chunk: n) ...
+CHUNK_T = (3, 4, 5, 37, 250)         # ... and hops of the time-pipelined streaming chunks: from below the pipeline's 4 frames on
 
 
 def make_engine(name):
@@ -36,6 +38,8 @@ def host_queries(name):
             key = f"{B}x{n * hop + 7}"
             out["offline_work_floats"][key] = lib.fe_offline_work_floats(h, B, n * hop + 7)
             out["offline_ragged_work_floats"][key] = lib.fe_offline_ragged_work_floats(h, B, n * hop + 7)
+    out["step_chunk_work_floats"] = {f"{B}x{T}": lib.fe_step_chunk_work_floats(h, B, T) for B in CHUNK_B for T in CHUNK_T}
+    out["step_streams_chunk_work_floats"] = {f"{n}x{T}": lib.fe_step_streams_chunk_work_floats(h, n, T) for n in CHUNK_B for T in CHUNK_T}
     out["debug_stages"] = lib.fe_debug_stages(h)
     out["debug_floats"] = lib.fe_debug_floats(h)
     stages = []
