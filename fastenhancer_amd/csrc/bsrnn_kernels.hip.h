@@ -178,6 +178,9 @@ struct BLds {
 // per (utterance, layer); the consumer waits and fetches right before the layer's gate GEMM.  The serial chain per frame and layer is
 // wait -> fetch -> gates -> publish; the band
 // recurrence, the fc layers and the mask MLPs - 9/10 of a frame - run in parallel across the frames in flight.
+// PIPE with mode == FE_MODE_STREAM (fe_step_backlog): the same launch on a streaming chunk.  `lstm` is the caller's streaming state, handed
+// on in place (frame 0 fetches it without a wait, the last frame's stores leave the new one); the frames read the call's old cache_stft side
+// by side and write neither STFT cache - stream_ola_kernel overlap-adds a.frames and writes both afterwards.
 // PART (the per-hop step split in three launches, blaunch_split): every workgroup of the fused kernel streams the mask decoder's 780 KB
 // (xt) of weights from L2 once per frame - each weight is used ONCE per stream (M = 1) - and that is 40 k of a frame's 240 k cycles at
 // ~20 B/clk per CU.  Batched over the streams the same products are a small MFMA GEMM whose weights are read once per 64 streams:
@@ -337,10 +340,17 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
         if (mode != FE_MODE_SPEC) {
             const float* win = wp + o.window;
             if (mode == FE_MODE_STREAM) {
+                // PIPE (a streaming chunk on the time pipeline, fe_step_backlog): frame t is samples t H .. t H + N - 1 of [the call's old
+                // cache_stft | the chunk] - sample n is cst[t H + n] while that index is inside the cache, else chunk[t H + n - OVL], which is
+                // xin[n - OVL] as in the serial walk (here with n - OVL < 0 for the frames that still start inside the cache).  Every frame of
+                // the stream reads the old cache side by side; stream_ola_kernel writes both caches afterwards.
+                // (the cache's base and end as values of the loop, not a branch around it: the other instantiations keep their code)
                 const float* xin = a.wav_in + (size_t)b * a.in_stride + (size_t)t * H;
+                const float* cs0 = PIPE ? cst + t * H : cst;
+                const int ovl0 = PIPE ? OVL - t * H : OVL;
                 for (int n = tid; n < N; n += kThreads) {
-                    float v = (n < OVL) ? cst[n] : xin[n - OVL];
-                    fb[n] = make_float2(v, 0.0f);
+                    float v = (n < ovl0) ? cs0[n] : xin[n - OVL];
+                    if constexpr (!PIPE) fb[n] = make_float2(v, 0.0f);
                     fa[n] = make_float2(v * win[n], 0.0f);
                 }
             } else {
@@ -355,9 +365,11 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
             __syncthreads();
             if constexpr (REGW) fetch_part(I0{}, I3{}, 0, std::true_type{});   // layer 0's weights: in flight across the FFT (three bursts:
                                                                                  // a wave keeps at most 63 vector-memory loads in flight)
+            if constexpr (!PIPE) {
             if (mode == FE_MODE_STREAM) {
                 for (int m = tid; m < OVL; m += kThreads) cst[m] = fb[m + H].x;
                 __syncthreads();
+            }
             }
             float2* Xf = fft_lds<S, false>(fa, fb, tw);
             if constexpr (REGW) fetch_part(I1{}, I3{}, 0, std::true_type{});
@@ -1455,8 +1467,9 @@ void blaunch_sb_impl(const BArgs& a, const SbOffsets& so, int total_floats, int 
 
 template <class S>
 void blaunch_pipe_impl(const BArgs& a, hipStream_t st, hipError_t* err) {
-    *err = launch_coop<&bsrnn_frame_kernel<S, false, false, false, false, true>>("bsrnn_frame_kernel<time-pipelined>", dim3(a.B * a.pipe_p), dim3(kThreads),
-                                                                                 BLds<S>::BYTES, st, a);
+    // (one instantiation, as for fe_frame_kernel: the mode is a run-time value there; a streaming chunk - fe_step_backlog - is named apart)
+    const char* name = a.mode == FE_MODE_STREAM ? "bsrnn_frame_kernel<time-pipelined, streaming>" : "bsrnn_frame_kernel<time-pipelined>";
+    *err = launch_coop<&bsrnn_frame_kernel<S, false, false, false, false, true>>(name, dim3(a.B * a.pipe_p), dim3(kThreads), BLds<S>::BYTES, st, a);
 }
 
 template <class S>

@@ -1966,6 +1966,78 @@ int fe_step_chunk(fe_handle* h, const float* wav_in_dev, size_t in_stride, float
     return launch_rc(hipGetLastError());
 }
 
+// fe_step_backlog: fe_step(B, T) with the frames of each stream on the time pipeline, for every family that has a streaming state.
+// FastEnhancer: fe_step_chunk.  The baseline families whose PIPE kernel hands the streaming state on in place (Fam::kPipeCarriesState:
+// BSRNN, FSPEN), written once per family trait like baseline_offline: work_dev is pipe_layout(h, B, T, Fam::counters(h), 0) - sized for
+// the pipelined launch whatever fe_set_time_pipeline says at the time of the query.
+extern "C++" template <class Fam>
+static PipeLayout baseline_backlog_layout(Fam, const fe_handle* h, int B, int T) {
+    if (!Fam::kPipeCarriesState || !Fam::impl(h)->launch_pipe || B <= 0 || T < 4) return {0, 0, 0};
+    return pipe_layout(h, B, T, Fam::counters(h), 0);
+}
+
+// workgroups per stream of fe_step_backlog's pipelined launch: the family's fe_offline width (0: fe_step's own launch), and the chunk has
+// to cover the overlap (stream_ola_kernel: T H >= N - H - every shipped BSRNN and FSPEN shape does at T = 4)
+extern "C++" template <class Fam>
+static int baseline_backlog_width(Fam, const fe_handle* h, int B, int T) {
+    if (!Fam::kPipeCarriesState || (long)T * h->d.HOP < h->d.NFFT - h->d.HOP) return 0;
+    return baseline_pipe_width(Fam{}, h, B, T);
+}
+
+// The pipelined chunk of a baseline family (P >= 2; the arguments are checked): a linear chain on the caller's stream - the counters'
+// zeroing (a kernel, not a memset node: stft_kernels.hip.h), the family's cooperative PIPE kernel in streaming mode on the caller's state
+// in place (not zeroed, not copied: frame 0 reads it, the last frame leaves the new one), stream_ola_kernel - that allocates nothing
+// (Fam::args takes the per-family scratch the handle got at fe_load_weights, as baseline_offline does).  A cooperative launch the runtime
+// refuses: fe_step's launch with the caller's own argument block - by then only the counters in work_dev have been written.
+extern "C++" template <class Fam>
+static int baseline_step_backlog(Fam, fe_handle* h, const float* wav_in, size_t in_stride, float* state, float* wav_out, size_t out_stride, int B, int T, int P,
+                                 float* work_dev, void* stream) {
+    int rc = check_ready(h);
+    if (rc != FE_OK) return rc;
+    KernelLogScope klog_(h);
+    hipStream_t st = (hipStream_t)stream;
+    const Dims& d = h->d;
+    typename Fam::Args a = Fam::args(h, B, T);
+    Fam::state(a) = stream_io(a, wav_in, in_stride, wav_out, out_stride, state, state_layout(h, B));
+    const PipeLayout L = baseline_backlog_layout(Fam{}, h, B, T);
+    const typename Fam::Args p = pipe_args(a, work_dev, L, P);
+    const int nflags = (int)((size_t)B * Fam::counters(h));
+    hipLaunchKernelGGL(fe::zero_counters_kernel, dim3((nflags + fe::kThreads - 1) / fe::kThreads), dim3(fe::kThreads), 0, st, p.pipe_flags, nflags);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return launch_rc(e);
+    Fam::impl(h)->launch_pipe(p, st, &e);
+    if (coop_refused(e)) {
+        fe::g_klog.n = 0;       // (the refused launch was named before it was tried)
+        return Fam::launch(h, a, stream);
+    }
+    fe::note_kernel("stream_ola_kernel");
+    hipLaunchKernelGGL(fe::stream_ola_kernel, dim3((T * d.HOP + fe::kThreads - 1) / fe::kThreads, B), dim3(fe::kThreads), 0, st,
+                       p.frames, wav_in, in_stride, p.cache_stft, p.cache_istft, wav_out, out_stride, d.NFFT, d.HOP, T);
+    return launch_rc(hipGetLastError());
+}
+
+size_t fe_step_backlog_work_floats(const fe_handle* h, int B, int T) {
+    if (!h || B <= 0 || T < 4) return 0;
+    size_t n = 0;
+    if (visit_baseline(h->cfg.arch, [&](auto F) { n = baseline_backlog_layout(F, h, B, T).total; })) return n;
+    return fe_step_chunk_work_floats(h, B, T);
+}
+
+int fe_step_backlog(fe_handle* h, const float* wav_in_dev, size_t in_stride, float* state_dev, float* wav_out_dev, size_t out_stride, int B, int T,
+                    float* work_dev, void* stream) {
+    if (!h) return fail(FE_ERR_INVALID_ARG, "null handle");
+    if (h->cfg.arch == FE_ARCH_FASTENHANCER) return fe_step_chunk(h, wav_in_dev, in_stride, state_dev, wav_out_dev, out_stride, B, T, work_dev, stream);
+    // fe_step's checks, the arguments first (as fe_step_chunk checks them)
+    int rc = check_step_args(h, nullptr, "bad argument", wav_in_dev && state_dev && wav_out_dev, B, B, T, in_stride, out_stride);
+    if (rc != FE_OK) return rc;
+    int P = 0;
+    visit_baseline(h->cfg.arch, [&](auto F) { P = baseline_backlog_width(F, h, B, T); });
+    if (P == 0) return run_step(h, wav_in_dev, in_stride, state_dev, wav_out_dev, out_stride, B, T, nullptr, nullptr, stream);
+    if (!work_dev) return fail(FE_ERR_INVALID_ARG, "fe_step_backlog: null work buffer (fe_step_backlog_work_floats(h, %d, %d) floats)", B, T);
+    visit_baseline(h->cfg.arch, [&](auto F) { rc = baseline_step_backlog(F, h, wav_in_dev, in_stride, state_dev, wav_out_dev, out_stride, B, T, P, work_dev, stream); });
+    return rc;
+}
+
 // fe_step_streams_chunk: the packet step with each stream's hops on the time pipeline.  work_dev: fe_pipe_layout(h, n, T_max).  Built
 // for the models whose frames exchange the GRU state only (default, ln, dprnn): the ring variants' ring_in_kernel /
 // ring_out_kernel are not slotted, so time_kernel and dptransformer take the packet step itself, like every call the pipeline cannot take.

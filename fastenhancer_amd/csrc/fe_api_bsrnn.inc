@@ -18,6 +18,7 @@ struct BsrnnFamily {
     // default frames in flight per utterance of a time-pipelined offline launch: a hand-off chain (wait, fetch, gate GEMM, publish) is ~1/40
     // of a frame, so every co-resident workgroup the batch leaves free is worth having
     static constexpr int kPipeFrames = 64;
+    static constexpr bool kPipeCarriesState = true;      // (fe_step_backlog: the PIPE kernel's frames hand the streaming state on in place)
     static size_t ring_floats(const fe_handle*) { return 0; }
     static void set_ring(Args&, float*) {}
     static size_t xp_floats(const fe_handle* h) { return (size_t)h->max_wgs * h->bimpl->xp_floats; }     // (band-LSTM input projections of C = 64)

@@ -21,6 +21,9 @@ struct LisennetFamily {
     }
     static size_t counters(const fe_handle* h) { return h->limpl->nsite; }      // time-pipeline frame counters per stream
     static constexpr int kPipeFrames = 32;
+    // fe_step_backlog walks: the PIPE kernel hands the nine caches through ring slots and starts from zero caches at frame 0 (cprev / ccur in
+    // lisennet_kernels.hip.h) - a streaming state would need kernels that move it into and out of the ring
+    static constexpr bool kPipeCarriesState = false;
     // the time pipeline's ring of the caches of the frames in flight (LArgs::ring), sized for the widest pipeline: two more slots than frames
     static size_t ring_floats(const fe_handle* h) { return (size_t)(kMaxPipeFrames + 2) * h->limpl->cache_floats; }
     static void set_ring(Args& a, float* ring) { a.ring = ring; }

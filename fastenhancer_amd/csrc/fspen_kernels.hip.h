@@ -288,6 +288,10 @@ __device__ __forceinline__ float row_dot(const float (&w)[12], float h, float ac
 // PIPE: time pipelining of an offline launch (as for FastEnhancer / BSRNN): the only thing a frame needs from the previous one are the
 // inter-GRU states (24 x [4][16] per stream), handed over per DPE block through `gru` by the protocol of fe_handover.h, a counter per
 // (utterance, block); the consumer waits and fetches the states right before the block's inter GRUs.
+// PIPE with mode == FE_MODE_STREAM (fe_step_backlog): the same launch on a streaming chunk.  `gru` is the caller's streaming state, handed
+// on in place (frame 0 fetches it without a wait - the 0.0f the block's prefetch puts into hprev under PIPE is overwritten by that fetch
+// before the inter GRUs read it); the frames read the call's old cache_stft side by side and write neither STFT cache - stream_ola_kernel
+// overlap-adds a.frames and writes both afterwards.
 // PART: 0 the whole frame; 1 the front (STFT, sub-band encoder, fullband_encoder.0-1: its LDS regions to global memory); 2 the tail
 // (sub-band decoder, fullband_decoder.2, masks, iSTFT) - the per-hop step of large batches runs 1 -> fspen_sb_dpe_kernel (fullband_encoder.2,
 // fullband_encoder_post, feature merge, 3 x DPE, feature split, fullband_decoder.0-1 - batched over the streams, fspen_sb_kernels.hip.h) -> 2
@@ -367,10 +371,18 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(P
             const WView win = wp + P::WINDOW;
             float* cst = a.cache_stft + (size_t)b * OVL;
             if (mode == FE_MODE_STREAM) {
+                // PIPE (a streaming chunk on the time pipeline, fe_step_backlog): frame t is samples t H .. t H + N - 1 of [the call's old
+                // cache_stft | the chunk] - sample n is cst[t H + n] while that index is inside the cache, else chunk[t H + n - OVL], which is
+                // xin[n - OVL] as in the serial walk (here with n - OVL < 0 for the frames that still start inside the cache).  Every frame of
+                // the stream reads the old cache side by side; stream_ola_kernel writes both caches afterwards.
+                // (the cache's base and end as values of the loop, not a branch around it: the other instantiations keep their code, and this
+                //  one its spill count)
                 const float* xin = a.wav_in + (size_t)b * a.in_stride + (size_t)t * H;
+                const float* cs0 = PIPE ? cst + t * H : cst;
+                const int ovl0 = PIPE ? OVL - t * H : OVL;
                 for (int n = tid; n < N; n += kThreads) {
-                    const float v = (n < OVL) ? cst[n] : xin[n - OVL];
-                    fb[n] = make_float2(v, 0.0f);
+                    const float v = (n < ovl0) ? cs0[n] : xin[n - OVL];
+                    if constexpr (!PIPE) fb[n] = make_float2(v, 0.0f);
                     fa[n] = make_float2(v * win[n], 0.0f);
                 }
             } else {
@@ -383,9 +395,11 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(P
                 }
             }
             __syncthreads();
+            if constexpr (!PIPE) {
             if (mode == FE_MODE_STREAM) {
                 for (int m = tid; m < OVL; m += kThreads) cst[m] = fb[m + H].x;
                 __syncthreads();
+            }
             }
             float2* Xf = fft_lds<S, false>(fa, fb, tw);
             if constexpr (DBG) { for (int f = tid; f < BINS; f += kThreads) { dbg[2 * f] = Xf[f].x; dbg[2 * f + 1] = Xf[f].y; } }
@@ -1187,7 +1201,8 @@ template <class S>
 void flaunch_pipe_impl(const FArgs& a, hipStream_t st, hipError_t* err) {
     FArgs args = a;
     void* kargs[] = {&args};
-    note_kernel("fspen_frame_kernel<time-pipelined>");
+    // (one instantiation: the mode is a run-time value there; a streaming chunk - fe_step_backlog - is named apart)
+    note_kernel(a.mode == FE_MODE_STREAM ? "fspen_frame_kernel<time-pipelined, streaming>" : "fspen_frame_kernel<time-pipelined>");
     *err = hipLaunchCooperativeKernel(reinterpret_cast<const void*>(&fspen_frame_kernel<S, false, false, true>), dim3(a.B * a.pipe_p), dim3(kThreads), kargs, 0, st);
 }
 

@@ -203,7 +203,23 @@ class Engine:
         """fe_step_chunk: step(wav_in, state, wav_out, T) with the T hops of each stream on the time pipeline - a recording, or a stream with
         a backlog.  wav_in [B, T*H] (row stride free; T defaults to wav_in.shape[1] // H) -> wav_out [B, T*H], which must not overlap wav_in;
         state updated in place.  Results agree with step() to fp32 rounding.  work: a float32 device tensor of at least
-        chunk_work_floats(B, T) floats (the form for graph capture); None: a scratch tensor kept on the engine, grown when needed."""
+        chunk_work_floats(B, T) floats (the form for graph capture); None: a scratch tensor kept on the engine, grown when needed.
+        BSRNN, FSPEN and LiSenNet are not pipelined here: step_backlog."""
+        return self._chunk("fe_step_chunk", "chunk_work_floats", wav_in, state, wav_out, T, work)
+
+    # ---- the same for every family with a streaming state (fe_step_backlog): BSRNN and FSPEN chunks on the time pipeline too
+    def backlog_work_floats(self, B: int, T: int) -> int:
+        """fe_step_backlog_work_floats: floats of scratch step_backlog needs for at most B streams of at most T hops (0: none)."""
+        return int(self.lib.fe_step_backlog_work_floats(self._h, int(B), int(T)))
+
+    def step_backlog(self, wav_in: Tensor, state: Tensor, wav_out: Optional[Tensor] = None, T: Optional[int] = None, work: Optional[Tensor] = None) -> Tensor:
+        """fe_step_backlog: step_chunk for every family - the FastEnhancer models as step_chunk runs them, BSRNN and FSPEN with the T hops
+        of each stream on their own time pipeline, LiSenNet as step() walks it.  Arguments, checks and the scratch tensor as for step_chunk,
+        with backlog_work_floats(B, T) for the size of work."""
+        return self._chunk("fe_step_backlog", "backlog_work_floats", wav_in, state, wav_out, T, work)
+
+    def _chunk(self, entry: str, query: str, wav_in: Tensor, state: Tensor, wav_out: Optional[Tensor], T: Optional[int], work: Optional[Tensor]) -> Tensor:
+        """step_chunk / step_backlog: the checks (all of them before any native call), the grow-only scratch tensor, the call of `entry`"""
         H = self.cfg.hop_size
         if not isinstance(wav_in, Tensor) or wav_in.dim() != 2 or wav_in.dtype != torch.float32 or wav_in.stride(1) != 1:
             raise ValueError("wav_in must be a 2-D float32 tensor [B, T*H] with unit stride along the samples")
@@ -219,25 +235,25 @@ class Engine:
         if not isinstance(state, Tensor) or state.dtype != torch.float32 or state.dim() != 1 or not state.is_contiguous():
             raise ValueError("state must be a contiguous 1-D float32 tensor (new_state(B))")
         if work is not None and (not isinstance(work, Tensor) or work.dtype != torch.float32 or not work.is_contiguous()):
-            raise ValueError("work must be a contiguous float32 tensor of chunk_work_floats(B, T) floats")
+            raise ValueError(f"work must be a contiguous float32 tensor of {query}(B, T) floats")
         self._require_gpu()
         if not wav_in.is_cuda or not state.is_cuda or (wav_out is not None and not wav_out.is_cuda) or (work is not None and not work.is_cuda):
             raise ValueError("wav_in, state, wav_out and work must be device tensors")
         if state.numel() != self.state_floats(B):
             raise ValueError(f"state has {state.numel()} floats, a state of {B} streams {self.state_floats(B)}")
-        need = self.chunk_work_floats(B, T)
+        need = getattr(self, query)(B, T)
         if work is None:
             if need > 0:
                 if getattr(self, "_chunk_work", None) is None or self._chunk_work.numel() < need:
                     self._chunk_work = torch.empty(need, dtype=torch.float32, device=self.device)
                 work = self._chunk_work
         elif work.numel() < need:
-            raise ValueError(f"work has {work.numel()} floats, chunk_work_floats({B}, {T}) = {need}")
+            raise ValueError(f"work has {work.numel()} floats, {query}({B}, {T}) = {need}")
         if wav_out is None:
             wav_out = torch.empty(B, T * H, dtype=torch.float32, device=wav_in.device)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.fe_step_chunk(self._h, _ptr(wav_in), wav_in.stride(0) if B > 1 else T * H, _ptr(state), _ptr(wav_out),
-                                              wav_out.stride(0) if B > 1 else T * H, B, T, _ptr(work), _stream(self.device)), "fe_step_chunk")
+            _lib.check(getattr(self.lib, entry)(self._h, _ptr(wav_in), wav_in.stride(0) if B > 1 else T * H, _ptr(state), _ptr(wav_out),
+                                                wav_out.stride(0) if B > 1 else T * H, B, T, _ptr(work), _stream(self.device)), entry)
         return wav_out
 
     def _slot_tensor(self, slots, capacity: int) -> Tensor:

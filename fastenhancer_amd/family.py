@@ -45,6 +45,7 @@ class Family:
     split: Callable = lambda cfg, h, B, head0=False: views(h, cfg.cache_shapes(B))      # h -> caches
     order: Callable = lambda cfg, caches: [t.reshape(-1) for t in caches]               # caches -> flat pieces of h, in its order
     start: Callable = lambda cfg, h, B: None                                            # zeroed h -> the state of a call without caches
+    backlog: bool = False           # chunks of many hops go through Engine.step_backlog (fe_step_backlog pipelines the family), not step_chunk
 
     def spec_bins(self, cfg) -> int:
         return cfg.F0 + (1 if self.nyquist else 0)
@@ -136,9 +137,9 @@ _FAMILIES = {
     FEConfig: Family(_lib.FE_ARCH_FASTENHANCER, _fe_config, W.fold_state_dict, W.check_fused, W.default_state_dict, nyquist=False,
                      split=_fe_split, order=_fe_order, start=_fe_start),
     BSRNNConfig: Family(_lib.FE_ARCH_BSRNN, _bsrnn_config, W.bsrnn_fold_state_dict, _shapes(W.bsrnn_expected_fused_shapes),
-                        W.bsrnn_default_state_dict),
+                        W.bsrnn_default_state_dict, backlog=True),
     FSPENConfig: Family(_lib.FE_ARCH_FSPEN, _fspen_config, W.fspen_fold_state_dict, _shapes(W.fspen_expected_fused_shapes),
-                        W.fspen_default_state_dict),
+                        W.fspen_default_state_dict, backlog=True),
     LiSenNetConfig: Family(_lib.FE_ARCH_LISENNET, _lisennet_config, W.lisennet_state_dict, _shapes(W.lisennet_expected_shapes),
                            W.lisennet_default_state_dict),
 }
@@ -146,3 +147,11 @@ _FAMILIES = {
 
 def family_of(cfg) -> Family:
     return _FAMILIES[type(cfg)]
+
+
+def chunk_step(engine) -> Callable:
+    """The engine's call for a chunk of many hops of few streams (streaming.enhance_stream(chunk_hops=...), StreamPool.catch_up):
+    step_backlog for the families fe_step_backlog pipelines (BSRNN, FSPEN), step_chunk for every other - FastEnhancer's own path as it
+    has always been called; for LiSenNet both are the walk of step()."""
+    fam = _FAMILIES.get(type(getattr(engine, "cfg", None)))
+    return engine.step_backlog if fam is not None and fam.backlog else engine.step_chunk

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """scripts/test_streaming.py with one more flag: --chunk-hops N runs the file in chunks of N hops on the time pipeline
-(Engine.step_chunk through streaming.enhance_stream(chunk_hops=N)) instead of hop by hop.  Off by default: without the flag this IS
+(Engine.step_chunk - BSRNN and FSPEN checkpoints: Engine.step_backlog - through streaming.enhance_stream(chunk_hops=N)) instead of hop by hop.  Off by default: without the flag this IS
 test_streaming.py (same flags, same loop, same output).
 
     python -m fastenhancer_amd.scripts.stream_chunks -c configs/fastenhancer/b.yaml --checkpoint logs/b/00500.pth \\

@@ -25,7 +25,9 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 from torch import Tensor
 
+from . import _lib
 from .engine import Engine
+from .family import chunk_step
 
 
 class StreamPool:
@@ -47,7 +49,15 @@ class StreamPool:
         if not self._free:
             raise RuntimeError(f"all {self.capacity} slots are open")
         slot = self._free.pop()
-        self.engine.reset_slots(self.state, self.capacity, [slot])
+        fam = getattr(self.engine, "family", None)
+        if fam is not None and fam.arch != _lib.FE_ARCH_FASTENHANCER:
+            # BSRNN, FSPEN, LiSenNet: fe_state_reset_slots is built for the FastEnhancer family; their fresh state is zeros, and the state
+            # records are built for every family - the slot takes a zero record (such a pool serves catch_up, export and import; the
+            # slotted steps stay FastEnhancer's)
+            fresh = torch.zeros(1, self.engine.record_floats, dtype=torch.float32, device=self.state.device)
+            self.engine.import_slots(self.state, self.capacity, [slot], fresh)
+        else:
+            self.engine.reset_slots(self.state, self.capacity, [slot])
         self._open.add(slot)
         return slot
 
@@ -74,8 +84,8 @@ class StreamPool:
 
     def catch_up(self, slot: int, wav_in: Tensor, T: Optional[int] = None) -> Tensor:
         """A live stream that comes back with a backlog: wav_in [T*H] or [1, T*H] (T defaults to its length // H) -> the T*H output samples
-        [1, T*H], the slot's state advanced by T hops - on the time pipeline (Engine.step_chunk) instead of hop after hop.  The slot's state
-        record is a capacity-1 state: it is exported, stepped as a batch of one, and imported back; no other slot is read or written.
+        [1, T*H], the slot's state advanced by T hops - on the time pipeline (Engine.step_chunk; BSRNN and FSPEN: Engine.step_backlog) instead
+        of hop after hop.  The slot's state record is a capacity-1 state: it is exported, stepped as a batch of one, and imported back; no other slot is read or written.
         The result agrees with step() over the same hops to fp32 rounding."""
         if slot not in self._open:
             raise ValueError(f"slot {slot} is not open")
@@ -84,7 +94,7 @@ class StreamPool:
         if wav_in.dim() != 2 or wav_in.shape[0] != 1:
             raise ValueError("catch_up takes the backlog of ONE stream: wav_in [T*H] or [1, T*H]")
         rec = self.engine.export_slots(self.state, self.capacity, [slot])
-        out = self.engine.step_chunk(wav_in, rec.view(-1), T=T)
+        out = chunk_step(self.engine)(wav_in, rec.view(-1), T=T)
         self.engine.import_slots(self.state, self.capacity, [slot], rec)
         return out
 

@@ -364,10 +364,44 @@ int fe_set_time_pipeline(fe_handle* h, int frames_in_flight);
  *     makes: bit-identical results.  A cooperative launch the runtime refuses falls back to the same walk.
  *   Two launches: the pipelined frame kernel, whose frames read the call's cache_stft / wav_in and store their windowed output to work_dev,
  *     then stream_ola_kernel - the streaming overlap-add (old cache_istft, then the covering frames, oldest first) and the two new STFT
- *     caches.  fe_last_step_kernel: "fe_frame_kernel<time-pipelined, streaming> + stream_ola_kernel [shape B]". */
+ *     caches.  fe_last_step_kernel: "fe_frame_kernel<time-pipelined, streaming> + stream_ola_kernel [shape B]".
+ *   BSRNN and FSPEN chunks on the time pipeline: fe_step_backlog, below. */
 size_t fe_step_chunk_work_floats(const fe_handle* h, int B, int T);
 int fe_step_chunk(fe_handle* h, const float* wav_in_dev, size_t in_stride, float* state_dev, float* wav_out_dev, size_t out_stride,
                   int B, int T, float* work_dev, void* stream);
+
+/* fe_step for few streams and many hops, for EVERY family with a streaming state: fe_step(h, ..., B, T, stream) with the T frames of each
+ * stream on the time pipeline wherever the family has one.  Rows, state buffer (fe_state_floats(h, B), updated in place), argument checks
+ * (before the handle's weights), error codes and refusals are fe_step's, as for fe_step_chunk; the noncausal model is refused with
+ * fe_step's message.
+ *   FastEnhancer family (default, ln, dprnn, time_kernel, dptransformer): the call IS fe_step_chunk and the query IS
+ *     fe_step_chunk_work_floats - everything above holds word for word.
+ *   BSRNN and FSPEN: the T frames of each stream run on P co-resident workgroups - the family's time-pipelined frame kernel, the one of
+ *     its fe_offline, in streaming mode - which exchange only the time-LSTM (h, c) per layer (BSRNN) or the inter-GRU states per DPE block
+ *     (FSPEN), in place in the caller's state: frame 0 reads it, the last frame leaves the new one.  Every frame reads the call's old
+ *     cache_stft and wav_in and stores its windowed output to work_dev; stream_ola_kernel then does the streaming overlap-add and writes
+ *     both STFT caches.
+ *     Results: wav_out and every model-state tensor agree with fe_step(B, T) to fp32 rounding (the overlap-add sums are formed in another
+ *       order); cache_stft agrees bit for bit.  The state left behind is valid for every other entry point: fe_step, the export and
+ *       import records, a later fe_step_backlog.
+ *     work_dev: fe_step_backlog_work_floats(h, B, T) floats - the frame counters [B][layers or blocks], rounded up to 4 floats, then the
+ *       windowed frames [B][T][N].  The size depends on the model, B and T only and is monotone in both; 0 for T < 4, for B <= 0 and for a
+ *       null handle, non-zero for every B >= 1 and T >= 4 whatever fe_set_time_pipeline says: a buffer sized once serves every setting.
+ *       NULL where the pipelined path would run is FE_ERR_INVALID_ARG.
+ *     Width P: that of the family's pipelined fe_offline (fe_set_time_pipeline; BSRNN up to 64, FSPEN up to 32 frames in flight, at most
+ *       the co-resident workgroups the B streams leave each other), and the chunk must cover the overlap, T * H >= N - H (every shipped
+ *       BSRNN and FSPEN shape does at T = 4).  P = 0 - T < 4, fe_set_time_pipeline(0 or 1), too many streams to give each two workgroups -
+ *       and a cooperative launch the runtime refuses: the call makes the very launch fe_step makes, bit for bit.
+ *     A linear chain of three kernels on the caller's stream (the counters are zeroed by a small kernel, not a memset node); the call
+ *       allocates nothing and can be captured into a graph.  wav_in and wav_out MUST NOT overlap, as for fe_step_chunk.
+ *     fe_last_step_kernel: "bsrnn_frame_kernel<time-pipelined, streaming> + stream_ola_kernel [shape xxt]",
+ *       "fspen_frame_kernel<time-pipelined, streaming> + stream_ola_kernel [shape fspen]" (the counters' zeroing is not named).
+ *   LiSenNet: the call is fe_step's launch and the work size is 0.  Its time-pipelined kernel hands nine caches from frame to frame
+ *     through ring slots and starts from zero caches at frame 0; carrying a streaming state through it needs kernels that move the state
+ *     into and out of the rings, like those of the time_kernel variant.  Deliberately not built here. */
+size_t fe_step_backlog_work_floats(const fe_handle* h, int B, int T);
+int fe_step_backlog(fe_handle* h, const float* wav_in_dev, size_t in_stride, float* state_dev, float* wav_out_dev, size_t out_stride,
+                    int B, int T, float* work_dev, void* stream);
 
 /* The packet step's time-pipelined form - a stream of a packet batch that comes back with a backlog: fe_step_streams_banked[_pinned] with the
  * hops of EACH stream spread over co-resident workgroups instead of walked by one.  Same descriptors, slots, formats, limit, meters and banks,
