@@ -54,6 +54,7 @@ SYMBOLS = {
     "fe_state_init": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "fe_step": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),
     "fe_step_slots": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),
+    "fe_step_pool": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),
     "fe_state_reset_slots": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "fe_state_export_slots": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "fe_state_import_slots": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),

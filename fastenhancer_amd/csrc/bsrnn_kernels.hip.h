@@ -126,6 +126,29 @@ struct BArgs {
     unsigned int* gsync;
 };
 
+// The slot-indexed step (fe_step_pool; the SLOT instantiations): BArgs with two fields at the end.  Call stream b is state slot slots[b] of a state
+// sized for `capacity` streams - every state address takes (slot, capacity) where the plain step takes (b, B); audio rows and the inter-launch
+// scratch (mlp_x / mlp_sp / mlp_pre, xp_scratch) stay in call order.  (A type of its own, so that the other instantiations keep their
+// kernel-argument block - and their code - as they were.)
+struct BSlotArgs : BArgs {
+    int capacity;
+    const int* slots;         // [B] device int32; a slot outside [0, capacity) gets zero output rows and touches no state
+};
+template <bool SLOT> struct BKernelArgs { using type = BArgs; };
+template <> struct BKernelArgs<true> { using type = BSlotArgs; };
+// rows of every state tensor: the call's streams, or the capacity of a slotted state (read where it is used, as a.B was)
+template <bool SLOT, class A>
+__device__ __forceinline__ int bstate_rows(const A& a) {
+    if constexpr (SLOT) return a.capacity;
+    else return a.B;
+}
+// call stream b's row of them: its slot (a scalar load, wave-uniform), or b itself
+template <bool SLOT, class A>
+__device__ __forceinline__ int bstate_row(const A& a, int b) {
+    if constexpr (SLOT) return __builtin_amdgcn_readfirstlane(a.slots[b]);
+    else return b;
+}
+
 // debug stage table: spec_in, compressed, band_split, (layer.l.time, layer.l.freq)..., mask_mlp, spec_out
 template <class S>
 struct BDebugLayout {
@@ -186,9 +209,14 @@ struct BLds {
 // ~20 B/clk per CU.  Batched over the streams the same products are a small MFMA GEMM whose weights are read once per 64 streams:
 // PART = 1 runs the frame up to the last layer and leaves the band features and the compressed spectrum in global memory,
 // bsrnn_mlp_kernel computes the two MLP layers for all streams, PART = 2 applies GLU / mask / residual and runs the iSTFT.
-template <class S, bool HOT, bool PROF, bool DBG, bool OCC2 = false, bool PIPE = false, int PART = 0>
-__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, PART == 2 ? 6 : PART == 3 ? 4 : OCC2 ? 2 : 1))) bsrnn_frame_kernel(BArgs a) {
+// SLOT (fe_step_pool): stream b's state is slot a.slots[b] of a state sized for a.capacity streams (sb, bstate_rows below), read by every launch of the
+// step itself; a slot out of range skips the stream in each of them - no state access, zero output rows from the launch that writes the audio,
+// nothing handed to the scratch (bsrnn_mlp_kernel, which touches no state, then works on that stream's stale scratch row: its rows are per
+// stream, so nothing of it reaches another stream, and the tail skips the stream again).
+template <class S, bool HOT, bool PROF, bool DBG, bool OCC2 = false, bool PIPE = false, int PART = 0, bool SLOT = false>
+__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, PART == 2 ? 6 : PART == 3 ? 4 : OCC2 ? 2 : 1))) bsrnn_frame_kernel(typename BKernelArgs<SLOT>::type a) {
     static_assert(!PIPE || (!HOT && !PROF && !DBG), "the time-pipelined instantiation is the plain offline kernel");
+    static_assert(!SLOT || (!PROF && !DBG && !PIPE && PART != 3), "the slotted instantiations are the plain per-stream kernels");
     static_assert(PART == 0 || (HOT && !PROF && !DBG && !PIPE), "the split step is the per-hop streaming step");
     // PART = 3: the front of the frame alone (STFT, compress, band split -> mlp_x / mlp_sp): the stream-batched step
     // (bsrnn_sb_kernels.hip.h) runs the layers for sixteen streams per workgroup on the matrix cores
@@ -300,11 +328,24 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
     // stream, so hipcc computed them above this loop and kept them alive through the whole frame - 29 to 35 spilled registers whose scratch
     // stores, made once per workgroup, were 40 % of the kernel's HBM writes (profiles/pmc_r2_bsrnn_xt.json).  Made loop-variant they are
     // computed where they are used.
+    const int sb = bstate_row<SLOT>(a, b);           // the stream's row of every state tensor (bstate_rows: the rows of each)
+    if constexpr (SLOT) {
+        if ((unsigned int)sb >= (unsigned int)a.capacity) {
+            if (PART != 1 && mode == FE_MODE_STREAM) {
+                float* out = a.wav_out + (size_t)b * a.out_stride;
+                for (int n = tid; n < aT * H; n += kThreads) out[n] = 0.0f;
+            }
+            b += gridDim.x;
+            continue;
+        }
+    }
+    // (the layers read the slot again - bstate_row - where they form their state addresses: a scalar load of the same word, wave-uniform.  Kept in a
+    //  register through the frame, it cost the generic instantiation of the 16-channel, 2-layer shape two spilled VGPRs that its unslotted twin does not have)
     int oz = 0;
     asm volatile("" : "+v"(oz));
     const int tidv = tid + oz;
-    float* cst = a.cache_stft + (size_t)b * OVL;
-    float* cis = a.cache_istft + (size_t)b * OVL;
+    float* cst = a.cache_stft + (size_t)sb * OVL;
+    float* cis = a.cache_istft + (size_t)sb * OVL;
     float* dbg = DBG ? a.dbg + (size_t)b * a.dbg_stride : nullptr;
     auto dump = [&](int stage, const float* src, int ld) {
         if constexpr (DBG) {
@@ -419,7 +460,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
         constexpr int HPT = (kBands * HH + kThreads - 1) / kThreads;
         float hpre[HPT];
         if constexpr (!PIPE && PART != 3) {
-            const float* hg0 = a.lstm + (size_t)b * (kBands * HH);
+            const float* hg0 = a.lstm + (size_t)sb * (kBands * HH);
 #pragma unroll
             for (int q = 0; q < HPT; ++q) { const int i = tid + q * kThreads; hpre[q] = hg0[i < kBands * HH ? i : kBands * HH - 1]; }
 #pragma unroll
@@ -433,8 +474,8 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
 
 #pragma unroll 1
         for (int l = 0; l < (PART == 3 ? 0 : S::NLAY); ++l) {
-            float* hg = a.lstm + ((size_t)(2 * l) * a.B + b) * (kBands * HH);
-            float* cg = a.lstm + ((size_t)(2 * l + 1) * a.B + b) * (kBands * HH);
+            float* hg = a.lstm + ((size_t)(2 * l) * bstate_rows<SLOT>(a) + bstate_row<SLOT>(a, b)) * (kBands * HH);
+            float* cg = a.lstm + ((size_t)(2 * l + 1) * bstate_rows<SLOT>(a) + bstate_row<SLOT>(a, b)) * (kBands * HH);
             if (l == 0) BE_CLK(2);
             if constexpr (PIPE) {
                 // frame t - 1's state of this layer: wait for it, fetch h into the GEMM's A operand buffer (c is fetched in the epilogue's place)
@@ -579,7 +620,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
             if (l == 0) BE_CLK(5);
             // next layer's time-LSTM hidden state: fetched now, parked in Hs after the recurrence
             if (!PIPE && l + 1 < S::NLAY) {
-                const float* hgn = a.lstm + ((size_t)(2 * l + 2) * a.B + b) * (kBands * HH);
+                const float* hgn = a.lstm + ((size_t)(2 * l + 2) * bstate_rows<SLOT>(a) + bstate_row<SLOT>(a, b)) * (kBands * HH);
 #pragma unroll
                 for (int q = 0; q < HPT; ++q) { const int i = tid + q * kThreads; hpre[q] = hgn[i < kBands * HH ? i : kBands * HH - 1]; }
             }
@@ -1347,6 +1388,9 @@ struct BImpl {
     // (PART 2); nullptr where the stream-batched layers are not built (num_channels > 16)
     void (*launch_sb)(const BArgs&, const SbOffsets&, int total_floats, int max_wgs, hipStream_t, hipError_t*);
     const char* name = nullptr;      // the line of fe_bsrnn_shapes.def (fe_bsrnn_shape.hip.in): part of fe_last_step_kernel's answer
+    // fe_step_pool: the launches of `launch` (split = false) / `launch_split` (split = true: mlp_x / mlp_sp / mlp_pre set) with the slotted
+    // instantiations of the per-stream kernels
+    void (*launch_slots)(const BSlotArgs&, bool split, int max_wgs, hipStream_t, hipError_t*) = nullptr;
 };
 
 template <class S, bool HOT, bool PROF, bool DBG, bool OCC2 = false>
@@ -1430,6 +1474,58 @@ void blaunch_split_impl(const BArgs& a, int max_wgs, hipStream_t st, hipError_t*
     else blaunch_part<S, false, 2>(a, bpart_grid<S, 2>(a.B, max_wgs), st, err);
 }
 
+// fe_step_pool: blaunch_impl / blaunch_split_impl with the slotted instantiations (streaming mode; no debug dumps, cycle probes or fused step)
+template <class S, bool HOT, bool OCC2>
+void blaunch_one_slots(const BSlotArgs& a, int grid, hipStream_t st, hipError_t* err) {
+    const char* name = HOT ? (OCC2 ? "bsrnn_frame_kernel<per-hop, slots, two workgroups per CU>" : "bsrnn_frame_kernel<per-hop, slots>")
+                           : (OCC2 ? "bsrnn_frame_kernel<generic, slots, two workgroups per CU>" : "bsrnn_frame_kernel<generic, slots>");
+    *err = launch<&bsrnn_frame_kernel<S, HOT, false, false, OCC2, false, 0, true>>(name, dim3(grid), dim3(kThreads), BLds<S>::BYTES, st, a);
+}
+
+template <class S, bool OCC2, int PART>
+void blaunch_part_slots(const BSlotArgs& a, int grid, hipStream_t st, hipError_t* err) {
+    static_assert(PART == 1 || PART == 2, "the three-launch step's per-stream parts");
+    using LP = BLds<S, PART == 2 ? 2 : 0>;
+    const char* name = PART == 1 ? (OCC2 ? "bsrnn_frame_kernel<PART 1, slots, two workgroups per CU>" : "bsrnn_frame_kernel<PART 1, slots>") : "bsrnn_frame_kernel<PART 2, slots>";
+    *err = launch<&bsrnn_frame_kernel<S, true, false, false, OCC2, false, PART, true>>(name, dim3(grid), dim3(kThreads), LP::BYTES, st, a);
+}
+
+template <class S>
+void blaunch_slots_impl(const BSlotArgs& a, bool split, int max_wgs, hipStream_t st, hipError_t* err) {
+    constexpr bool FITS2 = 2 * BLds<S>::BYTES <= 160 * 1024 && !S::XPG;
+    const bool two = FITS2 && a.B > max_wgs;
+    if (!split) {
+        const bool hot = a.mode == FE_MODE_STREAM && a.T == 1;
+        if (two) {      // two workgroups per CU, persistent above 2 x #CUs streams
+            const int grid2 = a.B < 2 * max_wgs ? a.B : 2 * max_wgs;
+            if (hot) blaunch_one_slots<S, true, FITS2>(a, grid2, st, err);
+            else blaunch_one_slots<S, false, FITS2>(a, grid2, st, err);
+            return;
+        }
+        const int grid = a.B < max_wgs ? a.B : max_wgs;
+        if (hot) blaunch_one_slots<S, true, false>(a, grid, st, err);
+        else blaunch_one_slots<S, false, false>(a, grid, st, err);
+        return;
+    }
+    // each of the three launches reads a.slots itself: the two per-stream parts skip a stream whose slot is out of range.  The batched mask decoder
+    // between them touches no state and takes no slots; its rows are per stream, so a skipped stream's stale scratch row reaches no other stream.
+    if (S::C == 16 && !a.ov_off && a.B <= max_wgs) blaunch_ov_slots<S>(a, a.B, st, err);
+    else if (two) blaunch_part_slots<S, FITS2, 1>(a, a.B < 2 * max_wgs ? a.B : 2 * max_wgs, st, err);
+    else blaunch_part_slots<S, false, 1>(a, a.B < max_wgs ? a.B : max_wgs, st, err);
+    if (*err != hipSuccess) return;
+    {
+        BArgs am = a;
+        const bool msplit = S::C == 16 && a.B <= max_wgs;
+        am.mlp_tpw = msplit ? 0 : 1;
+        const int groups = msplit ? (a.B + 15) / 16 : (a.B + 16 * kWaves - 1) / (16 * kWaves);
+        *err = launch<&bsrnn_mlp_kernel<S>>(msplit ? "bsrnn_mlp_kernel<one 16-stream tile per workgroup>" : "bsrnn_mlp_kernel", dim3(2 * kBands * groups),
+                                            dim3(kThreads), BMlpLds<S>::BYTES, st, am);
+        if (*err != hipSuccess) return;
+    }
+    if (two) blaunch_part_slots<S, FITS2, 2>(a, bpart_grid<S, 2>(a.B, max_wgs), st, err);
+    else blaunch_part_slots<S, false, 2>(a, bpart_grid<S, 2>(a.B, max_wgs), st, err);
+}
+
 template <class S, bool MULTI>
 void blaunch_mlp_one(const BArgs& am, int groups, hipStream_t st, hipError_t* err) {
     *err = launch<&bsrnn_mlp_kernel<S, MULTI>>(nullptr, dim3(2 * kBands * groups), dim3(kThreads), BMlpLds<S>::BYTES, st, am);      // (blaunch_mlp has noted it)
@@ -1481,10 +1577,12 @@ void bdbg_stage_impl(int s, int* rows, int* cols, size_t* off) {
 
 template <class S>
 BImpl make_bimpl() {
-    return BImpl{S::C, S::NLAY, S::HOP, BLds<S>::BYTES, S::XPG ? (size_t)2 * 32 * S::G4 : (size_t)0,
+    BImpl im = BImpl{S::C, S::NLAY, S::HOP, BLds<S>::BYTES, S::XPG ? (size_t)2 * 32 * S::G4 : (size_t)0,
                  BDebugLayout<S>::total(), BDebugLayout<S>::n_stages, S::WREG, S::KSPLIT, S::NTD, &blaunch_impl<S>, &bdbg_stage_impl<S>,
                  &blaunch_pipe_impl<S>, 1,       // (the PIPE instantiation is compiled for one workgroup per CU: waves_per_eu(1, 1))
                  &blaunch_split_impl<S>, (SbLds<S>::FITS || Sb64Lds<S>::FITS) ? &blaunch_sb_impl<S> : nullptr};
+    im.launch_slots = &blaunch_slots_impl<S>;
+    return im;
 }
 
 }  // namespace fe

@@ -104,9 +104,12 @@ __device__ __forceinline__ void ov_group_barrier(unsigned int* cnt, unsigned int
 // The three-launch step pays ~4.8 us per kernel boundary (an empty bsrnn_mlp_kernel: profiles/r3zz_*) twice in a 77-us step - but a barrier
 // over sixteen workgroups on eight XCDs measured 5.9 us, and a cooperative launch ~21 us more than a plain one: NEGATIVE (81 / 102 us),
 // profiles/r6_bsrnn_fused_step.txt.  Kept behind fe_set_option("bsrnn_fused_step", 1), bit-identical to the three launches.
-template <class S, bool PROF = false, bool FUSED = false>
-__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))) bsrnn_ov_kernel(BArgs a) {
+// SLOT (fe_step_pool): the workgroup's stream b is state slot a.slots[b] of a state sized for a.capacity streams (sb, bstate_rows below); a slot out of
+// range ends the workgroup before it touches anything (this launch writes no audio: the PART 2 launch zeroes the stream's output row).
+template <class S, bool PROF = false, bool FUSED = false, bool SLOT = false>
+__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))) bsrnn_ov_kernel(typename BKernelArgs<SLOT>::type a) {
     static_assert(S::C == 16 && S::HH == 32 && S::NFFT == 512, "the role-split kernel is built for num_channels = 16");
+    static_assert(!SLOT || (!PROF && !FUSED), "the slotted instantiation is PART 1 of the three-launch step");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     using L = BOvLds<S>;
     constexpr int N = S::NFFT, H = S::HOP, OVL = S::OVL, C = S::C, HH = S::HH;
@@ -138,7 +141,11 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
     int* flg = reinterpret_cast<int*>(smem + L::FLG);
     float* XPs = smem + L::XP;
     const int b = (int)blockIdx.x;
-    float* cst = a.cache_stft + (size_t)b * OVL;
+    const int sb = bstate_row<SLOT>(a, b);           // the stream's row of every state tensor (bstate_rows: the rows of each)
+    if constexpr (SLOT) {
+        if ((unsigned int)sb >= (unsigned int)a.capacity) return;
+    }
+    float* cst = a.cache_stft + (size_t)sb * OVL;
     const size_t lsz = (size_t)kBands * HH;                      // one (h or c) tensor of a layer and stream
 
     OV_CLK(0);
@@ -220,8 +227,8 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
     // the layer's weights are there (pre_mma)
     auto pre_load = [&](int l, auto T_, float (&af)[KSH]) {
         constexpr int T = decltype(T_)::value;
-        const float* hg = a.lstm + ((size_t)(2 * l) * a.B + b) * lsz;
-        const float* cg = hg + (size_t)a.B * lsz;
+        const float* hg = a.lstm + ((size_t)(2 * l) * bstate_rows<SLOT>(a) + sb) * lsz;
+        const float* cg = hg + (size_t)bstate_rows<SLOT>(a) * lsz;
         const float* hr = hg + ov_band<T>(li) * HH + lg;
 #pragma unroll
         for (int ks = 0; ks < KSH; ++ks) af[ks] = hr[4 * ks];
@@ -423,9 +430,9 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
         cclk(4);
         if (valid) {
             // the layer's new (h, c) -> the state tensors: units 16 ct + 4 lg + r of band li, 16 bytes each
-            float* hg = a.lstm + ((size_t)(2 * l) * a.B + b) * lsz + band * HH + 16 * ct + 4 * lg;
+            float* hg = a.lstm + ((size_t)(2 * l) * bstate_rows<SLOT>(a) + sb) * lsz + band * HH + 16 * ct + 4 * lg;
             *reinterpret_cast<f32x4*>(hg) = hn;
-            *reinterpret_cast<f32x4*>(hg + (size_t)a.B * lsz) = cn;
+            *reinterpret_cast<f32x4*>(hg + (size_t)bstate_rows<SLOT>(a) * lsz) = cn;
         }
         // fc_time + residual (:382-384): x^T += W h'^T + b.  Both waves of the pair compute it, in the SAME order (units 0..15 into c0,
         // 16..31 into c1, whoever produced them): their x must agree bit for bit - either one's copy is read by other waves
@@ -597,7 +604,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
         typename DI::InvConst idc;
         DI::load(idc, wb, o, wave);
         constexpr int OPT = (N + kThreads - 1) / kThreads, FPT = (kBins + kThreads - 1) / kThreads;
-        float* cis = a.cache_istft + (size_t)b * OVL;
+        float* cis = a.cache_istft + (size_t)sb * OVL;
         float ocis[OPT], owin[OPT];
         int bra[FPT], brg[FPT];
 #pragma unroll
@@ -700,6 +707,12 @@ void blaunch_ov(const BArgs& a, int grid, hipStream_t st, hipError_t* err) {
     } else {
         *err = hipErrorInvalidValue;
     }
+}
+
+template <class S>
+void blaunch_ov_slots(const BSlotArgs& a, int grid, hipStream_t st, hipError_t* err) {
+    if constexpr (S::C == 16) *err = launch<&bsrnn_ov_kernel<S, false, false, true>>("bsrnn_ov_kernel<slots>", dim3(grid), dim3(kThreads), BOvLds<S>::BYTES, st, a);
+    else *err = hipErrorInvalidValue;
 }
 
 }  // namespace fe

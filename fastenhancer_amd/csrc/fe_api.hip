@@ -1290,6 +1290,31 @@ int fe_step_slots(fe_handle* h, const float* wav_in_dev, size_t in_stride, float
         });
 }
 
+// fe_step_pool: fe_step_slots for every family with a streaming state.  FastEnhancer's handles take fe_step_slots' path as it stands (the noncausal
+// model its refusal, which is fe_step's); a baseline family runs the per-stream kernels fe_step(B = n, T) picks, in their slotted instantiations,
+// with fe_step_slots' checks in fe_step_slots' order.
+int fe_step_pool(fe_handle* h, const float* wav_in_dev, size_t in_stride, float* state_dev, int capacity, const int* slots_dev,
+                 float* wav_out_dev, size_t out_stride, int n, int T, void* stream) {
+    if (!h) return fail(FE_ERR_INVALID_ARG, "null handle");
+    if (h->cfg.arch == FE_ARCH_FASTENHANCER)
+        return fe_step_slots(h, wav_in_dev, in_stride, state_dev, capacity, slots_dev, wav_out_dev, out_stride, n, T, stream);
+    int rc = check_ready(h);
+    if (rc != FE_OK) return rc;
+    KernelLogScope klog_(h);
+    rc = check_step_args(h, nullptr, kBadSlotArgs, wav_in_dev && state_dev && slots_dev && wav_out_dev, n, capacity, T, in_stride, out_stride);
+    if (rc != FE_OK) return rc;
+    visit_baseline(h->cfg.arch, [&](auto F) {
+        using Fam = decltype(F);
+        typename Fam::SlotArgs a{};
+        static_cast<typename Fam::Args&>(a) = F.args(h, n, T);
+        a.capacity = capacity;
+        a.slots = slots_dev;
+        F.state(a) = stream_io(a, wav_in_dev, in_stride, wav_out_dev, out_stride, state_dev, state_layout(h, capacity));
+        rc = F.launch_slots(h, a, stream);
+    });
+    return rc;
+}
+
 // fe_step_pinned / fe_step_slots_pinned: `count` floats from p must be page-locked host memory with a device mapping on the current device
 // (hipHostMalloc / hipHostRegister: torch's pin_memory()).  Anything else - pageable or device memory - would make the kernel take a page
 // fault, so it is refused here, before any launch.  Both ends of the range are looked up; *dev = the device view of p.

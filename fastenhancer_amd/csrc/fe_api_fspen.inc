@@ -7,6 +7,7 @@ const int kSdN[5] = {2, 3, 5, 10, 20};                    // SubbandDecoder outp
 // The family as fe_api.hip's shared baseline-family paths see it (visit_baseline: the stream and spec steps, offline, the buffer sizes, debug stages)
 struct FspenFamily {
     using Args = fe::FArgs;
+    using SlotArgs = fe::FSlotArgs;
     static const fe::FImpl* impl(const fe_handle* h) { return h->fimpl; }
     static const char* shape_name(const fe_handle*) { return "fspen"; }
     static float*& state(Args& a) { return a.gru; }
@@ -28,6 +29,7 @@ struct FspenFamily {
     static int pack_weights(fe_handle* h, const Blob& S, std::vector<float>* out);
     static int ensure_sb(fe_handle* h, int B);
     static int launch(fe_handle* h, const Args& a, void* stream);
+    static int launch_slots(fe_handle* h, const SlotArgs& a, void* stream);
     static const char* stage_name(const fe_handle*, int idx);
     static double macs(const fe_handle* h);
 };
@@ -342,6 +344,13 @@ int FspenFamily::launch(fe_handle* h, const fe::FArgs& a_in, void* stream) {
         return launch_rc(e);
     }
     h->fimpl->launch(a, h->max_wgs, (hipStream_t)stream, &e);
+    return launch_rc(e);
+}
+
+// fe_step_pool: the per-stream kernel, slotted, at every batch size (the stream-batched middle's tensors are laid out per call tile)
+int FspenFamily::launch_slots(fe_handle* h, const fe::FSlotArgs& a, void* stream) {
+    hipError_t e = hipSuccess;
+    h->fimpl->launch_slots(a, h->max_wgs, (hipStream_t)stream, &e);
     return launch_rc(e);
 }
 

@@ -4,6 +4,7 @@
 // The family as fe_api.hip's shared baseline-family paths see it (visit_baseline: the stream and spec steps, offline, the buffer sizes, debug stages)
 struct LisennetFamily {
     using Args = fe::LArgs;
+    using SlotArgs = fe::LSlotArgs;
     static const fe::LImpl* impl(const fe_handle* h) { return h->limpl; }
     static const char* shape_name(const fe_handle*) { return "lisennet"; }
     static float*& state(Args& a) { return a.cache; }
@@ -33,6 +34,7 @@ struct LisennetFamily {
     static int pack_weights(fe_handle* h, const Blob& S, std::vector<float>* out);
     static int ensure_sb(fe_handle* h, int B);
     static int launch(fe_handle* h, const Args& a, void* stream);
+    static int launch_slots(fe_handle* h, const SlotArgs& a, void* stream);
     static const char* stage_name(const fe_handle*, int idx);
     static double macs(const fe_handle* h);
 };
@@ -441,6 +443,13 @@ int LisennetFamily::launch(fe_handle* h, const fe::LArgs& a_in, void* stream) {
         return launch_rc(e);
     }
     h->limpl->launch(a, h->max_wgs, (hipStream_t)stream, &e);
+    return launch_rc(e);
+}
+
+// fe_step_pool: the per-stream kernel, slotted, at every batch size (the stream-batched middle's tensors are laid out per call tile)
+int LisennetFamily::launch_slots(fe_handle* h, const fe::LSlotArgs& a, void* stream) {
+    hipError_t e = hipSuccess;
+    h->limpl->launch_slots(a, h->max_wgs, (hipStream_t)stream, &e);
     return launch_rc(e);
 }
 

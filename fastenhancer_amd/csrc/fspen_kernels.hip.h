@@ -124,6 +124,16 @@ struct FArgs {
     float* carry;             // [B][FCarry::FLOATS] the front's LDS regions that the DPE kernel (cat) and the tail read: compressed spectrum, encoder outputs, sub-band / full-band features
 };
 
+// The slot-indexed step (fe_step_pool; the SLOT instantiation): FArgs with two fields at the end.  Call stream b is state slot slots[b] of a state
+// sized for `capacity` streams - every state address takes (slot, capacity) where the plain step takes (b, B); audio rows stay in call order.
+// (A type of its own, so that the other instantiations keep their kernel-argument block - and their code - as they were.)
+struct FSlotArgs : FArgs {
+    int capacity;
+    const int* slots;         // [B] device int32; a slot outside [0, capacity) gets zero output rows and touches no state
+};
+template <bool SLOT> struct FKernelArgs { using type = FArgs; };
+template <> struct FKernelArgs<true> { using type = FSlotArgs; };
+
 // debug stages (fe_debug_step): name, rows, cols as dumped (row-major)
 struct FDebugLayout {
     static constexpr int n_stages = 16;
@@ -298,9 +308,12 @@ __device__ __forceinline__ float row_dot(const float (&w)[12], float h, float ac
 #ifndef FS_WPE_FRONT
 #define FS_WPE_FRONT 4
 #endif
-template <class S, bool PROF, bool DBG, bool PIPE = false, int PART = 0>
-__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(PART == 1 ? FS_WPE_FRONT : FS_WPE, PART == 1 ? FS_WPE_FRONT : FS_WPE))) fspen_frame_kernel(FArgs a) {
+// SLOT (fe_step_pool): stream b's state is slot a.slots[b] of a state sized for a.capacity streams (sb, nst below); a slot out of range skips
+// the stream - no state access, zero output rows.  Audio rows stay indexed by b.
+template <class S, bool PROF, bool DBG, bool PIPE = false, int PART = 0, bool SLOT = false>
+__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(PART == 1 ? FS_WPE_FRONT : FS_WPE, PART == 1 ? FS_WPE_FRONT : FS_WPE))) fspen_frame_kernel(typename FKernelArgs<SLOT>::type a) {
     static_assert(!PIPE || (!PROF && !DBG), "the time-pipelined instantiation is the plain offline kernel");
+    static_assert(!SLOT || (!PROF && !DBG && !PIPE && PART == 0), "the slotted instantiation is the plain per-stream kernel");
     static_assert(PART == 0 || (!PROF && !DBG && !PIPE), "the split step is the plain per-hop kernel");
     __shared__ __attribute__((aligned(16))) float smem[PART == 1 ? FLds::FRONT_TOTAL : FLds::TOTAL];
     using L = FLds;
@@ -332,6 +345,19 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(P
     using HO = HandOver<PIPE>;                       // inter-GRU state exchange between the workgroups of an utterance (fe_handover.h)
 #pragma unroll 1
     do {
+    int sb = b, nst = a.B;                           // the stream's row of every state tensor, and the rows of each
+    if constexpr (SLOT) {
+        nst = a.capacity;
+        sb = __builtin_amdgcn_readfirstlane(a.slots[b]);
+        if ((unsigned int)sb >= (unsigned int)nst) {
+            if (mode == FE_MODE_STREAM) {
+                float* out = a.wav_out + (size_t)b * a.out_stride;
+                for (int n = tid0; n < aT * H; n += kThreads) out[n] = 0.0f;
+            }
+            b += gridDim.x;
+            continue;
+        }
+    }
     // (per-stream pointers are derived from the kernel arguments where they are used, not kept live through the frame)
     float* dbg = DBG ? a.dbg + (size_t)b * a.dbg_stride : nullptr;
     // dump(stage, f): element (r, c) of the stage = f(r, c)
@@ -369,7 +395,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(P
         float* ein = smem + L::EIN;
         if (mode != FE_MODE_SPEC) {
             const WView win = wp + P::WINDOW;
-            float* cst = a.cache_stft + (size_t)b * OVL;
+            float* cst = a.cache_stft + (size_t)sb * OVL;
             if (mode == FE_MODE_STREAM) {
                 // PIPE (a streaming chunk on the time pipeline, fe_step_backlog): frame t is samples t H .. t H + N - 1 of [the call's old
                 // cache_stft | the chunk] - sample n is cst[t H + n] while that index is inside the cache, else chunk[t H + n - OVL], which is
@@ -640,7 +666,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(P
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
                 const int f = (tid >> 4) + 16 * q, g = f >> 2;
-                hp[q] = PIPE ? 0.0f : a.gru[(((size_t)(blk * S::G + g) * a.B + b) * S::FG + (f & 3)) * S::C + (tid & 15)];
+                hp[q] = PIPE ? 0.0f : a.gru[(((size_t)(blk * S::G + g) * nst + sb) * S::FG + (f & 3)) * S::C + (tid & 15)];
             }
             // ---- intra GRU input projections: gi[d][f][g48] = x[f] . W_ih^T + bias
             if (tid < 192) {
@@ -762,7 +788,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(P
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
                     const int f = (tid >> 4) + 16 * q, g = f >> 2;
-                    hprev[f * 16 + (tid & 15)] = HO::ld(a.gru + (((size_t)(blk * S::G + g) * a.B + b) * S::FG + (f & 3)) * S::C + (tid & 15));
+                    hprev[f * 16 + (tid & 15)] = HO::ld(a.gru + (((size_t)(blk * S::G + g) * nst + sb) * S::FG + (f & 3)) * S::C + (tid & 15));
                 }
                 __syncthreads();
             }
@@ -788,7 +814,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(P
                     const float n = tanh_f(in_ + r * hnn);
                     const float hnew = (1.0f - z) * n + z * hprev[f * 16 + c];
                     hn[f * 16 + c] = hnew;
-                    HO::st(a.gru + (((size_t)(blk * S::G + ig_) * a.B + b) * S::FG + fl) * S::C + c, hnew);
+                    HO::st(a.gru + (((size_t)(blk * S::G + ig_) * nst + sb) * S::FG + fl) * S::C + c, hnew);
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -1128,7 +1154,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(P
         if (mode != FE_MODE_SPEC) {
             float2* yv = fft_lds<S, true>(fa, fb, tw);
             float2* spare = (yv == fa) ? fb : fa;
-            float* cis = a.cache_istft + (size_t)b * OVL;
+            float* cis = a.cache_istft + (size_t)sb * OVL;
             const WView wi = wp + (mode == FE_MODE_STREAM ? P::WINDOW_I : P::WINDOW);
             float* xo = reinterpret_cast<float*>(spare);
             const float invN = 1.0f / (float)N;
@@ -1195,6 +1221,7 @@ struct FImpl {
     // per-hop step of large batches: front -> DPE blocks batched over the streams (fspen_sb_kernels.hip.h) -> tail; a.tok / a.carry set
     void (*launch_sb)(const FArgs&, int max_wgs, hipStream_t, hipError_t*);
     size_t split_floats_per_stream;      // tok + carry
+    void (*launch_slots)(const FSlotArgs&, int max_wgs, hipStream_t, hipError_t*);      // fe_step_pool: flaunch_impl's launch with the slotted instantiation
 };
 
 template <class S>
@@ -1216,6 +1243,16 @@ void flaunch_impl(const FArgs& a, int max_wgs, hipStream_t st, hipError_t* err) 
     if (a.dbg != nullptr) hipLaunchKernelGGL((fspen_frame_kernel<S, false, true>), dim3(grid), dim3(kThreads), 0, st, a);
     else if (a.clk != nullptr) hipLaunchKernelGGL((fspen_frame_kernel<S, true, false>), dim3(grid), dim3(kThreads), 0, st, a);
     else hipLaunchKernelGGL((fspen_frame_kernel<S, false, false>), dim3(grid), dim3(kThreads), 0, st, a);
+    *err = hipGetLastError();
+}
+
+template <class S>
+void flaunch_slots_impl(const FSlotArgs& a, int max_wgs, hipStream_t st, hipError_t* err) {
+    constexpr int OCC_LDS = (160 * 1024) / (FLds::TOTAL * 4);
+    constexpr int OCC = OCC_LDS < FS_WPE ? OCC_LDS : FS_WPE;
+    const int slots = max_wgs * OCC;
+    note_kernel("fspen_frame_kernel<slots>");
+    hipLaunchKernelGGL((fspen_frame_kernel<S, false, false, false, 0, true>), dim3(a.B < slots ? a.B : slots), dim3(kThreads), 0, st, a);
     *err = hipGetLastError();
 }
 
@@ -1247,7 +1284,7 @@ template <class S>
 FImpl make_fimpl() {
     constexpr int OCC_LDS = (160 * 1024) / (FLds::TOTAL * 4);
     return FImpl{S::HOP, (size_t)FLds::TOTAL * 4, FDebugLayout::total(), FDebugLayout::n_stages, (size_t)FPk::TOTAL, &flaunch_impl<S>, &fdbg_stage_impl,
-                 &flaunch_pipe_impl<S>, OCC_LDS < FS_WPE ? OCC_LDS : FS_WPE, S::NB, &flaunch_sb_impl<S>, (size_t)2048 + FCarry::FLOATS + 1024};
+                 &flaunch_pipe_impl<S>, OCC_LDS < FS_WPE ? OCC_LDS : FS_WPE, S::NB, &flaunch_sb_impl<S>, (size_t)2048 + FCarry::FLOATS + 1024, &flaunch_slots_impl<S>};
 }
 
 }  // namespace fe

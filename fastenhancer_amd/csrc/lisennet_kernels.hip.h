@@ -90,6 +90,16 @@ struct LArgs {
     float* carry;             // r6, the three-launch per-hop step of large batches (lisennet_sb_kernels.hip.h): [tiles][LCarry::TILE] [B][LCarry::SP]
 };
 
+// The slot-indexed step (fe_step_pool; the SLOT instantiation): LArgs with two fields at the end.  Call stream b is state slot slots[b] of a state
+// sized for `capacity` streams - every state address takes (slot, capacity) where the plain step takes (b, B); audio rows stay in call order.
+// (A type of its own, so that the other instantiations keep their kernel-argument block - and their code - as they were.)
+struct LSlotArgs : LArgs {
+    int capacity;
+    const int* slots;         // [B] device int32; a slot outside [0, capacity) gets zero output rows and touches no state
+};
+template <bool SLOT> struct LKernelArgs { using type = LArgs; };
+template <> struct LKernelArgs<true> { using type = LSlotArgs; };
+
 // debug stages: 0 spec_in [257][2], 1 compressed [257][2], 2 features [3][257], 3 encoder.conv_1 [4][257], 4 encoder.conv_2 [8][128],
 // 5 encoder.conv_3 [12][64], 6 encoder.conv_4 [16][32], 7+3b blocks.b.intra [32][16], 8+3b blocks.b.inter [32][16], 9+3b blocks.b [16][32],
 // 13 decoder.up3 [4][256], 14 mask [257][2], 15 spec_out [257][2]
@@ -172,9 +182,12 @@ namespace fe {
 // of fe_handover.h, one counter per (utterance, cache).
 // PART (r6): 0 = the whole frame; 1 = STFT .. encoder.conv_2 of a per-hop step whose middle runs batched over the streams (lisennet_sb_kernel): x2, its
 // cached frame and the compressed spectrum go to the carry; 2 = that step's tail (decoder cache, mask conv .. iSTFT) from the carry's up3 output.
-template <class S, bool PROF, bool DBG, bool PIPE = false, int PART = 0>
-__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((PART == 0 || DBG) ? 2 : 8, (PART == 0 || DBG) ? 2 : 8))) lisennet_frame_kernel(LArgs a) {
+// SLOT (fe_step_pool): stream b's state is slot a.slots[b] of a state sized for a.capacity streams (sb, nst below); a slot out of range skips
+// the stream - no state access, zero output rows.  Audio rows stay indexed by b.
+template <class S, bool PROF, bool DBG, bool PIPE = false, int PART = 0, bool SLOT = false>
+__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((PART == 0 || DBG) ? 2 : 8, (PART == 0 || DBG) ? 2 : 8))) lisennet_frame_kernel(typename LKernelArgs<SLOT>::type a) {
     static_assert(!PIPE || (!PROF && !DBG), "the time-pipelined instantiation is the plain offline kernel");
+    static_assert(!SLOT || (!PROF && !DBG && !PIPE && PART == 0), "the slotted instantiation is the plain per-stream kernel");
     static_assert(PART == 0 || !PIPE, "the split step is a streaming step");
     __shared__ __attribute__((aligned(16))) float smem[LLdsT<PART>::TOTAL];
     using L = LLdsT<PART>;
@@ -201,6 +214,19 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((
     using HO = HandOver<PIPE>;                       // cache exchange between the workgroups of an utterance (fe_handover.h)
 #pragma unroll 1
     do {
+    int sb = b, nst = a.B;                           // the stream's row of every state tensor, and the rows of each
+    if constexpr (SLOT) {
+        nst = a.capacity;
+        sb = __builtin_amdgcn_readfirstlane(a.slots[b]);
+        if ((unsigned int)sb >= (unsigned int)nst) {
+            if (mode == FE_MODE_STREAM) {
+                float* out = a.wav_out + (size_t)b * a.out_stride;
+                for (int n = tid0; n < aT * H; n += kThreads) out[n] = 0.0f;
+            }
+            b += gridDim.x;
+            continue;
+        }
+    }
     float* dbg = DBG ? a.dbg + (size_t)b * a.dbg_stride : nullptr;
     auto dump = [&](int stage, auto&& f) {
         if constexpr (DBG) {
@@ -217,7 +243,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((
     };
     // per-stream cache pointers (cache-major state)
     auto cache_ptr = [&](int off_floats_per_stream_sum, int per_stream) -> float* {
-        return a.cache + (size_t)off_floats_per_stream_sum * a.B + (size_t)b * per_stream;
+        return a.cache + (size_t)off_floats_per_stream_sum * nst + (size_t)sb * per_stream;
     };
 
 #pragma unroll 1
@@ -285,7 +311,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((
         if constexpr (PART != 2) {
         if (mode != FE_MODE_SPEC) {
             const float* win = wp + P::WINDOW;
-            float* cst = a.cache_stft + (size_t)b * OVL;
+            float* cst = a.cache_stft + (size_t)sb * OVL;
             if (mode == FE_MODE_STREAM) {
                 const float* xin = a.wav_in + (size_t)b * a.in_stride + (size_t)t * H;
                 for (int n = tid; n < N; n += kThreads) {
@@ -876,7 +902,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((
         if (mode != FE_MODE_SPEC) {
             float2* yv = fft_lds<S, true>(fa, fb, tw);
             float2* spare = (yv == fa) ? fb : fa;
-            float* cis = a.cache_istft + (size_t)b * OVL;
+            float* cis = a.cache_istft + (size_t)sb * OVL;
             const float* wi = wp + (mode == FE_MODE_STREAM ? P::WINDOW_I : P::WINDOW);
             float* xo = reinterpret_cast<float*>(spare);
             const float invN = 1.0f / (float)N;
@@ -937,6 +963,7 @@ struct LImpl {
     int occ;                  // workgroups per CU
     int nsite;                // caches handed from frame to frame (counters per stream)
     void (*launch_sb)(const LArgs&, int max_wgs, hipStream_t, hipError_t*);      // r6: the per-hop step of a large batch in three launches, the middle batched over the streams
+    void (*launch_slots)(const LSlotArgs&, int max_wgs, hipStream_t, hipError_t*);      // fe_step_pool: llaunch_impl's launch with the slotted instantiation
 };
 
 template <class S>
@@ -957,6 +984,16 @@ void llaunch_impl(const LArgs& a, int max_wgs, hipStream_t st, hipError_t* err) 
     if (a.dbg != nullptr) hipLaunchKernelGGL((lisennet_frame_kernel<S, false, true>), dim3(grid), dim3(kThreads), 0, st, a);
     else if (a.clk != nullptr) hipLaunchKernelGGL((lisennet_frame_kernel<S, true, false>), dim3(grid), dim3(kThreads), 0, st, a);
     else hipLaunchKernelGGL((lisennet_frame_kernel<S, false, false>), dim3(grid), dim3(kThreads), 0, st, a);
+    *err = hipGetLastError();
+}
+
+template <class S>
+void llaunch_slots_impl(const LSlotArgs& a, int max_wgs, hipStream_t st, hipError_t* err) {
+    constexpr int OCC_LDS = (160 * 1024) / (LLds::TOTAL * 4);
+    constexpr int OCC = OCC_LDS < 2 ? OCC_LDS : 2;
+    const int slots = max_wgs * OCC;
+    note_kernel("lisennet_frame_kernel<slots>");
+    hipLaunchKernelGGL((lisennet_frame_kernel<S, false, false, false, 0, true>), dim3(a.B < slots ? a.B : slots), dim3(kThreads), 0, st, a);
     *err = hipGetLastError();
 }
 
@@ -993,7 +1030,7 @@ template <class S>
 LImpl make_limpl() {
     constexpr int OCC_LDS = (160 * 1024) / (LLds::TOTAL * 4);
     return LImpl{S::HOP, (size_t)LLds::TOTAL * 4, LDebugLayout::total(), LDebugLayout::n_stages, (size_t)LPk::TOTAL + LSbPk::TOTAL, (size_t)S::CACHE_FLOATS,
-                 &llaunch_impl<S>, &ldbg_stage_impl, &llaunch_pipe_impl<S>, OCC_LDS < 2 ? OCC_LDS : 2, 5 + 2 * S::NB, &llaunch_sb_impl<S>};
+                 &llaunch_impl<S>, &ldbg_stage_impl, &llaunch_pipe_impl<S>, OCC_LDS < 2 ? OCC_LDS : 2, 5 + 2 * S::NB, &llaunch_sb_impl<S>, &llaunch_slots_impl<S>};
 }
 
 }  // namespace fe

@@ -141,6 +141,16 @@ class Engine:
         self._require_gpu()
         return torch.zeros(self.state_floats(B), dtype=torch.float32, device=self.device)
 
+    def init_state(self, state: Tensor, B: int) -> Tensor:
+        """fe_state_init: `state` (sized for B streams) zeroed, and the engine's per-hop scratch sized for B streams - what step_pool, which
+        allocates nothing, runs BSRNN's three-launch step on (step() grows that scratch itself on its first call)."""
+        self._require_gpu()
+        if not isinstance(state, Tensor) or not state.is_cuda or state.dtype != torch.float32 or not state.is_contiguous() or state.numel() != self.state_floats(B):
+            raise ValueError(f"state must be a contiguous float32 device tensor of state_floats({B}) = {self.state_floats(B)} floats")
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.fe_state_init(self._h, _ptr(state), int(B), _stream(self.device)), "fe_state_init")
+        return state
+
     def split_state(self, state: Tensor, B: int, head0: bool = False) -> List[Tensor]:
         """Views of the opaque state as the reference cache list [cache_stft [B,N-H], cache_istft [B,N-H], *the model's caches]
         (scripts/export_onnx.py:43-46).  The dptransformer variant's caches are copies unless head0 (family.py)."""
@@ -157,9 +167,10 @@ class Engine:
 
     # ------------------------------------------------------------------ compute
     def _step(self, wav_in: Tensor, state: Tensor, wav_out: Optional[Tensor], T: int, capacity: Optional[int] = None, slots=None,
-              pinned: bool = False) -> Tensor:
-        """The streaming step behind step / step_slots / step_pinned / step_slots_pinned.  slots (with capacity): the slot-indexed entry
-        points, `state` sized for `capacity` streams; pinned: wav_in / wav_out are page-locked host memory instead of device memory."""
+              pinned: bool = False, pool: bool = False) -> Tensor:
+        """The streaming step behind step / step_slots / step_pool / step_pinned / step_slots_pinned.  slots (with capacity): the slot-indexed
+        entry points, `state` sized for `capacity` streams; pinned: wav_in / wav_out are page-locked host memory instead of device memory;
+        pool (slotted, device audio): fe_step_pool, the slotted step of every family, instead of fe_step_slots."""
         slotted = slots is not None
         H = self.cfg.hop_size
         if pinned:
@@ -177,7 +188,7 @@ class Engine:
         assert (state.is_cuda or not pinned) and state.numel() == self.state_floats(capacity if slotted else n) and state.is_contiguous()
         if wav_out is None:
             wav_out = torch.empty(n, T * H, dtype=torch.float32, device=wav_in.device)
-        name = "fe_step" + ("_slots" if slotted else "") + ("_pinned" if pinned else "")
+        name = "fe_step_pool" if pool else "fe_step" + ("_slots" if slotted else "") + ("_pinned" if pinned else "")
         args = [self._h, _ptr(wav_in), wav_in.stride(0) if n > 1 else T * H, _ptr(state)]
         args += [int(capacity), _ptr(sl)] if slotted else []
         args += [_ptr(wav_out), wav_out.stride(0) if n > 1 else T * H, n, T, _stream(self.device)]
@@ -288,6 +299,11 @@ class Engine:
         """fe_step_slots: wav_in [n, T*H] (row i = state slot slots[i]) -> wav_out [n, T*H]; only the named slots of `state`
         (sized for `capacity` streams) are updated.  slots: a list / CPU tensor (checked) or a CUDA int32 tensor (not checked)."""
         return self._step(wav_in, state, wav_out, T, capacity, slots)
+
+    def step_pool(self, wav_in: Tensor, state: Tensor, capacity: int, slots, wav_out: Optional[Tensor] = None, T: int = 1) -> Tensor:
+        """fe_step_pool: step_slots for every family with a streaming state - FastEnhancer's models as step_slots runs them, BSRNN, FSPEN and
+        LiSenNet on the slotted forms of their per-stream kernels.  Arguments and checks as for step_slots."""
+        return self._step(wav_in, state, wav_out, T, capacity, slots, pool=True)
 
     def reset_slots(self, state: Tensor, capacity: int, slots) -> None:
         """fe_state_reset_slots: the named slots of `state` (sized for `capacity` streams) as fe_state_init leaves them (zero)."""

@@ -46,6 +46,7 @@ class Family:
     order: Callable = lambda cfg, caches: [t.reshape(-1) for t in caches]               # caches -> flat pieces of h, in its order
     start: Callable = lambda cfg, h, B: None                                            # zeroed h -> the state of a call without caches
     backlog: bool = False           # chunks of many hops go through Engine.step_backlog (fe_step_backlog pipelines the family), not step_chunk
+    pool: bool = False              # the slotted step of live streams is Engine.step_pool (fe_step_slots refuses the family), not step_slots
 
     def spec_bins(self, cfg) -> int:
         return cfg.F0 + (1 if self.nyquist else 0)
@@ -137,11 +138,11 @@ _FAMILIES = {
     FEConfig: Family(_lib.FE_ARCH_FASTENHANCER, _fe_config, W.fold_state_dict, W.check_fused, W.default_state_dict, nyquist=False,
                      split=_fe_split, order=_fe_order, start=_fe_start),
     BSRNNConfig: Family(_lib.FE_ARCH_BSRNN, _bsrnn_config, W.bsrnn_fold_state_dict, _shapes(W.bsrnn_expected_fused_shapes),
-                        W.bsrnn_default_state_dict, backlog=True),
+                        W.bsrnn_default_state_dict, backlog=True, pool=True),
     FSPENConfig: Family(_lib.FE_ARCH_FSPEN, _fspen_config, W.fspen_fold_state_dict, _shapes(W.fspen_expected_fused_shapes),
-                        W.fspen_default_state_dict, backlog=True),
+                        W.fspen_default_state_dict, backlog=True, pool=True),
     LiSenNetConfig: Family(_lib.FE_ARCH_LISENNET, _lisennet_config, W.lisennet_state_dict, _shapes(W.lisennet_expected_shapes),
-                           W.lisennet_default_state_dict),
+                           W.lisennet_default_state_dict, pool=True),
 }
 
 
@@ -155,3 +156,11 @@ def chunk_step(engine) -> Callable:
     has always been called; for LiSenNet both are the walk of step()."""
     fam = _FAMILIES.get(type(getattr(engine, "cfg", None)))
     return engine.step_backlog if fam is not None and fam.backlog else engine.step_chunk
+
+
+def slot_step(engine) -> Callable:
+    """The engine's call for one step of the named slots of a state buffer (StreamPool.step): step_pool for the families whose slotted
+    step is fe_step_pool's (BSRNN, FSPEN, LiSenNet), step_slots for FastEnhancer - its own path as it has always been called - and for an
+    engine object without a family description."""
+    fam = _FAMILIES.get(type(getattr(engine, "cfg", None)))
+    return engine.step_pool if fam is not None and fam.pool else engine.step_slots

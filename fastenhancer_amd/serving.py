@@ -1,4 +1,4 @@
-"""StreamPool: streams that join and leave one state buffer (fe_step_slots / fe_state_reset_slots).
+"""StreamPool: streams that join and leave one state buffer (fe_step_slots / fe_state_reset_slots; BSRNN, FSPEN, LiSenNet: fe_step_pool).
 
 The pool owns a state buffer sized for `capacity` streams.  open() hands out a free slot and resets its state; close() frees it;
 step() advances only the streams named, each reading and writing its own slot - no gather or scatter of state; step_host() does the
@@ -27,7 +27,7 @@ from torch import Tensor
 
 from . import _lib
 from .engine import Engine
-from .family import chunk_step
+from .family import chunk_step, slot_step
 
 
 class StreamPool:
@@ -36,9 +36,16 @@ class StreamPool:
             raise ValueError("capacity must be at least 1")
         self.engine = engine
         self.capacity = int(capacity)
-        self.state = engine.new_state(self.capacity)
+        self.state = self._new_state(self.capacity)
         self._free: List[int] = list(range(self.capacity - 1, -1, -1))      # popped from the end: lowest slot first
         self._open = set()
+
+    def _new_state(self, capacity: int) -> Tensor:
+        """engine.new_state; for a family that steps through fe_step_pool also fe_state_init, which sizes the scratch that step runs on (it
+        allocates nothing itself: BSRNN's three-launch step needs its scratch sized for the pool's capacity beforehand)"""
+        state = self.engine.new_state(capacity)
+        fam = getattr(self.engine, "family", None)
+        return self.engine.init_state(state, capacity) if fam is not None and getattr(fam, "pool", False) and state.is_cuda else state
 
     @property
     def active(self) -> List[int]:
@@ -52,8 +59,8 @@ class StreamPool:
         fam = getattr(self.engine, "family", None)
         if fam is not None and fam.arch != _lib.FE_ARCH_FASTENHANCER:
             # BSRNN, FSPEN, LiSenNet: fe_state_reset_slots is built for the FastEnhancer family; their fresh state is zeros, and the state
-            # records are built for every family - the slot takes a zero record (such a pool serves catch_up, export and import; the
-            # slotted steps stay FastEnhancer's)
+            # records are built for every family - the slot takes a zero record (such a pool steps through fe_step_pool; step_host and
+            # PacketPool stay FastEnhancer's)
             fresh = torch.zeros(1, self.engine.record_floats, dtype=torch.float32, device=self.state.device)
             self.engine.import_slots(self.state, self.capacity, [slot], fresh)
         else:
@@ -68,11 +75,12 @@ class StreamPool:
         self._free.append(slot)
 
     def step(self, slots: Sequence[int], wav_in: Tensor, wav_out: Optional[Tensor] = None, T: int = 1) -> Tensor:
-        """wav_in [n, T*H] (row i: stream slots[i]) -> wav_out [n, T*H]; the other streams' state is untouched."""
+        """wav_in [n, T*H] (row i: stream slots[i]) -> wav_out [n, T*H]; the other streams' state is untouched.  (Engine.step_slots; a
+        BSRNN, FSPEN or LiSenNet engine: Engine.step_pool.)"""
         for s in slots:
             if s not in self._open:
                 raise ValueError(f"slot {s} is not open")
-        return self.engine.step_slots(wav_in, self.state, self.capacity, list(slots), wav_out=wav_out, T=T)
+        return slot_step(self.engine)(wav_in, self.state, self.capacity, list(slots), wav_out=wav_out, T=T)
 
     def step_host(self, slots: Sequence[int], wav_in: Tensor, wav_out: Optional[Tensor] = None, T: int = 1) -> Tensor:
         """step() for audio in page-locked HOST memory (fe_step_slots_pinned): wav_in [n, T*H] pinned -> wav_out [n, T*H] pinned
@@ -159,7 +167,7 @@ class StreamPool:
             raise ValueError(f"slot {max(self._open)} is open: the pool cannot shrink below {1 + max(self._open)} slots")
         if capacity == self.capacity:
             return
-        state = self.engine.new_state(capacity)
+        state = self._new_state(capacity)
         if self._open:
             slots = sorted(self._open)
             self.engine.import_slots(state, capacity, slots, self.engine.export_slots(self.state, self.capacity, slots))

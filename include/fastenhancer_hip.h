@@ -174,6 +174,24 @@ int fe_step(fe_handle* h, const float* wav_in_dev, size_t in_stride, float* stat
  *     FE_ERR_UNSUPPORTED_CONFIG, and so does the noncausal model, as for fe_step. */
 int fe_step_slots(fe_handle* h, const float* wav_in_dev, size_t in_stride, float* state_dev, int capacity, const int* slots_dev,
                   float* wav_out_dev, size_t out_stride, int n, int T, void* stream);
+/* fe_step_slots for EVERY family with a streaming state: what a pool of live streams calls.  Signature, row layout, slot rules (slots_dev is
+ * device int32 read when the kernels run, unchecked on the host; a slot outside [0, capacity) touches no state and its T output rows are zero;
+ * duplicates are undefined; slots not named keep their bits) and host checks (same codes, same wording, before any device work) are
+ * fe_step_slots'.
+ *   FastEnhancer models: the call IS fe_step_slots - same launch, same bits, same refusals, same fe_last_step_kernel.  The noncausal model:
+ *     FE_ERR_UNSUPPORTED_CONFIG with fe_step's message.
+ *   FE_ARCH_BSRNN / FE_ARCH_FSPEN / FE_ARCH_LISENNET: the PER-STREAM kernels fe_step(B = n, T) picks, in slotted instantiations that take every
+ *     state address from (slots_dev[i], capacity) - BSRNN's role-split or phase-by-phase PART 1 (fe_set_step_kernel, "bsrnn_role_split"), its
+ *     three-launch step (each launch reads slots_dev itself), the single-kernel walk for T > 1, the persistent forms above the streams resident
+ *     at once.  The stream-batched forms (bsrnn_sb_*, "bsrnn_fused_step", FSPEN's and LiSenNet's *_sb_* middle) are never taken, at any n and
+ *     whatever the "..._stream_batch_min" options say: their tensors are laid out per call tile.  fe_last_step_kernel: "... slots>".
+ *     Each named stream's wav_out rows and state are those of fe_step(B = n, T) under the same per-stream kernel on a dense state holding the
+ *     named slots' records, bit for bit.
+ *   The call allocates nothing, is asynchronous on `stream` and can be captured in a graph.  BSRNN's three-launch step passes 10.6 KB per stream
+ *     through the scratch that fe_state_init(h, state, capacity) sized (see above), as fe_step does; where no fe_state_init of the handle has
+ *     sized it for n streams, the step runs the single-kernel walk instead of growing it. */
+int fe_step_pool(fe_handle* h, const float* wav_in_dev, size_t in_stride, float* state_dev, int capacity, const int* slots_dev,
+                 float* wav_out_dev, size_t out_stride, int n, int T, void* stream);
 /* What fe_state_init writes (zeros), for the named slots only: a stream joining.  slots_dev, capacity, duplicates and the families as for
  * fe_step_slots; out-of-range slots are skipped. */
 int fe_state_reset_slots(fe_handle* h, float* state_dev, int capacity, const int* slots_dev, int n, void* stream);

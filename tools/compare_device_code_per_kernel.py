@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """tools/compare_device_code.sh, function by function: which gfx950 functions of two builds differ?  (no GPU needed)
-   python tools/compare_device_code_per_kernel.py <parent csrc/_obj> <changed csrc/_obj> [--allow REGEX] [--removed REGEX] [--added REGEX] [--kernarg REGEX] > profiles/<name>_device_code.txt
+   python tools/compare_device_code_per_kernel.py <parent csrc/_obj> <changed csrc/_obj> [--allow REGEX] [--removed REGEX] [--added REGEX] [--kernarg REGEX] [--renamed 'REGEX=>REPL'] > profiles/<name>_device_code.txt
 For every *.o of both directories the gfx950 code object is unbundled and split into its functions; of each function the disassembly
 (without addresses and encodings) and the kernel's note metadata (registers, spills, LDS, scratch, kernarg layout) are compared.
 --allow: a regular expression on the name (demangled where a demangler is installed, and mangled) of the functions that are meant to change; any other difference is an error (exit
@@ -10,7 +10,10 @@ status 1).  A change that is confined to some instantiations of a kernel templat
 --kernarg: the functions whose argument block is meant to change and nothing else: their disassembly and every note field but the kernarg
 layout (.kernarg_segment_size, the .args list) must be identical.  One thing in the code follows the layout: the hidden arguments (grid size,
 ...) lie behind the explicit ones, so a kernel that reads one addresses it through an immediate that moves with the block's size.  Such a line
-may differ in that one immediate, by exactly the change of .kernarg_segment_size, in a scalar load or scalar add; the lines are counted."""
+may differ in that one immediate, by exactly the change of .kernarg_segment_size, in a scalar load or scalar add; the lines are counted.
+--renamed 'REGEX=>REPL' (needs a demangler): a kernel template that gained a defaulted parameter gives every old instantiation a new name.  A function of
+the changed build only whose demangled name, after re.sub(REGEX, REPL), is that of a function of the parent only is compared with that one (its
+own mangled name inside its disassembly counts as the parent's); the pairs are counted and, where they differ, reported under the parent's name."""
 import argparse
 import os
 import re
@@ -116,11 +119,14 @@ def main():
     ap.add_argument("--removed", default=None)
     ap.add_argument("--added", default=None)
     ap.add_argument("--kernarg", default=None)
+    ap.add_argument("--renamed", default=None)
     args = ap.parse_args()
     allow, removed, kernarg, added = (re.compile(r) if r else None for r in (args.allow, args.removed, args.kernarg, args.added))
     hit = lambda rx, dem, k: rx is not None and (rx.search(dem) or rx.search(k)) is not None
     names = sorted(set(f for d in (args.parent, args.changed) for f in os.listdir(d) if f.endswith(".o")))
-    bad = total = same = allowed = gone = args_only = new = 0
+    bad = total = same = allowed = gone = args_only = new = renamed = 0
+    ren_rx, _, ren_to = (args.renamed or "=>").partition("=>")
+    demangle = lambda ks: dict(zip(ks, run(FILT, *ks).splitlines())) if ks and FILT else {k: k for k in ks}
     print(f"{'object':<30} {'functions':>9} {'identical':>9} {'changed':>8}")
     with tempfile.TemporaryDirectory() as tmp:
         for n in names:
@@ -132,6 +138,14 @@ def main():
             fa, fb = functions(pa, tmp), functions(pb, tmp)
             if not fa and not fb:
                 continue
+            if args.renamed:
+                only_a, only_b = demangle(sorted(set(fa) - set(fb))), demangle(sorted(set(fb) - set(fa)))
+                by_dem = {d: k for k, d in only_a.items()}
+                for kb, d in only_b.items():
+                    ka = by_dem.get(re.sub(ren_rx, ren_to, d))
+                    if ka is not None and d != only_a[ka]:
+                        fb[ka] = (fb[kb][0].replace(kb, ka), fb.pop(kb)[1])
+                        renamed += 1
             diff = sorted(k for k in set(fa) | set(fb) if fa.get(k) != fb.get(k))
             total += len(fb)
             same += len(fb) - len([k for k in diff if k in fb])
@@ -162,7 +176,8 @@ def main():
                         print(f"        {side}: {figures(f[k][1])}, {f[k][0].count(chr(10)) + 1} lines")
     print()
     print(f"{total} functions: {same} identical in code and notes, {args_only} with another kernarg layout only, {allowed} changed as meant to, "
-          f"{gone} removed as meant to, {new} added as meant to, {bad} other differences")
+          f"{gone} removed as meant to, {new} added as meant to, {bad} other differences"
+          + (f"; {renamed} compared under their parent's name (--renamed)" if args.renamed else ""))
     sys.exit(1 if bad else 0)
 
 
