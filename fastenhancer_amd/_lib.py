@@ -55,7 +55,9 @@ SYMBOLS = {
     "fe_step": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),
     "fe_step_slots": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),
     "fe_step_pool": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),
-    "fe_state_reset_slots": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "fe_step_pool_streams": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
+    "fe_step_pool_streams_pinned": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
+    "fe_state_reset_slots":(c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "fe_state_export_slots": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "fe_state_import_slots": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "fe_step_pinned": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),

@@ -134,18 +134,25 @@ struct BSlotArgs : BArgs {
     int capacity;
     const int* slots;         // [B] device int32; a slot outside [0, capacity) gets zero output rows and touches no state
 };
-template <bool SLOT> struct BKernelArgs { using type = BArgs; };
-template <> struct BKernelArgs<true> { using type = BSlotArgs; };
+// The packet-audio step (fe_step_pool_streams[_pinned]; the STRM instantiations, SLOT only): BSlotArgs followed by StreamIoArgs (fe_kernels.hip.h).
+// Call stream b has a descriptor of its own - state slot, hops to advance in this call (0 .. T), element offsets of its first input and output
+// sample from wav_in / wav_out - and the audio is float32 or int16 PCM (format).  a.slots and the strides are unused: T is the cap on hops.
+// (Again a type of its own: the other instantiations keep their argument blocks.)
+struct BStreamArgs : BSlotArgs, StreamIoArgs {};
+template <bool SLOT, bool STRM = false> struct BKernelArgs { using type = BArgs; };
+template <> struct BKernelArgs<true, false> { using type = BSlotArgs; };
+template <> struct BKernelArgs<true, true> { using type = BStreamArgs; };
 // rows of every state tensor: the call's streams, or the capacity of a slotted state (read where it is used, as a.B was)
 template <bool SLOT, class A>
 __device__ __forceinline__ int bstate_rows(const A& a) {
     if constexpr (SLOT) return a.capacity;
     else return a.B;
 }
-// call stream b's row of them: its slot (a scalar load, wave-uniform), or b itself
+// call stream b's row of them: its slot (a scalar load, wave-uniform; the packet step: the slot word of its descriptor), or b itself
 template <bool SLOT, class A>
 __device__ __forceinline__ int bstate_row(const A& a, int b) {
-    if constexpr (SLOT) return __builtin_amdgcn_readfirstlane(a.slots[b]);
+    if constexpr (std::is_base_of<StreamIoArgs, A>::value) return __builtin_amdgcn_readfirstlane(a.desc[b].slot);
+    else if constexpr (SLOT) return __builtin_amdgcn_readfirstlane(a.slots[b]);
     else return b;
 }
 
@@ -213,8 +220,14 @@ struct BLds {
 // step itself; a slot out of range skips the stream in each of them - no state access, zero output rows from the launch that writes the audio,
 // nothing handed to the scratch (bsrnn_mlp_kernel, which touches no state, then works on that stream's stale scratch row: its rows are per
 // stream, so nothing of it reaches another stream, and the tail skips the stream again).
-template <class S, bool HOT, bool PROF, bool DBG, bool OCC2 = false, bool PIPE = false, int PART = 0, bool SLOT = false>
-__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, PART == 2 ? 6 : PART == 3 ? 4 : OCC2 ? 2 : 1))) bsrnn_frame_kernel(typename BKernelArgs<SLOT>::type a) {
+// STRM (fe_step_pool_streams[_pinned]; SLOT only): slot, hop count and audio offsets come from the stream's descriptor (stream_view: clamped and
+// bounds-checked by every launch of the step), the generic kernel's frame loop runs the stream's own hops, the audio is float32 or int16 PCM at
+// any element alignment in device or page-locked host memory - read through stream_sample by the launch that reads it (the whole frame, PART 1,
+// bsrnn_ov_kernel), written through stream_store_row by the one that writes it (the whole frame, PART 2).  A stream without a hop is skipped by
+// each launch as one with a slot out of range is - and gets no rows; `format` is a run-time, wave-uniform branch.
+template <class S, bool HOT, bool PROF, bool DBG, bool OCC2 = false, bool PIPE = false, int PART = 0, bool SLOT = false, bool STRM = false>
+__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, PART == 2 ? 6 : PART == 3 ? 4 : OCC2 ? 2 : 1))) bsrnn_frame_kernel(typename BKernelArgs<SLOT, STRM>::type a) {
+    static_assert(!STRM || SLOT, "the packet instantiations are slotted ones");
     static_assert(!PIPE || (!HOT && !PROF && !DBG), "the time-pipelined instantiation is the plain offline kernel");
     static_assert(!SLOT || (!PROF && !DBG && !PIPE && PART != 3), "the slotted instantiations are the plain per-stream kernels");
     static_assert(PART == 0 || (HOT && !PROF && !DBG && !PIPE), "the split step is the per-hop streaming step");
@@ -329,6 +342,15 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
     // stores, made once per workgroup, were 40 % of the kernel's HBM writes (profiles/pmc_r2_bsrnn_xt.json).  Made loop-variant they are
     // computed where they are used.
     const int sb = bstate_row<SLOT>(a, b);           // the stream's row of every state tensor (bstate_rows: the rows of each)
+    StreamView sv{-1, 0, 0, 0};                      // (STRM) the stream this workgroup is running
+    if constexpr (STRM) {
+        sv = stream_view_of<H>(a, b);
+        if (sv.hops == 0 || (unsigned int)sb >= (unsigned int)a.capacity) {      // (wave-uniform) no hop: nothing; no state: its hops output rows are zero
+            if (PART != 1 && sv.hops) stream_zero_row(a.wav_out, a.format, sv.out_off, sv.hops * H, tid, kThreads);
+            b += gridDim.x;
+            continue;
+        }
+    } else
     if constexpr (SLOT) {
         if ((unsigned int)sb >= (unsigned int)a.capacity) {
             if (PART != 1 && mode == FE_MODE_STREAM) {
@@ -357,8 +379,9 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
     };
 
     unsigned int* pflag = PIPE ? a.pipe_flags + (size_t)b * S::NLAY : nullptr;
+    const int nT = (STRM && !HOT) ? sv.hops : aT;    // frames of this stream (STRM: its own hops; the per-hop kernels run a stream that has its one)
 #pragma unroll 1
-    for (int t = t_first; t < aT; t += t_step) {
+    for (int t = t_first; t < nT; t += t_step) {
         BE_CLK(0);
         // r5, PART 2 (the per-hop tail): the inverse transform on the matrix cores (fe::Dft: one barrier instead of nine radix-2 passes);
         // its constants and the old overlap tail are requested here, ahead of the GLU
@@ -386,6 +409,14 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
                 // xin[n - OVL] as in the serial walk (here with n - OVL < 0 for the frames that still start inside the cache).  Every frame of
                 // the stream reads the old cache side by side; stream_ola_kernel writes both caches afterwards.
                 // (the cache's base and end as values of the loop, not a branch around it: the other instantiations keep their code)
+                if constexpr (STRM) {
+                    const long long x0 = sv.in_off + (long long)t * H - OVL;
+                    for (int n = tid; n < N; n += kThreads) {
+                        const float v = (n < OVL) ? cst[n] : stream_sample(a.wav_in, a.format, x0 + n);
+                        fb[n] = make_float2(v, 0.0f);
+                        fa[n] = make_float2(v * win[n], 0.0f);
+                    }
+                } else {
                 const float* xin = a.wav_in + (size_t)b * a.in_stride + (size_t)t * H;
                 const float* cs0 = PIPE ? cst + t * H : cst;
                 const int ovl0 = PIPE ? OVL - t * H : OVL;
@@ -393,6 +424,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
                     float v = (n < ovl0) ? cs0[n] : xin[n - OVL];
                     if constexpr (!PIPE) fb[n] = make_float2(v, 0.0f);
                     fa[n] = make_float2(v * win[n], 0.0f);
+                }
                 }
             } else {
                 const float* xin = a.wav_in + (size_t)b * a.in_stride;
@@ -1027,11 +1059,27 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
                 vo[q] = (P0[pi] + P1[pi] + ((nc & 1) ? -nyq : nyq)) * owin[q] + ocis[q];
             }
             // (every read of the old overlap tail landed before the GLU's barrier)
+            if constexpr (STRM) {
+                // the hop goes out through stream_store_row, which takes it from LDS: staged in the transform's input buffer once every wave
+                // is through with the transform and with Ys[N]; the buffer is free again before the next stream's GLU writes it
+                float* xo = reinterpret_cast<float*>(fa);
+                __syncthreads();
+#pragma unroll
+                for (int q = 0; q < OPT; ++q) {
+                    const int n = tid + q * kThreads;
+                    if (n < H) xo[n] = vo[q];
+                    else if (n < N) cis[n - H] = vo[q];
+                }
+                __syncthreads();
+                stream_store_row(a.wav_out, a.format, sv.out_off + (long long)t * H, xo, H, tid, kThreads);
+                __syncthreads();
+            } else {
 #pragma unroll
             for (int q = 0; q < OPT; ++q) {
                 const int n = tid + q * kThreads;
                 if (n < H) out[n] = vo[q];
                 else if (n < N) cis[n - H] = vo[q];
+            }
             }
         } else
         if (mode != FE_MODE_SPEC) {
@@ -1051,6 +1099,9 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
                 xo[n] = v;
             }
             __syncthreads();
+            if constexpr (STRM) {
+                stream_store_row(a.wav_out, a.format, sv.out_off + (long long)t * H, xo, H, tid, kThreads);
+            } else
             if (mode == FE_MODE_STREAM) {
                 float* out = a.wav_out + (size_t)b * a.out_stride + (size_t)t * H;
                 for (int n = tid; n < H; n += kThreads) out[n] = xo[n];
@@ -1391,6 +1442,8 @@ struct BImpl {
     // fe_step_pool: the launches of `launch` (split = false) / `launch_split` (split = true: mlp_x / mlp_sp / mlp_pre set) with the slotted
     // instantiations of the per-stream kernels
     void (*launch_slots)(const BSlotArgs&, bool split, int max_wgs, hipStream_t, hipError_t*) = nullptr;
+    // fe_step_pool_streams[_pinned]: launch_slots' launches with the packet instantiations
+    void (*launch_streams)(const BStreamArgs&, bool split, int max_wgs, hipStream_t, hipError_t*) = nullptr;
 };
 
 template <class S, bool HOT, bool PROF, bool DBG, bool OCC2 = false>
@@ -1435,6 +1488,28 @@ int bpart_grid(int B, int max_wgs) {
     return B < OCC * max_wgs ? B : OCC * max_wgs;
 }
 
+// fe_last_step_kernel's names of a slotted launch (fe_step_pool: s[0]) and of its packet twin (fe_step_pool_streams: "streams" after "slots", then
+// "pinned" and "s16" - where the audio lives and its format are run-time facts of that call, hence a constant string for each of the four:
+// s[1 + pinned + 2 * s16]): `pre` + "slots[, streams[, pinned][, s16]]" + `post`, put together at compile time so that note_kernel gets a constant string
+struct BSlotNames { char s[5][96] = {}; };
+constexpr BSlotNames bslot_names(const char* pre, const char* post) {
+    BSlotNames n;
+    const char* mid[5] = {"slots", "slots, streams", "slots, streams, pinned", "slots, streams, s16", "slots, streams, pinned, s16"};
+    for (int v = 0; v < 5; ++v) {
+        int k = 0;
+        const char* parts[3] = {pre, mid[v], post};
+        for (const char* p : parts)
+            while (*p) n.s[v][k++] = *p++;
+    }
+    return n;
+}
+template <class A> constexpr bool kBStreams = std::is_base_of<StreamIoArgs, A>::value;      // the launch is the packet step's
+template <class A>
+int bslot_name(const A& a) {
+    if constexpr (kBStreams<A>) return 1 + (a.pinned != 0) + 2 * (a.format != 0);
+    else return 0;
+}
+
 }  // namespace fe
 #include "bsrnn_sb_kernels.hip.h"
 #include "bsrnn_ov_kernels.hip.h"
@@ -1474,24 +1549,25 @@ void blaunch_split_impl(const BArgs& a, int max_wgs, hipStream_t st, hipError_t*
     else blaunch_part<S, false, 2>(a, bpart_grid<S, 2>(a.B, max_wgs), st, err);
 }
 
-// fe_step_pool: blaunch_impl / blaunch_split_impl with the slotted instantiations (streaming mode; no debug dumps, cycle probes or fused step)
-template <class S, bool HOT, bool OCC2>
-void blaunch_one_slots(const BSlotArgs& a, int grid, hipStream_t st, hipError_t* err) {
-    const char* name = HOT ? (OCC2 ? "bsrnn_frame_kernel<per-hop, slots, two workgroups per CU>" : "bsrnn_frame_kernel<per-hop, slots>")
-                           : (OCC2 ? "bsrnn_frame_kernel<generic, slots, two workgroups per CU>" : "bsrnn_frame_kernel<generic, slots>");
-    *err = launch<&bsrnn_frame_kernel<S, HOT, false, false, OCC2, false, 0, true>>(name, dim3(grid), dim3(kThreads), BLds<S>::BYTES, st, a);
+// fe_step_pool / fe_step_pool_streams: blaunch_impl / blaunch_split_impl with the slotted instantiations (A = BSlotArgs) or their packet twins
+// (A = BStreamArgs) - streaming mode; no debug dumps, cycle probes or fused step.
+
+template <class S, bool HOT, bool OCC2, class A>
+void blaunch_one_slots(const A& a, int grid, hipStream_t st, hipError_t* err) {
+    static constexpr BSlotNames names = bslot_names(HOT ? "bsrnn_frame_kernel<per-hop, " : "bsrnn_frame_kernel<generic, ", OCC2 ? ", two workgroups per CU>" : ">");
+    *err = launch<&bsrnn_frame_kernel<S, HOT, false, false, OCC2, false, 0, true, kBStreams<A>>>(names.s[bslot_name(a)], dim3(grid), dim3(kThreads), BLds<S>::BYTES, st, a);
 }
 
-template <class S, bool OCC2, int PART>
-void blaunch_part_slots(const BSlotArgs& a, int grid, hipStream_t st, hipError_t* err) {
+template <class S, bool OCC2, int PART, class A>
+void blaunch_part_slots(const A& a, int grid, hipStream_t st, hipError_t* err) {
     static_assert(PART == 1 || PART == 2, "the three-launch step's per-stream parts");
     using LP = BLds<S, PART == 2 ? 2 : 0>;
-    const char* name = PART == 1 ? (OCC2 ? "bsrnn_frame_kernel<PART 1, slots, two workgroups per CU>" : "bsrnn_frame_kernel<PART 1, slots>") : "bsrnn_frame_kernel<PART 2, slots>";
-    *err = launch<&bsrnn_frame_kernel<S, true, false, false, OCC2, false, PART, true>>(name, dim3(grid), dim3(kThreads), LP::BYTES, st, a);
+    static constexpr BSlotNames names = bslot_names(PART == 1 ? "bsrnn_frame_kernel<PART 1, " : "bsrnn_frame_kernel<PART 2, ", (PART == 1 && OCC2) ? ", two workgroups per CU>" : ">");
+    *err = launch<&bsrnn_frame_kernel<S, true, false, false, OCC2, false, PART, true, kBStreams<A>>>(names.s[bslot_name(a)], dim3(grid), dim3(kThreads), LP::BYTES, st, a);
 }
 
-template <class S>
-void blaunch_slots_impl(const BSlotArgs& a, bool split, int max_wgs, hipStream_t st, hipError_t* err) {
+template <class S, class A>
+void blaunch_slots_impl(const A& a, bool split, int max_wgs, hipStream_t st, hipError_t* err) {
     constexpr bool FITS2 = 2 * BLds<S>::BYTES <= 160 * 1024 && !S::XPG;
     const bool two = FITS2 && a.B > max_wgs;
     if (!split) {
@@ -1507,8 +1583,9 @@ void blaunch_slots_impl(const BSlotArgs& a, bool split, int max_wgs, hipStream_t
         else blaunch_one_slots<S, false, false>(a, grid, st, err);
         return;
     }
-    // each of the three launches reads a.slots itself: the two per-stream parts skip a stream whose slot is out of range.  The batched mask decoder
-    // between them touches no state and takes no slots; its rows are per stream, so a skipped stream's stale scratch row reaches no other stream.
+    // each of the three launches reads a.slots itself (the packet step: the stream's descriptor): the two per-stream parts skip a stream whose slot is out
+    // of range (or that has no hop, or whose audio ranges leave the buffers).  The batched mask decoder between them touches no state and takes no
+    // slots; its rows are per stream, so a skipped stream's stale scratch row reaches no other stream.
     if (S::C == 16 && !a.ov_off && a.B <= max_wgs) blaunch_ov_slots<S>(a, a.B, st, err);
     else if (two) blaunch_part_slots<S, FITS2, 1>(a, a.B < 2 * max_wgs ? a.B : 2 * max_wgs, st, err);
     else blaunch_part_slots<S, false, 1>(a, a.B < max_wgs ? a.B : max_wgs, st, err);
@@ -1581,7 +1658,8 @@ BImpl make_bimpl() {
                  BDebugLayout<S>::total(), BDebugLayout<S>::n_stages, S::WREG, S::KSPLIT, S::NTD, &blaunch_impl<S>, &bdbg_stage_impl<S>,
                  &blaunch_pipe_impl<S>, 1,       // (the PIPE instantiation is compiled for one workgroup per CU: waves_per_eu(1, 1))
                  &blaunch_split_impl<S>, (SbLds<S>::FITS || Sb64Lds<S>::FITS) ? &blaunch_sb_impl<S> : nullptr};
-    im.launch_slots = &blaunch_slots_impl<S>;
+    im.launch_slots = &blaunch_slots_impl<S, BSlotArgs>;
+    im.launch_streams = &blaunch_slots_impl<S, BStreamArgs>;
     return im;
 }
 

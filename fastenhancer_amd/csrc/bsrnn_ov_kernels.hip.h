@@ -106,8 +106,11 @@ __device__ __forceinline__ void ov_group_barrier(unsigned int* cnt, unsigned int
 // profiles/r6_bsrnn_fused_step.txt.  Kept behind fe_set_option("bsrnn_fused_step", 1), bit-identical to the three launches.
 // SLOT (fe_step_pool): the workgroup's stream b is state slot a.slots[b] of a state sized for a.capacity streams (sb, bstate_rows below); a slot out of
 // range ends the workgroup before it touches anything (this launch writes no audio: the PART 2 launch zeroes the stream's output row).
-template <class S, bool PROF = false, bool FUSED = false, bool SLOT = false>
-__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))) bsrnn_ov_kernel(typename BKernelArgs<SLOT>::type a) {
+// STRM (fe_step_pool_streams; SLOT only): slot and input offset come from the stream's descriptor (stream_view: clamped and bounds-checked here as in the
+// PART 2 launch); a stream without a hop ends the workgroup as a slot out of range does; the hop is float32 or int16 PCM, read through stream_sample.
+template <class S, bool PROF = false, bool FUSED = false, bool SLOT = false, bool STRM = false>
+__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))) bsrnn_ov_kernel(typename BKernelArgs<SLOT, STRM>::type a) {
+    static_assert(!STRM || SLOT, "the packet instantiation is the slotted one's twin");
     static_assert(S::C == 16 && S::HH == 32 && S::NFFT == 512, "the role-split kernel is built for num_channels = 16");
     static_assert(!SLOT || (!PROF && !FUSED), "the slotted instantiation is PART 1 of the three-launch step");
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -144,6 +147,11 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
     const int sb = bstate_row<SLOT>(a, b);           // the stream's row of every state tensor (bstate_rows: the rows of each)
     if constexpr (SLOT) {
         if ((unsigned int)sb >= (unsigned int)a.capacity) return;
+    }
+    StreamView sv{-1, 0, 0, 0};                      // (STRM) the workgroup's stream: its one hop, or none
+    if constexpr (STRM) {
+        sv = stream_view_of<H>(a, b);
+        if (sv.hops == 0) return;
     }
     float* cst = a.cache_stft + (size_t)sb * OVL;
     const size_t lsz = (size_t)kBands * HH;                      // one (h or c) tensor of a layer and stream
@@ -266,7 +274,12 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
         constexpr int NPT = N / kThreads;
         float fv[NPT], fw[NPT];
 #pragma unroll
-        for (int q = 0; q < NPT; ++q) { const int n = tid + q * kThreads; fv[q] = (n < OVL) ? cst[n] : xin[n - OVL]; fw[q] = win[n]; }
+        for (int q = 0; q < NPT; ++q) {
+            const int n = tid + q * kThreads;
+            if constexpr (STRM) fv[q] = (n < OVL) ? cst[n] : stream_sample(a.wav_in, a.format, sv.in_off + (n - OVL));
+            else fv[q] = (n < OVL) ? cst[n] : xin[n - OVL];
+            fw[q] = win[n];
+        }
         typename D::FwdConst dc;
         D::load(dc, wb, o, wave);
         if (wave < 2) pre_load(0, TA{}, af0);      // layer 0's state fragments and the band split's weight rows: independent of the frame
@@ -709,10 +722,15 @@ void blaunch_ov(const BArgs& a, int grid, hipStream_t st, hipError_t* err) {
     }
 }
 
-template <class S>
-void blaunch_ov_slots(const BSlotArgs& a, int grid, hipStream_t st, hipError_t* err) {
-    if constexpr (S::C == 16) *err = launch<&bsrnn_ov_kernel<S, false, false, true>>("bsrnn_ov_kernel<slots>", dim3(grid), dim3(kThreads), BOvLds<S>::BYTES, st, a);
-    else *err = hipErrorInvalidValue;
+// (A = BSlotArgs: fe_step_pool; BStreamArgs: the packet twin of fe_step_pool_streams)
+template <class S, class A>
+void blaunch_ov_slots(const A& a, int grid, hipStream_t st, hipError_t* err) {
+    if constexpr (S::C == 16) {
+        static constexpr BSlotNames names = bslot_names("bsrnn_ov_kernel<", ">");
+        *err = launch<&bsrnn_ov_kernel<S, false, false, true, kBStreams<A>>>(names.s[bslot_name(a)], dim3(grid), dim3(kThreads), BOvLds<S>::BYTES, st, a);
+    } else {
+        *err = hipErrorInvalidValue;
+    }
 }
 
 }  // namespace fe

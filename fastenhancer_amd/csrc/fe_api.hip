@@ -1422,30 +1422,39 @@ static int table_view(const void* p, size_t bytes, const char* fn, const char* w
 static int streams_chunk_pipe_width(const fe_handle* h, int n, int T_max);
 static int launch_streams_chunk(fe_handle* h, const fe::StreamFrameArgs& own, const float* wav_in, float* state, float* wav_out, int n, int T_max, int P,
                                 float* work_dev, void* stream, bool* refused);
+// the packet steps' own argument checks (fe_step_streams*, fe_step_pool_streams*), under the entry point's name
+static int check_streams_args(const char* fn, const void* wav_in, size_t in_count, const float* state_dev, int capacity, const fe_stream_desc* desc_dev,
+                              const void* wav_out, size_t out_count, int n, int T_max, int format, const fe_stream_levels* levels) {
+    if (!wav_in || !state_dev || !desc_dev || !wav_out || n <= 0 || T_max <= 0 || capacity < n || in_count == 0 || out_count == 0)
+        return fail(FE_ERR_INVALID_ARG, "%s: bad argument (need non-null pointers to at least one element, 1 <= n <= capacity, T_max >= 1)", fn);
+    if (format != FE_AUDIO_F32 && format != FE_AUDIO_S16)
+        return fail(FE_ERR_INVALID_ARG, "%s: format %d is neither FE_AUDIO_F32 (0) nor FE_AUDIO_S16 (1)", fn, format);
+    if (reinterpret_cast<size_t>(levels) & 15)
+        return fail(FE_ERR_INVALID_ARG, "%s: levels is not 16-byte aligned (the kernel writes each row as one 16-byte store)", fn);
+    return FE_OK;
+}
+// ... and what their kernels get as wav_in / wav_out: the whole of both buffers, [wav, wav + count) in elements of the format - what the kernel's own
+// bounds check confines every access to.  pinned: the device views of the two ranges, both ends of each looked up.
+static int streams_audio(const char* fn, bool pinned, int format, const void* wav_in, size_t in_count, const void* wav_out, size_t out_count, const void** in,
+                         const void** out) {
+    *in = wav_in;
+    *out = wav_out;
+    if (!pinned) return FE_OK;
+    const auto view = format == FE_AUDIO_S16 ? &pinned_view<short> : &pinned_view<float>;
+    const int rc = view(wav_in, in_count, fn, "wav_in", in);
+    return rc != FE_OK ? rc : view(wav_out, out_count, fn, "wav_out", out);
+}
 static int step_streams(fe_handle* h, const char* fn, bool pinned, const void* wav_in, size_t in_count, float* state_dev, int capacity,
                         const fe_stream_desc* desc_dev, void* wav_out, size_t out_count, int n, int T_max, int format, void* stream,
                         const float* min_gain = nullptr, fe_stream_levels* levels = nullptr, const int* bank = nullptr, bool chunk = false,
                         float* work_dev = nullptr) {
     return slotted_step(h, fn, true,
+        [&]() -> int { return check_streams_args(fn, wav_in, in_count, state_dev, capacity, desc_dev, wav_out, out_count, n, T_max, format, levels); },
         [&]() -> int {
-            if (!wav_in || !state_dev || !desc_dev || !wav_out || n <= 0 || T_max <= 0 || capacity < n || in_count == 0 || out_count == 0)
-                return fail(FE_ERR_INVALID_ARG, "%s: bad argument (need non-null pointers to at least one element, 1 <= n <= capacity, T_max >= 1)", fn);
-            if (format != FE_AUDIO_F32 && format != FE_AUDIO_S16)
-                return fail(FE_ERR_INVALID_ARG, "%s: format %d is neither FE_AUDIO_F32 (0) nor FE_AUDIO_S16 (1)", fn, format);
-            if (reinterpret_cast<size_t>(levels) & 15)
-                return fail(FE_ERR_INVALID_ARG, "%s: levels is not 16-byte aligned (the kernel writes each row as one 16-byte store)", fn);
-            return FE_OK;
-        },
-        [&]() -> int {
-            // the whole of both buffers, [wav, wav + count) in elements of the format: what the kernel's own bounds check confines every access to
-            const void* in = wav_in;
-            const void* out = wav_out;
-            if (pinned) {
-                const auto view = format == FE_AUDIO_S16 ? &pinned_view<short> : &pinned_view<float>;
-                int rc = view(wav_in, in_count, fn, "wav_in", &in);
-                if (rc == FE_OK) rc = view(wav_out, out_count, fn, "wav_out", &out);
-                if (rc != FE_OK) return rc;
-            }
+            const void* in = nullptr;
+            const void* out = nullptr;
+            int rc = streams_audio(fn, pinned, format, wav_in, in_count, wav_out, out_count, &in, &out);
+            if (rc != FE_OK) return rc;
             fe::StreamFrameArgs own{};
             own.capacity = capacity;
             own.desc = reinterpret_cast<const fe::StreamDesc*>(desc_dev);
@@ -1455,7 +1464,7 @@ static int step_streams(fe_handle* h, const char* fn, bool pinned, const void* w
             const void* gains = nullptr;
             const void* rows = nullptr;
             const void* banks = nullptr;
-            int rc = table_view(min_gain, (size_t)capacity * sizeof(float), fn, "min_gain", &gains);
+            rc = table_view(min_gain, (size_t)capacity * sizeof(float), fn, "min_gain", &gains);
             if (rc == FE_OK) rc = table_view(levels, (size_t)capacity * sizeof(fe_stream_levels), fn, "levels", &rows);
             if (rc == FE_OK) rc = table_view(bank, (size_t)capacity * sizeof(int), fn, "bank", &banks);
             if (rc != FE_OK) return rc;
@@ -1485,6 +1494,50 @@ static int step_streams(fe_handle* h, const char* fn, bool pinned, const void* w
 int fe_step_streams(fe_handle* h, const void* wav_in_dev, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,
                     void* wav_out_dev, size_t out_count, int n, int T_max, int format, void* stream) {
     return step_streams(h, "fe_step_streams", false, wav_in_dev, in_count, state_dev, capacity, desc_dev, wav_out_dev, out_count, n, T_max, format, stream);
+}
+
+// fe_step_pool_streams / fe_step_pool_streams_pinned: the packet step for every family with a streaming state - to fe_step_streams[_pinned] what
+// fe_step_pool is to fe_step_slots.  FastEnhancer's handles take step_streams' path as it stands, under this entry point's name (the noncausal
+// model its refusal, which is fe_step's); a baseline family runs the launches fe_step_pool(n, T = T_max) picks, in their packet instantiations,
+// with step_streams' checks in step_streams' order.  Nothing is allocated.
+static int step_pool_streams(fe_handle* h, const char* fn, bool pinned, const void* wav_in, size_t in_count, float* state_dev, int capacity,
+                             const fe_stream_desc* desc_dev, void* wav_out, size_t out_count, int n, int T_max, int format, void* stream) {
+    if (!h) return fail(FE_ERR_INVALID_ARG, "null handle");
+    if (h->cfg.arch == FE_ARCH_FASTENHANCER)
+        return step_streams(h, fn, pinned, wav_in, in_count, state_dev, capacity, desc_dev, wav_out, out_count, n, T_max, format, stream);
+    int rc = check_streams_args(fn, wav_in, in_count, state_dev, capacity, desc_dev, wav_out, out_count, n, T_max, format, nullptr);
+    if (rc == FE_OK) rc = check_ready(h);
+    if (rc != FE_OK) return rc;
+    KernelLogScope klog_(h);
+    const void* in = nullptr;
+    const void* out = nullptr;
+    rc = streams_audio(fn, pinned, format, wav_in, in_count, wav_out, out_count, &in, &out);
+    if (rc != FE_OK) return rc;
+    visit_baseline(h->cfg.arch, [&](auto F) {
+        using Fam = decltype(F);
+        typename Fam::StreamArgs a{};
+        static_cast<typename Fam::Args&>(a) = F.args(h, n, T_max);
+        a.capacity = capacity;
+        a.desc = reinterpret_cast<const fe::StreamDesc*>(desc_dev);
+        a.in_count = in_count; a.out_count = out_count;
+        a.format = format;
+        a.pinned = pinned ? 1 : 0;
+        // (the audio is typed by a.format in the kernel; no strides: each stream's rows lie at its own offsets)
+        F.state(a) = stream_io(a, static_cast<const float*>(in), 0, const_cast<float*>(static_cast<const float*>(out)), 0, state_dev, state_layout(h, capacity));
+        rc = F.launch_streams(h, a, stream);
+    });
+    return rc;
+}
+
+int fe_step_pool_streams(fe_handle* h, const void* wav_in_dev, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,
+                         void* wav_out_dev, size_t out_count, int n, int T_max, int format, void* stream) {
+    return step_pool_streams(h, "fe_step_pool_streams", false, wav_in_dev, in_count, state_dev, capacity, desc_dev, wav_out_dev, out_count, n, T_max, format, stream);
+}
+
+int fe_step_pool_streams_pinned(fe_handle* h, const void* wav_in_host, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,
+                                void* wav_out_host, size_t out_count, int n, int T_max, int format, void* stream) {
+    return step_pool_streams(h, "fe_step_pool_streams_pinned", true, wav_in_host, in_count, state_dev, capacity, desc_dev, wav_out_host, out_count, n, T_max, format,
+                             stream);
 }
 
 int fe_step_streams_pinned(fe_handle* h, const void* wav_in_host, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,

@@ -6,6 +6,7 @@ const int kSub[31] = {2, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 8, 8, 8, 8, 8, 8, 8, 8, 8
 struct BsrnnFamily {
     using Args = fe::BArgs;
     using SlotArgs = fe::BSlotArgs;
+    using StreamArgs = fe::BStreamArgs;
     static const fe::BImpl* impl(const fe_handle* h) { return h->bimpl; }
     static const char* shape_name(const fe_handle* h) { return h->bimpl->name; }
     static float*& state(Args& a) { return a.lstm; }
@@ -29,6 +30,7 @@ struct BsrnnFamily {
     static int ensure_sb(fe_handle* h, int B);
     static int launch(fe_handle* h, const Args& a, void* stream);
     static int launch_slots(fe_handle* h, const SlotArgs& a, void* stream);
+    static int launch_streams(fe_handle* h, const StreamArgs& a, void* stream);
     static const char* stage_name(const fe_handle* h, int idx);
     static double macs(const fe_handle* h);
 };
@@ -373,9 +375,8 @@ int BsrnnFamily::launch(fe_handle* h, const fe::BArgs& a_in, void* stream) {
 // fe_step_pool: the per-stream kernels launch() picks for a.B streams, slotted.  Never the stream-batched layers or the fused step (their tensors
 // are laid out per call tile), and nothing is allocated: the three-launch step runs where the scratch fe_state_init sized holds the call's
 // streams, as it does for fe_step after that call; without it the single-kernel walk.
-int BsrnnFamily::launch_slots(fe_handle* h, const fe::BSlotArgs& a_in, void* stream) {
-    hipError_t e = hipSuccess;
-    fe::BSlotArgs a = a_in;
+// (a: the slotted argument block, or the packet step's, which extends it; returns whether the three-launch step runs)
+static bool bsrnn_slots_plan(const fe_handle* h, fe::BSlotArgs& a) {
     a.ov_off = (h->step_kernel == FE_STEP_KERNEL_WAVES4 || !h->opt[OPT_BSRNN_ROLE_SPLIT]) ? 1 : 0;
     const bool split = a.T == 1 && h->sb_dev && a.B <= h->sb_streams;
     if (split) {
@@ -383,7 +384,23 @@ int BsrnnFamily::launch_slots(fe_handle* h, const fe::BSlotArgs& a_in, void* str
         a.mlp_sp = a.mlp_x + (size_t)a.B * 31 * h->cfg.channels;
         a.mlp_pre = a.mlp_sp + (size_t)a.B * 2 * 257;
     }
+    return split;
+}
+
+int BsrnnFamily::launch_slots(fe_handle* h, const fe::BSlotArgs& a_in, void* stream) {
+    hipError_t e = hipSuccess;
+    fe::BSlotArgs a = a_in;
+    const bool split = bsrnn_slots_plan(h, a);
     h->bimpl->launch_slots(a, split, h->max_wgs, (hipStream_t)stream, &e);
+    return launch_rc(e);
+}
+
+// fe_step_pool_streams[_pinned]: launch_slots' choice for a.B streams and a.T = T_max, with the packet instantiations
+int BsrnnFamily::launch_streams(fe_handle* h, const fe::BStreamArgs& a_in, void* stream) {
+    hipError_t e = hipSuccess;
+    fe::BStreamArgs a = a_in;
+    const bool split = bsrnn_slots_plan(h, a);
+    h->bimpl->launch_streams(a, split, h->max_wgs, (hipStream_t)stream, &e);
     return launch_rc(e);
 }
 

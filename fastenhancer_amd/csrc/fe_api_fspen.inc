@@ -8,6 +8,7 @@ const int kSdN[5] = {2, 3, 5, 10, 20};                    // SubbandDecoder outp
 struct FspenFamily {
     using Args = fe::FArgs;
     using SlotArgs = fe::FSlotArgs;
+    using StreamArgs = fe::FStreamArgs;
     static const fe::FImpl* impl(const fe_handle* h) { return h->fimpl; }
     static const char* shape_name(const fe_handle*) { return "fspen"; }
     static float*& state(Args& a) { return a.gru; }
@@ -30,6 +31,7 @@ struct FspenFamily {
     static int ensure_sb(fe_handle* h, int B);
     static int launch(fe_handle* h, const Args& a, void* stream);
     static int launch_slots(fe_handle* h, const SlotArgs& a, void* stream);
+    static int launch_streams(fe_handle* h, const StreamArgs& a, void* stream);
     static const char* stage_name(const fe_handle*, int idx);
     static double macs(const fe_handle* h);
 };
@@ -351,6 +353,13 @@ int FspenFamily::launch(fe_handle* h, const fe::FArgs& a_in, void* stream) {
 int FspenFamily::launch_slots(fe_handle* h, const fe::FSlotArgs& a, void* stream) {
     hipError_t e = hipSuccess;
     h->fimpl->launch_slots(a, h->max_wgs, (hipStream_t)stream, &e);
+    return launch_rc(e);
+}
+
+// fe_step_pool_streams[_pinned]: the same kernel in its packet instantiation
+int FspenFamily::launch_streams(fe_handle* h, const fe::FStreamArgs& a, void* stream) {
+    hipError_t e = hipSuccess;
+    h->fimpl->launch_streams(a, h->max_wgs, (hipStream_t)stream, &e);
     return launch_rc(e);
 }
 

@@ -5,6 +5,7 @@
 struct LisennetFamily {
     using Args = fe::LArgs;
     using SlotArgs = fe::LSlotArgs;
+    using StreamArgs = fe::LStreamArgs;
     static const fe::LImpl* impl(const fe_handle* h) { return h->limpl; }
     static const char* shape_name(const fe_handle*) { return "lisennet"; }
     static float*& state(Args& a) { return a.cache; }
@@ -35,6 +36,7 @@ struct LisennetFamily {
     static int ensure_sb(fe_handle* h, int B);
     static int launch(fe_handle* h, const Args& a, void* stream);
     static int launch_slots(fe_handle* h, const SlotArgs& a, void* stream);
+    static int launch_streams(fe_handle* h, const StreamArgs& a, void* stream);
     static const char* stage_name(const fe_handle*, int idx);
     static double macs(const fe_handle* h);
 };
@@ -450,6 +452,13 @@ int LisennetFamily::launch(fe_handle* h, const fe::LArgs& a_in, void* stream) {
 int LisennetFamily::launch_slots(fe_handle* h, const fe::LSlotArgs& a, void* stream) {
     hipError_t e = hipSuccess;
     h->limpl->launch_slots(a, h->max_wgs, (hipStream_t)stream, &e);
+    return launch_rc(e);
+}
+
+// fe_step_pool_streams[_pinned]: the same kernel in its packet instantiation
+int LisennetFamily::launch_streams(fe_handle* h, const fe::LStreamArgs& a, void* stream) {
+    hipError_t e = hipSuccess;
+    h->limpl->launch_streams(a, h->max_wgs, (hipStream_t)stream, &e);
     return launch_rc(e);
 }
 

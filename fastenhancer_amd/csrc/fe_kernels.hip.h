@@ -463,6 +463,28 @@ __device__ __forceinline__ void stream_zero_row(void* base, int format, long lon
     short* out = static_cast<short*>(base) + idx;
     for (int i = tid; i < n; i += nth) __builtin_nontemporal_store((short)0, out + i);
 }
+// The packet step of the other families' per-stream kernels (fe_step_pool_streams; the STRM instantiations in bsrnn_, fspen_ and
+// lisennet_kernels.hip.h): what StreamFrameArgs adds to SlotFrameArgs, less the per-stream controls and the weight banks, which stay
+// FastEnhancer's.  A family's packet argument block is its slotted one followed by these fields (struct XStreamArgs : XSlotArgs, StreamIoArgs);
+// a.slots and the strides are unused there, and a.T is the cap on hops.
+struct StreamIoArgs {
+    const StreamDesc* desc;   // [B] device memory, read when the kernel runs
+    size_t in_count, out_count;   // elements of wav_in / wav_out: no access outside [0, count)
+    int format;               // 0 = float32, 1 = int16 PCM (FE_AUDIO_*)
+    int pinned;               // host side only (the kernel's name): the audio is page-locked host memory
+};
+// stream_view for such a block: the same clamp and the same bounds check, made by the one definition above (the StreamFrameArgs built
+// here is five scalars in registers)
+template <int H, class A>
+__device__ __forceinline__ StreamView stream_view_of(const A& a, int b) {
+    StreamFrameArgs s{};
+    s.B = a.B;
+    s.T = a.T;
+    s.desc = a.desc;
+    s.in_count = a.in_count;
+    s.out_count = a.out_count;
+    return stream_view<H>(s, b);
+}
 
 // ------------------------------------------------------------------------------------------
 #ifndef FE_PROBE_TID

@@ -131,8 +131,14 @@ struct FSlotArgs : FArgs {
     int capacity;
     const int* slots;         // [B] device int32; a slot outside [0, capacity) gets zero output rows and touches no state
 };
-template <bool SLOT> struct FKernelArgs { using type = FArgs; };
-template <> struct FKernelArgs<true> { using type = FSlotArgs; };
+// The packet-audio step (fe_step_pool_streams[_pinned]; the STRM instantiation, SLOT only): FSlotArgs followed by StreamIoArgs (fe_kernels.hip.h).
+// Call stream b has a descriptor of its own - state slot, hops to advance in this call (0 .. T), element offsets of its first input and output
+// sample from wav_in / wav_out - and the audio is float32 or int16 PCM (format).  a.slots and the strides are unused: T is the cap on hops.
+// (Again a type of its own: the other instantiations keep their argument blocks.)
+struct FStreamArgs : FSlotArgs, StreamIoArgs {};
+template <bool SLOT, bool STRM = false> struct FKernelArgs { using type = FArgs; };
+template <> struct FKernelArgs<true, false> { using type = FSlotArgs; };
+template <> struct FKernelArgs<true, true> { using type = FStreamArgs; };
 
 // debug stages (fe_debug_step): name, rows, cols as dumped (row-major)
 struct FDebugLayout {
@@ -310,8 +316,13 @@ __device__ __forceinline__ float row_dot(const float (&w)[12], float h, float ac
 #endif
 // SLOT (fe_step_pool): stream b's state is slot a.slots[b] of a state sized for a.capacity streams (sb, nst below); a slot out of range skips
 // the stream - no state access, zero output rows.  Audio rows stay indexed by b.
-template <class S, bool PROF, bool DBG, bool PIPE = false, int PART = 0, bool SLOT = false>
-__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(PART == 1 ? FS_WPE_FRONT : FS_WPE, PART == 1 ? FS_WPE_FRONT : FS_WPE))) fspen_frame_kernel(typename FKernelArgs<SLOT>::type a) {
+// STRM (fe_step_pool_streams[_pinned]; SLOT only): slot, hop count and audio offsets come from the stream's descriptor (stream_view: clamped and
+// bounds-checked on every call), the frame loop runs the stream's own hops, the audio is float32 or int16 PCM at any element alignment in device
+// or page-locked host memory - read through stream_sample, written through stream_store_row.  A stream without a hop reads and writes nothing;
+// one with hops and a slot out of range gets zero rows.  `format` is a run-time, wave-uniform branch: one instantiation.
+template <class S, bool PROF, bool DBG, bool PIPE = false, int PART = 0, bool SLOT = false, bool STRM = false>
+__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(PART == 1 ? FS_WPE_FRONT : FS_WPE, PART == 1 ? FS_WPE_FRONT : FS_WPE))) fspen_frame_kernel(typename FKernelArgs<SLOT, STRM>::type a) {
+    static_assert(!STRM || SLOT, "the packet instantiation is a slotted one");
     static_assert(!PIPE || (!PROF && !DBG), "the time-pipelined instantiation is the plain offline kernel");
     static_assert(!SLOT || (!PROF && !DBG && !PIPE && PART == 0), "the slotted instantiation is the plain per-stream kernel");
     static_assert(PART == 0 || (!PROF && !DBG && !PIPE), "the split step is the plain per-hop kernel");
@@ -346,6 +357,19 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(P
 #pragma unroll 1
     do {
     int sb = b, nst = a.B;                           // the stream's row of every state tensor, and the rows of each
+    int nT = aT;                                     // frames of this stream (STRM: its own hops)
+    StreamView sv{-1, 0, 0, 0};                      // (STRM) the stream this workgroup is running
+    if constexpr (STRM) {
+        nst = a.capacity;
+        sv = stream_view_of<H>(a, b);
+        sb = sv.slot;
+        nT = sv.hops;
+        if (nT == 0 || (unsigned int)sb >= (unsigned int)nst) {      // (wave-uniform) no hop: nothing; no state: its hops output rows are zero
+            if (nT) stream_zero_row(a.wav_out, a.format, sv.out_off, nT * H, tid0, kThreads);
+            b += gridDim.x;
+            continue;
+        }
+    } else
     if constexpr (SLOT) {
         nst = a.capacity;
         sb = __builtin_amdgcn_readfirstlane(a.slots[b]);
@@ -376,7 +400,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(P
     };
 
 #pragma unroll 1
-    for (int t = t_first; t < aT; t += t_step) {
+    for (int t = t_first; t < nT; t += t_step) {
         // a loop-variant zero on the weight pointer: the weights sit at compile-time offsets, and hoisted out of the frame /
         // stream loops their loads would stay live for the whole kernel (512 VGPRs, 229 spilled SGPRs without it)
         // (the same for the thread index: ~250 hoisted LDS addresses otherwise)
@@ -403,6 +427,14 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(P
                 // the stream reads the old cache side by side; stream_ola_kernel writes both caches afterwards.
                 // (the cache's base and end as values of the loop, not a branch around it: the other instantiations keep their code, and this
                 //  one its spill count)
+                if constexpr (STRM) {
+                    const long long x0 = sv.in_off + (long long)t * H - OVL;
+                    for (int n = tid; n < N; n += kThreads) {
+                        const float v = (n < OVL) ? cst[n] : stream_sample(a.wav_in, a.format, x0 + n);
+                        fb[n] = make_float2(v, 0.0f);
+                        fa[n] = make_float2(v * win[n], 0.0f);
+                    }
+                } else {
                 const float* xin = a.wav_in + (size_t)b * a.in_stride + (size_t)t * H;
                 const float* cs0 = PIPE ? cst + t * H : cst;
                 const int ovl0 = PIPE ? OVL - t * H : OVL;
@@ -410,6 +442,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(P
                     const float v = (n < ovl0) ? cs0[n] : xin[n - OVL];
                     if constexpr (!PIPE) fb[n] = make_float2(v, 0.0f);
                     fa[n] = make_float2(v * win[n], 0.0f);
+                }
                 }
             } else {
                 const float* xin = a.wav_in + (size_t)b * a.in_stride;
@@ -1169,6 +1202,9 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(P
                 xo[n] = v;
             }
             __syncthreads();
+            if constexpr (STRM) {
+                stream_store_row(a.wav_out, a.format, sv.out_off + (long long)t * H, xo, H, tid, kThreads);
+            } else
             if (mode == FE_MODE_STREAM) {
                 float* out = a.wav_out + (size_t)b * a.out_stride + (size_t)t * H;
                 for (int n = tid; n < H; n += kThreads) out[n] = xo[n];
@@ -1222,6 +1258,7 @@ struct FImpl {
     void (*launch_sb)(const FArgs&, int max_wgs, hipStream_t, hipError_t*);
     size_t split_floats_per_stream;      // tok + carry
     void (*launch_slots)(const FSlotArgs&, int max_wgs, hipStream_t, hipError_t*);      // fe_step_pool: flaunch_impl's launch with the slotted instantiation
+    void (*launch_streams)(const FStreamArgs&, int max_wgs, hipStream_t, hipError_t*);  // fe_step_pool_streams[_pinned]: launch_slots' launch with the packet instantiation
 };
 
 template <class S>
@@ -1257,6 +1294,19 @@ void flaunch_slots_impl(const FSlotArgs& a, int max_wgs, hipStream_t st, hipErro
 }
 
 template <class S>
+void flaunch_streams_impl(const FStreamArgs& a, int max_wgs, hipStream_t st, hipError_t* err) {
+    constexpr int OCC_LDS = (160 * 1024) / (FLds::TOTAL * 4);
+    constexpr int OCC = OCC_LDS < FS_WPE ? OCC_LDS : FS_WPE;
+    const int slots = max_wgs * OCC;
+    // (where the audio lives and its format are run-time facts of the call: a name for each of the four)
+    static const char* const names[4] = {"fspen_frame_kernel<slots, streams>", "fspen_frame_kernel<slots, streams, pinned>",
+                                         "fspen_frame_kernel<slots, streams, s16>", "fspen_frame_kernel<slots, streams, pinned, s16>"};
+    note_kernel(names[(a.pinned != 0) + 2 * (a.format != 0)]);
+    hipLaunchKernelGGL((fspen_frame_kernel<S, false, false, false, 0, true, true>), dim3(a.B < slots ? a.B : slots), dim3(kThreads), 0, st, a);
+    *err = hipGetLastError();
+}
+
+template <class S>
 void flaunch_sb_impl(const FArgs& a, int max_wgs, hipStream_t st, hipError_t* err) {
     constexpr int OCC_LDS = (160 * 1024) / (FLds::TOTAL * 4);
     constexpr int OCC = OCC_LDS < FS_WPE ? OCC_LDS : FS_WPE;
@@ -1284,7 +1334,8 @@ template <class S>
 FImpl make_fimpl() {
     constexpr int OCC_LDS = (160 * 1024) / (FLds::TOTAL * 4);
     return FImpl{S::HOP, (size_t)FLds::TOTAL * 4, FDebugLayout::total(), FDebugLayout::n_stages, (size_t)FPk::TOTAL, &flaunch_impl<S>, &fdbg_stage_impl,
-                 &flaunch_pipe_impl<S>, OCC_LDS < FS_WPE ? OCC_LDS : FS_WPE, S::NB, &flaunch_sb_impl<S>, (size_t)2048 + FCarry::FLOATS + 1024, &flaunch_slots_impl<S>};
+                 &flaunch_pipe_impl<S>, OCC_LDS < FS_WPE ? OCC_LDS : FS_WPE, S::NB, &flaunch_sb_impl<S>, (size_t)2048 + FCarry::FLOATS + 1024, &flaunch_slots_impl<S>,
+                 &flaunch_streams_impl<S>};
 }
 
 }  // namespace fe

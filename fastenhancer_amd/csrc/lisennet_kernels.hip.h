@@ -97,8 +97,14 @@ struct LSlotArgs : LArgs {
     int capacity;
     const int* slots;         // [B] device int32; a slot outside [0, capacity) gets zero output rows and touches no state
 };
-template <bool SLOT> struct LKernelArgs { using type = LArgs; };
-template <> struct LKernelArgs<true> { using type = LSlotArgs; };
+// The packet-audio step (fe_step_pool_streams[_pinned]; the STRM instantiation, SLOT only): LSlotArgs followed by StreamIoArgs (fe_kernels.hip.h).
+// Call stream b has a descriptor of its own - state slot, hops to advance in this call (0 .. T), element offsets of its first input and output
+// sample from wav_in / wav_out - and the audio is float32 or int16 PCM (format).  a.slots and the strides are unused: T is the cap on hops.
+// (Again a type of its own: the other instantiations keep their argument blocks.)
+struct LStreamArgs : LSlotArgs, StreamIoArgs {};
+template <bool SLOT, bool STRM = false> struct LKernelArgs { using type = LArgs; };
+template <> struct LKernelArgs<true, false> { using type = LSlotArgs; };
+template <> struct LKernelArgs<true, true> { using type = LStreamArgs; };
 
 // debug stages: 0 spec_in [257][2], 1 compressed [257][2], 2 features [3][257], 3 encoder.conv_1 [4][257], 4 encoder.conv_2 [8][128],
 // 5 encoder.conv_3 [12][64], 6 encoder.conv_4 [16][32], 7+3b blocks.b.intra [32][16], 8+3b blocks.b.inter [32][16], 9+3b blocks.b [16][32],
@@ -184,8 +190,13 @@ namespace fe {
 // cached frame and the compressed spectrum go to the carry; 2 = that step's tail (decoder cache, mask conv .. iSTFT) from the carry's up3 output.
 // SLOT (fe_step_pool): stream b's state is slot a.slots[b] of a state sized for a.capacity streams (sb, nst below); a slot out of range skips
 // the stream - no state access, zero output rows.  Audio rows stay indexed by b.
-template <class S, bool PROF, bool DBG, bool PIPE = false, int PART = 0, bool SLOT = false>
-__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((PART == 0 || DBG) ? 2 : 8, (PART == 0 || DBG) ? 2 : 8))) lisennet_frame_kernel(typename LKernelArgs<SLOT>::type a) {
+// STRM (fe_step_pool_streams[_pinned]; SLOT only): slot, hop count and audio offsets come from the stream's descriptor (stream_view: clamped and
+// bounds-checked on every call), the frame loop runs the stream's own hops, the audio is float32 or int16 PCM at any element alignment in device
+// or page-locked host memory - read through stream_sample, written through stream_store_row.  A stream without a hop reads and writes nothing;
+// one with hops and a slot out of range gets zero rows.  `format` is a run-time, wave-uniform branch: one instantiation.
+template <class S, bool PROF, bool DBG, bool PIPE = false, int PART = 0, bool SLOT = false, bool STRM = false>
+__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((PART == 0 || DBG) ? 2 : 8, (PART == 0 || DBG) ? 2 : 8))) lisennet_frame_kernel(typename LKernelArgs<SLOT, STRM>::type a) {
+    static_assert(!STRM || SLOT, "the packet instantiation is a slotted one");
     static_assert(!PIPE || (!PROF && !DBG), "the time-pipelined instantiation is the plain offline kernel");
     static_assert(!SLOT || (!PROF && !DBG && !PIPE && PART == 0), "the slotted instantiation is the plain per-stream kernel");
     static_assert(PART == 0 || !PIPE, "the split step is a streaming step");
@@ -215,6 +226,19 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((
 #pragma unroll 1
     do {
     int sb = b, nst = a.B;                           // the stream's row of every state tensor, and the rows of each
+    int nT = aT;                                     // frames of this stream (STRM: its own hops)
+    StreamView sv{-1, 0, 0, 0};                      // (STRM) the stream this workgroup is running
+    if constexpr (STRM) {
+        nst = a.capacity;
+        sv = stream_view_of<H>(a, b);
+        sb = sv.slot;
+        nT = sv.hops;
+        if (nT == 0 || (unsigned int)sb >= (unsigned int)nst) {      // (wave-uniform) no hop: nothing; no state: its hops output rows are zero
+            if (nT) stream_zero_row(a.wav_out, a.format, sv.out_off, nT * H, tid0, kThreads);
+            b += gridDim.x;
+            continue;
+        }
+    } else
     if constexpr (SLOT) {
         nst = a.capacity;
         sb = __builtin_amdgcn_readfirstlane(a.slots[b]);
@@ -247,7 +271,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((
     };
 
 #pragma unroll 1
-    for (int t = t_first; t < aT; t += t_step) {
+    for (int t = t_first; t < nT; t += t_step) {
         // PIPE: the ring slots of this utterance; cprev(off, back) = cache `off` as frame t - back left it, ccur(off) = where frame t leaves it
         const int RS = PIPE ? a.pipe_p + 2 : 1;
         float* const ringb = PIPE ? a.ring + (size_t)b * RS * S::CACHE_FLOATS : nullptr;
@@ -313,11 +337,20 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((
             const float* win = wp + P::WINDOW;
             float* cst = a.cache_stft + (size_t)sb * OVL;
             if (mode == FE_MODE_STREAM) {
+                if constexpr (STRM) {
+                    const long long x0 = sv.in_off + (long long)t * H - OVL;
+                    for (int n = tid; n < N; n += kThreads) {
+                        const float v = (n < OVL) ? cst[n] : stream_sample(a.wav_in, a.format, x0 + n);
+                        fb[n] = make_float2(v, 0.0f);
+                        fa[n] = make_float2(v * win[n], 0.0f);
+                    }
+                } else {
                 const float* xin = a.wav_in + (size_t)b * a.in_stride + (size_t)t * H;
                 for (int n = tid; n < N; n += kThreads) {
                     const float v = (n < OVL) ? cst[n] : xin[n - OVL];
                     fb[n] = make_float2(v, 0.0f);
                     fa[n] = make_float2(v * win[n], 0.0f);
+                }
                 }
             } else {
                 const float* xin = a.wav_in + (size_t)b * a.in_stride;
@@ -917,6 +950,9 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((
                 xo[n] = v;
             }
             __syncthreads();
+            if constexpr (STRM) {
+                stream_store_row(a.wav_out, a.format, sv.out_off + (long long)t * H, xo, H, tid, kThreads);
+            } else
             if (mode == FE_MODE_STREAM) {
                 float* out = a.wav_out + (size_t)b * a.out_stride + (size_t)t * H;
                 for (int n = tid; n < H; n += kThreads) out[n] = xo[n];
@@ -964,6 +1000,7 @@ struct LImpl {
     int nsite;                // caches handed from frame to frame (counters per stream)
     void (*launch_sb)(const LArgs&, int max_wgs, hipStream_t, hipError_t*);      // r6: the per-hop step of a large batch in three launches, the middle batched over the streams
     void (*launch_slots)(const LSlotArgs&, int max_wgs, hipStream_t, hipError_t*);      // fe_step_pool: llaunch_impl's launch with the slotted instantiation
+    void (*launch_streams)(const LStreamArgs&, int max_wgs, hipStream_t, hipError_t*);  // fe_step_pool_streams[_pinned]: launch_slots' launch with the packet instantiation
 };
 
 template <class S>
@@ -994,6 +1031,19 @@ void llaunch_slots_impl(const LSlotArgs& a, int max_wgs, hipStream_t st, hipErro
     const int slots = max_wgs * OCC;
     note_kernel("lisennet_frame_kernel<slots>");
     hipLaunchKernelGGL((lisennet_frame_kernel<S, false, false, false, 0, true>), dim3(a.B < slots ? a.B : slots), dim3(kThreads), 0, st, a);
+    *err = hipGetLastError();
+}
+
+template <class S>
+void llaunch_streams_impl(const LStreamArgs& a, int max_wgs, hipStream_t st, hipError_t* err) {
+    constexpr int OCC_LDS = (160 * 1024) / (LLds::TOTAL * 4);
+    constexpr int OCC = OCC_LDS < 2 ? OCC_LDS : 2;
+    const int slots = max_wgs * OCC;
+    // (where the audio lives and its format are run-time facts of the call: a name for each of the four)
+    static const char* const names[4] = {"lisennet_frame_kernel<slots, streams>", "lisennet_frame_kernel<slots, streams, pinned>",
+                                         "lisennet_frame_kernel<slots, streams, s16>", "lisennet_frame_kernel<slots, streams, pinned, s16>"};
+    note_kernel(names[(a.pinned != 0) + 2 * (a.format != 0)]);
+    hipLaunchKernelGGL((lisennet_frame_kernel<S, false, false, false, 0, true, true>), dim3(a.B < slots ? a.B : slots), dim3(kThreads), 0, st, a);
     *err = hipGetLastError();
 }
 
@@ -1030,7 +1080,8 @@ template <class S>
 LImpl make_limpl() {
     constexpr int OCC_LDS = (160 * 1024) / (LLds::TOTAL * 4);
     return LImpl{S::HOP, (size_t)LLds::TOTAL * 4, LDebugLayout::total(), LDebugLayout::n_stages, (size_t)LPk::TOTAL + LSbPk::TOTAL, (size_t)S::CACHE_FLOATS,
-                 &llaunch_impl<S>, &ldbg_stage_impl, &llaunch_pipe_impl<S>, OCC_LDS < 2 ? OCC_LDS : 2, 5 + 2 * S::NB, &llaunch_sb_impl<S>, &llaunch_slots_impl<S>};
+                 &llaunch_impl<S>, &ldbg_stage_impl, &llaunch_pipe_impl<S>, OCC_LDS < 2 ? OCC_LDS : 2, 5 + 2 * S::NB, &llaunch_sb_impl<S>, &llaunch_slots_impl<S>,
+                 &llaunch_streams_impl<S>};
 }
 
 }  // namespace fe

@@ -456,11 +456,20 @@ class Engine:
 
     def _step_streams(self, wav_in: Tensor, state: Tensor, capacity: int, desc, wav_out: Tensor, T_max: int, pinned: bool,
                       min_gain: Optional[Tensor] = None, levels: Optional[Tensor] = None, bank: Optional[Tensor] = None, chunk: bool = False,
-                      work: Optional[Tensor] = None) -> Tensor:
+                      work: Optional[Tensor] = None, pool: bool = False) -> Tensor:
+        """The packet step behind step_streams* / step_streams_chunk* / step_pool_streams*.  pool: fe_step_pool_streams[_pinned], the packet
+        step of every family - the same checks of buffers and descriptors; the per-stream controls, the weight banks and the pipelined form
+        are FastEnhancer's and are refused here."""
         ctl = min_gain is not None or levels is not None
         name = "fe_step_streams" + ("_banked" if bank is not None else "_ctl" if ctl else "") + ("_pinned" if pinned else "")
         if chunk:       # (one entry point, every table an argument that may be NULL)
             name = "fe_step_streams_chunk" + ("_pinned" if pinned else "")
+        if pool:
+            given = [k for k, v in (("min_gain", min_gain), ("levels", levels), ("bank", bank), ("chunk", chunk or None)) if v is not None]
+            if given:
+                raise ValueError(f"step_pool_streams takes no {' / '.join(given)}: the suppression limit, the level meters, the weight banks and the "
+                                 "pipelined packet step are built for the FastEnhancer family (step_streams, step_streams_chunk)")
+            name = "fe_step_pool_streams" + ("_pinned" if pinned else "")
         for what, x in (("wav_in", wav_in), ("wav_out", wav_out)):
             if not isinstance(x, Tensor) or x.dtype not in (torch.float32, torch.int16) or not x.is_contiguous() or x.numel() == 0:
                 raise ValueError(f"{what} must be a contiguous, non-empty float32 or int16 tensor")
@@ -529,6 +538,22 @@ class Engine:
         """fe_step_streams_pinned: step_streams with wav_in / wav_out in page-locked HOST memory, read and written by the kernel over PCIe.
         Asynchronous on the current stream: synchronise it before reading wav_out (or a pinned levels table) or rewriting wav_in."""
         return self._step_streams(wav_in, state, capacity, desc, wav_out, T_max, pinned=True, min_gain=min_gain, levels=levels, bank=bank)
+
+    def step_pool_streams(self, wav_in: Tensor, state: Tensor, capacity: int, desc, wav_out: Tensor, T_max: int = 1, *,
+                          min_gain=None, levels=None, bank=None, chunk=None) -> Tensor:
+        """fe_step_pool_streams: step_streams for every family with a streaming state - FastEnhancer's models as step_streams runs them,
+        BSRNN, FSPEN and LiSenNet on the packet forms of their per-stream kernels (what step_pool(T = T_max) launches; allocates nothing:
+        init_state sizes the scratch of BSRNN's three-launch step).  Buffers, descriptors and their checks as for step_streams; wav_in and
+        wav_out must not overlap.  min_gain, levels, bank and chunk are FastEnhancer's (step_streams, step_streams_chunk): a ValueError here."""
+        return self._step_streams(wav_in, state, capacity, desc, wav_out, T_max, pinned=False, min_gain=min_gain, levels=levels, bank=bank,
+                                  chunk=chunk, pool=True)
+
+    def step_pool_streams_pinned(self, wav_in: Tensor, state: Tensor, capacity: int, desc, wav_out: Tensor, T_max: int = 1, *,
+                                 min_gain=None, levels=None, bank=None, chunk=None) -> Tensor:
+        """fe_step_pool_streams_pinned: step_pool_streams with wav_in / wav_out in page-locked HOST memory (the completion rule of
+        step_streams_pinned: synchronise the stream before reading wav_out or rewriting wav_in)."""
+        return self._step_streams(wav_in, state, capacity, desc, wav_out, T_max, pinned=True, min_gain=min_gain, levels=levels, bank=bank,
+                                  chunk=chunk, pool=True)
 
     # ---- the packet step on the time pipeline: streams that come back with a backlog (fe_step_streams_chunk[_pinned])
     def streams_chunk_work_floats(self, n: int, T_max: int) -> int:

@@ -164,3 +164,21 @@ def slot_step(engine) -> Callable:
     engine object without a family description."""
     fam = _FAMILIES.get(type(getattr(engine, "cfg", None)))
     return engine.step_pool if fam is not None and fam.pool else engine.step_slots
+
+
+def packet_step(engine, pinned: bool) -> Callable:
+    """The engine's call for one packet step of a state buffer's streams (PacketPool.tick): step_pool_streams[_pinned] for the families whose
+    slotted steps are fe_step_pool's (BSRNN, FSPEN, LiSenNet), step_streams[_pinned] for FastEnhancer - its own path as it has always been
+    called - and for an engine object without a family description."""
+    fam = _FAMILIES.get(type(getattr(engine, "cfg", None)))
+    if fam is not None and fam.pool:
+        return engine.step_pool_streams_pinned if pinned else engine.step_pool_streams
+    return engine.step_streams_pinned if pinned else engine.step_streams
+
+
+def pool_family_name(engine) -> Optional[str]:
+    """"BSRNN", "FSPEN" or "LiSenNet" for an engine of a family that steps through fe_step_pool / fe_step_pool_streams, else None: what a
+    pool names when it refuses a control that is FastEnhancer's (suppression limit, level meters, weight banks, the pipelined packet step)."""
+    cfg = getattr(engine, "cfg", None)
+    fam = _FAMILIES.get(type(cfg))
+    return type(cfg).__name__[:-len("Config")] if fam is not None and fam.pool else None

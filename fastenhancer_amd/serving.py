@@ -27,7 +27,7 @@ from torch import Tensor
 
 from . import _lib
 from .engine import Engine
-from .family import chunk_step, slot_step
+from .family import chunk_step, packet_step, pool_family_name, slot_step
 
 
 class StreamPool:
@@ -59,8 +59,8 @@ class StreamPool:
         fam = getattr(self.engine, "family", None)
         if fam is not None and fam.arch != _lib.FE_ARCH_FASTENHANCER:
             # BSRNN, FSPEN, LiSenNet: fe_state_reset_slots is built for the FastEnhancer family; their fresh state is zeros, and the state
-            # records are built for every family - the slot takes a zero record (such a pool steps through fe_step_pool; step_host and
-            # PacketPool stay FastEnhancer's)
+            # records are built for every family - the slot takes a zero record (such a pool steps through fe_step_pool, a PacketPool
+            # through fe_step_pool_streams_pinned; step_host stays FastEnhancer's)
             fresh = torch.zeros(1, self.engine.record_floats, dtype=torch.float32, device=self.state.device)
             self.engine.import_slots(self.state, self.capacity, [slot], fresh)
         else:
@@ -238,9 +238,17 @@ class PacketPool(StreamPool):
     backlog_hops = K >= 4: a stream that holds more than T_max complete hops (up to its ring end) - one that comes back after a stall -
     is taken out of the tick's ordinary launch and served, up to K hops a tick, by a second launch on the time pipeline
     (Engine.step_streams_chunk_pinned: same slot, bank, limit and meters), so the other streams' launch stays T_max hops long.  0 (the
-    default): one launch, as ever."""
+    default): one launch, as ever.
+    A BSRNN, FSPEN or LiSenNet engine: tick() launches Engine.step_pool_streams_pinned (fe_step_pool_streams_pinned); push, pull, move,
+    resize, adopt, export and catch_up work as for FastEnhancer.  The meters, the suppression limit, the weight banks and backlog_hops are
+    FastEnhancer's: such a pool refuses them with a ValueError that names the family, before it calls the engine."""
 
     def __init__(self, engine: Engine, capacity: int, ring_hops: int, T_max: int = 1, meters: bool = False, backlog_hops: int = 0):
+        self._baseline = pool_family_name(engine)          # "BSRNN" / "FSPEN" / "LiSenNet", or None: the per-stream controls are available
+        if meters:
+            self._refuse_baseline("level meters (meters=True)")
+        if backlog_hops != 0:
+            self._refuse_baseline("the pipelined packet step (backlog_hops)")
         super().__init__(engine, capacity)
         if ring_hops < 1 or T_max < 1:
             raise ValueError("ring_hops and T_max must be at least 1")
@@ -263,6 +271,11 @@ class PacketPool(StreamPool):
         self._stepped = [0] * self.capacity
         self._pulled = [0] * self.capacity
 
+    def _refuse_baseline(self, what: str) -> None:
+        if self._baseline is not None:
+            raise ValueError(f"a PacketPool of a {self._baseline} engine has no {what}: suppression limits, level meters, weight banks and the "
+                             "pipelined packet step are built for the FastEnhancer family")
+
     def _reset_ctl(self, slot: int) -> None:
         """limit off, no level row"""
         if self._gain is not None:
@@ -273,6 +286,8 @@ class PacketPool(StreamPool):
 
     def open(self, bank: int = 0) -> int:
         """StreamPool.open; the stream runs on weight bank `bank` of the engine (ValueError, and no slot is opened, outside its banks)."""
+        if bank != 0:
+            self._refuse_baseline(f"weight bank {bank!r}")
         bank = self._check_bank(bank, self.engine)
         slot = super().open()
         self._pushed[slot] = self._stepped[slot] = self._pulled[slot] = 0
@@ -327,6 +342,8 @@ class PacketPool(StreamPool):
         """The stream runs on weight bank `bank` from the next tick on.  (Its state carries over - the layout is the same - but what a
         stream sounds like across a change of checkpoint is the checkpoints' business.)"""
         self._check_open(slot)
+        if bank != 0:
+            self._refuse_baseline(f"weight bank {bank!r}")
         self._set_bank(slot, self._check_bank(bank, self.engine))
 
     def bank(self, slot: int) -> int:
@@ -349,7 +366,10 @@ class PacketPool(StreamPool):
         """No bin of the stream is attenuated by more than `db` (-20.0: at most 20 dB of suppression) from the next tick on; None or -inf
         lifts the limit.  Open streams start without one."""
         self._check_open(slot)
-        self._set_gain(slot, self._limit_gain(db))
+        gain = self._limit_gain(db)
+        if gain != 0.0:
+            self._refuse_baseline("suppression limit")
+        self._set_gain(slot, gain)
 
     def _get_gain(self, slot: int) -> float:
         return 0.0 if self._gain is None else float(self._gain[slot])
@@ -450,8 +470,8 @@ class PacketPool(StreamPool):
         self._pushed[slot] = w + n
 
     def tick(self) -> List[Tuple[int, int, int, int]]:
-        """One launch for every open stream with at least one complete hop: each advances min(complete hops, hops up to the ring end,
-        T_max); the rest waits for the next tick.  With backlog_hops = K, a stream whose complete hops up to the ring end exceed T_max
+        """One launch (Engine.step_streams_pinned; a BSRNN, FSPEN or LiSenNet engine: Engine.step_pool_streams_pinned) for every open stream
+        with at least one complete hop: each advances min(complete hops, hops up to the ring end, T_max); the rest waits for the next tick.  With backlog_hops = K, a stream whose complete hops up to the ring end exceed T_max
         advances min(complete hops, hops up to the ring end, K) in a second launch on the same stream, on the time pipeline.  Waits once,
         for both (the rings are host memory the caller reads next).  Returns the descriptors (slot, hops, in_offset, out_offset) it
         launched, the ordinary launch's first - [] when no stream had a hop, and then nothing is launched."""
@@ -470,7 +490,7 @@ class PacketPool(StreamPool):
         if self._bank is not None:
             ctl["bank"] = self._bank
         if desc:
-            self.engine.step_streams_pinned(self.ring_in, self.state, self.capacity, desc, self.ring_out, T_max=self.T_max, **ctl)
+            packet_step(self.engine, pinned=True)(self.ring_in, self.state, self.capacity, desc, self.ring_out, T_max=self.T_max, **ctl)
         if backlog:
             if self._backlog_work is None:
                 need = self.engine.streams_chunk_work_floats(self.capacity, self.backlog_hops)

@@ -268,6 +268,33 @@ int fe_step_streams(fe_handle* h, const void* wav_in_dev, size_t in_count, float
                     void* wav_out_dev, size_t out_count, int n, int T_max, int format, void* stream);
 int fe_step_streams_pinned(fe_handle* h, const void* wav_in_host, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,
                            void* wav_out_host, size_t out_count, int n, int T_max, int format, void* stream);
+/* fe_step_streams[_pinned] for EVERY family with a streaming state: what a service's packet pool calls.  It stands to fe_step_streams[_pinned] as
+ * fe_step_pool stands to fe_step_slots: the same parameter lists, descriptor rules (desc_dev read by the kernels when they run, unchecked on the
+ * host; hops clamped to [0, T_max]; a stream with 0 hops reads and writes nothing, no audio and no state; a stream whose clamped range
+ * [offset, offset + hops*H) leaves [0, count) on either side is skipped like one with 0 hops - checked for every stream on every call; a slot
+ * outside [0, capacity) touches no state and its hops output rows are zero; duplicate slots are undefined; slots the call does not advance keep
+ * every bit), formats (FE_AUDIO_F32 / FE_AUDIO_S16 with the conversion rules above, any element alignment, 16-byte stores for rows that are
+ * 16-byte aligned), pinning and completion rules, and host checks (same codes, same wording under this function's name, before any device work).
+ *   FastEnhancer models: the call IS fe_step_streams[_pinned] - same launch, same bits, same refusals, same fe_last_step_kernel.  The noncausal
+ *     model: FE_ERR_UNSUPPORTED_CONFIG with fe_step's message.  (fe_step_streams* itself keeps refusing the other families.)
+ *   FE_ARCH_BSRNN / FE_ARCH_FSPEN / FE_ARCH_LISENNET: the launches fe_step_pool(n, T = T_max) picks - per-stream kernels only, never a
+ *     stream-batched form - in packet instantiations that take slot, hop count and audio offsets from the stream's descriptor.  BSRNN with
+ *     T_max == 1 and the scratch fe_state_init sized: the three-launch step (bsrnn_ov_kernel or PART 1, bsrnn_mlp_kernel, PART 2), each
+ *     per-stream launch reading the descriptor itself and skipping a stream without a hop or with ranges outside the buffers as it skips a
+ *     slot out of range (nothing is handed to the scratch; the batched MLP works on that stream's stale row, which reaches no other stream);
+ *     the first launch reads the audio, the last writes it.  BSRNN otherwise: the single-kernel walk.  fe_last_step_kernel: "streams" (and
+ *     "pinned", "s16") after "slots" in the brackets.
+ *   wav_in and wav_out must not overlap: a later launch of the step, or another stream's workgroup, may write output while input is still read.
+ *   Each stream's output rows and state are those of fe_step_pool(T = its hops) on the same slot, bit for bit wherever that call dispatches
+ *     the same kernel functions: always for FSPEN and LiSenNet (one kernel for every T); for BSRNN every stream of a T_max == 1 call and every
+ *     stream with 2 or more hops of a T_max > 1 call.  A BSRNN stream with 1 hop in a T_max > 1 call runs the generic walk where
+ *     fe_step_pool(T = 1) runs the per-hop kernels: equal to the relative tolerance those two kernels agree to (a few float32 ulps of the
+ *     waveform's scale), not bit for bit.
+ *   The call allocates nothing, is asynchronous on `stream` and can be captured in a graph (BSRNN's three launches: a linear chain). */
+int fe_step_pool_streams(fe_handle* h, const void* wav_in_dev, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,
+                         void* wav_out_dev, size_t out_count, int n, int T_max, int format, void* stream);
+int fe_step_pool_streams_pinned(fe_handle* h, const void* wav_in_host, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,
+                                void* wav_out_host, size_t out_count, int n, int T_max, int format, void* stream);
 
 /* The packet step with two per-stream controls, both inside the frame kernels of fe_step_streams (the same kernels, the same names from
  * fe_last_step_kernel, the same host checks, families and refusals): a limit on how far a stream may be attenuated, and input / output level meters.
