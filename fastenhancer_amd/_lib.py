@@ -42,6 +42,11 @@ class fe_stream_levels(ctypes.Structure):
     _fields_ = [("in_sumsq", c_float), ("in_peak", c_float), ("out_sumsq", c_float), ("out_peak", c_float)]
 
 
+class fe_resample_desc(ctypes.Structure):
+    """one stream of fe_resample_streams: state slot, samples consumed now, element offsets of its first input / output sample (24 bytes)"""
+    _fields_ = [("slot", c_int), ("n_in", c_int), ("in_offset", c_longlong), ("out_offset", c_longlong)]
+
+
 # every symbol include/fastenhancer_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "fe_create": (c_int, [POINTER(fe_config), POINTER(c_void_p)]),
@@ -109,6 +114,22 @@ SYMBOLS = {
     "fe_profile_step": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p, c_void_p]),
     "fe_debug_poison_lds": (c_int, [c_void_p]),
     "fe_debug_pack_weights": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, POINTER(c_size_t)]),
+    "fe_resampler_create": (c_int, [c_int, c_int, POINTER(c_void_p)]),
+    "fe_resampler_destroy": (None, [c_void_p]),
+    "fe_resampler_up": (c_int, [c_void_p]),
+    "fe_resampler_down": (c_int, [c_void_p]),
+    "fe_resampler_taps_per_output": (c_int, [c_void_p]),
+    "fe_resampler_half_len": (c_int, [c_void_p]),
+    "fe_resampler_taps": (c_int, [c_void_p, POINTER(c_double), c_size_t]),
+    "fe_resampler_out_count": (c_longlong, [c_void_p, c_longlong]),
+    "fe_resampler_produced": (c_longlong, [c_void_p, c_longlong, c_longlong]),
+    "fe_resampler_state_floats": (c_size_t, [c_void_p]),
+    "fe_resampler_last_kernel": (c_char_p, [c_void_p]),
+    "fe_resample": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_longlong, c_void_p, c_size_t, c_int, c_int, c_void_p]),
+    "fe_resample_streams": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_int, c_int,
+                                    c_void_p]),
+    "fe_resample_streams_pinned": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_int,
+                                           c_int, c_void_p]),
     "fe_last_error": (c_char_p, []),
     "fe_version": (c_char_p, []),
     "fe_build_key": (c_char_p, []),

@@ -221,6 +221,9 @@ def build(force: bool = False, verbose: bool = True) -> str:
     lsn = os.path.join(CSRC, "fe_lisennet.hip")
     jobs.append((lsn, os.path.join(OBJ, "fe_lisennet.o"), valu_defs, os.path.join(OBJ, "fe_lisennet.stamp"),
                  _digest(deps(lsn), " ".join(FLAGS + valu_defs))))
+    # the polyphase resampler's kernels: a translation unit of their own (the C-ABI unit's device code stays what it was)
+    rsm = os.path.join(CSRC, "fe_resample.hip")
+    jobs.append((rsm, os.path.join(OBJ, "fe_resample.o"), [], os.path.join(OBJ, "fe_resample.stamp"), _digest(deps(rsm), " ".join(FLAGS))))
     # fe_build_key(): the digest of the sources, compiled into the library (a translation unit of its own: seconds)
     bk = os.path.join(OBJ, "fe_build_key.cpp")
     skey = source_key()

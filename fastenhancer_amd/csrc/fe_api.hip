@@ -18,6 +18,7 @@
 #include "fspen_kernels.hip.h"
 #include "lisennet_kernels.hip.h"
 #include "stft_kernels.hip.h"
+#include "resample_kernels.hip.h"
 
 // fe_last_step_kernel: the launchers (per-shape translation units included) name what they enqueue; a compute entry point
 // clears the log when it starts and leaves it in its handle when it returns (KernelLogScope)
@@ -2584,3 +2585,6 @@ int fe_debug_stage(const fe_handle* h, int idx, const char** name, int* rows, in
 }
 
 }  // extern "C"
+
+// the polyphase resampler: a handle of its own (fe_resampler), no model behind it
+#include "fe_api_resample.inc"

@@ -1,0 +1,178 @@
+// resample_kernels.hip.h — polyphase resampling sr_in -> sr_out (fe_resample / fe_resample_streams of the C ABI): one template, two forms.
+//
+// The contract ("Audio at another sample rate"): up = sr_out / g, down = sr_in / g, R = max(up, down), hl = 10 R, L = 2 hl + 1
+// taps h = up * firwin(L, 1 / R, kaiser 5.0), K = ceil(L / up) taps per output.  Output m:  c = m down + hl, kmax = c div up, r = c mod up,
+//   y[m] = sum over j = 0 .. K - 1 with r + j up <= 2 hl of h[r + j up] x[kmax - j],     x = 0 outside the signal,
+// accumulated in fp32 from +0, j ascending, one fused multiply-add per tap - the same sequence of operations for an output whichever form,
+// tile or packetisation computes it, so a stream's outputs are the bits of the whole-signal call's.
+//
+// A workgroup of 256 threads keeps in LDS: the phase-major tap table T[r][j] = h[r + j up] (row stride KP = K | 1: the lanes of a wave read
+// one j of different rows r, and an odd stride spreads rows over the 32 banks of a 4-byte read; up = 1 is one row, read as a broadcast), one
+// tile of input as floats (the tile's oldest tap to its newest sample: xcap floats) and the tile's outputs (tile_out floats).  One thread per
+// output of the tile.  The host chooses tile_out so that a tile advances at most 4096 input samples (fe_api_resample.inc).
+//
+// !STRM (whole signals): grid (tiles, B), rows addressed by strides, no state.
+// STRM (packet streams): one workgroup per call stream walks the stream's tiles, so the LDS footprint does not depend on n_in_max.  The
+// descriptor is read wave-uniformly (as fe_kernels.hip.h::stream_view reads fe_stream_desc) and checked before anything is read or
+// written; samples before the packet come from the slot's history; the new history and count are written after a barrier behind the last tile.
+// No atomics, no waiting on other workgroups, no cooperative launch.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "fe_kernels.hip.h"
+#include "fe_launch.h"
+
+namespace fe {
+
+constexpr int kResampleThreads = 256;
+
+struct ResampleDesc {         // = fe_resample_desc of the C ABI (24 bytes)
+    int slot, n_in;
+    long long in_offset, out_offset;
+};
+
+struct ResampleArgs {
+    const float* table;       // [up][KP] device copy of the tap table (zeros where r + j up > 2 hl: never multiplied)
+    int up, down, hl, K, KP;
+    int tile_out, xcap;       // outputs per tile (<= 1024), floats of the input tile
+    const void* in;
+    void* out;
+    int in_format, out_format;   // FE_AUDIO_*
+    // whole signals
+    long long n_in, n_out;
+    size_t in_stride, out_stride;
+    // packet streams
+    int n_in_max;             // (the grid is one workgroup per call stream)
+    const ResampleDesc* desc; // [n] device memory, read when the kernel runs
+    size_t in_count, out_count;   // elements of in / out: no access outside [0, count)
+    float* state;             // [capacity][state_floats]: hist[K - 1] oldest first, the consumed count as two 32-bit words, padding
+    int capacity, state_floats;
+    int* produced;            // [n] or null
+};
+
+// outputs a stream that has consumed N samples has emitted: every output whose newest input has arrived
+__device__ __forceinline__ long long resample_emitted(long long N, int up, int down, int hl) {
+    const long long a = N * up - hl;
+    return a > 0 ? (a + down - 1) / down : 0;
+}
+
+template <bool STRM>
+__global__ __launch_bounds__(kResampleThreads) void fe_resample_kernel(ResampleArgs a) {
+    extern __shared__ float rs_lds[];
+    const int tid = (int)threadIdx.x;
+    const int up = a.up, down = a.down, K = a.K, KP = a.KP;
+    float* T = rs_lds;                          // [up][KP]
+    float* X = T + ((up * KP + 3) & ~3);        // [xcap]
+    float* Y = X + ((a.xcap + 3) & ~3);         // [tile_out]
+
+    // what this workgroup resamples: outputs [m_begin, m_end) of a signal whose sample g is element in_base + g - g0 of a.in for
+    // g0 <= g < g0 + n (STRM: g0 = the stream's consumed count, and hist holds g0 - (K - 1) .. g0 - 1; else g0 = 0 and there is no history)
+    long long m_begin = 0, m_end = 0, g0 = 0, in_base = 0, out_base = 0;
+    int n = 0;
+    float* row = nullptr;
+    if constexpr (STRM) {
+        const int b = (int)blockIdx.x;
+        const int* p = reinterpret_cast<const int*>(a.desc + b);
+        int w[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) w[i] = __builtin_amdgcn_readfirstlane(p[i]);
+        const int slot = w[0];
+        n = w[1] < 0 ? 0 : (w[1] > a.n_in_max ? a.n_in_max : w[1]);
+        in_base = (long long)(((unsigned long long)(unsigned)w[3] << 32) | (unsigned)w[2]);
+        out_base = (long long)(((unsigned long long)(unsigned)w[5] << 32) | (unsigned)w[4]);
+        long long made = 0;
+        bool ok = (unsigned)slot < (unsigned)a.capacity;
+        if (ok) {
+            row = a.state + (size_t)slot * a.state_floats;
+            const unsigned* cw = reinterpret_cast<const unsigned*>(row + (K - 1));
+            const unsigned lo = __builtin_amdgcn_readfirstlane(cw[0]), hi = __builtin_amdgcn_readfirstlane(cw[1]);
+            g0 = (long long)(((unsigned long long)hi << 32) | lo);
+            // (a count that is no count - a row is plain data - must not become an access: beyond 2^40 samples the stream is skipped)
+            ok = g0 >= 0 && g0 < (1ll << 40);
+        }
+        if (ok) {
+            m_begin = resample_emitted(g0, up, down, a.hl);
+            m_end = resample_emitted(g0 + n, up, down, a.hl);
+            made = m_end - m_begin;
+            const unsigned long long len_in = (unsigned long long)n, len_out = (unsigned long long)made;
+            const bool in_ok = in_base >= 0 && (unsigned long long)in_base <= a.in_count && a.in_count - (unsigned long long)in_base >= len_in;
+            const bool out_ok = out_base >= 0 && (unsigned long long)out_base <= a.out_count && a.out_count - (unsigned long long)out_base >= len_out;
+            ok = in_ok && out_ok;
+        }
+        if (a.produced != nullptr && tid == 0) a.produced[b] = ok ? (int)made : 0;
+        if (!ok || n == 0) return;              // skipped, or nothing new: nothing read, nothing written, the row as it was
+    } else {
+        const int b = (int)blockIdx.y;
+        n = 0;                                  // (unused: the whole-signal bound is a.n_in)
+        m_begin = (long long)blockIdx.x * a.tile_out;
+        m_end = m_begin + a.tile_out < a.n_out ? m_begin + a.tile_out : a.n_out;
+        in_base = (long long)((size_t)b * a.in_stride);
+        out_base = (long long)((size_t)b * a.out_stride) + m_begin;
+    }
+    const long long n_sig = STRM ? (long long)n : a.n_in;
+
+    for (int i = tid; i < up * KP; i += kResampleThreads) T[i] = a.table[i];
+
+    for (long long m0 = m_begin; m0 < m_end; m0 += a.tile_out) {
+        const int cnt = (int)(m_end - m0 < a.tile_out ? m_end - m0 : a.tile_out);
+        const long long c0 = m0 * down + a.hl;
+        const long long kmax0 = c0 / up;
+        const int r0 = (int)(c0 - kmax0 * up);
+        // the tile's inputs: signal samples x_lo .. x_lo + span - 1, the oldest tap of its first output to the newest of its last
+        const long long x_lo = kmax0 - (K - 1);
+        const int span = (r0 + (cnt - 1) * down) / up + K;         // <= xcap (the host's bound is this expression at r0 = up - 1, cnt = tile_out)
+        for (int i = tid; i < span; i += kResampleThreads) {
+            const long long l = x_lo + i - g0;                     // index into this call's samples
+            float v = 0.0f;
+            if (l >= 0 && l < n_sig) v = stream_sample(a.in, a.in_format, in_base + l);
+            if constexpr (STRM) {
+                if (l < 0 && l >= -(long long)(K - 1)) v = row[(K - 1) + (int)l];
+            }
+            X[i] = v;
+        }
+        __syncthreads();
+        for (int t = tid; t < cnt; t += kResampleThreads) {
+            const int c = r0 + t * down;
+            const int q = c / up, r = c - q * up;
+            const float* tr = T + r * KP;
+            const float* xr = X + q + (K - 1);                     // x[kmax], then backwards
+            float acc = 0.0f;
+            for (int j = 0; j < K - 1; ++j) acc = __builtin_fmaf(tr[j], xr[-j], acc);
+            if (r + (K - 1) * up <= 2 * a.hl) acc = __builtin_fmaf(tr[K - 1], xr[-(K - 1)], acc);
+            Y[t] = acc;
+        }
+        __syncthreads();
+        stream_store_row(a.out, a.out_format, out_base + (STRM ? m0 - m_begin : 0), Y, cnt, tid, kResampleThreads);
+        // (no barrier here: the next tile overwrites X only behind the barrier above, and Y only behind its own first barrier, which no
+        // thread passes before every thread has left this store)
+    }
+
+    if constexpr (STRM) {
+        // the new history: samples g0 + n - (K - 1) .. g0 + n - 1, from the packet or - a packet shorter than K - 1 - the old history
+        // shifted; staged in LDS so that every old value is read before any is overwritten
+        for (int i = tid; i < K - 1; i += kResampleThreads) {
+            const long long l = (long long)n - (K - 1) + i;
+            X[i] = l >= 0 ? stream_sample(a.in, a.in_format, in_base + l) : row[(K - 1) + (int)l];
+        }
+        __syncthreads();
+        for (int i = tid; i < K - 1; i += kResampleThreads) row[i] = X[i];
+        if (tid == 0) {
+            const unsigned long long g1 = (unsigned long long)(g0 + n);
+            unsigned* cw = reinterpret_cast<unsigned*>(row + (K - 1));
+            cw[0] = (unsigned)g1;
+            cw[1] = (unsigned)(g1 >> 32);
+        }
+    }
+}
+
+// LDS floats of a launch (the three regions, each rounded up to 4 floats)
+inline size_t resample_lds_floats(int up, int KP, int xcap, int tile_out) {
+    return (size_t)((up * KP + 3) & ~3) + (size_t)((xcap + 3) & ~3) + (size_t)((tile_out + 3) & ~3);
+}
+
+// The launcher, defined in fe_resample.hip - the one translation unit that instantiates the two kernels, so that the C-ABI unit, which
+// includes this header for the argument block, carries no device code of them.  Every resampler of the process shares the two kernels, and
+// the opt-in for dynamic LDS is made once per kernel and device: for the most any ratio needs (160 KiB), not for one handle's footprint.
+hipError_t launch_resample(bool strm, dim3 grid, size_t lds_bytes, hipStream_t st, const ResampleArgs& a);
+
+}  // namespace fe

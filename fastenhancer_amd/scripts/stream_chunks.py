@@ -2,6 +2,8 @@
 """scripts/test_streaming.py with one more flag: --chunk-hops N runs the file in chunks of N hops on the time pipeline
 (Engine.step_chunk - BSRNN and FSPEN checkpoints: Engine.step_backlog - through streaming.enhance_stream(chunk_hops=N)) instead of hop by hop.  Off by default: without the flag this IS
 test_streaming.py (same flags, same loop, same output).
+And a second one: --resample takes a file that is not at the model's rate (with or without --chunk-hops; test_streaming.py itself refuses
+such a file): it is read at its own rate, resampled on the GPU and written at the model's rate.  Off by default.
 
     python -m fastenhancer_amd.scripts.stream_chunks -c configs/fastenhancer/b.yaml --checkpoint logs/b/00500.pth \\
         --audio-path noisy.wav --save-output --chunk-hops 256
@@ -17,15 +19,17 @@ import torch
 
 from ..streaming import enhance_stream
 from . import test_streaming
-from .common import build_model, latest_checkpoint, load_hparams, read_wav, write_wav
+from .common import build_model, latest_checkpoint, load_hparams, read_wav, resampling, split_resample_flag, write_wav
 
 
 def main(argv=None):
     p = argparse.ArgumentParser(add_help=False)
     p.add_argument("--chunk-hops", type=int, default=None, help="hops per call on the time pipeline (default: off - hop by hop)")
     own, rest = p.parse_known_args(argv)
+    resample_on, rest = split_resample_flag(rest)
     if own.chunk_hops is None:
-        return test_streaming.main(rest)
+        with resampling(resample_on):
+            return test_streaming.main(rest)
     q = argparse.ArgumentParser()
     q.add_argument("-n", "--name", type=str)
     q.add_argument("-c", "--config", type=str)
@@ -47,7 +51,7 @@ def main(argv=None):
         assert got is None or got == want, f"--{flag.replace('_', '-')}={got} does not match the config ({want})"
     ckpt = args.checkpoint or (latest_checkpoint(os.path.join("logs", args.name)) if args.name else None)
     model = build_model(hps, args.device, offline=False, checkpoint=ckpt)
-    wav = torch.from_numpy(np.clip(read_wav(args.audio_path, sr).reshape(1, -1), -1, 1)).to(args.device)
+    wav = torch.from_numpy(np.clip(read_wav(args.audio_path, sr, resample_on is not None, resample_on).reshape(1, -1), -1, 1)).to(args.device)
     print("Inferencing...")
     torch.cuda.synchronize()
     tic = time.perf_counter()

@@ -14,7 +14,10 @@ checkpoint of the same shape - still in that one launch (fe_step_streams_banked_
 
 Moving a stream: export() gathers the state records of open slots (fe_state_export_slots: a record is the stream's state as a capacity-1
 state buffer), adopt() opens slots for records made elsewhere, move() takes a live stream to another pool - of another engine of the same
-config, on another GPU if need be - and resize() grows or shrinks a pool in place.  PacketPool carries the stream's rings along."""
+config, on another GPU if need be - and resize() grows or shrinks a pool in place.  PacketPool carries the stream's rings along.
+
+ResampledPacketPool: a PacketPool behind two polyphase resamplers (fastenhancer_amd.resample) for clients at another sample rate - a
+telephone leg at 8 kHz, a WebRTC leg at 48 kHz: push() and pull() speak the client's rate, the model runs at its own."""
 from __future__ import annotations
 
 import math
@@ -28,6 +31,7 @@ from torch import Tensor
 from . import _lib
 from .engine import Engine
 from .family import chunk_step, packet_step, pool_family_name, slot_step
+from .resample import Resampler
 
 
 class StreamPool:
@@ -513,3 +517,152 @@ class PacketPool(StreamPool):
         out = torch.cat([self.ring_out[slot, pos:pos + first], self.ring_out[slot, :n - first]])
         self._pulled[slot] = r + n
         return out
+
+
+class ResampledPacketPool:
+    """A PacketPool for clients at `client_rate`, the model at `model_rate`.  It holds a PacketPool (`inner`) and two Resamplers with one
+    state row per slot each, and uses the inner pool's public methods only, so it serves every family the PacketPool serves.  push() takes
+    int16 PCM at the client's rate - up to max_packet samples per slot between two ticks - and pull() returns int16 PCM at the client's rate.
+    tick() is five steps in order:
+      1. one Resampler.step_streams_pinned launch: every slot's pending input -> model-rate PCM in a page-locked staging buffer;
+      2. inner.push of each slot's new model-rate samples;
+      3. inner.tick();
+      4. inner.pull of every slot;
+      5. one Resampler.step_streams_pinned launch back to the client's rate.
+    That is three launches and two host hops a tick, where PacketPool has one launch: resampling into the rings inside the packet step
+    itself is left for later.  Both resamplers are streaming-exact across packets (the outputs are those of one call on the whole signal),
+    each with its own latency of half_len / up input samples; nothing is flushed when a slot closes.
+    model_rate: the engine's configuration does not carry a sample rate - 16000 for the 16 kHz configurations, 48000 for the 48 kHz ones."""
+
+    def __init__(self, engine: Engine, capacity: int, ring_hops: int, client_rate: int, T_max: int = 1, max_packet: Optional[int] = None, *,
+                 model_rate: int = 16000):
+        client_rate, model_rate = operator.index(client_rate), operator.index(model_rate)
+        if client_rate == model_rate:
+            raise ValueError(f"client_rate {client_rate} is the model's rate: there is nothing to resample, use PacketPool")
+        device = getattr(engine, "device", None)
+        self.client_rate, self.model_rate = client_rate, model_rate
+        self.to_model = self._make_resampler(client_rate, model_rate, device)
+        self.to_client = self._make_resampler(model_rate, client_rate, device)
+        self.inner = self._make_pool(engine, capacity, ring_hops, T_max)
+        self.capacity = int(capacity)
+        step = int(self.inner.T_max) * int(self.inner.H)                   # model-rate samples a slot advances per tick at most
+        if max_packet is None:                                             # what a tick can take away, at the client's rate
+            max_packet = -(-step * client_rate // model_rate)
+        self.max_packet = operator.index(max_packet)
+        if self.max_packet < 1:
+            raise ValueError("max_packet must be at least 1")
+        self._model_cap = self.to_model.out_count(self.max_packet) + 1    # model-rate samples of max_packet client samples at most
+        self._client_cap = self.to_client.out_count(step) + 1             # client-rate samples of one tick's output at most
+        self._step = step
+        self.state_in = self.to_model.new_state(self.capacity)
+        self.state_out = self.to_client.new_state(self.capacity)
+        self._cin = self.to_model.new_pinned(self.capacity, self.max_packet, dtype=torch.int16)
+        self._min = self.to_model.new_pinned(self.capacity, self._model_cap, dtype=torch.int16)
+        self._mout = self.to_client.new_pinned(self.capacity, step, dtype=torch.int16)
+        self._cout = self.to_client.new_pinned(self.capacity, self._client_cap, dtype=torch.int16)
+        self._made_in = self.to_model.new_pinned(self.capacity, dtype=torch.int32)
+        self._made_out = self.to_client.new_pinned(self.capacity, dtype=torch.int32)
+        self._pending = [0] * self.capacity          # client-rate samples waiting in _cin
+        self._consumed = [0] * self.capacity         # client-rate samples the resampler to the model's rate has consumed
+        self._fill = [0] * self.capacity             # model-rate samples pushed into the inner pool and not yet pulled from it
+        self._ready: List[List[Tensor]] = [[] for _ in range(self.capacity)]
+        self._open = set()
+
+    # (the two constructors tick() depends on, apart for the tests that record the calls instead of running them)
+    @staticmethod
+    def _make_pool(engine, capacity, ring_hops, T_max) -> PacketPool:
+        return PacketPool(engine, capacity, ring_hops, T_max=T_max)
+
+    @staticmethod
+    def _make_resampler(sr_in, sr_out, device) -> Resampler:
+        return Resampler(sr_in, sr_out, device)
+
+    @property
+    def active(self) -> List[int]:
+        return sorted(self._open)
+
+    def _check_open(self, slot: int) -> None:
+        if slot not in self._open:
+            raise ValueError(f"slot {slot} is not open")
+
+    def _fresh(self, slot: int) -> None:
+        self.state_in[slot] = 0.0
+        self.state_out[slot] = 0.0
+        self._pending[slot] = self._consumed[slot] = self._fill[slot] = 0
+        self._ready[slot] = []
+
+    def open(self) -> int:
+        """inner.open(); the slot's two resampler rows start as zeros (fresh streams)"""
+        slot = self.inner.open()
+        self._fresh(slot)
+        self._open.add(slot)
+        return slot
+
+    def close(self, slot: int) -> None:
+        self._check_open(slot)
+        self.inner.close(slot)
+        self._open.remove(slot)
+        self._fresh(slot)
+
+    def push(self, slot: int, pcm) -> None:
+        """Append a packet at the client's rate: a 1-D int16 array or tensor.  OverflowError, and nothing taken, when more than max_packet
+        samples would wait for the next tick or the inner pool's ring could not hold what they become."""
+        self._check_open(slot)
+        x = torch.as_tensor(pcm)
+        if x.dim() != 1 or x.dtype != torch.int16:
+            raise ValueError(f"a packet is a 1-D int16 array, got {x.dtype} {tuple(x.shape)}")
+        n, have = x.numel(), self._pending[slot]
+        if have + n > self.max_packet:
+            raise OverflowError(f"slot {slot}: {n} samples do not fit - {have} of max_packet = {self.max_packet} samples wait for the next tick")
+        if self._fill[slot] + self.to_model.produced(self._consumed[slot], have + n) > self.inner.ring:
+            raise OverflowError(f"slot {slot}: {n} samples do not fit - the inner pool's ring holds {self.inner.ring} samples, {self._fill[slot]} are in it")
+        self._cin[slot, have:have + n] = x
+        self._pending[slot] = have + n
+
+    def tick(self) -> List[Tuple[int, int, int, int]]:
+        """The five steps above.  Waits for each of its launches (the staging buffers are host memory it reads next).  Returns what
+        inner.tick() returned."""
+        todo = [(slot, self._pending[slot], slot * self.max_packet, slot * self._model_cap) for slot in sorted(self._open) if self._pending[slot] > 0]
+        if todo:
+            self.to_model.step_streams_pinned(self._cin, self.state_in, self.capacity, todo, self._min, self.max_packet, produced=self._made_in[:len(todo)])
+            self.to_model.synchronize()
+            # the launch has consumed every stream's samples: the counters follow it for all of them before anything can raise
+            made_in = []
+            for i, (slot, n, _, _) in enumerate(todo):
+                made = int(self._made_in[i])
+                if made != self.to_model.produced(self._consumed[slot], n):
+                    raise RuntimeError(f"slot {slot}: the resampler made {made} samples of {n}, {self.to_model.produced(self._consumed[slot], n)} were due")
+                made_in.append(made)
+            for slot, n, _, _ in todo:
+                self._consumed[slot] += n
+                self._pending[slot] = 0
+            # push() has checked that the inner ring holds them.  Should inner.push raise all the same, the exception leaves the pool
+            # consistent - every counter describes what the resamplers and the inner pool hold - and the samples of that slot and of the
+            # slots behind it in this tick are dropped: those streams go on with a gap
+            for (slot, _, _, _), made in zip(todo, made_in):
+                if made:
+                    self.inner.push(slot, self._min[slot, :made])
+                    self._fill[slot] += made
+        launched = self.inner.tick()
+        back = []
+        for slot in sorted(self._open):
+            y = self.inner.pull(slot)
+            n = int(y.numel())
+            if n:
+                self._mout[slot, :n] = y
+                self._fill[slot] -= n
+                back.append((slot, n, slot * self._step, slot * self._client_cap))
+        if back:
+            self.to_client.step_streams_pinned(self._mout, self.state_out, self.capacity, back, self._cout, self._step, produced=self._made_out[:len(back)])
+            self.to_client.synchronize()
+            for i, (slot, _, _, _) in enumerate(back):
+                made = int(self._made_out[i])
+                if made:
+                    self._ready[slot].append(self._cout[slot, :made].clone())
+        return launched
+
+    def pull(self, slot: int) -> Tensor:
+        """The enhanced int16 samples at the client's rate made since the last pull (a copy; empty when there are none)."""
+        self._check_open(slot)
+        parts, self._ready[slot] = self._ready[slot], []
+        return torch.cat(parts) if parts else torch.zeros(0, dtype=torch.int16)

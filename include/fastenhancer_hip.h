@@ -632,6 +632,78 @@ int fe_debug_poison_lds(void* stream);
  * FE_ERR_INVALID_ARG with nothing written. */
 int fe_debug_pack_weights(fe_handle* h, const float* blob_host, size_t nfloats, float* out_host, size_t capacity, size_t* packed_floats);
 
+/* ---- Audio at another sample rate: a polyphase resampler sr_in -> sr_out, for whole signals and for packet streams.
+ * (The reference's callers load every file with librosa.load(path, sr=model_rate) - scripts/test_onnx.py:14, scripts/test_pytorch.py:29 - and
+ * scripts/resample.py:75-80 offers this filter as its `polyphase` type: scipy.signal.resample_poly(x, up, down) with its defaults.)
+ *
+ * The contract.  g = gcd(sr_in, sr_out), up = sr_out / g, down = sr_in / g, R = max(up, down), hl = 10 R, L = 2 hl + 1.
+ * Taps h[t] = up * h0[t], h0[t] = sinc((t - hl) / R) / R * I0(5 sqrt(1 - ((t - hl) / hl)^2)) / I0(5) scaled to sum 1 - that is
+ * up * firwin(L, 1 / R, window = ("kaiser", 5.0)) - designed in double and rounded to fp32 once.  K = ceil(L / up) taps per output.
+ * Output m of an input x[0 .. N):  c = m down + hl,  kmax = c div up,  r = c mod up,
+ *     y[m] = sum over j = 0 .. K - 1 with r + j up <= 2 hl of  h[r + j up] * x[kmax - j],      x = 0 outside [0, N),
+ * accumulated in fp32 from +0 with j ascending, one fused multiply-add per tap.  Against the same sum in double the error is at most
+ * (K + 2) 2^-24 S max|x| with S = max over r of sum over j of |h[r + j up]| (a K-term fp32 dot product and one rounding of each tap).
+ * A whole-signal call returns ceil(N up / down) outputs.  A stream that has consumed N samples has emitted
+ *     M(N) = max(0, ceil((N up - hl) / down))
+ * outputs - every output whose newest input x[kmax] has arrived - so its latency is hl / up input samples (30 at 48 -> 16 kHz, 10 at
+ * 8 -> 16 kHz), and under ANY packetisation its outputs are the first M(N) outputs of the whole-signal call on the same samples, bit for
+ * bit.  There is no flush: a caller that wants the tail pushes hl / up zeros.  int16 input is the float input s / 32768 (exact); int16
+ * output is clamp(rint(y * 32768), -32768, 32767), ties to even, NaN -> 0, of the float output (the rules of fe_step_streams).
+ *
+ * The create call and every query work without a GPU (as the model handle's do); the tap table is uploaded to the device that is current
+ * at the handle's FIRST launch (one allocation and one synchronous copy: make that launch outside a graph capture), and the handle
+ * belongs to that device from then on.  Equal rates or a rate <= 0 are FE_ERR_INVALID_ARG; a reduced ratio with max(up, down) > 640 is
+ * FE_ERR_UNSUPPORTED_CONFIG (every pair among 8, 11.025, 12, 16, 22.05, 24, 32, 44.1 and 48 kHz fits - 48 -> 11.025 kHz is 147 / 640 -
+ * except 11.025 <-> 32 kHz, which is 441 / 1280). */
+typedef struct fe_resampler fe_resampler;
+int fe_resampler_create(int sr_in, int sr_out, fe_resampler** out);
+void fe_resampler_destroy(fe_resampler* rs);
+int fe_resampler_up(const fe_resampler* rs);
+int fe_resampler_down(const fe_resampler* rs);
+int fe_resampler_taps_per_output(const fe_resampler* rs);      /* K */
+int fe_resampler_half_len(const fe_resampler* rs);             /* hl */
+/* the L = 2 hl + 1 taps h in double, as designed (n < L is FE_ERR_INVALID_ARG with nothing written; out == NULL returns L) */
+int fe_resampler_taps(const fe_resampler* rs, double* out, size_t n);
+/* ceil(n_in up / down); and M(consumed + n_in) - M(consumed), what a stream emits for its next n_in samples.  Negative arguments give -1. */
+long long fe_resampler_out_count(const fe_resampler* rs, long long n_in);
+long long fe_resampler_produced(const fe_resampler* rs, long long consumed, long long n_in);
+/* floats of one stream's state row (below) */
+size_t fe_resampler_state_floats(const fe_resampler* rs);
+/* the kernel the handle's last launch enqueued ("" before the first) */
+const char* fe_resampler_last_kernel(const fe_resampler* rs);
+
+/* B whole signals: row b is in_dev[b * in_stride + i], i < n_in, elements of in_format (FE_AUDIO_*); its fe_resampler_out_count outputs
+ * go to out_dev[b * out_stride + m] as elements of out_format, and nothing else of a row is written.  n_in >= 1, B >= 1,
+ * in_stride >= n_in, out_stride >= the output count.  Asynchronous on `stream`. */
+int fe_resample(fe_resampler* rs, const void* in_dev, size_t in_stride, int in_format, long long n_in, void* out_dev, size_t out_stride,
+                int out_format, int B, void* stream);
+
+/* n packet streams in one launch.  Call stream i has a descriptor in DEVICE memory, read when the kernel runs: its state slot, the samples it
+ * consumes now and the element offsets of its first input / output sample in the flat buffers in [in_count] / out [out_count].
+ * State: state_dev [capacity][state_floats] floats, one row per slot -
+ *     hist[K - 1]     the last K - 1 input samples as floats, oldest first
+ *     2 words         the consumed sample count, low 32-bit word first
+ *     padding         to a multiple of 4 floats
+ * A zero row is a fresh stream; rows are plain data: copying a row moves a stream, zeroing it restarts one.
+ * Per stream: n_in is clamped to [0, n_in_max]; the stream then emits p = M(consumed + n_in) - M(consumed) outputs.  A stream whose slot is
+ * outside [0, capacity), or whose ranges [in_offset, in_offset + n_in) / [out_offset, out_offset + p) do not lie inside the buffers, is
+ * SKIPPED: nothing of it is read, nothing written, its row untouched.  produced (may be NULL) is an int table [n] indexed by call stream,
+ * device or page-locked host memory: p, and 0 for a skipped stream, written for every i.  Elements of out past a stream's p outputs are
+ * not written.  One slot named twice in a call is undefined.  The call allocates nothing and synchronises nothing (after the handle's
+ * first launch, above).
+ * _pinned: in / out are page-locked HOST memory with a device mapping (the rules of fe_step_streams_pinned: pageable memory is refused
+ * before any launch, the launch is asynchronous, synchronise the stream before reading out or rewriting in). */
+typedef struct fe_resample_desc {    /* 24 bytes */
+    int slot, n_in;
+    long long in_offset, out_offset;
+} fe_resample_desc;
+int fe_resample_streams(fe_resampler* rs, const void* in, size_t in_count, int in_format, float* state_dev, int capacity,
+                        const fe_resample_desc* desc_dev, void* out, size_t out_count, int out_format, int* produced, int n, int n_in_max,
+                        void* stream);
+int fe_resample_streams_pinned(fe_resampler* rs, const void* in, size_t in_count, int in_format, float* state_dev, int capacity,
+                               const fe_resample_desc* desc_dev, void* out, size_t out_count, int out_format, int* produced, int n, int n_in_max,
+                               void* stream);
+
 const char* fe_last_error(void);
 const char* fe_version(void);
 /* r6: the digest of the sources this library was built from (fastenhancer_amd/build.py::source_key: csrc/* and this header).  The Python binding refuses an
