@@ -1430,54 +1430,73 @@ struct BImpl {
     bool whh_regs;            // W_hh packing: [rr][k'][128] floats (register shapes) or [rr][k'/4][128] float4 (streamed)
     bool ksplit;              // thread <-> (unit, K quarter) holding all four gates (BShape::KSPLIT) or (unit, gate) over the whole K
     int rec_threads;          // threads of one direction of the band recurrence (BShape::NTD)
-    void (*launch)(const BArgs&, int max_wgs, hipStream_t, hipError_t*);
+    // every launch of the per-stream kernels but the two further down: the flavour's instantiations on the prefix of the block that is their
+    // argument block (plain: fe_step and the debug / profile steps, fe_spec_step, fe_offline; slotted: fe_step_pool; packet:
+    // fe_step_pool_streams[_pinned]).  split: the per-hop step as three launches (mlp_x / mlp_sp / mlp_pre set), else one kernel walks the frame.
+    void (*launch_step)(const BStreamArgs&, StepFlavour, bool split, int max_wgs, hipStream_t, hipError_t*);
     void (*dbg_stage)(int, int*, int*, size_t*);
     void (*launch_pipe)(const BArgs&, hipStream_t, hipError_t*);       // time-pipelined offline launch (cooperative: B * pipe_p workgroups)
     int occ;                  // workgroups per CU the LDS plan allows
-    void (*launch_split)(const BArgs&, int max_wgs, hipStream_t, hipError_t*);   // the per-hop step as three launches (mlp_x / mlp_sp / mlp_pre set)
     // the per-hop step with the layers batched over the streams (bsrnn_sb_kernels.hip.h): front (PART 3) -> layers -> mask-decoder MLP -> tail
     // (PART 2); nullptr where the stream-batched layers are not built (num_channels > 16)
     void (*launch_sb)(const BArgs&, const SbOffsets&, int total_floats, int max_wgs, hipStream_t, hipError_t*);
     const char* name = nullptr;      // the line of fe_bsrnn_shapes.def (fe_bsrnn_shape.hip.in): part of fe_last_step_kernel's answer
-    // fe_step_pool: the launches of `launch` (split = false) / `launch_split` (split = true: mlp_x / mlp_sp / mlp_pre set) with the slotted
-    // instantiations of the per-stream kernels
-    void (*launch_slots)(const BSlotArgs&, bool split, int max_wgs, hipStream_t, hipError_t*) = nullptr;
-    // fe_step_pool_streams[_pinned]: launch_slots' launches with the packet instantiations
-    void (*launch_streams)(const BStreamArgs&, bool split, int max_wgs, hipStream_t, hipError_t*) = nullptr;
 };
 
-template <class S, bool HOT, bool PROF, bool DBG, bool OCC2 = false>
-void blaunch_one(const BArgs& a, int grid, hipStream_t st, hipError_t* err) {
-    const char* name = DBG ? "bsrnn_frame_kernel<debug>" : PROF ? "bsrnn_frame_kernel<profile>" : HOT ? (OCC2 ? "bsrnn_frame_kernel<per-hop, two workgroups per CU>" : "bsrnn_frame_kernel<per-hop>")
-                           : (OCC2 ? "bsrnn_frame_kernel<generic, two workgroups per CU>" : "bsrnn_frame_kernel<generic>");
-    *err = launch<&bsrnn_frame_kernel<S, HOT, PROF, DBG, OCC2>>(name, dim3(grid), dim3(kThreads), BLds<S>::BYTES, st, a);
+// fe_last_step_kernel's texts of the per-stream kernel: what it is, the flavour, and the occupancy it was compiled for
+constexpr KernelNames bframe_names(const char* what, bool occ2, bool slot, bool strm) {
+    return kernel_names("bsrnn_frame_kernel", 0, what, baseline_flavour(slot, strm), occ2 ? "two workgroups per CU" : "");
+}
+static_assert(same_text(bframe_names("per-hop", false, false, false).s[0], "bsrnn_frame_kernel<per-hop>") &&
+              same_text(bframe_names("generic", true, false, false).s[0], "bsrnn_frame_kernel<generic, two workgroups per CU>") &&
+              same_text(bframe_names("per-hop", false, true, false).s[0], "bsrnn_frame_kernel<per-hop, slots>") &&
+              same_text(bframe_names("generic", true, true, true).s[3], "bsrnn_frame_kernel<generic, slots, streams, pinned, s16, two workgroups per CU>") &&
+              same_text(bframe_names("PART 1", false, false, false).s[0], "bsrnn_frame_kernel<PART 1>") &&
+              same_text(bframe_names("PART 1", true, true, false).s[0], "bsrnn_frame_kernel<PART 1, slots, two workgroups per CU>") &&
+              same_text(bframe_names("PART 1", true, true, true).s[3], "bsrnn_frame_kernel<PART 1, slots, streams, pinned, s16, two workgroups per CU>") &&
+              same_text(bframe_names("PART 2", false, true, true).s[1], "bsrnn_frame_kernel<PART 2, slots, streams, pinned>"),
+              "the texts fe_last_step_kernel has always reported (the longest: 79 characters)");
+
+// SLOT (fe_step_pool) / STRM (fe_step_pool_streams[_pinned]): the slotted / packet instantiation - streaming mode; no debug dumps or cycle probes
+template <class S, bool HOT, bool PROF, bool DBG, bool OCC2 = false, bool SLOT = false, bool STRM = false>
+void blaunch_one(const typename BKernelArgs<SLOT, STRM>::type& a, int grid, hipStream_t st, hipError_t* err) {
+    static constexpr KernelNames names = bframe_names(DBG ? "debug" : PROF ? "profile" : HOT ? "per-hop" : "generic", OCC2, SLOT, STRM);
+    *err = launch<&bsrnn_frame_kernel<S, HOT, PROF, DBG, OCC2, false, 0, SLOT, STRM>>(baseline_name<STRM>(names, a), dim3(grid), dim3(kThreads), BLds<S>::BYTES, st, a);
 }
 
-template <class S>
-void blaunch_impl(const BArgs& a, int max_wgs, hipStream_t st, hipError_t* err) {
+// one kernel walks the frame(s) of a stream
+template <class S, bool SLOT = false, bool STRM = false>
+void blaunch_impl(const typename BKernelArgs<SLOT, STRM>::type& a, int max_wgs, hipStream_t st, hipError_t* err) {
     constexpr bool FITS2 = 2 * BLds<S>::BYTES <= 160 * 1024 && !S::XPG;
-    if (FITS2 && a.B > max_wgs && a.dbg == nullptr && a.clk == nullptr) {      // two workgroups per CU, persistent above 2 x #CUs streams
+    const bool hot = a.mode == FE_MODE_STREAM && a.T == 1;
+    bool probed = false;                                                                        // fe_debug_step / fe_profile_step: never slotted
+    if constexpr (!SLOT) probed = a.dbg != nullptr || a.clk != nullptr;
+    if (FITS2 && a.B > max_wgs && !probed) {      // two workgroups per CU, persistent above 2 x #CUs streams
         const int grid2 = a.B < 2 * max_wgs ? a.B : 2 * max_wgs;
-        if (a.mode == FE_MODE_STREAM && a.T == 1) blaunch_one<S, true, false, false, FITS2>(a, grid2, st, err);
-        else blaunch_one<S, false, false, false, FITS2>(a, grid2, st, err);
+        if (hot) blaunch_one<S, true, false, false, FITS2, SLOT, STRM>(a, grid2, st, err);
+        else blaunch_one<S, false, false, false, FITS2, SLOT, STRM>(a, grid2, st, err);
         return;
     }
     const int grid = a.B < max_wgs ? a.B : max_wgs;      // more streams than CUs: persistent workgroups walk b, b + grid, ...
-    if (a.dbg != nullptr) blaunch_one<S, false, false, true>(a, grid, st, err);                 // fe_debug_step
-    else if (a.clk != nullptr) {                                                                // fe_profile_step
-        if (a.mode == FE_MODE_STREAM && a.T == 1) blaunch_one<S, true, true, false>(a, grid, st, err);
-        else blaunch_one<S, false, true, false>(a, grid, st, err);
+    if constexpr (!SLOT) {
+        if (a.dbg != nullptr) return blaunch_one<S, false, false, true>(a, grid, st, err);      // fe_debug_step
+        if (a.clk != nullptr) {                                                                 // fe_profile_step
+            if (hot) blaunch_one<S, true, true, false>(a, grid, st, err);
+            else blaunch_one<S, false, true, false>(a, grid, st, err);
+            return;
+        }
     }
-    else if (a.mode == FE_MODE_STREAM && a.T == 1) blaunch_one<S, true, false, false>(a, grid, st, err);
-    else blaunch_one<S, false, false, false>(a, grid, st, err);
+    if (hot) blaunch_one<S, true, false, false, false, SLOT, STRM>(a, grid, st, err);
+    else blaunch_one<S, false, false, false, false, SLOT, STRM>(a, grid, st, err);
 }
 
-template <class S, bool OCC2, int PART>
-void blaunch_part(const BArgs& a, int grid, hipStream_t st, hipError_t* err) {
-    using LP = BLds<S, (PART == 2 || PART == 3) ? PART : 0>;
-    const char* name = PART == 1 ? (OCC2 ? "bsrnn_frame_kernel<PART 1, two workgroups per CU>" : "bsrnn_frame_kernel<PART 1>")
-                       : PART == 2 ? "bsrnn_frame_kernel<PART 2>" : "bsrnn_frame_kernel<PART 3>";      // (r6: their own LDS plans, up to four workgroups per CU)
-    *err = launch<&bsrnn_frame_kernel<S, true, false, false, OCC2, false, PART>>(name, dim3(grid), dim3(kThreads), LP::BYTES, st, a);
+// a per-stream part of the per-hop step in several launches (PART 3: the stream-batched step's front, plain only)
+template <class S, bool OCC2, int PART, bool SLOT = false, bool STRM = false>
+void blaunch_part(const typename BKernelArgs<SLOT, STRM>::type& a, int grid, hipStream_t st, hipError_t* err) {
+    static_assert(!SLOT || PART == 1 || PART == 2, "slotted: the three-launch step's per-stream parts");
+    using LP = BLds<S, (PART == 2 || PART == 3) ? PART : 0>;      // (r6: their own LDS plans, up to four workgroups per CU)
+    static constexpr KernelNames names = bframe_names(PART == 1 ? "PART 1" : PART == 2 ? "PART 2" : "PART 3", PART == 1 && OCC2, SLOT, STRM);
+    *err = launch<&bsrnn_frame_kernel<S, true, false, false, OCC2, false, PART, SLOT, STRM>>(baseline_name<STRM>(names, a), dim3(grid), dim3(kThreads), LP::BYTES, st, a);
 }
 
 // grid of a per-stream front / tail launch (PART 3 / 2): their own LDS plans fit four times per CU
@@ -1488,53 +1507,40 @@ int bpart_grid(int B, int max_wgs) {
     return B < OCC * max_wgs ? B : OCC * max_wgs;
 }
 
-// fe_last_step_kernel's names of a slotted launch (fe_step_pool: s[0]) and of its packet twin (fe_step_pool_streams: "streams" after "slots", then
-// "pinned" and "s16" - where the audio lives and its format are run-time facts of that call, hence a constant string for each of the four:
-// s[1 + pinned + 2 * s16]): `pre` + "slots[, streams[, pinned][, s16]]" + `post`, put together at compile time so that note_kernel gets a constant string
-struct BSlotNames { char s[5][96] = {}; };
-constexpr BSlotNames bslot_names(const char* pre, const char* post) {
-    BSlotNames n;
-    const char* mid[5] = {"slots", "slots, streams", "slots, streams, pinned", "slots, streams, s16", "slots, streams, pinned, s16"};
-    for (int v = 0; v < 5; ++v) {
-        int k = 0;
-        const char* parts[3] = {pre, mid[v], post};
-        for (const char* p : parts)
-            while (*p) n.s[v][k++] = *p++;
-    }
-    return n;
-}
-template <class A> constexpr bool kBStreams = std::is_base_of<StreamIoArgs, A>::value;      // the launch is the packet step's
-template <class A>
-int bslot_name(const A& a) {
-    if constexpr (kBStreams<A>) return 1 + (a.pinned != 0) + 2 * (a.format != 0);
-    else return 0;
-}
-
 }  // namespace fe
 #include "bsrnn_sb_kernels.hip.h"
 #include "bsrnn_ov_kernels.hip.h"
 namespace fe {
 
-// the per-hop streaming step (mode = stream, T = 1) as head -> batched mask-decoder MLP -> tail
-template <class S>
-void blaunch_split_impl(const BArgs& a, int max_wgs, hipStream_t st, hipError_t* err) {
+// the per-hop streaming step (mode = stream, T = 1) as head -> batched mask-decoder MLP -> tail.  SLOT / STRM: each of the three launches reads
+// a.slots itself (the packet step: the stream's descriptor): the two per-stream parts skip a stream whose slot is out of range (or that has no hop,
+// or whose audio ranges leave the buffers).  The batched mask decoder between them touches no state and takes no slots; its rows are per stream,
+// so a skipped stream's stale scratch row reaches no other stream.
+template <class S, bool SLOT = false, bool STRM = false>
+void blaunch_split_impl(const typename BKernelArgs<SLOT, STRM>::type& a, int max_wgs, hipStream_t st, hipError_t* err) {
     constexpr bool FITS2 = 2 * BLds<S>::BYTES <= 160 * 1024 && !S::XPG;
+    const bool two = FITS2 && a.B > max_wgs;      // two workgroups per CU
     // r5: at most one stream per CU and num_channels = 16 - the role-split PART 1 (bsrnn_ov_kernels.hip.h: the scans alone on two
     // waves, the layers' matrix-core work under them on the other two).  a.ov_off (fe_set_step_kernel(WAVES4) / fe_set_option("bsrnn_role_split", 0)):
     // the phase-by-phase kernel.
-    if (S::C == 16 && !a.ov_off && a.B <= max_wgs && a.clk != nullptr) blaunch_ov<S, true>(a, a.B, st, err);      // (fe_profile_step with fe_set_option("bsrnn_ov_profile", 1))
-    else if (S::C == 16 && !a.ov_off && a.B <= max_wgs && a.gsync != nullptr) {
-        // r6: the whole step in ONE cooperative launch (fe_set_option("bsrnn_fused_step", 1); MEASURED NEGATIVE - 81 us against 77, and the
-        // cooperative launch adds ~21 us on top: profiles/r6_bsrnn_fused_step.txt - hence off by default); a launch the runtime refuses
-        // (co-residency not guaranteed) falls through to the three launches
-        blaunch_ov<S, false, true>(a, a.B, st, err);
-        if (*err == hipSuccess) return;
-        *err = hipSuccess;
-        blaunch_ov<S>(a, a.B, st, err);
+    if (S::C == 16 && !a.ov_off && a.B <= max_wgs) {
+        if constexpr (!SLOT) {
+            if (a.clk != nullptr) blaunch_ov<S, true>(a, a.B, st, err);      // (fe_profile_step with fe_set_option("bsrnn_ov_profile", 1))
+            else {
+                if (a.gsync != nullptr) {
+                    // r6: the whole step in ONE cooperative launch (fe_set_option("bsrnn_fused_step", 1); MEASURED NEGATIVE - 81 us against 77, and the
+                    // cooperative launch adds ~21 us on top: profiles/r6_bsrnn_fused_step.txt - hence off by default); a launch the runtime refuses
+                    // (co-residency not guaranteed) falls through to the three launches
+                    blaunch_ov<S, false, true>(a, a.B, st, err);
+                    if (*err == hipSuccess) return;
+                    *err = hipSuccess;
+                }
+                blaunch_ov<S>(a, a.B, st, err);
+            }
+        } else blaunch_ov<S, false, false, SLOT, STRM>(a, a.B, st, err);
     }
-    else if (S::C == 16 && !a.ov_off && a.B <= max_wgs) blaunch_ov<S>(a, a.B, st, err);
-    else if (FITS2 && a.B > max_wgs) blaunch_part<S, FITS2, 1>(a, a.B < 2 * max_wgs ? a.B : 2 * max_wgs, st, err);
-    else blaunch_part<S, false, 1>(a, a.B < max_wgs ? a.B : max_wgs, st, err);
+    else if (two) blaunch_part<S, FITS2, 1, SLOT, STRM>(a, a.B < 2 * max_wgs ? a.B : 2 * max_wgs, st, err);
+    else blaunch_part<S, false, 1, SLOT, STRM>(a, a.B < max_wgs ? a.B : max_wgs, st, err);
     if (*err != hipSuccess) return;
     {
         BArgs am = a;
@@ -1545,62 +1551,18 @@ void blaunch_split_impl(const BArgs& a, int max_wgs, hipStream_t st, hipError_t*
                                             dim3(kThreads), BMlpLds<S>::BYTES, st, am);
         if (*err != hipSuccess) return;
     }
-    if (FITS2 && a.B > max_wgs) blaunch_part<S, FITS2, 2>(a, bpart_grid<S, 2>(a.B, max_wgs), st, err);
-    else blaunch_part<S, false, 2>(a, bpart_grid<S, 2>(a.B, max_wgs), st, err);
+    if (two) blaunch_part<S, FITS2, 2, SLOT, STRM>(a, bpart_grid<S, 2>(a.B, max_wgs), st, err);
+    else blaunch_part<S, false, 2, SLOT, STRM>(a, bpart_grid<S, 2>(a.B, max_wgs), st, err);
 }
 
-// fe_step_pool / fe_step_pool_streams: blaunch_impl / blaunch_split_impl with the slotted instantiations (A = BSlotArgs) or their packet twins
-// (A = BStreamArgs) - streaming mode; no debug dumps, cycle probes or fused step.
-
-template <class S, bool HOT, bool OCC2, class A>
-void blaunch_one_slots(const A& a, int grid, hipStream_t st, hipError_t* err) {
-    static constexpr BSlotNames names = bslot_names(HOT ? "bsrnn_frame_kernel<per-hop, " : "bsrnn_frame_kernel<generic, ", OCC2 ? ", two workgroups per CU>" : ">");
-    *err = launch<&bsrnn_frame_kernel<S, HOT, false, false, OCC2, false, 0, true, kBStreams<A>>>(names.s[bslot_name(a)], dim3(grid), dim3(kThreads), BLds<S>::BYTES, st, a);
-}
-
-template <class S, bool OCC2, int PART, class A>
-void blaunch_part_slots(const A& a, int grid, hipStream_t st, hipError_t* err) {
-    static_assert(PART == 1 || PART == 2, "the three-launch step's per-stream parts");
-    using LP = BLds<S, PART == 2 ? 2 : 0>;
-    static constexpr BSlotNames names = bslot_names(PART == 1 ? "bsrnn_frame_kernel<PART 1, " : "bsrnn_frame_kernel<PART 2, ", (PART == 1 && OCC2) ? ", two workgroups per CU>" : ">");
-    *err = launch<&bsrnn_frame_kernel<S, true, false, false, OCC2, false, PART, true, kBStreams<A>>>(names.s[bslot_name(a)], dim3(grid), dim3(kThreads), LP::BYTES, st, a);
-}
-
-template <class S, class A>
-void blaunch_slots_impl(const A& a, bool split, int max_wgs, hipStream_t st, hipError_t* err) {
-    constexpr bool FITS2 = 2 * BLds<S>::BYTES <= 160 * 1024 && !S::XPG;
-    const bool two = FITS2 && a.B > max_wgs;
-    if (!split) {
-        const bool hot = a.mode == FE_MODE_STREAM && a.T == 1;
-        if (two) {      // two workgroups per CU, persistent above 2 x #CUs streams
-            const int grid2 = a.B < 2 * max_wgs ? a.B : 2 * max_wgs;
-            if (hot) blaunch_one_slots<S, true, FITS2>(a, grid2, st, err);
-            else blaunch_one_slots<S, false, FITS2>(a, grid2, st, err);
-            return;
-        }
-        const int grid = a.B < max_wgs ? a.B : max_wgs;
-        if (hot) blaunch_one_slots<S, true, false>(a, grid, st, err);
-        else blaunch_one_slots<S, false, false>(a, grid, st, err);
-        return;
+template <class S>
+void blaunch_step_impl(const BStreamArgs& a, StepFlavour flavour, bool split, int max_wgs, hipStream_t st, hipError_t* err) {
+    switch (flavour) {       // (each instantiation's launcher binds the prefix of a that is its kernels' argument block)
+    case STEP_PLAIN: return split ? blaunch_split_impl<S>(a, max_wgs, st, err) : blaunch_impl<S>(a, max_wgs, st, err);
+    case STEP_SLOTS: return split ? blaunch_split_impl<S, true>(a, max_wgs, st, err) : blaunch_impl<S, true>(a, max_wgs, st, err);
+    case STEP_STREAMS: return split ? blaunch_split_impl<S, true, true>(a, max_wgs, st, err) : blaunch_impl<S, true, true>(a, max_wgs, st, err);
+    default: *err = hipErrorInvalidValue;       // (STEP_SLOTS_PINNED: no entry point of this family asks for it)
     }
-    // each of the three launches reads a.slots itself (the packet step: the stream's descriptor): the two per-stream parts skip a stream whose slot is out
-    // of range (or that has no hop, or whose audio ranges leave the buffers).  The batched mask decoder between them touches no state and takes no
-    // slots; its rows are per stream, so a skipped stream's stale scratch row reaches no other stream.
-    if (S::C == 16 && !a.ov_off && a.B <= max_wgs) blaunch_ov_slots<S>(a, a.B, st, err);
-    else if (two) blaunch_part_slots<S, FITS2, 1>(a, a.B < 2 * max_wgs ? a.B : 2 * max_wgs, st, err);
-    else blaunch_part_slots<S, false, 1>(a, a.B < max_wgs ? a.B : max_wgs, st, err);
-    if (*err != hipSuccess) return;
-    {
-        BArgs am = a;
-        const bool msplit = S::C == 16 && a.B <= max_wgs;
-        am.mlp_tpw = msplit ? 0 : 1;
-        const int groups = msplit ? (a.B + 15) / 16 : (a.B + 16 * kWaves - 1) / (16 * kWaves);
-        *err = launch<&bsrnn_mlp_kernel<S>>(msplit ? "bsrnn_mlp_kernel<one 16-stream tile per workgroup>" : "bsrnn_mlp_kernel", dim3(2 * kBands * groups),
-                                            dim3(kThreads), BMlpLds<S>::BYTES, st, am);
-        if (*err != hipSuccess) return;
-    }
-    if (two) blaunch_part_slots<S, FITS2, 2>(a, bpart_grid<S, 2>(a.B, max_wgs), st, err);
-    else blaunch_part_slots<S, false, 2>(a, bpart_grid<S, 2>(a.B, max_wgs), st, err);
 }
 
 template <class S, bool MULTI>
@@ -1654,13 +1616,10 @@ void bdbg_stage_impl(int s, int* rows, int* cols, size_t* off) {
 
 template <class S>
 BImpl make_bimpl() {
-    BImpl im = BImpl{S::C, S::NLAY, S::HOP, BLds<S>::BYTES, S::XPG ? (size_t)2 * 32 * S::G4 : (size_t)0,
-                 BDebugLayout<S>::total(), BDebugLayout<S>::n_stages, S::WREG, S::KSPLIT, S::NTD, &blaunch_impl<S>, &bdbg_stage_impl<S>,
+    return BImpl{S::C, S::NLAY, S::HOP, BLds<S>::BYTES, S::XPG ? (size_t)2 * 32 * S::G4 : (size_t)0,
+                 BDebugLayout<S>::total(), BDebugLayout<S>::n_stages, S::WREG, S::KSPLIT, S::NTD, &blaunch_step_impl<S>, &bdbg_stage_impl<S>,
                  &blaunch_pipe_impl<S>, 1,       // (the PIPE instantiation is compiled for one workgroup per CU: waves_per_eu(1, 1))
-                 &blaunch_split_impl<S>, (SbLds<S>::FITS || Sb64Lds<S>::FITS) ? &blaunch_sb_impl<S> : nullptr};
-    im.launch_slots = &blaunch_slots_impl<S, BSlotArgs>;
-    im.launch_streams = &blaunch_slots_impl<S, BStreamArgs>;
-    return im;
+                 (SbLds<S>::FITS || Sb64Lds<S>::FITS) ? &blaunch_sb_impl<S> : nullptr};
 }
 
 }  // namespace fe

@@ -710,24 +710,23 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
 }
 #undef OV_CLK
 
-template <class S, bool PROF = false, bool FUSED = false>
-void blaunch_ov(const BArgs& a, int grid, hipStream_t st, hipError_t* err) {
+constexpr KernelNames bov_names(const char* what, bool slot, bool strm) { return kernel_names("bsrnn_ov_kernel", 0, what, baseline_flavour(slot, strm)); }
+static_assert(same_text(bov_names("", false, false).s[0], "bsrnn_ov_kernel") && same_text(bov_names("", true, false).s[0], "bsrnn_ov_kernel<slots>") &&
+              same_text(bov_names("", true, true).s[3], "bsrnn_ov_kernel<slots, streams, pinned, s16>") &&
+              same_text(bov_names("profile", false, false).s[0], "bsrnn_ov_kernel<profile>") && same_text(bov_names("fused step", false, false).s[0], "bsrnn_ov_kernel<fused step>"),
+              "the texts fe_last_step_kernel has always reported");
+
+// (SLOT: fe_step_pool; STRM: the packet twin of fe_step_pool_streams - neither has a profile or a fused form)
+template <class S, bool PROF = false, bool FUSED = false, bool SLOT = false, bool STRM = false>
+void blaunch_ov(const typename BKernelArgs<SLOT, STRM>::type& a, int grid, hipStream_t st, hipError_t* err) {
+    static_assert(!SLOT || (!PROF && !FUSED), "the slotted instantiations are the plain role-split kernel");
     if constexpr (S::C == 16) {
+        static constexpr KernelNames names = bov_names(FUSED ? "fused step" : PROF ? "profile" : "", SLOT, STRM);
+        const char* name = baseline_name<STRM>(names, a);
         // FUSED: the workgroups of a sixteen-stream tile wait for each other - a cooperative launch (co-residency guaranteed, or refused: the
         // caller then falls back to the three launches, so a refusal notes nothing and leaves no error behind)
-        if constexpr (FUSED) *err = launch_coop<&bsrnn_ov_kernel<S, PROF, FUSED>, true>("bsrnn_ov_kernel<fused step>", dim3(grid), dim3(kThreads), BOvLds<S>::BYTES, st, a);
-        else *err = launch<&bsrnn_ov_kernel<S, PROF, FUSED>>(PROF ? "bsrnn_ov_kernel<profile>" : "bsrnn_ov_kernel", dim3(grid), dim3(kThreads), BOvLds<S>::BYTES, st, a);
-    } else {
-        *err = hipErrorInvalidValue;
-    }
-}
-
-// (A = BSlotArgs: fe_step_pool; BStreamArgs: the packet twin of fe_step_pool_streams)
-template <class S, class A>
-void blaunch_ov_slots(const A& a, int grid, hipStream_t st, hipError_t* err) {
-    if constexpr (S::C == 16) {
-        static constexpr BSlotNames names = bslot_names("bsrnn_ov_kernel<", ">");
-        *err = launch<&bsrnn_ov_kernel<S, false, false, true, kBStreams<A>>>(names.s[bslot_name(a)], dim3(grid), dim3(kThreads), BOvLds<S>::BYTES, st, a);
+        if constexpr (FUSED) *err = launch_coop<&bsrnn_ov_kernel<S, PROF, FUSED>, true>(name, dim3(grid), dim3(kThreads), BOvLds<S>::BYTES, st, a);
+        else *err = launch<&bsrnn_ov_kernel<S, PROF, FUSED, SLOT, STRM>>(name, dim3(grid), dim3(kThreads), BOvLds<S>::BYTES, st, a);
     } else {
         *err = hipErrorInvalidValue;
     }

@@ -876,7 +876,7 @@ int baseline_offline(Fam, fe_handle* h, const float* noisy_dev, int B, int Tw, f
     const int T = 1 + Tw / d.HOP;
     const OfflineLayout L = baseline_layout(Fam{}, h, B, T);
     FE_HIP_CHECK(hipMemsetAsync(work_dev, 0, (L.pipe + L.p.frames) * sizeof(float), st));      // (the counters too, whichever launch follows)
-    typename Fam::Args a = Fam::args(h, B, T);
+    typename Fam::StreamArgs a = Fam::args(h, B, T);
     a.mode = fe::FE_MODE_OFFLINE;
     a.Tw = Tw;
     a.wav_in = noisy_dev; a.in_stride = (size_t)Tw;
@@ -894,7 +894,7 @@ int baseline_offline(Fam, fe_handle* h, const float* noisy_dev, int B, int Tw, f
         Fam::impl(h)->launch_pipe(p, st, &e);
         if (!coop_refused(e)) return ola(h, p.frames, wav_hat_dev, a.out_stride, B, T, st);
     }
-    return Fam::launch(h, a, st);
+    return Fam::launch_step(h, a, fe::STEP_PLAIN, st);
 }
 
 extern "C" {
@@ -1236,6 +1236,32 @@ static int launch_fe_step(fe_handle* h, const char* fn, fe::StepFlavour flavour,
     return launch_rc(e);
 }
 
+// launch_fe_step's counterpart for BSRNN, FSPEN and LiSenNet: the family's streaming step of n streams, however it was asked for.  The entry point
+// sets the flavour's own fields in `own`, this builds the family's argument block around them and launches.  own.capacity = the rows of the state
+// (n for the plain flavour).  STEP_PLAIN (fe_step, the debug / profile steps): dbg, clk.  STEP_SLOTS (fe_step_pool): slots.  STEP_STREAMS
+// (fe_step_pool_streams[_pinned]): io - desc, in_count, out_count, format, pinned (no strides: each stream's rows lie at its own offsets).
+struct BaselineStepOwn {
+    float* dbg = nullptr;
+    unsigned long long* clk = nullptr;
+    int capacity = 0;
+    const int* slots = nullptr;
+    fe::StreamIoArgs io{};
+};
+static int launch_baseline_step(fe_handle* h, fe::StepFlavour flavour, const BaselineStepOwn& own, const float* wav_in, size_t in_stride, float* state,
+                                float* wav_out, size_t out_stride, int n, int T, void* stream) {
+    int rc = FE_OK;
+    visit_baseline(h->cfg.arch, [&](auto F) {
+        auto a = F.args(h, n, T);
+        if (flavour == fe::STEP_PLAIN) { a.dbg = own.dbg; a.clk = own.clk; a.dbg_stride = F.impl(h)->dbg_floats; }
+        a.capacity = own.capacity;
+        a.slots = own.slots;
+        static_cast<fe::StreamIoArgs&>(a) = own.io;
+        F.state(a) = stream_io(a, wav_in, in_stride, wav_out, out_stride, state, state_layout(h, own.capacity));
+        rc = F.launch_step(h, a, flavour, stream);
+    });
+    return rc;
+}
+
 static int run_step(fe_handle* h, const float* wav_in, size_t in_stride, float* state, float* wav_out, size_t out_stride,
                     int B, int T, float* dbg, unsigned long long* clk, void* stream) {
     int rc = check_ready(h);
@@ -1243,15 +1269,12 @@ static int run_step(fe_handle* h, const float* wav_in, size_t in_stride, float* 
     KernelLogScope klog_(h);
     rc = check_step_args(h, nullptr, "bad argument", wav_in && state && wav_out, B, B, T, in_stride, out_stride);
     if (rc != FE_OK) return rc;
-    if (visit_baseline(h->cfg.arch, [&](auto F) {
-            auto a = F.args(h, B, T);
-            a.clk = clk;
-            a.dbg = dbg;
-            a.dbg_stride = F.impl(h)->dbg_floats;
-            F.state(a) = stream_io(a, wav_in, in_stride, wav_out, out_stride, state, state_layout(h, B));
-            rc = F.launch(h, a, stream);
-        }))
-        return rc;
+    if (h->cfg.arch != FE_ARCH_FASTENHANCER) {
+        BaselineStepOwn own;
+        own.dbg = dbg; own.clk = clk;
+        own.capacity = B;
+        return launch_baseline_step(h, fe::STEP_PLAIN, own, wav_in, in_stride, state, wav_out, out_stride, B, T, stream);
+    }
     if (h->d.BD) return fail(FE_ERR_UNSUPPORTED_CONFIG, "%s", kNoncausalNoStep);
     fe::StreamFrameArgs own{};
     own.dbg = dbg; own.clk = clk; own.dbg_stride = h->impl->dbg_floats;
@@ -1304,16 +1327,9 @@ int fe_step_pool(fe_handle* h, const float* wav_in_dev, size_t in_stride, float*
     KernelLogScope klog_(h);
     rc = check_step_args(h, nullptr, kBadSlotArgs, wav_in_dev && state_dev && slots_dev && wav_out_dev, n, capacity, T, in_stride, out_stride);
     if (rc != FE_OK) return rc;
-    visit_baseline(h->cfg.arch, [&](auto F) {
-        using Fam = decltype(F);
-        typename Fam::SlotArgs a{};
-        static_cast<typename Fam::Args&>(a) = F.args(h, n, T);
-        a.capacity = capacity;
-        a.slots = slots_dev;
-        F.state(a) = stream_io(a, wav_in_dev, in_stride, wav_out_dev, out_stride, state_dev, state_layout(h, capacity));
-        rc = F.launch_slots(h, a, stream);
-    });
-    return rc;
+    BaselineStepOwn own;
+    own.capacity = capacity; own.slots = slots_dev;
+    return launch_baseline_step(h, fe::STEP_SLOTS, own, wav_in_dev, in_stride, state_dev, wav_out_dev, out_stride, n, T, stream);
 }
 
 // fe_step_pinned / fe_step_slots_pinned: `count` floats from p must be page-locked host memory with a device mapping on the current device
@@ -1514,20 +1530,12 @@ static int step_pool_streams(fe_handle* h, const char* fn, bool pinned, const vo
     const void* out = nullptr;
     rc = streams_audio(fn, pinned, format, wav_in, in_count, wav_out, out_count, &in, &out);
     if (rc != FE_OK) return rc;
-    visit_baseline(h->cfg.arch, [&](auto F) {
-        using Fam = decltype(F);
-        typename Fam::StreamArgs a{};
-        static_cast<typename Fam::Args&>(a) = F.args(h, n, T_max);
-        a.capacity = capacity;
-        a.desc = reinterpret_cast<const fe::StreamDesc*>(desc_dev);
-        a.in_count = in_count; a.out_count = out_count;
-        a.format = format;
-        a.pinned = pinned ? 1 : 0;
-        // (the audio is typed by a.format in the kernel; no strides: each stream's rows lie at its own offsets)
-        F.state(a) = stream_io(a, static_cast<const float*>(in), 0, const_cast<float*>(static_cast<const float*>(out)), 0, state_dev, state_layout(h, capacity));
-        rc = F.launch_streams(h, a, stream);
-    });
-    return rc;
+    BaselineStepOwn own;
+    own.capacity = capacity;
+    own.io = fe::StreamIoArgs{reinterpret_cast<const fe::StreamDesc*>(desc_dev), in_count, out_count, format, pinned ? 1 : 0};
+    // (the audio is typed by the format in the kernel)
+    return launch_baseline_step(h, fe::STEP_STREAMS, own, static_cast<const float*>(in), 0, state_dev, const_cast<float*>(static_cast<const float*>(out)), 0, n,
+                                T_max, stream);
 }
 
 int fe_step_pool_streams(fe_handle* h, const void* wav_in_dev, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,
@@ -1943,7 +1951,7 @@ int fe_spec_step(fe_handle* h, const float* spec_in_dev, float* h_dev, float* sp
             auto a = F.args(h, B, T);
             a.mode = fe::FE_MODE_SPEC;
             a.spec_in = spec_in_dev; a.spec_out = spec_out_dev; F.state(a) = h_dev;
-            rc = F.launch(h, a, stream);
+            rc = F.launch_step(h, a, fe::STEP_PLAIN, stream);
         }))
         return rc;
     if (h->d.BD) return fail(FE_ERR_UNSUPPORTED_CONFIG, "the noncausal model has no spec -> spec step with caches (models/fastenhancer/noncausal/model.py has the offline Model only): use fe_offline");
@@ -2076,7 +2084,7 @@ static int baseline_step_backlog(Fam, fe_handle* h, const float* wav_in, size_t 
     KernelLogScope klog_(h);
     hipStream_t st = (hipStream_t)stream;
     const Dims& d = h->d;
-    typename Fam::Args a = Fam::args(h, B, T);
+    typename Fam::StreamArgs a = Fam::args(h, B, T);
     Fam::state(a) = stream_io(a, wav_in, in_stride, wav_out, out_stride, state, state_layout(h, B));
     const PipeLayout L = baseline_backlog_layout(Fam{}, h, B, T);
     const typename Fam::Args p = pipe_args(a, work_dev, L, P);
@@ -2087,7 +2095,7 @@ static int baseline_step_backlog(Fam, fe_handle* h, const float* wav_in, size_t 
     Fam::impl(h)->launch_pipe(p, st, &e);
     if (coop_refused(e)) {
         fe::g_klog.n = 0;       // (the refused launch was named before it was tried)
-        return Fam::launch(h, a, stream);
+        return Fam::launch_step(h, a, fe::STEP_PLAIN, stream);
     }
     fe::note_kernel("stream_ola_kernel");
     hipLaunchKernelGGL(fe::stream_ola_kernel, dim3((T * d.HOP + fe::kThreads - 1) / fe::kThreads, B), dim3(fe::kThreads), 0, st,

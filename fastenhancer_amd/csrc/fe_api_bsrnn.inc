@@ -5,7 +5,6 @@ const int kSub[31] = {2, 3, 3, 3, 3, 3, 3, 3, 3, 3, 3, 8, 8, 8, 8, 8, 8, 8, 8, 8
 // The family as fe_api.hip's shared baseline-family paths see it (visit_baseline: the stream and spec steps, offline, the buffer sizes, debug stages)
 struct BsrnnFamily {
     using Args = fe::BArgs;
-    using SlotArgs = fe::BSlotArgs;
     using StreamArgs = fe::BStreamArgs;
     static const fe::BImpl* impl(const fe_handle* h) { return h->bimpl; }
     static const char* shape_name(const fe_handle* h) { return h->bimpl->name; }
@@ -24,13 +23,11 @@ struct BsrnnFamily {
     static size_t ring_floats(const fe_handle*) { return 0; }
     static void set_ring(Args&, float*) {}
     static size_t xp_floats(const fe_handle* h) { return (size_t)h->max_wgs * h->bimpl->xp_floats; }     // (band-LSTM input projections of C = 64)
-    static Args args(fe_handle* h, int B, int T);
+    static StreamArgs args(fe_handle* h, int B, int T);
     static int create(const fe_config* cfg, fe_handle** out);
     static int pack_weights(fe_handle* h, const Blob& S, std::vector<float>* out);
     static int ensure_sb(fe_handle* h, int B);
-    static int launch(fe_handle* h, const Args& a, void* stream);
-    static int launch_slots(fe_handle* h, const SlotArgs& a, void* stream);
-    static int launch_streams(fe_handle* h, const StreamArgs& a, void* stream);
+    static int launch_step(fe_handle* h, StreamArgs& a, fe::StepFlavour flavour, void* stream);
     static const char* stage_name(const fe_handle* h, int idx);
     static double macs(const fe_handle* h);
 };
@@ -314,8 +311,8 @@ int BsrnnFamily::pack_weights(fe_handle* h, const Blob& S, std::vector<float>* o
     return FE_OK;
 }
 
-fe::BArgs BsrnnFamily::args(fe_handle* h, int B, int T) {
-    fe::BArgs a{};
+fe::BStreamArgs BsrnnFamily::args(fe_handle* h, int B, int T) {
+    fe::BStreamArgs a{};
     a.xp_scratch = h->skip_dev;
     a.wp = h->packed_dev;
     a.off = h->boff;
@@ -341,66 +338,47 @@ int BsrnnFamily::ensure_sb(fe_handle* h, int B) {
     return FE_OK;
 }
 
-int BsrnnFamily::launch(fe_handle* h, const fe::BArgs& a_in, void* stream) {
+// Every launch of the per-stream kernels, with the plan of the step made here.  The plain flavour (fe_step and the debug / profile steps,
+// fe_spec_step, fe_offline) may grow the stream-batched scratch and take the three-launch step from it, the stream-batched layers, the fused step or
+// the role-split profile.  The slotted and packet flavours (fe_step_pool, fe_step_pool_streams[_pinned]: always streaming steps) run the per-stream
+// kernels that choice leaves, in their own instantiations: never the stream-batched layers or the fused step (their tensors are laid out per call
+// tile), and nothing is allocated - the three-launch step runs where the scratch fe_state_init sized holds the call's streams, as it does for fe_step
+// after that call; without it the single-kernel walk.
+int BsrnnFamily::launch_step(fe_handle* h, fe::BStreamArgs& a, fe::StepFlavour flavour, void* stream) {
     hipError_t e = hipSuccess;
-    fe::BArgs a = a_in;
+    const bool plain = flavour == fe::STEP_PLAIN;
     a.ov_off = (h->step_kernel == FE_STEP_KERNEL_WAVES4 || !h->opt[OPT_BSRNN_ROLE_SPLIT]) ? 1 : 0;
-    // (fe_set_option("bsrnn_ov_profile", 1): fe_profile_step probes the role-split PART 1 of the three-launch step instead of the fused kernel's phases)
-    const bool ov_prof = h->opt[OPT_BSRNN_OV_PROFILE] != 0;
-    if (a.mode == fe::FE_MODE_STREAM && a.T == 1 && a.dbg == nullptr && (a.clk == nullptr || (ov_prof && h->cfg.channels == 16 && a.B <= h->max_wgs))) {
-        const int rc = ensure_sb(h, a.B);
-        if (rc != FE_OK) return rc;
-        if (h->sb_dev && a.B <= h->sb_streams) {
-            a.mlp_x = h->sb_dev;
-            a.mlp_sp = a.mlp_x + (size_t)a.B * 31 * h->cfg.channels;
-            a.mlp_pre = a.mlp_sp + (size_t)a.B * 2 * 257;
-            a.sb_y = a.mlp_pre + (size_t)a.B * 2 * 1028;
-            a.gsync = (h->opt[OPT_BSRNN_FUSED] && a.clk == nullptr && (a.B + 15) / 16 <= kSyncTiles) ? h->bsync_dev : nullptr;
-            // large batches: the LSTM layers batched over the streams on the matrix cores (sixteen streams per workgroup) - from the batch
-            // size where sixteen-stream workgroups fill the chip better than one stream per workgroup (FE_BSRNN_SB: that threshold; 0 = never)
-            // (default 2048; measured crossover on 256 CUs: ~1900 streams, profiles/r4c_bsrnn_stream_batched.txt.  num_channels = 64 (r6): a sixteen-stream tile takes 5.8 ms
-            //  whatever the batch and the per-stream kernel 2.3 us per stream - crossover at ~2700 streams: the threshold counts 11 / 8 there)
-            const int sb_opt = h->opt[OPT_BSRNN_SB_MIN];
-            const int sb_min = h->cfg.channels == 64 ? (int)((long long)sb_opt * 11 / 8) : sb_opt;
-            if (h->bimpl->launch_sb && sb_min > 0 && a.B >= sb_min) h->bimpl->launch_sb(a, h->sboff, h->packed_floats, h->max_wgs, (hipStream_t)stream, &e);
-            else
-            h->bimpl->launch_split(a, h->max_wgs, (hipStream_t)stream, &e);
-            return launch_rc(e);
+    bool split = a.mode == fe::FE_MODE_STREAM && a.T == 1;
+    if (split && plain) {
+        // (fe_set_option("bsrnn_ov_profile", 1): fe_profile_step probes the role-split PART 1 of the three-launch step instead of the fused kernel's phases)
+        const bool ov_prof = h->opt[OPT_BSRNN_OV_PROFILE] != 0;
+        split = a.dbg == nullptr && (a.clk == nullptr || (ov_prof && h->cfg.channels == 16 && a.B <= h->max_wgs));
+        if (split) {
+            const int rc = ensure_sb(h, a.B);
+            if (rc != FE_OK) return rc;
         }
     }
-    h->bimpl->launch(a, h->max_wgs, (hipStream_t)stream, &e);
-    return launch_rc(e);
-}
-
-// fe_step_pool: the per-stream kernels launch() picks for a.B streams, slotted.  Never the stream-batched layers or the fused step (their tensors
-// are laid out per call tile), and nothing is allocated: the three-launch step runs where the scratch fe_state_init sized holds the call's
-// streams, as it does for fe_step after that call; without it the single-kernel walk.
-// (a: the slotted argument block, or the packet step's, which extends it; returns whether the three-launch step runs)
-static bool bsrnn_slots_plan(const fe_handle* h, fe::BSlotArgs& a) {
-    a.ov_off = (h->step_kernel == FE_STEP_KERNEL_WAVES4 || !h->opt[OPT_BSRNN_ROLE_SPLIT]) ? 1 : 0;
-    const bool split = a.T == 1 && h->sb_dev && a.B <= h->sb_streams;
+    split = split && h->sb_dev && a.B <= h->sb_streams;
     if (split) {
         a.mlp_x = h->sb_dev;
         a.mlp_sp = a.mlp_x + (size_t)a.B * 31 * h->cfg.channels;
         a.mlp_pre = a.mlp_sp + (size_t)a.B * 2 * 257;
     }
-    return split;
-}
-
-int BsrnnFamily::launch_slots(fe_handle* h, const fe::BSlotArgs& a_in, void* stream) {
-    hipError_t e = hipSuccess;
-    fe::BSlotArgs a = a_in;
-    const bool split = bsrnn_slots_plan(h, a);
-    h->bimpl->launch_slots(a, split, h->max_wgs, (hipStream_t)stream, &e);
-    return launch_rc(e);
-}
-
-// fe_step_pool_streams[_pinned]: launch_slots' choice for a.B streams and a.T = T_max, with the packet instantiations
-int BsrnnFamily::launch_streams(fe_handle* h, const fe::BStreamArgs& a_in, void* stream) {
-    hipError_t e = hipSuccess;
-    fe::BStreamArgs a = a_in;
-    const bool split = bsrnn_slots_plan(h, a);
-    h->bimpl->launch_streams(a, split, h->max_wgs, (hipStream_t)stream, &e);
+    if (split && plain) {
+        a.sb_y = a.mlp_pre + (size_t)a.B * 2 * 1028;
+        a.gsync = (h->opt[OPT_BSRNN_FUSED] && a.clk == nullptr && (a.B + 15) / 16 <= kSyncTiles) ? h->bsync_dev : nullptr;
+        // large batches: the LSTM layers batched over the streams on the matrix cores (sixteen streams per workgroup) - from the batch
+        // size where sixteen-stream workgroups fill the chip better than one stream per workgroup (FE_BSRNN_SB: that threshold; 0 = never)
+        // (default 2048; measured crossover on 256 CUs: ~1900 streams, profiles/r4c_bsrnn_stream_batched.txt.  num_channels = 64 (r6): a sixteen-stream tile takes 5.8 ms
+        //  whatever the batch and the per-stream kernel 2.3 us per stream - crossover at ~2700 streams: the threshold counts 11 / 8 there)
+        const int sb_opt = h->opt[OPT_BSRNN_SB_MIN];
+        const int sb_min = h->cfg.channels == 64 ? (int)((long long)sb_opt * 11 / 8) : sb_opt;
+        if (h->bimpl->launch_sb && sb_min > 0 && a.B >= sb_min) {
+            h->bimpl->launch_sb(a, h->sboff, h->packed_floats, h->max_wgs, (hipStream_t)stream, &e);
+            return launch_rc(e);
+        }
+    }
+    h->bimpl->launch_step(a, flavour, split, h->max_wgs, (hipStream_t)stream, &e);
     return launch_rc(e);
 }
 

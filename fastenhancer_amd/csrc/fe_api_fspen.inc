@@ -7,7 +7,6 @@ const int kSdN[5] = {2, 3, 5, 10, 20};                    // SubbandDecoder outp
 // The family as fe_api.hip's shared baseline-family paths see it (visit_baseline: the stream and spec steps, offline, the buffer sizes, debug stages)
 struct FspenFamily {
     using Args = fe::FArgs;
-    using SlotArgs = fe::FSlotArgs;
     using StreamArgs = fe::FStreamArgs;
     static const fe::FImpl* impl(const fe_handle* h) { return h->fimpl; }
     static const char* shape_name(const fe_handle*) { return "fspen"; }
@@ -25,13 +24,11 @@ struct FspenFamily {
     static size_t ring_floats(const fe_handle*) { return 0; }
     static void set_ring(Args&, float*) {}
     static size_t xp_floats(const fe_handle*) { return 0; }
-    static Args args(fe_handle* h, int B, int T);
+    static StreamArgs args(fe_handle* h, int B, int T);
     static int create(const fe_config* cfg, fe_handle** out);
     static int pack_weights(fe_handle* h, const Blob& S, std::vector<float>* out);
     static int ensure_sb(fe_handle* h, int B);
-    static int launch(fe_handle* h, const Args& a, void* stream);
-    static int launch_slots(fe_handle* h, const SlotArgs& a, void* stream);
-    static int launch_streams(fe_handle* h, const StreamArgs& a, void* stream);
+    static int launch_step(fe_handle* h, StreamArgs& a, fe::StepFlavour flavour, void* stream);
     static const char* stage_name(const fe_handle*, int idx);
     static double macs(const fe_handle* h);
 };
@@ -316,8 +313,8 @@ int FspenFamily::pack_weights(fe_handle* h, const Blob& S, std::vector<float>* o
     return FE_OK;
 }
 
-fe::FArgs FspenFamily::args(fe_handle* h, int B, int T) {
-    fe::FArgs a{};
+fe::FStreamArgs FspenFamily::args(fe_handle* h, int B, int T) {
+    fe::FStreamArgs a{};
     a.wp = h->packed_dev;
     a.B = B;
     a.T = T;
@@ -333,11 +330,13 @@ int FspenFamily::ensure_sb(fe_handle* h, int B) {
     return ensure_sb_scratch(h, B, h->opt[OPT_FSPEN_SB_MIN], ((size_t)B + 16) * h->fimpl->split_floats_per_stream * sizeof(float));
 }
 
-int FspenFamily::launch(fe_handle* h, const fe::FArgs& a_in, void* stream) {
+// Every launch of the per-stream kernel.  The plain flavour may grow the stream-batched scratch and run the per-hop step of a large batch through
+// it; the slotted and packet flavours (fe_step_pool, fe_step_pool_streams[_pinned]) run the per-stream kernel in their own instantiation at every
+// batch size (the stream-batched middle's tensors are laid out per call tile) and allocate nothing.
+int FspenFamily::launch_step(fe_handle* h, fe::FStreamArgs& a, fe::StepFlavour flavour, void* stream) {
     hipError_t e = hipSuccess;
-    fe::FArgs a = a_in;
     const int sb_min = h->opt[OPT_FSPEN_SB_MIN];
-    if (a.mode == fe::FE_MODE_STREAM && a.T == 1 && a.dbg == nullptr && sb_min > 0 && a.B >= sb_min) {      // (fe_profile_step: the DPE kernel's counters only)
+    if (flavour == fe::STEP_PLAIN && a.mode == fe::FE_MODE_STREAM && a.T == 1 && a.dbg == nullptr && sb_min > 0 && a.B >= sb_min) {      // (fe_profile_step: the DPE kernel's counters only)
         const int rc = ensure_sb(h, a.B);
         if (rc != FE_OK) return rc;
         a.tok = h->sb_dev;
@@ -345,21 +344,7 @@ int FspenFamily::launch(fe_handle* h, const fe::FArgs& a_in, void* stream) {
         h->fimpl->launch_sb(a, h->max_wgs, (hipStream_t)stream, &e);
         return launch_rc(e);
     }
-    h->fimpl->launch(a, h->max_wgs, (hipStream_t)stream, &e);
-    return launch_rc(e);
-}
-
-// fe_step_pool: the per-stream kernel, slotted, at every batch size (the stream-batched middle's tensors are laid out per call tile)
-int FspenFamily::launch_slots(fe_handle* h, const fe::FSlotArgs& a, void* stream) {
-    hipError_t e = hipSuccess;
-    h->fimpl->launch_slots(a, h->max_wgs, (hipStream_t)stream, &e);
-    return launch_rc(e);
-}
-
-// fe_step_pool_streams[_pinned]: the same kernel in its packet instantiation
-int FspenFamily::launch_streams(fe_handle* h, const fe::FStreamArgs& a, void* stream) {
-    hipError_t e = hipSuccess;
-    h->fimpl->launch_streams(a, h->max_wgs, (hipStream_t)stream, &e);
+    h->fimpl->launch_step(a, flavour, h->max_wgs, (hipStream_t)stream, &e);
     return launch_rc(e);
 }
 

@@ -4,7 +4,6 @@
 // The family as fe_api.hip's shared baseline-family paths see it (visit_baseline: the stream and spec steps, offline, the buffer sizes, debug stages)
 struct LisennetFamily {
     using Args = fe::LArgs;
-    using SlotArgs = fe::LSlotArgs;
     using StreamArgs = fe::LStreamArgs;
     static const fe::LImpl* impl(const fe_handle* h) { return h->limpl; }
     static const char* shape_name(const fe_handle*) { return "lisennet"; }
@@ -30,13 +29,11 @@ struct LisennetFamily {
     static size_t ring_floats(const fe_handle* h) { return (size_t)(kMaxPipeFrames + 2) * h->limpl->cache_floats; }
     static void set_ring(Args& a, float* ring) { a.ring = ring; }
     static size_t xp_floats(const fe_handle*) { return 0; }
-    static Args args(fe_handle* h, int B, int T);
+    static StreamArgs args(fe_handle* h, int B, int T);
     static int create(const fe_config* cfg, fe_handle** out);
     static int pack_weights(fe_handle* h, const Blob& S, std::vector<float>* out);
     static int ensure_sb(fe_handle* h, int B);
-    static int launch(fe_handle* h, const Args& a, void* stream);
-    static int launch_slots(fe_handle* h, const SlotArgs& a, void* stream);
-    static int launch_streams(fe_handle* h, const StreamArgs& a, void* stream);
+    static int launch_step(fe_handle* h, StreamArgs& a, fe::StepFlavour flavour, void* stream);
     static const char* stage_name(const fe_handle*, int idx);
     static double macs(const fe_handle* h);
 };
@@ -418,8 +415,8 @@ int LisennetFamily::pack_weights(fe_handle* h, const Blob& S, std::vector<float>
     return FE_OK;
 }
 
-fe::LArgs LisennetFamily::args(fe_handle* h, int B, int T) {
-    fe::LArgs a{};
+fe::LStreamArgs LisennetFamily::args(fe_handle* h, int B, int T) {
+    fe::LStreamArgs a{};
     a.wp = h->packed_dev;
     a.B = B;
     a.T = T;
@@ -433,32 +430,20 @@ int LisennetFamily::ensure_sb(fe_handle* h, int B) {
     return ensure_sb_scratch(h, B, h->opt[OPT_LISENNET_SB_MIN], fe::LCarry::floats(B) * sizeof(float));
 }
 
-int LisennetFamily::launch(fe_handle* h, const fe::LArgs& a_in, void* stream) {
+// Every launch of the per-stream kernel.  The plain flavour may grow the stream-batched scratch and run the per-hop step of a large batch through
+// it; the slotted and packet flavours (fe_step_pool, fe_step_pool_streams[_pinned]) run the per-stream kernel in their own instantiation at every
+// batch size (the stream-batched middle's tensors are laid out per call tile) and allocate nothing.
+int LisennetFamily::launch_step(fe_handle* h, fe::LStreamArgs& a, fe::StepFlavour flavour, void* stream) {
     hipError_t e = hipSuccess;
-    fe::LArgs a = a_in;
     const int sb_min = h->opt[OPT_LISENNET_SB_MIN];
-    if (a.mode == fe::FE_MODE_STREAM && a.T == 1 && sb_min > 0 && a.B >= sb_min && h->limpl->launch_sb) {
+    if (flavour == fe::STEP_PLAIN && a.mode == fe::FE_MODE_STREAM && a.T == 1 && sb_min > 0 && a.B >= sb_min && h->limpl->launch_sb) {
         const int rc = ensure_sb(h, a.B);
         if (rc != FE_OK) return rc;
         a.carry = h->sb_dev;
         h->limpl->launch_sb(a, h->max_wgs, (hipStream_t)stream, &e);
         return launch_rc(e);
     }
-    h->limpl->launch(a, h->max_wgs, (hipStream_t)stream, &e);
-    return launch_rc(e);
-}
-
-// fe_step_pool: the per-stream kernel, slotted, at every batch size (the stream-batched middle's tensors are laid out per call tile)
-int LisennetFamily::launch_slots(fe_handle* h, const fe::LSlotArgs& a, void* stream) {
-    hipError_t e = hipSuccess;
-    h->limpl->launch_slots(a, h->max_wgs, (hipStream_t)stream, &e);
-    return launch_rc(e);
-}
-
-// fe_step_pool_streams[_pinned]: the same kernel in its packet instantiation
-int LisennetFamily::launch_streams(fe_handle* h, const fe::LStreamArgs& a, void* stream) {
-    hipError_t e = hipSuccess;
-    h->limpl->launch_streams(a, h->max_wgs, (hipStream_t)stream, &e);
+    h->limpl->launch_step(a, flavour, h->max_wgs, (hipStream_t)stream, &e);
     return launch_rc(e);
 }
 

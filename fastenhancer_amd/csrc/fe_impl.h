@@ -10,12 +10,6 @@
 
 namespace fe {
 
-// How a launch of the frame kernels was asked for = the instantiations that run it and the prefix of StreamFrameArgs they take as their argument block:
-// plain (fe_step, the debug / profile steps, fe_spec_step, fe_offline: FrameArgs), SLOT (fe_step_slots: SlotFrameArgs, a.slots / a.capacity), HIO
-// (fe_step_pinned / fe_step_slots_pinned: wav_in / wav_out are device views of page-locked host memory) or STRM (fe_step_streams[_pinned]: all of it -
-// a.desc, a.T = T_max; float32 or int16 audio in device or page-locked host memory, one set of kernels for the four)
-enum StepFlavour { STEP_PLAIN, STEP_SLOTS, STEP_SLOTS_PINNED, STEP_STREAMS };
-
 struct Impl {
     int C1, NL, C2, F2, KB, NFFT, HOP, KT, LOW, FR, TA, LN, BD;
     const tb::TbImpl* tb;   // time-batched engine (tb_kernels.hip.h) or nullptr
@@ -42,27 +36,8 @@ struct Impl {
     hipError_t (*launch_streams_pipe)(const StreamFrameArgs&, hipStream_t) = nullptr;
 };
 
-// What fe_last_step_kernel reports for the instantiation a launcher picked: the kernel's name, then in angle brackets and joined by ", " whichever
-// apply of "LOW=n", what it is (debug, per-hop, ...), "slots" or "streams" (the SLOT / STRM instantiations), "pinned" and "s16" - put together at
-// compile time, so that fe::note_kernel still gets a constant string.  HIO says where a slotted step's audio lives; for the STRM instantiations
-// that, the audio's format and a bank table (fe_step_streams_banked) are run-time facts of the call (a.pinned, a.format, a.bank), hence a name for
-// each of the eight: s[pinned + 2 * s16 + 4 * banks].
-struct KernelNames { char s[8][80] = {}; };
-constexpr KernelNames kernel_names(const char* kernel, int low, const char* what, const char* flavour) {
-    KernelNames n;
-    for (int v = 0; v < 8; ++v) {
-        const char* parts[] = {low == 2 ? "LOW=2" : low == 1 ? "LOW=1" : "", what, flavour, v & 1 ? "pinned" : "", v & 2 ? "s16" : "", v & 4 ? "banks" : ""};
-        int k = 0;
-        auto put = [&](const char* p) { while (*p) n.s[v][k++] = *p++; };
-        put(kernel);
-        bool open = false;
-        for (const char* p : parts)
-            if (*p) { put(open ? ", " : "<"); put(p); open = true; }
-        if (open) put(">");
-    }
-    return n;
-}
-constexpr bool same_text(const char* a, const char* b) { for (; *a == *b; ++a, ++b) if (!*a) return true; return false; }
+// The texts of the frame kernels (kernel_names, fe_launch.h).  HIO says where a slotted step's audio lives; for the STRM instantiations that, the
+// audio's format and a bank table are run-time facts of the call: s[pinned + 2 * s16 + 4 * banks].
 static_assert(same_text(kernel_names("fe_frame8_kernel", 0, "", "").s[0], "fe_frame8_kernel") &&
               same_text(kernel_names("fe_frame8_kernel", 0, "persistent", "slots").s[1], "fe_frame8_kernel<persistent, slots, pinned>") &&
               same_text(kernel_names("fe_frame_kernel", 2, "per-hop, persistent", "streams").s[3], "fe_frame_kernel<LOW=2, per-hop, persistent, streams, pinned, s16>") &&
@@ -191,10 +166,6 @@ Impl make_impl() {
         im.EP = S::EP;
         return im;
     } else {
-    // Kernels land in the code object in the order in which their launchers are first named.  Naming the plain and the time-pipelined launcher here,
-    // ahead of launch_step_impl (which names every flavour), keeps each shape's object as it was: tools/compare_device_code.sh compares line by line.
-    // (No run-time purpose: the line may go once that tool compares per symbol or the recorded comparison with the parent no longer matters.)
-    (void)&launch_impl<S>, (void)&launch_pipe_impl<S>;
     Impl im{S::C1, S::NL, S::C2, S::F2, S::KB, S::NFFT, S::HOP, S::KT, S::LOW, S::FRNN ? 1 : 0, S::LB, S::LN ? 1 : 0, 0, tbp, Lds<S>::BYTES, Lds<S>::OCC, Lds<S>::MANY_PERSIST, Wg8<S>::OK, S::NU, Pack<S>::umax(), Lds<S>::STAGED,
             Lds<S>::SKIPS_LDS ? (size_t)0 : (size_t)(S::NL + 1) * S::F1 * S::C1,
             DebugLayout<S>::total(), DebugLayout<S>::n_stages, &Pack<S>::v, &launch_step_impl<S>, &launch_pipe_impl<S>, &dbg_stage_impl<S>};

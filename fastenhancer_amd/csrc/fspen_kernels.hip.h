@@ -1249,7 +1249,9 @@ struct FImpl {
     size_t dbg_floats;
     int dbg_stages;
     size_t packed_floats;
-    void (*launch)(const FArgs&, int max_wgs, hipStream_t, hipError_t*);
+    // every launch of the per-stream kernel but the two below: the flavour's instantiation on the prefix of the block that is its argument
+    // block (plain: fe_step and the debug / profile steps, fe_spec_step, fe_offline; slotted: fe_step_pool; packet: fe_step_pool_streams[_pinned])
+    void (*launch_step)(const FStreamArgs&, StepFlavour, int max_wgs, hipStream_t, hipError_t*);
     void (*dbg_stage)(int, int*, int*, size_t*);
     void (*launch_pipe)(const FArgs&, hipStream_t, hipError_t*);       // time-pipelined offline launch (cooperative: B * pipe_p workgroups)
     int occ;                  // workgroups per CU
@@ -1257,71 +1259,56 @@ struct FImpl {
     // per-hop step of large batches: front -> DPE blocks batched over the streams (fspen_sb_kernels.hip.h) -> tail; a.tok / a.carry set
     void (*launch_sb)(const FArgs&, int max_wgs, hipStream_t, hipError_t*);
     size_t split_floats_per_stream;      // tok + carry
-    void (*launch_slots)(const FSlotArgs&, int max_wgs, hipStream_t, hipError_t*);      // fe_step_pool: flaunch_impl's launch with the slotted instantiation
-    void (*launch_streams)(const FStreamArgs&, int max_wgs, hipStream_t, hipError_t*);  // fe_step_pool_streams[_pinned]: launch_slots' launch with the packet instantiation
 };
+
+// workgroups per CU: LDS- and register-limited (the front, PART 1: its own LDS plan and register budget)
+constexpr int kFOccLds = (160 * 1024) / (FLds::TOTAL * 4), kFOcc = kFOccLds < FS_WPE ? kFOccLds : FS_WPE;
+constexpr int kFOccFrontLds = (160 * 1024) / (FLds::FRONT_TOTAL * 4), kFOccFront = kFOccFrontLds < FS_WPE_FRONT ? kFOccFrontLds : FS_WPE_FRONT;
+// more streams than resident workgroups: persistent workgroups walk b, b + grid, ...
+inline dim3 fgrid(int B, int max_wgs, int occ = kFOcc) { return dim3(B < max_wgs * occ ? B : max_wgs * occ); }
 
 template <class S>
 void flaunch_pipe_impl(const FArgs& a, hipStream_t st, hipError_t* err) {
-    FArgs args = a;
-    void* kargs[] = {&args};
     // (one instantiation: the mode is a run-time value there; a streaming chunk - fe_step_backlog - is named apart)
-    note_kernel(a.mode == FE_MODE_STREAM ? "fspen_frame_kernel<time-pipelined, streaming>" : "fspen_frame_kernel<time-pipelined>");
-    *err = hipLaunchCooperativeKernel(reinterpret_cast<const void*>(&fspen_frame_kernel<S, false, false, true>), dim3(a.B * a.pipe_p), dim3(kThreads), kargs, 0, st);
+    const char* name = a.mode == FE_MODE_STREAM ? "fspen_frame_kernel<time-pipelined, streaming>" : "fspen_frame_kernel<time-pipelined>";
+    *err = launch_coop<&fspen_frame_kernel<S, false, false, true>>(name, dim3(a.B * a.pipe_p), dim3(kThreads), 0, st, a);
+}
+
+constexpr KernelNames fframe_names(bool slot, bool strm) { return kernel_names("fspen_frame_kernel", 0, "", baseline_flavour(slot, strm)); }
+static_assert(same_text(fframe_names(false, false).s[0], "fspen_frame_kernel") && same_text(fframe_names(true, false).s[0], "fspen_frame_kernel<slots>") &&
+              same_text(fframe_names(true, true).s[3], "fspen_frame_kernel<slots, streams, pinned, s16>"),
+              "the texts fe_last_step_kernel has always reported");
+
+// SLOT (fe_step_pool): the slotted instantiation - streaming mode; no debug dumps or cycle probes.  STRM (fe_step_pool_streams[_pinned]): the packet one.
+template <class S, bool SLOT = false, bool STRM = false>
+void flaunch_impl(const typename FKernelArgs<SLOT, STRM>::type& a, int max_wgs, hipStream_t st, hipError_t* err) {
+    const dim3 grid = fgrid(a.B, max_wgs), block(kThreads);
+    if constexpr (!SLOT) {
+        if (a.dbg != nullptr) { *err = launch<&fspen_frame_kernel<S, false, true>>("fspen_frame_kernel<debug>", grid, block, 0, st, a); return; }
+        if (a.clk != nullptr) { *err = launch<&fspen_frame_kernel<S, true, false>>("fspen_frame_kernel<profile>", grid, block, 0, st, a); return; }
+    }
+    static constexpr KernelNames names = fframe_names(SLOT, STRM);
+    *err = launch<&fspen_frame_kernel<S, false, false, false, 0, SLOT, STRM>>(baseline_name<STRM>(names, a), grid, block, 0, st, a);
 }
 
 template <class S>
-void flaunch_impl(const FArgs& a, int max_wgs, hipStream_t st, hipError_t* err) {
-    constexpr int OCC_LDS = (160 * 1024) / (FLds::TOTAL * 4);      // workgroups per CU: LDS- and register-limited
-    constexpr int OCC = OCC_LDS < FS_WPE ? OCC_LDS : FS_WPE;
-    const int slots = max_wgs * OCC;
-    const int grid = a.B < slots ? a.B : slots;                    // more streams than slots: persistent workgroups walk b, b + grid, ...
-    note_kernel(a.dbg != nullptr ? "fspen_frame_kernel<debug>" : a.clk != nullptr ? "fspen_frame_kernel<profile>" : "fspen_frame_kernel");
-    if (a.dbg != nullptr) hipLaunchKernelGGL((fspen_frame_kernel<S, false, true>), dim3(grid), dim3(kThreads), 0, st, a);
-    else if (a.clk != nullptr) hipLaunchKernelGGL((fspen_frame_kernel<S, true, false>), dim3(grid), dim3(kThreads), 0, st, a);
-    else hipLaunchKernelGGL((fspen_frame_kernel<S, false, false>), dim3(grid), dim3(kThreads), 0, st, a);
-    *err = hipGetLastError();
-}
-
-template <class S>
-void flaunch_slots_impl(const FSlotArgs& a, int max_wgs, hipStream_t st, hipError_t* err) {
-    constexpr int OCC_LDS = (160 * 1024) / (FLds::TOTAL * 4);
-    constexpr int OCC = OCC_LDS < FS_WPE ? OCC_LDS : FS_WPE;
-    const int slots = max_wgs * OCC;
-    note_kernel("fspen_frame_kernel<slots>");
-    hipLaunchKernelGGL((fspen_frame_kernel<S, false, false, false, 0, true>), dim3(a.B < slots ? a.B : slots), dim3(kThreads), 0, st, a);
-    *err = hipGetLastError();
-}
-
-template <class S>
-void flaunch_streams_impl(const FStreamArgs& a, int max_wgs, hipStream_t st, hipError_t* err) {
-    constexpr int OCC_LDS = (160 * 1024) / (FLds::TOTAL * 4);
-    constexpr int OCC = OCC_LDS < FS_WPE ? OCC_LDS : FS_WPE;
-    const int slots = max_wgs * OCC;
-    // (where the audio lives and its format are run-time facts of the call: a name for each of the four)
-    static const char* const names[4] = {"fspen_frame_kernel<slots, streams>", "fspen_frame_kernel<slots, streams, pinned>",
-                                         "fspen_frame_kernel<slots, streams, s16>", "fspen_frame_kernel<slots, streams, pinned, s16>"};
-    note_kernel(names[(a.pinned != 0) + 2 * (a.format != 0)]);
-    hipLaunchKernelGGL((fspen_frame_kernel<S, false, false, false, 0, true, true>), dim3(a.B < slots ? a.B : slots), dim3(kThreads), 0, st, a);
-    *err = hipGetLastError();
+void flaunch_step_impl(const FStreamArgs& a, StepFlavour flavour, int max_wgs, hipStream_t st, hipError_t* err) {
+    switch (flavour) {       // (each instantiation's launcher binds the prefix of a that is its kernel's argument block)
+    case STEP_PLAIN: return flaunch_impl<S>(a, max_wgs, st, err);
+    case STEP_SLOTS: return flaunch_impl<S, true>(a, max_wgs, st, err);
+    case STEP_STREAMS: return flaunch_impl<S, true, true>(a, max_wgs, st, err);
+    default: *err = hipErrorInvalidValue;       // (STEP_SLOTS_PINNED: no entry point of this family asks for it)
+    }
 }
 
 template <class S>
 void flaunch_sb_impl(const FArgs& a, int max_wgs, hipStream_t st, hipError_t* err) {
-    constexpr int OCC_LDS = (160 * 1024) / (FLds::TOTAL * 4);
-    constexpr int OCC = OCC_LDS < FS_WPE ? OCC_LDS : FS_WPE;
-    const int slots = max_wgs * OCC;
-    const int grid = a.B < slots ? a.B : slots;
-    constexpr int OCC_F_LDS = (160 * 1024) / (FLds::FRONT_TOTAL * 4);
-    const int slots_f = max_wgs * (OCC_F_LDS < FS_WPE_FRONT ? OCC_F_LDS : FS_WPE_FRONT);
-    note_kernel("fspen_frame_kernel<PART 1>");
-    hipLaunchKernelGGL((fspen_frame_kernel<S, false, false, false, 1>), dim3(a.B < slots_f ? a.B : slots_f), dim3(kThreads), 0, st, a);
+    *err = launch<&fspen_frame_kernel<S, false, false, false, 1>>("fspen_frame_kernel<PART 1>", fgrid(a.B, max_wgs, kFOccFront), dim3(kThreads), 0, st, a);
+    if (*err != hipSuccess) return;
     FSbArgs sa{a.wp, a.carry, a.tok, a.carry + (size_t)a.B * FCarry::FLOATS, a.gru, a.B, a.clk};
     *err = fspen_sb_launch<S>(sa, st);
     if (*err != hipSuccess) return;
-    note_kernel("fspen_frame_kernel<PART 2>");
-    hipLaunchKernelGGL((fspen_frame_kernel<S, false, false, false, 2>), dim3(grid), dim3(kThreads), 0, st, a);
-    *err = hipGetLastError();
+    *err = launch<&fspen_frame_kernel<S, false, false, false, 2>>("fspen_frame_kernel<PART 2>", fgrid(a.B, max_wgs), dim3(kThreads), 0, st, a);
 }
 
 inline void fdbg_stage_impl(int s, int* rows, int* cols, size_t* off) {
@@ -1332,10 +1319,8 @@ inline void fdbg_stage_impl(int s, int* rows, int* cols, size_t* off) {
 
 template <class S>
 FImpl make_fimpl() {
-    constexpr int OCC_LDS = (160 * 1024) / (FLds::TOTAL * 4);
-    return FImpl{S::HOP, (size_t)FLds::TOTAL * 4, FDebugLayout::total(), FDebugLayout::n_stages, (size_t)FPk::TOTAL, &flaunch_impl<S>, &fdbg_stage_impl,
-                 &flaunch_pipe_impl<S>, OCC_LDS < FS_WPE ? OCC_LDS : FS_WPE, S::NB, &flaunch_sb_impl<S>, (size_t)2048 + FCarry::FLOATS + 1024, &flaunch_slots_impl<S>,
-                 &flaunch_streams_impl<S>};
+    return FImpl{S::HOP, (size_t)FLds::TOTAL * 4, FDebugLayout::total(), FDebugLayout::n_stages, (size_t)FPk::TOTAL, &flaunch_step_impl<S>, &fdbg_stage_impl,
+                 &flaunch_pipe_impl<S>, kFOcc, S::NB, &flaunch_sb_impl<S>, (size_t)2048 + FCarry::FLOATS + 1024};
 }
 
 }  // namespace fe

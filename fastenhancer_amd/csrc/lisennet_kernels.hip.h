@@ -993,81 +993,70 @@ struct LImpl {
     int dbg_stages;
     size_t packed_floats;
     size_t cache_floats;      // model caches per stream
-    void (*launch)(const LArgs&, int max_wgs, hipStream_t, hipError_t*);
+    // every launch of the per-stream kernel but the two below: the flavour's instantiation on the prefix of the block that is its argument
+    // block (plain: fe_step and the debug / profile steps, fe_spec_step, fe_offline; slotted: fe_step_pool; packet: fe_step_pool_streams[_pinned])
+    void (*launch_step)(const LStreamArgs&, StepFlavour, int max_wgs, hipStream_t, hipError_t*);
     void (*dbg_stage)(int, int*, int*, size_t*);
     void (*launch_pipe)(const LArgs&, hipStream_t, hipError_t*);       // time-pipelined offline launch (cooperative: B * pipe_p workgroups)
     int occ;                  // workgroups per CU
     int nsite;                // caches handed from frame to frame (counters per stream)
     void (*launch_sb)(const LArgs&, int max_wgs, hipStream_t, hipError_t*);      // r6: the per-hop step of a large batch in three launches, the middle batched over the streams
-    void (*launch_slots)(const LSlotArgs&, int max_wgs, hipStream_t, hipError_t*);      // fe_step_pool: llaunch_impl's launch with the slotted instantiation
-    void (*launch_streams)(const LStreamArgs&, int max_wgs, hipStream_t, hipError_t*);  // fe_step_pool_streams[_pinned]: launch_slots' launch with the packet instantiation
 };
+
+// workgroups per CU: LDS-limited, and two by the registers (256 VGPRs per wave); the parts of the three-launch step run eight (16.5 / 14.4 KB
+// of LDS, <= 64 VGPRs)
+constexpr int kLOccLds = (160 * 1024) / (LLds::TOTAL * 4), kLOcc = kLOccLds < 2 ? kLOccLds : 2, kLOccPart = 8;
+static_assert(LLdsT<1>::TOTAL * 4 * kLOccPart <= 160 * 1024 && LLdsT<2>::TOTAL * 4 * kLOccPart <= 160 * 1024, "LDS of the parts");
+// more streams than resident workgroups: persistent workgroups walk b, b + grid, ...
+inline dim3 lgrid(int B, int max_wgs, int occ = kLOcc) { return dim3(B < max_wgs * occ ? B : max_wgs * occ); }
 
 template <class S>
 void llaunch_pipe_impl(const LArgs& a, hipStream_t st, hipError_t* err) {
-    LArgs args = a;
-    void* kargs[] = {&args};
-    note_kernel("lisennet_frame_kernel<time-pipelined>");
-    *err = hipLaunchCooperativeKernel(reinterpret_cast<const void*>(&lisennet_frame_kernel<S, false, false, true>), dim3(a.B * a.pipe_p), dim3(kThreads), kargs, 0, st);
+    *err = launch_coop<&lisennet_frame_kernel<S, false, false, true>>("lisennet_frame_kernel<time-pipelined>", dim3(a.B * a.pipe_p), dim3(kThreads), 0, st, a);
+}
+
+constexpr KernelNames lframe_names(bool slot, bool strm) { return kernel_names("lisennet_frame_kernel", 0, "", baseline_flavour(slot, strm)); }
+static_assert(same_text(lframe_names(false, false).s[0], "lisennet_frame_kernel") && same_text(lframe_names(true, false).s[0], "lisennet_frame_kernel<slots>") &&
+              same_text(lframe_names(true, true).s[3], "lisennet_frame_kernel<slots, streams, pinned, s16>"),
+              "the texts fe_last_step_kernel has always reported");
+
+// SLOT (fe_step_pool): the slotted instantiation - streaming mode; no debug dumps or cycle probes.  STRM (fe_step_pool_streams[_pinned]): the packet one.
+template <class S, bool SLOT = false, bool STRM = false>
+void llaunch_impl(const typename LKernelArgs<SLOT, STRM>::type& a, int max_wgs, hipStream_t st, hipError_t* err) {
+    const dim3 grid = lgrid(a.B, max_wgs), block(kThreads);
+    if constexpr (!SLOT) {
+        if (a.dbg != nullptr) { *err = launch<&lisennet_frame_kernel<S, false, true>>("lisennet_frame_kernel<debug>", grid, block, 0, st, a); return; }
+        if (a.clk != nullptr) { *err = launch<&lisennet_frame_kernel<S, true, false>>("lisennet_frame_kernel<profile>", grid, block, 0, st, a); return; }
+    }
+    static constexpr KernelNames names = lframe_names(SLOT, STRM);
+    *err = launch<&lisennet_frame_kernel<S, false, false, false, 0, SLOT, STRM>>(baseline_name<STRM>(names, a), grid, block, 0, st, a);
 }
 
 template <class S>
-void llaunch_impl(const LArgs& a, int max_wgs, hipStream_t st, hipError_t* err) {
-    constexpr int OCC_LDS = (160 * 1024) / (LLds::TOTAL * 4);
-    constexpr int OCC = OCC_LDS < 2 ? OCC_LDS : 2;                 // (256 VGPRs per wave: two workgroups per CU)
-    const int slots = max_wgs * OCC;
-    const int grid = a.B < slots ? a.B : slots;
-    note_kernel(a.dbg != nullptr ? "lisennet_frame_kernel<debug>" : a.clk != nullptr ? "lisennet_frame_kernel<profile>" : "lisennet_frame_kernel");
-    if (a.dbg != nullptr) hipLaunchKernelGGL((lisennet_frame_kernel<S, false, true>), dim3(grid), dim3(kThreads), 0, st, a);
-    else if (a.clk != nullptr) hipLaunchKernelGGL((lisennet_frame_kernel<S, true, false>), dim3(grid), dim3(kThreads), 0, st, a);
-    else hipLaunchKernelGGL((lisennet_frame_kernel<S, false, false>), dim3(grid), dim3(kThreads), 0, st, a);
-    *err = hipGetLastError();
-}
-
-template <class S>
-void llaunch_slots_impl(const LSlotArgs& a, int max_wgs, hipStream_t st, hipError_t* err) {
-    constexpr int OCC_LDS = (160 * 1024) / (LLds::TOTAL * 4);
-    constexpr int OCC = OCC_LDS < 2 ? OCC_LDS : 2;
-    const int slots = max_wgs * OCC;
-    note_kernel("lisennet_frame_kernel<slots>");
-    hipLaunchKernelGGL((lisennet_frame_kernel<S, false, false, false, 0, true>), dim3(a.B < slots ? a.B : slots), dim3(kThreads), 0, st, a);
-    *err = hipGetLastError();
-}
-
-template <class S>
-void llaunch_streams_impl(const LStreamArgs& a, int max_wgs, hipStream_t st, hipError_t* err) {
-    constexpr int OCC_LDS = (160 * 1024) / (LLds::TOTAL * 4);
-    constexpr int OCC = OCC_LDS < 2 ? OCC_LDS : 2;
-    const int slots = max_wgs * OCC;
-    // (where the audio lives and its format are run-time facts of the call: a name for each of the four)
-    static const char* const names[4] = {"lisennet_frame_kernel<slots, streams>", "lisennet_frame_kernel<slots, streams, pinned>",
-                                         "lisennet_frame_kernel<slots, streams, s16>", "lisennet_frame_kernel<slots, streams, pinned, s16>"};
-    note_kernel(names[(a.pinned != 0) + 2 * (a.format != 0)]);
-    hipLaunchKernelGGL((lisennet_frame_kernel<S, false, false, false, 0, true, true>), dim3(a.B < slots ? a.B : slots), dim3(kThreads), 0, st, a);
-    *err = hipGetLastError();
+void llaunch_step_impl(const LStreamArgs& a, StepFlavour flavour, int max_wgs, hipStream_t st, hipError_t* err) {
+    switch (flavour) {       // (each instantiation's launcher binds the prefix of a that is its kernel's argument block)
+    case STEP_PLAIN: return llaunch_impl<S>(a, max_wgs, st, err);
+    case STEP_SLOTS: return llaunch_impl<S, true>(a, max_wgs, st, err);
+    case STEP_STREAMS: return llaunch_impl<S, true, true>(a, max_wgs, st, err);
+    default: *err = hipErrorInvalidValue;       // (STEP_SLOTS_PINNED: no entry point of this family asks for it)
+    }
 }
 
 // the per-hop step of a LARGE batch: front per stream (PART 1), conv_3 .. up3 for sixteen streams per workgroup on the matrix cores
 // (lisennet_sb_kernel), tail per stream (PART 2).  fe_debug_step: the same three launches with per-stage dumps; fe_profile_step: the middle's counters.
 template <class S>
 void llaunch_sb_impl(const LArgs& a, int max_wgs, hipStream_t st, hipError_t* err) {
-    constexpr int OCC1 = 8, OCC2 = 8;                              // (16.5 / 14.4 KB of LDS, <= 64 VGPRs: the parts run eight workgroups per CU)
-    static_assert(LLdsT<1>::TOTAL * 4 * OCC1 <= 160 * 1024 && LLdsT<2>::TOTAL * 4 * OCC2 <= 160 * 1024, "LDS of the parts");
-    const int grid = a.B < max_wgs * OCC1 ? a.B : max_wgs * OCC1;          // (one workgroup per stream instead of persistent ones: measured neutral, 328 / 334 us at 4096 streams)
-    const int grid2 = a.B < max_wgs * OCC2 ? a.B : max_wgs * OCC2;
-    note_kernel(a.dbg != nullptr ? "lisennet_frame_kernel<PART 1, debug>" : "lisennet_frame_kernel<PART 1>");
-    if (a.dbg != nullptr) hipLaunchKernelGGL((lisennet_frame_kernel<S, false, true, false, 1>), dim3(grid), dim3(kThreads), 0, st, a);
-    else hipLaunchKernelGGL((lisennet_frame_kernel<S, false, false, false, 1>), dim3(grid), dim3(kThreads), 0, st, a);
-    *err = hipGetLastError();
+    // (one workgroup per stream instead of persistent ones: measured neutral, 328 / 334 us at 4096 streams)
+    const dim3 grid = lgrid(a.B, max_wgs, kLOccPart), block(kThreads);
+    if (a.dbg != nullptr) *err = launch<&lisennet_frame_kernel<S, false, true, false, 1>>("lisennet_frame_kernel<PART 1, debug>", grid, block, 0, st, a);
+    else *err = launch<&lisennet_frame_kernel<S, false, false, false, 1>>("lisennet_frame_kernel<PART 1>", grid, block, 0, st, a);
     if (*err != hipSuccess) return;
     LSbArgs sa{};
     sa.wp = a.wp; sa.wp_floats = LPk::TOTAL + LSbPk::TOTAL; sa.carry = a.carry; sa.cache = a.cache; sa.dbg = a.dbg; sa.dbg_stride = a.dbg_stride; sa.B = a.B; sa.clk = a.clk;
     *err = lisennet_sb_launch<S>(sa, st);
     if (*err != hipSuccess) return;
-    note_kernel(a.dbg != nullptr ? "lisennet_frame_kernel<PART 2, debug>" : "lisennet_frame_kernel<PART 2>");
-    if (a.dbg != nullptr) hipLaunchKernelGGL((lisennet_frame_kernel<S, false, true, false, 2>), dim3(grid2), dim3(kThreads), 0, st, a);
-    else hipLaunchKernelGGL((lisennet_frame_kernel<S, false, false, false, 2>), dim3(grid2), dim3(kThreads), 0, st, a);
-    *err = hipGetLastError();
+    if (a.dbg != nullptr) *err = launch<&lisennet_frame_kernel<S, false, true, false, 2>>("lisennet_frame_kernel<PART 2, debug>", grid, block, 0, st, a);
+    else *err = launch<&lisennet_frame_kernel<S, false, false, false, 2>>("lisennet_frame_kernel<PART 2>", grid, block, 0, st, a);
 }
 
 inline void ldbg_stage_impl(int s, int* rows, int* cols, size_t* off) {
@@ -1078,10 +1067,13 @@ inline void ldbg_stage_impl(int s, int* rows, int* cols, size_t* off) {
 
 template <class S>
 LImpl make_limpl() {
-    constexpr int OCC_LDS = (160 * 1024) / (LLds::TOTAL * 4);
+    // Kernels land in the code object in the order in which their launchers are first named, and lisennet_sb_kernel reaches its constant tables
+    // PC-relative: its instructions carry the size of the code that follows it.  Naming the plain, the time-pipelined and the three-launch
+    // launcher ahead of llaunch_step_impl (whose slotted and packet instantiations then come last, as they always have) keeps that kernel's
+    // code what the recorded comparisons with earlier builds have (profiles/baseline_launch_device_code.txt).  No run-time purpose.
+    (void)&llaunch_impl<S>, (void)&llaunch_pipe_impl<S>, (void)&llaunch_sb_impl<S>;
     return LImpl{S::HOP, (size_t)LLds::TOTAL * 4, LDebugLayout::total(), LDebugLayout::n_stages, (size_t)LPk::TOTAL + LSbPk::TOTAL, (size_t)S::CACHE_FLOATS,
-                 &llaunch_impl<S>, &ldbg_stage_impl, &llaunch_pipe_impl<S>, OCC_LDS < 2 ? OCC_LDS : 2, 5 + 2 * S::NB, &llaunch_sb_impl<S>, &llaunch_slots_impl<S>,
-                 &llaunch_streams_impl<S>};
+                 &llaunch_step_impl<S>, &ldbg_stage_impl, &llaunch_pipe_impl<S>, kLOcc, 5 + 2 * S::NB, &llaunch_sb_impl<S>};
 }
 
 }  // namespace fe
