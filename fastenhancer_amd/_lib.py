@@ -72,6 +72,10 @@ SYMBOLS = {
     "fe_step_streams_ctl": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "fe_step_streams_ctl_pinned": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p,
                                            c_void_p]),
+    "fe_step_pool_streams_ctl": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p,
+                                         c_void_p]),
+    "fe_step_pool_streams_ctl_pinned": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p,
+                                                c_void_p, c_void_p]),
     "fe_set_weight_banks": (c_int, [c_void_p, c_int, c_void_p]),
     "fe_weight_banks": (c_int, [c_void_p]),
     "fe_load_weights_bank": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p]),

@@ -366,6 +366,8 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
     int oz = 0;
     asm volatile("" : "+v"(oz));
     const int tidv = tid + oz;
+    StreamCtl<STRM> ctl;                             // (STRM, fe_step_pool_streams_ctl) this stream's limit and the meters' partials of this wave
+    if constexpr (STRM && PART != 1) { if (a.min_gain != nullptr) ctl.m_min = stream_mask_floor(a.min_gain[sb], a.compression); }
     float* cst = a.cache_stft + (size_t)sb * OVL;
     float* cis = a.cache_istft + (size_t)sb * OVL;
     float* dbg = DBG ? a.dbg + (size_t)b * a.dbg_stride : nullptr;
@@ -441,6 +443,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
             if constexpr (!PIPE) {
             if (mode == FE_MODE_STREAM) {
                 for (int m = tid; m < OVL; m += kThreads) cst[m] = fb[m + H].x;
+                if constexpr (STRM) { if (a.levels != nullptr) levels_row(ctl.lv.in_ss, ctl.lv.in_pk, &fb[OVL].x, 2, H, tid); }     // (the hop as loaded)
                 __syncthreads();
             }
             }
@@ -1038,6 +1041,44 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
                     fa[N - f] = make_float2(yr, -yi);
                 }
             }
+            // fe_step_pool_streams_ctl, a limited stream (wave-uniform): its bins again, with the floor before the un-compress, over what the loop
+            // above left - the same thread writes the same places.  A second pass, as in fe_frame_kernel: with the floor inside the loop above
+            // the un-compress of an unlimited stream was contracted differently, and its bits were no longer the slotted kernel's.
+            if constexpr (STRM) {
+                if (ctl.m_min > 0.0f) {
+#pragma unroll
+                    for (int q = 0; q < FPT; ++q) {
+                        const int f = tid + q * kThreads;
+                        if (f >= kBins) break;
+                        const int ra = bra[q], rg = ra + brg[q];
+                        float mr[4];
+#pragma unroll
+                        for (int kind = 0; kind < 2; ++kind)
+#pragma unroll
+                            for (int ri = 0; ri < 2; ++ri)
+                                mr[kind * 2 + ri] = PRE[kind * kMlpRows + ra + ri] * sigmoid_f(PRE[kind * kMlpRows + rg + ri]);
+                        const float xr = sp[2 * f], xi = sp[2 * f + 1];
+                        float yr = xr * mr[0] - xi * mr[1] + mr[2];
+                        float yi = xr * mr[1] + xi * mr[0] + mr[3];
+                        bin_floor(yr, yi, xr, xi, ctl.m_min);
+                        const float g = pow_f(sqrtf(yr * yr + yi * yi), 1.0f / a.compression - 1.0f);
+                        yr *= g;
+                        yi *= g;
+                        if constexpr (MIDFT) {
+                            float* Ys = reinterpret_cast<float*>(fa);
+                            if (f < N / 2) { Ys[f] = yr; Ys[N / 2 + f] = yi; }
+                            else Ys[N] = yr;
+                        } else if (f == 0) {
+                            fa[0] = make_float2(yr, 0.0f);
+                        } else if (f == N / 2) {
+                            fa[N / 2] = make_float2(yr, 0.0f);
+                        } else {
+                            fa[f] = make_float2(yr, yi);
+                            fa[N - f] = make_float2(yr, -yi);
+                        }
+                    }
+                }
+            }
         }
         __syncthreads();
 
@@ -1071,6 +1112,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
                     else if (n < N) cis[n - H] = vo[q];
                 }
                 __syncthreads();
+                if (a.levels != nullptr) levels_row(ctl.lv.out_ss, ctl.lv.out_pk, xo, 1, H, tid);
                 stream_store_row(a.wav_out, a.format, sv.out_off + (long long)t * H, xo, H, tid, kThreads);
                 __syncthreads();
             } else {
@@ -1100,6 +1142,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
             }
             __syncthreads();
             if constexpr (STRM) {
+                if (a.levels != nullptr) levels_row(ctl.lv.out_ss, ctl.lv.out_pk, xo, 1, H, tid);
                 stream_store_row(a.wav_out, a.format, sv.out_off + (long long)t * H, xo, H, tid, kThreads);
             } else
             if (mode == FE_MODE_STREAM) {
@@ -1129,6 +1172,20 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
         }
         }      // (PART != 1)
         BE_CLK(11);
+    }
+    if constexpr (STRM) {
+        // the stream's level row: the waves' partials through the (idle) transform buffer, wave 0 first.  One 16-byte store where one kernel walks
+        // the frames; in the three-launch step PART 1 stores the input half, PART 2 the output half
+        if (a.levels != nullptr) {
+            float* red = reinterpret_cast<float*>(fa);
+            levels_put(red, ctl.lv, wave, lane);
+            __syncthreads();
+            if (tid == 0) {
+                if constexpr (PART == 0) levels_store<kWaves>(a.levels + sb, red);
+                else levels_store_half<kWaves, PART - 1>(a.levels + sb, red);
+            }
+            __syncthreads();
+        }
     }
     if constexpr (PIPE) break;
     b += gridDim.x;

@@ -295,7 +295,25 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
         tw[tid] = twv;
 #pragma unroll
         for (int q = 0; q < NPT; ++q) { const int n = tid + q * kThreads; xw[n] = fv[q] * fw[q]; }
+        if constexpr (STRM) {
+            // fe_step_pool_streams_ctl: this launch reads the audio, so it meters the hop - the waves' partials through the head of sp (not written
+            // before the transform's own barrier), combined by thread 0 behind the barrier below into the input half of the stream's level row
+            if (a.levels != nullptr) {
+                LevelAcc lv;
+                float ss = 0.0f, pk = 0.0f;
+#pragma unroll
+                for (int q = 0; q < NPT; ++q) {
+                    const float x = tid + q * kThreads >= OVL ? fv[q] : 0.0f;
+                    ss += x * x;
+                    pk = fmaxf(pk, fabsf(x));
+                }
+                lv.in_ss = wave_sum(0.0f, ss);
+                lv.in_pk = wave_max(0.0f, pk);
+                levels_put(sp, lv, wave, lane);
+            }
+        }
         __syncthreads();                           // (every read of the old cache has landed)
+        if constexpr (STRM) { if (a.levels != nullptr && tid == 0) levels_store_half<kWaves, 0>(a.levels + sb, sp); }
         if (wave == 0) OV_CLK(12);
 #pragma unroll
         for (int q = 0; q < NPT; ++q) { const int n = tid + q * kThreads; if (n >= H) cst[n - H] = fv[q]; }      // cache' = frame[H:]

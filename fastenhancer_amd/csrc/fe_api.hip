@@ -1517,22 +1517,30 @@ int fe_step_streams(fe_handle* h, const void* wav_in_dev, size_t in_count, float
 // fe_step_pool is to fe_step_slots.  FastEnhancer's handles take step_streams' path as it stands, under this entry point's name (the noncausal
 // model its refusal, which is fe_step's); a baseline family runs the launches fe_step_pool(n, T = T_max) picks, in their packet instantiations,
 // with step_streams' checks in step_streams' order.  Nothing is allocated.
+// min_gain / levels (fe_step_pool_streams_ctl[_pinned]; null from fe_step_pool_streams[_pinned]): the two slot-indexed tables, looked up as
+// step_streams looks them up (table_view) and handed to the same launches - the packet instantiations apply them behind null tests.
 static int step_pool_streams(fe_handle* h, const char* fn, bool pinned, const void* wav_in, size_t in_count, float* state_dev, int capacity,
-                             const fe_stream_desc* desc_dev, void* wav_out, size_t out_count, int n, int T_max, int format, void* stream) {
+                             const fe_stream_desc* desc_dev, void* wav_out, size_t out_count, int n, int T_max, int format, void* stream,
+                             const float* min_gain = nullptr, fe_stream_levels* levels = nullptr) {
     if (!h) return fail(FE_ERR_INVALID_ARG, "null handle");
     if (h->cfg.arch == FE_ARCH_FASTENHANCER)
-        return step_streams(h, fn, pinned, wav_in, in_count, state_dev, capacity, desc_dev, wav_out, out_count, n, T_max, format, stream);
-    int rc = check_streams_args(fn, wav_in, in_count, state_dev, capacity, desc_dev, wav_out, out_count, n, T_max, format, nullptr);
+        return step_streams(h, fn, pinned, wav_in, in_count, state_dev, capacity, desc_dev, wav_out, out_count, n, T_max, format, stream, min_gain, levels);
+    int rc = check_streams_args(fn, wav_in, in_count, state_dev, capacity, desc_dev, wav_out, out_count, n, T_max, format, levels);
     if (rc == FE_OK) rc = check_ready(h);
     if (rc != FE_OK) return rc;
     KernelLogScope klog_(h);
     const void* in = nullptr;
     const void* out = nullptr;
     rc = streams_audio(fn, pinned, format, wav_in, in_count, wav_out, out_count, &in, &out);
+    const void* gains = nullptr;
+    const void* rows = nullptr;
+    if (rc == FE_OK) rc = table_view(min_gain, (size_t)capacity * sizeof(float), fn, "min_gain", &gains);
+    if (rc == FE_OK) rc = table_view(levels, (size_t)capacity * sizeof(fe_stream_levels), fn, "levels", &rows);
     if (rc != FE_OK) return rc;
     BaselineStepOwn own;
     own.capacity = capacity;
-    own.io = fe::StreamIoArgs{reinterpret_cast<const fe::StreamDesc*>(desc_dev), in_count, out_count, format, pinned ? 1 : 0};
+    own.io = fe::StreamIoArgs{reinterpret_cast<const fe::StreamDesc*>(desc_dev), in_count, out_count, format, pinned ? 1 : 0,
+                              static_cast<const float*>(gains), static_cast<fe::StreamLevels*>(const_cast<void*>(rows))};
     // (the audio is typed by the format in the kernel)
     return launch_baseline_step(h, fe::STEP_STREAMS, own, static_cast<const float*>(in), 0, state_dev, const_cast<float*>(static_cast<const float*>(out)), 0, n,
                                 T_max, stream);
@@ -1547,6 +1555,19 @@ int fe_step_pool_streams_pinned(fe_handle* h, const void* wav_in_host, size_t in
                                 void* wav_out_host, size_t out_count, int n, int T_max, int format, void* stream) {
     return step_pool_streams(h, "fe_step_pool_streams_pinned", true, wav_in_host, in_count, state_dev, capacity, desc_dev, wav_out_host, out_count, n, T_max, format,
                              stream);
+}
+
+int fe_step_pool_streams_ctl(fe_handle* h, const void* wav_in_dev, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,
+                             void* wav_out_dev, size_t out_count, int n, int T_max, int format, const float* min_gain, fe_stream_levels* levels, void* stream) {
+    return step_pool_streams(h, "fe_step_pool_streams_ctl", false, wav_in_dev, in_count, state_dev, capacity, desc_dev, wav_out_dev, out_count, n, T_max, format,
+                             stream, min_gain, levels);
+}
+
+int fe_step_pool_streams_ctl_pinned(fe_handle* h, const void* wav_in_host, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,
+                                    void* wav_out_host, size_t out_count, int n, int T_max, int format, const float* min_gain, fe_stream_levels* levels,
+                                    void* stream) {
+    return step_pool_streams(h, "fe_step_pool_streams_ctl_pinned", true, wav_in_host, in_count, state_dev, capacity, desc_dev, wav_out_host, out_count, n, T_max,
+                             format, stream, min_gain, levels);
 }
 
 int fe_step_streams_pinned(fe_handle* h, const void* wav_in_host, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,

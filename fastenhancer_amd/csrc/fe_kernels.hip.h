@@ -464,14 +464,18 @@ __device__ __forceinline__ void stream_zero_row(void* base, int format, long lon
     for (int i = tid; i < n; i += nth) __builtin_nontemporal_store((short)0, out + i);
 }
 // The packet step of the other families' per-stream kernels (fe_step_pool_streams; the STRM instantiations in bsrnn_, fspen_ and
-// lisennet_kernels.hip.h): what StreamFrameArgs adds to SlotFrameArgs, less the per-stream controls and the weight banks, which stay
-// FastEnhancer's.  A family's packet argument block is its slotted one followed by these fields (struct XStreamArgs : XSlotArgs, StreamIoArgs);
-// a.slots and the strides are unused there, and a.T is the cap on hops.
+// lisennet_kernels.hip.h): what StreamFrameArgs adds to SlotFrameArgs, less the weight banks, which stay FastEnhancer's.  A family's packet
+// argument block is its slotted one followed by these fields (struct XStreamArgs : XSlotArgs, StreamIoArgs); a.slots and the strides are unused
+// there, and a.T is the cap on hops.
 struct StreamIoArgs {
     const StreamDesc* desc;   // [B] device memory, read when the kernel runs
     size_t in_count, out_count;   // elements of wav_in / wav_out: no access outside [0, count)
     int format;               // 0 = float32, 1 = int16 PCM (FE_AUDIO_*)
     int pinned;               // host side only (the kernel's name): the audio is page-locked host memory
+    // fe_step_pool_streams_ctl[_pinned]; either may be null (both null: fe_step_pool_streams).  Slot-indexed, [capacity], read / written when the
+    // kernels run.  The limit here is on the output bin against the input bin (bin_floor below): these families' outputs are not a mask times the input.
+    const float* min_gain;    // suppression limit: the least net amplitude gain of a bin, linear, clamped to [0, 1]; 0 / NaN = off
+    StreamLevels* levels;     // one 16-byte row per stream that advanced (16-byte aligned)
 };
 // stream_view for such a block: the same clamp and the same bounds check, made by the one definition above (the StreamFrameArgs built
 // here is five scalars in registers)
@@ -918,6 +922,40 @@ __device__ __forceinline__ void levels_store(StreamLevels* row, const float* red
         r[2] += red[4 * w + 2]; r[3] = fmaxf(r[3], red[4 * w + 3]);
     }
     *reinterpret_cast<f32x4*>(row) = r;
+}
+// ---- fe_step_pool_streams_ctl (the STRM instantiations of bsrnn_, fspen_ and lisennet_kernels.hip.h).  Their outputs are not a mask times the
+// input (BSRNN adds a residual, FSPEN combines two masks), so the limit is on the output bin Y against the input bin X, both compressed, right
+// before the un-compress: Y' = Y max(1, m |X| / |Y|) with m = min_gain^c (stream_mask_floor), and m X - the input's phase - where |Y|^2 is below
+// the normal range (v_rsq_f32 has no answer there).  After the un-compress |Y'| >= min_gain |X|.  Called only for m > 0 (wave-uniform): a stream
+// without a limit keeps the code path, and the bits, of fe_step_pool_streams.
+__device__ __forceinline__ void bin_floor(float& yr, float& yi, float xr, float xi, float m) {
+    const float y2 = yr * yr + yi * yi;
+    const float s = fmaxf(1.0f, m * sqrtf(xr * xr + xi * xi) * __builtin_amdgcn_rsqf(y2));
+    const bool zero = y2 < 1.17549435e-38f;
+    yr = zero ? m * xr : yr * s;
+    yi = zero ? m * xi : yi * s;
+}
+// BSRNN's three-launch step has no launch that sees both ends of the audio: the one that reads it stores the row's input half (HALF = 0), PART 2
+// the output half (HALF = 1) - 8 bytes each, combined as levels_store combines them
+template <int NW, int HALF>
+__device__ __forceinline__ void levels_store_half(StreamLevels* row, const float* red) {
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    f32x2 r = {red[2 * HALF], red[2 * HALF + 1]};
+#pragma unroll
+    for (int w = 1; w < NW; ++w) { r[0] += red[4 * w + 2 * HALF]; r[1] = fmaxf(r[1], red[4 * w + 2 * HALF + 1]); }
+    *reinterpret_cast<f32x2*>(reinterpret_cast<float*>(row) + 2 * HALF) = r;
+}
+// the meters of those kernels: n samples of a row in LDS (the hop as loaded, the hop as it goes out), thread tid's of every kThreads, into the
+// wave's partials
+__device__ __forceinline__ void levels_row(float& acc_ss, float& acc_pk, const float* row, int stride, int n, int tid) {
+    float ss = 0.0f, pk = 0.0f;
+    for (int i = tid; i < n; i += kThreads) {
+        const float x = row[i * stride];
+        ss += x * x;
+        pk = fmaxf(pk, fabsf(x));
+    }
+    acc_ss = wave_sum(acc_ss, ss);
+    acc_pk = wave_max(acc_pk, pk);
 }
 
 // ln variant: one norm site.  buf holds the [ROWS x COLS] pre-norm values of the frame (leading dimension LD); the statistics are

@@ -383,6 +383,8 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(P
         }
     }
     // (per-stream pointers are derived from the kernel arguments where they are used, not kept live through the frame)
+    StreamCtl<STRM> ctl;                             // (STRM, fe_step_pool_streams_ctl) this stream's limit and the meters' partials of this wave
+    if constexpr (STRM) { if (a.min_gain != nullptr) ctl.m_min = stream_mask_floor(a.min_gain[sb], a.compression); }
     float* dbg = DBG ? a.dbg + (size_t)b * a.dbg_stride : nullptr;
     // dump(stage, f): element (r, c) of the stage = f(r, c)
     auto dump = [&](int stage, auto&& f) {
@@ -457,6 +459,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(P
             if constexpr (!PIPE) {
             if (mode == FE_MODE_STREAM) {
                 for (int m = tid; m < OVL; m += kThreads) cst[m] = fb[m + H].x;
+                if constexpr (STRM) { if (a.levels != nullptr) levels_row(ctl.lv.in_ss, ctl.lv.in_pk, &fb[OVL].x, 2, H, tid); }     // (the hop as loaded)
                 __syncthreads();
             }
             }
@@ -1182,6 +1185,26 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(P
                     fa[N - f] = make_float2(yr, -yi);
                 }
             }
+            // fe_step_pool_streams_ctl, a limited stream (wave-uniform): its bins again, with the floor before the un-compress, over what the loop
+            // above left - the same thread writes the same places.  A second pass, as in fe_frame_kernel: with the floor inside the loop above
+            // the un-compress of an unlimited stream was contracted differently, and its bits were no longer the slotted kernel's.
+            if constexpr (STRM) {
+                if (ctl.m_min > 0.0f) {
+                    for (int f = tid; f < BINS; f += kThreads) {
+                        const float sr = sp[2 * f], si = sp[2 * f + 1], mr = mf[f], mi = mf[258 + f];
+                        const float o_r = sr * mr - si * mi, o_i = sr * mi + si * mr;
+                        const float mfm = sqrtf(mr * mr + mi * mi);
+                        const float mm = (msub[f] + mfm) * 0.5f;
+                        float yr = o_r / mfm * mm, yi = o_i / mfm * mm;
+                        bin_floor(yr, yi, sr, si, ctl.m_min);
+                        const float g = pow_f(sqrtf(yr * yr + yi * yi), 1.0f / a.compression - 1.0f);
+                        yr *= g; yi *= g;
+                        if (f == 0) fa[0] = make_float2(yr, 0.0f);
+                        else if (f == N / 2) fa[N / 2] = make_float2(yr, 0.0f);
+                        else { fa[f] = make_float2(yr, yi); fa[N - f] = make_float2(yr, -yi); }
+                    }
+                }
+            }
         }
         __syncthreads();
         if (mode != FE_MODE_SPEC) {
@@ -1203,6 +1226,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(P
             }
             __syncthreads();
             if constexpr (STRM) {
+                if (a.levels != nullptr) levels_row(ctl.lv.out_ss, ctl.lv.out_pk, xo, 1, H, tid);
                 stream_store_row(a.wav_out, a.format, sv.out_off + (long long)t * H, xo, H, tid, kThreads);
             } else
             if (mode == FE_MODE_STREAM) {
@@ -1231,6 +1255,16 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(P
             }
         }
         FS_CLK(7);
+    }
+    if constexpr (STRM) {
+        // the stream's level row, one 16-byte store: the waves' partials through the (idle) transform buffer, wave 0 first
+        if (a.levels != nullptr) {
+            float* red = reinterpret_cast<float*>(fa);
+            levels_put(red, ctl.lv, wave, tid0 & 63);
+            __syncthreads();
+            if (tid0 == 0) levels_store<kWaves>(a.levels + sb, red);
+            __syncthreads();
+        }
     }
     if constexpr (PIPE) break;
     b += gridDim.x;

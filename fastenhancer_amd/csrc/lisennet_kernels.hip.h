@@ -251,6 +251,8 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((
             continue;
         }
     }
+    StreamCtl<STRM> ctl;                             // (STRM, fe_step_pool_streams_ctl) this stream's limit and the meters' partials of this wave
+    if constexpr (STRM) { if (a.min_gain != nullptr) ctl.m_min = stream_mask_floor(a.min_gain[sb], a.compression); }
     float* dbg = DBG ? a.dbg + (size_t)b * a.dbg_stride : nullptr;
     auto dump = [&](int stage, auto&& f) {
         if constexpr (DBG) {
@@ -364,6 +366,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((
             __syncthreads();
             if (mode == FE_MODE_STREAM) {
                 for (int m = tid; m < OVL; m += kThreads) cst[m] = fb[m + H].x;
+                if constexpr (STRM) { if (a.levels != nullptr) levels_row(ctl.lv.in_ss, ctl.lv.in_pk, &fb[OVL].x, 2, H, tid); }     // (the hop as loaded)
                 __syncthreads();
             }
             float2* Xf = fft_lds<S, false>(fa, fb, tw);
@@ -930,6 +933,23 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((
                     fa[N - f] = make_float2(yr, -yi);
                 }
             }
+            // fe_step_pool_streams_ctl, a limited stream (wave-uniform): its bins again, with the floor before the un-compress, over what the loop
+            // above left - the same thread writes the same places.  A second pass, as in fe_frame_kernel: with the floor inside the loop above
+            // the un-compress of an unlimited stream was contracted differently, and its bits were no longer the slotted kernel's.
+            if constexpr (STRM) {
+                if (ctl.m_min > 0.0f) {
+                    for (int f = tid; f < BINS; f += kThreads) {
+                        const float sr = sp[2 * f], si = sp[2 * f + 1], mr = mk[f], mi = mk[260 + f];
+                        float yr = sr * mr - si * mi, yi = sr * mi + si * mr;
+                        bin_floor(yr, yi, sr, si, ctl.m_min);
+                        const float g = pow_f(sqrtf(yr * yr + yi * yi), 1.0f / a.compression - 1.0f);
+                        yr *= g; yi *= g;
+                        if (f == 0) fa[0] = make_float2(yr, 0.0f);
+                        else if (f == N / 2) fa[N / 2] = make_float2(yr, 0.0f);
+                        else { fa[f] = make_float2(yr, yi); fa[N - f] = make_float2(yr, -yi); }
+                    }
+                }
+            }
         }
         __syncthreads();
         if (mode != FE_MODE_SPEC) {
@@ -951,6 +971,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((
             }
             __syncthreads();
             if constexpr (STRM) {
+                if (a.levels != nullptr) levels_row(ctl.lv.out_ss, ctl.lv.out_pk, xo, 1, H, tid);
                 stream_store_row(a.wav_out, a.format, sv.out_off + (long long)t * H, xo, H, tid, kThreads);
             } else
             if (mode == FE_MODE_STREAM) {
@@ -980,6 +1001,16 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((
         }
         }   // PART != 1
         LS_CLK(5);
+    }
+    if constexpr (STRM) {
+        // the stream's level row, one 16-byte store: the waves' partials through the (idle) transform buffer, wave 0 first
+        if (a.levels != nullptr) {
+            float* lred = reinterpret_cast<float*>(fa);
+            levels_put(lred, ctl.lv, wave, tid0 & 63);
+            __syncthreads();
+            if (tid0 == 0) levels_store<kWaves>(a.levels + sb, lred);
+            __syncthreads();
+        }
     }
     if constexpr (PIPE) break;
     b += gridDim.x;

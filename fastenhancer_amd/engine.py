@@ -456,11 +456,12 @@ class Engine:
 
     def _step_streams(self, wav_in: Tensor, state: Tensor, capacity: int, desc, wav_out: Tensor, T_max: int, pinned: bool,
                       min_gain: Optional[Tensor] = None, levels: Optional[Tensor] = None, bank: Optional[Tensor] = None, chunk: bool = False,
-                      work: Optional[Tensor] = None, pool: bool = False) -> Tensor:
+                      work: Optional[Tensor] = None, pool: bool = False, pool_ctl: bool = False) -> Tensor:
         """The packet step behind step_streams* / step_streams_chunk* / step_pool_streams*.  pool: fe_step_pool_streams[_pinned], the packet
         step of every family - the same checks of buffers and descriptors; the per-stream controls, the weight banks and the pipelined form
-        are FastEnhancer's and are refused here."""
-        ctl = min_gain is not None or levels is not None
+        are FastEnhancer's and are refused here.  pool_ctl: fe_step_pool_streams_ctl[_pinned], that step with the two controls for every
+        family (either table may be None: a NULL)."""
+        ctl = min_gain is not None or levels is not None or pool_ctl
         name = "fe_step_streams" + ("_banked" if bank is not None else "_ctl" if ctl else "") + ("_pinned" if pinned else "")
         if chunk:       # (one entry point, every table an argument that may be NULL)
             name = "fe_step_streams_chunk" + ("_pinned" if pinned else "")
@@ -470,6 +471,8 @@ class Engine:
                 raise ValueError(f"step_pool_streams takes no {' / '.join(given)}: the suppression limit, the level meters, the weight banks and the "
                                  "pipelined packet step are built for the FastEnhancer family (step_streams, step_streams_chunk)")
             name = "fe_step_pool_streams" + ("_pinned" if pinned else "")
+        if pool_ctl:
+            name = "fe_step_pool_streams_ctl" + ("_pinned" if pinned else "")
         for what, x in (("wav_in", wav_in), ("wav_out", wav_out)):
             if not isinstance(x, Tensor) or x.dtype not in (torch.float32, torch.int16) or not x.is_contiguous() or x.numel() == 0:
                 raise ValueError(f"{what} must be a contiguous, non-empty float32 or int16 tensor")
@@ -554,6 +557,22 @@ class Engine:
         step_streams_pinned: synchronise the stream before reading wav_out or rewriting wav_in)."""
         return self._step_streams(wav_in, state, capacity, desc, wav_out, T_max, pinned=True, min_gain=min_gain, levels=levels, bank=bank,
                                   chunk=chunk, pool=True)
+
+    def step_pool_streams_ctl(self, wav_in: Tensor, state: Tensor, capacity: int, desc, wav_out: Tensor, T_max: int = 1, *,
+                              min_gain: Optional[Tensor] = None, levels: Optional[Tensor] = None) -> Tensor:
+        """fe_step_pool_streams_ctl: step_pool_streams with the suppression limit and the level meters for every family with a streaming state -
+        FastEnhancer's models as step_streams(min_gain=, levels=) runs them; BSRNN, FSPEN and LiSenNet inside the launches of step_pool_streams.
+        min_gain [capacity] / levels [capacity, 4]: the tables of step_streams, with its checks (float32, contiguous, indexed by SLOT, on the
+        device or in page-locked host memory); either may be None, both None is step_pool_streams.  On BSRNN, FSPEN and LiSenNet the limit
+        holds the output bin against the input bin, |Y| >= min_gain |X| (their outputs are not a mask times the input); every state tensor
+        but cache_istft keeps the bits of the unlimited run."""
+        return self._step_streams(wav_in, state, capacity, desc, wav_out, T_max, pinned=False, min_gain=min_gain, levels=levels, pool_ctl=True)
+
+    def step_pool_streams_ctl_pinned(self, wav_in: Tensor, state: Tensor, capacity: int, desc, wav_out: Tensor, T_max: int = 1, *,
+                                     min_gain: Optional[Tensor] = None, levels: Optional[Tensor] = None) -> Tensor:
+        """fe_step_pool_streams_ctl_pinned: step_pool_streams_ctl with wav_in / wav_out in page-locked HOST memory (the completion rule of
+        step_streams_pinned: synchronise the stream before reading wav_out or a pinned levels table, or rewriting wav_in)."""
+        return self._step_streams(wav_in, state, capacity, desc, wav_out, T_max, pinned=True, min_gain=min_gain, levels=levels, pool_ctl=True)
 
     # ---- the packet step on the time pipeline: streams that come back with a backlog (fe_step_streams_chunk[_pinned])
     def streams_chunk_work_floats(self, n: int, T_max: int) -> int:

@@ -176,6 +176,16 @@ def packet_step(engine, pinned: bool) -> Callable:
     return engine.step_streams_pinned if pinned else engine.step_streams
 
 
+def packet_ctl_step(engine, pinned: bool) -> Callable:
+    """The engine's call for one packet step with a suppression limit or level meters (FamilyPacketPool.tick, when either control is in use):
+    step_pool_streams_ctl[_pinned] for BSRNN, FSPEN and LiSenNet, step_streams[_pinned] - which takes min_gain= and levels= itself - for
+    FastEnhancer and for an engine object without a family description."""
+    fam = _FAMILIES.get(type(getattr(engine, "cfg", None)))
+    if fam is not None and fam.pool:
+        return engine.step_pool_streams_ctl_pinned if pinned else engine.step_pool_streams_ctl
+    return engine.step_streams_pinned if pinned else engine.step_streams
+
+
 def pool_family_name(engine) -> Optional[str]:
     """"BSRNN", "FSPEN" or "LiSenNet" for an engine of a family that steps through fe_step_pool / fe_step_pool_streams, else None: what a
     pool names when it refuses a control that is FastEnhancer's (suppression limit, level meters, weight banks, the pipelined packet step)."""

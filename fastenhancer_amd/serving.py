@@ -30,7 +30,7 @@ from torch import Tensor
 
 from . import _lib
 from .engine import Engine
-from .family import chunk_step, packet_step, pool_family_name, slot_step
+from .family import chunk_step, packet_ctl_step, packet_step, pool_family_name, slot_step
 from .resample import Resampler
 
 
@@ -245,7 +245,8 @@ class PacketPool(StreamPool):
     default): one launch, as ever.
     A BSRNN, FSPEN or LiSenNet engine: tick() launches Engine.step_pool_streams_pinned (fe_step_pool_streams_pinned); push, pull, move,
     resize, adopt, export and catch_up work as for FastEnhancer.  The meters, the suppression limit, the weight banks and backlog_hops are
-    FastEnhancer's: such a pool refuses them with a ValueError that names the family, before it calls the engine."""
+    FastEnhancer's: such a pool refuses them with a ValueError that names the family, before it calls the engine.  (FamilyPacketPool, below,
+    has the meters and the limit for those families too.)"""
 
     def __init__(self, engine: Engine, capacity: int, ring_hops: int, T_max: int = 1, meters: bool = False, backlog_hops: int = 0):
         self._baseline = pool_family_name(engine)          # "BSRNN" / "FSPEN" / "LiSenNet", or None: the per-stream controls are available
@@ -494,7 +495,7 @@ class PacketPool(StreamPool):
         if self._bank is not None:
             ctl["bank"] = self._bank
         if desc:
-            packet_step(self.engine, pinned=True)(self.ring_in, self.state, self.capacity, desc, self.ring_out, T_max=self.T_max, **ctl)
+            self._packet_call(ctl)(self.ring_in, self.state, self.capacity, desc, self.ring_out, T_max=self.T_max, **ctl)
         if backlog:
             if self._backlog_work is None:
                 need = self.engine.streams_chunk_work_floats(self.capacity, self.backlog_hops)
@@ -508,6 +509,10 @@ class PacketPool(StreamPool):
             self._level_samples[slot] = hops * self.H
         return desc
 
+    def _packet_call(self, ctl: dict):
+        """the engine's call for the tick's ordinary launch, given the tables it will be handed"""
+        return packet_step(self.engine, pinned=True)
+
     def pull(self, slot: int) -> Tensor:
         """The enhanced int16 samples produced since the last pull (a copy; empty when there are none)."""
         self._check_open(slot)
@@ -517,6 +522,35 @@ class PacketPool(StreamPool):
         out = torch.cat([self.ring_out[slot, pos:pos + first], self.ring_out[slot, :n - first]])
         self._pulled[slot] = r + n
         return out
+
+
+class FamilyPacketPool(PacketPool):
+    """A PacketPool whose suppression limit and level meters work for every family.  On a FastEnhancer engine it is PacketPool, call for call.
+    On a BSRNN, FSPEN or LiSenNet engine tick() launches Engine.step_pool_streams_pinned while neither control is in use - no meters, no
+    limit ever set - and Engine.step_pool_streams_ctl_pinned (fe_step_pool_streams_ctl_pinned) otherwise; set_suppression_limit, levels,
+    move, resize and adopt carry the two tables as PacketPool does.  There the limit holds each output bin against the input bin,
+    |Y| >= 10^(dB / 20) |X| (the output of these models is not a mask times the input).  Weight banks other than 0 and backlog_hops stay
+    FastEnhancer's and are refused with the family's name; catch_up keeps refusing a slot with a limit."""
+
+    _FAMILY_CONTROLS = ("level meters", "suppression limit")
+
+    def _refuse_baseline(self, what: str) -> None:
+        if self._baseline is not None and not what.startswith(self._FAMILY_CONTROLS):
+            raise ValueError(f"a FamilyPacketPool of a {self._baseline} engine has no {what}: weight banks and the pipelined packet step are built "
+                             "for the FastEnhancer family")
+
+    def _packet_call(self, ctl: dict):
+        if self._baseline is not None and ctl:
+            return packet_ctl_step(self.engine, pinned=True)
+        return packet_step(self.engine, pinned=True)
+
+    def move(self, slot: int, dst_pool: "PacketPool") -> int:
+        """PacketPool.move; a stream with a limit on a BSRNN, FSPEN or LiSenNet engine moves to a FamilyPacketPool only (a plain PacketPool of
+        such an engine has no limit to carry it)."""
+        if isinstance(dst_pool, PacketPool) and not isinstance(dst_pool, FamilyPacketPool) and dst_pool._baseline is not None \
+                and slot in self._open and self._get_gain(slot) != 0.0:
+            dst_pool._refuse_baseline("suppression limit")
+        return super().move(slot, dst_pool)
 
 
 class ResampledPacketPool:

@@ -324,6 +324,38 @@ int fe_step_streams_ctl(fe_handle* h, const void* wav_in_dev, size_t in_count, f
 int fe_step_streams_ctl_pinned(fe_handle* h, const void* wav_in_host, size_t in_count, float* state_dev, int capacity,
                                const fe_stream_desc* desc_dev, void* wav_out_host, size_t out_count, int n, int T_max, int format,
                                const float* min_gain, fe_stream_levels* levels, void* stream);
+/* The two controls for EVERY family with a streaming state: fe_step_pool_streams[_pinned] with the two tables of fe_step_streams_ctl.  The
+ * parameter lists are those of fe_step_streams_ctl[_pinned].  Descriptor rules, in-kernel bounds check, formats, pinning and completion rules, kernel
+ * choice, fe_last_step_kernel's strings and "allocates nothing, capturable" are those of fe_step_pool_streams[_pinned]; the tables are those of
+ * fe_step_streams_ctl - slot-indexed, [capacity], device or mapped page-locked host memory, both ends looked up on every call, levels 16-byte
+ * aligned, read and written when the kernels run - with the same codes and wording under these names.
+ *   FastEnhancer models: the call IS fe_step_streams_ctl[_pinned] - same launch, bits, refusals and fe_last_step_kernel; the noncausal model gets
+ *     fe_step's refusal.  (fe_step_streams_ctl* itself keeps refusing the other families.)
+ *   Both tables NULL: the call is fe_step_pool_streams[_pinned] - the same code path, the same bits.
+ *   min_gain on BSRNN, FSPEN and LiSenNet: their outputs are not a mask times the input (BSRNN's is X M + R with an additive residual, FSPEN
+ *     combines two masks), so a floor on a mask bounds nothing.  The limit is on the output bin against the input bin.  g = min_gain[slot],
+ *     clamped to [0, 1] by the kernel (NaN and 0: off); c = input_compression, m = g^c.  Per frame, for all 257 bins, with X_c the compressed
+ *     input bin the model saw and Y_c the bin it produced in the compressed domain, right before the un-compress:
+ *       Y_c' = Y_c max(1, m |X_c| / |Y_c|),   and   Y_c' = m X_c (the input's phase) where |Y_c|^2 < FLT_MIN.
+ *     Un-compress and iSTFT follow unchanged; after the un-compress |Y| >= g max(|X|, 1e-5): no bin leaves attenuated by more than min_gain.
+ *     For a pure complex mask this is FastEnhancer's floor in value, not in bits (FastEnhancer keeps its own).  The limit touches the output
+ *     path only: every state tensor but cache_istft holds the bits of the unlimited run.  A stream whose gain is off takes the code path of
+ *     fe_step_pool_streams: its rows and state are those, bit for bit.
+ *   levels: as for fe_step_streams_ctl - for every stream that advanced at least one hop, row `slot` is (sum of squares, max |x|) of its
+ *     hops * H input samples as floats (int16: s / 32768) and of its hops * H output samples as floats before quantisation; peaks exact, sums
+ *     fp32 sums without atomics in a fixed order; a row is bitwise reproducible and does not depend on the stream's position in the batch, on
+ *     device or pinned audio, or on int16 against float32 of s / 32768.  Rows of streams with 0 hops, of streams skipped by the bounds check, of
+ *     slots outside [0, capacity) and of slots not named keep every bit.  FSPEN, LiSenNet and BSRNN's single-kernel walk write the row as one
+ *     16-byte store at the end of the stream.  BSRNN's three-launch step (T_max == 1) writes it as two 8-byte halves: the launch that reads
+ *     the audio (bsrnn_ov_kernel or PART 1) stores the input half, PART 2 the output half - the one-store promise is NOT made for this step;
+ *     the row is complete once `stream` has completed the call.
+ *   Weight banks and the pipelined backlog stay FastEnhancer's. */
+int fe_step_pool_streams_ctl(fe_handle* h, const void* wav_in_dev, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,
+                             void* wav_out_dev, size_t out_count, int n, int T_max, int format, const float* min_gain, fe_stream_levels* levels,
+                             void* stream);
+int fe_step_pool_streams_ctl_pinned(fe_handle* h, const void* wav_in_host, size_t in_count, float* state_dev, int capacity,
+                                    const fe_stream_desc* desc_dev, void* wav_out_host, size_t out_count, int n, int T_max, int format,
+                                    const float* min_gain, fe_stream_levels* levels, void* stream);
 
 /* Weight banks: the streams of one packet batch on different checkpoints of the handle's shape (a canary, per-customer fine-tunes, a roll-out
  * under live streams) - one handle, one state buffer and one launch per tick for all of them.
