@@ -95,6 +95,11 @@ SYMBOLS = {
                                       c_void_p, c_void_p, c_void_p]),
     "fe_step_streams_chunk_pinned": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p,
                                              c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fe_step_pool_streams_chunk_work_floats": (c_size_t, [c_void_p, c_int, c_int]),
+    "fe_step_pool_streams_chunk": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p,
+                                           c_void_p, c_void_p, c_void_p]),
+    "fe_step_pool_streams_chunk_pinned": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p,
+                                                  c_void_p, c_void_p, c_void_p]),
     "fe_set_offline_engine": (c_int, [c_void_p, c_int]),
     "fe_set_step_kernel": (c_int, [c_void_p, c_int]),
     "fe_set_option": (c_int, [c_void_p, c_char_p, c_int]),

@@ -225,11 +225,20 @@ struct BLds {
 // any element alignment in device or page-locked host memory - read through stream_sample by the launch that reads it (the whole frame, PART 1,
 // bsrnn_ov_kernel), written through stream_store_row by the one that writes it (the whole frame, PART 2).  A stream without a hop is skipped by
 // each launch as one with a slot out of range is - and gets no rows; `format` is a run-time, wave-uniform branch.
+// PIPE + SLOT + STRM (fe_step_pool_streams_chunk[_pinned]; generic, PART 0, streaming mode): the packet step's time-pipelined form, after
+// fe_frame_kernel's (fe_kernels.hip.h).  Workgroup blockIdx.x serves call stream b = blockIdx.x / pipe_p and the frames p, p + P, ... < hops of
+// that stream's own stream_view - all P workgroups of a stream read the same descriptor and make the same check - at the state row of its slot:
+// frame 0 fetches the slot's (h, c) without a wait, every frame leaves its own there through HO::st, the next takes it through HO::ld.  The
+// stream's frame count is sv.hops everywhere (loop bound, waits); a.T = T_max is the row stride of a.frames only.  Frame t's samples are
+// positions t H + n of [the slot's old cache_stft | the stream's samples through stream_sample]; the limit is applied per frame as in the
+// serial packet step.  A stream without a hop, one the bounds check skips and one without state compute nothing here and touch neither counter
+// nor state; zero rows, output rows, both STFT caches and the level row are stream_ola_streams_kernel's (stft_kernels.hip.h).
 template <class S, bool HOT, bool PROF, bool DBG, bool OCC2 = false, bool PIPE = false, int PART = 0, bool SLOT = false, bool STRM = false>
 __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, PART == 2 ? 6 : PART == 3 ? 4 : OCC2 ? 2 : 1))) bsrnn_frame_kernel(typename BKernelArgs<SLOT, STRM>::type a) {
     static_assert(!STRM || SLOT, "the packet instantiations are slotted ones");
     static_assert(!PIPE || (!HOT && !PROF && !DBG), "the time-pipelined instantiation is the plain offline kernel");
-    static_assert(!SLOT || (!PROF && !DBG && !PIPE && PART != 3), "the slotted instantiations are the plain per-stream kernels");
+    static_assert(!SLOT || (!PROF && !DBG && (!PIPE || (STRM && !HOT && !OCC2 && PART == 0)) && PART != 3),
+                  "the slotted instantiations are the plain per-stream kernels, and the time-pipelined packet form of the generic one");
     static_assert(PART == 0 || (HOT && !PROF && !DBG && !PIPE), "the split step is the per-hop streaming step");
     // PART = 3: the front of the frame alone (STFT, compress, band split -> mlp_x / mlp_sp): the stream-batched step
     // (bsrnn_sb_kernels.hip.h) runs the layers for sixteen streams per workgroup on the matrix cores
@@ -345,6 +354,12 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
     StreamView sv{-1, 0, 0, 0};                      // (STRM) the stream this workgroup is running
     if constexpr (STRM) {
         sv = stream_view_of<H>(a, b);
+        if constexpr (PIPE) {
+            // the time-pipelined form: a stream without a hop (none asked for, or skipped by the bounds check) or without state computes
+            // nothing here - its zero rows are stream_ola_streams_kernel's - and a workgroup whose first frame lies beyond the stream's hops
+            // leaves: neither has touched a counter or the state (wave-uniform: the whole workgroup returns)
+            if (t_first >= sv.hops || (unsigned int)sb >= (unsigned int)a.capacity) return;
+        } else
         if (sv.hops == 0 || (unsigned int)sb >= (unsigned int)a.capacity) {      // (wave-uniform) no hop: nothing; no state: its hops output rows are zero
             if (PART != 1 && sv.hops) stream_zero_row(a.wav_out, a.format, sv.out_off, sv.hops * H, tid, kThreads);
             b += gridDim.x;
@@ -411,6 +426,16 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
                 // xin[n - OVL] as in the serial walk (here with n - OVL < 0 for the frames that still start inside the cache).  Every frame of
                 // the stream reads the old cache side by side; stream_ola_kernel writes both caches afterwards.
                 // (the cache's base and end as values of the loop, not a branch around it: the other instantiations keep their code)
+                if constexpr (STRM && PIPE) {
+                    // (position t H + n of [old cache_stft | the stream's samples]: inside the cache while t H + n < OVL)
+                    const long long x0 = sv.in_off + (long long)t * H - OVL;
+                    const float* cs0 = cst + t * H;
+                    const int ovl0 = OVL - t * H;
+                    for (int n = tid; n < N; n += kThreads) {
+                        const float v = (n < ovl0) ? cs0[n] : stream_sample(a.wav_in, a.format, x0 + n);
+                        fa[n] = make_float2(v * win[n], 0.0f);
+                    }
+                } else
                 if constexpr (STRM) {
                     const long long x0 = sv.in_off + (long long)t * H - OVL;
                     for (int n = tid; n < N; n += kThreads) {
@@ -514,6 +539,15 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
             if (l == 0) BE_CLK(2);
             if constexpr (PIPE) {
                 // frame t - 1's state of this layer: wait for it, fetch h into the GEMM's A operand buffer (c is fetched in the epilogue's place)
+                // No wait depends on a frame the stream does not have (nT frames: a.T offline, STRM the stream's own sv.hops, 1 .. T_max).
+                // Frame 0 does not wait.  Frame t >= 1 polls counter (b, l) for the value t, which only frame t - 1 publishes; it runs here
+                // only if t < nT, so t - 1 < nT is a frame of the stream, and it belongs to workgroup (t - 1) mod P of the stream, which
+                // exists (the grid has P workgroups per stream) and did not leave at the top: its first frame (t - 1) mod P <= t - 1 < nT.
+                // That workgroup reaches frame t - 1 after its earlier frames t - 1 - P, t - 1 - 2 P, ..., which by induction on the frame
+                // index wait only on frames below them, and frame t - 1's publish of layer l follows from frame t - 2's alone.  nT < P: the
+                // workgroups p >= nT have left, nobody polls for their frames (a poll for frame p's state would come from frame p + 1 > nT).
+                // nT not a multiple of P: the last round is short, its frames wait on the frames before them as every other does.  All
+                // workgroups of the launch are co-resident (cooperative launch), so a polled producer is running or has finished.
                 HO::wait(pflag, l, t);
 #pragma unroll
                 for (int q = 0; q < HPT; ++q) { const int i = tid + q * kThreads; hpre[q] = HO::ld(hg + (i < kBands * HH ? i : kBands * HH - 1)); }
@@ -1173,7 +1207,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1
         }      // (PART != 1)
         BE_CLK(11);
     }
-    if constexpr (STRM) {
+    if constexpr (STRM && !PIPE) {      // (the time-pipelined form: the level row is stream_ola_streams_kernel's)
         // the stream's level row: the waves' partials through the (idle) transform buffer, wave 0 first.  One 16-byte store where one kernel walks
         // the frames; in the three-launch step PART 1 stores the input half, PART 2 the output half
         if (a.levels != nullptr) {
@@ -1497,6 +1531,9 @@ struct BImpl {
     // the per-hop step with the layers batched over the streams (bsrnn_sb_kernels.hip.h): front (PART 3) -> layers -> mask-decoder MLP -> tail
     // (PART 2); nullptr where the stream-batched layers are not built (num_channels > 16)
     void (*launch_sb)(const BArgs&, const SbOffsets&, int total_floats, int max_wgs, hipStream_t, hipError_t*);
+    // the packet step's time-pipelined launch (fe_step_pool_streams_chunk: a.pipe_p workgroups per call stream; cooperative, a refusal leaves no
+    // error behind and names no kernel)
+    hipError_t (*launch_streams_pipe)(const BStreamArgs&, hipStream_t);
     const char* name = nullptr;      // the line of fe_bsrnn_shapes.def (fe_bsrnn_shape.hip.in): part of fe_last_step_kernel's answer
 };
 
@@ -1664,6 +1701,17 @@ void blaunch_pipe_impl(const BArgs& a, hipStream_t st, hipError_t* err) {
     *err = launch_coop<&bsrnn_frame_kernel<S, false, false, false, false, true>>(name, dim3(a.B * a.pipe_p), dim3(kThreads), BLds<S>::BYTES, st, a);
 }
 
+// fe_step_pool_streams_chunk: the PIPE + SLOT + STRM instantiation, n * pipe_p cooperative workgroups (one per CU, as blaunch_pipe_impl's)
+constexpr KernelNames bpipe_streams_names() { return kernel_names("bsrnn_frame_kernel", 0, "time-pipelined", "streams"); }
+static_assert(same_text(bpipe_streams_names().s[0], "bsrnn_frame_kernel<time-pipelined, streams>") &&
+              same_text(bpipe_streams_names().s[3], "bsrnn_frame_kernel<time-pipelined, streams, pinned, s16>"), "what fe_last_step_kernel reports for it");
+template <class S>
+hipError_t blaunch_streams_pipe_impl(const BStreamArgs& a, hipStream_t st) {
+    static constexpr KernelNames names = bpipe_streams_names();
+    return launch_coop<&bsrnn_frame_kernel<S, false, false, false, false, true, 0, true, true>, true>(baseline_name<true>(names, a), dim3(a.B * a.pipe_p),
+                                                                                                      dim3(kThreads), BLds<S>::BYTES, st, a);
+}
+
 template <class S>
 void bdbg_stage_impl(int s, int* rows, int* cols, size_t* off) {
     *rows = BDebugLayout<S>::rows(s);
@@ -1676,7 +1724,7 @@ BImpl make_bimpl() {
     return BImpl{S::C, S::NLAY, S::HOP, BLds<S>::BYTES, S::XPG ? (size_t)2 * 32 * S::G4 : (size_t)0,
                  BDebugLayout<S>::total(), BDebugLayout<S>::n_stages, S::WREG, S::KSPLIT, S::NTD, &blaunch_step_impl<S>, &bdbg_stage_impl<S>,
                  &blaunch_pipe_impl<S>, 1,       // (the PIPE instantiation is compiled for one workgroup per CU: waves_per_eu(1, 1))
-                 (SbLds<S>::FITS || Sb64Lds<S>::FITS) ? &blaunch_sb_impl<S> : nullptr};
+                 (SbLds<S>::FITS || Sb64Lds<S>::FITS) ? &blaunch_sb_impl<S> : nullptr, &blaunch_streams_pipe_impl<S>};
 }
 
 }  // namespace fe

@@ -1519,14 +1519,24 @@ int fe_step_streams(fe_handle* h, const void* wav_in_dev, size_t in_count, float
 // with step_streams' checks in step_streams' order.  Nothing is allocated.
 // min_gain / levels (fe_step_pool_streams_ctl[_pinned]; null from fe_step_pool_streams[_pinned]): the two slot-indexed tables, looked up as
 // step_streams looks them up (table_view) and handed to the same launches - the packet instantiations apply them behind null tests.
+// chunk (fe_step_pool_streams_chunk[_pinned]): the same call with each stream's hops on the family's time pipeline where
+// pool_streams_chunk_pipe_width says so and the runtime accepts the cooperative launch (launch_pool_streams_chunk, below fe_step_backlog);
+// otherwise - and always after the same checks - the launch of the packet step itself.  FastEnhancer: fe_step_streams_chunk without a bank table.
+static int pool_streams_chunk_pipe_width(const fe_handle* h, int n, int T_max);
+static int launch_pool_streams_chunk(fe_handle* h, const BaselineStepOwn& own, const float* wav_in, float* state, float* wav_out, int n, int T_max, int P,
+                                     float* work_dev, void* stream, bool* refused);
 static int step_pool_streams(fe_handle* h, const char* fn, bool pinned, const void* wav_in, size_t in_count, float* state_dev, int capacity,
                              const fe_stream_desc* desc_dev, void* wav_out, size_t out_count, int n, int T_max, int format, void* stream,
-                             const float* min_gain = nullptr, fe_stream_levels* levels = nullptr) {
+                             const float* min_gain = nullptr, fe_stream_levels* levels = nullptr, bool chunk = false, float* work_dev = nullptr) {
     if (!h) return fail(FE_ERR_INVALID_ARG, "null handle");
     if (h->cfg.arch == FE_ARCH_FASTENHANCER)
-        return step_streams(h, fn, pinned, wav_in, in_count, state_dev, capacity, desc_dev, wav_out, out_count, n, T_max, format, stream, min_gain, levels);
+        return step_streams(h, fn, pinned, wav_in, in_count, state_dev, capacity, desc_dev, wav_out, out_count, n, T_max, format, stream, min_gain, levels,
+                            nullptr, chunk, work_dev);
     int rc = check_streams_args(fn, wav_in, in_count, state_dev, capacity, desc_dev, wav_out, out_count, n, T_max, format, levels);
-    if (rc == FE_OK) rc = check_ready(h);
+    if (rc != FE_OK) return rc;
+    const int P = chunk ? pool_streams_chunk_pipe_width(h, n, T_max) : 0;
+    if (P && !work_dev) return fail(FE_ERR_INVALID_ARG, "%s: null work buffer (fe_step_pool_streams_chunk_work_floats(h, %d, %d) floats)", fn, n, T_max);
+    rc = check_ready(h);
     if (rc != FE_OK) return rc;
     KernelLogScope klog_(h);
     const void* in = nullptr;
@@ -1542,6 +1552,13 @@ static int step_pool_streams(fe_handle* h, const char* fn, bool pinned, const vo
     own.io = fe::StreamIoArgs{reinterpret_cast<const fe::StreamDesc*>(desc_dev), in_count, out_count, format, pinned ? 1 : 0,
                               static_cast<const float*>(gains), static_cast<fe::StreamLevels*>(const_cast<void*>(rows))};
     // (the audio is typed by the format in the kernel)
+    if (P) {
+        bool refused = false;
+        rc = launch_pool_streams_chunk(h, own, static_cast<const float*>(in), state_dev, const_cast<float*>(static_cast<const float*>(out)), n, T_max, P, work_dev,
+                                       stream, &refused);
+        if (!refused) return rc;
+        // the runtime refused co-residency (GPU shared with other work): the packet step's own launch
+    }
     return launch_baseline_step(h, fe::STEP_STREAMS, own, static_cast<const float*>(in), 0, state_dev, const_cast<float*>(static_cast<const float*>(out)), 0, n,
                                 T_max, stream);
 }
@@ -2146,6 +2163,74 @@ int fe_step_backlog(fe_handle* h, const float* wav_in_dev, size_t in_stride, flo
     return rc;
 }
 
+// fe_step_pool_streams_chunk: fe_step_pool_streams_ctl with each stream's hops on the time pipeline, for every family with a streaming state.
+// FastEnhancer: fe_step_streams_chunk (step_pool_streams hands the call over).  The baseline families whose PIPE kernel hands the streaming
+// state on in place (Fam::kPipeCarriesState: BSRNN, FSPEN), written once over the family traits like baseline_step_backlog: work_dev is that
+// call's layout, pipe_layout(h, n, T_max, Fam::counters(h), 0) - the size depends on the model, n and T_max only.  LiSenNet: no work, no pipeline.
+size_t fe_step_pool_streams_chunk_work_floats(const fe_handle* h, int n, int T_max) {
+    if (!h || n <= 0 || T_max < 4) return 0;
+    size_t floats = 0;
+    if (visit_baseline(h->cfg.arch, [&](auto F) { floats = baseline_backlog_layout(F, h, n, T_max).total; })) return floats;
+    return fe_step_streams_chunk_work_floats(h, n, T_max);
+}
+
+// workgroups per call stream of fe_step_pool_streams_chunk's pipelined launch: the family's fe_offline width for n streams of T_max frames
+// (0: the packet step's own launch - T_max < 4, fe_set_time_pipeline(0 | 1), or too many streams to give each two co-resident workgroups).
+// Any hop count 0 .. T_max is served on the pipeline - the host cannot see the descriptors - so there is no T H >= N - H condition here:
+// stream_ola_streams_kernel orders its cache reads before its cache writes instead.
+static int pool_streams_chunk_pipe_width(const fe_handle* h, int n, int T_max) {
+    int P = 0;
+    if (n > 0) visit_baseline(h->cfg.arch, [&](auto F) {
+        if constexpr (decltype(F)::kPipeCarriesState) P = baseline_pipe_width(F, h, n, T_max);
+    });
+    return P;
+}
+
+// own: the packet step's fields as step_pool_streams has set them; wav_in / wav_out: device views.  A linear chain on the caller's stream - the
+// counters' zeroing (stft_kernels.hip.h: a kernel, not a memset node), the family's cooperative PIPE + STRM frame kernel on the caller's state in
+// place at each stream's slot, the audio kernel - that allocates nothing (Fam::args takes the per-family scratch the handle got at
+// fe_load_weights, sized for a workgroup per CU, which bounds the cooperative grid).
+// *refused: the runtime refused the cooperative launch; only the counters have been written.
+static int launch_pool_streams_chunk(fe_handle* h, const BaselineStepOwn& own, const float* wav_in, float* state, float* wav_out, int n, int T_max, int P,
+                                     float* work_dev, void* stream, bool* refused) {
+    *refused = false;
+    int rc = FE_OK;
+    hipStream_t st = (hipStream_t)stream;
+    visit_baseline(h->cfg.arch, [&](auto F) {
+        using Fam = decltype(F);
+        if constexpr (Fam::kPipeCarriesState) {
+            typename Fam::StreamArgs a = Fam::args(h, n, T_max);
+            a.capacity = own.capacity;
+            static_cast<fe::StreamIoArgs&>(a) = own.io;
+            Fam::state(a) = stream_io(a, wav_in, 0, wav_out, 0, state, state_layout(h, own.capacity));
+            const typename Fam::StreamArgs p = pipe_args(a, work_dev, baseline_backlog_layout(F, h, n, T_max), P);
+            const int nflags = (int)((size_t)n * Fam::counters(h));
+            hipLaunchKernelGGL(fe::zero_counters_kernel, dim3((nflags + fe::kThreads - 1) / fe::kThreads), dim3(fe::kThreads), 0, st, p.pipe_flags, nflags);
+            hipError_t e = hipGetLastError();
+            if (e != hipSuccess) { rc = launch_rc(e); return; }
+            if ((*refused = coop_refused(Fam::impl(h)->launch_streams_pipe(p, st)))) return;
+            fe::note_kernel("stream_ola_streams_kernel");
+            hipLaunchKernelGGL(fe::stream_ola_streams_kernel<typename Fam::StreamArgs>, dim3(n), dim3(fe::kThreads), 0, st, p, h->d.NFFT, h->d.HOP);
+            rc = launch_rc(hipGetLastError());
+        }
+    });
+    return rc;
+}
+
+int fe_step_pool_streams_chunk(fe_handle* h, const void* wav_in_dev, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,
+                               void* wav_out_dev, size_t out_count, int n, int T_max, int format, const float* min_gain, fe_stream_levels* levels,
+                               float* work_dev, void* stream) {
+    return step_pool_streams(h, "fe_step_pool_streams_chunk", false, wav_in_dev, in_count, state_dev, capacity, desc_dev, wav_out_dev, out_count, n, T_max,
+                             format, stream, min_gain, levels, true, work_dev);
+}
+
+int fe_step_pool_streams_chunk_pinned(fe_handle* h, const void* wav_in_host, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,
+                                      void* wav_out_host, size_t out_count, int n, int T_max, int format, const float* min_gain, fe_stream_levels* levels,
+                                      float* work_dev, void* stream) {
+    return step_pool_streams(h, "fe_step_pool_streams_chunk_pinned", true, wav_in_host, in_count, state_dev, capacity, desc_dev, wav_out_host, out_count, n,
+                             T_max, format, stream, min_gain, levels, true, work_dev);
+}
+
 // fe_step_streams_chunk: the packet step with each stream's hops on the time pipeline.  work_dev: fe_pipe_layout(h, n, T_max).  Built
 // for the models whose frames exchange the GRU state only (default, ln, dprnn): the ring variants' ring_in_kernel /
 // ring_out_kernel are not slotted, so time_kernel and dptransformer take the packet step itself, like every call the pipeline cannot take.
@@ -2182,7 +2267,7 @@ static int launch_streams_chunk(fe_handle* h, const fe::StreamFrameArgs& own, co
     if ((*refused = coop_refused(h->impl->launch_streams_pipe(a, st)))) return FE_OK;
     h->last_shape = h->impl->name;
     fe::note_kernel("stream_ola_streams_kernel");
-    hipLaunchKernelGGL(fe::stream_ola_streams_kernel, dim3(n), dim3(fe::kThreads), 0, st, a, h->d.NFFT, h->d.HOP);
+    hipLaunchKernelGGL(fe::stream_ola_streams_kernel<fe::StreamFrameArgs>, dim3(n), dim3(fe::kThreads), 0, st, a, h->d.NFFT, h->d.HOP);
     return launch_rc(hipGetLastError());
 }
 

@@ -320,11 +320,20 @@ __device__ __forceinline__ float row_dot(const float (&w)[12], float h, float ac
 // bounds-checked on every call), the frame loop runs the stream's own hops, the audio is float32 or int16 PCM at any element alignment in device
 // or page-locked host memory - read through stream_sample, written through stream_store_row.  A stream without a hop reads and writes nothing;
 // one with hops and a slot out of range gets zero rows.  `format` is a run-time, wave-uniform branch: one instantiation.
+// PIPE + SLOT + STRM (fe_step_pool_streams_chunk[_pinned]; PART 0, streaming mode): the packet step's time-pipelined form, after
+// fe_frame_kernel's (fe_kernels.hip.h).  Workgroup blockIdx.x serves call stream b = blockIdx.x / pipe_p and the frames p, p + P, ... < hops of
+// that stream's own stream_view - all P workgroups of a stream read the same descriptor and make the same check - at its slot of the
+// capacity-sized state (nst = capacity): frame 0 fetches the slot's inter-GRU states without a wait, every frame leaves its own there through
+// HO::st, the next takes them through HO::ld.  The stream's frame count is sv.hops everywhere (loop bound, waits); a.T = T_max is the row
+// stride of a.frames only.  Frame t's samples are positions t H + n of [the slot's old cache_stft | the stream's samples through
+// stream_sample]; the limit is applied per frame as in the serial packet step.  A stream without a hop, one the bounds check skips and one
+// without state compute nothing here and touch neither counter nor state; zero rows, output rows, both STFT caches and the level row are
+// stream_ola_streams_kernel's (stft_kernels.hip.h).
 template <class S, bool PROF, bool DBG, bool PIPE = false, int PART = 0, bool SLOT = false, bool STRM = false>
 __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(PART == 1 ? FS_WPE_FRONT : FS_WPE, PART == 1 ? FS_WPE_FRONT : FS_WPE))) fspen_frame_kernel(typename FKernelArgs<SLOT, STRM>::type a) {
     static_assert(!STRM || SLOT, "the packet instantiation is a slotted one");
     static_assert(!PIPE || (!PROF && !DBG), "the time-pipelined instantiation is the plain offline kernel");
-    static_assert(!SLOT || (!PROF && !DBG && !PIPE && PART == 0), "the slotted instantiation is the plain per-stream kernel");
+    static_assert(!SLOT || (!PROF && !DBG && (!PIPE || STRM) && PART == 0), "the slotted instantiations are the plain per-stream kernel and the time-pipelined packet form");
     static_assert(PART == 0 || (!PROF && !DBG && !PIPE), "the split step is the plain per-hop kernel");
     __shared__ __attribute__((aligned(16))) float smem[PART == 1 ? FLds::FRONT_TOTAL : FLds::TOTAL];
     using L = FLds;
@@ -364,6 +373,12 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(P
         sv = stream_view_of<H>(a, b);
         sb = sv.slot;
         nT = sv.hops;
+        if constexpr (PIPE) {
+            // the time-pipelined form: a stream without a hop (none asked for, or skipped by the bounds check) or without state computes
+            // nothing here - its zero rows are stream_ola_streams_kernel's - and a workgroup whose first frame lies beyond the stream's hops
+            // leaves: neither has touched a counter or the state (wave-uniform: the whole workgroup returns)
+            if (t_first >= nT || (unsigned int)sb >= (unsigned int)nst) return;
+        } else
         if (nT == 0 || (unsigned int)sb >= (unsigned int)nst) {      // (wave-uniform) no hop: nothing; no state: its hops output rows are zero
             if (nT) stream_zero_row(a.wav_out, a.format, sv.out_off, nT * H, tid0, kThreads);
             b += gridDim.x;
@@ -429,6 +444,16 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(P
                 // the stream reads the old cache side by side; stream_ola_kernel writes both caches afterwards.
                 // (the cache's base and end as values of the loop, not a branch around it: the other instantiations keep their code, and this
                 //  one its spill count)
+                if constexpr (STRM && PIPE) {
+                    // (position t H + n of [old cache_stft | the stream's samples]: inside the cache while t H + n < OVL)
+                    const long long x0 = sv.in_off + (long long)t * H - OVL;
+                    const float* cs0 = cst + t * H;
+                    const int ovl0 = OVL - t * H;
+                    for (int n = tid; n < N; n += kThreads) {
+                        const float v = (n < ovl0) ? cs0[n] : stream_sample(a.wav_in, a.format, x0 + n);
+                        fa[n] = make_float2(v * win[n], 0.0f);
+                    }
+                } else
                 if constexpr (STRM) {
                     const long long x0 = sv.in_off + (long long)t * H - OVL;
                     for (int n = tid; n < N; n += kThreads) {
@@ -820,6 +845,15 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(P
             if (blk == 0) FS_CLK(10);
             if constexpr (PIPE) {
                 // frame t - 1's inter-GRU states of this block: wait for them, fetch them into hprev
+                // No wait depends on a frame the stream does not have (nT frames: a.T offline, STRM the stream's own sv.hops, 1 .. T_max).
+                // Frame 0 does not wait.  Frame t >= 1 polls counter (b, blk) for the value t, which only frame t - 1 publishes; it runs
+                // here only if t < nT, so t - 1 < nT is a frame of the stream, and it belongs to workgroup (t - 1) mod P of the stream,
+                // which exists (the grid has P workgroups per stream) and did not leave at the top: its first frame (t - 1) mod P <= t - 1
+                // < nT.  That workgroup reaches frame t - 1 after its earlier frames t - 1 - P, t - 1 - 2 P, ..., which by induction on the
+                // frame index wait only on frames below them, and frame t - 1's signal of block blk follows from frame t - 2's alone.
+                // nT < P: the workgroups p >= nT have left, nobody polls for their frames (that poll would come from frame p + 1 > nT).
+                // nT not a multiple of P: the last round is short, its frames wait on the frames before them as every other does.  All
+                // workgroups of the launch are co-resident (cooperative launch), so a polled producer is running or has finished.
                 HO::wait(a.pipe_flags + (size_t)b * S::NB, blk, t, tid);      // (tid: the frame loop's copy of the thread index, see above)
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
@@ -1256,7 +1290,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(P
         }
         FS_CLK(7);
     }
-    if constexpr (STRM) {
+    if constexpr (STRM && !PIPE) {      // (the time-pipelined form: the level row is stream_ola_streams_kernel's)
         // the stream's level row, one 16-byte store: the waves' partials through the (idle) transform buffer, wave 0 first
         if (a.levels != nullptr) {
             float* red = reinterpret_cast<float*>(fa);
@@ -1293,6 +1327,9 @@ struct FImpl {
     // per-hop step of large batches: front -> DPE blocks batched over the streams (fspen_sb_kernels.hip.h) -> tail; a.tok / a.carry set
     void (*launch_sb)(const FArgs&, int max_wgs, hipStream_t, hipError_t*);
     size_t split_floats_per_stream;      // tok + carry
+    // the packet step's time-pipelined launch (fe_step_pool_streams_chunk: a.pipe_p workgroups per call stream; cooperative, a refusal leaves no
+    // error behind and names no kernel)
+    hipError_t (*launch_streams_pipe)(const FStreamArgs&, hipStream_t);
 };
 
 // workgroups per CU: LDS- and register-limited (the front, PART 1: its own LDS plan and register budget)
@@ -1306,6 +1343,16 @@ void flaunch_pipe_impl(const FArgs& a, hipStream_t st, hipError_t* err) {
     // (one instantiation: the mode is a run-time value there; a streaming chunk - fe_step_backlog - is named apart)
     const char* name = a.mode == FE_MODE_STREAM ? "fspen_frame_kernel<time-pipelined, streaming>" : "fspen_frame_kernel<time-pipelined>";
     *err = launch_coop<&fspen_frame_kernel<S, false, false, true>>(name, dim3(a.B * a.pipe_p), dim3(kThreads), 0, st, a);
+}
+
+// fe_step_pool_streams_chunk: the PIPE + SLOT + STRM instantiation, n * pipe_p cooperative workgroups
+constexpr KernelNames fpipe_streams_names() { return kernel_names("fspen_frame_kernel", 0, "time-pipelined", "streams"); }
+static_assert(same_text(fpipe_streams_names().s[0], "fspen_frame_kernel<time-pipelined, streams>") &&
+              same_text(fpipe_streams_names().s[3], "fspen_frame_kernel<time-pipelined, streams, pinned, s16>"), "what fe_last_step_kernel reports for it");
+template <class S>
+hipError_t flaunch_streams_pipe_impl(const FStreamArgs& a, hipStream_t st) {
+    static constexpr KernelNames names = fpipe_streams_names();
+    return launch_coop<&fspen_frame_kernel<S, false, false, true, 0, true, true>, true>(baseline_name<true>(names, a), dim3(a.B * a.pipe_p), dim3(kThreads), 0, st, a);
 }
 
 constexpr KernelNames fframe_names(bool slot, bool strm) { return kernel_names("fspen_frame_kernel", 0, "", baseline_flavour(slot, strm)); }
@@ -1354,7 +1401,8 @@ inline void fdbg_stage_impl(int s, int* rows, int* cols, size_t* off) {
 template <class S>
 FImpl make_fimpl() {
     return FImpl{S::HOP, (size_t)FLds::TOTAL * 4, FDebugLayout::total(), FDebugLayout::n_stages, (size_t)FPk::TOTAL, &flaunch_step_impl<S>, &fdbg_stage_impl,
-                 &flaunch_pipe_impl<S>, kFOcc, S::NB, &flaunch_sb_impl<S>, (size_t)2048 + FCarry::FLOATS + 1024};
+                 &flaunch_pipe_impl<S>, kFOcc, S::NB, &flaunch_sb_impl<S>, (size_t)2048 + FCarry::FLOATS + 1024,
+                 &flaunch_streams_pipe_impl<S>};
 }
 
 }  // namespace fe

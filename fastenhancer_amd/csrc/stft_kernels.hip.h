@@ -212,7 +212,9 @@ __global__ void __launch_bounds__(kThreads) stream_ola_kernel(const float* __res
 
 // stream_view (fe_kernels.hip.h) with the hop a run-time value: this file's kernels are not compiled per shape.  The same clamp and the same
 // bounds check, word for word - the frame kernel's workgroups and the audio kernel below must make the same stream of a descriptor.
-__device__ __forceinline__ StreamView stream_view_rt(const StreamFrameArgs& a, int b, int H) {
+// (A: the packet argument block of any family - StreamFrameArgs, BStreamArgs, FStreamArgs: a.B, a.T, a.desc and the two counts.)
+template <class A>
+__device__ __forceinline__ StreamView stream_view_rt(const A& a, int b, int H) {
     StreamView v{-1, 0, 0, 0};
     if (b < a.B) {
         const int* p = reinterpret_cast<const int*>(a.desc + b);
@@ -252,14 +254,23 @@ __global__ void __launch_bounds__(kThreads) zero_counters_kernel(unsigned int* _
 // rows.  The level row: per-thread partials over the thread's own positions in a fixed order, the wave reductions of the frame kernels, the
 // waves' words through LDS, wave 0 first, one 16-byte store (levels_put / levels_store) - no atomics, the same bits on every run.
 // a: the frame kernel's argument block (a.frames [B][a.T][N], a.T = T_max).  wav_in and wav_out do not overlap.
+// A template over that block: FastEnhancer's StreamFrameArgs (fe_step_streams_chunk - the only one with a bank table), and the packet blocks of
+// the families whose time pipeline carries the streaming state (fe_step_pool_streams_chunk: BStreamArgs, FStreamArgs), which name the same
+// fields - audio, the two STFT caches, descriptors, counts, format, capacity, levels, frames.
 constexpr int kOlaTile = 4 * kThreads;
-__global__ void __launch_bounds__(kThreads) stream_ola_streams_kernel(StreamFrameArgs a, int N, int H) {
+template <class A>
+__device__ __forceinline__ int stream_ola_bank(const A& a, const StreamView& sv) {
+    if constexpr (std::is_same<A, StreamFrameArgs>::value) return stream_bank<true>(a, sv);
+    else return 0;
+}
+template <class A>
+__global__ void __launch_bounds__(kThreads) stream_ola_streams_kernel(A a, int N, int H) {
     __shared__ float old_cis[1024], old_cst[1024], tile[kOlaTile], red[4 * kWaves];
     const int b = blockIdx.x, tid = threadIdx.x;
     const StreamView sv = stream_view_rt(a, b, H);
     if (sv.hops == 0) return;                                   // (wave-uniform, as the two below)
     const int sb = sv.slot;
-    if ((unsigned)sb >= (unsigned)a.capacity || stream_bank<true>(a, sv) < 0) {
+    if ((unsigned)sb >= (unsigned)a.capacity || stream_ola_bank(a, sv) < 0) {
         stream_zero_row(a.wav_out, a.format, sv.out_off, sv.hops * H, tid, kThreads);
         return;
     }

@@ -456,12 +456,14 @@ class Engine:
 
     def _step_streams(self, wav_in: Tensor, state: Tensor, capacity: int, desc, wav_out: Tensor, T_max: int, pinned: bool,
                       min_gain: Optional[Tensor] = None, levels: Optional[Tensor] = None, bank: Optional[Tensor] = None, chunk: bool = False,
-                      work: Optional[Tensor] = None, pool: bool = False, pool_ctl: bool = False) -> Tensor:
+                      work: Optional[Tensor] = None, pool: bool = False, pool_ctl: bool = False, pool_chunk: bool = False) -> Tensor:
         """The packet step behind step_streams* / step_streams_chunk* / step_pool_streams*.  pool: fe_step_pool_streams[_pinned], the packet
         step of every family - the same checks of buffers and descriptors; the per-stream controls, the weight banks and the pipelined form
         are FastEnhancer's and are refused here.  pool_ctl: fe_step_pool_streams_ctl[_pinned], that step with the two controls for every
-        family (either table may be None: a NULL)."""
+        family (either table may be None: a NULL).  pool_chunk: fe_step_pool_streams_chunk[_pinned], the pipelined form of pool_ctl - the
+        checks and the scratch of chunk, no bank table."""
         ctl = min_gain is not None or levels is not None or pool_ctl
+        chunk = chunk or pool_chunk
         name = "fe_step_streams" + ("_banked" if bank is not None else "_ctl" if ctl else "") + ("_pinned" if pinned else "")
         if chunk:       # (one entry point, every table an argument that may be NULL)
             name = "fe_step_streams_chunk" + ("_pinned" if pinned else "")
@@ -473,6 +475,9 @@ class Engine:
             name = "fe_step_pool_streams" + ("_pinned" if pinned else "")
         if pool_ctl:
             name = "fe_step_pool_streams_ctl" + ("_pinned" if pinned else "")
+        if pool_chunk:
+            name = "fe_step_pool_streams_chunk" + ("_pinned" if pinned else "")
+        work_query = self.pool_streams_chunk_work_floats if pool_chunk else self.streams_chunk_work_floats
         for what, x in (("wav_in", wav_in), ("wav_out", wav_out)):
             if not isinstance(x, Tensor) or x.dtype not in (torch.float32, torch.int16) or not x.is_contiguous() or x.numel() == 0:
                 raise ValueError(f"{what} must be a contiguous, non-empty float32 or int16 tensor")
@@ -490,21 +495,23 @@ class Engine:
         bank = self._bank_table(bank, capacity)
         if chunk and work is not None:
             if not isinstance(work, Tensor) or work.dtype != torch.float32 or not work.is_contiguous():
-                raise ValueError("work must be a contiguous float32 tensor of streams_chunk_work_floats(n, T_max) floats")
+                raise ValueError(f"work must be a contiguous float32 tensor of {work_query.__name__}(n, T_max) floats")
             # (the windowed frames [n][T_max][N] at least, where the model pipelines at all: known without the library)
             n_desc = desc.shape[0] if isinstance(desc, Tensor) else len(desc)
             c = self.cfg      # (the default, ln and dprnn models: the ring variants, the noncausal model and the baselines never pipeline this call)
             pipelines = hasattr(c, "rf_blocks") and not getattr(c, "dpt", False) and getattr(c, "kernel_size_time", 1) == 1 and not getattr(c, "noncausal", False)
+            if pool_chunk and self.family.pool:       # (the pool call: the families whose time pipeline carries the streaming state - BSRNN, FSPEN)
+                pipelines = self.family.backlog
             if T_max >= 4 and pipelines and work.numel() < n_desc * T_max * c.n_fft:
                 raise ValueError(f"work has {work.numel()} floats, {n_desc} streams of up to {T_max} hops need at least {n_desc * T_max * self.cfg.n_fft} "
-                                 "(streams_chunk_work_floats)")
+                                 f"({work_query.__name__})")
         d = self._stream_desc_tensor(desc, capacity, T_max, wav_in.numel(), wav_out.numel())
         self._require_gpu()
         assert state.is_cuda and state.numel() == self.state_floats(capacity) and state.is_contiguous()
         fmt = _lib.FE_AUDIO_S16 if wav_in.dtype == torch.int16 else _lib.FE_AUDIO_F32
         tables = (_ptr(min_gain), _ptr(levels), _ptr(bank)) if bank is not None else (_ptr(min_gain), _ptr(levels)) if ctl else ()
         if chunk:
-            need = self.streams_chunk_work_floats(d.shape[0], T_max)
+            need = work_query(d.shape[0], T_max)
             if work is None:
                 if need > 0:        # (a scratch tensor kept on the engine, grown when needed; pass `work` inside a graph capture)
                     if getattr(self, "_streams_chunk_work", None) is None or self._streams_chunk_work.numel() < need:
@@ -513,8 +520,8 @@ class Engine:
             elif not work.is_cuda:
                 raise ValueError("work must be a device tensor")
             elif work.numel() < need:
-                raise ValueError(f"work has {work.numel()} floats, streams_chunk_work_floats({d.shape[0]}, {T_max}) is {need}")
-            tables = (_ptr(min_gain), _ptr(levels), _ptr(bank), _ptr(work))
+                raise ValueError(f"work has {work.numel()} floats, {work_query.__name__}({d.shape[0]}, {T_max}) is {need}")
+            tables = (_ptr(min_gain), _ptr(levels), _ptr(work)) if pool_chunk else (_ptr(min_gain), _ptr(levels), _ptr(bank), _ptr(work))
         with torch.cuda.device(self.device):
             _lib.check(getattr(self.lib, name)(self._h, _ptr(wav_in), wav_in.numel(), _ptr(state), int(capacity), _ptr(d), _ptr(wav_out), wav_out.numel(),
                                                d.shape[0], int(T_max), fmt, *tables, _stream(self.device)), name)
@@ -598,6 +605,32 @@ class Engine:
         step_streams_pinned: synchronise the stream before reading wav_out or rewriting wav_in)."""
         return self._step_streams(wav_in, state, capacity, desc, wav_out, T_max, pinned=True, min_gain=min_gain, levels=levels, bank=bank,
                                   chunk=True, work=work)
+
+    # ---- ... for every family with a streaming state (fe_step_pool_streams_chunk[_pinned])
+    def pool_streams_chunk_work_floats(self, n: int, T_max: int) -> int:
+        """fe_step_pool_streams_chunk_work_floats: floats of scratch step_pool_streams_chunk needs for at most n streams of at most T_max
+        hops (0: none - T_max < 4, LiSenNet, the FastEnhancer models whose streams_chunk_work_floats is 0)."""
+        return int(self.lib.fe_step_pool_streams_chunk_work_floats(self._h, int(n), int(T_max)))
+
+    def step_pool_streams_chunk(self, wav_in: Tensor, state: Tensor, capacity: int, desc, wav_out: Tensor, T_max: int, *,
+                                min_gain: Optional[Tensor] = None, levels: Optional[Tensor] = None, work: Optional[Tensor] = None) -> Tensor:
+        """fe_step_pool_streams_chunk: step_pool_streams_ctl(..., min_gain=, levels=) with the hops of EACH stream spread over the time
+        pipeline - the same descriptors, slots, formats, limit and meters, in place on the capacity-sized state.  FastEnhancer's models as
+        step_streams_chunk runs them; BSRNN and FSPEN on the time-pipelined packet form of their frame kernels, results agreeing with
+        step_pool_streams_ctl to fp32 rounding (cache_stft bit for bit); LiSenNet, whose pipeline carries no streaming state, and every
+        call that is not pipelined (T_max < 4, set_time_pipeline(0 | 1), too many streams) as step_pool_streams_ctl itself, bit for bit
+        (last_step_kernel() says which ran).  wav_in and wav_out must not overlap.  work: a float32 device tensor of at least
+        pool_streams_chunk_work_floats(n, T_max) floats (the form for graph capture); None: a scratch tensor kept on the engine, grown
+        when needed."""
+        return self._step_streams(wav_in, state, capacity, desc, wav_out, T_max, pinned=False, min_gain=min_gain, levels=levels, work=work,
+                                  pool_chunk=True)
+
+    def step_pool_streams_chunk_pinned(self, wav_in: Tensor, state: Tensor, capacity: int, desc, wav_out: Tensor, T_max: int, *,
+                                       min_gain: Optional[Tensor] = None, levels: Optional[Tensor] = None, work: Optional[Tensor] = None) -> Tensor:
+        """fe_step_pool_streams_chunk_pinned: step_pool_streams_chunk with wav_in / wav_out in page-locked HOST memory (the completion rule
+        of step_streams_pinned: synchronise the stream before reading wav_out or a pinned levels table, or rewriting wav_in)."""
+        return self._step_streams(wav_in, state, capacity, desc, wav_out, T_max, pinned=True, min_gain=min_gain, levels=levels, work=work,
+                                  pool_chunk=True)
 
     def new_pinned(self, *shape: int, dtype=torch.float32) -> Tensor:
         """a zeroed page-locked host tensor (the audio of the pinned steps)"""

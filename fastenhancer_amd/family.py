@@ -186,6 +186,16 @@ def packet_ctl_step(engine, pinned: bool) -> Callable:
     return engine.step_streams_pinned if pinned else engine.step_streams
 
 
+def packet_chunk_step(engine, pinned: bool) -> Callable:
+    """The engine's call for a packet step whose streams come with a backlog, each stream's hops on the time pipeline
+    (BacklogPacketPool.tick's second launch): step_pool_streams_chunk[_pinned] for BSRNN, FSPEN and LiSenNet - min_gain=, levels= and work=, no
+    bank table - and step_streams_chunk[_pinned] for FastEnhancer and for an engine object without a family description."""
+    fam = _FAMILIES.get(type(getattr(engine, "cfg", None)))
+    if fam is not None and fam.pool:
+        return engine.step_pool_streams_chunk_pinned if pinned else engine.step_pool_streams_chunk
+    return engine.step_streams_chunk_pinned if pinned else engine.step_streams_chunk
+
+
 def pool_family_name(engine) -> Optional[str]:
     """"BSRNN", "FSPEN" or "LiSenNet" for an engine of a family that steps through fe_step_pool / fe_step_pool_streams, else None: what a
     pool names when it refuses a control that is FastEnhancer's (suppression limit, level meters, weight banks, the pipelined packet step)."""

@@ -30,7 +30,7 @@ from torch import Tensor
 
 from . import _lib
 from .engine import Engine
-from .family import chunk_step, packet_ctl_step, packet_step, pool_family_name, slot_step
+from .family import chunk_step, packet_chunk_step, packet_ctl_step, packet_step, pool_family_name, slot_step
 from .resample import Resampler
 
 
@@ -246,7 +246,7 @@ class PacketPool(StreamPool):
     A BSRNN, FSPEN or LiSenNet engine: tick() launches Engine.step_pool_streams_pinned (fe_step_pool_streams_pinned); push, pull, move,
     resize, adopt, export and catch_up work as for FastEnhancer.  The meters, the suppression limit, the weight banks and backlog_hops are
     FastEnhancer's: such a pool refuses them with a ValueError that names the family, before it calls the engine.  (FamilyPacketPool, below,
-    has the meters and the limit for those families too.)"""
+    has the meters and the limit for those families too, BacklogPacketPool backlog_hops as well.)"""
 
     def __init__(self, engine: Engine, capacity: int, ring_hops: int, T_max: int = 1, meters: bool = False, backlog_hops: int = 0):
         self._baseline = pool_family_name(engine)          # "BSRNN" / "FSPEN" / "LiSenNet", or None: the per-stream controls are available
@@ -477,7 +477,8 @@ class PacketPool(StreamPool):
     def tick(self) -> List[Tuple[int, int, int, int]]:
         """One launch (Engine.step_streams_pinned; a BSRNN, FSPEN or LiSenNet engine: Engine.step_pool_streams_pinned) for every open stream
         with at least one complete hop: each advances min(complete hops, hops up to the ring end, T_max); the rest waits for the next tick.  With backlog_hops = K, a stream whose complete hops up to the ring end exceed T_max
-        advances min(complete hops, hops up to the ring end, K) in a second launch on the same stream, on the time pipeline.  Waits once,
+        advances min(complete hops, hops up to the ring end, K) in a second launch on the same stream, on the time pipeline (_backlog_call,
+        its scratch sized by _backlog_work_floats: the two hooks BacklogPacketPool answers for the other families).  Waits once,
         for both (the rings are host memory the caller reads next).  Returns the descriptors (slot, hops, in_offset, out_offset) it
         launched, the ordinary launch's first - [] when no stream had a hop, and then nothing is launched."""
         desc, backlog = [], []
@@ -498,10 +499,10 @@ class PacketPool(StreamPool):
             self._packet_call(ctl)(self.ring_in, self.state, self.capacity, desc, self.ring_out, T_max=self.T_max, **ctl)
         if backlog:
             if self._backlog_work is None:
-                need = self.engine.streams_chunk_work_floats(self.capacity, self.backlog_hops)
+                need = self._backlog_work_floats()(self.capacity, self.backlog_hops)
                 self._backlog_work = torch.empty(max(need, 1), dtype=torch.float32, device=getattr(self.engine, "device", None))
-            self.engine.step_streams_chunk_pinned(self.ring_in, self.state, self.capacity, backlog, self.ring_out, T_max=self.backlog_hops,
-                                                  min_gain=self._gain, levels=self._levels, bank=self._bank, work=self._backlog_work)
+            self._backlog_call()(self.ring_in, self.state, self.capacity, backlog, self.ring_out, T_max=self.backlog_hops,
+                                 min_gain=self._gain, levels=self._levels, bank=self._bank, work=self._backlog_work)
             desc = desc + backlog
         self.engine.synchronize()
         for slot, hops, _, _ in desc:
@@ -512,6 +513,14 @@ class PacketPool(StreamPool):
     def _packet_call(self, ctl: dict):
         """the engine's call for the tick's ordinary launch, given the tables it will be handed"""
         return packet_step(self.engine, pinned=True)
+
+    def _backlog_call(self):
+        """the engine's call for the tick's backlog launch (min_gain=, levels=, bank=, work=)"""
+        return self.engine.step_streams_chunk_pinned
+
+    def _backlog_work_floats(self):
+        """... and the query (n, T_max) that sizes its scratch"""
+        return self.engine.streams_chunk_work_floats
 
     def pull(self, slot: int) -> Tensor:
         """The enhanced int16 samples produced since the last pull (a copy; empty when there are none)."""
@@ -529,8 +538,8 @@ class FamilyPacketPool(PacketPool):
     On a BSRNN, FSPEN or LiSenNet engine tick() launches Engine.step_pool_streams_pinned while neither control is in use - no meters, no
     limit ever set - and Engine.step_pool_streams_ctl_pinned (fe_step_pool_streams_ctl_pinned) otherwise; set_suppression_limit, levels,
     move, resize and adopt carry the two tables as PacketPool does.  There the limit holds each output bin against the input bin,
-    |Y| >= 10^(dB / 20) |X| (the output of these models is not a mask times the input).  Weight banks other than 0 and backlog_hops stay
-    FastEnhancer's and are refused with the family's name; catch_up keeps refusing a slot with a limit."""
+    |Y| >= 10^(dB / 20) |X| (the output of these models is not a mask times the input).  Weight banks other than 0 and backlog_hops are
+    refused with the family's name (backlog_hops for those families: BacklogPacketPool, below); catch_up keeps refusing a slot with a limit."""
 
     _FAMILY_CONTROLS = ("level meters", "suppression limit")
 
@@ -551,6 +560,29 @@ class FamilyPacketPool(PacketPool):
                 and slot in self._open and self._get_gain(slot) != 0.0:
             dst_pool._refuse_baseline("suppression limit")
         return super().move(slot, dst_pool)
+
+
+class BacklogPacketPool(FamilyPacketPool):
+    """A FamilyPacketPool with backlog_hops = K for every family.  On a FastEnhancer engine it is PacketPool, call for call.  On a BSRNN, FSPEN
+    or LiSenNet engine a stream with more than T_max complete hops up to the ring end leaves the tick's ordinary launch and advances up to K
+    hops in a second launch on the same stream, Engine.step_pool_streams_chunk_pinned (fe_step_pool_streams_chunk_pinned: each stream's hops
+    on the time pipeline for BSRNN and FSPEN, the serial packet step for LiSenNet), with its limit and its meters; tick() waits once, for
+    both.  Weight banks other than 0 stay FastEnhancer's and are refused with the family's name."""
+
+    _FAMILY_CONTROLS = FamilyPacketPool._FAMILY_CONTROLS + ("the pipelined packet step",)
+
+    def _refuse_baseline(self, what: str) -> None:
+        if self._baseline is not None and not what.startswith(self._FAMILY_CONTROLS):
+            raise ValueError(f"a BacklogPacketPool of a {self._baseline} engine has no {what}: weight banks are built for the FastEnhancer family")
+
+    def _backlog_call(self):
+        if self._baseline is None:
+            return super()._backlog_call()
+        call = packet_chunk_step(self.engine, pinned=True)
+        return lambda *a, bank=None, **kw: call(*a, **kw)       # (no bank table in that call: such a pool has none)
+
+    def _backlog_work_floats(self):
+        return super()._backlog_work_floats() if self._baseline is None else self.engine.pool_streams_chunk_work_floats
 
 
 class ResampledPacketPool:

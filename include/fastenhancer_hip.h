@@ -349,7 +349,7 @@ int fe_step_streams_ctl_pinned(fe_handle* h, const void* wav_in_host, size_t in_
  *     16-byte store at the end of the stream.  BSRNN's three-launch step (T_max == 1) writes it as two 8-byte halves: the launch that reads
  *     the audio (bsrnn_ov_kernel or PART 1) stores the input half, PART 2 the output half - the one-store promise is NOT made for this step;
  *     the row is complete once `stream` has completed the call.
- *   Weight banks and the pipelined backlog stay FastEnhancer's. */
+ *   Weight banks stay FastEnhancer's.  A stream that comes back with a backlog: fe_step_pool_streams_chunk, below. */
 int fe_step_pool_streams_ctl(fe_handle* h, const void* wav_in_dev, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,
                              void* wav_out_dev, size_t out_count, int n, int T_max, int format, const float* min_gain, fe_stream_levels* levels,
                              void* stream);
@@ -512,6 +512,56 @@ int fe_step_streams_chunk(fe_handle* h, const void* wav_in_dev, size_t in_count,
 int fe_step_streams_chunk_pinned(fe_handle* h, const void* wav_in_host, size_t in_count, float* state_dev, int capacity,
                                  const fe_stream_desc* desc_dev, void* wav_out_host, size_t out_count, int n, int T_max, int format,
                                  const float* min_gain, fe_stream_levels* levels, const int* bank, float* work_dev, void* stream);
+
+/* The packet step's time-pipelined form for EVERY family with a streaming state: fe_step_pool_streams_ctl[_pinned] with the hops of EACH
+ * stream spread over co-resident workgroups instead of walked by one - to fe_step_pool_streams_ctl what fe_step_streams_chunk is to
+ * fe_step_streams_banked.  Same descriptors, slots, formats, limit and meters, in place on the capacity-sized state buffer.
+ *   Meaning: for every stream of the call, what fe_step_pool_streams_ctl[_pinned] gives for the same arguments - the kernel reads the
+ *     descriptors when it runs; hops is clamped to [0, T_max]; a stream whose input or output range leaves [0, count) is skipped like a 0-hop
+ *     stream (checked in the kernel, by every workgroup of the stream and by the audio kernel); a slot outside [0, capacity) gives zero output
+ *     rows, no state write and no level row; min_gain and levels may each be NULL; the int16 conversion rules.
+ *   FastEnhancer family: the call IS fe_step_streams_chunk[_pinned] with bank = NULL and the query IS fe_step_streams_chunk_work_floats - the
+ *     same launch, the same bits, the same refusals; the noncausal model is refused with fe_step's message.  (fe_step_streams_chunk itself
+ *     keeps refusing BSRNN, FSPEN and LiSenNet.)
+ *   BSRNN and FSPEN: the hops of each stream run on P co-resident workgroups - the time-pipelined PACKET instantiation of the family's frame
+ *     kernel: workgroup p of a stream runs its frames p, p + P, ... < hops, the frames exchange only the time-LSTM (h, c) per layer (BSRNN) or
+ *     the inter-GRU states per DPE block (FSPEN), in place at the stream's slot of the caller's state; every frame reads the slot's old
+ *     cache_stft and the stream's samples, applies the stream's limit in the compressed domain and stores its windowed output to work_dev.
+ *     stream_ola_streams_kernel then does each stream's streaming overlap-add, writes its output rows (zero rows for a stream without state),
+ *     both STFT caches and its level row.
+ *     Host checks: those of fe_step_pool_streams_ctl[_pinned] - the same codes, the same wording under this function's name - all before any
+ *       device work, the argument checks before the weights check.  work_dev == NULL where the pipeline would run is FE_ERR_INVALID_ARG (an
+ *       argument check; the message names the query).  The two tables are looked up as fe_step_pool_streams_ctl looks them up.
+ *     Results: output samples and every model-state tensor of the stepped slots agree with fe_step_pool_streams_ctl to fp32 rounding (the
+ *       frames' sums are formed in another order); cache_stft, a copy of input samples, bit for bit; every float of state_dev that belongs to
+ *       a slot the call does not advance keeps its bits; no sample outside the rows the descriptors name is written.  Level rows: in_peak is
+ *       exact, the other three words agree to rounding; a row is formed without atomics in a fixed order - bitwise reproducible from run to
+ *       run at a fixed pipeline width.  The limit touches the output path only: every state tensor but cache_istft holds the bits of the
+ *       unlimited pipelined run.
+ *     Any hop count 0 .. T_max of a stream is served on the pipeline (the host cannot see the descriptors), 1, 2, 3 hops included: there is
+ *       no T * H >= N - H condition - the audio kernel orders every read of a stream's old STFT caches before every write of its new ones.
+ *     work_dev: fe_step_pool_streams_chunk_work_floats(h, n, T_max) floats - the frame counters [n][layers or blocks], rounded up to 4 floats,
+ *       then the windowed frames [n][T_max][N] (fe_step_backlog's layout).  The size depends on the model, n and T_max only and is monotone in
+ *       both; 0 for T_max < 4, for n <= 0 and for a null handle, non-zero for every n >= 1 and T_max >= 4 whatever fe_set_time_pipeline
+ *       says: a buffer sized once serves every setting.
+ *     Width P: that of the family's pipelined fe_offline for n streams of T_max frames (fe_set_time_pipeline; at most the co-resident
+ *       workgroups the n streams leave each other).  P = 0 - T_max < 4, fe_set_time_pipeline(0 or 1), too many streams to give each two
+ *       co-resident workgroups - and a cooperative launch the runtime refuses: the call makes the very launch of
+ *       fe_step_pool_streams_ctl[_pinned], bit for bit, which fe_last_step_kernel shows.
+ *     A linear chain of three kernels on the caller's stream (the counters are zeroed by a small kernel, not a memset node); the call
+ *       allocates nothing and can be captured into a graph.  wav_in and wav_out MUST NOT overlap.
+ *     fe_last_step_kernel on the pipelined path: "bsrnn_frame_kernel<time-pipelined, streams[, pinned][, s16]> + stream_ola_streams_kernel
+ *       [shape xxt]", "fspen_frame_kernel<time-pipelined, streams[, pinned][, s16]> + stream_ola_streams_kernel [shape fspen]" (the counters'
+ *       zeroing is not named).
+ *   LiSenNet: the call is fe_step_pool_streams_ctl[_pinned]'s launch and the work size is 0: its time-pipelined kernel carries no streaming
+ *     state (see fe_step_backlog). */
+size_t fe_step_pool_streams_chunk_work_floats(const fe_handle* h, int n, int T_max);
+int fe_step_pool_streams_chunk(fe_handle* h, const void* wav_in_dev, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,
+                               void* wav_out_dev, size_t out_count, int n, int T_max, int format, const float* min_gain, fe_stream_levels* levels,
+                               float* work_dev, void* stream);
+int fe_step_pool_streams_chunk_pinned(fe_handle* h, const void* wav_in_host, size_t in_count, float* state_dev, int capacity,
+                                      const fe_stream_desc* desc_dev, void* wav_out_host, size_t out_count, int n, int T_max, int format,
+                                      const float* min_gain, fe_stream_levels* levels, float* work_dev, void* stream);
 
 /* Engine of fe_offline for the default and noncausal FastEnhancer models:
  *   FE_OFFLINE_TIME_BATCHED (the default where compiled; the only engine of the noncausal model): the network is cut at the
