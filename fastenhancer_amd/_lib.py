@@ -47,6 +47,13 @@ class fe_resample_desc(ctypes.Structure):
     _fields_ = [("slot", c_int), ("n_in", c_int), ("in_offset", c_longlong), ("out_offset", c_longlong)]
 
 
+class fe_resample_ring_desc(ctypes.Structure):
+    """one stream of fe_resample_rings: state slot, samples consumed now, the element index of element 0 of its input / output ring, and each
+    ring's length and the position of the first sample read / written (40 bytes)"""
+    _fields_ = [("slot", c_int), ("n_in", c_int), ("in_base", c_longlong), ("out_base", c_longlong), ("in_len", c_int), ("in_pos", c_int),
+                ("out_len", c_int), ("out_pos", c_int)]
+
+
 # every symbol include/fastenhancer_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "fe_create": (c_int, [POINTER(fe_config), POINTER(c_void_p)]),
@@ -139,6 +146,10 @@ SYMBOLS = {
                                     c_void_p]),
     "fe_resample_streams_pinned": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_int,
                                            c_int, c_void_p]),
+    "fe_resample_rings": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_int, c_int,
+                                  c_void_p]),
+    "fe_resample_rings_pinned": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_int,
+                                         c_int, c_void_p]),
     "fe_last_error": (c_char_p, []),
     "fe_version": (c_char_p, []),
     "fe_build_key": (c_char_p, []),

@@ -1,4 +1,5 @@
-// fe_api_resample.inc — the host side of the polyphase resampler (fe_resampler_*, fe_resample, fe_resample_streams[_pinned]): the filter
+// fe_api_resample.inc — the host side of the polyphase resampler (fe_resampler_*, fe_resample, fe_resample_streams[_pinned],
+// fe_resample_rings[_pinned]): the filter
 // design, the index arithmetic of the contract (include/fastenhancer_hip.h, "Audio at another sample rate"), the argument checks and the
 // launches of resample_kernels.hip.h (through fe::launch_resample of fe_resample.hip, where the kernels are compiled).  Included by fe_api.hip at file scope, behind the model handle's entry points (it uses their fail,
 // pinned_view and table_view).
@@ -26,6 +27,11 @@ constexpr long long kResampleMaxWorkgroups = 0xffffffffll / fe::kResampleThreads
 static_assert(sizeof(fe_resample_desc) == 24 && sizeof(fe::ResampleDesc) == 24 && offsetof(fe_resample_desc, slot) == offsetof(fe::ResampleDesc, slot) &&
               offsetof(fe_resample_desc, n_in) == offsetof(fe::ResampleDesc, n_in) && offsetof(fe_resample_desc, in_offset) == offsetof(fe::ResampleDesc, in_offset) &&
               offsetof(fe_resample_desc, out_offset) == offsetof(fe::ResampleDesc, out_offset), "fe_resample_desc is the kernel's ResampleDesc");
+static_assert(sizeof(fe_resample_ring_desc) == 40 && sizeof(fe::ResampleRingDesc) == 40 && offsetof(fe_resample_ring_desc, slot) == offsetof(fe::ResampleRingDesc, slot) &&
+              offsetof(fe_resample_ring_desc, n_in) == offsetof(fe::ResampleRingDesc, n_in) && offsetof(fe_resample_ring_desc, in_base) == offsetof(fe::ResampleRingDesc, in_base) &&
+              offsetof(fe_resample_ring_desc, out_base) == offsetof(fe::ResampleRingDesc, out_base) && offsetof(fe_resample_ring_desc, in_len) == offsetof(fe::ResampleRingDesc, in_len) &&
+              offsetof(fe_resample_ring_desc, in_pos) == offsetof(fe::ResampleRingDesc, in_pos) && offsetof(fe_resample_ring_desc, out_len) == offsetof(fe::ResampleRingDesc, out_len) &&
+              offsetof(fe_resample_ring_desc, out_pos) == offsetof(fe::ResampleRingDesc, out_pos), "fe_resample_ring_desc is the kernel's ResampleRingDesc");
 
 // modified Bessel function I0 by its power series (every term positive: relative error of a few ulp for the arguments 0 .. 5 used here)
 double bessel_i0(double x) {
@@ -90,8 +96,12 @@ fe::ResampleArgs resample_args(const fe_resampler* rs, const void* in, int in_fo
     return a;
 }
 
+// fe_resample_streams[_pinned] (Desc = fe_resample_desc) and fe_resample_rings[_pinned] (fe_resample_ring_desc): one set of checks, in one
+// order, with one set of texts; the descriptor type picks the argument block, the launcher and the kernel's name
+template <class Desc>
 int resample_streams(fe_resampler* rs, const char* fn, bool pinned, const void* in, size_t in_count, int in_format, float* state_dev, int capacity,
-                     const fe_resample_desc* desc_dev, void* out, size_t out_count, int out_format, int* produced, int n, int n_in_max, void* stream) {
+                     const Desc* desc_dev, void* out, size_t out_count, int out_format, int* produced, int n, int n_in_max, void* stream) {
+    constexpr bool RING = std::is_same<Desc, fe_resample_ring_desc>::value;
     if (!rs) return fail(FE_ERR_INVALID_ARG, "%s: null resampler", fn);
     if (!in || !state_dev || !desc_dev || !out || n <= 0 || n_in_max <= 0 || capacity < n || in_count == 0 || out_count == 0)
         return fail(FE_ERR_INVALID_ARG, "%s: bad argument (need non-null pointers to at least one element, 1 <= n <= capacity, n_in_max >= 1)", fn);
@@ -114,14 +124,21 @@ int resample_streams(fe_resampler* rs, const char* fn, bool pinned, const void* 
     rc = table_view(produced, (size_t)n * sizeof(int), fn, "produced", &prod_v);
     if (rc == FE_OK) rc = resample_ensure_table(rs, fn);
     if (rc != FE_OK) return rc;
-    fe::ResampleArgs a = resample_args(rs, in_v, in_format, const_cast<void*>(out_v), out_format);
+    typename fe::ResampleKernelArgs<RING>::type a{};
+    static_cast<fe::ResampleArgs&>(a) = resample_args(rs, in_v, in_format, const_cast<void*>(out_v), out_format);
     a.n_in_max = n_in_max;
-    a.desc = reinterpret_cast<const fe::ResampleDesc*>(desc_dev);
     a.in_count = in_count; a.out_count = out_count;
     a.state = state_dev; a.capacity = capacity; a.state_floats = (int)fe_resampler_state_floats(rs);
     a.produced = static_cast<int*>(const_cast<void*>(prod_v));
-    rs->last_kernel = pinned ? "fe_resample_kernel<streams,pinned>" : "fe_resample_kernel<streams>";
-    return launch_rc(fe::launch_resample(true, dim3((unsigned)n), rs->lds_bytes, (hipStream_t)stream, a));
+    if constexpr (RING) {
+        a.ring_desc = reinterpret_cast<const fe::ResampleRingDesc*>(desc_dev);
+        rs->last_kernel = pinned ? "fe_resample_kernel<ring,pinned>" : "fe_resample_kernel<ring>";
+        return launch_rc(fe::launch_resample_rings(dim3((unsigned)n), rs->lds_bytes, (hipStream_t)stream, a));
+    } else {
+        a.desc = reinterpret_cast<const fe::ResampleDesc*>(desc_dev);
+        rs->last_kernel = pinned ? "fe_resample_kernel<streams,pinned>" : "fe_resample_kernel<streams>";
+        return launch_rc(fe::launch_resample(true, dim3((unsigned)n), rs->lds_bytes, (hipStream_t)stream, a));
+    }
 }
 
 }  // namespace
@@ -245,6 +262,20 @@ int fe_resample_streams_pinned(fe_resampler* rs, const void* in, size_t in_count
                                const fe_resample_desc* desc_dev, void* out, size_t out_count, int out_format, int* produced, int n, int n_in_max,
                                void* stream) {
     return resample_streams(rs, "fe_resample_streams_pinned", true, in, in_count, in_format, state_dev, capacity, desc_dev, out, out_count, out_format,
+                            produced, n, n_in_max, stream);
+}
+
+int fe_resample_rings(fe_resampler* rs, const void* in, size_t in_count, int in_format, float* state_dev, int capacity,
+                      const fe_resample_ring_desc* desc_dev, void* out, size_t out_count, int out_format, int* produced, int n, int n_in_max,
+                      void* stream) {
+    return resample_streams(rs, "fe_resample_rings", false, in, in_count, in_format, state_dev, capacity, desc_dev, out, out_count, out_format, produced, n,
+                            n_in_max, stream);
+}
+
+int fe_resample_rings_pinned(fe_resampler* rs, const void* in, size_t in_count, int in_format, float* state_dev, int capacity,
+                             const fe_resample_ring_desc* desc_dev, void* out, size_t out_count, int out_format, int* produced, int n, int n_in_max,
+                             void* stream) {
+    return resample_streams(rs, "fe_resample_rings_pinned", true, in, in_count, in_format, state_dev, capacity, desc_dev, out, out_count, out_format,
                             produced, n, n_in_max, stream);
 }
 

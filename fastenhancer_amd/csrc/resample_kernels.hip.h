@@ -1,4 +1,5 @@
-// resample_kernels.hip.h — polyphase resampling sr_in -> sr_out (fe_resample / fe_resample_streams of the C ABI): one template, two forms.
+// resample_kernels.hip.h — polyphase resampling sr_in -> sr_out (fe_resample / fe_resample_streams / fe_resample_rings of the C ABI): one
+// template, three forms.
 //
 // The contract ("Audio at another sample rate"): up = sr_out / g, down = sr_in / g, R = max(up, down), hl = 10 R, L = 2 hl + 1
 // taps h = up * firwin(L, 1 / R, kaiser 5.0), K = ceil(L / up) taps per output.  Output m:  c = m down + hl, kmax = c div up, r = c mod up,
@@ -16,6 +17,10 @@
 // descriptor is read wave-uniformly (as fe_kernels.hip.h::stream_view reads fe_stream_desc) and checked before anything is read or
 // written; samples before the packet come from the slot's history; the new history and count are written after a barrier behind the last tile.
 // No atomics, no waiting on other workgroups, no cooperative launch.
+// RING (packet streams whose samples live in rings; implies STRM): the STRM form with another descriptor and other addresses, nothing else -
+// sample i of the packet is element in_base + (in_pos + i) mod in_len of a.in, output m of the call element out_base + (out_pos + m) mod
+// out_len of a.out.  A tile's outputs go out as at most two contiguous segments (the split is wave-uniform), each through
+// stream_store_row; the history update reads the packet's last K - 1 samples through the ring index, since they may straddle the wrap.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -29,6 +34,12 @@ constexpr int kResampleThreads = 256;
 struct ResampleDesc {         // = fe_resample_desc of the C ABI (24 bytes)
     int slot, n_in;
     long long in_offset, out_offset;
+};
+
+struct ResampleRingDesc {     // = fe_resample_ring_desc of the C ABI (40 bytes)
+    int slot, n_in;
+    long long in_base, out_base;
+    int in_len, in_pos, out_len, out_pos;
 };
 
 struct ResampleArgs {
@@ -50,14 +61,29 @@ struct ResampleArgs {
     int* produced;            // [n] or null
 };
 
+// The ring form's argument block: ResampleArgs with one field at the end (a.desc is unused).  A type of its own, so that the other two
+// instantiations keep their kernel-argument block - and their code - as they were.
+struct ResampleRingArgs : ResampleArgs {
+    const ResampleRingDesc* ring_desc;   // [n] device memory, read when the kernel runs
+};
+template <bool RING> struct ResampleKernelArgs { using type = ResampleArgs; };
+template <> struct ResampleKernelArgs<true> { using type = ResampleRingArgs; };
+
 // outputs a stream that has consumed N samples has emitted: every output whose newest input has arrived
 __device__ __forceinline__ long long resample_emitted(long long N, int up, int down, int hl) {
     const long long a = N * up - hl;
     return a > 0 ? (a + down - 1) / down : 0;
 }
 
-template <bool STRM>
-__global__ __launch_bounds__(kResampleThreads) void fe_resample_kernel(ResampleArgs a) {
+// position l places behind `pos` in a ring of `len` elements, for 0 <= pos < len and 0 <= l <= len
+__device__ __forceinline__ long long ring_index(int pos, int len, long long l) {
+    const long long p = (long long)pos + l;
+    return p >= len ? p - len : p;
+}
+
+template <bool STRM, bool RING = false>
+__global__ __launch_bounds__(kResampleThreads) void fe_resample_kernel(typename ResampleKernelArgs<RING>::type a) {
+    static_assert(STRM || !RING, "the ring form is a form of the packet-stream form");
     extern __shared__ float rs_lds[];
     const int tid = (int)threadIdx.x;
     const int up = a.up, down = a.down, K = a.K, KP = a.KP;
@@ -70,7 +96,40 @@ __global__ __launch_bounds__(kResampleThreads) void fe_resample_kernel(ResampleA
     long long m_begin = 0, m_end = 0, g0 = 0, in_base = 0, out_base = 0;
     int n = 0;
     float* row = nullptr;
-    if constexpr (STRM) {
+    [[maybe_unused]] int in_len = 0, in_pos = 0, out_len = 0, out_pos = 0;       // RING
+    if constexpr (RING) {
+        const int b = (int)blockIdx.x;
+        const int* p = reinterpret_cast<const int*>(a.ring_desc + b);
+        int w[10];
+#pragma unroll
+        for (int i = 0; i < 10; ++i) w[i] = __builtin_amdgcn_readfirstlane(p[i]);
+        const int slot = w[0];
+        n = w[1] < 0 ? 0 : (w[1] > a.n_in_max ? a.n_in_max : w[1]);
+        in_base = (long long)(((unsigned long long)(unsigned)w[3] << 32) | (unsigned)w[2]);
+        out_base = (long long)(((unsigned long long)(unsigned)w[5] << 32) | (unsigned)w[4]);
+        in_len = w[6]; in_pos = w[7]; out_len = w[8]; out_pos = w[9];
+        long long made = 0;
+        bool ok = (unsigned)slot < (unsigned)a.capacity && in_len >= 1 && out_len >= 1 && (unsigned)in_pos < (unsigned)in_len &&
+                  (unsigned)out_pos < (unsigned)out_len && n <= in_len;
+        if (ok) {
+            row = a.state + (size_t)slot * a.state_floats;
+            const unsigned* cw = reinterpret_cast<const unsigned*>(row + (K - 1));
+            const unsigned lo = __builtin_amdgcn_readfirstlane(cw[0]), hi = __builtin_amdgcn_readfirstlane(cw[1]);
+            g0 = (long long)(((unsigned long long)hi << 32) | lo);
+            ok = g0 >= 0 && g0 < (1ll << 40);                      // (the rule of the STRM form, below)
+        }
+        if (ok) {
+            m_begin = resample_emitted(g0, up, down, a.hl);
+            m_end = resample_emitted(g0 + n, up, down, a.hl);
+            made = m_end - m_begin;
+            // the whole of each ring inside its buffer: then every index base + (pos + i) mod len is
+            const bool in_ok = in_base >= 0 && (unsigned long long)in_base <= a.in_count && a.in_count - (unsigned long long)in_base >= (unsigned long long)in_len;
+            const bool out_ok = out_base >= 0 && (unsigned long long)out_base <= a.out_count && a.out_count - (unsigned long long)out_base >= (unsigned long long)out_len;
+            ok = made <= (long long)out_len && in_ok && out_ok;
+        }
+        if (a.produced != nullptr && tid == 0) a.produced[b] = ok ? (int)made : 0;
+        if (!ok || n == 0) return;              // skipped, or nothing new: nothing read, nothing written, the row as it was
+    } else if constexpr (STRM) {
         const int b = (int)blockIdx.x;
         const int* p = reinterpret_cast<const int*>(a.desc + b);
         int w[6];
@@ -124,7 +183,11 @@ __global__ __launch_bounds__(kResampleThreads) void fe_resample_kernel(ResampleA
         for (int i = tid; i < span; i += kResampleThreads) {
             const long long l = x_lo + i - g0;                     // index into this call's samples
             float v = 0.0f;
-            if (l >= 0 && l < n_sig) v = stream_sample(a.in, a.in_format, in_base + l);
+            if constexpr (RING) {
+                if (l >= 0 && l < n_sig) v = stream_sample(a.in, a.in_format, in_base + ring_index(in_pos, in_len, l));
+            } else {
+                if (l >= 0 && l < n_sig) v = stream_sample(a.in, a.in_format, in_base + l);
+            }
             if constexpr (STRM) {
                 if (l < 0 && l >= -(long long)(K - 1)) v = row[(K - 1) + (int)l];
             }
@@ -142,7 +205,15 @@ __global__ __launch_bounds__(kResampleThreads) void fe_resample_kernel(ResampleA
             Y[t] = acc;
         }
         __syncthreads();
-        stream_store_row(a.out, a.out_format, out_base + (STRM ? m0 - m_begin : 0), Y, cnt, tid, kResampleThreads);
+        if constexpr (RING) {
+            // outputs m0 - m_begin .. of this call: up to the ring's end, then from its start (o and first are wave-uniform)
+            const long long o = ring_index(out_pos, out_len, m0 - m_begin);
+            const int first = (long long)cnt < out_len - o ? cnt : (int)(out_len - o);
+            stream_store_row(a.out, a.out_format, out_base + o, Y, first, tid, kResampleThreads);
+            if (first < cnt) stream_store_row(a.out, a.out_format, out_base, Y + first, cnt - first, tid, kResampleThreads);
+        } else {
+            stream_store_row(a.out, a.out_format, out_base + (STRM ? m0 - m_begin : 0), Y, cnt, tid, kResampleThreads);
+        }
         // (no barrier here: the next tile overwrites X only behind the barrier above, and Y only behind its own first barrier, which no
         // thread passes before every thread has left this store)
     }
@@ -152,7 +223,8 @@ __global__ __launch_bounds__(kResampleThreads) void fe_resample_kernel(ResampleA
         // shifted; staged in LDS so that every old value is read before any is overwritten
         for (int i = tid; i < K - 1; i += kResampleThreads) {
             const long long l = (long long)n - (K - 1) + i;
-            X[i] = l >= 0 ? stream_sample(a.in, a.in_format, in_base + l) : row[(K - 1) + (int)l];
+            if constexpr (RING) X[i] = l >= 0 ? stream_sample(a.in, a.in_format, in_base + ring_index(in_pos, in_len, l)) : row[(K - 1) + (int)l];
+            else X[i] = l >= 0 ? stream_sample(a.in, a.in_format, in_base + l) : row[(K - 1) + (int)l];
         }
         __syncthreads();
         for (int i = tid; i < K - 1; i += kResampleThreads) row[i] = X[i];
@@ -170,9 +242,10 @@ inline size_t resample_lds_floats(int up, int KP, int xcap, int tile_out) {
     return (size_t)((up * KP + 3) & ~3) + (size_t)((xcap + 3) & ~3) + (size_t)((tile_out + 3) & ~3);
 }
 
-// The launcher, defined in fe_resample.hip - the one translation unit that instantiates the two kernels, so that the C-ABI unit, which
-// includes this header for the argument block, carries no device code of them.  Every resampler of the process shares the two kernels, and
+// The launchers, defined in fe_resample.hip - the one translation unit that instantiates the three kernels, so that the C-ABI unit, which
+// includes this header for the argument blocks, carries no device code of them.  Every resampler of the process shares the three kernels, and
 // the opt-in for dynamic LDS is made once per kernel and device: for the most any ratio needs (160 KiB), not for one handle's footprint.
 hipError_t launch_resample(bool strm, dim3 grid, size_t lds_bytes, hipStream_t st, const ResampleArgs& a);
+hipError_t launch_resample_rings(dim3 grid, size_t lds_bytes, hipStream_t st, const ResampleRingArgs& a);
 
 }  // namespace fe

@@ -35,6 +35,8 @@ class Resampler:
         self.taps_per_output = int(self.lib.fe_resampler_taps_per_output(self._h))
         self.half_len = int(self.lib.fe_resampler_half_len(self._h))
         self.state_floats = int(self.lib.fe_resampler_state_floats(self._h))
+        self._desc_pin: Optional[Tensor] = None      # page-locked staging of ring descriptors (_upload_desc)
+        self._desc_event = None
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -136,8 +138,78 @@ class Resampler:
         self._require_gpu()
         return self.pack_desc(rows).to(self.device)
 
-    def _step_streams(self, x: Tensor, state: Tensor, capacity: int, desc, out: Tensor, n_in_max: int, produced: Optional[Tensor], pinned: bool):
-        name = "fe_resample_streams" + ("_pinned" if pinned else "")
+    @staticmethod
+    def pack_ring_desc(rows) -> Tensor:
+        """[(slot, n_in, in_base, out_base, in_len, in_pos, out_len, out_pos), ...] -> a CPU int32 tensor [n, 10], the memory image of n
+        fe_resample_ring_desc"""
+        rows = [tuple(operator.index(v) for v in d) for d in rows]
+        if any(len(r) != 8 for r in rows):
+            raise ValueError("a ring descriptor is (slot, n_in, in_base, out_base, in_len, in_pos, out_len, out_pos)")
+        arr = (_lib.fe_resample_ring_desc * max(len(rows), 1))(*[_lib.fe_resample_ring_desc(*r) for r in rows])
+        words = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.int32).view(-1, 10)
+        return words[:len(rows)].clone()
+
+    @staticmethod
+    def check_ring_desc(rows, capacity: int, n_in_max: int, in_count: int, out_count: int) -> None:
+        """The kernel's rules for ring descriptors, on the host: where the kernel would skip the stream without a word, a ValueError.  Slots in
+        [0, capacity) without duplicates, 0 <= n_in <= n_in_max, each ring at least one element long with its position inside it and the
+        whole of it inside its buffer, n_in <= in_len.  (That the outputs fit, p <= out_len, depends on the stream's count: the kernel's to
+        check, and `produced` says what it found.)"""
+        if not 1 <= len(rows) <= capacity:
+            raise ValueError(f"{len(rows)} streams for a capacity of {capacity}")
+        for slot, n_in, in_base, out_base, in_len, in_pos, out_len, out_pos in rows:
+            if not 0 <= slot < capacity:
+                raise ValueError(f"slot {slot} is outside [0, {capacity})")
+            if not 0 <= n_in <= n_in_max:
+                raise ValueError(f"n_in {n_in} is outside [0, {n_in_max}]")
+            for what, base, length, pos, count in (("input", in_base, in_len, in_pos, in_count), ("output", out_base, out_len, out_pos, out_count)):
+                if length < 1:
+                    raise ValueError(f"slot {slot}: the {what} ring's length {length} is less than 1")
+                if not 0 <= pos < length:
+                    raise ValueError(f"slot {slot}: the {what} ring's position {pos} is outside [0, {length})")
+                if base < 0 or base + length > count:
+                    raise ValueError(f"slot {slot}: the {what} ring [{base}, {base + length}) is outside [0, {count})")
+            if n_in > in_len:
+                raise ValueError(f"slot {slot}: n_in {n_in} is more than the input ring's length {in_len}")
+        if len({r[0] for r in rows}) != len(rows):
+            raise ValueError("duplicate slots")
+
+    def _ring_desc_tensor(self, desc, capacity: int, n_in_max: int, in_count: int, out_count: int) -> Tensor:
+        """_desc_tensor for ring descriptors: a CUDA int32 tensor [n, 10] passes unchecked, a list is checked (check_ring_desc) and copied"""
+        if isinstance(desc, Tensor):
+            if desc.dtype != torch.int32 or desc.dim() != 2 or desc.shape[1] != 10 or not desc.is_contiguous():
+                raise ValueError("a ring descriptor tensor must be a contiguous int32 tensor [n, 10] (Resampler.pack_ring_desc)")
+            if desc.is_cuda:
+                return desc
+            self._require_gpu()
+            return desc.to(self.device)
+        rows = [tuple(operator.index(v) for v in d) for d in desc]
+        if any(len(r) != 8 for r in rows):
+            raise ValueError("a ring descriptor is (slot, n_in, in_base, out_base, in_len, in_pos, out_len, out_pos)")
+        self.check_ring_desc(rows, capacity, n_in_max, in_count, out_count)
+        self._require_gpu()
+        return self._upload_desc(self.pack_ring_desc(rows))
+
+    def _upload_desc(self, words: Tensor) -> Tensor:
+        """CPU descriptor words -> a device tensor, without waiting for the stream (a copy from pageable memory would wait for everything
+        launched before it): staged in a page-locked buffer of the handle's and copied asynchronously on the current stream.  The event
+        keeps the next call from rewriting the staging buffer before this copy has read it."""
+        n = words.shape[0]
+        if self._desc_event is not None:
+            self._desc_event.synchronize()
+        if self._desc_pin is None or self._desc_pin.shape[0] < n:
+            self._desc_pin = torch.empty(max(n, 16), words.shape[1], dtype=torch.int32).pin_memory()
+        self._desc_pin[:n].copy_(words)
+        with torch.cuda.device(self.device):
+            d = self._desc_pin[:n].to(self.device, non_blocking=True)
+            if self._desc_event is None:
+                self._desc_event = torch.cuda.Event()
+            self._desc_event.record(torch.cuda.current_stream(self.device))
+        return d
+
+    def _step_streams(self, x: Tensor, state: Tensor, capacity: int, desc, out: Tensor, n_in_max: int, produced: Optional[Tensor], pinned: bool,
+                      rings: bool = False):
+        name = ("fe_resample_rings" if rings else "fe_resample_streams") + ("_pinned" if pinned else "")
         for what, t in (("x", x), ("out", out)):
             if not isinstance(t, Tensor) or t.dtype not in (torch.float32, torch.int16) or not t.is_contiguous() or t.numel() == 0:
                 raise ValueError(f"{what} must be a contiguous, non-empty float32 or int16 tensor")
@@ -153,7 +225,7 @@ class Resampler:
                 raise ValueError(f"produced must be a contiguous int32 tensor [{n_desc}]")
             if not produced.is_cuda and not (produced.device.type == "cpu" and produced.is_pinned()):
                 raise ValueError("produced must be a device tensor or a CPU tensor in page-locked memory (pin_memory())")
-        d = self._desc_tensor(desc, capacity, n_in_max, x.numel())
+        d = self._ring_desc_tensor(desc, capacity, n_in_max, x.numel(), out.numel()) if rings else self._desc_tensor(desc, capacity, n_in_max, x.numel())
         self._require_gpu()
         if not (isinstance(state, Tensor) and state.is_cuda and state.dtype == torch.float32 and state.is_contiguous()
                 and state.numel() == capacity * self.state_floats):
@@ -174,6 +246,19 @@ class Resampler:
         """fe_resample_streams_pinned: step_streams with x / out in page-locked HOST memory.  Asynchronous on the current stream: synchronise
         it before reading out (or a pinned `produced`) or rewriting x."""
         return self._step_streams(x, state, capacity, desc, out, n_in_max, produced, pinned=True)
+
+    def step_rings(self, x: Tensor, state: Tensor, capacity: int, desc, out: Tensor, n_in_max: int, produced: Optional[Tensor] = None) -> Tensor:
+        """fe_resample_rings: step_streams for streams whose samples live in rings inside x and out.  desc: a list of
+        (slot, n_in, in_base, out_base, in_len, in_pos, out_len, out_pos) - sample i of the packet is x[in_base + (in_pos + i) % in_len],
+        output m of the call out[out_base + (out_pos + m) % out_len]; checked on the host (check_ring_desc: ValueError where the kernel
+        would skip the stream) - or a CUDA int32 tensor [n, 10] (pack_ring_desc), which the kernel alone checks.  A flat buffer is pos = 0
+        with len at least the count."""
+        return self._step_streams(x, state, capacity, desc, out, n_in_max, produced, pinned=False, rings=True)
+
+    def step_rings_pinned(self, x: Tensor, state: Tensor, capacity: int, desc, out: Tensor, n_in_max: int, produced: Optional[Tensor] = None) -> Tensor:
+        """fe_resample_rings_pinned: step_rings with x / out in page-locked HOST memory - the rings of a PacketPool, for one.  Asynchronous on
+        the current stream: synchronise it before reading out (or a pinned `produced`) or rewriting x."""
+        return self._step_streams(x, state, capacity, desc, out, n_in_max, produced, pinned=True, rings=True)
 
     def new_pinned(self, *shape: int, dtype=torch.float32) -> Tensor:
         self._require_gpu()

@@ -17,7 +17,14 @@ state buffer), adopt() opens slots for records made elsewhere, move() takes a li
 config, on another GPU if need be - and resize() grows or shrinks a pool in place.  PacketPool carries the stream's rings along.
 
 ResampledPacketPool: a PacketPool behind two polyphase resamplers (fastenhancer_amd.resample) for clients at another sample rate - a
-telephone leg at 8 kHz, a WebRTC leg at 48 kHz: push() and pull() speak the client's rate, the model runs at its own."""
+telephone leg at 8 kHz, a WebRTC leg at 48 kHz: push() and pull() speak the client's rate, the model runs at its own.  It uses the inner
+pool's public methods only: model-rate audio passes through two staging buffers on the host, and a tick waits three times.
+
+RingResampledPacketPool: the same surface and, call for call, the same samples, with the two resamplers reading and writing the inner
+pool's rings themselves (Resampler.step_rings_pinned: descriptors that address a ring, with wrap-around).  tick() chains the launch to the
+model's rate, the inner pool's launches (PacketPool._enqueue) and the launch back to the client's rate on one stream and waits once; no
+model-rate audio is copied on the host.  Any PacketPool class may be the inner pool (pool=FamilyPacketPool, BacklogPacketPool).  What
+remains for later: the filter fused into the frame kernels' own sample reads and row stores."""
 from __future__ import annotations
 
 import math
@@ -463,16 +470,30 @@ class PacketPool(StreamPool):
         x = torch.as_tensor(pcm)
         if x.dim() != 1 or x.dtype != torch.int16:
             raise ValueError(f"a packet is a 1-D int16 array, got {x.dtype} {tuple(x.shape)}")
-        n, w = x.numel(), self._pushed[slot]
-        if w + n - self._pulled[slot] > self.ring:
-            raise OverflowError(f"slot {slot}: {n} samples do not fit - the ring holds {self.ring} samples between pull() and push(), "
-                                f"{w - self._pulled[slot]} are in it")
-        pos = w % self.ring
+        n = x.numel()
+        pos = self._reserve_push(slot, n)
         first = min(n, self.ring - pos)
         self.ring_in[slot, pos:pos + first] = x[:first]
         if first < n:
             self.ring_in[slot, :n - first] = x[first:]
+
+    def _reserve_push(self, slot: int, n: int) -> int:
+        """The input ring's bookkeeping for n new samples: OverflowError, and nothing taken, when they would overwrite samples not yet pulled;
+        else the slot has pushed n more, and the ring position of the first of them is returned (they wrap at the ring end).  Whoever calls
+        this writes the samples there before the next tick: push(), or a launch that writes into the ring (RingResampledPacketPool)."""
+        w = self._pushed[slot]
+        if w + n - self._pulled[slot] > self.ring:
+            raise OverflowError(f"slot {slot}: {n} samples do not fit - the ring holds {self.ring} samples between pull() and push(), "
+                                f"{w - self._pulled[slot]} are in it")
         self._pushed[slot] = w + n
+        return w % self.ring
+
+    def _reserve_pull(self, slot: int) -> Tuple[int, int]:
+        """The output ring's bookkeeping for everything stepped since the last pull: (ring position of the first sample, count) - they wrap at
+        the ring end - and the slot has pulled them."""
+        r, n = self._pulled[slot], self._stepped[slot] - self._pulled[slot]
+        self._pulled[slot] = r + n
+        return r % self.ring, n
 
     def tick(self) -> List[Tuple[int, int, int, int]]:
         """One launch (Engine.step_streams_pinned; a BSRNN, FSPEN or LiSenNet engine: Engine.step_pool_streams_pinned) for every open stream
@@ -480,7 +501,17 @@ class PacketPool(StreamPool):
         advances min(complete hops, hops up to the ring end, K) in a second launch on the same stream, on the time pipeline (_backlog_call,
         its scratch sized by _backlog_work_floats: the two hooks BacklogPacketPool answers for the other families).  Waits once,
         for both (the rings are host memory the caller reads next).  Returns the descriptors (slot, hops, in_offset, out_offset) it
-        launched, the ordinary launch's first - [] when no stream had a hop, and then nothing is launched."""
+        launched, the ordinary launch's first - [] when no stream had a hop, and then nothing is launched.
+        (Two parts, _enqueue and _complete, with the wait between them: a pool that chains launches of its own in front of and behind
+        these - RingResampledPacketPool - calls the parts and waits once for all of them.)"""
+        desc = self._enqueue()
+        if desc:
+            self.engine.synchronize()
+        self._complete(desc)
+        return desc
+
+    def _enqueue(self) -> List[Tuple[int, int, int, int]]:
+        """tick()'s descriptors and its one or two launches, without the wait; returns the descriptors launched"""
         desc, backlog = [], []
         for slot in sorted(self._open):
             pos = self._stepped[slot] % self.ring
@@ -504,11 +535,13 @@ class PacketPool(StreamPool):
             self._backlog_call()(self.ring_in, self.state, self.capacity, backlog, self.ring_out, T_max=self.backlog_hops,
                                  min_gain=self._gain, levels=self._levels, bank=self._bank, work=self._backlog_work)
             desc = desc + backlog
-        self.engine.synchronize()
+        return desc
+
+    def _complete(self, desc) -> None:
+        """the counters follow what _enqueue launched, once the stream has been waited for"""
         for slot, hops, _, _ in desc:
             self._stepped[slot] += hops * self.H
             self._level_samples[slot] = hops * self.H
-        return desc
 
     def _packet_call(self, ctl: dict):
         """the engine's call for the tick's ordinary launch, given the tables it will be handed"""
@@ -525,12 +558,9 @@ class PacketPool(StreamPool):
     def pull(self, slot: int) -> Tensor:
         """The enhanced int16 samples produced since the last pull (a copy; empty when there are none)."""
         self._check_open(slot)
-        r, n = self._pulled[slot], self._stepped[slot] - self._pulled[slot]
-        pos = r % self.ring
+        pos, n = self._reserve_pull(slot)
         first = min(n, self.ring - pos)
-        out = torch.cat([self.ring_out[slot, pos:pos + first], self.ring_out[slot, :n - first]])
-        self._pulled[slot] = r + n
-        return out
+        return torch.cat([self.ring_out[slot, pos:pos + first], self.ring_out[slot, :n - first]])
 
 
 class FamilyPacketPool(PacketPool):
@@ -595,8 +625,9 @@ class ResampledPacketPool:
       3. inner.tick();
       4. inner.pull of every slot;
       5. one Resampler.step_streams_pinned launch back to the client's rate.
-    That is three launches and two host hops a tick, where PacketPool has one launch: resampling into the rings inside the packet step
-    itself is left for later.  Both resamplers are streaming-exact across packets (the outputs are those of one call on the whole signal),
+    That is three launches and two host hops a tick, where PacketPool has one launch: RingResampledPacketPool, below, resamples straight
+    into and out of the inner pool's rings and waits once (this class is its oracle, and the form that needs nothing but the inner pool's
+    public methods); fusing the filter into the frame kernels themselves is left for later.  Both resamplers are streaming-exact across packets (the outputs are those of one call on the whole signal),
     each with its own latency of half_len / up input samples; nothing is flushed when a slot closes.
     model_rate: the engine's configuration does not carry a sample rate - 16000 for the 16 kHz configurations, 48000 for the 48 kHz ones."""
 
@@ -732,3 +763,117 @@ class ResampledPacketPool:
         self._check_open(slot)
         parts, self._ready[slot] = self._ready[slot], []
         return torch.cat(parts) if parts else torch.zeros(0, dtype=torch.int16)
+
+
+class RingResampledPacketPool(ResampledPacketPool):
+    """ResampledPacketPool with the two resamplers reading and writing the inner pool's rings themselves (Resampler.step_rings_pinned,
+    fe_resample_rings_pinned): no model-rate audio is copied on the host, and a tick waits once.  The surface is ResampledPacketPool's -
+    open, close, push, tick, pull, active, inner, to_model, to_client, state_in, state_out, the _make_pool / _make_resampler hooks - and
+    `pool` names the inner pool's class: PacketPool, FamilyPacketPool or BacklogPacketPool, built with **pool_kwargs (meters=, backlog_hops=).
+    Limits, meters, banks and backlogs are used through `inner`, whose slots are this pool's.
+    It owns two page-locked client-rate staging buffers ([capacity, max_packet] in, [capacity, client_cap] out) and two page-locked
+    `produced` tables, and NO model-rate staging.  tick():
+      1. for every open slot with pending samples the host computes made = to_model.produced(consumed, n) and reserves `made` samples in the
+         inner input ring (PacketPool._reserve_push; push() has checked that they fit); one to_model.step_rings_pinned launch from the flat
+         client staging into inner.ring_in at the reserved ring positions - the outputs wrap with the ring;
+      2. inner._enqueue(): the inner pool's descriptors, which see the samples of step 1, and its one or two launches;
+      3. for every stream those advanced, one to_client.step_rings_pinned launch from inner.ring_out, hops * H samples at the stream's pull
+         position, into the flat client staging;
+      4. ONE synchronize();
+      5. inner._complete() and the inner pull counters (PacketPool._reserve_pull);
+      6. both `produced` tables against the host's predictions: RuntimeError as ResampledPacketPool raises it, the counters describing what
+         the launches consumed;
+      7. the ready client-rate samples are appended per slot.
+    All launches are on the current stream, and no descriptor depends on a device result: how many samples a stream emits for its next n is a
+    host function (fe_resampler_produced), and the hop schedule follows from host counters.
+    The contract: for the same sequence of open / push / tick / pull / close calls every pull() returns the int16 samples
+    ResampledPacketPool returns, bit for bit, tick() returns the same list, and state_in / state_out hold the same rows - both pools round to
+    int16 at the model's rate, the resampler is packetisation-exact, and the hop schedule is a function of host counters only.
+    Not here: device-resident rings; the filter fused into the frame kernels' stream_sample / stream_store_row; move / resize / export of a
+    resampled pool; a flush on close()."""
+
+    def __init__(self, engine: Engine, capacity: int, ring_hops: int, client_rate: int, T_max: int = 1, max_packet: Optional[int] = None, *,
+                 model_rate: int = 16000, pool=PacketPool, **pool_kwargs):
+        client_rate, model_rate = operator.index(client_rate), operator.index(model_rate)
+        if client_rate == model_rate:
+            raise ValueError(f"client_rate {client_rate} is the model's rate: there is nothing to resample, use PacketPool")
+        device = getattr(engine, "device", None)
+        self.client_rate, self.model_rate = client_rate, model_rate
+        self.to_model = self._make_resampler(client_rate, model_rate, device)
+        self.to_client = self._make_resampler(model_rate, client_rate, device)
+        self.inner = self._make_pool(engine, capacity, ring_hops, T_max, pool, **pool_kwargs)
+        self.capacity = int(capacity)
+        # model-rate samples a slot advances per tick at most: T_max hops, or a backlog launch's
+        step = max(int(self.inner.T_max), int(getattr(self.inner, "backlog_hops", 0))) * int(self.inner.H)
+        if max_packet is None:                                             # what an ordinary tick can take away, at the client's rate
+            max_packet = -(-int(self.inner.T_max) * int(self.inner.H) * client_rate // model_rate)
+        self.max_packet = operator.index(max_packet)
+        if self.max_packet < 1:
+            raise ValueError("max_packet must be at least 1")
+        self._client_cap = self.to_client.out_count(step) + 1             # client-rate samples of one tick's output at most
+        self._step = step
+        self.state_in = self.to_model.new_state(self.capacity)
+        self.state_out = self.to_client.new_state(self.capacity)
+        self._cin = self.to_model.new_pinned(self.capacity, self.max_packet, dtype=torch.int16)
+        self._cout = self.to_client.new_pinned(self.capacity, self._client_cap, dtype=torch.int16)
+        self._made_in = self.to_model.new_pinned(self.capacity, dtype=torch.int32)
+        self._made_out = self.to_client.new_pinned(self.capacity, dtype=torch.int32)
+        self._pending = [0] * self.capacity          # client-rate samples waiting in _cin
+        self._consumed = [0] * self.capacity         # client-rate samples the resampler to the model's rate has consumed
+        self._fill = [0] * self.capacity             # model-rate samples in the inner pool's rings: reserved and not yet pulled
+        self._returned = [0] * self.capacity         # model-rate samples the resampler to the client's rate has consumed
+        self._ready: List[List[Tensor]] = [[] for _ in range(self.capacity)]
+        self._open = set()
+
+    @staticmethod
+    def _make_pool(engine, capacity, ring_hops, T_max, pool=PacketPool, **pool_kwargs) -> PacketPool:
+        return pool(engine, capacity, ring_hops, T_max=T_max, **pool_kwargs)
+
+    def _fresh(self, slot: int) -> None:
+        super()._fresh(slot)
+        self._returned[slot] = 0
+
+    def tick(self) -> List[Tuple[int, int, int, int]]:
+        """The seven steps above: up to three launches (four with a backlog) and one wait.  Returns what inner.tick() would have returned."""
+        inner, ring = self.inner, self.inner.ring
+        todo, due_in = [], []
+        for slot in sorted(self._open):
+            n = self._pending[slot]
+            if n > 0:
+                made = self.to_model.produced(self._consumed[slot], n)
+                pos = inner._reserve_push(slot, made)                     # (push() has checked that the ring holds them)
+                todo.append((slot, n, slot * self.max_packet, slot * ring, self.max_packet, 0, ring, pos))
+                due_in.append(made)
+        if todo:
+            self.to_model.step_rings_pinned(self._cin, self.state_in, self.capacity, todo, inner.ring_in, self.max_packet,
+                                            produced=self._made_in[:len(todo)])
+        launched = inner._enqueue()
+        back = [(slot, hops * inner.H, slot * ring, slot * self._client_cap, ring, inner._pulled[slot] % ring, self._client_cap, 0)
+                for slot, hops, _, _ in sorted(launched)]
+        due_out = [self.to_client.produced(self._returned[slot], n) for slot, n, *_ in back]
+        if back:
+            self.to_client.step_rings_pinned(inner.ring_out, self.state_out, self.capacity, back, self._cout, self._step,
+                                             produced=self._made_out[:len(back)])
+        if todo or launched:
+            inner.engine.synchronize()
+        inner._complete(launched)
+        # the launches have consumed every stream's samples: the counters follow them for all streams before anything can raise
+        for (slot, n, *_), made in zip(todo, due_in):
+            self._consumed[slot] += n
+            self._pending[slot] = 0
+            self._fill[slot] += made
+        for slot, n, *_ in back:
+            inner._reserve_pull(slot)
+            self._fill[slot] -= n
+            self._returned[slot] += n
+        for i, ((slot, n, *_), due) in enumerate(zip(todo, due_in)):
+            made = int(self._made_in[i])
+            if made != due:
+                raise RuntimeError(f"slot {slot}: the resampler made {made} samples of {n}, {due} were due")
+        for i, ((slot, n, *_), due) in enumerate(zip(back, due_out)):
+            made = int(self._made_out[i])
+            if made != due:
+                raise RuntimeError(f"slot {slot}: the resampler made {made} samples of {n}, {due} were due")
+            if made:
+                self._ready[slot].append(self._cout[slot, :made].clone())
+        return launched

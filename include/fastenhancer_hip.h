@@ -786,6 +786,28 @@ int fe_resample_streams_pinned(fe_resampler* rs, const void* in, size_t in_count
                                const fe_resample_desc* desc_dev, void* out, size_t out_count, int out_format, int* produced, int n, int n_in_max,
                                void* stream);
 
+/* The ring form of fe_resample_streams: the same call - state rows, n_in clamped to [0, n_in_max], p = M(consumed + n_in) - M(consumed)
+ * outputs, produced, the _pinned twin, the same refusals in the same order - for streams whose samples live in RINGS inside the flat
+ * buffers, such as the page-locked rings of a packet pool: sample i of a stream's input is element in_base + (in_pos + i) mod in_len of in,
+ * output m of this call is element out_base + (out_pos + m) mod out_len of out; a packet and its outputs may wrap.  A flat buffer is the
+ * special case pos = 0 with len at least the count.  The outputs are, bit for bit, those of fe_resample_streams on the same samples.
+ * A stream is SKIPPED - nothing read, nothing written, its row untouched, produced[i] = 0 - unless its slot is in [0, capacity), its stored
+ * count is one, in_len >= 1 and out_len >= 1, 0 <= in_pos < in_len and 0 <= out_pos < out_len, n_in <= in_len and p <= out_len, and the
+ * whole of each ring, [base, base + len), lies inside [0, count) of its buffer.  No element outside a stream's ranges is written.
+ * fe_resampler_last_kernel reports fe_resample_kernel<ring> or <ring,pinned>. */
+typedef struct fe_resample_ring_desc {   /* 40 bytes */
+    int slot, n_in;
+    long long in_base, out_base;         /* element index of ring element 0 in in / out */
+    int in_len, in_pos;                  /* ring length in elements; position of the first sample read, 0 <= in_pos < in_len */
+    int out_len, out_pos;                /* ...; position of the first output written */
+} fe_resample_ring_desc;
+int fe_resample_rings(fe_resampler* rs, const void* in, size_t in_count, int in_format, float* state_dev, int capacity,
+                      const fe_resample_ring_desc* desc_dev, void* out, size_t out_count, int out_format, int* produced, int n, int n_in_max,
+                      void* stream);
+int fe_resample_rings_pinned(fe_resampler* rs, const void* in, size_t in_count, int in_format, float* state_dev, int capacity,
+                             const fe_resample_ring_desc* desc_dev, void* out, size_t out_count, int out_format, int* produced, int n, int n_in_max,
+                             void* stream);
+
 const char* fe_last_error(void);
 const char* fe_version(void);
 /* r6: the digest of the sources this library was built from (fastenhancer_amd/build.py::source_key: csrc/* and this header).  The Python binding refuses an
