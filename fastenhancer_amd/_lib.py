@@ -20,6 +20,7 @@ FE_STEP_KERNEL_WAVES4, FE_STEP_KERNEL_WG8, FE_STEP_KERNEL_WG8_PERSIST = 0, 1, 2
 FE_ACT_SILU, FE_ACT_RELU, FE_ACT_LEAKY_RELU, FE_ACT_ELU, FE_ACT_GELU, FE_ACT_GELU_TANH = 0, 1, 2, 3, 4, 5
 FE_MASK_NONE, FE_MASK_SIGMOID, FE_MASK_TANH = 0, 1, 2
 FE_AUDIO_F32, FE_AUDIO_S16 = 0, 1
+FE_AUDIO_ULAW, FE_AUDIO_ALAW = 4, 5          # G.711, one byte per sample: formats of the resampler only
 
 
 class fe_config(ctypes.Structure):

@@ -56,10 +56,21 @@ long long resample_emitted(const fe_resampler* rs, long long N) {
     return a > 0 ? (a + rs->down - 1) / rs->down : 0;
 }
 
+static_assert(FE_AUDIO_ULAW == fe::kAudioUlaw && FE_AUDIO_ALAW == fe::kAudioAlaw, "the G.711 format codes are the kernel's");
+
+bool resample_is_g711(int format) { return format == FE_AUDIO_ULAW || format == FE_AUDIO_ALAW; }
+
 int resample_check_format(const char* fn, const char* what, int format) {
-    if (format != FE_AUDIO_F32 && format != FE_AUDIO_S16)
-        return fail(FE_ERR_INVALID_ARG, "%s: %s %d is neither FE_AUDIO_F32 (0) nor FE_AUDIO_S16 (1)", fn, what, format);
+    if (format != FE_AUDIO_F32 && format != FE_AUDIO_S16 && !resample_is_g711(format))
+        return fail(FE_ERR_INVALID_ARG, "%s: %s %d is neither FE_AUDIO_F32 (0) nor FE_AUDIO_S16 (1), nor FE_AUDIO_ULAW (4) or FE_AUDIO_ALAW (5)", fn, what,
+                    format);
     return FE_OK;
+}
+
+// the page-locked range lookup for a buffer of `format`: elements of 4, 2 or 1 bytes
+auto resample_pinned_view(int format) -> int (*)(const void*, size_t, const char*, const char*, const void**) {
+    if (resample_is_g711(format)) return &pinned_view<unsigned char>;
+    return format == FE_AUDIO_S16 ? &pinned_view<short> : &pinned_view<float>;
 }
 
 // the first launch of a handle: the tap table goes to the current device
@@ -114,8 +125,7 @@ int resample_streams(fe_resampler* rs, const char* fn, bool pinned, const void* 
     const void* in_v = in;
     const void* out_v = out;
     if (pinned) {
-        const auto vin = in_format == FE_AUDIO_S16 ? &pinned_view<short> : &pinned_view<float>;
-        const auto vout = out_format == FE_AUDIO_S16 ? &pinned_view<short> : &pinned_view<float>;
+        const auto vin = resample_pinned_view(in_format), vout = resample_pinned_view(out_format);
         rc = vin(in, in_count, fn, "in", &in_v);
         if (rc == FE_OK) rc = vout(out, out_count, fn, "out", &out_v);
         if (rc != FE_OK) return rc;
@@ -130,14 +140,17 @@ int resample_streams(fe_resampler* rs, const char* fn, bool pinned, const void* 
     a.in_count = in_count; a.out_count = out_count;
     a.state = state_dev; a.capacity = capacity; a.state_floats = (int)fe_resampler_state_floats(rs);
     a.produced = static_cast<int*>(const_cast<void*>(prod_v));
+    const bool g711 = resample_is_g711(in_format) || resample_is_g711(out_format);      // (the instantiation that knows the byte formats)
     if constexpr (RING) {
         a.ring_desc = reinterpret_cast<const fe::ResampleRingDesc*>(desc_dev);
-        rs->last_kernel = pinned ? "fe_resample_kernel<ring,pinned>" : "fe_resample_kernel<ring>";
-        return launch_rc(fe::launch_resample_rings(dim3((unsigned)n), rs->lds_bytes, (hipStream_t)stream, a));
+        if (g711) rs->last_kernel = pinned ? "fe_resample_kernel<ring,pinned,g711>" : "fe_resample_kernel<ring,g711>";
+        else rs->last_kernel = pinned ? "fe_resample_kernel<ring,pinned>" : "fe_resample_kernel<ring>";
+        return launch_rc(fe::launch_resample_rings(g711, dim3((unsigned)n), rs->lds_bytes, (hipStream_t)stream, a));
     } else {
         a.desc = reinterpret_cast<const fe::ResampleDesc*>(desc_dev);
-        rs->last_kernel = pinned ? "fe_resample_kernel<streams,pinned>" : "fe_resample_kernel<streams>";
-        return launch_rc(fe::launch_resample(true, dim3((unsigned)n), rs->lds_bytes, (hipStream_t)stream, a));
+        if (g711) rs->last_kernel = pinned ? "fe_resample_kernel<streams,pinned,g711>" : "fe_resample_kernel<streams,g711>";
+        else rs->last_kernel = pinned ? "fe_resample_kernel<streams,pinned>" : "fe_resample_kernel<streams>";
+        return launch_rc(fe::launch_resample(true, g711, dim3((unsigned)n), rs->lds_bytes, (hipStream_t)stream, a));
     }
 }
 
@@ -248,8 +261,9 @@ int fe_resample(fe_resampler* rs, const void* in_dev, size_t in_stride, int in_f
     fe::ResampleArgs a = resample_args(rs, in_dev, in_format, out_dev, out_format);
     a.n_in = n_in; a.n_out = n_out;
     a.in_stride = in_stride; a.out_stride = out_stride;
-    rs->last_kernel = "fe_resample_kernel<whole>";
-    return launch_rc(fe::launch_resample(false, dim3((unsigned)tiles, (unsigned)B), rs->lds_bytes, (hipStream_t)stream, a));
+    const bool g711 = resample_is_g711(in_format) || resample_is_g711(out_format);
+    rs->last_kernel = g711 ? "fe_resample_kernel<whole,g711>" : "fe_resample_kernel<whole>";
+    return launch_rc(fe::launch_resample(false, g711, dim3((unsigned)tiles, (unsigned)B), rs->lds_bytes, (hipStream_t)stream, a));
 }
 
 int fe_resample_streams(fe_resampler* rs, const void* in, size_t in_count, int in_format, float* state_dev, int capacity, const fe_resample_desc* desc_dev,

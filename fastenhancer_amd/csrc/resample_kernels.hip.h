@@ -21,6 +21,9 @@
 // sample i of the packet is element in_base + (in_pos + i) mod in_len of a.in, output m of the call element out_base + (out_pos + m) mod
 // out_len of a.out.  A tile's outputs go out as at most two contiguous segments (the split is wave-uniform), each through
 // stream_store_row; the history update reads the packet's last K - 1 samples through the ring index, since they may straddle the wrap.
+// G711 (any form): the instantiations the host launches where either format of the call is a G.711 law (FE_AUDIO_ULAW / FE_AUDIO_ALAW, one
+// byte per sample).  They load and store through helpers of this file that dispatch over all four formats; the instantiations without it
+// keep stream_sample / stream_store_row, their argument blocks and their code.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -81,7 +84,94 @@ __device__ __forceinline__ long long ring_index(int pos, int len, long long l) {
     return p >= len ? p - len : p;
 }
 
-template <bool STRM, bool RING = false>
+// ---- G.711 (FE_AUDIO_ULAW / FE_AUDIO_ALAW of the C ABI: one unsigned byte per sample).  The formulas are the contract's (INTEGRATION.md,
+// "Audio at another sample rate"), in integer ALU operations: no table, no LDS, no barrier.
+constexpr int kAudioUlaw = 4, kAudioAlaw = 5;
+
+__device__ __forceinline__ int g711_ulaw_dec(int b) {
+    const int u = ~b & 0xFF, e = (u >> 4) & 7, m = u & 15;
+    const int mag = (((m << 3) + 0x84) << e) - 0x84;
+    return (u & 0x80) ? -mag : mag;
+}
+__device__ __forceinline__ int g711_alaw_dec(int b) {
+    const int a = b ^ 0x55, e = (a >> 4) & 7, m = a & 15;
+    const int mag = e == 0 ? (m << 4) + 8 : ((m << 4) + 0x108) << (e - 1);
+    return (a & 0x80) ? mag : -mag;
+}
+// q: an int16 value (pcm16_out).  hibit(v) = 31 - clz(v) of a value that is never 0: v >= 33 here, n | 256 >= 256 below (where n < 256
+// the exponent so computed is not used)
+__device__ __forceinline__ int g711_ulaw_enc(int q) {
+    int v = q >> 2;
+    const int mask = v < 0 ? 0x7F : 0xFF;
+    v = v < 0 ? -v : v;
+    v = (v < 8159 ? v : 8159) + 33;
+    const int seg = 31 - __builtin_clz((unsigned)v) - 5;
+    const int t = seg >= 8 ? 0x7F : (seg << 4) | ((v >> (seg + 1)) & 15);
+    return t ^ mask;
+}
+__device__ __forceinline__ int g711_alaw_enc(int q) {
+    const int n = q >= 0 ? q : ~q, sign = q >= 0 ? 0x80 : 0;
+    const int eh = 31 - __builtin_clz((unsigned)(n | 256)) - 7;
+    const int e = n < 256 ? 0 : eh;
+    const int m = n < 256 ? n >> 4 : (n >> (eh + 3)) & 15;
+    return (sign | (e << 4) | m) ^ 0x55;
+}
+template <bool ALAW>
+__device__ __forceinline__ int g711_enc(float y) { return ALAW ? g711_alaw_enc(pcm16_out(y)) : g711_ulaw_enc(pcm16_out(y)); }
+
+// sample `idx` of the input in any of the four formats (a wave-uniform branch); a G.711 byte is the int16 sample it decodes to
+__device__ __forceinline__ float resample_sample_g711(const void* base, int format, long long idx) {
+    if (format == kAudioUlaw) return (float)g711_ulaw_dec(static_cast<const unsigned char*>(base)[idx]) * (1.0f / 32768.0f);
+    if (format == kAudioAlaw) return (float)g711_alaw_dec(static_cast<const unsigned char*>(base)[idx]) * (1.0f / 32768.0f);
+    return stream_sample(base, format, idx);
+}
+
+// n samples from src (LDS) to the BYTES out .. out + n of a G.711 output, as head / body / tail: single bytes up to the first 16-byte
+// boundary of the destination, then sixteen samples per lane packed into one non-temporal 16-byte store, then single bytes.  A one-byte
+// store per lane is a one-byte write on the bus where the destination is page-locked host memory; with byte elements a row's base is
+// 16-byte aligned one time in sixteen, hence the head.  The split depends on the address and the length only (wave-uniform), and no store
+// covers a byte outside [out, out + n).  (Vector stores only.)
+template <bool ALAW>
+__device__ __forceinline__ void g711_store_row(unsigned char* out, const float* src, int n, int tid, int nth) {
+    const int to_boundary = (int)((16u - (unsigned)(reinterpret_cast<size_t>(out) & 15)) & 15u);
+    const int head = to_boundary < n ? to_boundary : n;
+    for (int i = tid; i < head; i += nth) __builtin_nontemporal_store((unsigned char)g711_enc<ALAW>(src[i]), out + i);
+#ifdef FE_G711_BYTE_BODY       // (a side build for tools/gpu_g711_timing.py: the whole row as single bytes)
+    const int n16 = 0;
+#else
+    const int n16 = (n - head) >> 4;
+#endif
+    i32x4* o4 = reinterpret_cast<i32x4*>(out + head);
+    for (int i = tid; i < n16; i += nth) {
+        const float* s = src + head + 16 * i;
+        i32x4 v;
+#pragma unroll
+        for (int w = 0; w < 4; ++w)
+            v[w] = g711_enc<ALAW>(s[4 * w]) | (g711_enc<ALAW>(s[4 * w + 1]) << 8) | (g711_enc<ALAW>(s[4 * w + 2]) << 16) | (g711_enc<ALAW>(s[4 * w + 3]) << 24);
+        __builtin_nontemporal_store(v, o4 + i);
+    }
+    for (int i = head + 16 * n16 + tid; i < n; i += nth) __builtin_nontemporal_store((unsigned char)g711_enc<ALAW>(src[i]), out + i);
+}
+// ... to elements idx .. of an output in any of the four formats (a wave-uniform branch)
+__device__ __forceinline__ void resample_store_row_g711(void* base, int format, long long idx, const float* src, int n, int tid, int nth) {
+    if (format == kAudioUlaw) return g711_store_row<false>(static_cast<unsigned char*>(base) + idx, src, n, tid, nth);
+    if (format == kAudioAlaw) return g711_store_row<true>(static_cast<unsigned char*>(base) + idx, src, n, tid, nth);
+    stream_store_row(base, format, idx, src, n, tid, nth);
+}
+// the load and the store of an instantiation: G711 - launched only where either format of the call is a G.711 law - dispatches over the
+// four formats, the others are stream_sample / stream_store_row as before
+template <bool G711>
+__device__ __forceinline__ float resample_sample(const void* base, int format, long long idx) {
+    if constexpr (G711) return resample_sample_g711(base, format, idx);
+    else return stream_sample(base, format, idx);
+}
+template <bool G711>
+__device__ __forceinline__ void resample_store_row(void* base, int format, long long idx, const float* src, int n, int tid, int nth) {
+    if constexpr (G711) resample_store_row_g711(base, format, idx, src, n, tid, nth);
+    else stream_store_row(base, format, idx, src, n, tid, nth);
+}
+
+template <bool STRM, bool RING = false, bool G711 = false>
 __global__ __launch_bounds__(kResampleThreads) void fe_resample_kernel(typename ResampleKernelArgs<RING>::type a) {
     static_assert(STRM || !RING, "the ring form is a form of the packet-stream form");
     extern __shared__ float rs_lds[];
@@ -184,9 +274,9 @@ __global__ __launch_bounds__(kResampleThreads) void fe_resample_kernel(typename 
             const long long l = x_lo + i - g0;                     // index into this call's samples
             float v = 0.0f;
             if constexpr (RING) {
-                if (l >= 0 && l < n_sig) v = stream_sample(a.in, a.in_format, in_base + ring_index(in_pos, in_len, l));
+                if (l >= 0 && l < n_sig) v = resample_sample<G711>(a.in, a.in_format, in_base + ring_index(in_pos, in_len, l));
             } else {
-                if (l >= 0 && l < n_sig) v = stream_sample(a.in, a.in_format, in_base + l);
+                if (l >= 0 && l < n_sig) v = resample_sample<G711>(a.in, a.in_format, in_base + l);
             }
             if constexpr (STRM) {
                 if (l < 0 && l >= -(long long)(K - 1)) v = row[(K - 1) + (int)l];
@@ -209,10 +299,10 @@ __global__ __launch_bounds__(kResampleThreads) void fe_resample_kernel(typename 
             // outputs m0 - m_begin .. of this call: up to the ring's end, then from its start (o and first are wave-uniform)
             const long long o = ring_index(out_pos, out_len, m0 - m_begin);
             const int first = (long long)cnt < out_len - o ? cnt : (int)(out_len - o);
-            stream_store_row(a.out, a.out_format, out_base + o, Y, first, tid, kResampleThreads);
-            if (first < cnt) stream_store_row(a.out, a.out_format, out_base, Y + first, cnt - first, tid, kResampleThreads);
+            resample_store_row<G711>(a.out, a.out_format, out_base + o, Y, first, tid, kResampleThreads);
+            if (first < cnt) resample_store_row<G711>(a.out, a.out_format, out_base, Y + first, cnt - first, tid, kResampleThreads);
         } else {
-            stream_store_row(a.out, a.out_format, out_base + (STRM ? m0 - m_begin : 0), Y, cnt, tid, kResampleThreads);
+            resample_store_row<G711>(a.out, a.out_format, out_base + (STRM ? m0 - m_begin : 0), Y, cnt, tid, kResampleThreads);
         }
         // (no barrier here: the next tile overwrites X only behind the barrier above, and Y only behind its own first barrier, which no
         // thread passes before every thread has left this store)
@@ -223,8 +313,8 @@ __global__ __launch_bounds__(kResampleThreads) void fe_resample_kernel(typename 
         // shifted; staged in LDS so that every old value is read before any is overwritten
         for (int i = tid; i < K - 1; i += kResampleThreads) {
             const long long l = (long long)n - (K - 1) + i;
-            if constexpr (RING) X[i] = l >= 0 ? stream_sample(a.in, a.in_format, in_base + ring_index(in_pos, in_len, l)) : row[(K - 1) + (int)l];
-            else X[i] = l >= 0 ? stream_sample(a.in, a.in_format, in_base + l) : row[(K - 1) + (int)l];
+            if constexpr (RING) X[i] = l >= 0 ? resample_sample<G711>(a.in, a.in_format, in_base + ring_index(in_pos, in_len, l)) : row[(K - 1) + (int)l];
+            else X[i] = l >= 0 ? resample_sample<G711>(a.in, a.in_format, in_base + l) : row[(K - 1) + (int)l];
         }
         __syncthreads();
         for (int i = tid; i < K - 1; i += kResampleThreads) row[i] = X[i];
@@ -242,10 +332,11 @@ inline size_t resample_lds_floats(int up, int KP, int xcap, int tile_out) {
     return (size_t)((up * KP + 3) & ~3) + (size_t)((xcap + 3) & ~3) + (size_t)((tile_out + 3) & ~3);
 }
 
-// The launchers, defined in fe_resample.hip - the one translation unit that instantiates the three kernels, so that the C-ABI unit, which
-// includes this header for the argument blocks, carries no device code of them.  Every resampler of the process shares the three kernels, and
+// The launchers, defined in fe_resample.hip - the one translation unit that instantiates the kernels (three forms, each with and without G711), so that the C-ABI unit, which
+// includes this header for the argument blocks, carries no device code of them.  Every resampler of the process shares the kernels, and
 // the opt-in for dynamic LDS is made once per kernel and device: for the most any ratio needs (160 KiB), not for one handle's footprint.
-hipError_t launch_resample(bool strm, dim3 grid, size_t lds_bytes, hipStream_t st, const ResampleArgs& a);
-hipError_t launch_resample_rings(dim3 grid, size_t lds_bytes, hipStream_t st, const ResampleRingArgs& a);
+// g711: the G711 instantiation of the form.
+hipError_t launch_resample(bool strm, bool g711, dim3 grid, size_t lds_bytes, hipStream_t st, const ResampleArgs& a);
+hipError_t launch_resample_rings(bool g711, dim3 grid, size_t lds_bytes, hipStream_t st, const ResampleRingArgs& a);
 
 }  // namespace fe

@@ -19,6 +19,24 @@ def _fmt(t: Tensor) -> int:
     return _lib.FE_AUDIO_S16 if t.dtype == torch.int16 else _lib.FE_AUDIO_F32
 
 
+_LAW_FORMATS = {"ulaw": _lib.FE_AUDIO_ULAW, "alaw": _lib.FE_AUDIO_ALAW}
+
+
+def _check_law(what: str, law) -> None:
+    """in_format= / out_format=: None (the format is the tensor's dtype) or a G.711 law"""
+    if law is not None and law not in _LAW_FORMATS:
+        raise ValueError(f"{what} must be None, 'ulaw' or 'alaw', got {law!r}")
+
+
+def _law_fmt(what: str, t: Tensor, law) -> int:
+    """the format code of tensor t under `law`: a law's bytes are a uint8 tensor"""
+    if law is None:
+        return _fmt(t)
+    if t.dtype != torch.uint8:
+        raise ValueError(f"{what}: G.711 {law} is one byte per sample - the tensor must be torch.uint8, got {t.dtype}")
+    return _LAW_FORMATS[law]
+
+
 class Resampler:
     """sr_in -> sr_out.  Creation and every query work without a GPU; the calls that resample need a CUDA device."""
 
@@ -78,20 +96,34 @@ class Resampler:
         if self.device is None or self.device.type != "cuda" or not torch.cuda.is_available():
             raise _lib.FEError("the resampler needs a GPU device (no CPU fallback); got device=%r" % (self.device,))
 
-    def __call__(self, x: Tensor, out_dtype=None) -> Tensor:
-        """x: float32 or int16 [B, L] (or [L]) on the device -> [B, out_count(L)] of out_dtype (default: x's)"""
-        if not isinstance(x, Tensor) or x.dtype not in (torch.float32, torch.int16) or x.dim() not in (1, 2) or x.numel() == 0:
+    def __call__(self, x: Tensor, out_dtype=None, *, in_format=None, out_format=None) -> Tensor:
+        """x: float32 or int16 [B, L] (or [L]) on the device -> [B, out_count(L)] of out_dtype (default: x's).
+        in_format="ulaw" / "alaw": x is uint8 G.711 bytes (out_dtype then defaults to int16).  out_format="ulaw" / "alaw": the output is
+        uint8 G.711 bytes (out_dtype must be left alone).  See fastenhancer_amd.g711 for making and reading such bytes."""
+        _check_law("in_format", in_format)
+        _check_law("out_format", out_format)
+        if in_format is not None:
+            if not isinstance(x, Tensor) or x.dim() not in (1, 2) or x.numel() == 0:
+                raise ValueError("x must be a non-empty tensor [B, L] or [L]")
+            _law_fmt("x", x, in_format)
+        elif not isinstance(x, Tensor) or x.dtype not in (torch.float32, torch.int16) or x.dim() not in (1, 2) or x.numel() == 0:
             raise ValueError("x must be a non-empty float32 or int16 tensor [B, L] or [L]")
-        out_dtype = x.dtype if out_dtype is None else out_dtype
-        if out_dtype not in (torch.float32, torch.int16):
-            raise ValueError("out_dtype must be float32 or int16")
+        if out_format is not None:
+            if out_dtype not in (None, torch.uint8):
+                raise ValueError(f"out_format={out_format!r} makes the output torch.uint8: leave out_dtype alone (got {out_dtype})")
+            out_dtype = torch.uint8
+        else:
+            out_dtype = (torch.int16 if in_format is not None else x.dtype) if out_dtype is None else out_dtype
+            if out_dtype not in (torch.float32, torch.int16):
+                raise ValueError("out_dtype must be float32 or int16")
         self._require_gpu()
         rows = x.to(self.device).reshape(-1, x.shape[-1]).contiguous()
         B, n_in = rows.shape
         n_out = self.out_count(n_in)
         out = torch.empty(B, n_out, dtype=out_dtype, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.fe_resample(self._h, _ptr(rows), n_in, _fmt(rows), n_in, _ptr(out), n_out, _fmt(out), B, _stream(self.device)), "fe_resample")
+            _lib.check(self.lib.fe_resample(self._h, _ptr(rows), n_in, _law_fmt("x", rows, in_format), n_in, _ptr(out), n_out,
+                                            _law_fmt("out", out, out_format), B, _stream(self.device)), "fe_resample")
         return out[0] if x.dim() == 1 else out
 
     def new_state(self, capacity: int) -> Tensor:
@@ -208,10 +240,16 @@ class Resampler:
         return d
 
     def _step_streams(self, x: Tensor, state: Tensor, capacity: int, desc, out: Tensor, n_in_max: int, produced: Optional[Tensor], pinned: bool,
-                      rings: bool = False):
+                      rings: bool = False, in_format=None, out_format=None):
         name = ("fe_resample_rings" if rings else "fe_resample_streams") + ("_pinned" if pinned else "")
-        for what, t in (("x", x), ("out", out)):
-            if not isinstance(t, Tensor) or t.dtype not in (torch.float32, torch.int16) or not t.is_contiguous() or t.numel() == 0:
+        _check_law("in_format", in_format)
+        _check_law("out_format", out_format)
+        for what, t, law in (("x", x, in_format), ("out", out, out_format)):
+            if law is not None:
+                if not isinstance(t, Tensor) or not t.is_contiguous() or t.numel() == 0:
+                    raise ValueError(f"{what} must be a contiguous, non-empty tensor")
+                _law_fmt(what, t, law)
+            elif not isinstance(t, Tensor) or t.dtype not in (torch.float32, torch.int16) or not t.is_contiguous() or t.numel() == 0:
                 raise ValueError(f"{what} must be a contiguous, non-empty float32 or int16 tensor")
             if pinned and (t.device.type != "cpu" or not t.is_pinned()):
                 raise ValueError(f"{what} must be a CPU tensor in page-locked memory (pin_memory())")
@@ -231,34 +269,41 @@ class Resampler:
                 and state.numel() == capacity * self.state_floats):
             raise ValueError(f"state must be a contiguous float32 device tensor of {capacity} x {self.state_floats} floats (new_state)")
         with torch.cuda.device(self.device):
-            _lib.check(getattr(self.lib, name)(self._h, _ptr(x), x.numel(), _fmt(x), _ptr(state), int(capacity), _ptr(d), _ptr(out), out.numel(), _fmt(out),
-                                               _ptr(produced), d.shape[0], int(n_in_max), _stream(self.device)), name)
+            _lib.check(getattr(self.lib, name)(self._h, _ptr(x), x.numel(), _law_fmt("x", x, in_format), _ptr(state), int(capacity), _ptr(d), _ptr(out),
+                                               out.numel(), _law_fmt("out", out, out_format), _ptr(produced), d.shape[0], int(n_in_max),
+                                               _stream(self.device)), name)
         self._keep = (d, x, out, produced)       # (alive until the next call - the launch is asynchronous)
         return out
 
-    def step_streams(self, x: Tensor, state: Tensor, capacity: int, desc, out: Tensor, n_in_max: int, produced: Optional[Tensor] = None) -> Tensor:
+    def step_streams(self, x: Tensor, state: Tensor, capacity: int, desc, out: Tensor, n_in_max: int, produced: Optional[Tensor] = None, *,
+                         in_format=None, out_format=None) -> Tensor:
         """fe_resample_streams: every stream of `desc` - (slot, n_in, in_offset, out_offset), or a CUDA int32 tensor [n, 6] - consumes its n_in
         samples from the flat device buffer x and writes the outputs that become due to the flat device buffer `out` (either float32 or
-        int16, independently).  state: new_state(capacity).  produced: an int32 tensor [n] (device or page-locked), each stream's output count."""
-        return self._step_streams(x, state, capacity, desc, out, n_in_max, produced, pinned=False)
+        int16, independently).  state: new_state(capacity).  produced: an int32 tensor [n] (device or page-locked), each stream's output count.
+        in_format / out_format: None - the format is the tensor's dtype - or "ulaw" / "alaw": that side is a uint8 tensor of G.711 bytes
+        (one byte per sample: counts and offsets are bytes), decoded or encoded by the kernel.  The same two keywords on the three forms below."""
+        return self._step_streams(x, state, capacity, desc, out, n_in_max, produced, pinned=False, in_format=in_format, out_format=out_format)
 
-    def step_streams_pinned(self, x: Tensor, state: Tensor, capacity: int, desc, out: Tensor, n_in_max: int, produced: Optional[Tensor] = None) -> Tensor:
+    def step_streams_pinned(self, x: Tensor, state: Tensor, capacity: int, desc, out: Tensor, n_in_max: int, produced: Optional[Tensor] = None, *,
+                                in_format=None, out_format=None) -> Tensor:
         """fe_resample_streams_pinned: step_streams with x / out in page-locked HOST memory.  Asynchronous on the current stream: synchronise
         it before reading out (or a pinned `produced`) or rewriting x."""
-        return self._step_streams(x, state, capacity, desc, out, n_in_max, produced, pinned=True)
+        return self._step_streams(x, state, capacity, desc, out, n_in_max, produced, pinned=True, in_format=in_format, out_format=out_format)
 
-    def step_rings(self, x: Tensor, state: Tensor, capacity: int, desc, out: Tensor, n_in_max: int, produced: Optional[Tensor] = None) -> Tensor:
+    def step_rings(self, x: Tensor, state: Tensor, capacity: int, desc, out: Tensor, n_in_max: int, produced: Optional[Tensor] = None, *,
+                       in_format=None, out_format=None) -> Tensor:
         """fe_resample_rings: step_streams for streams whose samples live in rings inside x and out.  desc: a list of
         (slot, n_in, in_base, out_base, in_len, in_pos, out_len, out_pos) - sample i of the packet is x[in_base + (in_pos + i) % in_len],
         output m of the call out[out_base + (out_pos + m) % out_len]; checked on the host (check_ring_desc: ValueError where the kernel
         would skip the stream) - or a CUDA int32 tensor [n, 10] (pack_ring_desc), which the kernel alone checks.  A flat buffer is pos = 0
         with len at least the count."""
-        return self._step_streams(x, state, capacity, desc, out, n_in_max, produced, pinned=False, rings=True)
+        return self._step_streams(x, state, capacity, desc, out, n_in_max, produced, pinned=False, rings=True, in_format=in_format, out_format=out_format)
 
-    def step_rings_pinned(self, x: Tensor, state: Tensor, capacity: int, desc, out: Tensor, n_in_max: int, produced: Optional[Tensor] = None) -> Tensor:
+    def step_rings_pinned(self, x: Tensor, state: Tensor, capacity: int, desc, out: Tensor, n_in_max: int, produced: Optional[Tensor] = None, *,
+                              in_format=None, out_format=None) -> Tensor:
         """fe_resample_rings_pinned: step_rings with x / out in page-locked HOST memory - the rings of a PacketPool, for one.  Asynchronous on
         the current stream: synchronise it before reading out (or a pinned `produced`) or rewriting x."""
-        return self._step_streams(x, state, capacity, desc, out, n_in_max, produced, pinned=True, rings=True)
+        return self._step_streams(x, state, capacity, desc, out, n_in_max, produced, pinned=True, rings=True, in_format=in_format, out_format=out_format)
 
     def new_pinned(self, *shape: int, dtype=torch.float32) -> Tensor:
         self._require_gpu()

@@ -629,10 +629,15 @@ class ResampledPacketPool:
     into and out of the inner pool's rings and waits once (this class is its oracle, and the form that needs nothing but the inner pool's
     public methods); fusing the filter into the frame kernels themselves is left for later.  Both resamplers are streaming-exact across packets (the outputs are those of one call on the whole signal),
     each with its own latency of half_len / up input samples; nothing is flushed when a slot closes.
-    model_rate: the engine's configuration does not carry a sample rate - 16000 for the 16 kHz configurations, 48000 for the 48 kHz ones."""
+    model_rate: the engine's configuration does not carry a sample rate - 16000 for the 16 kHz configurations, 48000 for the 48 kHz ones.
+    client_format: "s16" (the above), or "ulaw" / "alaw" for telephony clients - G.711, one byte per sample (fastenhancer_amd.g711): push()
+    then takes a 1-D uint8 array of that law and pull() returns uint8, the client-rate staging buffers are uint8, and the two resampler
+    launches decode and encode on their client side (in_format= / out_format=).  The model-rate side, the inner pool and every counter are
+    as with "s16": each pull() is the G.711 encoding of what the "s16" pool returns when fed the decoded bytes."""
 
     def __init__(self, engine: Engine, capacity: int, ring_hops: int, client_rate: int, T_max: int = 1, max_packet: Optional[int] = None, *,
-                 model_rate: int = 16000):
+                 model_rate: int = 16000, client_format: str = "s16"):
+        self._set_client_format(client_format)
         client_rate, model_rate = operator.index(client_rate), operator.index(model_rate)
         if client_rate == model_rate:
             raise ValueError(f"client_rate {client_rate} is the model's rate: there is nothing to resample, use PacketPool")
@@ -653,10 +658,10 @@ class ResampledPacketPool:
         self._step = step
         self.state_in = self.to_model.new_state(self.capacity)
         self.state_out = self.to_client.new_state(self.capacity)
-        self._cin = self.to_model.new_pinned(self.capacity, self.max_packet, dtype=torch.int16)
+        self._cin = self.to_model.new_pinned(self.capacity, self.max_packet, dtype=self._client_dtype)
         self._min = self.to_model.new_pinned(self.capacity, self._model_cap, dtype=torch.int16)
         self._mout = self.to_client.new_pinned(self.capacity, step, dtype=torch.int16)
-        self._cout = self.to_client.new_pinned(self.capacity, self._client_cap, dtype=torch.int16)
+        self._cout = self.to_client.new_pinned(self.capacity, self._client_cap, dtype=self._client_dtype)
         self._made_in = self.to_model.new_pinned(self.capacity, dtype=torch.int32)
         self._made_out = self.to_client.new_pinned(self.capacity, dtype=torch.int32)
         self._pending = [0] * self.capacity          # client-rate samples waiting in _cin
@@ -664,6 +669,18 @@ class ResampledPacketPool:
         self._fill = [0] * self.capacity             # model-rate samples pushed into the inner pool and not yet pulled from it
         self._ready: List[List[Tensor]] = [[] for _ in range(self.capacity)]
         self._open = set()
+
+    def _set_client_format(self, client_format) -> None:
+        """client_format: what push() takes and pull() returns at the client's rate - "s16" (int16 PCM), or "ulaw" / "alaw": G.711, one
+        uint8 byte per sample, decoded and encoded by the two resampler launches (Resampler's in_format= / out_format=)"""
+        if client_format not in ("s16", "ulaw", "alaw"):
+            raise ValueError(f"client_format must be 's16', 'ulaw' or 'alaw', got {client_format!r}")
+        self.client_format = client_format
+        law = None if client_format == "s16" else client_format
+        self._client_dtype = torch.int16 if law is None else torch.uint8
+        # the keywords of the two launches' client sides ("s16": none - the calls are what they were)
+        self._in_kw = {} if law is None else {"in_format": law}
+        self._out_kw = {} if law is None else {"out_format": law}
 
     # (the two constructors tick() depends on, apart for the tests that record the calls instead of running them)
     @staticmethod
@@ -706,7 +723,9 @@ class ResampledPacketPool:
         samples would wait for the next tick or the inner pool's ring could not hold what they become."""
         self._check_open(slot)
         x = torch.as_tensor(pcm)
-        if x.dim() != 1 or x.dtype != torch.int16:
+        if x.dim() != 1 or x.dtype != self._client_dtype:
+            if self.client_format != "s16":
+                raise ValueError(f"a packet is a 1-D uint8 array of G.711 {self.client_format} bytes, got {x.dtype} {tuple(x.shape)}")
             raise ValueError(f"a packet is a 1-D int16 array, got {x.dtype} {tuple(x.shape)}")
         n, have = x.numel(), self._pending[slot]
         if have + n > self.max_packet:
@@ -721,7 +740,8 @@ class ResampledPacketPool:
         inner.tick() returned."""
         todo = [(slot, self._pending[slot], slot * self.max_packet, slot * self._model_cap) for slot in sorted(self._open) if self._pending[slot] > 0]
         if todo:
-            self.to_model.step_streams_pinned(self._cin, self.state_in, self.capacity, todo, self._min, self.max_packet, produced=self._made_in[:len(todo)])
+            self.to_model.step_streams_pinned(self._cin, self.state_in, self.capacity, todo, self._min, self.max_packet, produced=self._made_in[:len(todo)],
+                                              **self._in_kw)
             self.to_model.synchronize()
             # the launch has consumed every stream's samples: the counters follow it for all of them before anything can raise
             made_in = []
@@ -750,7 +770,8 @@ class ResampledPacketPool:
                 self._fill[slot] -= n
                 back.append((slot, n, slot * self._step, slot * self._client_cap))
         if back:
-            self.to_client.step_streams_pinned(self._mout, self.state_out, self.capacity, back, self._cout, self._step, produced=self._made_out[:len(back)])
+            self.to_client.step_streams_pinned(self._mout, self.state_out, self.capacity, back, self._cout, self._step, produced=self._made_out[:len(back)],
+                                               **self._out_kw)
             self.to_client.synchronize()
             for i, (slot, _, _, _) in enumerate(back):
                 made = int(self._made_out[i])
@@ -762,7 +783,7 @@ class ResampledPacketPool:
         """The enhanced int16 samples at the client's rate made since the last pull (a copy; empty when there are none)."""
         self._check_open(slot)
         parts, self._ready[slot] = self._ready[slot], []
-        return torch.cat(parts) if parts else torch.zeros(0, dtype=torch.int16)
+        return torch.cat(parts) if parts else torch.zeros(0, dtype=self._client_dtype)
 
 
 class RingResampledPacketPool(ResampledPacketPool):
@@ -789,11 +810,13 @@ class RingResampledPacketPool(ResampledPacketPool):
     The contract: for the same sequence of open / push / tick / pull / close calls every pull() returns the int16 samples
     ResampledPacketPool returns, bit for bit, tick() returns the same list, and state_in / state_out hold the same rows - both pools round to
     int16 at the model's rate, the resampler is packetisation-exact, and the hop schedule is a function of host counters only.
+    client_format="ulaw" / "alaw" (ResampledPacketPool's keyword): G.711 bytes in and out, the same bytes ResampledPacketPool returns.
     Not here: device-resident rings; the filter fused into the frame kernels' stream_sample / stream_store_row; move / resize / export of a
-    resampled pool; a flush on close()."""
+    resampled pool; a flush on close(); G.711 straight into a PacketPool at the model's rate; G.722 and other codecs."""
 
     def __init__(self, engine: Engine, capacity: int, ring_hops: int, client_rate: int, T_max: int = 1, max_packet: Optional[int] = None, *,
-                 model_rate: int = 16000, pool=PacketPool, **pool_kwargs):
+                 model_rate: int = 16000, client_format: str = "s16", pool=PacketPool, **pool_kwargs):
+        self._set_client_format(client_format)
         client_rate, model_rate = operator.index(client_rate), operator.index(model_rate)
         if client_rate == model_rate:
             raise ValueError(f"client_rate {client_rate} is the model's rate: there is nothing to resample, use PacketPool")
@@ -814,8 +837,8 @@ class RingResampledPacketPool(ResampledPacketPool):
         self._step = step
         self.state_in = self.to_model.new_state(self.capacity)
         self.state_out = self.to_client.new_state(self.capacity)
-        self._cin = self.to_model.new_pinned(self.capacity, self.max_packet, dtype=torch.int16)
-        self._cout = self.to_client.new_pinned(self.capacity, self._client_cap, dtype=torch.int16)
+        self._cin = self.to_model.new_pinned(self.capacity, self.max_packet, dtype=self._client_dtype)
+        self._cout = self.to_client.new_pinned(self.capacity, self._client_cap, dtype=self._client_dtype)
         self._made_in = self.to_model.new_pinned(self.capacity, dtype=torch.int32)
         self._made_out = self.to_client.new_pinned(self.capacity, dtype=torch.int32)
         self._pending = [0] * self.capacity          # client-rate samples waiting in _cin
@@ -846,14 +869,14 @@ class RingResampledPacketPool(ResampledPacketPool):
                 due_in.append(made)
         if todo:
             self.to_model.step_rings_pinned(self._cin, self.state_in, self.capacity, todo, inner.ring_in, self.max_packet,
-                                            produced=self._made_in[:len(todo)])
+                                            produced=self._made_in[:len(todo)], **self._in_kw)
         launched = inner._enqueue()
         back = [(slot, hops * inner.H, slot * ring, slot * self._client_cap, ring, inner._pulled[slot] % ring, self._client_cap, 0)
                 for slot, hops, _, _ in sorted(launched)]
         due_out = [self.to_client.produced(self._returned[slot], n) for slot, n, *_ in back]
         if back:
             self.to_client.step_rings_pinned(inner.ring_out, self.state_out, self.capacity, back, self._cout, self._step,
-                                             produced=self._made_out[:len(back)])
+                                             produced=self._made_out[:len(back)], **self._out_kw)
         if todo or launched:
             inner.engine.synchronize()
         inner._complete(launched)

@@ -264,6 +264,10 @@ typedef struct fe_stream_desc {      /* 24 bytes */
 } fe_stream_desc;
 #define FE_AUDIO_F32 0
 #define FE_AUDIO_S16 1               /* int16 PCM, full scale 32768 */
+/* G.711, one unsigned byte per sample - formats of the RESAMPLER only ("Audio at another sample rate", below); every model step refuses
+ * them as it refuses any format but the two above.  Codes 2 and 3 are not formats. */
+#define FE_AUDIO_ULAW  4             /* G.711 mu-law (PCMU) */
+#define FE_AUDIO_ALAW  5             /* G.711 A-law (PCMA) */
 int fe_step_streams(fe_handle* h, const void* wav_in_dev, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,
                     void* wav_out_dev, size_t out_count, int n, int T_max, int format, void* stream);
 int fe_step_streams_pinned(fe_handle* h, const void* wav_in_host, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,
@@ -731,6 +735,29 @@ int fe_debug_pack_weights(fe_handle* h, const float* blob_host, size_t nfloats, 
  * 8 -> 16 kHz), and under ANY packetisation its outputs are the first M(N) outputs of the whole-signal call on the same samples, bit for
  * bit.  There is no flush: a caller that wants the tail pushes hl / up zeros.  int16 input is the float input s / 32768 (exact); int16
  * output is clamp(rint(y * 32768), -32768, 32767), ties to even, NaN -> 0, of the float output (the rules of fe_step_streams).
+ *
+ * G.711 (FE_AUDIO_ULAW, FE_AUDIO_ALAW: telephony's one byte per sample, RTP payload types 0 and 8).  fe_resample, fe_resample_streams[_pinned]
+ * and fe_resample_rings[_pinned] take them as in_format and as out_format, independently (mu-law in and float out, int16 in and A-law out).
+ * Every count, stride, offset and ring base / length / position stays in ELEMENTS of the format - bytes here - and any byte alignment is
+ * legal.  All arithmetic below is on 32-bit ints, >> is arithmetic, hibit(v) is the index of the highest set bit.
+ *   In: a byte b is the 16-bit linear sample s = dec(b), seen as the float s / 32768 exactly as an int16 s is.
+ *     mu-law: u = ~b & 0xFF, e = (u >> 4) & 7, m = u & 15, mag = (((m << 3) + 0x84) << e) - 0x84, s = (u & 0x80) ? -mag : mag
+ *             (-32124 .. 32124; 0xFF and 0x7F both decode to 0)
+ *     A-law:  a = b ^ 0x55, e = (a >> 4) & 7, m = a & 15, mag = e == 0 ? (m << 4) + 8 : ((m << 4) + 0x108) << (e - 1),
+ *             s = (a & 0x80) ? mag : -mag       (-32256 .. 32256)
+ *   Out: the float y is quantised by the int16 rule above to q, then b = enc(q).
+ *     mu-law: v = q >> 2; if v < 0: mask = 0x7F, v = -v, else mask = 0xFF; v = min(v, 8159) + 33, seg = hibit(v) - 5,
+ *             t = seg >= 8 ? 0x7F : (seg << 4) | ((v >> (seg + 1)) & 15), b = t ^ mask
+ *     A-law:  if q >= 0: n = q, sign = 0x80, else n = ~q, sign = 0; if n < 256: e = 0, m = n >> 4, else e = hibit(n) - 7,
+ *             m = (n >> (e + 3)) & 15; b = (sign | (e << 4) | m) ^ 0x55
+ *   These are the ITU-T G.711 tables as CPython's audioop computes them (ulaw2lin, alaw2lin, lin2ulaw, lin2alaw on 16-bit samples).
+ * The state row is floats whatever the formats: a row written under one input format continues under another.  Streaming exactness is
+ * unchanged: under any packetisation the output bytes are the first M(N) bytes of the whole-signal call.  "Nothing outside a stream's
+ * ranges is written" holds to the BYTE: no store covers a byte that is not the stream's.  A call with a G.711 format on either side runs
+ * an instantiation of its own, and fe_resampler_last_kernel names it with g711 as the last item: fe_resample_kernel<whole,g711>,
+ * <streams,g711>, <streams,pinned,g711>, <ring,g711>, <ring,pinned,g711>; every other call runs and reports what it did before.
+ * Not here: G.711 straight into a model step (fe_step_streams* and fe_step_pool_streams* refuse the two codes), G.711 WAV files, G.722
+ * and other codecs.
  *
  * The create call and every query work without a GPU (as the model handle's do); the tap table is uploaded to the device that is current
  * at the handle's FIRST launch (one allocation and one synchronous copy: make that launch outside a graph capture), and the handle
