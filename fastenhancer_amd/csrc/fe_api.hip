@@ -2102,6 +2102,23 @@ static PipeLayout baseline_backlog_layout(Fam, const fe_handle* h, int B, int T)
     return pipe_layout(h, B, T, Fam::counters(h), 0);
 }
 
+// A family whose PIPE kernel carries the streaming state only when asked (Fam::kPipeCarriesStateOnRequest: LiSenNet, under an explicit
+// fe_set_time_pipeline(P >= 2)): that launch's work buffer - the counters, the windowed frames and the rings of the frames in flight, sized
+// for the widest pipeline as baseline_layout sizes them.  A query of its own (fe_lisennet_backlog_work_floats): baseline_backlog_layout is 0.
+extern "C++" template <class Fam>
+static PipeLayout baseline_request_layout(Fam, const fe_handle* h, int B, int T) {
+    if (!Fam::kPipeCarriesStateOnRequest || B <= 0 || T < 4) return {0, 0, 0};
+    return pipe_layout(h, B, T, Fam::counters(h), (size_t)B * Fam::ring_floats(h));
+}
+
+// workgroups per stream of that launch (0: fe_step's own launch): an explicit width of two or more, a work buffer, a chunk that covers the
+// overlap (stream_ola_kernel) - then what the family's fe_offline launch would take
+extern "C++" template <class Fam>
+static int baseline_request_width(Fam, const fe_handle* h, int B, int T, const float* work_dev) {
+    if (!Fam::kPipeCarriesStateOnRequest || h->pipe_frames < 2 || !work_dev || (long)T * h->d.HOP < h->d.NFFT - h->d.HOP) return 0;
+    return baseline_pipe_width(Fam{}, h, B, T);
+}
+
 // workgroups per stream of fe_step_backlog's pipelined launch: the family's fe_offline width (0: fe_step's own launch), and the chunk has
 // to cover the overlap (stream_ola_kernel: T H >= N - H - every shipped BSRNN and FSPEN shape does at T = 4)
 extern "C++" template <class Fam>
@@ -2115,7 +2132,8 @@ static int baseline_backlog_width(Fam, const fe_handle* h, int B, int T) {
 // in place (not zeroed, not copied: frame 0 reads it, the last frame leaves the new one), stream_ola_kernel - that allocates nothing
 // (Fam::args takes the per-family scratch the handle got at fe_load_weights, as baseline_offline does).  A cooperative launch the runtime
 // refuses: fe_step's launch with the caller's own argument block - by then only the counters in work_dev have been written.
-extern "C++" template <class Fam>
+// REQ: the launch a family makes on request only (baseline_request_layout, with the rings; Fam::launch_pipe_stream) - the same chain.
+extern "C++" template <class Fam, bool REQ = false>
 static int baseline_step_backlog(Fam, fe_handle* h, const float* wav_in, size_t in_stride, float* state, float* wav_out, size_t out_stride, int B, int T, int P,
                                  float* work_dev, void* stream) {
     int rc = check_ready(h);
@@ -2125,12 +2143,14 @@ static int baseline_step_backlog(Fam, fe_handle* h, const float* wav_in, size_t 
     const Dims& d = h->d;
     typename Fam::StreamArgs a = Fam::args(h, B, T);
     Fam::state(a) = stream_io(a, wav_in, in_stride, wav_out, out_stride, state, state_layout(h, B));
-    const PipeLayout L = baseline_backlog_layout(Fam{}, h, B, T);
-    const typename Fam::Args p = pipe_args(a, work_dev, L, P);
+    const PipeLayout L = REQ ? baseline_request_layout(Fam{}, h, B, T) : baseline_backlog_layout(Fam{}, h, B, T);
+    typename Fam::Args p = pipe_args(a, work_dev, L, P);
+    if constexpr (REQ) Fam::set_ring(p, work_dev + L.ring);
     const int nflags = (int)((size_t)B * Fam::counters(h));
     hipLaunchKernelGGL(fe::zero_counters_kernel, dim3((nflags + fe::kThreads - 1) / fe::kThreads), dim3(fe::kThreads), 0, st, p.pipe_flags, nflags);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return launch_rc(e);
+    if constexpr (REQ) Fam::launch_pipe_stream(h, p, st, &e); else
     Fam::impl(h)->launch_pipe(p, st, &e);
     if (coop_refused(e)) {
         fe::g_klog.n = 0;       // (the refused launch was named before it was tried)
@@ -2158,10 +2178,31 @@ int fe_step_backlog(fe_handle* h, const float* wav_in_dev, size_t in_stride, flo
     if (rc != FE_OK) return rc;
     int P = 0;
     visit_baseline(h->cfg.arch, [&](auto F) { P = baseline_backlog_width(F, h, B, T); });
-    if (P == 0) return run_step(h, wav_in_dev, in_stride, state_dev, wav_out_dev, out_stride, B, T, nullptr, nullptr, stream);
+    if (P == 0) {
+        // a family that pipelines on request (LiSenNet): an explicit width >= 2 and a work buffer of fe_lisennet_backlog_work_floats
+        bool done = false;
+        visit_baseline(h->cfg.arch, [&](auto F) {
+            using Fam = decltype(F);
+            if constexpr (Fam::kPipeCarriesStateOnRequest) {
+                if (const int Q = baseline_request_width(F, h, B, T, work_dev)) {
+                    rc = baseline_step_backlog<Fam, true>(F, h, wav_in_dev, in_stride, state_dev, wav_out_dev, out_stride, B, T, Q, work_dev, stream);
+                    done = true;
+                }
+            }
+        });
+        if (done) return rc;
+        return run_step(h, wav_in_dev, in_stride, state_dev, wav_out_dev, out_stride, B, T, nullptr, nullptr, stream);
+    }
     if (!work_dev) return fail(FE_ERR_INVALID_ARG, "fe_step_backlog: null work buffer (fe_step_backlog_work_floats(h, %d, %d) floats)", B, T);
     visit_baseline(h->cfg.arch, [&](auto F) { rc = baseline_step_backlog(F, h, wav_in_dev, in_stride, state_dev, wav_out_dev, out_stride, B, T, P, work_dev, stream); });
     return rc;
+}
+
+size_t fe_lisennet_backlog_work_floats(const fe_handle* h, int B, int T) {
+    if (!h || B <= 0 || T < 4) return 0;
+    size_t n = 0;
+    visit_baseline(h->cfg.arch, [&](auto F) { n = baseline_request_layout(F, h, B, T).total; });
+    return n;
 }
 
 // fe_step_pool_streams_chunk: fe_step_pool_streams_ctl with each stream's hops on the time pipeline, for every family with a streaming state.

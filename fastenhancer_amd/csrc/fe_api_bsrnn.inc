@@ -20,6 +20,7 @@ struct BsrnnFamily {
     // of a frame, so every co-resident workgroup the batch leaves free is worth having
     static constexpr int kPipeFrames = 64;
     static constexpr bool kPipeCarriesState = true;      // (fe_step_backlog: the PIPE kernel's frames hand the streaming state on in place)
+    static constexpr bool kPipeCarriesStateOnRequest = false;      // (it always does: nothing to ask for)
     static size_t ring_floats(const fe_handle*) { return 0; }
     static void set_ring(Args&, float*) {}
     static size_t xp_floats(const fe_handle* h) { return (size_t)h->max_wgs * h->bimpl->xp_floats; }     // (band-LSTM input projections of C = 64)

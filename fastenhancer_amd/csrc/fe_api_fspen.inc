@@ -21,6 +21,7 @@ struct FspenFamily {
     static size_t counters(const fe_handle* h) { return h->fimpl->num_blocks; }      // time-pipeline frame counters per stream
     static constexpr int kPipeFrames = 32;
     static constexpr bool kPipeCarriesState = true;      // (fe_step_backlog: the PIPE kernel's frames hand the streaming state on in place)
+    static constexpr bool kPipeCarriesStateOnRequest = false;      // (it always does: nothing to ask for)
     static size_t ring_floats(const fe_handle*) { return 0; }
     static void set_ring(Args&, float*) {}
     static size_t xp_floats(const fe_handle*) { return 0; }

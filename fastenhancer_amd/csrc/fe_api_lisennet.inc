@@ -22,9 +22,13 @@ struct LisennetFamily {
     }
     static size_t counters(const fe_handle* h) { return h->limpl->nsite; }      // time-pipeline frame counters per stream
     static constexpr int kPipeFrames = 32;
-    // fe_step_backlog walks: the PIPE kernel hands the nine caches through ring slots and starts from zero caches at frame 0 (cprev / ccur in
-    // lisennet_kernels.hip.h) - a streaming state would need kernels that move it into and out of the ring
+    // fe_step_backlog walks unless it is asked not to: the PIPE kernel hands the nine caches through ring slots and starts from zero caches at
+    // frame 0 (cprev / ccur in lisennet_kernels.hip.h).  Its CARRY instantiation takes frame 0's caches from the caller's state and leaves the
+    // last frames' there, in place - under an explicit fe_set_time_pipeline(P >= 2) and with a work buffer of
+    // fe_lisennet_backlog_work_floats (which has the ring; fe_step_backlog_work_floats stays 0), fe_step_backlog launches that one.
     static constexpr bool kPipeCarriesState = false;
+    static constexpr bool kPipeCarriesStateOnRequest = true;
+    static void launch_pipe_stream(const fe_handle* h, const Args& a, hipStream_t st, hipError_t* e) { h->limpl->launch_pipe_stream(a, st, e); }
     // the time pipeline's ring of the caches of the frames in flight (LArgs::ring), sized for the widest pipeline: two more slots than frames
     static size_t ring_floats(const fe_handle* h) { return (size_t)(kMaxPipeFrames + 2) * h->limpl->cache_floats; }
     static void set_ring(Args& a, float* ring) { a.ring = ring; }

@@ -226,8 +226,27 @@ class Engine:
     def step_backlog(self, wav_in: Tensor, state: Tensor, wav_out: Optional[Tensor] = None, T: Optional[int] = None, work: Optional[Tensor] = None) -> Tensor:
         """fe_step_backlog: step_chunk for every family - the FastEnhancer models as step_chunk runs them, BSRNN and FSPEN with the T hops
         of each stream on their own time pipeline, LiSenNet as step() walks it.  Arguments, checks and the scratch tensor as for step_chunk,
-        with backlog_work_floats(B, T) for the size of work."""
+        with backlog_work_floats(B, T) for the size of work.
+        LiSenNet on the time pipeline is opt-in: after set_time_pipeline(P) with P >= 2, a `work` of lisennet_backlog_work_floats(B, T)
+        floats is passed through and the chunk (T >= 4) runs pipelined on the caller's state; work=None walks, as at every other setting
+        (lisennet_backlog_work(B, T) hands out the engine's scratch tensor at that size, or None where the call would walk anyway)."""
         return self._chunk("fe_step_backlog", "backlog_work_floats", wav_in, state, wav_out, T, work)
+
+    def lisennet_backlog_work_floats(self, B: int, T: int) -> int:
+        """fe_lisennet_backlog_work_floats: floats of the work buffer with which step_backlog runs a LiSenNet chunk on the time pipeline
+        (counters, windowed frames, the rings of the nine caches); 0 for every other family, for B <= 0 and for T < 4."""
+        return int(self.lib.fe_lisennet_backlog_work_floats(self._h, int(B), int(T)))
+
+    def lisennet_backlog_work(self, B: int, T: int) -> Optional[Tensor]:
+        """The engine's grow-only scratch tensor at lisennet_backlog_work_floats(B, T) floats for step_backlog(work=...), when the last
+        set_time_pipeline() named a width of two or more; else None - the call then walks (what the callers that size the buffer
+        themselves pass: streaming.enhance_stream(chunk_hops=...), StreamPool.catch_up)."""
+        need = self.lisennet_backlog_work_floats(B, T) if getattr(self, "_time_pipeline", -1) >= 2 else 0
+        if need == 0:
+            return None
+        if getattr(self, "_chunk_work", None) is None or self._chunk_work.numel() < need:
+            self._chunk_work = torch.empty(need, dtype=torch.float32, device=self.device)
+        return self._chunk_work
 
     def _chunk(self, entry: str, query: str, wav_in: Tensor, state: Tensor, wav_out: Optional[Tensor], T: Optional[int], work: Optional[Tensor]) -> Tensor:
         """step_chunk / step_backlog: the checks (all of them before any native call), the grow-only scratch tensor, the call of `entry`"""
@@ -253,6 +272,8 @@ class Engine:
         if state.numel() != self.state_floats(B):
             raise ValueError(f"state has {state.numel()} floats, a state of {B} streams {self.state_floats(B)}")
         need = getattr(self, query)(B, T)
+        if need == 0 and work is not None and entry == "fe_step_backlog":
+            need = self.lisennet_backlog_work_floats(B, T)      # (LiSenNet: a work buffer asks for the pipeline, and has to hold its launch)
         if work is None:
             if need > 0:
                 if getattr(self, "_chunk_work", None) is None or self._chunk_work.numel() < need:
@@ -693,6 +714,7 @@ class Engine:
     def set_time_pipeline(self, frames_in_flight: int):
         """fe_set_time_pipeline: workgroups per stream in offline / spec launches with T >= 4 (0 = one workgroup per stream)."""
         _lib.check(self.lib.fe_set_time_pipeline(self._h, int(frames_in_flight)), "fe_set_time_pipeline")
+        self._time_pipeline = int(frames_in_flight)       # (lisennet_backlog_work: an explicit width >= 2 opts LiSenNet's backlogs in)
 
     def model_state_floats(self, B: int) -> int:
         """floats of the model's own caches (fe_spec_step's h_dev): the state without the two STFT caches"""

@@ -46,6 +46,7 @@ class Family:
     order: Callable = lambda cfg, caches: [t.reshape(-1) for t in caches]               # caches -> flat pieces of h, in its order
     start: Callable = lambda cfg, h, B: None                                            # zeroed h -> the state of a call without caches
     backlog: bool = False           # chunks of many hops go through Engine.step_backlog (fe_step_backlog pipelines the family), not step_chunk
+    backlog_on_request: bool = False  # ... and fe_step_backlog pipelines the family when handed Engine.lisennet_backlog_work(B, T) (LiSenNet)
     pool: bool = False              # the slotted step of live streams is Engine.step_pool (fe_step_slots refuses the family), not step_slots
 
     def spec_bins(self, cfg) -> int:
@@ -142,7 +143,7 @@ _FAMILIES = {
     FSPENConfig: Family(_lib.FE_ARCH_FSPEN, _fspen_config, W.fspen_fold_state_dict, _shapes(W.fspen_expected_fused_shapes),
                         W.fspen_default_state_dict, backlog=True, pool=True),
     LiSenNetConfig: Family(_lib.FE_ARCH_LISENNET, _lisennet_config, W.lisennet_state_dict, _shapes(W.lisennet_expected_shapes),
-                           W.lisennet_default_state_dict, pool=True),
+                           W.lisennet_default_state_dict, pool=True, backlog_on_request=True),
 }
 
 
@@ -153,8 +154,14 @@ def family_of(cfg) -> Family:
 def chunk_step(engine) -> Callable:
     """The engine's call for a chunk of many hops of few streams (streaming.enhance_stream(chunk_hops=...), StreamPool.catch_up):
     step_backlog for the families fe_step_backlog pipelines (BSRNN, FSPEN), step_chunk for every other - FastEnhancer's own path as it
-    has always been called; for LiSenNet both are the walk of step()."""
+    has always been called.  LiSenNet: step_chunk too - the walk of step() - unless the engine's time pipeline was set to an explicit
+    width of two or more: then step_backlog with the engine's scratch tensor sized for that family's pipelined launch."""
     fam = _FAMILIES.get(type(getattr(engine, "cfg", None)))
+    if fam is not None and fam.backlog_on_request and getattr(engine, "_time_pipeline", -1) >= 2:
+        def step(wav_in, state, wav_out=None, T=None):
+            hops = wav_in.shape[1] // engine.cfg.hop_size if T is None else T
+            return engine.step_backlog(wav_in, state, wav_out, T=T, work=engine.lisennet_backlog_work(wav_in.shape[0], hops))
+        return step
     return engine.step_backlog if fam is not None and fam.backlog else engine.step_chunk
 
 

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """scripts/test_streaming.py with one more flag: --chunk-hops N runs the file in chunks of N hops on the time pipeline
-(Engine.step_chunk - BSRNN and FSPEN checkpoints: Engine.step_backlog - through streaming.enhance_stream(chunk_hops=N)) instead of hop by hop.  Off by default: without the flag this IS
+(Engine.step_chunk - BSRNN and FSPEN checkpoints: Engine.step_backlog - through streaming.enhance_stream(chunk_hops=N)) instead of hop by hop.
+A LiSenNet checkpoint walks its chunks unless --time-pipeline P (P >= 2: Engine.set_time_pipeline) opts it in to the pipeline.  Off by default: without the flag this IS
 test_streaming.py (same flags, same loop, same output).
 And a second one: --resample takes a file that is not at the model's rate (with or without --chunk-hops; test_streaming.py itself refuses
 such a file): it is read at its own rate, resampled on the GPU and written at the model's rate.  Off by default.
@@ -25,6 +26,8 @@ from .common import build_model, latest_checkpoint, load_hparams, read_wav, resa
 def main(argv=None):
     p = argparse.ArgumentParser(add_help=False)
     p.add_argument("--chunk-hops", type=int, default=None, help="hops per call on the time pipeline (default: off - hop by hop)")
+    p.add_argument("--time-pipeline", type=int, default=None, help="with --chunk-hops: frames in flight per stream (Engine.set_time_pipeline; "
+                   "default: the model family's own; a LiSenNet model takes the pipeline only with a value of 2 or more)")
     own, rest = p.parse_known_args(argv)
     resample_on, rest = split_resample_flag(rest)
     if own.chunk_hops is None:
@@ -51,6 +54,8 @@ def main(argv=None):
         assert got is None or got == want, f"--{flag.replace('_', '-')}={got} does not match the config ({want})"
     ckpt = args.checkpoint or (latest_checkpoint(os.path.join("logs", args.name)) if args.name else None)
     model = build_model(hps, args.device, offline=False, checkpoint=ckpt)
+    if own.time_pipeline is not None:
+        model.engine.set_time_pipeline(own.time_pipeline)
     wav = torch.from_numpy(np.clip(read_wav(args.audio_path, sr, resample_on is not None, resample_on).reshape(1, -1), -1, 1)).to(args.device)
     print("Inferencing...")
     torch.cuda.synchronize()

@@ -103,8 +103,8 @@ class StreamPool:
 
     def catch_up(self, slot: int, wav_in: Tensor, T: Optional[int] = None) -> Tensor:
         """A live stream that comes back with a backlog: wav_in [T*H] or [1, T*H] (T defaults to its length // H) -> the T*H output samples
-        [1, T*H], the slot's state advanced by T hops - on the time pipeline (Engine.step_chunk; BSRNN and FSPEN: Engine.step_backlog) instead
-        of hop after hop.  The slot's state record is a capacity-1 state: it is exported, stepped as a batch of one, and imported back; no other slot is read or written.
+        [1, T*H], the slot's state advanced by T hops - on the time pipeline (Engine.step_chunk; BSRNN and FSPEN: Engine.step_backlog; LiSenNet: after
+        Engine.set_time_pipeline(P >= 2), else the walk) instead of hop after hop.  The slot's state record is a capacity-1 state: it is exported, stepped as a batch of one, and imported back; no other slot is read or written.
         The result agrees with step() over the same hops to fp32 rounding."""
         if slot not in self._open:
             raise ValueError(f"slot {slot} is not open")

@@ -108,7 +108,7 @@ def enhance_stream(model, wav: Tensor, frames_per_call: int = 1, chunk_hops: tp.
     """Driver loop of scripts/test_onnx.py:11-60 for wav [B, L] on the model's device:
     clip to [-1,1], right-pad n_fft zeros, run hop by hop (or ``frames_per_call`` hops per
     launch), drop the n_fft-hop samples of latency, clip.
-    ``chunk_hops`` (None = the loops above, exactly; with a number, audio in host memory is copied to the device first and the result is a device tensor, not the pinned host tensor of the loop above): the recording goes through Engine.step_chunk (BSRNN and FSPEN: Engine.step_backlog) in chunks of that
+    ``chunk_hops`` (None = the loops above, exactly; with a number, audio in host memory is copied to the device first and the result is a device tensor, not the pinned host tensor of the loop above): the recording goes through Engine.step_chunk (BSRNN and FSPEN: Engine.step_backlog; LiSenNet: the walk, or step_backlog on the pipeline after Engine.set_time_pipeline(P >= 2)) in chunks of that
     many hops, each on the time pipeline - the same result to fp32 rounding, many times faster for one or a few recordings."""
     cfg: FEConfig = model.cfg
     eng: Engine = model.engine
@@ -141,7 +141,7 @@ def enhance_stream(model, wav: Tensor, frames_per_call: int = 1, chunk_hops: tp.
     if chunk_hops is not None:
         if int(chunk_hops) < 1:
             raise ValueError("chunk_hops must be at least 1")
-        step = chunk_step(eng)          # (Engine.step_chunk; step_backlog for BSRNN and FSPEN)
+        step = chunk_step(eng)          # (Engine.step_chunk; step_backlog for BSRNN and FSPEN, and for LiSenNet under an explicit width)
         while t < n_hops:
             T = min(int(chunk_hops), n_hops - t)
             step(padded[:, t * H:(t + T) * H], state, out[:, t * H:(t + T) * H], T=T)

@@ -477,12 +477,22 @@ int fe_step_chunk(fe_handle* h, const float* wav_in_dev, size_t in_stride, float
  *       allocates nothing and can be captured into a graph.  wav_in and wav_out MUST NOT overlap, as for fe_step_chunk.
  *     fe_last_step_kernel: "bsrnn_frame_kernel<time-pipelined, streaming> + stream_ola_kernel [shape xxt]",
  *       "fspen_frame_kernel<time-pipelined, streaming> + stream_ola_kernel [shape fspen]" (the counters' zeroing is not named).
- *   LiSenNet: the call is fe_step's launch and the work size is 0.  Its time-pipelined kernel hands nine caches from frame to frame
- *     through ring slots and starts from zero caches at frame 0; carrying a streaming state through it needs kernels that move the state
- *     into and out of the rings, like those of the time_kernel variant.  Deliberately not built here. */
+ *   LiSenNet: at the default setting, and under fe_set_time_pipeline(0 or 1), the call is fe_step's launch, and
+ *     fe_step_backlog_work_floats is 0 at every setting.  The pipeline is OPT-IN by an explicit width: under fe_set_time_pipeline(P) with
+ *     P >= 2, with T >= 4, T * H >= N - H and a work_dev of fe_lisennet_backlog_work_floats(h, B, T) floats, the T frames of each stream
+ *     run on the family's time-pipelined frame kernel in its streaming instantiation.  That kernel hands NINE caches from frame to frame
+ *     (the phase, three encoder frames, per block the GRU state and the ConvGLU's two frames, the decoder frame) through ring slots in
+ *     work_dev; frame 0 takes each from the caller's state, the last frame (the ConvGLU: the last two) leaves its own there, in place.
+ *     Results, the chain of three kernels, graph capture and the no-overlap rule are as for BSRNN and FSPEN above.
+ *     fe_last_step_kernel: "lisennet_frame_kernel<time-pipelined, streaming> + stream_ola_kernel [shape lisennet]".
+ *     work_dev == NULL, T < 4 and a cooperative launch the runtime refuses: fe_step's launch, bit for bit (NULL is not an error here).
+ *     fe_lisennet_backlog_work_floats(h, B, T): the frame counters [B][9] rounded up to 4 floats, the windowed frames [B][T][N] and the
+ *       rings [B][66][cache floats of a stream] (sized for the widest pipeline, as fe_offline_work_floats sizes them) - whatever
+ *       fe_set_time_pipeline says; 0 for every other family, for B <= 0, for T < 4 and for a null handle. */
 size_t fe_step_backlog_work_floats(const fe_handle* h, int B, int T);
 int fe_step_backlog(fe_handle* h, const float* wav_in_dev, size_t in_stride, float* state_dev, float* wav_out_dev, size_t out_stride,
                     int B, int T, float* work_dev, void* stream);
+size_t fe_lisennet_backlog_work_floats(const fe_handle* h, int B, int T);
 
 /* The packet step's time-pipelined form - a stream of a packet batch that comes back with a backlog: fe_step_streams_banked[_pinned] with the
  * hops of EACH stream spread over co-resident workgroups instead of walked by one.  Same descriptors, slots, formats, limit, meters and banks,
