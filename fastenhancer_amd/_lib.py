@@ -105,6 +105,7 @@ SYMBOLS = {
     "fe_step_streams_chunk_pinned": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p,
                                              c_void_p, c_void_p, c_void_p, c_void_p]),
     "fe_step_pool_streams_chunk_work_floats": (c_size_t, [c_void_p, c_int, c_int]),
+    "fe_lisennet_pool_streams_chunk_work_floats": (c_size_t, [c_void_p, c_int, c_int]),
     "fe_step_pool_streams_chunk": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p,
                                            c_void_p, c_void_p, c_void_p]),
     "fe_step_pool_streams_chunk_pinned": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p,

@@ -1523,7 +1523,7 @@ int fe_step_streams(fe_handle* h, const void* wav_in_dev, size_t in_count, float
 // chunk (fe_step_pool_streams_chunk[_pinned]): the same call with each stream's hops on the family's time pipeline where
 // pool_streams_chunk_pipe_width says so and the runtime accepts the cooperative launch (launch_pool_streams_chunk, below fe_step_backlog);
 // otherwise - and always after the same checks - the launch of the packet step itself.  FastEnhancer: fe_step_streams_chunk without a bank table.
-static int pool_streams_chunk_pipe_width(const fe_handle* h, int n, int T_max);
+static int pool_streams_chunk_pipe_width(const fe_handle* h, int n, int T_max, const float* work_dev);
 static int launch_pool_streams_chunk(fe_handle* h, const BaselineStepOwn& own, const float* wav_in, float* state, float* wav_out, int n, int T_max, int P,
                                      float* work_dev, void* stream, bool* refused);
 static int step_pool_streams(fe_handle* h, const char* fn, bool pinned, const void* wav_in, size_t in_count, float* state_dev, int capacity,
@@ -1535,7 +1535,8 @@ static int step_pool_streams(fe_handle* h, const char* fn, bool pinned, const vo
                             nullptr, chunk, work_dev);
     int rc = check_streams_args(fn, wav_in, in_count, state_dev, capacity, desc_dev, wav_out, out_count, n, T_max, format, levels);
     if (rc != FE_OK) return rc;
-    const int P = chunk ? pool_streams_chunk_pipe_width(h, n, T_max) : 0;
+    const int P = chunk ? pool_streams_chunk_pipe_width(h, n, T_max, work_dev) : 0;
+    // (a family that pipelines on request has P = 0 without a buffer: the packet step itself, no error)
     if (P && !work_dev) return fail(FE_ERR_INVALID_ARG, "%s: null work buffer (fe_step_pool_streams_chunk_work_floats(h, %d, %d) floats)", fn, n, T_max);
     rc = check_ready(h);
     if (rc != FE_OK) return rc;
@@ -2208,7 +2209,8 @@ size_t fe_lisennet_backlog_work_floats(const fe_handle* h, int B, int T) {
 // fe_step_pool_streams_chunk: fe_step_pool_streams_ctl with each stream's hops on the time pipeline, for every family with a streaming state.
 // FastEnhancer: fe_step_streams_chunk (step_pool_streams hands the call over).  The baseline families whose PIPE kernel hands the streaming
 // state on in place (Fam::kPipeCarriesState: BSRNN, FSPEN), written once over the family traits like baseline_step_backlog: work_dev is that
-// call's layout, pipe_layout(h, n, T_max, Fam::counters(h), 0) - the size depends on the model, n and T_max only.  LiSenNet: no work, no pipeline.
+// call's layout, pipe_layout(h, n, T_max, Fam::counters(h), 0) - the size depends on the model, n and T_max only.  LiSenNet: 0 here - it
+// pipelines on request (Fam::kPipeCarriesStateOnRequest), with the buffer of fe_lisennet_pool_streams_chunk_work_floats (below).
 size_t fe_step_pool_streams_chunk_work_floats(const fe_handle* h, int n, int T_max) {
     if (!h || n <= 0 || T_max < 4) return 0;
     size_t floats = 0;
@@ -2220,12 +2222,30 @@ size_t fe_step_pool_streams_chunk_work_floats(const fe_handle* h, int n, int T_m
 // (0: the packet step's own launch - T_max < 4, fe_set_time_pipeline(0 | 1), or too many streams to give each two co-resident workgroups).
 // Any hop count 0 .. T_max is served on the pipeline - the host cannot see the descriptors - so there is no T H >= N - H condition here:
 // stream_ola_streams_kernel orders its cache reads before its cache writes instead.
-static int pool_streams_chunk_pipe_width(const fe_handle* h, int n, int T_max) {
+// A family whose pipeline carries the state on request only (Fam::kPipeCarriesStateOnRequest: LiSenNet) is pipelined on fe_step_backlog's
+// terms: an explicit fe_set_time_pipeline(P >= 2) and a work buffer (fe_lisennet_pool_streams_chunk_work_floats) - without either the width
+// is 0, and a null work buffer is no error.
+static int pool_streams_chunk_pipe_width(const fe_handle* h, int n, int T_max, const float* work_dev) {
     int P = 0;
     if (n > 0) visit_baseline(h->cfg.arch, [&](auto F) {
-        if constexpr (decltype(F)::kPipeCarriesState) P = baseline_pipe_width(F, h, n, T_max);
+        using Fam = decltype(F);
+        if constexpr (Fam::kPipeCarriesState) P = baseline_pipe_width(F, h, n, T_max);
+        else if constexpr (Fam::kPipeCarriesStateOnRequest) P = (h->pipe_frames >= 2 && work_dev) ? baseline_pipe_width(F, h, n, T_max) : 0;
     });
     return P;
+}
+
+// that launch's work buffer: fe_step_backlog's layout of the family - with the rings of the frames in flight where the family pipelines on request
+extern "C++" template <class Fam>
+static PipeLayout pool_streams_chunk_layout(Fam, const fe_handle* h, int n, int T_max) {
+    return Fam::kPipeCarriesStateOnRequest ? baseline_request_layout(Fam{}, h, n, T_max) : baseline_backlog_layout(Fam{}, h, n, T_max);
+}
+
+size_t fe_lisennet_pool_streams_chunk_work_floats(const fe_handle* h, int n, int T_max) {
+    if (!h || n <= 0 || T_max < 4) return 0;
+    size_t floats = 0;
+    visit_baseline(h->cfg.arch, [&](auto F) { floats = baseline_request_layout(F, h, n, T_max).total; });
+    return floats;
 }
 
 // own: the packet step's fields as step_pool_streams has set them; wav_in / wav_out: device views.  A linear chain on the caller's stream - the
@@ -2240,12 +2260,14 @@ static int launch_pool_streams_chunk(fe_handle* h, const BaselineStepOwn& own, c
     hipStream_t st = (hipStream_t)stream;
     visit_baseline(h->cfg.arch, [&](auto F) {
         using Fam = decltype(F);
-        if constexpr (Fam::kPipeCarriesState) {
+        if constexpr (Fam::kPipeCarriesState || Fam::kPipeCarriesStateOnRequest) {
             typename Fam::StreamArgs a = Fam::args(h, n, T_max);
             a.capacity = own.capacity;
             static_cast<fe::StreamIoArgs&>(a) = own.io;
             Fam::state(a) = stream_io(a, wav_in, 0, wav_out, 0, state, state_layout(h, own.capacity));
-            const typename Fam::StreamArgs p = pipe_args(a, work_dev, baseline_backlog_layout(F, h, n, T_max), P);
+            const PipeLayout L = pool_streams_chunk_layout(F, h, n, T_max);
+            typename Fam::StreamArgs p = pipe_args(a, work_dev, L, P);
+            Fam::set_ring(p, work_dev + L.ring);        // (a family without rings: nothing)
             const int nflags = (int)((size_t)n * Fam::counters(h));
             hipLaunchKernelGGL(fe::zero_counters_kernel, dim3((nflags + fe::kThreads - 1) / fe::kThreads), dim3(fe::kThreads), 0, st, p.pipe_flags, nflags);
             hipError_t e = hipGetLastError();

@@ -26,6 +26,7 @@ struct LisennetFamily {
     // frame 0 (cprev / ccur in lisennet_kernels.hip.h).  Its CARRY instantiation takes frame 0's caches from the caller's state and leaves the
     // last frames' there, in place - under an explicit fe_set_time_pipeline(P >= 2) and with a work buffer of
     // fe_lisennet_backlog_work_floats (which has the ring; fe_step_backlog_work_floats stays 0), fe_step_backlog launches that one.
+    // fe_step_pool_streams_chunk, on the same terms and with fe_lisennet_pool_streams_chunk_work_floats: its packet form (LImpl::launch_streams_pipe).
     static constexpr bool kPipeCarriesState = false;
     static constexpr bool kPipeCarriesStateOnRequest = true;
     static void launch_pipe_stream(const fe_handle* h, const Args& a, hipStream_t st, hipError_t* e) { h->limpl->launch_pipe_stream(a, st, e); }

@@ -213,6 +213,37 @@ namespace fe {
 // puts every writer behind every reader of what it replaces; the host side asks for T >= 4.  Frame 0's loads of the state need no wait (the
 // previous launch wrote it; its counter test is `t > 0` as ever); the last frames' stores need no reader in this launch but frame T - 1's of
 // the ConvGLU's older half, which is an ordinary hand-over.
+// CARRY + PIPE + SLOT + STRM (fe_step_pool_streams_chunk[_pinned] under an explicit fe_set_time_pipeline(P >= 2)): the packet step's
+// time-pipelined form, after fspen_frame_kernel's.  Workgroup blockIdx.x serves call stream b = blockIdx.x / pipe_p and the frames p, p + P,
+// ... < hops of that stream's own stream_view - all P workgroups of a stream read the same descriptor and make the same check - at its slot
+// of the capacity-sized state (sb, nst = capacity): the nine caches and cache_stft go through (sb, nst), the ring, the counters and the
+// frames stay indexed by b.  The stream's frame count is nT = sv.hops at every site (loop bound, waits, sprev / scur, gloc); a.T = T_max is
+// the row stride of a.frames only.  Frame t's samples are positions t H + n of [the slot's old cache_stft | the stream's samples through
+// stream_sample]; the limit is applied per frame as in the serial packet step.  A stream without a hop, one the bounds check skips, one
+// without state and a workgroup whose first frame is beyond the stream's hops leave before they touch a counter, the ring or the state:
+// every frame t < nT has its workgroup (t mod P, co-resident: the launch is cooperative) and every wait of frame t >= 1 its producer,
+// frame t - 1 of the same stream - no wait is on a workgroup that left.  Zero rows, output rows, both STFT caches and the level row are
+// stream_ola_streams_kernel's (stft_kernels.hip.h).
+// The ordering argument again, per stream, for the hop counts the host cannot rule out here (it does not see the descriptors): nT = 1, 2, 3.
+//   nT = 1.  Frame 0 is the reader of the old state AND the last frame: sprev and scur of a site are the same memory, no other workgroup
+//     touches the slot, and the site is the serial kernel's in-place update with HO::ld / HO::st for the plain accesses.  Phase, conv_1's
+//     frame, the two DSConv frames and the decoder frame: element i is loaded and then stored by the SAME thread, the load first in program
+//     order (two accesses of one thread to one address are not reordered).  GRU state: every thread loads its three elements through
+//     sprev INTO hp (LDS) and meets the barrier behind that loop - an LDS store needs its datum, so every load of the old state has
+//     returned before any thread passes - and the new state is stored only after it, by other threads ((f, c) of the walk): barrier in
+//     between.  ConvGLU: the threads with dt_ = 0 load the older half, those with dt_ = 1 the newer, into cpre and from there into xx
+//     (LDS) before the barrier that ends that block; a second barrier follows fc1; only then does thread (chn, f) store the frame's own
+//     fc1 rows to the newer half - and, because gloc's rule (frame nT - 2 leaves the older half) names no frame when nT = 1, the OLD newer
+//     half (xx[1]) to the older half, as the serial kernel's two stores do.  Every read of either half is two barriers before every write.
+//   nT = 2.  Frame 0 reads the old state at every site and is the ConvGLU's frame nT - 2; frame 1 is the last frame.  Every cache but the
+//     ConvGLU's: frame 0 reads the state and writes its ring slot, frame 1 waits for frame 0's publish() - which follows frame 0's reads of
+//     the state at that site - reads slot 0 and writes the state.  ConvGLU: frame 0 reads both halves, then (two barriers later, same
+//     workgroup) stores its frame to the OLDER half; frame 1, behind frame 0's publish(), reads the older half (frame 0's frame, an
+//     ordinary hand-over) and the newer half (still the old one: frame -1), then stores its own to the newer half, two barriers after its
+//     own reads and behind frame 0's.
+//   nT = 3.  As T >= 3 above: frame 1 (= nT - 2) writes the older half behind frame 0's publish(), frame 0 being the half's only reader;
+//     frame 2 writes everything else behind frame 1's publish(), which is behind frame 0's: every reader of the old state (frames 0, 1).
+//   The ring has pipe_p + 2 >= 4 slots: frames t - 2, t - 1 and t never share one, whatever nT.
 // (CARRY is a mark on the shape type, LCarried<S>, not a template parameter of the kernel: the other instantiations keep their names)
 template <class S_> struct LCarried : S_ {};
 template <class S> struct LCarries : std::false_type {};
@@ -223,7 +254,8 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((
     static_assert(!PIPE || (!PROF && !DBG), "the time-pipelined instantiation is the plain offline kernel");
     constexpr bool CARRY = LCarries<S>::value;
     static_assert(!CARRY || PIPE, "the state is carried through the time-pipelined launch");
-    static_assert(!SLOT || (!PROF && !DBG && !PIPE && PART == 0), "the slotted instantiation is the plain per-stream kernel");
+    static_assert(!SLOT || (!PROF && !DBG && (!PIPE || (STRM && CARRY)) && PART == 0),
+                  "the slotted instantiations are the plain per-stream kernel and the time-pipelined packet form, which carries the state");
     static_assert(PART == 0 || !PIPE, "the split step is a streaming step");
     __shared__ __attribute__((aligned(16))) float smem[LLdsT<PART>::TOTAL];
     using L = LLdsT<PART>;
@@ -258,6 +290,12 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((
         sv = stream_view_of<H>(a, b);
         sb = sv.slot;
         nT = sv.hops;
+        if constexpr (PIPE) {
+            // the time-pipelined form: a stream without a hop (none asked for, or skipped by the bounds check) or without state computes
+            // nothing here - its zero rows are stream_ola_streams_kernel's - and a workgroup whose first frame lies beyond the stream's hops
+            // leaves: neither has touched a counter, the ring or the state (wave-uniform: the whole workgroup returns)
+            if (t_first >= nT || (unsigned int)sb >= (unsigned int)nst) return;
+        } else
         if (nT == 0 || (unsigned int)sb >= (unsigned int)nst) {      // (wave-uniform) no hop: nothing; no state: its hops output rows are zero
             if (nT) stream_zero_row(a.wav_out, a.format, sv.out_off, nT * H, tid0, kThreads);
             b += gridDim.x;
@@ -369,6 +407,16 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((
             const float* win = wp + P::WINDOW;
             float* cst = a.cache_stft + (size_t)sb * OVL;
             if (mode == FE_MODE_STREAM) {
+                if constexpr (STRM && PIPE) {
+                    // (position t H + n of [the slot's old cache_stft | the stream's samples]: inside the cache while t H + n < OVL)
+                    const long long x0 = sv.in_off + (long long)t * H - OVL;
+                    const float* cs0 = cst + t * H;
+                    const int ovl0 = OVL - t * H;
+                    for (int n = tid; n < N; n += kThreads) {
+                        const float v = (n < ovl0) ? cs0[n] : stream_sample(a.wav_in, a.format, x0 + n);
+                        fa[n] = make_float2(v * win[n], 0.0f);
+                    }
+                } else
                 if constexpr (STRM) {
                     const long long x0 = sv.in_off + (long long)t * H - OVL;
                     for (int n = tid; n < N; n += kThreads) {
@@ -859,6 +907,10 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((
                     const bool in_state = t >= nT - 2;
                     float* gdst = in_state ? cg + (t - (nT - 2)) * 32 : ccur(OFF_BLK + blk * (S::K_H + S::K_GLU) + S::K_H);
                     HO::st(gdst + chn * (in_state ? 64 : 32) + f, xx[(64 + chn) * 32 + f]);
+                    // (STRM) a one-hop stream: frame 0 is the only frame, its own goes to the newer half above - and what the call found in
+                    // the newer half is now the older frame, as the serial step leaves it.  xx[1] holds it: fetched above by other threads,
+                    // two barriers ago - every read of the old older half is behind us.  (Wave-uniform; no hop count below 4 without STRM.)
+                    if constexpr (STRM) { if (nT == 1) HO::st(cg + chn * 64 + f, xx[(32 + chn) * 32 + f]); }
                 } else
                 if constexpr (PIPE) HO::st(ccur(OFF_BLK + blk * (S::K_H + S::K_GLU) + S::K_H) + chn * 32 + f, xx[(64 + chn) * 32 + f]); else {
                 cg[(chn * 2 + 0) * 32 + f] = xx[(32 + chn) * 32 + f];
@@ -1088,7 +1140,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu((
         }   // PART != 1
         LS_CLK(5);
     }
-    if constexpr (STRM) {
+    if constexpr (STRM && !PIPE) {      // (the time-pipelined form: the level row is stream_ola_streams_kernel's)
         // the stream's level row, one 16-byte store: the waves' partials through the (idle) transform buffer, wave 0 first
         if (a.levels != nullptr) {
             float* lred = reinterpret_cast<float*>(fa);
@@ -1119,6 +1171,9 @@ struct LImpl {
     int nsite;                // caches handed from frame to frame (counters per stream)
     void (*launch_sb)(const LArgs&, int max_wgs, hipStream_t, hipError_t*);      // r6: the per-hop step of a large batch in three launches, the middle batched over the streams
     void (*launch_pipe_stream)(const LArgs&, hipStream_t, hipError_t*);          // time-pipelined launch of a streaming chunk on the caller's state (CARRY; cooperative, as launch_pipe)
+    // the packet step's time-pipelined launch (fe_step_pool_streams_chunk on request: a.pipe_p workgroups per call stream, CARRY + SLOT + STRM;
+    // cooperative, a refusal leaves no error behind and names no kernel)
+    hipError_t (*launch_streams_pipe)(const LStreamArgs&, hipStream_t);
 };
 
 // workgroups per CU: LDS-limited, and two by the registers (256 VGPRs per wave); the parts of the three-launch step run eight (16.5 / 14.4 KB
@@ -1138,6 +1193,17 @@ template <class S>
 void llaunch_pipe_stream_impl(const LArgs& a, hipStream_t st, hipError_t* err) {
     *err = launch_coop<&lisennet_frame_kernel<LCarried<S>, false, false, true>>("lisennet_frame_kernel<time-pipelined, streaming>", dim3(a.B * a.pipe_p),
                                                                                           dim3(kThreads), 0, st, a);
+}
+
+// fe_step_pool_streams_chunk: the CARRY + PIPE + SLOT + STRM instantiation, n * pipe_p cooperative workgroups
+constexpr KernelNames lpipe_streams_names() { return kernel_names("lisennet_frame_kernel", 0, "time-pipelined", "streams"); }
+static_assert(same_text(lpipe_streams_names().s[0], "lisennet_frame_kernel<time-pipelined, streams>") &&
+              same_text(lpipe_streams_names().s[3], "lisennet_frame_kernel<time-pipelined, streams, pinned, s16>"), "what fe_last_step_kernel reports for it");
+template <class S>
+hipError_t llaunch_streams_pipe_impl(const LStreamArgs& a, hipStream_t st) {
+    static constexpr KernelNames names = lpipe_streams_names();
+    return launch_coop<&lisennet_frame_kernel<LCarried<S>, false, false, true, 0, true, true>, true>(baseline_name<true>(names, a), dim3(a.B * a.pipe_p), dim3(kThreads),
+                                                                                                  0, st, a);
 }
 
 constexpr KernelNames lframe_names(bool slot, bool strm) { return kernel_names("lisennet_frame_kernel", 0, "", baseline_flavour(slot, strm)); }
@@ -1196,10 +1262,11 @@ LImpl make_limpl() {
     // PC-relative: its instructions carry the size of the code that follows it.  Naming the plain, the time-pipelined and the three-launch
     // launcher ahead of llaunch_step_impl (whose slotted and packet instantiations then come last, as they always have) keeps that kernel's
     // code what the recorded comparisons with earlier builds have (profiles/baseline_launch_device_code.txt).  No run-time purpose.
-    // (llaunch_pipe_stream_impl is named last, after llaunch_step_impl: its kernel lands behind all the others.)
+    // (llaunch_pipe_stream_impl and llaunch_streams_pipe_impl are named last, after llaunch_step_impl: their kernels land behind all the others.)
     (void)&llaunch_impl<S>, (void)&llaunch_pipe_impl<S>, (void)&llaunch_sb_impl<S>;
     return LImpl{S::HOP, (size_t)LLds::TOTAL * 4, LDebugLayout::total(), LDebugLayout::n_stages, (size_t)LPk::TOTAL + LSbPk::TOTAL, (size_t)S::CACHE_FLOATS,
-                 &llaunch_step_impl<S>, &ldbg_stage_impl, &llaunch_pipe_impl<S>, kLOcc, 5 + 2 * S::NB, &llaunch_sb_impl<S>, &llaunch_pipe_stream_impl<S>};
+                 &llaunch_step_impl<S>, &ldbg_stage_impl, &llaunch_pipe_impl<S>, kLOcc, 5 + 2 * S::NB, &llaunch_sb_impl<S>, &llaunch_pipe_stream_impl<S>,
+                 &llaunch_streams_pipe_impl<S>};
 }
 
 }  // namespace fe

@@ -212,7 +212,7 @@ __global__ void __launch_bounds__(kThreads) stream_ola_kernel(const float* __res
 
 // stream_view (fe_kernels.hip.h) with the hop a run-time value: this file's kernels are not compiled per shape.  The same clamp and the same
 // bounds check, word for word - the frame kernel's workgroups and the audio kernel below must make the same stream of a descriptor.
-// (A: the packet argument block of any family - StreamFrameArgs, BStreamArgs, FStreamArgs: a.B, a.T, a.desc and the two counts.)
+// (A: the packet argument block of any family - StreamFrameArgs, BStreamArgs, FStreamArgs, LStreamArgs: a.B, a.T, a.desc and the two counts.)
 template <class A>
 __device__ __forceinline__ StreamView stream_view_rt(const A& a, int b, int H) {
     StreamView v{-1, 0, 0, 0};
@@ -255,8 +255,8 @@ __global__ void __launch_bounds__(kThreads) zero_counters_kernel(unsigned int* _
 // waves' words through LDS, wave 0 first, one 16-byte store (levels_put / levels_store) - no atomics, the same bits on every run.
 // a: the frame kernel's argument block (a.frames [B][a.T][N], a.T = T_max).  wav_in and wav_out do not overlap.
 // A template over that block: FastEnhancer's StreamFrameArgs (fe_step_streams_chunk - the only one with a bank table), and the packet blocks of
-// the families whose time pipeline carries the streaming state (fe_step_pool_streams_chunk: BStreamArgs, FStreamArgs), which name the same
-// fields - audio, the two STFT caches, descriptors, counts, format, capacity, levels, frames.
+// the families whose time pipeline carries the streaming state (fe_step_pool_streams_chunk: BStreamArgs, FStreamArgs, and LStreamArgs for
+// LiSenNet's launch on request), which name the same fields - audio, the two STFT caches, descriptors, counts, format, capacity, levels, frames.
 constexpr int kOlaTile = 4 * kThreads;
 template <class A>
 __device__ __forceinline__ int stream_ola_bank(const A& a, const StreamView& sv) {

@@ -14,7 +14,7 @@ from torch import Tensor
 
 from . import _lib
 from .config import FEConfig
-from .family import family_of, views
+from .family import family_of, packet_chunk_on_request, views
 
 
 def _ptr(t: Optional[Tensor]) -> c_void_p:
@@ -499,6 +499,10 @@ class Engine:
         if pool_chunk:
             name = "fe_step_pool_streams_chunk" + ("_pinned" if pinned else "")
         work_query = self.pool_streams_chunk_work_floats if pool_chunk else self.streams_chunk_work_floats
+        # (LiSenNet pipelines this call on request: after set_time_pipeline(P >= 2) the scratch is that launch's - the rule of lisennet_backlog_work)
+        on_request = pool_chunk and packet_chunk_on_request(self)
+        if on_request:
+            work_query = self.lisennet_pool_streams_chunk_work_floats
         for what, x in (("wav_in", wav_in), ("wav_out", wav_out)):
             if not isinstance(x, Tensor) or x.dtype not in (torch.float32, torch.int16) or not x.is_contiguous() or x.numel() == 0:
                 raise ValueError(f"{what} must be a contiguous, non-empty float32 or int16 tensor")
@@ -522,7 +526,7 @@ class Engine:
             c = self.cfg      # (the default, ln and dprnn models: the ring variants, the noncausal model and the baselines never pipeline this call)
             pipelines = hasattr(c, "rf_blocks") and not getattr(c, "dpt", False) and getattr(c, "kernel_size_time", 1) == 1 and not getattr(c, "noncausal", False)
             if pool_chunk and self.family.pool:       # (the pool call: the families whose time pipeline carries the streaming state - BSRNN, FSPEN)
-                pipelines = self.family.backlog
+                pipelines = self.family.backlog or on_request
             if T_max >= 4 and pipelines and work.numel() < n_desc * T_max * c.n_fft:
                 raise ValueError(f"work has {work.numel()} floats, {n_desc} streams of up to {T_max} hops need at least {n_desc * T_max * self.cfg.n_fft} "
                                  f"({work_query.__name__})")
@@ -633,16 +637,25 @@ class Engine:
         hops (0: none - T_max < 4, LiSenNet, the FastEnhancer models whose streams_chunk_work_floats is 0)."""
         return int(self.lib.fe_step_pool_streams_chunk_work_floats(self._h, int(n), int(T_max)))
 
+    def lisennet_pool_streams_chunk_work_floats(self, n: int, T_max: int) -> int:
+        """fe_lisennet_pool_streams_chunk_work_floats: floats of the work buffer with which step_pool_streams_chunk runs a LiSenNet packet
+        call on the time pipeline (counters, windowed frames, the rings of the nine caches), whatever set_time_pipeline says at the time of
+        the query; 0 for every other family, for n <= 0 and for T_max < 4."""
+        return int(self.lib.fe_lisennet_pool_streams_chunk_work_floats(self._h, int(n), int(T_max)))
+
     def step_pool_streams_chunk(self, wav_in: Tensor, state: Tensor, capacity: int, desc, wav_out: Tensor, T_max: int, *,
                                 min_gain: Optional[Tensor] = None, levels: Optional[Tensor] = None, work: Optional[Tensor] = None) -> Tensor:
         """fe_step_pool_streams_chunk: step_pool_streams_ctl(..., min_gain=, levels=) with the hops of EACH stream spread over the time
         pipeline - the same descriptors, slots, formats, limit and meters, in place on the capacity-sized state.  FastEnhancer's models as
         step_streams_chunk runs them; BSRNN and FSPEN on the time-pipelined packet form of their frame kernels, results agreeing with
-        step_pool_streams_ctl to fp32 rounding (cache_stft bit for bit); LiSenNet, whose pipeline carries no streaming state, and every
-        call that is not pipelined (T_max < 4, set_time_pipeline(0 | 1), too many streams) as step_pool_streams_ctl itself, bit for bit
-        (last_step_kernel() says which ran).  wav_in and wav_out must not overlap.  work: a float32 device tensor of at least
-        pool_streams_chunk_work_floats(n, T_max) floats (the form for graph capture); None: a scratch tensor kept on the engine, grown
-        when needed."""
+        step_pool_streams_ctl to fp32 rounding (cache_stft bit for bit); every call that is not pipelined (T_max < 4,
+        set_time_pipeline(0 | 1), too many streams) as step_pool_streams_ctl itself, bit for bit (last_step_kernel() says which ran).
+        wav_in and wav_out must not overlap.  work: a float32 device tensor of at least pool_streams_chunk_work_floats(n, T_max) floats
+        (the form for graph capture); None: a scratch tensor kept on the engine, grown when needed.
+        LiSenNet on the time pipeline is opt-in: after set_time_pipeline(P) with P >= 2 the call runs the time-pipelined packet form of
+        its frame kernel on the slots' nine caches in place, with a `work` of lisennet_pool_streams_chunk_work_floats(n, T_max) floats
+        (checked; None: the engine's scratch tensor at that size).  At every other setting it is step_pool_streams_ctl itself,
+        pool_streams_chunk_work_floats is 0 and a `work` is passed through unread."""
         return self._step_streams(wav_in, state, capacity, desc, wav_out, T_max, pinned=False, min_gain=min_gain, levels=levels, work=work,
                                   pool_chunk=True)
 

@@ -203,6 +203,13 @@ def packet_chunk_step(engine, pinned: bool) -> Callable:
     return engine.step_streams_chunk_pinned if pinned else engine.step_streams_chunk
 
 
+def packet_chunk_on_request(engine) -> bool:
+    """Whether that call runs pipelined only because the engine was asked to: a family whose pipeline carries the streaming state on request
+    (LiSenNet) after Engine.set_time_pipeline(P >= 2) - the scratch is then Engine.lisennet_pool_streams_chunk_work_floats(n, T_max)."""
+    fam = _FAMILIES.get(type(getattr(engine, "cfg", None)))
+    return fam is not None and fam.backlog_on_request and getattr(engine, "_time_pipeline", -1) >= 2
+
+
 def pool_family_name(engine) -> Optional[str]:
     """"BSRNN", "FSPEN" or "LiSenNet" for an engine of a family that steps through fe_step_pool / fe_step_pool_streams, else None: what a
     pool names when it refuses a control that is FastEnhancer's (suppression limit, level meters, weight banks, the pipelined packet step)."""

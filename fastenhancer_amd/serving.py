@@ -37,7 +37,7 @@ from torch import Tensor
 
 from . import _lib
 from .engine import Engine
-from .family import chunk_step, packet_chunk_step, packet_ctl_step, packet_step, pool_family_name, slot_step
+from .family import chunk_step, packet_chunk_on_request, packet_chunk_step, packet_ctl_step, packet_step, pool_family_name, slot_step
 from .resample import Resampler
 
 
@@ -596,8 +596,9 @@ class BacklogPacketPool(FamilyPacketPool):
     """A FamilyPacketPool with backlog_hops = K for every family.  On a FastEnhancer engine it is PacketPool, call for call.  On a BSRNN, FSPEN
     or LiSenNet engine a stream with more than T_max complete hops up to the ring end leaves the tick's ordinary launch and advances up to K
     hops in a second launch on the same stream, Engine.step_pool_streams_chunk_pinned (fe_step_pool_streams_chunk_pinned: each stream's hops
-    on the time pipeline for BSRNN and FSPEN, the serial packet step for LiSenNet), with its limit and its meters; tick() waits once, for
-    both.  Weight banks other than 0 stay FastEnhancer's and are refused with the family's name."""
+    on the time pipeline for BSRNN and FSPEN; for LiSenNet too once the engine's time pipeline was set to an explicit width of two or more,
+    Engine.set_time_pipeline(P >= 2), and the packet step itself at every other setting), with its limit and its meters; tick() waits once,
+    for both.  Weight banks other than 0 stay FastEnhancer's and are refused with the family's name."""
 
     _FAMILY_CONTROLS = FamilyPacketPool._FAMILY_CONTROLS + ("the pipelined packet step",)
 
@@ -612,7 +613,14 @@ class BacklogPacketPool(FamilyPacketPool):
         return lambda *a, bank=None, **kw: call(*a, **kw)       # (no bank table in that call: such a pool has none)
 
     def _backlog_work_floats(self):
-        return super()._backlog_work_floats() if self._baseline is None else self.engine.pool_streams_chunk_work_floats
+        """The query that sizes the backlog launch's scratch.  A family that pipelines the call on request (LiSenNet) answers with its own
+        query when the engine's width is two or more - read when the scratch is first made, so a pool that ticked a backlog before
+        Engine.set_time_pipeline(P >= 2) keeps the small scratch (the engine then refuses it by size): resize() makes it again."""
+        if self._baseline is None:
+            return super()._backlog_work_floats()
+        if packet_chunk_on_request(self.engine):
+            return self.engine.lisennet_pool_streams_chunk_work_floats
+        return self.engine.pool_streams_chunk_work_floats
 
 
 class ResampledPacketPool:

@@ -567,9 +567,24 @@ int fe_step_streams_chunk_pinned(fe_handle* h, const void* wav_in_host, size_t i
  *     fe_last_step_kernel on the pipelined path: "bsrnn_frame_kernel<time-pipelined, streams[, pinned][, s16]> + stream_ola_streams_kernel
  *       [shape xxt]", "fspen_frame_kernel<time-pipelined, streams[, pinned][, s16]> + stream_ola_streams_kernel [shape fspen]" (the counters'
  *       zeroing is not named).
- *   LiSenNet: the call is fe_step_pool_streams_ctl[_pinned]'s launch and the work size is 0: its time-pipelined kernel carries no streaming
- *     state (see fe_step_backlog). */
+ *   LiSenNet: at the default setting, and under fe_set_time_pipeline(0 or 1), the call is fe_step_pool_streams_ctl[_pinned]'s launch, bit
+ *     for bit and under that name, and fe_step_pool_streams_chunk_work_floats is 0 at every setting.  The pipeline is OPT-IN, on
+ *     fe_step_backlog's terms: under an explicit fe_set_time_pipeline(P) with P >= 2, with T_max >= 4, a width of at least two workgroups
+ *     per stream for n streams and a work_dev of fe_lisennet_pool_streams_chunk_work_floats(h, n, T_max) floats, the hops of each stream
+ *     run on the time-pipelined PACKET instantiation of the family's frame kernel.  Its frames hand the NINE caches on through ring slots
+ *     in work_dev; frame 0 takes each from the stream's slot of the caller's state, the stream's last frame (the ConvGLU: its last two;
+ *     a one-hop stream: the one frame, which also moves the newer half to the older) leaves its own there, in place.  Any hop count
+ *     0 .. T_max is served there.  Meaning, results, the chain of three kernels, graph capture and the no-overlap rule are as for BSRNN and
+ *     FSPEN above.
+ *     fe_last_step_kernel: "lisennet_frame_kernel<time-pipelined, streams[, pinned][, s16]> + stream_ola_streams_kernel [shape lisennet]".
+ *     work_dev == NULL (not an error for this family), T_max < 4, too many streams to give each two co-resident workgroups and a cooperative
+ *     launch the runtime refuses (by then only the counters in work_dev have been written): the launch of fe_step_pool_streams_ctl[_pinned].
+ *     The argument checks and their order are those of every family.
+ *     fe_lisennet_pool_streams_chunk_work_floats(h, n, T_max): the frame counters [n][9] rounded up to 4 floats, the windowed frames
+ *       [n][T_max][N] and the rings [n][66][cache floats of a stream] (sized for the widest pipeline) - whatever fe_set_time_pipeline
+ *       says; monotone in n and T_max; 0 for every other family, for n <= 0, for T_max < 4 and for a null handle. */
 size_t fe_step_pool_streams_chunk_work_floats(const fe_handle* h, int n, int T_max);
+size_t fe_lisennet_pool_streams_chunk_work_floats(const fe_handle* h, int n, int T_max);
 int fe_step_pool_streams_chunk(fe_handle* h, const void* wav_in_dev, size_t in_count, float* state_dev, int capacity, const fe_stream_desc* desc_dev,
                                void* wav_out_dev, size_t out_count, int n, int T_max, int format, const float* min_gain, fe_stream_levels* levels,
                                float* work_dev, void* stream);
